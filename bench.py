@@ -69,7 +69,26 @@ def parse():
     ap.add_argument("--refbench-json", default="", help="with --refbench: also write the rows as JSON")
     ap.add_argument("--no-pmc", action="store_true",
                     help="do not run the rocprofv3 PMC passes for roofline.traffic (use when bench.py itself runs under a profiler)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32): "
+                         "c2_C (the BRGEMM's C) and, unless --no-mlp, mlp_out (the MLP's output, gathered at N > 1). Inputs are "
+                         "seeded: the same arguments give the same inputs in every run")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(d, arrays):
+    """arrays: name -> host array; written as float32 d/<name>.npy (at most DUMP_LIMIT_BYTES in all)"""
+    out = {k_: np.ascontiguousarray(v_, dtype=np.float32) for k_, v_ in arrays.items()}
+    total = sum(v_.nbytes for v_ in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k_, v_ in out.items():
+        np.save(os.path.join(d, k_ + ".npy"), v_)
+    return {k_: list(v_.shape) for k_, v_ in out.items()}
 
 
 def timed(fn, steps, sync, barrier):
@@ -604,6 +623,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: become the launcher. One rank per GPU under torch.distributed.run on a free
         # local port; the ranks' stdout / stderr pass through, so rank 0's ONE JSON line is this process' line; its exit code is ours.
@@ -676,6 +697,7 @@ def main():
     flops = 2.0 * m * n * k * br
     runs = {}
     mode = "invoke-loop"
+    outputs = {}  # --dump-outputs: name -> host copy of what the last timed step produced
     other = "uniform" if args.init == "reference" else "reference"
     for kind in (other, args.init):  # the stream `value` is quoted on runs last, right after its own warm-up
         hA, hB, hC = inputs(kind)
@@ -697,6 +719,8 @@ def main():
                 wall_g, devs_g = timed(replay, K, sync, barrier)
                 if wall_g < wall:
                     wall, devs, mode = wall_g, devs_g, "hipGraph-replay"
+        if kind == args.init and args.dump_outputs:
+            outputs["c2_C"] = dC.cpu().view(m, n)
         t = torch.tensor([wall, devs], dtype=torch.float64, device="cuda")
         if use_dist:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -824,14 +848,16 @@ def main():
             return ref, rt.kernel_name(whole.handles[0][0]), name
 
         if not use_dist:
-            spec, sh, mstep, _ = run_mlp(4096, K, W)
+            spec, sh, mstep, out_ = run_mlp(4096, K, W)
             mcompute = mstep
+            if args.dump_outputs:
+                outputs["mlp_out"] = out_.float().cpu()
             gathers = None
         else:
             # N > 1: the strong-scaled step with the all-gather INSIDE the timed region, BOTH gather paths in the same run, then the
             # check: every rank recomputes the full batch unsharded and compares the gathered output bit for bit
             spec, sh, mcompute, _ = run_mlp(4096, K, W)
-            gathers = {}
+            gathers, gathered_out = {}, {}
             ref, ref_kernel, shard_kernel = unsharded_on_the_shards_tile(4096, sh)
             for path in (["peer"] if peer_for(4096) is not None else []) + ["rccl"]:
                 t_, full_, err_ = run_gathered(4096, K, W, path)
@@ -843,6 +869,8 @@ def main():
                 dist.all_reduce(ok_, op=dist.ReduceOp.MIN)
                 gathers[path] = {"ms_per_step": round(t_ * 1e3, 5), "value": round(spec.flops() / t_ / 1e9, 1), "unit": "GFLOP/s",
                                  "gathered_bit_identical": bool(int(ok_[0]))}
+                if args.dump_outputs:
+                    gathered_out[path] = full_.view(torch.bfloat16).float().cpu().view(4096, N)  # (the peer path hands back an int16 view)
             timed_paths = [p_ for p_ in gathers if "ms_per_step" in gathers[p_]]
             if not timed_paths:
                 # every gather path failed (on some rank): no headline can be quoted. The line still goes out - value null, the
@@ -861,6 +889,8 @@ def main():
                 sys.exit(4)
             best = min(timed_paths, key=lambda p_: gathers[p_]["ms_per_step"])
             mstep = gathers[best]["ms_per_step"] * 1e-3
+            if args.dump_outputs:
+                outputs["mlp_out"] = gathered_out[best]
             if peer_for(4096) is None and "peer" not in gathers:
                 gathers["peer"] = {"unavailable": "the peer buffers could not be mapped or the self-test failed on a rank: RCCL only"}
             # the same step on ONE GPU in the same run (rank 0's device, the others wait): the denominator of the speed-up
@@ -1354,6 +1384,8 @@ def main():
                                               "per-kernel roofline of the shard kernels is in the N = 1 line (mlp.per_rank_step_us)"}})
             if one_device:
                 line["data"] = "synthetic (TEST RIG: all ranks on ONE device - the timings of this line are meaningless)"
+        if args.dump_outputs:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dump_outputs(args.dump_outputs, {k_: v_.numpy() for k_, v_ in outputs.items()})}
         emit(line)
         if mlp is not None and mlp.get("gathered_bit_identical") is False:
             sys.stderr.write("[bench] the gathered MLP output differs from the unsharded result: this run is INVALID\n")

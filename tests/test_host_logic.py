@@ -123,6 +123,32 @@ def test_bench_gpus_n_without_world_size_launches_n_ranks():
         assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    """ms_per_step is the wall time of the timed steps / --steps: zero steps is an error, before anything touches a GPU"""
+    r = _run_bench(["--gpus", "1", "--steps", "0", "--warmup", "1"], {})
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and "{" not in r.stdout
+
+
+def test_bench_dump_outputs_writes_float32_npy_within_the_limit(tmp_path):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (bf16 / f32 values exactly), 64 MB in all at most"""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    arrays = {"c2_C": rng.standard_normal((64, 32)).astype(np.float32), "mlp_out": rng.standard_normal((16, 8))}
+    shapes = bench.dump_outputs(str(tmp_path / "out"), arrays)
+    assert shapes == {"c2_C": [64, 32], "mlp_out": [16, 8]}
+    for name, a in arrays.items():
+        got = np.load(str(tmp_path / "out" / (name + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    big = {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)}
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), big)
+    assert not os.path.exists(str(tmp_path / "big"))
+
+
 def test_bench_final_line_is_compact_and_keeps_every_baseline_config():
     """the driver keeps an 8 KB tail of bench.py's stdout; round 5's ONE line had grown to 16 KB and the
     driver-written record lost the C4 step. The final line is now a pure function of the full line (bench.compact_line): under
