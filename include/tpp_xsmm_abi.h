@@ -337,6 +337,19 @@ TPP_XSMM_EXPORT void xsmm_hip_fold_transpose_stats(int64_t out[3]);
  * checked against the same factor (k a multiple of it; [m][k/v][v] is byte-identical to the flat row). */
 TPP_XSMM_EXPORT int xsmm_hip_set_vnni_factor(int factor);
 TPP_XSMM_EXPORT int xsmm_hip_get_vnni_factor(void);
+/* f32 GEMM arithmetic of descriptors dispatched from now on: 0 = exact f32 MFMA (default), 6 = bf16x6 split. Read once per
+ * dispatch and kept by the handle (part of the descriptor key). Returns the previous setting; other values are refused (-1).
+ * Also TPP_HIP_F32_PRECISION=bf16x6 (or 6). bf16x6 writes every f32 operand as hi + mid + lo, three bf16 parts rounded to nearest
+ * even one after another (about 2^-27 relative left over), and sums the six part products down to 2^-18 relative (hi.hi, hi.mid,
+ * mid.hi, hi.lo, lo.hi, mid.mid) on the bf16 MFMA in its f32 accumulator: the dropped terms are about 2^-26 relative, below the f32
+ * rounding of the sum. The first split kernel measured SLOWER than the exact one on every shape (profiles/x6_first_ab.txt), so it runs
+ * only where a split tile is also forced (xsmm_hip_force_variant 12 = 64x64, 13 = 64x32, 14 = 32x32, 15 = 128x64) and the shape fits
+ * (k a multiple of 64, m / n multiples of the tile, leading dimensions and strides multiples of 4); every other bf16x6 descriptor runs
+ * on the exact kernel it gets under 0. The kernel name (xsmm_hip_kernel_name) contains "bf16x6" only where the split kernel runs. bf16
+ * descriptors ignore the setting. A bf16x6 handle is never grouped by the tile queue or chained (xsmm_hip_fused_brgemm_chain_invoke
+ * runs a chain holding one call by call). */
+TPP_XSMM_EXPORT int xsmm_hip_set_f32_precision(int mode);
+TPP_XSMM_EXPORT int xsmm_hip_get_f32_precision(void);
 /* Library version string. */
 TPP_XSMM_EXPORT const char *xsmm_hip_version(void);
 

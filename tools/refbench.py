@@ -23,6 +23,7 @@ fp32-query-times-key.mlir, fp32-out-softmax-times-value.mlir, the pack / unpack 
 (form "script"; the pack rows' "GFLOP/s" counts bytes as their BENCH_TOTAL_FLOPS lines do, their fraction is of the HBM peak).
 
 usage: python tools/refbench.py [--quick] [--only matmul|fc|base|mlir] [-n ITER] [--json out.json] [--cpu-json cpu_rows.json]
+       [--f32-precision exact|bf16x6]
 """
 import argparse
 import json
@@ -94,7 +95,7 @@ def cases(only):
     return out
 
 
-def argv_of(c, n_iter, repeats=1):
+def argv_of(c, n_iter, repeats=1, f32_precision="exact"):
     if c.get("script"):
         return ["--script", c["script"], "--queue", "1", "-n", str(n_iter)]
     a = ["--batch", str(c["M"]), "--layers", ",".join(map(str, c["layers"])), "--kernel", c["kernel"], "-n", str(n_iter), "--queue", "1"]
@@ -108,6 +109,8 @@ def argv_of(c, n_iter, repeats=1):
         a += ["--bias", "--relu"]
     if c["dtype"].startswith("bf16"):
         a += ["--bf16", "--vnni", c["dtype"][-1]]
+    elif f32_precision != "exact":
+        a += ["--f32-precision", f32_precision]
     return a
 
 
@@ -128,6 +131,8 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("-n", type=int, default=300)
     ap.add_argument("--json", default="")
+    ap.add_argument("--f32-precision", default="exact", choices=["exact", "bf16x6"],
+                    help="arithmetic of the f32 rows' dispatches (xsmm_hip_set_f32_precision): exact f32 MFMA or the bf16x6 split")
     ap.add_argument("--repeats", type=int, default=3, help="timed loops per row (own timer each): the row gets us_min / us_median / us_max and "
                     "the tile queue's abandoned-replay count (VERDICT r5 weak 9: a row must say whether its mean is typical)")
     args = ap.parse_args()
@@ -138,7 +143,7 @@ def main():
     cs = [c for c in cs if not c.get("script")] + [c for c in cs if c.get("script")]
     with tempfile.NamedTemporaryFile("w", suffix=".cases", delete=False) as f:
         for c in cs:
-            f.write(" ".join(argv_of(c, args.n, args.repeats)) + "\n")
+            f.write(" ".join(argv_of(c, args.n, args.repeats, args.f32_precision)) + "\n")
         path = f.name
     r = subprocess.run([replay, "--cases", path], capture_output=True, text=True, timeout=3000)
     os.unlink(path)

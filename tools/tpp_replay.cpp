@@ -68,7 +68,7 @@ int main(int argc, char **argv) {
 static int run_case(int argc, char **argv) {
   int64_t batch = 256, tile = 32, tile_n = 0, tile_k = 0, n_iter = 100;
   bool kernel_args = false; // mlir-gen --kernel=args: the output is an argument, the matmul accumulates into it (no BETA_0)
-  int vnni = 2, split = -1, variant = -1, repeats = 1;
+  int vnni = 2, split = -1, variant = -1, repeats = 1, f32p = 0;
   int64_t block_pad = 0; // --block-pad P (experiments): P elements between consecutive packed blocks of A and of W (the block strides stop being powers of two)
   std::vector<int64_t> layers = {1024, 1024, 1024, 1024};
   bool bias = false, relu = false, whole = false, chain = false, print = false, c1 = false, rnd = false, bf16 = false, host_buffers = false;
@@ -101,6 +101,12 @@ static int run_case(int argc, char **argv) {
     else if (a == "--kernel") kernel_args = std::string(next()) == "args"; // const (default): zero fill folded into BETA_0; args: C += ...
     else if (a == "--split") split = atoi(next());     // xsmm_hip_force_split for this case (-1: the runtime's model)
     else if (a == "--variant") variant = atoi(next()); // xsmm_hip_force_variant at dispatch (-1: the runtime's choice)
+    else if (a == "--f32-precision") { // xsmm_hip_set_f32_precision for this case's dispatches: exact (default) or bf16x6
+      const std::string v = next();
+      if (v == "bf16x6" || v == "6") f32p = 6;
+      else if (v == "exact" || v == "0") f32p = 0;
+      else { fprintf(stderr, "tpp_replay: --f32-precision takes exact or bf16x6, got %s\n", v.c_str()); return 2; }
+    }
     else if (a == "--block-pad") block_pad = atoll(next());
     else if (a == "--repeats") repeats = atoi(next()); // the timed loop R times (own timer each): min / median / max + the queue's abandon counter per case
     else if (a == "--host-buffers") host_buffers = true; // what an UNMODIFIED tpp-run hands over: plain malloc'ed host memory, modes from the environment only
@@ -199,13 +205,14 @@ static int run_case(int argc, char **argv) {
   // --host-buffers: NO xsmm_hip_* call before or inside the timed region - the program below is the reference's 13 + 2 symbols only,
   // the runtime's modes come from the environment (TPP_HIP_ASYNC / TPP_HIP_TILE_QUEUE / TPP_HIP_HOST_CACHE), like under an unmodified tpp-run
   const int old_vf = host_buffers ? 2 : xsmm_hip_set_vnni_factor(bf16 ? vnni : 2);
+  const int old_f32p = host_buffers ? 0 : xsmm_hip_set_f32_precision(f32p);
   if (!host_buffers) {
     xsmm_hip_force_split(split);
     xsmm_hip_force_variant(variant);
     xsmm_hip_set_async(1);
     xsmm_hip_set_tile_queue(queue);
-  } else if ((bf16 && vnni != 2) || split != -1 || variant != -1 || chain) {
-    fprintf(stderr, "tpp_replay: --host-buffers takes its settings from the environment only (no --vnni 4 / --split / --variant / --chain)\n");
+  } else if ((bf16 && vnni != 2) || split != -1 || variant != -1 || chain || f32p) {
+    fprintf(stderr, "tpp_replay: --host-buffers takes its settings from the environment only (no --vnni 4 / --split / --variant / --chain / --f32-precision)\n");
     return 2;
   }
   std::vector<int64_t> handle(L);
@@ -336,6 +343,7 @@ static int run_case(int argc, char **argv) {
     printf("( %g, %g, %g, %g, %g, %g, %g, %g )\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
   }
   xsmm_hip_set_vnni_factor(old_vf);
+  if (!host_buffers) xsmm_hip_set_f32_precision(old_f32p);
   xsmm_hip_force_split(-1);
   for (void *p : act) CHECK(hipFree(p));
   for (void *p : W) CHECK(hipFree(p));

@@ -658,6 +658,10 @@ enum GemmVariant : int {
   V_F32_LW_32x32K4 = 9,   // 4 MFMA waves 1x1x4 + 2 loader waves
   V_F32_LW_128x64 = 10,   // 8 MFMA waves 4x2x1 + 2 x 2 loader waves, 3-slot ring (large outputs)
   V_F32_LW16_32x16 = 11,  // brgemm_f32_lw16.hip: 32x16 tiles on v_mfma_f32_16x16x4_f32, 4 MFMA waves (K split) + 3 loader waves: outputs of at most one 32x16 tile per CU
+  V_F32_X6_64x64 = 12,    // brgemm_f32_x6.hip: the bf16x6 split on v_mfma_f32_32x32x16_bf16 (f32 descriptors dispatched under xsmm_hip_set_f32_precision(6)
+  V_F32_X6_64x32K2 = 13,  //   with this variant forced: plan_gemm); 4 waves, K split over the rest of them; 128x64 with 8 waves
+  V_F32_X6_32x32K4 = 14,
+  V_F32_X6_128x64 = 15,
   V_BF16_FAST = 16,  // brgemm_bf16.hip: 64x64 register-staged
   V_BF16_DMA128 = 17, // brgemm_bf16.hip: 128x128, LDS-DMA + loader waves
   V_BF16_DMA256 = 18, // brgemm_bf16_dma256.hip: 256x256, LDS-DMA
@@ -722,6 +726,7 @@ hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         //
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
 hipError_t launch_f32_lw16(int tile, const GemmArgs &a, const WorkItem *items, int n_items, bool grouped, hipStream_t s); // brgemm_f32_lw16.hip: tile 0 = 32x16
+hipError_t launch_f32_x6(int tile, const GemmArgs &a, bool vec, hipStream_t s); // brgemm_f32_x6.hip: tile = variant - V_F32_X6_64x64
 int pick_bf16_tile(const GemmDesc &d);
 bool bf16_fast_eligible(const GemmDesc &d);
 
@@ -764,6 +769,7 @@ static bool bf16_small_eligible(const GemmDesc &d) {
 // the f32 chain tile (brgemm_f32_lw.hip, launch_f32_chain) a whole-layer f32 descriptor was planned on: 1 / 2 / 3, or -1 (another
 // kernel family, a VNNI operand, k not in 64-k chunks ... - whatever pick_f32_variant sent elsewhere)
 int f32_chain_tile(const GemmDesc &d) {
+  if (gemm_on_x6(d)) return -1; // the bf16x6 split kernel: chains that hold such a call run call by call (it has no chain form)
   if (d.dtype != DT_F32 || d.vnni_b || d.vnni_c || d.k <= 0 || d.k % BK) return -1;
   // (the 32x32 + K4 tile - the reference's batch-256 layers, 3.4 us of MFMA work per tile - is NOT chained: measured 21.9 us per
   // three-layer step as one launch against 20.6 as three, profiles/r04_f32_chain.txt: a seam is four dependent memory round trips
@@ -861,6 +867,7 @@ const char *last_refined_kernel() { return g_last_refined.load(std::memory_order
 hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_items, bool vec_ok, bool out_ok, bool pair_ok,
                                int64_t br_hint, hipStream_t stream) {
   if (d.m <= 0 || d.n <= 0 || n_items <= 0) return hipSuccess;
+  if (gemm_on_x6(d)) return hipErrorInvalidValue; // the split kernel is never queued or grouped (try_enqueue, gemm_invoke_unqueued)
   // n_dec: the number of items every size-dependent DECISION below is taken for. Normally the group's - the group is what fills the
   // chip. In strict mode 1: a single invoke, the first pass of a queued group and its replays then all run on the same kernel.
   const int64_t n_dec = strict_kernels() ? 1 : n_items;
@@ -1206,6 +1213,10 @@ static const char *variant_name(int v) {
   case V_F32_LW_32x32K4: return "brgemm_f32_fast_lw<32x32,k4>";
   case V_F32_LW_128x64: return "brgemm_f32_fast_lw<128x64,k1>";
   case V_F32_LW16_32x16: return "brgemm_f32_lw16<32x16,k4>";
+  case V_F32_X6_64x64: return "brgemm_f32_bf16x6<64x64,k1>";
+  case V_F32_X6_64x32K2: return "brgemm_f32_bf16x6<64x32,k2>";
+  case V_F32_X6_32x32K4: return "brgemm_f32_bf16x6<32x32,k4>";
+  case V_F32_X6_128x64: return "brgemm_f32_bf16x6<128x64,k1>";
   case V_BF16_FAST: return "brgemm_bf16_fast<64x64>";
   case V_BF16_DMA128: return "brgemm_bf16_dma<128x128>";
   case V_BF16_DMA256: return "brgemm_bf16_dma<256x256>";
@@ -1213,6 +1224,18 @@ static const char *variant_name(int v) {
   default: return "brgemm_grouped(generic)";
   }
 }
+
+// shapes the bf16x6 split kernel takes: the f32 loader-wave family's preconditions (pick_f32_variant) plus ldc a multiple of 4
+static bool f32_x6_eligible(const GemmDesc &d) {
+  return d.k > 0 && d.k % BK == 0 && d.m % 32 == 0 && d.n % 32 == 0 && !((d.lda | d.ldb | d.ldc | d.stride_a | d.stride_b) & 3) &&
+         d.lda < (1 << 22) && d.ldb < (1 << 22) && d.ldc < (1 << 22);
+}
+
+// split tiles the planner picks by itself for a bf16x6 descriptor (64x64, 64x32 + K2, 32x32 + K4, 128x64): the ones that beat the exact
+// kernel of the same tile. None does yet (profiles/x6_first_ab.txt, kernel averages bf16x6 / exact: first version 1.25 - 4.36; with
+// loader waves doing the split 1.29 - 3.99, e.g. 4096^3 1312.54 against 1015.14 us, 1024x2560x1024 103.87 against 57.49 us): a
+// bf16x6 descriptor stays on the exact plan of mode 0 unless a split tile is forced (xsmm_hip_force_variant 12 .. 15).
+static const bool X6_AUTO[4] = {false, false, false, false};
 
 bool plan_gemm(GemmDesc &d, int forced_variant) {
   int v = V_GENERIC;
@@ -1299,6 +1322,27 @@ bool plan_gemm(GemmDesc &d, int forced_variant) {
   } else if (forced_variant == V_GENERIC) {
     v = V_GENERIC;
   }
+  if (d.f32_prec == 6 && d.dtype == DT_F32 && !d.vnni_b && !d.vnni_c && f32_x6_eligible(d)) {
+    // bf16x6: the split kernel needs 64-k chunks, 16-byte row pieces, the 32-bit lane offsets and ldc a multiple of 4.
+    // It takes the output tile of the exact plan where the split tile of that size measured faster than the exact kernel (X6_AUTO: none
+    // yet); the skinny 32x16 tiles, the generic kernel and forced exact variants stay exact. A forced split tile (xsmm_hip_force_variant
+    // 12 .. 15) is honoured if the shape divides it.
+    const int fx = forced_variant - V_F32_X6_64x64;
+    if (fx >= 0 && fx <= 3) {
+      const int bm[] = {64, 64, 32, 128}, bn[] = {64, 32, 32, 64};
+      if (d.m % bm[fx] == 0 && d.n % bn[fx] == 0) v = forced_variant;
+    } else if (forced_variant < 0) {
+      int t = -1;
+      switch (v) {
+      case V_F32_64x64: case V_F32_64x64K2: case V_F32_LW_64x64: case V_F32_LW_64x64K2: t = 0; break;
+      case V_F32_64x32K2: case V_F32_LW_64x32K2: t = 1; break;
+      case V_F32_32x32K4: case V_F32_LW_32x32K4: t = 2; break;
+      case V_F32_128x64: case V_F32_LW_128x64: t = 3; break;
+      default: break;
+      }
+      if (t >= 0 && X6_AUTO[t]) v = V_F32_X6_64x64 + t;
+    }
+  }
   d.variant = v;
   d.generic_forced = forced_variant == V_GENERIC;
   d.variant_forced = forced_variant >= 0 && v == forced_variant;
@@ -1325,6 +1369,9 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     if (d.dtype != DT_F32 || d.vnni_b) return hipErrorInvalidValue;
     return launch_grouped_t<float, false, false>(a, nullptr, 1, stream);
   }
+  // bf16x6: the planned split tile whatever the batch count, split setting or pointer alignment (unaligned A / B: element loads)
+  if (v >= V_F32_X6_64x64 && v <= V_F32_X6_128x64)
+    return launch_f32_x6(v - V_F32_X6_64x64, a, ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0, stream);
   const bool aligned16 = ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0;
   if (v != V_GENERIC && !aligned16) v = V_GENERIC;
   // the bf16 kernel stores 16-byte row pieces and reads the bias 8 bytes at a time

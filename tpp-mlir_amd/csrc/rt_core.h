@@ -34,6 +34,7 @@ struct Config {
   std::atomic<hipStream_t> stream{nullptr};
   std::atomic<int> forced_variant{-1};
   std::atomic<int> tile_queue{0};
+  std::atomic<int> f32_precision{0}; // f32 arithmetic of descriptors dispatched from now on: 0 = exact, 6 = bf16x6 (xsmm_hip_set_f32_precision / TPP_HIP_F32_PRECISION)
   std::atomic<int> vnni_factor{2}; // blocking factor of VNNI B operands dispatched from now on (xsmm_hip_set_vnni_factor / TPP_HIP_VNNI_FACTOR)
   int trace = 0; // TPP_HIP_TRACE: 1 = one stderr line per dispatch + a roctx range per invoke, 2 = also one stderr line per invoke
   std::atomic<int> fold_transpose{1}; // TPP_HIP_FOLD_TRANSPOSE / xsmm_hip_set_fold_transpose: transposes that feed a gemm's B operand are folded into it
@@ -56,6 +57,12 @@ struct Config {
     if (const char *e = getenv("TPP_HIP_VNNI_FACTOR")) {
       if (atoi(e) == 2 || atoi(e) == 4) vnni_factor = atoi(e);
       else fprintf(stderr, "[tpp-xsmm-hip] TPP_HIP_VNNI_FACTOR=%s ignored: the factor is 2 or 4\n", e);
+    }
+    if (const char *e = getenv("TPP_HIP_F32_PRECISION")) {
+      if (!strcmp(e, "bf16x6") || !strcmp(e, "6")) f32_precision = 6;
+      if (trace)
+        fprintf(stderr, "[tpp-xsmm-hip] TPP_HIP_F32_PRECISION=%s: f32 gemm arithmetic %s\n", e,
+                f32_precision.load() == 6 ? "bf16x6 (split into three bf16 parts, six bf16 MFMA products)" : "exact f32 (the value is not bf16x6 / 6)");
     }
   }
 };

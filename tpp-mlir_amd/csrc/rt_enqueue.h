@@ -260,6 +260,7 @@ bool queue_active() {
 
 bool try_enqueue(const GemmDesc *d, void *a, void *b, void *c, void *dp, int64_t br, hipStream_t s) {
   if (d->m > 64 || d->n > 64) return false; // big descriptors fill the chip on their own
+  if (gemm_on_x6(*d)) return false;          // the bf16x6 split kernel: one launch per invoke (it has no grouped form)
   const void *ptrs[4] = {a, b, c, dp};
   return enqueue_item(d, WorkItem{a, b, c, dp, br}, ptrs, 4, s);
 }

@@ -84,7 +84,7 @@ __attribute__((noinline)) void gemm_invoke_unqueued(const GemmDesc *d, void *pa,
   C.read = !d->beta0; // pure output under BETA_0: never uploaded
   std::vector<Operand *> ops = {&A, &B, &C, &D};
   stage_in(ops, s);
-  if (cfg().strict.load(std::memory_order_relaxed) && d->m <= 64 && d->n <= 64) {
+  if (cfg().strict.load(std::memory_order_relaxed) && d->m <= 64 && d->n <= 64 && !gemm_on_x6(*d)) {
     // strict mode: a tile the queue would take runs on the kernel its group runs on - the grouped launcher with a work list of one
     // (launch_gemm_grouped decides as if every list held one item: xsmm_desc.h strict_kernels)
     const WorkItem one{A.dev, B.dev, C.dev, D.dev, br};

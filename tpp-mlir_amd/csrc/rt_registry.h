@@ -74,6 +74,9 @@ int64_t gemm_dispatch_common(const char *who, int has_batch, int fused, int64_t 
       fprintf(stderr, "[tpp-xsmm-hip] %s: the VNNI factor changed from %d to %d between two VNNI dispatches (handles keep the factor they were "
                       "dispatched with)\n", who, prev, vf_now);
   }
+  // f32 arithmetic (xsmm_hip_set_f32_precision / TPP_HIP_F32_PRECISION): read ONCE per dispatch, like the VNNI factor; the handle
+  // keeps the mode it was dispatched with (it is part of the key). bf16 descriptors ignore it.
+  const int f32p = dtype == DT_F32 ? cfg().f32_precision.load(std::memory_order_relaxed) : 0;
   if (vnni_c && (m & 1)) die("%s: VNNI-2 C operand needs an even m, got %ld", who, (long)m);
   if (fused) {
     if (unary_flags != 0) die("%s: unsupported unary flags %ld on a fused brgemm", who, (long)unary_flags);
@@ -89,7 +92,7 @@ int64_t gemm_dispatch_common(const char *who, int has_batch, int fused, int64_t 
   }
   std::vector<int64_t> key = {KIND_GEMM, has_batch, fused, dtype, m, n, k, lda, ldb, ldc, stride_a, stride_b,
                               flags & (XSMM_GEMM_FLAG_BETA_0 | XSMM_GEMM_WIRE_VNNI_B | XSMM_GEMM_FLAG_VNNI_C), unary_kind, binary_kind,
-                              cfg().forced_variant.load(), vf};
+                              cfg().forced_variant.load(), vf, f32p};
   void *h = intern(key, [&]() {
     GemmDesc *d = new GemmDesc();
     memset(d, 0, sizeof(*d));
@@ -102,6 +105,7 @@ int64_t gemm_dispatch_common(const char *who, int has_batch, int fused, int64_t 
     d->vnni_b = vnni_b;
     d->vnni_c = vnni_c;
     d->vnni_factor = vf;
+    d->f32_prec = f32p;
     d->bias = fused && binary_kind == XSMM_BINARY_ADD;
     d->relu = fused && unary_kind == XSMM_UNARY_RELU;
     plan_gemm(*d, cfg().forced_variant.load());

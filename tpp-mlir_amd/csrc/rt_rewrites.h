@@ -67,6 +67,7 @@ inline void detect_grid(Segment &S) {
     GemmDesc *g = new GemmDesc(*d);
     g->m = M;
     g->n = N;
+    g->f32_prec = 0; // the tiles ran on exact kernels (a split-kernel handle is never queued): so does the merged grid
     ok = plan_gemm(*g, -1);
     snprintf(g->trace, sizeof(g->trace), "tile grid %zu x %zu of gemm[%ld,%ld,%ld] merged -> [%ld,%ld,%ld,%ld,%ld,%ld] %s", R, Cn, (long)d->m, (long)d->n,
              (long)d->k, (long)M, (long)N, (long)d->k, (long)d->lda, (long)d->ldb, (long)d->ldc, g->name);
@@ -375,7 +376,7 @@ const GemmDesc *dt_gemm(const GemmDesc *d, void *pa, void *pb, void *pc, void *p
         // record keeps its transpose descriptor for as long as it lives)
         const bool known = r.sib_of == d;
         if (pb == r.dst && br == 1 && s == r.stream && queue_active() &&
-            (known || (d->dtype == DT_F32 && !d->vnni_b && !d->vnni_c && !d->b_trans && d->k == t->n && d->n == t->m && d->ldb == t->ldo && d->m <= 64 && d->n <= 64))) {
+            (known || (d->dtype == DT_F32 && !gemm_on_x6(*d) && !d->vnni_b && !d->vnni_c && !d->b_trans && d->k == t->n && d->n == t->m && d->ldb == t->ldo && d->m <= 64 && d->n <= 64))) {
           const size_t a_bytes = known ? r.a_bytes : span(d->m, d->lda, d->k) * 4, c_bytes = known ? r.c_bytes : span(d->m, d->ldc, d->n) * 4,
                        d_bytes = known ? r.d_bytes : (d->bias ? (size_t)d->n * 4 : 0);
           if (!dt_overlap(pa, a_bytes, r.dst, dst_bytes) && !dt_overlap(pc, c_bytes, r.dst, dst_bytes) && !dt_overlap(pd, d_bytes, r.dst, dst_bytes) &&

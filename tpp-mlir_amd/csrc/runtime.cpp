@@ -504,4 +504,10 @@ extern "C" int xsmm_hip_set_vnni_factor(int v) {
   return cfg().vnni_factor.exchange(v);
 }
 extern "C" int xsmm_hip_get_vnni_factor(void) { return cfg().vnni_factor.load(); }
+// the f32 gemm arithmetic of descriptors dispatched from now on (0 = exact, 6 = bf16x6); returns the previous one, -1 for another value
+extern "C" int xsmm_hip_set_f32_precision(int mode) {
+  if (mode != 0 && mode != 6) return -1;
+  return cfg().f32_precision.exchange(mode);
+}
+extern "C" int xsmm_hip_get_f32_precision(void) { return cfg().f32_precision.load(); }
 extern "C" const char *xsmm_hip_version(void) { return "tpp-xsmm-hip 0.1 (gfx950)"; }

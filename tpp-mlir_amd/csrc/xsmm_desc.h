@@ -24,6 +24,8 @@ struct GemmDesc {
   int vnni_c;           // C stored / read as VNNI-2 [m/2][n][2] (wire flag 8192): generic kernel only
   int vnni_factor;      // blocking factor v of a VNNI B operand [k/v][n][v]: 2, or 4 (xsmm_hip_set_vnni_factor at dispatch time; the
                         // factor is not on the wire - the reference asks libxsmm_cpuid_dot_pack_factor, VNNIUtils.cpp:25-45)
+  int f32_prec;         // f32 arithmetic: 0 = exact f32 MFMA, 6 = bf16x6 split (xsmm_hip_set_f32_precision at dispatch time; part of the
+                        // descriptor key; 0 for bf16 descriptors). plan_gemm runs brgemm_f32_x6.hip where a split tile is forced and fits, else the exact kernel
   int variant;          // kernel variant chosen at dispatch (see gemm_variants.h), -1 = by invoke
   int generic_forced;   // variant = generic because it was asked for (xsmm_hip_force_variant / a VNNI C store), not because no fast tile fits
   int variant_forced;   // variant is the one xsmm_hip_force_variant asked for: invoke-time refinements (batch-count dependent) leave it alone
@@ -101,7 +103,11 @@ const char *last_refined_kernel(); // most recent launch_gemm: the kernel an inv
 bool plan_gemm(GemmDesc &d, int forced_variant);
 constexpr int GEMM_VARIANT_BF16_LW0 = 20; // = V_BF16_LW_32x64: first of the four loader-wave bf16 tiles (brgemm_bf16_lw.hip)
 constexpr int GEMM_VARIANT_BF16_LW4_0 = 28; // = V_BF16_LW4_32x64: the same four tiles for a VNNI-4 B operand
-constexpr int GEMM_VARIANT_GENERIC = 8; // = V_GENERIC of brgemm_f32.hip: the generic kernel was chosen (or forced) at dispatch
+constexpr int GEMM_VARIANT_F32_X6_0 = 12; // = V_F32_X6_64x64: first of the four bf16x6 split tiles (brgemm_f32_x6.hip)
+constexpr int GEMM_VARIANT_GENERIC = 8;
+// planned on the bf16x6 split kernel (brgemm_f32_x6.hip: variants 12 .. 15). Such handles are never queued, grouped, chained or given a
+// folded transpose; a bf16x6 descriptor planned on an exact kernel (a shape the split kernel does not take) goes every way a mode-0 one goes
+inline bool gemm_on_x6(const GemmDesc &d) { return d.variant >= GEMM_VARIANT_F32_X6_0 && d.variant <= GEMM_VARIANT_F32_X6_0 + 3; } // = V_GENERIC of brgemm_f32.hip: the generic kernel was chosen (or forced) at dispatch
 // bf16 + VNNI-2 B, k a multiple of 64, m and n of 64, 16-byte-aligned leading dimensions within the 32-bit lane offsets: what the
 // LDS-DMA bf16 tile families (brgemm_bf16.hip, brgemm_bf16_lw.hip) need
 bool bf16_fast_eligible(const GemmDesc &d);

@@ -113,6 +113,8 @@ _SIGNATURES = {
     "xsmm_hip_fold_transpose_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_vnni_factor": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_get_vnni_factor": (ctypes.c_int, []),
+    "xsmm_hip_set_f32_precision": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_get_f32_precision": (ctypes.c_int, []),
     "xsmm_hip_version": (ctypes.c_char_p, []),
 }
 
@@ -333,6 +335,14 @@ class XsmmRuntime:
         if old < 0:
             raise ValueError("the VNNI factor is 2 or 4")
         return old
+
+    def set_f32_precision(self, mode):
+        """f32 gemm arithmetic of descriptors dispatched from now on: 0 = exact f32 MFMA, 6 = bf16x6 split. Returns the previous
+        setting, or -1 (setting unchanged) for any other value"""
+        return self.lib.xsmm_hip_set_f32_precision(int(mode))
+
+    def get_f32_precision(self):
+        return self.lib.xsmm_hip_get_f32_precision()
 
     def version(self):
         return self.lib.xsmm_hip_version().decode()
