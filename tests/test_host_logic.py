@@ -85,13 +85,17 @@ def test_bf16_loader_wave_kernels_do_not_spill():
 
 
 def test_shipped_library_has_no_measurement_switches():
-    """the switches that take work out of the chain kernel (TPP_HIP_CHAIN_DBG, results wrong by design) and the in-kernel stamps
-    (TPP_HIP_CHAIN_STAMPS) exist in -DTPP_HIP_ABLATION side builds only (tpp-mlir_amd/build.py --ablation): the shipped library
-    must not even contain the variable names"""
+    """the retired measurement and A/B switches - the chain kernel's timing bits and in-kernel stamps, and the environment
+    variables that brought back an older kernel path - are gone: the library must not even contain their names"""
     import importlib
     build = importlib.import_module("tpp-mlir_amd.build")
     blob = open(build.build(), "rb").read()
-    for name in (b"TPP_HIP_CHAIN_DBG", b"TPP_HIP_CHAIN_STAMPS"):
+    for name in (b"TPP_HIP_CHAIN_DBG", b"TPP_HIP_CHAIN_STAMPS",
+                 b"TPP_HIP_F32_LW16", b"TPP_HIP_BF16_LONG_K", b"TPP_HIP_BF16_LW32", b"TPP_HIP_GROUPED_K32_PAIRS",
+                 b"TPP_HIP_BF16_LW_GROUPED", b"TPP_HIP_BF16_LW_RAGGED", b"TPP_HIP_BF16_LW_T4_VNNI4", b"TPP_HIP_BF16_QUADS",
+                 b"TPP_HIP_BF16_LW\0", b"TPP_HIP_BF16_LW_PICK", b"TPP_HIP_BF16_LW_XM", b"TPP_HIP_BLW_SUP", b"TPP_HIP_BLW_T3",
+                 b"TPP_HIP_F32_LW_XM", b"TPP_HIP_F32_LW_C3_LOADERS", b"TPP_HIP_TRANSPOSE_TILE", b"TPP_HIP_PACK_PIECE",
+                 b"TPP_HIP_PACK_POLICY", b"TPP_HIP_PEER_FINEGRAINED", b"TPP_HIP_QUEUE_SOLO", b"TPP_HIP_GRID_MERGE"):
         assert name not in blob, name
 
 

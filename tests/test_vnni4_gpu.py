@@ -298,7 +298,7 @@ def test_vnni4_groups_of_64x64_tiles_run_on_the_64x64_family(rt):
             finally:
                 rt.set_tile_queue(prev_q)
                 rt.set_async(prev_async)
-            # (round 6: such a group runs on the grouped loader-wave tile; TPP_HIP_BF16_LW_GROUPED=0 brings the 64x64 family back)
+            # (round 6: such a group runs on the grouped loader-wave tile)
             assert ("lw_vnni4<64x64> grouped" if v == 4 else "lw<64x64> grouped") in ran or ("fast_vnni4<64x64> grouped" if v == 4 else "fast<64x64> grouped") in ran, ran
             got = host(dC, C0)
             sel = np.concatenate([np.arange((i * NB) * t * t, (i * NB + NB) * t * t) for i in range(0, MB, 5)])

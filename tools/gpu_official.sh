@@ -32,18 +32,9 @@ PY
   timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$tag -o p -- $cmd > /dev/null 2>&1
   f=$(find /tmp/ks_$tag -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && grep brgemm $f | cut -c1-170 | sed "s/^/$tag /" >> $R/$OUT/mfma_busy.txt
 done )
-# the per-rank step of the row-sharded C4 MLP (one chain launch vs three launches), forced tiles, and the chain kernel's phases
+# the per-rank step of the row-sharded C4 MLP (one chain launch vs three launches) and forced tiles
 for i in 1 2 3; do timeout 100 tools/mlp_probe; done > $OUT/mlp_probe.txt 2>&1
 for v in 16 17 19 20 21 22 23; do timeout 60 tools/mlp_probe --variant $v --only layers --rows 256,512,1024,2048,4096; done > $OUT/mlp_probe_forced.txt 2>&1
-[ -f tools/_abl/libtpp_xsmm_runner_utils.so ] && for rows in 512 1024 2048 4096; do
-  LD_LIBRARY_PATH=tools/_abl TPP_HIP_CHAIN_STAMPS=$OUT/stamps_${rows}.txt timeout 60 tools/mlp_probe --only chain --rows $rows --iters 50 > /dev/null 2>&1
-  echo "== rows $rows"; python tools/stamps_report.py $OUT/stamps_${rows}.txt; done > $OUT/chain_anatomy.txt 2>&1
-# timing with parts of the chain kernel switched off: side builds only (python tpp-mlir_amd/build.py --ablation BEFORE the gpurun call;
-# the shipped library has no such switch). 32 / 48 need the build with the fragment reads and MFMAs compiled out as well.
-if [ -f tools/_abl/libtpp_xsmm_runner_utils.so ]; then
-for dbg in 0 16 32 48 2 6 7; do echo "dbg=$dbg"; lib=tools/_abl; [ $((dbg & 32)) -ne 0 ] && lib=tools/_abl_nomath
-  LD_LIBRARY_PATH=$lib TPP_HIP_CHAIN_DBG=$dbg timeout 100 tools/mlp_probe 2>&1; done > $OUT/chain_ablation.txt
-fi
 # round 5: the reference's benchmark shape set (full table + json), the split / half-width-tile sweep, the self-launching N = 2 bench on the one-device rig
 timeout 900 python bench.py --refbench --refbench-json $OUT/refbench.json > $OUT/refbench.txt 2> $OUT/refbench.err
 timeout 300 python tools/split_sweep.py > $OUT/split_sweep.txt 2>&1
@@ -67,7 +58,7 @@ g++ -O2 -std=c++17 tools/ubench/wp_async_probe.cpp -o /tmp/wp_async_probe -inclu
 timeout 200 tools/ubench/split_handoff.out > $OUT/split_handoff.txt 2>&1
 echo "# matmul_128x768x768 as tile invokes (32,64,64), 50 timed loops of 200 calls each (VERDICT r5 weak 9: the 51 us row)" > $OUT/outlier.txt
 timeout 300 tools/tpp_replay --batch 128 --layers 768,768 --kernel args --tiles 32,64,64 --queue 1 -n 200 --repeats 50 2>&1 | grep -v "^[0-9.e-]*$" >> $OUT/outlier.txt
-# round 6, second half: the launch thread and the quads, on / off on this box (short forms of profiles/r06_launch_thread_ab.txt, r06_bf16_quads_ab.txt)
+# round 6, second half: the launch thread on / off, and the whole-layer call the quads are measured against, on this box (short forms of profiles/r06_launch_thread_ab.txt, r06_bf16_quads_ab.txt)
 {
 R=tools/tpp_replay; M="--batch 256 --layers 1024,1024,1024,1024 --tiles 32 --bias --relu"
 for lt in 0 1 0 1; do echo "### TPP_HIP_LAUNCH_THREAD=$lt"; export TPP_HIP_LAUNCH_THREAD=$lt
@@ -75,9 +66,6 @@ for lt in 0 1 0 1; do echo "### TPP_HIP_LAUNCH_THREAD=$lt"; export TPP_HIP_LAUNC
   $R $M --bf16 --queue 1 -n 300 --repeats 5 2>&1 | grep "repeats" | sed 's/^/MLP tiles bf16: /'
   for s in mha_qk mha_sv pack_a unpack_c; do $R --script $s --queue 1 -n 1000 2>&1 | grep "mean" | cut -c1-130; done
 done; unset TPP_HIP_LAUNCH_THREAD
-for q in 0 1 0 1; do echo "### TPP_HIP_BF16_QUADS=$q"
-  for v in 2 4; do TPP_HIP_BF16_QUADS=$q $R --batch 1024 --layers 1024,2560 --tiles 64,64,64 --bf16 --vnni $v --queue 1 -n 300 --repeats 3 2>&1 | grep "repeats\|mean" | cut -c1-230; done
-done
 $R --batch 1024 --layers 1024,2560 --whole-layer --bf16 -n 300 --repeats 3 2>&1 | grep "repeats\|mean" | cut -c1-230
 } > $OUT/launch_thread_and_quads.txt 2>&1
 python tools/eltwise_bw.py > $OUT/eltwise_bw.txt 2>/dev/null

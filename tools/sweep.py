@@ -170,9 +170,9 @@ if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "big":
     sys.exit(0)
 
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "shards":
-    # per-rank layer shapes of the row-sharded C4 MLP at 8/4/2/1 GPUs (kernel choice: TPP_HIP_BF16_T128MIN)
+    # per-rank layer shapes of the row-sharded C4 MLP at 8/4/2/1 GPUs
     for m in (512, 1024, 2048, 4096):
-        bf16_case(m, 1024, 64, 16, tag="C4 layer shard, T128MIN=%s" % os.environ.get("TPP_HIP_BF16_T128MIN", "default"))
+        bf16_case(m, 1024, 64, 16, tag="C4 layer shard")
     sys.exit(0)
 
 if __name__ == "__main__":

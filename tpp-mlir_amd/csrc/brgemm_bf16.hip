@@ -25,15 +25,6 @@ namespace tpp {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
-// Timing-only ablation masks: SIDE builds only (tools/sessions/ablate_bf16.sh compiles this file with -DTPP_ABLATE=mask into
-// build/libabl_*.so); the shipped library is built with 0 and every `if (TPP_ABLATE & ...)` below folds away.
-#ifndef TPP_ABLATE
-#define TPP_ABLATE 0
-#endif
-constexpr int HABL_NO_GLOAD = 1, HABL_NO_SWRITE = 2, HABL_NO_BARRIER = 4, HABL_NO_FRAG = 8, HABL_NO_TRANSPOSE = 16,
-              HABL_NO_BFRAG = 64 /* dma128: no B fragment reads */, HABL_NO_BDMA = 128 /* dma128: the B loader wave fetches nothing */,
-              HABL_NO_ADMA = 256 /* dma128: the A loader wave fetches nothing */, HABL_LOADERS_ONLY = 512 /* dma128: the MFMA waves leave at once */;
-
 constexpr int BKH = 64;     // k per chunk
 constexpr int NSTAGE_H = 3;
 constexpr int NSET_H = 3;  // staging register sets (chunks of global loads in flight per lane)
@@ -125,7 +116,6 @@ __global__ __launch_bounds__(64 * WM * WN) void brgemm_bf16_fast(GemmArgs p, con
           const int c2 = e >> 1, o = 2 * (e & 1);
           v = u32x4{rb[stage][u][c2][o], rb[stage][u][c2][o + 1], rb[stage][u][2 + c2][o], rb[stage][u][2 + c2][o + 1]};
         }
-        if (TPP_ABLATE & HABL_NO_TRANSPOSE) v = rb[stage][u][e];
         *(u32x4 *)(bs + g * B_GROW + ((4 * jq + e) << 4)) = v;
       }
     }
@@ -165,10 +155,8 @@ __global__ __launch_bounds__(64 * WM * WN) void brgemm_bf16_fast(GemmArgs p, con
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int cur = q & 1, nxt = cur ^ 1;
-      if (!(TPP_ABLATE & HABL_NO_FRAG)) {
-        if (q + 1 < 4) frag_load(nxt, STAGE, q + 1);
-        else if (HAS_NEXT) frag_load(nxt, NSTG, 0);
-      }
+      if (q + 1 < 4) frag_load(nxt, STAGE, q + 1);
+      else if (HAS_NEXT) frag_load(nxt, NSTG, 0);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -189,13 +177,13 @@ __global__ __launch_bounds__(64 * WM * WN) void brgemm_bf16_fast(GemmArgs p, con
           }
 #pragma unroll
           for (int it = 0; it < NWRITE; ++it)
-            if (HAS_NEXT && !(TPP_ABLATE & HABL_NO_SWRITE) && q < 2 && (it * SLOTS) / NWRITE == slot) swrite_item(NSTG, it);
+            if (HAS_NEXT && q < 2 && (it * SLOTS) / NWRITE == slot) swrite_item(NSTG, it);
 #pragma unroll
           for (int it = 0; it < NLOAD; ++it)
-            if (HAS_LOAD && !(TPP_ABLATE & HABL_NO_GLOAD) && q >= 2 && (it * SLOTS) / NLOAD == slot) gload_item(NSTG, it);
+            if (HAS_LOAD && q >= 2 && (it * SLOTS) / NLOAD == slot) gload_item(NSTG, it);
           __builtin_amdgcn_sched_barrier(0);
         }
-      if (q == 1 && !(TPP_ABLATE & HABL_NO_BARRIER)) __syncthreads();
+      if (q == 1) __syncthreads();
     }
   };
   using yes = std::integral_constant<bool, true>;
@@ -279,21 +267,6 @@ __global__ __launch_bounds__(64 * WM * WN) void brgemm_bf16_fast(GemmArgs p, con
     if (t < T) tail(S2{});
   }
 
-  if (TPP_ABLATE) {
-#pragma unroll
-    for (int st = 0; st < NSET_H; ++st) {
-#pragma unroll
-      for (int u = 0; u < LA; ++u) asm volatile("" ::"v"(ra[st][u]));
-#pragma unroll
-      for (int u = 0; u < LB; ++u)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) asm volatile("" ::"v"(rb[st][u][r]));
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(af[0][i]), "v"(af[1][i]));
-#pragma unroll
-    for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(bfr[0][j]), "v"(bfr[1][j]));
-  }
   // epilogue: (+bias[col]) (relu) -> bf16 (RNE, v_cvt_pk_bf16_f32) -> 16-byte stores. A lane
   // holds 4 consecutive columns per register quad and its partner lane (lh ^ 1) the next 4;
   // one v_permlane32_swap per dword gives the lower half-wave columns 8g..8g+7 of quad g and
@@ -422,13 +395,10 @@ __global__ __launch_bounds__(256 + 64 * NLW) void brgemm_bf16_dma128(GemmArgs p)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_d[];
 
   const int tid = threadIdx.x, lane = tid & 63;
-#ifndef TPP_BF16_LOADERS_FIRST
-#define TPP_BF16_LOADERS_FIRST 1
-#endif
   // the loader waves are the FIRST hardware waves of the workgroup (waves start in order: the first chunks are requested before
   // the MFMA waves have been launched); `wave` is the role index: MFMA waves 0-3, loaders 4 .. 4 + NLW - 1
   const int hw_wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wave = (LW && TPP_BF16_LOADERS_FIRST) ? (hw_wave < NLW ? 4 + hw_wave : hw_wave - NLW) : hw_wave;
+  const int wave = LW ? (hw_wave < NLW ? 4 + hw_wave : hw_wave - NLW) : hw_wave;
   const int wm = wave >> 1, wn = wave & 1;
   const int li = lane & 31, lh = lane >> 5;
   const int tm = (int)(blockIdx.x >> 1) * p.tiles_m + (int)blockIdx.z;
@@ -498,13 +468,11 @@ __global__ __launch_bounds__(256 + 64 * NLW) void brgemm_bf16_dma128(GemmArgs p)
     auto issue = [&](int slot) __attribute__((always_inline)) {
       unsigned char *base = smem_d + slot * SLOT + (isA ? 0 : A_SLOT) + v0 * 1024;
       if (isA) {
-        if (!(TPP_ABLATE & HABL_NO_ADMA)) {
-          const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)gA, 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)gA, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
-          for (int v = 0; v < PPL; ++v)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t *)(base + v * 1024), 16, (v & 1) ? voA1 : voA0, (v0 + v) * stepA, 0, 0);
-        }
-      } else if (!(TPP_ABLATE & HABL_NO_BDMA)) {
+        for (int v = 0; v < PPL; ++v)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t *)(base + v * 1024), 16, (v & 1) ? voA1 : voA0, (v0 + v) * stepA, 0, 0);
+      } else {
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)gB, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
         for (int v = 0; v < PPL; ++v)
@@ -529,13 +497,12 @@ __global__ __launch_bounds__(256 + 64 * NLW) void brgemm_bf16_dma128(GemmArgs p)
       if (t + 3 < T) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPL) : "memory");
       else if (t + 2 < T) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPL) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (!(TPP_ABLATE & HABL_NO_BARRIER)) __builtin_amdgcn_s_barrier(); // = the MFMA waves' mid-chunk barrier of chunk t: chunk t+1 published, slot of chunk t-1 retired
+      __builtin_amdgcn_s_barrier(); // = the MFMA waves' mid-chunk barrier of chunk t: chunk t+1 published, slot of chunk t-1 retired
       if (t + 4 < T) issue((t + 4) % NSLOT);
     }
     return; // ended waves do not take part in later barriers
   }
 
-  if (TPP_ABLATE & HABL_LOADERS_ONLY) return; // timing only: how fast can the loader waves alone fill the ring?
   f32x16 acc[TM][TN];
   constexpr int NFB = 4; // fragment buffers: step q+2 is read while step q multiplies
   bf16x8_t af[NFB][TM];
@@ -557,7 +524,6 @@ __global__ __launch_bounds__(256 + 64 * NLW) void brgemm_bf16_dma128(GemmArgs p)
       const int row = (wm * TM + i) * 32 + li;
       af[buf][i] = *(const bf16x8_t *)(as + row * 128 + (((2 * ks + lh) ^ ((row >> 1) & 7)) << 4));
     } else {
-      if (TPP_ABLATE & HABL_NO_BFRAG) return;
       const int j = (idx - 1) >> 1, h = (idx - 1) & 1;
       const unsigned int *bp = bs + b_lane[j] + (8 * ks) * BN;
       bw[buf][j][2 * h] = bp[(2 * h) * BN];
@@ -568,15 +534,6 @@ __global__ __launch_bounds__(256 + 64 * NLW) void brgemm_bf16_dma128(GemmArgs p)
 #pragma unroll
     for (int idx = 0; idx < 6; ++idx) frag_piece(buf, slot, ks, idx);
   };
-#ifndef TPP_BF16_SPREAD_READS
-#define TPP_BF16_SPREAD_READS 0 // A/B measured: no gain at this tile (not issue-bound: DESIGN.md 4.2); the 256x256 kernel needs it
-#endif
-  // one chunk in ring slot S. H1/H2/H3: chunk t+1 / t+2 / t+3 exist. Step q multiplies the
-  // fragments in buffer q (4 steps per chunk, 4 buffers) while the fragments of step q+2 are
-  // read (steps 2, 3 read the first two steps of chunk t+1, published by the mid barrier), the six
-  // reads spread over the step's four MFMAs (a burst from four waves at once fills the LDS queue and
-  // holds up the MFMA issue behind it). The 8 DMA instructions of chunk t+3 ride one per MFMA in
-  // steps 2 and 3.
   // One chunk in ring slot S. STEADY: chunks t+1 .. t+3 exist, S is a literal (every LDS address is a
   // base VGPR + immediate) and nothing is conditional. Otherwise one of the last <= 6 chunks, with
   // run-time slot and flags h1 / h2 / h3 (chunk t+1 / t+2 / t+3 exists). Exactly TWO code instances: the
@@ -584,27 +541,23 @@ __global__ __launch_bounds__(256 + 64 * NLW) void brgemm_bf16_dma128(GemmArgs p)
   // misses (~600 cycles each) in a kernel of 16 chunks.
   // Step q multiplies the fragments in buffer q (4 steps per chunk, 4 buffers) while the fragments of
   // step q+2 are read (steps 2, 3 read the first two steps of chunk t+1, published by the mid barrier).
-  // Without loader waves the 8 DMA instructions of chunk t+3 ride one per MFMA in steps 2 and 3.
+  // Without loader waves the 8 DMA instructions of chunk t+3 ride one per MFMA in steps 2 and 3. (Spreading the six fragment
+  // reads of a steady step over its four MFMAs, as the 256x256 kernel does, measured no gain here: not issue-bound)
   auto chunk = [&](auto steady_c, int S, bool h1, bool h2, bool h3) __attribute__((always_inline)) {
     constexpr bool STEADY = decltype(steady_c)::value;
     const bool H1 = STEADY || h1, H2 = STEADY || h2, H3 = STEADY || h3;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const bool reads = !(TPP_ABLATE & HABL_NO_FRAG) && (q + 2 < 4 || H1);
+      const bool reads = q + 2 < 4 || H1;
       const int rbuf = q + 2 < 4 ? q + 2 : q - 2, rslot = q + 2 < 4 ? S : (S + 1) % NSLOT, rks = rbuf;
-      if (reads && !(STEADY && TPP_BF16_SPREAD_READS)) frag_load(rbuf, rslot, rks);
+      if (reads) frag_load(rbuf, rslot, rks);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, bw[q][j]), af[q][i], acc[i][j], 0, 0, 0);
-          if (STEADY && TPP_BF16_SPREAD_READS && reads) {
-            const int m = i * TN + j; // after MFMA 0: A0, B0 lo | 1: B0 hi, B1 lo | 2: B1 hi | 3: A1
-            frag_piece(rbuf, rslot, rks, m == 0 ? 0 : m == 1 ? 2 : m == 2 ? 4 : 5);
-            if (m < 2) frag_piece(rbuf, rslot, rks, m == 0 ? 1 : 3);
-          }
-          if (!LW && STEADY && q >= 2 && !(TPP_ABLATE & HABL_NO_GLOAD)) {
+          if (!LW && STEADY && q >= 2) {
             dma_piece((S + 3) % NSLOT, (q - 2) * 4 + i * TN + j); // a slot no wave reads any more (NLW = 0 keeps 3 chunks in flight)
             if (q == 3 && i == TM - 1 && j == TN - 1) TPP_DMA_ADVANCE();
           }
@@ -616,9 +569,9 @@ __global__ __launch_bounds__(256 + 64 * NLW) void brgemm_bf16_dma128(GemmArgs p)
           if (H2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_CHUNK) : "memory");
           else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        if (!(TPP_ABLATE & HABL_NO_BARRIER)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (!LW && !STEADY && H3 && !(TPP_ABLATE & HABL_NO_GLOAD)) { // the last chunks: one burst
+        if (!LW && !STEADY && H3) { // the last chunks: one burst
           dma_chunk((S + 3) % NSLOT);
           TPP_DMA_ADVANCE();
           __builtin_amdgcn_sched_barrier(0);
@@ -681,12 +634,6 @@ __global__ __launch_bounds__(256 + 64 * NLW) void brgemm_bf16_dma128(GemmArgs p)
   }
   for (; t < T; ++t) chunk(no{}, t % NSLOT, t + 1 < T, t + 2 < T, t + 3 < T); // the last <= 7 chunks
 
-  if (TPP_ABLATE & HABL_NO_FRAG) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(af[0][i]), "v"(af[1][i]), "v"(af[2][i]), "v"(af[3][i]));
-#pragma unroll
-    for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(bw[0][j]), "v"(bw[1][j]), "v"(bw[2][j]), "v"(bw[3][j]));
-  }
   // ---- epilogue ------------------------------------------------------------------------
   // lane (li, lh) owns row 32*i + li of wave-tile row block i and, in registers 4g..4g+3 of
   // tile (i, j), columns 32*j + 8*g + 4*lh + (0..3)
@@ -799,7 +746,7 @@ hipError_t launch_bf16_dma256(const GemmArgs &a, hipStream_t s); // brgemm_bf16_
 //    so a grid of t tiles takes ceil(t / 256) rounds;
 //  * 128 x 128 as soon as the 64 x 64 family would need a second round of workgroups (more than 256 tiles of
 //    64 x 64 = more than 64 of 128 x 128): measured (n = 1024, K = 1024) the DMA kernel takes 9.2-9.4 us from 64
-//    to 256 tiles while the 64 x 64 family jumps from 9.1 to 12.8 us past one tile per CU (tools/sessions/mid_probe.py);
+//    to 256 tiles while the 64 x 64 family jumps from 9.1 to 12.8 us past one tile per CU;
 //  * 64 x 64 below that, so that more CUs have work.
 int pick_bf16_tile(const GemmDesc &d) {
   constexpr int64_t t256_min = 240, t128_min = 65; // crossovers measured in profiles/r01_sweep_shapes.txt
@@ -814,11 +761,8 @@ int pick_bf16_tile(const GemmDesc &d) {
 hipError_t launch_gemm_bf16_fast(int tile, const GemmArgs &a, hipStream_t s) {
   if (tile == 2) return launch_bf16_dma256(a, s);
   // two loader waves; none / four were measured equal (profiles/r02_bf16_dma128_ablation.txt: the loop is bound by the
-  // fill path, not by the DMA issue rate of a wave). -DTPP_BF16_NLW=0|4 builds those variants for A/B runs.
-#ifndef TPP_BF16_NLW
-#define TPP_BF16_NLW 2
-#endif
-  if (tile == 1) return launch_bf16_dma128<TPP_BF16_NLW>(a, s);
+  // fill path, not by the DMA issue rate of a wave).
+  if (tile == 1) return launch_bf16_dma128<2>(a, s);
   return launch_bf16<2, 2, 1, 1>(a, s);
 }
 

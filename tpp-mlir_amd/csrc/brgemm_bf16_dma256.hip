@@ -32,10 +32,6 @@ namespace tpp {
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-#ifndef TPP_ABLATE256
-#define TPP_ABLATE256 0 // timing experiments (results are wrong): 1 no DMA in the loop, 2 no fragment reads, 4 no barrier
-#endif
-
 __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
   constexpr int BM = 256, BN = 256, BK2 = 32, NSLOT = 4, TM = 4, TN = 4;
   constexpr int A_SLOT = BM * BK2 * 2, B_SLOT = (BK2 / 2) * BN * 4, SLOT = A_SLOT + B_SLOT;
@@ -112,7 +108,6 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
   // B1, B2, B3, A1, A2, A3. They are issued ONE PER MFMA (a burst of 12 reads from four waves at once
   // fills the LDS queue and stalls the MFMA issue behind it: measured 217 cycles per K step).
   auto frag_piece = [&](int buf, int slot, int ks, int idx) __attribute__((always_inline)) {
-    if (TPP_ABLATE256 & 2) return;
     const unsigned char *s = smem_x + slot * SLOT;
     if (idx == 0 || idx >= 9) {
       const int i = idx == 0 ? 0 : idx - 8;
@@ -149,7 +144,7 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
       // chunk t+1: this wave's DMA has landed (chunk t+2's may still fly), then everybody's
       if (STEADY || h2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_CHUNK) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (!(TPP_ABLATE256 & 4)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       if (!STEADY) { // the last chunks: plain bursts, a branch per MFMA would cost more
         frag_load(0, (slot + 1) & (NSLOT - 1), 0);
@@ -169,7 +164,7 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
       for (int j = 0; j < TN; ++j) {
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, bw[1][j]), af[1][i], acc[i][j], 0, 0, 0);
         if (STEADY && i * TN + j < 12) frag_piece(0, (slot + 1) & (NSLOT - 1), 0, i * TN + j);
-        if (STEADY && ((i * TN + j) & 1) && !(TPP_ABLATE256 & 1)) {
+        if (STEADY && ((i * TN + j) & 1)) {
           dma_piece((slot + 3) & (NSLOT - 1), (i * TN + j) >> 1);
           if (i == TM - 1 && j == TN - 1) TPP_DMA256_ADVANCE();
         }
@@ -199,16 +194,6 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
   if (T > 0) frag_load(0, 0, 0);
-  if (TPP_ABLATE256 & 2) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        af[q][i] = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
-        bw[q][i] = u32x4{0, 0, 0, 0};
-        asm volatile("" : "+v"(af[q][i]), "+v"(bw[q][i]));
-      }
-  }
   int t = 0;
   for (; t + 6 < T; t += 4) { // steady state: ring slots are compile-time constants (t % 4 == 0 here)
     chunk(yes{}, 0, true, true, true);

@@ -46,70 +46,9 @@ typedef unsigned int u32x2_lw __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) unsigned int g_u32_lw;
 
 constexpr int BLW_BK = 64; // k per chunk
-#ifndef TPP_BLW_INTERLEAVE
-#define TPP_BLW_INTERLEAVE 2 // fragment reads dealt between the MFMAs of a k-step: 1 = the four-accumulator tile (128x128), 2 = + 64x128; 0 = in front (A/B)
-#endif
 // The kernel's argument block, read where it lies (kernarg segment, constant address space): the layer table is indexed at
 // run time, and a by-value / by-reference copy of the struct would be spilled to scratch (640 bytes per lane) for that.
 typedef const __attribute__((address_space(4))) ChainArgs chain_kernarg_t;
-
-// profiling stamps (chain mode, TPP_HIP_CHAIN_STAMPS, ABLATION BUILDS ONLY - in the shipped kernels this is empty: each stamp was a
-// scalar load of p.stamps + a wait + a branch on the path of MFMA wave 0 and of the polling loader, five and three times per layer):
-// slot of (workgroup, layer): 0 layer start, 1 chunk 0 published, 2 K loop done, 3 tile stores issued, 4 stores drained + S1 (MFMA
-// wave 0); 5 A loader starts waiting, 6 producers have arrived, 7 first chunks requested
-__device__ __forceinline__ void blw_stamp(chain_kernarg_t &p, int layer, int slot, int lane) {
-#ifdef TPP_HIP_ABLATION
-  if (p.stamps && lane == 0) p.stamps[((size_t)blockIdx.x * CH_MAXL + layer) * 8 + slot] = __builtin_amdgcn_s_memrealtime();
-#endif
-}
-
-// Per-chunk stamps of the LOADER waves (ablation builds, TPP_HIP_CHAIN_DBG & 1024, chain launches; the first 16 workgroups): shader-clock
-// stamps (s_memtime) at three points of every steady-state iteration - the chunk awaited has landed / the barrier has released /
-// the next chunk's DMA instructions are issued - buffered in LDS behind the ring (a VMEM store would count in the loaders' vmcnt
-// bookkeeping) and copied to p.stamps behind the per-layer stamps when the wave ends. A stamp is REQUESTED at its point and
-// collected at the next one (s_memtime returns through lgkmcnt, ~70 cycles: waiting for it on the spot stretched the
-// 4096-row chain from 28.9 to 38.3 us; collected late the three stamps cost a few issue slots). The MFMA waves are not
-// stamped: s_memtime shares lgkmcnt with their fragment reads. landed -> released = how long the loader waited for the
-// slowest wave at the barrier; issued(t-1) -> landed(t) = how long it waited for its own DMA. tools/stamps_report.py --chunks.
-// dbg & 2048 (ablation builds): the loaders' DMA instructions are ISSUED with every lane switched off - no memory traffic, no LDS
-// write, but the same instruction stream on the SIMD: what of the DMA's cost to the MFMA waves is issue-side
-#ifdef TPP_HIP_ABLATION
-#define BLW_DBG_EXEC_OFF() do { if (dbg & 2048) asm volatile("s_mov_b64 exec, 0" ::: "memory"); } while (0)
-#define BLW_DBG_EXEC_ON() do { if (dbg & 2048) asm volatile("s_mov_b64 exec, -1" ::: "memory"); } while (0)
-#else
-#define BLW_DBG_EXEC_OFF() ((void)0)
-#define BLW_DBG_EXEC_ON() ((void)0)
-#endif
-#ifdef TPP_BLW_SKIP_BARRIER
-#define BLW_MID_BARRIER() ((void)0) // (timing side build: see brgemm_bf16_lw's skip switches)
-#else
-#define BLW_MID_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
-constexpr int BLW_CS_ENTRIES = 64; // (layer, chunk) records per loader wave
-struct BlwChunkStamps {
-  unsigned long long pend = 0; // (an SGPR pair: the s_memtime in flight)
-  int pend_off = -1;           // LDS byte offset it belongs to
-  __device__ __forceinline__ void collect(unsigned char *smem, int lane) {
-#ifdef TPP_HIP_ABLATION
-    if (pend_off >= 0) {
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(pend)::"memory");
-      if (lane == 0) *(unsigned long long *)(smem + pend_off) = pend;
-      pend_off = -1;
-    }
-#endif
-  }
-  __device__ __forceinline__ void stamp(unsigned char *smem, int area, int which, int idx, int k, int lane) {
-#ifdef TPP_HIP_ABLATION
-    if (area >= 0) {
-      collect(smem, lane);
-      if (idx < BLW_CS_ENTRIES) {
-        pend_off = area + ((which * BLW_CS_ENTRIES + idx) * 3 + k) * 8;
-        asm volatile("s_memtime %0" : "=s"(pend)::"memory");
-      }
-    }
-#endif
-  }
-};
 
 // s_waitcnt vmcnt(younger * PPL): this wave's DMA of all but the `younger` most recent chunks has landed
 template <int PPL> __device__ __forceinline__ void blw_wait_younger(int younger) {
@@ -153,17 +92,6 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   [[maybe_unused]] constexpr int RPI = 256 / BN;     // VNNI pair-rows per B instruction
   static_assert(PPC >= 1 && (IS_A ? BM / 8 : BN / 8) % NL == 0 && (!IS_A || NL == 1 || NL % 2 == 0), "panel instructions divide over the loader waves");
   static_assert(NSLOT >= 3 && NSLOT_C % SUP == 0 && (NSLOT - 1) * PPL <= 63, "ring depth / vmcnt is 6 bits");
-#ifdef TPP_HIP_ABLATION
-  const int dbg = p.dbg;
-#else
-  constexpr int dbg = 0; // the timing switches exist in ablation builds only (chain_args.h)
-#endif
-  const bool no_dma = (dbg & (16 | (IS_A ? 128 : 64))) != 0; // timing experiments: this panel is not fetched
-  // per-chunk stamps (see BlwChunkStamps): LDS area behind the ring, this wave's row = 0 (A loader 0) / 1 (B loader 0)
-  const int cs_area = ((dbg & 1024) && MULTI && part == 0 && blockIdx.x < 16 && p.stamps) ? NSLOT_C * SLOT + (WK > 1 ? (BM / 32) * (BN / 32) * 4096 : 0) : -1;
-  constexpr int cs_which = IS_A ? 0 : 1;
-  int cs_idx = 0;
-  BlwChunkStamps cs;
   bool ahead = false;
   if (MULTI && !IS_A) {
     ahead = true;
@@ -195,7 +123,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       vo0 = rowoff_ + (unsigned)(((lane & 7) ^ (4 * (part & 1) + (lane >> 4))) << 4);                                  \
       vo1 = NL == 1 ? rowoff_ + (unsigned)(((lane & 7) ^ (4 + (lane >> 4))) << 4) : vo0;                               \
       step = (unsigned)(NL * 8 * (int)lda_ * 2);                                                                       \
-      sc1 = MULTI && (l) > 0 && !(dbg & 1); /* written by other workgroups in THIS launch: sc1 loads (L1 bypassed) */  \
+      sc1 = MULTI && (l) > 0; /* written by other workgroups in THIS launch: sc1 loads (L1 bypassed) */              \
     } else if (FB == 2) {                                                                                              \
       /* FLAT B ([k][ldb]), image = the chunk's 64 rows as they are, for the transpose reads of the MFMA waves: instruction v */ \
       /* covers rows (512/BN)*v ..: lane -> row lane / (BN/8), 16-byte piece lane % (BN/8); the 64-byte blocks of a row are */ \
@@ -239,9 +167,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
     _Pragma("unroll") for (int sub_ = 0; sub_ < SUP; ++sub_) {                                                         \
       unsigned char *base_ = smem + ((slot) * SUP + sub_) * SLOT + (IS_A ? 0 : A_SLOT) + part * 1024;                  \
       const __amdgpu_buffer_rsrc_t r_ = __builtin_amdgcn_make_buffer_rsrc((void *)g, 0, 0x7fffffff, 0x00020000);       \
-      BLW_DBG_EXEC_OFF();                                                                                              \
-      if (no_dma) {                                                                                                    \
-      } else if (IS_A && sc1) {                                                                                        \
+      if (IS_A && sc1) {                                                                                               \
         _Pragma("unroll") for (int v = 0; v < PPC; ++v)                                                                \
             __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (lds_void_b *)(base_ + v * NL * 1024), 16, (v & 1) ? vo1 : vo0, v * step, 0, 16); \
       } else {                                                                                                         \
@@ -249,7 +175,6 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
             __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (lds_void_b *)(base_ + v * NL * 1024), 16, (v & 1) ? vo1 : vo0,   \
                                                      v * step + ((GRP == 2 && IS_A && v >= 8) ? q_delta : 0u), 0, 0);      \
       }                                                                                                                \
-      BLW_DBG_EXEC_ON();                                                                                               \
       if (flat) { /* the batch elements continue each other (whole-layer dispatches): one 64-bit add */               \
         g += d_in;                                                                                                     \
       } else if (++kc == kchunks) {                                                                                    \
@@ -271,8 +196,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       pre = 0;
       slot = s0;
     }
-    if (poller) blw_stamp(p, lc, 5, lane);
-    if (poller && lc > 0 && !(dbg & 2)) {
+    if (poller && lc > 0) {
       // every producer tile of row block tm of layer lc-1 has been stored (write-through) and drained
       g_u32_lw *c = (g_u32_lw *)(p.cnt + ((size_t)(lc - 1) * p.tiles_m + tm) * CHAIN_CNT_STRIDE);
       const unsigned target = p.target;
@@ -288,18 +212,16 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       }
       asm volatile("" ::: "memory");
     }
-    if (poller) blw_stamp(p, lc, 6, lane);
     if (MULTI && NLA > 1 && lc > 0) __builtin_amdgcn_s_barrier(); // S2: the polling wave has seen the producers arrive
     // Prologue. (Filling the ring two chunks per barrier - a ramp through the first iterations - was measured: chunk 0 is ready
     // 0.4 us earlier, the 16-chunk loop of the 32x64 tile takes 1.0 us longer: the loader is the pace-maker and the ramp costs it
     // a second ISSUE and a variable wait per iteration. So: one burst, but behind the barrier that publishes chunk 0.)
     const int npro = T < NSLOT - 1 ? T : NSLOT - 1;
     // chunks 0 and 1 first, chunk 0 PUBLISHED as soon as it has landed, the rest of the prologue behind the barrier (the MFMA
-    // waves work on chunk 0 while it is issued; dbg & 256: everything before the barrier, for A/B runs)
-    const int nfirst = (dbg & 256) ? npro : (npro < 2 ? npro : 2);
+    // waves work on chunk 0 while it is issued)
+    const int nfirst = npro < 2 ? npro : 2;
     int c = pre;
     for (; c < nfirst; ++c) BLW_ISSUE(slot);
-    if (poller) blw_stamp(p, lc, 7, lane);
     blw_wait_younger<PPL>((c > nfirst ? c : nfirst) - 1);
     __builtin_amdgcn_s_barrier(); // P: chunk 0 of this layer published
     for (; c < npro; ++c) BLW_ISSUE(slot);
@@ -308,40 +230,24 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
     // mid-chunk barrier of chunk t) publishes it and retires the slot of chunk t-1, which takes chunk t + NSLOT - 1
     for (; t + NSLOT - 1 < T; ++t) {
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSLOT - 3) * PPL) : "memory");
-      cs.stamp(smem, cs_area, cs_which, cs_idx, 0, lane);
-      BLW_MID_BARRIER();
-      cs.stamp(smem, cs_area, cs_which, cs_idx, 1, lane);
+      __builtin_amdgcn_s_barrier();
       BLW_ISSUE(slot);
-      cs.stamp(smem, cs_area, cs_which, cs_idx, 2, lane);
-      ++cs_idx;
     }
     // the last NSLOT - 2 barriers of the layer: nothing of THIS layer is left to request
     if (MULTI && ahead && lc + 1 < L) {
       BLW_LOAD_STATE(lc + 1); // (the slot rotation carries over into the next layer)
       for (; t + 1 < T; ++t) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSLOT - 3) * PPL) : "memory");
-        BLW_MID_BARRIER();
+        __builtin_amdgcn_s_barrier();
         BLW_ISSUE(slot);
       }
     } else {
       for (; t + 1 < T; ++t) {
         blw_wait_younger<PPL>(T - 2 - t);
-        BLW_MID_BARRIER();
+        __builtin_amdgcn_s_barrier();
       }
     }
-    if (lc + 1 == L) {
-#ifdef TPP_HIP_ABLATION
-      cs.collect(smem, lane);
-      if (cs_area >= 0 && lane == 0) { // copy this wave's records out: [workgroup < 16][A, B][entry][3] behind the per-layer stamps
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        unsigned long long *dst = p.stamps + (size_t)p.tiles_m * p.tiles_n * CH_MAXL * 8 + ((size_t)blockIdx.x * 2 + cs_which) * (BLW_CS_ENTRIES * 3 + 1);
-        dst[0] = (unsigned long long)cs_idx;
-        const unsigned long long *src = (const unsigned long long *)(smem + cs_area) + cs_which * BLW_CS_ENTRIES * 3;
-        for (int i = 0; i < BLW_CS_ENTRIES * 3; ++i) dst[1 + i] = i < cs_idx * 3 ? src[i] : 0ull;
-      }
-#endif
-      return;
-    }
+    if (lc + 1 == L) return;
     if constexpr (WK > 1) __builtin_amdgcn_s_barrier(); // R1 (K groups combine)
     __builtin_amdgcn_s_barrier();                        // S1 (tile stored and drained)
     s0 = (s0 + T) % NSLOT;
@@ -449,13 +355,6 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
     tm = b / p.tiles_n;
     tn = b - tm * p.tiles_n;
   }
-#ifdef TPP_HIP_ABLATION
-  // timing experiment (dbg & 512): every workgroup LOADS the panels of tile (0, 0) - 100 % L2 hits after the first touch, no fabric
-  // traffic - and stores its own tile: what the K loop costs when no byte comes from beyond the L2
-  const bool alias_ = (p.dbg & 512) != 0;
-  const int m0 = tm * BM, n0 = tn * BN, m0_ld = alias_ ? 0 : m0, n0_ld = alias_ ? 0 : n0;
-  [[maybe_unused]] constexpr int skip_cols = 0; // (timing builds: no ragged items)
-#else
   // RAGGED n of grouped items (round 6: the reference's --tiles=64,48,64 rows): an item whose n is not a multiple of the tile's width
   // gets ceil(n / BN) column tiles, the LAST one moved left to end at column n - it recomputes the columns it shares with its
   // neighbour (panels in bounds, no masking of loads) and stores only its own (skip_cols: the first columns of its tile are the
@@ -463,14 +362,12 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   const int m0 = tm * BM;
   const int n0 = (GRP == 1 && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
   [[maybe_unused]] const int skip_cols = tn * BN - n0;
-  const int m0_ld = m0, n0_ld = n0;
-#endif
   const int L = MULTI ? p.nlayers : 1;
 
   if (wave >= NMW) {
     // ---- loader waves (blw_loader above) ---------------------------------------------------------------------------
-    if (wave < NMW + NLA) blw_loader<true, NLA, NLA, NSLOT, SUP, BM, BN, WK, MULTI, 0, GRP>(pp, smem_c, lane, m0_ld, n0_ld, tm, L, wave - NMW, it_A, it_B, it_br, q_da);
-    else blw_loader<false, NLB, NLA, NSLOT, SUP, BM, BN, WK, MULTI, FLATB, GRP>(pp, smem_c, lane, m0_ld, n0_ld, tm, L, wave - NMW - NLA, it_A, it_B, it_br, q_db);
+    if (wave < NMW + NLA) blw_loader<true, NLA, NLA, NSLOT, SUP, BM, BN, WK, MULTI, 0, GRP>(pp, smem_c, lane, m0, n0, tm, L, wave - NMW, it_A, it_B, it_br, q_da);
+    else blw_loader<false, NLB, NLA, NSLOT, SUP, BM, BN, WK, MULTI, FLATB, GRP>(pp, smem_c, lane, m0, n0, tm, L, wave - NMW - NLA, it_A, it_B, it_br, q_db);
     return; // ended waves do not take part in later barriers
   }
 
@@ -537,29 +434,6 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
       }
     }
   };
-#ifdef TPP_HIP_ABLATION
-  const int dbg = p.dbg;
-#else
-  constexpr int dbg = 0; // the timing switches exist in ablation builds only (chain_args.h)
-#endif
-  // Timing experiment "no fragment reads / MFMAs" (dbg & 32) is a COMPILE-TIME switch (-DTPP_BLW_SKIP_MATH): as a run-time branch
-  // around every group of reads and MFMAs it split the chunk body into basic blocks, the compiler's wait-count insertion lost track
-  // of which LDS reads were outstanding across them and put s_waitcnt lgkmcnt(0..2) in front of the MFMAs - each k-step waited for
-  // the fragment reads issued just before it (274 cycles per k-step of 128 cycles of MFMA on the 128x128 tile).
-#ifdef TPP_BLW_SKIP_MATH
-  const bool skip_math = (dbg & 32) != 0;
-#else
-  constexpr bool skip_math = false;
-  (void)dbg;
-#endif
-  // two more compile-time timing switches (side builds only, results WRONG by design): -DTPP_BLW_SKIP_READS = the MFMAs run on
-  // whatever the fragment registers hold (no LDS reads in the K loop), -DTPP_BLW_SKIP_BARRIER = no mid-chunk barrier in any wave
-  // (with TPP_HIP_CHAIN_DBG=16, no DMA: what the MFMA side alone costs per chunk, and what of it is the barrier / the reads)
-#ifdef TPP_BLW_SKIP_READS
-  constexpr bool skip_reads = true;
-#else
-  constexpr bool skip_reads = false;
-#endif
   // One chunk in ring slot `slot` (a run-time value: ONE body - two for the tiles that alternate fragment sets - instead of one per
   // ring slot entered through a switch; the slot's LDS offset costs TM + TN vector adds per k-step. The per-slot bodies with their
   // exit after every chunk made hipcc rename the accumulators from body to body - v_mfma D != C - in the chain and flat-B
@@ -581,41 +455,38 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
     constexpr int CUR = FULLPF ? PAR * KS : 0, NXT = FULLPF ? (PAR ^ 1) * KS : 0; // fragment sets of chunk t / t+1
 #pragma unroll
     for (int q = 0; q < KS; ++q) {
-      if (!skip_math && !skip_reads) {
-        if constexpr (FULLPF && SUP == 2) {
-          // two chunks per barrier: everything up to the end of chunk t+1 was published before chunk t began (the odd chunk with
-          // its pair, the next even one by the barrier in the middle of the even chunk before it) and the step after the barrier
-          // may read one chunk further. So the fragments are read ONE k-step per step, BLW_RD steps ahead of their MFMA, through
-          // the 2 * KS buffers as a ring: the LDS pipe works all the time instead of in the second halves of the chunks, and the
-          // wait in front of an MFMA is for reads issued three MFMAs earlier (3 * BLW_RD + 3 reads in flight: lgkmcnt has 4 bits).
-          const int tg = q + BLW_RD, ch = tg / KS;
-          const int nns = ns + 1 == NSLOT ? 0 : ns + 1;
-          frag_load((PAR * KS + tg) % NFB, ch == 0 ? slot : ch == 1 ? ns : nns, wk * KS + tg % KS);
-        } else if constexpr (FULLPF) {
-          // second half of the chunk (chunk t+1 is published): two of its k-steps per step
-          if (q >= KS / 2) {
-            const int r = 2 * (q - KS / 2);
-            frag_load(NXT + r, ns, wk * KS + r);
-            if (r + 1 < KS) frag_load(NXT + r + 1, ns, wk * KS + r + 1);
-          }
-        } else {
-          if (q + PD < KS) frag_load(q + PD, slot, wk * KS + q + PD);
-          else frag_load(q + PD - KS, ns, wk * KS + q + PD - KS);
+      if constexpr (FULLPF && SUP == 2) {
+        // two chunks per barrier: everything up to the end of chunk t+1 was published before chunk t began (the odd chunk with
+        // its pair, the next even one by the barrier in the middle of the even chunk before it) and the step after the barrier
+        // may read one chunk further. So the fragments are read ONE k-step per step, BLW_RD steps ahead of their MFMA, through
+        // the 2 * KS buffers as a ring: the LDS pipe works all the time instead of in the second halves of the chunks, and the
+        // wait in front of an MFMA is for reads issued three MFMAs earlier (3 * BLW_RD + 3 reads in flight: lgkmcnt has 4 bits).
+        const int tg = q + BLW_RD, ch = tg / KS;
+        const int nns = ns + 1 == NSLOT ? 0 : ns + 1;
+        frag_load((PAR * KS + tg) % NFB, ch == 0 ? slot : ch == 1 ? ns : nns, wk * KS + tg % KS);
+      } else if constexpr (FULLPF) {
+        // second half of the chunk (chunk t+1 is published): two of its k-steps per step
+        if (q >= KS / 2) {
+          const int r = 2 * (q - KS / 2);
+          frag_load(NXT + r, ns, wk * KS + r);
+          if (r + 1 < KS) frag_load(NXT + r + 1, ns, wk * KS + r + 1);
         }
+      } else {
+        if (q + PD < KS) frag_load(q + PD, slot, wk * KS + q + PD);
+        else frag_load(q + PD - KS, ns, wk * KS + q + PD - KS);
       }
       // The step's fragment reads (for MFMAs two steps / half a chunk ahead) are dealt BETWEEN the step's MFMAs, not in front of them:
       // a 32x32x16 bf16 MFMA holds the matrix pipe for 32 cycles, six DS instructions take the wave longer than that to issue - in
       // front of the MFMAs the pipe ran dry once per k-step (same-box A/B, profiles/r04_bf16_lw_read_interleave.txt: the 4096-row
       // layer 10.02 -> 9.45 us, its chain 30.5 -> 29.4, C5 17.6 -> 17.0, 4096^3 on this tile 128.2 -> 122.3).
-      constexpr bool IL = TPP_BLW_INTERLEAVE >= 1 && (!FULLPF || (TPP_BLW_INTERLEAVE >= 2 && SUP == 1 && TM * TN >= 2));
+      // Interleaved: the four-accumulator tile (128x128) and 64x128; the others read in front of the MFMAs.
+      constexpr bool IL = !FULLPF || (SUP == 1 && TM * TN >= 2);
       if constexpr (!IL) __builtin_amdgcn_sched_barrier(0);
-      if (!skip_math) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+      for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_lw, bw[CUR + q][j]), af[CUR + q][i], acc[i][j], 0, 0, 0);
-      }
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_lw, bw[CUR + q][j]), af[CUR + q][i], acc[i][j], 0, 0, 0);
       if constexpr (IL && !FULLPF) {
         constexpr int NRD = TM + (FLATB == 4 ? TN : 2 * TN); // DS read instructions of a step (VNNI-4: one ds_read2_b64 per column tile)
         constexpr int PER = (NRD + TM * TN - 2) / (TM * TN - 1);
@@ -635,12 +506,10 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-#ifndef TPP_BLW_SKIP_BARRIER
       if (q == KS / 2 - 1 && has_next) {
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
       }
-#endif
     }
   };
   using P0 = std::integral_constant<int, 0>;
@@ -668,11 +537,9 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
         biasw[j][g] = u32x2_lw{0u, 0u};
         if (ep & EP_BIAS) biasw[j][g] = *(const u32x2_lw *)((const unsigned short *)(GRP ? it_D : Y.D) + n0 + ((GRP == 2 ? 0 : wn * TN) + j) * 32 + 8 * g + 4 * lh);
       }
-    if (MULTI && wave == 0) blw_stamp(p, l, 0, lane);
     if (MULTI && NLA > 1 && l > 0) __builtin_amdgcn_s_barrier(); // S2 (the loaders' rendezvous after the seam wait)
     __builtin_amdgcn_s_barrier(); // P: chunk 0 published
     __builtin_amdgcn_sched_barrier(0);
-    if (MULTI && wave == 0) blw_stamp(p, l, 1, lane);
     // (T >= 1: the launchers send empty batches to the generic kernel - a branch around this loop costs the 128-wide tiles
     // a second copy of the accumulators and 250 spilled registers)
     // the layers follow each other through the ring: this one starts at slot s0 (the loaders count the same way)
@@ -754,7 +621,6 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
       for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(bw[s][j]));
     }
 
-    if (MULTI && wave == 0) blw_stamp(p, l, 2, lane);
     // ---- epilogue ------------------------------------------------------------------------------------------------
     if constexpr (WK > 1) {
       // K group 1 parks its 32x32 partial, group 0 adds it (group order: 0 + 1) and finishes the tile
@@ -840,12 +706,11 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
           const u32x4 v = *(const u32x4 *)(ot + row * ES + ch * 16);
           const unsigned voff = (unsigned)(32 * i + row) * ldcb + (unsigned)(ch * 16);
           if (GRP == 1 && ch * 8 < skip_cols) continue; // (a ragged item's last column tile: these columns are the neighbour tile's)
-          if (MULTI && l + 1 < L && !(dbg & 4)) __builtin_amdgcn_raw_buffer_store_b128(v, rsrcC, voff, 0, 16); // sc1: write-through (hand-off)
+          if (MULTI && l + 1 < L) __builtin_amdgcn_raw_buffer_store_b128(v, rsrcC, voff, 0, 16); // sc1: write-through (hand-off)
           else __builtin_amdgcn_raw_buffer_store_b128(v, rsrcC, voff, 0, C_STORE_AUX); // (last layer / single layer: gemm_common.h)
         }
       }
     }
-    if (MULTI && wave == 0) blw_stamp(p, l, 3, lane);
     if (l + 1 == L) break;
     if constexpr (MULTI) {
       // ---- seam: publish this tile to the row block's consumers ------------------------------------------------
@@ -854,7 +719,6 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
       if (wave == 0 && lane == 0)
         __hip_atomic_fetch_add((g_u32_lw *)(p.cnt + ((size_t)l * p.tiles_m + tm) * CHAIN_CNT_STRIDE), 1u, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
-      if (wave == 0) blw_stamp(p, l, 4, lane);
     }
   }
 }
@@ -863,15 +727,10 @@ template <int WM, int WN, int WK, int TM, int TN, int NSLOT, int NLA, int NLB, i
 static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *items = nullptr, int n_items = 0) {
   constexpr int NOUT = WM * WN, BM = 32 * WM * TM, BN = 32 * WN * TN, NT = 64 * (WM * WN * WK + NLA + NLB);
   constexpr size_t lds = (size_t)NSLOT * (BM + BN) * 128 + (WK > 1 ? (size_t)NOUT * 4096 : 0);
-#ifdef TPP_HIP_ABLATION
-  constexpr size_t lds_alloc = lds + (lds + 4096 <= 160 * 1024 ? 4096 : 0); // room for the loaders' per-chunk stamps (BlwChunkStamps)
-#else
-  constexpr size_t lds_alloc = lds;
-#endif
   static_assert(lds <= 160 * 1024, "LDS budget");
   auto kern = brgemm_bf16_lw<WM, WN, WK, TM, TN, NSLOT, NLA, NLB, SUP, MULTI, FLATB, GRP>;
   static std::atomic<unsigned long long> lds_set{0};
-  if (hipError_t e = ensure_dynamic_lds((const void *)kern, (int)lds_alloc, lds_set); e != hipSuccess) return e;
+  if (hipError_t e = ensure_dynamic_lds((const void *)kern, (int)lds, lds_set); e != hipSuccess) return e;
   ChainArgs args = a;
   args.tiles_m = a.m / BM;
   args.tiles_n = GRP == 1 ? (a.n + BN - 1) / BN : a.n / BN; // (grouped items: a ragged last column tile, see the kernel)
@@ -886,26 +745,22 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
     args.items = items;
     args.item_subs = (int)tiles;
     args.xm = 0;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * n_items)), dim3(NT), lds_alloc, s, args);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * n_items)), dim3(NT), lds, s, args);
     return hipGetLastError();
   }
   // XCD grid xm x (8 / xm) over the tile grid: minimise xn * m + xm * n (bytes of A and W all eight L2s fetch, in units of 2K)
   args.xm = 0;
-  static const int forced_xm = [] {
-    const char *e = getenv("TPP_HIP_BF16_LW_XM"); // A/B runs: 1, 2, 4, 8, or 0 = linear mapping
-    return e ? atoi(e) : -1;
-  }();
   long long best = -1;
   for (int xm = 8; xm >= 1; xm >>= 1) {
     const int xn = 8 / xm;
     if (args.tiles_m % xm || args.tiles_n % xn) continue;
     const long long cost = (long long)xn * a.m + (long long)xm * a.n;
-    if (forced_xm >= 0 ? xm == forced_xm : (best < 0 || cost < best)) {
+    if (best < 0 || cost < best) {
       best = cost;
       args.xm = xm;
     }
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(NT), lds_alloc, s, args);
+  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(NT), lds, s, args);
   return hipGetLastError();
 }
 
@@ -918,26 +773,10 @@ void blw_tile_dims(int tile, int *bm, int *bn) {
 
 // Loader waves per tile (NLA + NLB), same-box A/B (profiles/r03_blw_loader_split.txt): 32x64 1 + 2 (1 + 1: +2 %, 2 + 2: +5 %),
 // 64x64 1 + 1 (1 + 2: +2 %, 2 + 2: +7 %), 64x128 1 + 2 (1 + 1: same, 2 + 4: +5 %), 128x128 1 + 1 (2 + 2, 1 + 2: same).
-// SUP = 2 (one workgroup barrier per TWO chunks) for the 32x64 and 64x64 tiles when every layer has an even chunk count
-// (TPP_HIP_BLW_SUP=1 forces one chunk per barrier for A/B runs). Ring depths: 8 / 8 / 6 / 4 slots; a 5-slot ring with 2 + 2
-// loaders for the 128x128 tile and 4 against 6 slots for 64x128 measured the same (same box, +-0.5 %); FOUR chunks per barrier on
-// a 12-slot ring for the 32x64 tile measured 9 % slower than two on 8 slots (the prologue must request 8 chunks before the first barrier).
-// side builds only (-DTPP_HIP_ABLATION): TPP_HIP_BLW_T3 = 1: the 128x128 tile with a 5-slot ring and two loader waves per panel,
-// 2: 4 slots, two loader waves per panel (timing experiments on the fill loop; the product has ONE instance of the tile)
-#ifdef TPP_HIP_ABLATION
-static int blw_t3_alt() {
-  static const int v = [] {
-    const char *e = getenv("TPP_HIP_BLW_T3");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-#define BLW_T3_ALTS(MULTI, FB)                                                                 \
-  if (blw_t3_alt() == 1) return launch_blw_t<2, 2, 1, 2, 2, 5, 2, 2, 1, MULTI, FB>(a, s);      \
-  if (blw_t3_alt() == 2) return launch_blw_t<2, 2, 1, 2, 2, 4, 2, 2, 1, MULTI, FB>(a, s);
-#else
-#define BLW_T3_ALTS(MULTI, FB)
-#endif
+// SUP = 2 (one workgroup barrier per TWO chunks) for the 32x64 and 64x64 tiles when every layer has an even chunk count.
+// Ring depths: 8 / 8 / 6 / 4 slots; a 5-slot ring with 2 + 2 loaders for the 128x128 tile and 4 against 6 slots for 64x128
+// measured the same (same box, +-0.5 %); FOUR chunks per barrier on a 12-slot ring for the 32x64 tile measured 9 % slower than
+// two on 8 slots (the prologue must request 8 chunks before the first barrier).
 #define BLW_DISPATCH(MULTI, FB)                                                              \
   switch (tile * 2 + (sup2 ? 1 : 0)) {                                                       \
   case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, MULTI, FB>(a, s);                   \
@@ -947,15 +786,10 @@ static int blw_t3_alt() {
   case 4:                                                                                    \
   case 5: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, MULTI, FB>(a, s);                   \
   case 6:                                                                                    \
-  case 7: BLW_T3_ALTS(MULTI, FB) return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, MULTI, FB>(a, s); \
+  case 7: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, MULTI, FB>(a, s);                   \
   default: return hipErrorInvalidValue;                                                      \
   }
 static bool blw_sup2(const ChainArgs &a) {
-  static const int forced = [] {
-    const char *e = getenv("TPP_HIP_BLW_SUP");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced == 1) return false;
   for (int l = 0; l < a.nlayers; ++l)
     if ((a.L[l].br * (a.L[l].k / BLW_BK)) & 1) return false;
   return true;
@@ -1004,27 +838,18 @@ hipError_t launch_bf16_lw_vnni4(int tile, const ChainArgs &a, hipStream_t s) {
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s) {
   if (a.L[0].k < BLW_BK || a.L[0].k % BLW_BK || tile < 0 || (tile > 1 && tile != 4) || (b_kind != 0 && b_kind != 4)) return hipErrorInvalidValue;
   if (tile == 4) { // 32x32 + K2 (launch_bf16_lw's tile 4): four workgroups per 64x64 item - skinny groups with a long reduction
-    static const int forced4 = [] {
-      const char *e = getenv("TPP_HIP_BLW_SUP");
-      return e ? atoi(e) : 0;
-    }();
     if (b_kind == 4) // (VNNI-4 operands: grouped form only - the image rows of a 32-column tile are 256 bytes, four per DMA instruction)
-      return even_chunks && forced4 != 1 ? launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 2, false, 4, true>(a, s, items, n_items)
-                                         : launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 1, false, 4, true>(a, s, items, n_items);
-    return even_chunks && forced4 != 1 ? launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 2, false, 0, true>(a, s, items, n_items)
-                                       : launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 1, false, 0, true>(a, s, items, n_items);
+      return even_chunks ? launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 2, false, 4, true>(a, s, items, n_items)
+                         : launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 1, false, 4, true>(a, s, items, n_items);
+    return even_chunks ? launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 2, false, 0, true>(a, s, items, n_items)
+                       : launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 1, false, 0, true>(a, s, items, n_items);
   }
-  static const int forced = [] {
-    const char *e = getenv("TPP_HIP_BLW_SUP");
-    return e ? atoi(e) : 0;
-  }();
-  const bool sup2 = even_chunks && forced != 1;
   if (b_kind == 4) {
-    if (tile == 0) return sup2 ? launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 2, false, 4, true>(a, s, items, n_items) : launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, 4, true>(a, s, items, n_items);
-    return sup2 ? launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 2, false, 4, true>(a, s, items, n_items) : launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, 4, true>(a, s, items, n_items);
+    if (tile == 0) return even_chunks ? launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 2, false, 4, true>(a, s, items, n_items) : launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, 4, true>(a, s, items, n_items);
+    return even_chunks ? launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 2, false, 4, true>(a, s, items, n_items) : launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, 4, true>(a, s, items, n_items);
   }
-  if (tile == 0) return sup2 ? launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 2, false, 0, true>(a, s, items, n_items) : launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, 0, true>(a, s, items, n_items);
-  return sup2 ? launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 2, false, 0, true>(a, s, items, n_items) : launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, 0, true>(a, s, items, n_items);
+  if (tile == 0) return even_chunks ? launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 2, false, 0, true>(a, s, items, n_items) : launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, 0, true>(a, s, items, n_items);
+  return even_chunks ? launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 2, false, 0, true>(a, s, items, n_items) : launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, 0, true>(a, s, items, n_items);
 }
 
 // QUADS (round 6): a group of 64x64 items that forms an R x C grid of item rows (A blocks) and item columns (B blocks), R and C even,

@@ -32,16 +32,6 @@
 
 namespace tpp {
 
-// Timing-only ablation switches for kernel work (tools/ablate.sh builds side libraries
-// with -DTPP_ABLATE=mask; the shipped library is always built with 0 = full kernel).
-#ifndef TPP_ABLATE
-#define TPP_ABLATE 0
-#endif
-#ifndef TPP_NACC
-#define TPP_NACC 1 // accumulator chains per wave: 1 measured +0.9 % on C2 over 2 (and it is the oracle's summation order: one chain)
-#endif
-constexpr int ABL_NO_GLOAD = 1, ABL_NO_SWRITE = 2, ABL_NO_BARRIER = 4, ABL_NO_FRAG = 8;
-
 constexpr int BK = 64;     // k columns per chunk
 constexpr int NSTAGE = 3;  // LDS ring slots
 constexpr int NSET = 3;    // staging register sets = chunks of global loads in flight per lane
@@ -65,7 +55,7 @@ static __device__ __forceinline__ void lds_dma_16B(const void *panel, unsigned l
 // items != nullptr: GROUPED mode (tile queue) - the grid is (items, tiles_n, tiles_m) and workgroup
 // (x, y, z) computes tile (z, y) of queued invoke x, whose operand pointers and batch count come from
 // items[x]; the descriptor fields (m, n, k, leading dimensions, strides, epilogue) are shared.
-template <int WM, int WN, int WK, int NACC, bool DMA>
+template <int WM, int WN, int WK, bool DMA>
 __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p, const WorkItem *__restrict__ items) {
   if (items) { // wave-uniform: overwrite the per-invoke fields of the (by-value) argument block
     const WorkItem it = items[blockIdx.x];
@@ -104,7 +94,8 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
   const int kchunks = p.k / BK;
   const int T = p.br * kchunks;
 
-  f32x16 acc[NACC]; // initialised after the first loads are on their way
+  // ONE accumulator chain per wave: measured +0.9 % on C2 over two, and it is the oracle's summation order
+  f32x16 acc; // initialised after the first loads are on their way
 
   // staging registers of the chunk in flight (HBM -> VGPR -> LDS). Pieces 0..LA-1 are
   // A, LA..LA+LB-1 are B (16 bytes per lane each). The LDS writes of a chunk are spread
@@ -199,18 +190,16 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
 #pragma unroll
     for (int q = 0; q < KB_PER_WAVE; ++q) {
       const int cur = q & 1, nxt = cur ^ 1;
-      if (!(TPP_ABLATE & ABL_NO_FRAG)) {
-        if (q + 1 < KB_PER_WAVE) frag_load(nxt, STAGE, kbw + q + 1);
-        else if (HAS_NEXT) frag_load(nxt, NSTG, kbw);
-      }
+      if (q + 1 < KB_PER_WAVE) frag_load(nxt, STAGE, kbw + q + 1);
+      else if (HAS_NEXT) frag_load(nxt, NSTG, kbw);
       // pin the issue order: the fragment reads of step q+1 stay ABOVE the MFMAs of
       // step q, and each piece of staging work sits in the shadow of one MFMA (the
       // wave is in-order: it idles at the next MFMA until the matrix pipe frees up).
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        acc[s % NACC] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][s], fb[cur][s], acc[s % NACC], 0, 0, 0);
-        if (!DMA && HAS_LOAD && !(TPP_ABLATE & ABL_NO_GLOAD) && q == 0 && s == 0) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][s], fb[cur][s], acc, 0, 0, 0);
+        if (!DMA && HAS_LOAD && q == 0 && s == 0) {
           // panel base of the next chunk to load: scalar work in the shadow of the MFMA above
           if (++kc == kchunks) {
             kc = 0;
@@ -223,13 +212,13 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
         }
 #pragma unroll
         for (int u = 0; u < NP; ++u) {
-          if (!DMA && HAS_NEXT && !(TPP_ABLATE & ABL_NO_SWRITE) && (u * WSLOTS) / NP == q * 4 + s) swrite_piece(NSTG, u);
-          if (HAS_LOAD && !(TPP_ABLATE & ABL_NO_GLOAD) && (u * 4 * (KB_PER_WAVE - KB_HALF)) / NP == (q - KB_HALF) * 4 + s) {
+          if (!DMA && HAS_NEXT && (u * WSLOTS) / NP == q * 4 + s) swrite_piece(NSTG, u);
+          if (HAS_LOAD && (u * 4 * (KB_PER_WAVE - KB_HALF)) / NP == (q - KB_HALF) * 4 + s) {
             if (DMA) dma_piece((STAGE + 2) % NSTAGE, u); // chunk t+2 into the slot chunk t-1 has left (after the barrier)
             else gload_piece(NSTG, u);
           }
         }
-        if (DMA && HAS_LOAD && !(TPP_ABLATE & ABL_NO_GLOAD) && q == KB_PER_WAVE - 1 && s == 3) {
+        if (DMA && HAS_LOAD && q == KB_PER_WAVE - 1 && s == 3) {
           if (++kc == kchunks) { // panel base of the chunk after the one just requested
             kc = 0;
             gA += dA_wrap;
@@ -241,7 +230,7 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (q == KB_HALF - 1 && !(TPP_ABLATE & ABL_NO_BARRIER)) {
+      if (q == KB_HALF - 1) {
         // DMA: this wave's pieces of chunk t+1 have landed in the LDS (the fence of __syncthreads
         // does not wait for LDS-DMA), then everybody's
         if (DMA && HAS_NEXT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -274,9 +263,7 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
   // accumulators: wk == 0 starts from C (beta = 1) so the chain is C + sum, as in
   // the reference; other K groups start from zero.
 #pragma unroll
-  for (int a = 0; a < NACC; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[a][r] = 0.0f;
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
   // C tile through buffer ops: wave-uniform tile base in the descriptor, per-lane offset
   // constant, the row of accumulator register r as a scalar offset -> one instruction per
   // register, no 64-bit vector address math in the epilogue.
@@ -288,7 +275,7 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
   if (!(p.ep & EP_BETA0) && wk == 0) {
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      acc[0][r] = __builtin_bit_cast(
+      acc[r] = __builtin_bit_cast(
           float, __builtin_amdgcn_raw_buffer_load_b32(rsrcC, voffC, (unsigned)((r & 3) + 8 * (r >> 2)) * ldcb, 0));
   }
 
@@ -330,16 +317,6 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
     if (t < T) tail(S2{});
   }
 
-  if (TPP_ABLATE & (ABL_NO_SWRITE | ABL_NO_FRAG)) { // keep ablated producers alive
-#pragma unroll
-    for (int u = 0; u < LA + LB; ++u) asm volatile("" ::"v"(rs[0][u]), "v"(rs[DMA ? 0 : 1][u]), "v"(rs[DMA ? 0 : 2][u]));
-    asm volatile("" ::"v"(fa[0]), "v"(fa[1]));
-  }
-#pragma unroll
-  for (int a = 1; a < NACC; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][r] += acc[a][r];
-
   if constexpr (WK > 1) {
     // combine the K groups through LDS: group g>0 parks its 32x32 partial, group 0 adds
     __syncthreads();
@@ -347,7 +324,7 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
     if (wk > 0) {
       float *dst = red + ((wk - 1) * (WM * WN) + wmn) * 1024 + lane;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) dst[r * 64] = acc[0][r];
+      for (int r = 0; r < 16; ++r) dst[r * 64] = acc[r];
     }
     __syncthreads();
     if (wk > 0) return;
@@ -355,14 +332,14 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
     for (int g = 1; g < WK; ++g) {
       const float *src = red + ((g - 1) * (WM * WN) + wmn) * 1024 + lane;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[0][r] += src[r * 64];
+      for (int r = 0; r < 16; ++r) acc[r] += src[r * 64];
     }
   }
 
   const float bias = (p.ep & EP_BIAS) ? ((const float *)p.D)[ccol] : 0.0f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    float v = acc[0][r] + bias;
+    float v = acc[r] + bias;
     if (p.ep & EP_RELU) v = v > 0.0f ? v : 0.0f;
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrcC, voffC,
                                           (unsigned)((r & 3) + 8 * (r >> 2)) * ldcb, C_STORE_AUX);
@@ -680,12 +657,12 @@ enum GemmVariant : int {
   V_BF16_LW4_128x128 = 31,
 };
 
-template <int WM, int WN, int WK, int NACC, bool DMA>
+template <int WM, int WN, int WK, bool DMA>
 static hipError_t launch_fast_t(const GemmArgs &a, hipStream_t s) {
   constexpr int BM = 32 * WM, BN = 32 * WN, NT = 64 * WM * WN * WK;
   constexpr size_t lds = (size_t)NSTAGE * (BM * BK + BK * BN) * sizeof(float);
   static std::atomic<unsigned long long> lds_set{0};
-  if (hipError_t e = ensure_dynamic_lds((const void *)brgemm_f32_fast<WM, WN, WK, NACC, DMA>, (int)lds, lds_set); e != hipSuccess) return e;
+  if (hipError_t e = ensure_dynamic_lds((const void *)brgemm_f32_fast<WM, WN, WK, DMA>, (int)lds, lds_set); e != hipSuccess) return e;
   GemmArgs args = a;
   const int tiles_m = a.m / BM, tiles_n = a.n / BN;
   dim3 grid;
@@ -698,27 +675,13 @@ static hipError_t launch_fast_t(const GemmArgs &a, hipStream_t s) {
     if (tiles_m > 65535 || tiles_n > 65535) return hipErrorInvalidValue;
     grid = dim3(1, tiles_n, tiles_m);
   }
-  hipLaunchKernelGGL((brgemm_f32_fast<WM, WN, WK, NACC, DMA>), grid, dim3(NT), lds, s, args, (const WorkItem *)nullptr);
+  hipLaunchKernelGGL((brgemm_f32_fast<WM, WN, WK, DMA>), grid, dim3(NT), lds, s, args, (const WorkItem *)nullptr);
   return hipGetLastError();
 }
 
-// grouped launch of a fast tile family: one workgroup per (item, tile of the item)
-template <int WM, int WN, int WK, int NACC, bool DMA>
-static hipError_t launch_fast_grouped_t(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s) {
-  constexpr int BM = 32 * WM, BN = 32 * WN, NT = 64 * WM * WN * WK;
-  constexpr size_t lds = (size_t)NSTAGE * (BM * BK + BK * BN) * sizeof(float);
-  static std::atomic<unsigned long long> lds_set{0};
-  if (hipError_t e = ensure_dynamic_lds((const void *)brgemm_f32_fast<WM, WN, WK, NACC, DMA>, (int)lds, lds_set); e != hipSuccess) return e;
-  GemmArgs args = a;
-  args.tiles_m = args.tiles_n = 0;
-  hipLaunchKernelGGL((brgemm_f32_fast<WM, WN, WK, NACC, DMA>), dim3((unsigned)n_items, a.n / BN, a.m / BM), dim3(NT), lds, s, args,
-                     items);
-  return hipGetLastError();
-}
-
-template <int WM, int WN, int WK, int NACC, bool DMA>
+template <int WM, int WN, int WK, bool DMA>
 static hipError_t launch_fast(const GemmArgs &a, hipStream_t s) {
-  return launch_fast_t<WM, WN, WK, NACC, DMA>(a, s);
+  return launch_fast_t<WM, WN, WK, DMA>(a, s);
 }
 
 hipError_t launch_gemm_bf16_fast(int tile, const GemmArgs &a, hipStream_t s); // brgemm_bf16.hip
@@ -822,39 +785,6 @@ static int choose_f32_split(int tile, long long tiles, long long chunks) {
   return saved > 2.7 + 0.8 ? (int)S : 1;
 }
 
-static bool lw16_on() {
-  static const bool on = [] {
-    const char *e = getenv("TPP_HIP_F32_LW16"); // A/B runs: 0 = never the 32x16 tiles
-    return !e || atoi(e) != 0;
-  }();
-  return on;
-}
-static int64_t bf16_long_k() {
-  static const int64_t v = [] {
-    const char *e = getenv("TPP_HIP_BF16_LONG_K"); // A/B runs: the reduction length from which small bf16 outputs leave the 32x32 K-split kernel
-    return e ? (int64_t)atoll(e) : (int64_t)1536;
-  }();
-  return v;
-}
-static bool bf16_lw32_on() {
-  static const bool on = [] {
-    const char *e = getenv("TPP_HIP_BF16_LW32"); // A/B runs: 0 = long-reduction bf16 layers stay on the 32x64 tile
-    return !e || atoi(e) != 0;
-  }();
-  return on;
-}
-static bool k32_pairs_on() {
-  static const bool on = [] {
-    const char *e = getenv("TPP_HIP_GROUPED_K32_PAIRS"); // A/B runs: 0 = 32-k tiles on the generic grouped kernel, as before round 4
-#ifdef TPP_GROUPED_FAST
-    (void)e;
-    return false;
-#else
-    return !e || atoi(e) != 0;
-#endif
-  }();
-  return on;
-}
 // name of the kernel family of the most recent grouped GEMM launch (xsmm_hip_last_grouped_kernel: tests and tools/tpp_replay
 // report which kernel a tile-queue group ran on - the descriptor's own name is what a SINGLE invoke would run on)
 static std::atomic<const char *> g_last_grouped{""};
@@ -892,7 +822,7 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
   // workgroup per CU over the whole work list (the same rule as pick_f32_variant)
   // ... and 32-k tiles (--tiles=32,32,32, the reference's MLP benchmark) when every batch count is even: the loader waves build a
   // 64-k chunk from the blocks of two batch elements (brgemm_f32_lw.hip, pair mode)
-  const bool k_pairs = k32_pairs_on() && d.k == 32 && pair_ok && d.stride_a >= 0 && d.stride_b >= 0 && d.stride_a < (1 << 26) && d.stride_b < (1 << 26);
+  const bool k_pairs = d.k == 32 && pair_ok && d.stride_a >= 0 && d.stride_b >= 0 && d.stride_a < (1 << 26) && d.stride_b < (1 << 26);
   // (n that is not a multiple of 32 - the reference's --tiles=64,48,64 / 32,48,32 configs: the last 32-column tile of an item is
   // ragged, the loader-wave kernels clamp its loads and mask its stores; needs the 16-byte output pieces of out_ok and ldc % 4)
   // skinny groups - at most one 32x16 tile per CU over the whole work list: the half-width tiles (brgemm_f32_lw16.hip), every CU a
@@ -904,7 +834,7 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
     const int64_t t16 = (d.m % 32 == 0 && d.n % 16 == 0) ? n_dec * (d.m / 32) * (d.n / 16) : 0;
     const bool k_ok = (d.k % BK == 0 && d.k > 0) || (k_pairs && d.n % 32 != 0);
     static const char *const l16_names[1][2] = {{"brgemm_f32_lw16<32x16,k4> grouped", "brgemm_f32_lw16<32x16,k4> grouped, 32-k pairs"}};
-    if (vec && out_ok && lw16_on() && !d.generic_forced && t16 > 0 && t16 <= g_num_cus && k_ok && d.ldc % 4 == 0 && n_items <= 65535 && d.lda < (1 << 22) &&
+    if (vec && out_ok && !d.generic_forced && t16 > 0 && t16 <= g_num_cus && k_ok && d.ldc % 4 == 0 && n_items <= 65535 && d.lda < (1 << 22) &&
         d.ldb < (1 << 22) && d.ldc < (1 << 22) && (!d.bias || out_ok) &&
         !((d.k == 32 ? br_hint / 2 : br_hint * (d.k / BK)) >= 48 && d.n % 32 == 0 && d.k % BK == 0)) // (long reductions: the split 32x32 tiles below, as launch_gemm)
       return note_grouped(l16_names[l16_tile][d.k == 32], launch_f32_lw16(l16_tile, a, items, n_items, true, stream));
@@ -917,13 +847,7 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
     const int64_t t6432 = (d.m % 64 == 0) ? n_dec * (d.m / 64) * ((d.n + 31) / 32) : 0;
     if (n_items <= 65535 * 2) { // grid.x carries the item index (x split)
       auto nm = [&](const char *plain, const char *pairs) { return d.k == 32 ? pairs : plain; };
-      (void)nm;
-      // the loader-wave kernels (brgemm_f32_lw.hip) in grouped mode; TPP_GROUPED_FAST builds the round-1 register-staged family for A/B runs
-#ifdef TPP_GROUPED_FAST
-      if (t64 >= g_num_cus) return note_grouped("brgemm_f32_fast<64x64> grouped", launch_fast_grouped_t<2, 2, 1, TPP_NACC, true>(a, items, n_items, stream));
-      if (t6432 >= g_num_cus) return note_grouped("brgemm_f32_fast<64x32,k2> grouped", launch_fast_grouped_t<2, 1, 2, TPP_NACC, true>(a, items, n_items, stream));
-      return note_grouped("brgemm_f32_fast<32x32,k4> grouped", launch_fast_grouped_t<1, 1, 4, TPP_NACC, false>(a, items, n_items, stream));
-#else
+      // the loader-wave kernels (brgemm_f32_lw.hip) in grouped mode
       if (t64 >= g_num_cus) return note_grouped(t64 >= 2 * g_num_cus ? nm("brgemm_f32_lw<64x64> grouped", "brgemm_f32_lw<64x64> grouped, 32-k pairs") : nm("brgemm_f32_lw<64x64,k2> grouped", "brgemm_f32_lw<64x64,k2> grouped, 32-k pairs"), launch_f32_lw_grouped(t64 >= 2 * g_num_cus ? 0 : 1, a, items, n_items, 1, stream));
       const int64_t t32 = n_dec * (d.m / 32) * ((d.n + 31) / 32);
       // (rounds of workgroups x per-chunk time, as pick_f32_variant: 1.5 rounds of 64x32 tiles lose to 3 half-rounds of 32x32 tiles)
@@ -936,7 +860,6 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
       static const char *const split_names[2] = {"brgemm_f32_lw<32x32,k4> grouped, split", "brgemm_f32_lw<32x32,k4> grouped, 32-k pairs, split"};
       if (S > 1) return note_grouped(split_names[d.k == 32], launch_f32_lw_grouped(3, a, items, n_items, S, stream));
       return note_grouped(nm("brgemm_f32_lw<32x32,k4> grouped", "brgemm_f32_lw<32x32,k4> grouped, 32-k pairs"), launch_f32_lw_grouped(3, a, items, n_items, 1, stream));
-#endif
     }
   }
   // bf16 + VNNI-2 B with 16-byte loads: 8-element A pieces, pair-rows of B 16-byte aligned
@@ -950,12 +873,8 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
   // item) or 64x64. Against the two older grouped kernels (profiles/r06_bf16_sweep_before.txt, forced-variant rows): the loader-wave
   // tiles win whenever the group fills 3/4 of the chip with 64x64 tiles (1024 x 1024 x 512: 5.1 us against 6.7) or the reduction is
   // long (16 chunks or more: 128 x 4096 x 1024 5.3 against 9.4) or half the chip gets a 32x64 tile of at least 8 chunks (128 x 3072 x 768: 4.9 against 6.3; 1024 x 512 x 256, 4 chunks: 5.6 against 5.1);
-  // short reductions of small groups stay on the K-split kernel (128 x 768 x 768: 4.3 against 4.7). TPP_HIP_BF16_LW_GROUPED=0 switches the path off (A/B runs).
+  // short reductions of small groups stay on the K-split kernel (128 x 768 x 768: 4.3 against 4.7).
   {
-    static const bool lwg_on = [] {
-      const char *e = getenv("TPP_HIP_BF16_LW_GROUPED");
-      return !e || atoi(e) != 0;
-    }();
     const bool v2 = d.vnni_factor == 2, v4 = d.vnni_factor == 4;
     const bool shape_ok = d.dtype == DT_BF16 && d.vnni_b && (v2 || v4) && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.k > 0 && d.k % BK == 0 &&
                           d.m % 32 == 0 && d.n % 64 == 0 && !((d.lda | d.stride_a | d.stride_b | d.ldc) & 7) && !(d.ldb & (v2 ? 3 : 1)) &&
@@ -965,14 +884,10 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
     // columns it shares with its neighbour and stores its own 16: brgemm_bf16_lw.hip skip_cols). Skinny groups with a long reduction
     // only, like the instance's other uses; everything else with such an n stays on the K-split kernel below.
     {
-      static const bool ragged_on = [] {
-        const char *e = getenv("TPP_HIP_BF16_LW_RAGGED");
-        return !e || atoi(e) != 0;
-      }();
-      const bool ragged_ok = ragged_on && d.dtype == DT_BF16 && d.vnni_b && (v2 || v4) && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.k > 0 && d.k % BK == 0 &&
+      const bool ragged_ok = d.dtype == DT_BF16 && d.vnni_b && (v2 || v4) && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.k > 0 && d.k % BK == 0 &&
                              d.m % 32 == 0 && d.n % 32 == 16 && d.n >= 48 && !((d.lda | d.stride_a | d.stride_b | d.ldc) & 7) && !(d.ldb & (v2 ? 3 : 1)) &&
                              d.lda < (1 << 21) && d.ldb < (1 << 20) && d.ldc < (1 << 22) && d.stride_a >= 0 && d.stride_b >= 0;
-      if (lwg_on && ragged_ok && vec_ok && out_ok && br_hint >= 1 && g_forced_split.load(std::memory_order_relaxed) < 0) {
+      if (ragged_ok && vec_ok && out_ok && br_hint >= 1 && g_forced_split.load(std::memory_order_relaxed) < 0) {
         const int64_t chunks = br_hint * (d.k / BK);
         const int64_t wg4 = n_dec * (d.m / 32) * ((d.n + 31) / 32);
         if (wg4 <= (int64_t)g_num_cus && chunks >= 16) {
@@ -989,7 +904,7 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
         }
       }
     }
-    if (lwg_on && shape_ok && vec_ok && out_ok && br_hint >= 1 && g_forced_split.load(std::memory_order_relaxed) < 0) { // (a forced split count: the K-split kernel below)
+    if (shape_ok && vec_ok && out_ok && br_hint >= 1 && g_forced_split.load(std::memory_order_relaxed) < 0) { // (a forced split count: the K-split kernel below)
       const int64_t chunks = br_hint * (d.k / BK);
       const int64_t t64 = d.m % 64 == 0 ? n_dec * (d.m / 64) * (d.n / 64) : 0;
       const int64_t wg0 = n_dec * (d.m / 32) * (d.n / 64);
@@ -1002,11 +917,7 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
         // launch_gemm does for the whole-layer call (one round of workgroups at most, 16 chunks or more; (a, b) = (3.52, 0.072) from
         // 128 x 1024 x 1024 / x 4096 on that tile)
         const int64_t wg4 = n_dec * (d.m / 32) * (d.n / 32);
-        static const bool t4_v4 = [] { // (A/B runs: TPP_HIP_BF16_LW_T4_VNNI4=0 keeps VNNI-4 groups on the 32x64 / 64x64 tiles)
-          const char *e = getenv("TPP_HIP_BF16_LW_T4_VNNI4");
-          return !e || atoi(e) != 0;
-        }();
-        if ((v2 || (v4 && t4_v4)) && wg4 <= (int64_t)g_num_cus && chunks >= 16 && 3.52 + 0.072 * (double)chunks < (c1 < c0 ? c1 : c0)) tile = 4;
+        if (wg4 <= (int64_t)g_num_cus && chunks >= 16 && 3.52 + 0.072 * (double)chunks < (c1 < c0 ? c1 : c0)) tile = 4;
         ChainArgs c;
         memset(&c, 0, sizeof(c));
         c.lda = d.lda;
@@ -1073,7 +984,7 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
 // QUADS (round 6; xsmm_desc.h QuadItem, brgemm_bf16_lw.hip GRP = 2): a group of 64x64 bf16 tile invokes that forms a grid of item rows and
 // item columns runs as 2 x 2 blocks on the 128x128 loader-wave tile when the tile model says so - the kernel the same layer gets as
 // ONE whole-layer call once it is large enough (pick_bf16_lw_tile). 1024 x 2560 x 1024 as 640 invokes: 3 rounds of 64x64 tiles
-// (15.3 us) against 160 workgroups of 128x128 (whole-layer call 10.2 us). TPP_HIP_BF16_QUADS=0: off (A/B runs).
+// (15.3 us) against 160 workgroups of 128x128 (whole-layer call 10.2 us).
 static bool quads_shape_ok(const GemmDesc &d) {
   const bool v2 = d.vnni_factor == 2 || d.vnni_factor == 0, v4 = d.vnni_factor == 4;
   return d.dtype == DT_BF16 && d.vnni_b && (v2 || v4) && !d.vnni_c && !d.b_trans && !d.generic_forced && !d.variant_forced && d.m == 64 && d.n == 64 && d.k > 0 &&
@@ -1081,11 +992,7 @@ static bool quads_shape_ok(const GemmDesc &d) {
          d.ldc < (1 << 22) && d.stride_a >= 0 && d.stride_b >= 0;
 }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) {
-  static const bool on = [] {
-    const char *e = getenv("TPP_HIP_BF16_QUADS");
-    return !e || atoi(e) != 0;
-  }();
-  if (!on || strict_kernels() || !quads_shape_ok(d) || br < 1 || n_items < 4 || (n_items & 3) || g_forced_split.load(std::memory_order_relaxed) >= 0) return false;
+  if (strict_kernels() || !quads_shape_ok(d) || br < 1 || n_items < 4 || (n_items & 3) || g_forced_split.load(std::memory_order_relaxed) >= 0) return false;
   const double chunks = (double)(br * (d.k / BK));
   const int64_t cus = g_num_cus;
   // (a, b) of the tile model: 64x64 (3.75, 0.135), 32x64 + K2 (3.56, 0.098) - what the grouped path would pick from - and 128x128 (6.06, 0.236)
@@ -1120,14 +1027,14 @@ static int pick_f32_variant(const GemmDesc &d) {
   // Outputs with at least one 64x64 tile per CU: 64x64 or 128x64 tiles, whichever needs less time over its rounds
   // of workgroups (one per CU at a time). A 128x64 round takes ~1.85x a 64x64 round (measured, K = 1024: 32.7 vs
   // 17.6 us), so 128x64 wins at 1280-2048 x 1024 (one round instead of two) and for large outputs (0.93x), and
-  // loses e.g. at 3072 x 1024 (two rounds against three; tools/sessions/mid_probe.py).
+  // loses e.g. at 3072 x 1024 (two rounds against three).
   // Skinny outputs - at most one 32x16 tile per CU (the reference's M = 128 shapes: 128 x 1024 = 256 tiles, 128 x 768 = 192): the
   // half-width tiles of brgemm_f32_lw16.hip put a workgroup on every CU where 32x32 tiles would leave half the chip idle, and need
   // no hand-off between workgroups (the SPLIT launches pay 2.6-2.7 us for one); profiles/r05_lw16_vs_split.txt
   // (a 16x48 tile of the same family - 256 x 768 outputs are exactly 256 of them - was built and measured: 256 x 768 x 768 5.59 us
   // against 5.48 on 192 tiles of 32x32, x 3072 14.9 against 13.7: 16 KiB of panel per 98 kflop chunk, the launch is bound by the
   // L2 -> LDS traffic of all CUs together, ~16 TB/s; removed. profiles/r05_lw16_vs_split.txt)
-  if (d.ldc % 4 == 0 && lw16_on() && tiles(32, 16) > 0 && tiles(32, 16) <= g_num_cus) return V_F32_LW16_32x16;
+  if (d.ldc % 4 == 0 && tiles(32, 16) > 0 && tiles(32, 16) <= g_num_cus) return V_F32_LW16_32x16;
   if (tiles(64, 64) >= g_num_cus) {
     const int64_t r64 = (tiles(64, 64) + g_num_cus - 1) / g_num_cus, r128 = (tiles(128, 64) + g_num_cus - 1) / g_num_cus;
     if (tiles(128, 64) > 0 && 1.85 * (double)r128 < (double)r64) return V_F32_128x64;
@@ -1151,13 +1058,8 @@ static int pick_f32_variant(const GemmDesc &d) {
 // Mid-size bf16 outputs: the loader-wave family (brgemm_bf16_lw.hip), the largest tile that still gives at least 3/4 of the CUs
 // a workgroup (one workgroup per CU: 160 KiB of LDS). Outputs too small for that even with 32x64 tiles stay with the 32x32 K-split
 // family (m = 256, n = 1024, K = 1024: 4.9 us against 5.7 on 128 tiles of 32x64, profiles/r03_sweep_shapes.txt).
-// Returns the tile index (0 .. 3) or -1. TPP_HIP_BF16_LW=0 switches the family off (A/B runs).
+// Returns the tile index (0 .. 3) or -1.
 static int pick_bf16_lw_tile(const GemmDesc &d) {
-  static const int enabled = [] {
-    const char *e = getenv("TPP_HIP_BF16_LW");
-    return e ? atoi(e) : 1;
-  }();
-  if (!enabled) return -1;
   // Gate (unchanged since round 3): some tile of the family gives at least 3/4 of the CUs a workgroup. Which tile, round 6 - fitted to the
   // sweep of the reference's whole shape set over every tile (tools/bf16_sweep.py, profiles/r06_bf16_sweep.txt): a launch costs
   // rounds x (a + b x chunks), rounds = ceil(tiles / CUs) (one workgroup per CU: a second round is a second kernel's worth), with
@@ -1165,10 +1067,6 @@ static int pick_bf16_lw_tile(const GemmDesc &d) {
   // (6.06, 0.236). The old rule - the LARGEST tile that still reaches 3/4 of the CUs - put 1024 x 2560 on 320 tiles of 64x128 (two
   // rounds: 15.1 us) instead of 160 tiles of 128x128 (one round: 10.2 us). The batch count arrives with the invoke: priced at 16 chunks
   // (K = 1024; the order of two candidates flips with K only when their round counts differ AND the sums are within a few percent).
-  static const int legacy = [] {
-    const char *e = getenv("TPP_HIP_BF16_LW_PICK");
-    return e ? atoi(e) == 0 : 0; // TPP_HIP_BF16_LW_PICK=0: the round-3 rule (A/B runs)
-  }();
   static const double ca[4] = {3.56, 3.75, 4.66, 6.06}, cb[4] = {0.098, 0.135, 0.204, 0.236};
   bool gate = false;
   int best = -1;
@@ -1178,10 +1076,7 @@ static int pick_bf16_lw_tile(const GemmDesc &d) {
     blw_tile_dims(t, &bm, &bn);
     if (d.m % bm || d.n % bn) continue;
     const int64_t tiles = (d.m / bm) * (d.n / bn);
-    if (tiles * 4 >= 3 * (int64_t)g_num_cus) {
-      if (legacy) return t;
-      gate = true;
-    }
+    if (tiles * 4 >= 3 * (int64_t)g_num_cus) gate = true;
     const double cost = (double)((tiles + g_num_cus - 1) / g_num_cus) * (ca[t] + cb[t] * 16.0);
     if (best < 0 || cost < best_t) best = t, best_t = cost;
   }
@@ -1387,8 +1282,8 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   bool bf16_lw_32x32 = false;
   if (v == V_BF16_SMALL32 && d.variant == V_BF16_SMALL32 && !d.generic_forced && d.k % 64 == 0 && d.m % 32 == 0 && d.n % 64 == 0 && !(((uintptr_t)C) & 15) &&
       !(d.bias && (((uintptr_t)D) & 7)) && !d.variant_forced) {
-    const bool t32 = (d.m / 32) * (d.n / 32) <= (int64_t)g_num_cus && bf16_lw32_on();
-    const int64_t thr = t32 && bf16_long_k() > 1024 ? 1024 : bf16_long_k();
+    const bool t32 = (d.m / 32) * (d.n / 32) <= (int64_t)g_num_cus;
+    const int64_t thr = t32 ? 1024 : 1536;
     GemmDesc e = d;
     e.m = (d.m + 63) / 64 * 64; // (bf16_fast_eligible asks for m % 64; these tiles need m % 32 only)
     if ((int64_t)a.br * d.k >= thr && bf16_fast_eligible(e)) {
@@ -1404,11 +1299,11 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   // 512-cycle chunks and short kernels: in a chain of dependent layers (3 x 1024 MLP, batch 256) the DMA
   // path's 2-chunk lead and slower prologue (an LDS-DMA instruction takes ~60 cycles to issue) cost more
   // than the ds_write path saves (32.4 vs 29.2 us); deeper rings (5-6 slots) made the prologue worse.
-  case V_F32_64x64: return launch_fast<2, 2, 1, TPP_NACC, true>(a, stream);
-  case V_F32_64x32K2: return launch_fast<2, 1, 2, TPP_NACC, true>(a, stream);
-  case V_F32_32x32K4: return launch_fast<1, 1, 4, TPP_NACC, false>(a, stream);
-  case V_F32_128x64: return launch_fast<4, 2, 1, TPP_NACC, true>(a, stream);
-  case V_F32_64x64K2: return launch_fast<2, 2, 2, TPP_NACC, true>(a, stream);
+  case V_F32_64x64: return launch_fast<2, 2, 1, true>(a, stream);
+  case V_F32_64x32K2: return launch_fast<2, 1, 2, true>(a, stream);
+  case V_F32_32x32K4: return launch_fast<1, 1, 4, false>(a, stream);
+  case V_F32_128x64: return launch_fast<4, 2, 1, true>(a, stream);
+  case V_F32_64x64K2: return launch_fast<2, 2, 2, true>(a, stream);
   case V_F32_LW_64x64: return launch_f32_lw(0, a, stream);
   case V_F32_LW_64x64K2:
   case V_F32_LW_64x32K2:
@@ -1457,8 +1352,7 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   case V_BF16_LW_128x128: {
     ChainArgs c;
     c.A = a.A; c.lda = a.lda; c.cnt = nullptr; c.err = nullptr; c.target = 0;
-    c.m = a.m; c.n = a.n; c.nlayers = 1; c.tiles_m = c.tiles_n = 0; c.xm = 0; c.stamps = nullptr;
-    c.dbg = chain_ablation_bits();
+    c.m = a.m; c.n = a.n; c.nlayers = 1; c.tiles_m = c.tiles_n = 0; c.xm = 0;
     c.L[0] = ChainLayer{a.B, a.D, a.C, a.ldb, a.ldc, a.stride_a, a.stride_b, a.k, a.br, a.ep, 0};
     return launch_bf16_lw(bf16_lw_32x32 ? 4 : v - V_BF16_LW_32x64, c, stream);
   }
@@ -1468,12 +1362,11 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   case V_BF16_LW4_128x128: {
     ChainArgs c;
     c.A = a.A; c.lda = a.lda; c.cnt = nullptr; c.err = nullptr; c.target = 0;
-    c.m = a.m; c.n = a.n; c.nlayers = 1; c.tiles_m = c.tiles_n = 0; c.xm = 0; c.stamps = nullptr;
-    c.dbg = chain_ablation_bits();
+    c.m = a.m; c.n = a.n; c.nlayers = 1; c.tiles_m = c.tiles_n = 0; c.xm = 0;
     c.L[0] = ChainLayer{a.B, a.D, a.C, a.ldb, a.ldc, a.stride_a, a.stride_b, a.k, a.br, a.ep, 0};
     // (round 6) skinny outputs with a long reduction: the 32x32 + K2 instance, as for VNNI-2 operands above - at most one 32x32 tile
     // per CU and K >= 1024: twice the workgroups of the 32x64 tile pulling panels (128 x 1024 x 4096: 9.3 -> 7.6 us)
-    if (v == V_BF16_LW4_32x64 && !d.variant_forced && !d.generic_forced && bf16_lw32_on() && d.m % 32 == 0 && d.n % 32 == 0 &&
+    if (v == V_BF16_LW4_32x64 && !d.variant_forced && !d.generic_forced && d.m % 32 == 0 && d.n % 32 == 0 &&
         (d.m / 32) * (d.n / 32) <= (int64_t)g_num_cus && (int64_t)a.br * d.k >= 1024) {
       g_last_refined.store("brgemm_bf16_lw_vnni4<32x32,k2> (long reduction)", std::memory_order_relaxed);
       return launch_bf16_lw_vnni4(4, c, stream);
@@ -1486,8 +1379,7 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   case V_BF16_LWF_128x128: {
     ChainArgs c;
     c.A = a.A; c.lda = a.lda; c.cnt = nullptr; c.err = nullptr; c.target = 0;
-    c.m = a.m; c.n = a.n; c.nlayers = 1; c.tiles_m = c.tiles_n = 0; c.xm = 0; c.stamps = nullptr;
-    c.dbg = chain_ablation_bits();
+    c.m = a.m; c.n = a.n; c.nlayers = 1; c.tiles_m = c.tiles_n = 0; c.xm = 0;
     c.L[0] = ChainLayer{a.B, a.D, a.C, a.ldb, a.ldc, a.stride_a, a.stride_b, a.k, a.br, a.ep, 0};
     return launch_bf16_lw_flatb(v - V_BF16_LWF_32x64, c, stream);
   }
@@ -1503,7 +1395,7 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
                      d.lda < (1 << 21) && d.ldb < (1 << 21); // (32-bit lane offsets)
   // a SINGLE invoke of a 32-k f32 tile with an even batch count: the kernel its group would run on in the tile queue (the
   // loader-wave pair mode, tile chosen as launch_gemm_grouped does for one item) - queue on and queue off then add in the same order
-  if (vec && k32_pairs_on() && !d.generic_forced && d.k == 32 && a.br >= 2 && !(a.br & 1) && d.m % 32 == 0 && d.n % 32 == 0 && d.stride_a >= 0 &&
+  if (vec && !d.generic_forced && d.k == 32 && a.br >= 2 && !(a.br & 1) && d.m % 32 == 0 && d.n % 32 == 0 && d.stride_a >= 0 &&
       d.stride_b >= 0 && d.stride_a < (1 << 26) && d.stride_b < (1 << 26) && d.lda < (1 << 22) && d.ldb < (1 << 22) && d.ldc < (1 << 22)) {
     const int64_t t64 = (d.m % 64 == 0 && d.n % 64 == 0) ? (d.m / 64) * (d.n / 64) : 0;
     const int64_t t6432 = (d.m % 64 == 0) ? (d.m / 64) * (d.n / 32) : 0;

@@ -55,13 +55,10 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
   extern __shared__ __attribute__((aligned(16))) float smem_lw[];
 
   const int tid = threadIdx.x, lane = tid & 63;
-#ifndef TPP_LW_LOADERS_FIRST
-#define TPP_LW_LOADERS_FIRST 1
-#endif
   // the two loader waves are the FIRST two hardware waves of the workgroup (waves start in order: the panels' first
   // chunks are requested before the MFMA waves have been launched); `wave` is the role index: MFMA waves 0 .. NMW-1, loaders NMW, NMW+1
   const int hw_wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wave = TPP_LW_LOADERS_FIRST ? (hw_wave < NL + NLB ? NMW + hw_wave : hw_wave - (NL + NLB)) : hw_wave;
+  const int wave = hw_wave < NL + NLB ? NMW + hw_wave : hw_wave - (NL + NLB);
   // XCD-blocked (8, bn, bm) or plain (1, tiles_n, tiles_m) grid: see brgemm_f32.hip. GROUPED (tile queue): grid (items,
   // tiles_n, tiles_m), workgroup = one tile of one queued invoke, operands and batch count from its item. A template
   // parameter, not a run-time test: the plain kernel is the headline kernel and must not carry a second mode (measured: 0.6 %).
@@ -414,18 +411,14 @@ template <int WM, int WN, int WK, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL
   // XCD-blocked grid: xm x xn = 8 XCD blocks of tiles_m/xm x tiles_n/xn tiles (blockIdx.x = the XCD: workgroups go to XCDs round
   // robin). Each XCD's L2 then fetches m/xm rows of A and n/xn columns of B: the split that minimises m/xm + n/xn - 4 x 2 for
   // square outputs (C2; ties keep it: rounds 1-3 had only this one), 2 x 4 for C3's 512 x 1024 and the batch-256 layers (-20 / -33 % of
-  // the L2 fill). TPP_HIP_F32_LW_XM forces xm (A/B runs).
-  static const int forced_xm = [] {
-    const char *e = getenv("TPP_HIP_F32_LW_XM");
-    return e ? atoi(e) : 0;
-  }();
+  // the L2 fill).
   int xm = 0;
   long long best = -1;
   for (int c : {4, 2, 8, 1}) {
     const int xn = 8 / c;
     if (tiles_m % c || tiles_n % xn || tiles_m / c > 65535 || tiles_n / xn > 65535) continue;
     const long long cost = (long long)a.m / c + (long long)a.n / xn;
-    if (forced_xm ? c == forced_xm : (best < 0 || cost < best)) {
+    if (best < 0 || cost < best) {
       best = cost;
       xm = c;
     }
@@ -805,16 +798,6 @@ hipError_t launch_f32_chain(int tile, const ChainArgs &a, hipStream_t s) {
   }
 }
 
-// The 64x32 tile's loader waves: 21 (default) = two for the A panel (16 requests per chunk) and one for B (8) - every loader issues 8;
-// C3 9.912 -> 9.881 us, four alternating pairs on one box (profiles/r04_c3_loaders_and_launch_knobs.txt); 11 = one per panel
-// (rounds 2-3), 22 = two each (9.888). TPP_HIP_F32_LW_C3_LOADERS for A/B runs.
-static int f32_lw_c3_loaders() {
-  static const int v = [] {
-    const char *e = getenv("TPP_HIP_F32_LW_C3_LOADERS");
-    return e ? atoi(e) : 21;
-  }();
-  return v;
-}
 // tile: 0 = 64x64 (4 MFMA waves), 1 = 64x64 with K split over 2 wave groups (8 MFMA waves, two per
 // SIMD), 2 = 64x32 with K split over 4 (8 MFMA waves), 3 = 32x32 with K split over 4 (4 MFMA waves)
 hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s) {
@@ -825,7 +808,9 @@ hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s) {
   case 1: return launch_lw_t<2, 2, 2, 2>(a, s); // (four per panel: 18.25 us)
   // 64x32 with K split over FOUR wave groups: 8 MFMA waves = two per SIMD, like the 64x64 k2 tile - one wave's fragment reads and
   // barrier waits hide behind the other's MFMAs. C3 (512 x 1024 x 1024): 10.52 -> 10.21 us same-box against the K2 split (4 waves).
-  case 2: return f32_lw_c3_loaders() == 11 ? launch_lw_t<2, 1, 4>(a, s) : f32_lw_c3_loaders() == 22 ? launch_lw_t<2, 1, 4, 2>(a, s) : launch_lw_t<2, 1, 4, 2, LW_NSLOT, 1>(a, s);
+  // Its loader waves: two for the A panel (16 requests per chunk) and one for B (8) - every loader issues 8; C3 9.912 -> 9.881 us
+  // against one per panel, four alternating pairs on one box (two each: 9.888; profiles/r04_c3_loaders_and_launch_knobs.txt).
+  case 2: return launch_lw_t<2, 1, 4, 2, LW_NSLOT, 1>(a, s);
   // (the same tile with its K split over EIGHT wave groups - two MFMA waves per SIMD, one k-block per wave and chunk, the barrier behind
   // the block - measured 3-4.5 % slower on the reference's batch-256 layers: profiles/r04_c3_loaders_and_launch_knobs.txt (5))
   case 3: return launch_lw_t<1, 1, 4>(a, s);

@@ -30,10 +30,7 @@
 namespace tpp {
 
 constexpr int X6_BK = 64; // k per chunk
-#ifndef TPP_X6_LOADERS
-#define TPP_X6_LOADERS 4
-#endif
-constexpr int X6_LOADERS = TPP_X6_LOADERS; // loader (split) waves per workgroup; -DTPP_X6_LOADERS=n: side builds for A/B runs
+constexpr int X6_LOADERS = 4; // loader (split) waves per workgroup
 typedef __bf16 x6_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float x6_f32x2 __attribute__((ext_vector_type(2)));
 

@@ -2,8 +2,8 @@
 // one launch (layer l+1 reads layer l's output rows; xsmm_hip_fused_brgemm_chain_invoke in runtime.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 namespace tpp {
 
@@ -29,14 +29,9 @@ struct ChainArgs {
   int nlayers;
   int tiles_m, tiles_n; // filled by the launcher
   int xm;               // filled by the launcher: XCD grid xm x (8 / xm) over the tile grid, 0 = linear tile order
-  int dbg;              // timing experiments, ABLATION BUILDS ONLY (-DTPP_HIP_ABLATION, then TPP_HIP_CHAIN_DBG): 1 plain A loads,
-                        // 2 no wait at the seams, 4 plain stores, 16 no DMA, 32 no fragment reads / MFMAs, 64 no B DMA, 128 no A DMA,
-                        // 256 whole prologue before the first barrier, 512 every workgroup loads the panels of tile (0, 0) (no fabric
-                        // traffic: the K loop on L2 hits only), 1024 per-chunk s_memtime stamps of the loader waves of the first 16
-                        // workgroups (needs stamps; written to <TPP_HIP_CHAIN_STAMPS>.chunks, tools/stamps_report.py --chunks), 2048 the loaders issue
-                        // their DMA instructions with every lane switched off (no traffic, no LDS write: the issue-side cost alone). The shipped library compiles the kernels with dbg == 0 and
-                        // never reads the variable: several of these switches give wrong results by design.
-  unsigned long long *stamps; // profiling (ablation builds, TPP_HIP_CHAIN_STAMPS=file): [workgroup][layer][8] s_memrealtime stamps, else nullptr
+  // Unused. Keeps L at byte 72 of the argument block: without these bytes every L[] load moves and the compiler assigns
+  // registers differently in the f32 chain kernels' K loop, a code change that would have to be measured on its own.
+  char reserved[12];
   ChainLayer L[CH_MAXL];
   // GROUPED launches (round 6, the tile queue's bf16 groups: launch_bf16_lw_grouped): a work list of tile invokes of ONE descriptor - every
   // workgroup takes A, B, C, D and the batch count of ITS item from the list, everything else (leading dimensions, strides, k, epilogue)
@@ -45,19 +40,7 @@ struct ChainArgs {
   int item_subs;
   int pad_items;
 };
-
-// the value of ChainArgs::dbg on the host side
-static inline int chain_ablation_bits() {
-#ifdef TPP_HIP_ABLATION
-  static const int v = [] {
-    const char *e = getenv("TPP_HIP_CHAIN_DBG");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-#else
-  return 0;
-#endif
-}
+static_assert(offsetof(ChainArgs, L) == 72, "the kernels' code depends on where the layer table lies");
 
 // tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128
 void blw_tile_dims(int tile, int *bm, int *bn);

@@ -94,11 +94,7 @@ static inline hipError_t ensure_dynamic_lds(const void *kernel, int bytes, std::
 // helps C2 but not C3. ONLY where one store instruction writes whole 128-byte lines (8 lanes x 16 bytes or 32 lanes x 4 bytes of
 // one row): write-through of partial lines costs - the reg-staged 64x64 bf16 kernel (32 contiguous bytes per row and instruction)
 // measured 4-7 % slower with sc1, the VNNI-2 pack kernel (two 16-byte stores per lane) 6.5 -> 3.8 TB/s; both keep plain stores.
-// -DTPP_C_STORE_AUX=n: side builds for A/B runs.
-#ifndef TPP_C_STORE_AUX
-#define TPP_C_STORE_AUX 16
-#endif
-constexpr int C_STORE_AUX = TPP_C_STORE_AUX;
+constexpr int C_STORE_AUX = 16;
 
 // compute units of the current device (queried once per process; tile heuristics use it)
 static inline int device_cu_count() {

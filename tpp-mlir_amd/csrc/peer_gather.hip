@@ -145,11 +145,7 @@ extern "C" void xsmm_hip_peer_drain(void) {
 // self-test (peer.py: three gathers incl. a re-use of a buffer this device has read before) decides whether the result can be used.
 extern "C" void *xsmm_hip_peer_alloc(int64_t bytes) {
   void *p = nullptr;
-  static const bool fine = [] {
-    const char *e = getenv("TPP_HIP_PEER_FINEGRAINED"); // 0: plain hipMalloc (A/B runs)
-    return !e || atoi(e) != 0;
-  }();
-  if (fine && hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocFinegrained) == hipSuccess && p) {
+  if (hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocFinegrained) == hipSuccess && p) {
     hipIpcMemHandle_t probe;
     if (hipIpcGetMemHandle(&probe, p) == hipSuccess) { // (only if it can be shared like the others)
       PG_OK(hipMemset(p, 0, (size_t)bytes));

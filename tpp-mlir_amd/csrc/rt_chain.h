@@ -68,7 +68,6 @@ ChainBlock &chain_block(hipStream_t s, int tiles_m, int tiles_n, int nlayers) { 
   return g_chain_blocks.back();
 }
 // after stream `s` has been drained: did a hand-off of a chain launch on it time out?
-void dump_chain_stamps();
 void chain_rerun_call_by_call(const ChainCall &c);
 void check_chain_errors(hipStream_t s) {
   if (!g_chain_launched.load(std::memory_order_acquire)) return;
@@ -76,7 +75,6 @@ void check_chain_errors(hipStream_t s) {
   unsigned layer = 0;
   {
     std::lock_guard<std::mutex> lk(g_chain_mu);
-    dump_chain_stamps();
     std::vector<ChainCall> keep;
     for (const ChainCall &c : g_chain_journal) {
       if (c.stream != s) { // another stream's launch: not drained by this synchronisation, stays
@@ -136,57 +134,6 @@ int stream_cus(hipStream_t s) {
   int bits = 0;
   for (uint32_t w : mask) bits += __builtin_popcount(w);
   return bits > 0 && bits < all ? bits : all;
-}
-
-// profiling (-DTPP_HIP_ABLATION side builds only, build.py --ablation): TPP_HIP_CHAIN_STAMPS=<file> makes every chain launch record s_memrealtime stamps (100 MHz) per workgroup and layer
-// (see blw_stamp in brgemm_bf16_lw.hip) into pinned host memory; the LAST launch's stamps are written to the file at every sync point.
-unsigned long long *g_stamps = nullptr;
-size_t g_stamps_wgs = 0;
-unsigned long long *chain_stamps(size_t wgs) { // under g_chain_mu
-#ifdef TPP_HIP_ABLATION
-  static const char *path = getenv("TPP_HIP_CHAIN_STAMPS");
-  if (!path) return nullptr;
-  if (!g_stamps) HIP_OK(hipHostMalloc((void **)&g_stamps, sizeof(unsigned long long) * 8 * CH_MAXL * 1024, hipHostMallocDefault));
-  if (wgs > 1024) return nullptr;
-  g_stamps_wgs = wgs;
-  return g_stamps;
-#else
-  (void)wgs;
-  return nullptr; // the shipped kernels carry no stamp code (brgemm_bf16_lw.hip: blw_stamp)
-#endif
-}
-void dump_chain_stamps() {
-#ifdef TPP_HIP_ABLATION
-  const char *path = getenv("TPP_HIP_CHAIN_STAMPS");
-#else
-  const char *path = nullptr;
-#endif
-  if (!path || !g_stamps || !g_stamps_wgs) return;
-  if (FILE *f = fopen(path, "w")) {
-    for (size_t w = 0; w < g_stamps_wgs; ++w)
-      for (int l = 0; l < CH_MAXL; ++l) {
-        const unsigned long long *s = g_stamps + (w * CH_MAXL + l) * 8;
-        if (!s[0] && !s[5]) continue;
-        fprintf(f, "%zu %d", w, l);
-        for (int i = 0; i < 8; ++i) fprintf(f, " %llu", s[i]);
-        fputc('\n', f);
-      }
-    fclose(f);
-  }
-  // the loaders' per-chunk records of the first 16 workgroups (TPP_HIP_CHAIN_DBG & 1024; brgemm_bf16_lw.hip BlwChunkStamps)
-  if (chain_ablation_bits() & 1024) {
-    const std::string p2 = std::string(path) + ".chunks";
-    if (FILE *f = fopen(p2.c_str(), "w")) {
-      const unsigned long long *base = g_stamps + g_stamps_wgs * CH_MAXL * 8;
-      for (int w = 0; w < 16 && (size_t)w < g_stamps_wgs; ++w)
-        for (int which = 0; which < 2; ++which) {
-          const unsigned long long *r = base + ((size_t)w * 2 + which) * (64 * 3 + 1);
-          const int n = (int)(r[0] > 64 ? 64 : r[0]);
-          for (int i = 0; i < n; ++i) fprintf(f, "%d %d %d %llu %llu %llu\n", w, which, i, r[1 + 3 * i], r[2 + 3 * i], r[3 + 3 * i]);
-        }
-      fclose(f);
-    }
-  }
 }
 
 bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
@@ -300,7 +247,6 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   c.m = (int)m;
   c.n = (int)nn;
   c.nlayers = n;
-  c.dbg = chain_ablation_bits();
   for (int i = 0; i < n; ++i)
     c.L[i] = ChainLayer{pb[i], pd[i], pc[i], d[i]->ldb, d[i]->ldc, d[i]->stride_a, d[i]->stride_b, (int)d[i]->k, (int)br[i],
                         EP_BETA0 | (d[i]->bias ? EP_BIAS : 0) | (d[i]->relu ? EP_RELU : 0), 0};
@@ -337,7 +283,6 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     g_chain_err_free.pop_back();
   }
   c.target = ++blk.epoch * (unsigned)blk.tiles_n;
-  c.stamps = chain_stamps((size_t)blk.tiles_m * (size_t)blk.tiles_n);
   if (f32) HIP_OK(launch_f32_chain(tile, c, s));
   else HIP_OK(launch_bf16_chain(tile, b_kind, c, s));
   if (blk.verified < 1) {

@@ -11,13 +11,9 @@
 // bias D0 + c n, every (r, c) once - a complete replay of it is launched as ONE invoke of the merged problem (rows m, cols n) on the
 // kernel plan_gemm picks for THAT shape (64x64 tiles instead of 1024 workgroups of 32x32 with 8 chunks each: 13.0 -> ~10.5 us). Same
 // reads, same writes, the same sums per element in a different (fixed) order: like every kernel choice that depends on the group.
-// Packed block layouts (mlir-gen's tiles) are never grids: their B tiles are not columns of one row. TPP_HIP_GRID_MERGE=0: off.
+// Packed block layouts (mlir-gen's tiles) are never grids: their B tiles are not columns of one row.
 static bool grid_merge_on() {
-  static const bool on = [] {
-    const char *e = getenv("TPP_HIP_GRID_MERGE");
-    return !e || atoi(e) != 0;
-  }();
-  return on && !cfg().strict.load(std::memory_order_relaxed); // (a merged grid sums in the merged problem's order: not in strict mode)
+  return !cfg().strict.load(std::memory_order_relaxed); // (a merged grid sums in the merged problem's order: not in strict mode)
 }
 std::atomic<const char *> g_last_merged{nullptr}; // trace text of the merged descriptor if the most recent group launch was a merged one
 inline void detect_grid(Segment &S) {

@@ -346,8 +346,7 @@ struct DirectWindow {
   std::atomic<uintptr_t> solo_owner{0};      // thread_token() of the one thread
   Caller callers[MAXC];
   DirectWindow() {
-    const char *e = getenv("TPP_HIP_QUEUE_SOLO"); // 0: the two-sided protocol from the start (A/B runs)
-    if ((!e || atoi(e) != 0) && !getenv("TPP_HIP_NO_MEMBARRIER") && syscall(__NR_membarrier, MEMBARRIER_CMD_REGISTER_PRIVATE_EXPEDITED, 0) == 0) {
+    if (!getenv("TPP_HIP_NO_MEMBARRIER") && syscall(__NR_membarrier, MEMBARRIER_CMD_REGISTER_PRIVATE_EXPEDITED, 0) == 0) {
       multi.store(false, std::memory_order_relaxed);
       multi_ready.store(false, std::memory_order_relaxed);
     }
