@@ -19,6 +19,7 @@ import threading
 import numpy as np
 import pytest
 
+import exact_data as ed
 import fixture_runner as fr
 from abi_backend import AbiBackend
 from oracle import pyoracle as orc
@@ -114,9 +115,16 @@ def test_golden_fixture_through_abi(rt, path, mode):
 # ---------------------------------------------------------------- GEMM family
 def gemm_case(rt, dt, m, n, k, br, lda=None, ldb=None, ldc=None, sa=None, sb=None, beta0=False, bias=False,
               relu=False, vnni=False, fused=None, offs=(0, 0, 0, 0), seed=0, mode="device", force=None,
-              row_blocks=None):
+              row_blocks=None, values=None, poison=False, scale=(0, 0), ranges=None, xflags=0, expect=None):
     """row_blocks: [(first_row, rows)] to verify when the full oracle would be slow - output
-    rows are independent, so the oracle is run on those row blocks only."""
+    rows are independent, so the oracle is run on those row blocks only.
+    values: None = uniform(-1, 1) operands and the tolerance bars; "exact" = small integers times powers of two (A on 2^scale[0],
+    B on 2^scale[1], C and bias on 2^(scale[0] + scale[1]); integer ranges `ranges` = (Ra, Rb, Rc) or exact_data.exact_ranges),
+    checked bit for bit against the oracle; "special" = the same with inf, -inf and NaN sprinkled into A, B, C (beta = 1) and the
+    bias, non-finite results compared by kind.
+    poison: every element of the four buffers that the descriptor does not name is NaN (f32: NaN, +inf, -inf), the oracle runs on
+    the poisoned buffers too (its result must stay finite), and the bytes outside the output window must keep their bits.
+    xflags: extra wire flags (4096 VNNI-A, 8192 VNNI-C; bf16 only). expect: a substring the kernel name must contain."""
     rng = np.random.default_rng(seed)
     lda = lda or max(k, 1)
     ldb = ldb or max(n, 1)
@@ -126,11 +134,27 @@ def gemm_case(rt, dt, m, n, k, br, lda=None, ldb=None, ldc=None, sa=None, sb=Non
     sa = m * lda if sa is None else sa
     sb = bmat if sb is None else sb
     fused = (bias or relu) if fused is None else fused
+    vnni_c = bool(xflags & 8192)
     na = offs[0] + max(br - 1, 0) * sa + m * lda + 8
     nb = offs[1] + max(br - 1, 0) * sb + bmat + 2 * ldb + 8
-    nc = offs[2] + m * ldc + 8
-    A, B, C, D = rand(rng, na, dt), rand(rng, nb, dt), rand(rng, nc, dt), rand(rng, offs[3] + n + 8, dt)
-    flags = (4 if beta0 else 0) | (VB if vnni else 0)
+    nc = offs[2] + m * ldc + (2 * ldc if vnni_c else 0) + 8
+    if values is None:
+        A, B, C, D = rand(rng, na, dt), rand(rng, nb, dt), rand(rng, nc, dt), rand(rng, offs[3] + n + 8, dt)
+    else:
+        ra, rb, rc = ranges or ed.exact_ranges(dt, k * br)
+        s_, t_ = scale
+        A, B = ed.exact_fill(rng, na, dt, ra, s_), ed.exact_fill(rng, nb, dt, rb, t_)
+        C, D = ed.exact_fill(rng, nc, dt, rc, s_ + t_), ed.exact_fill(rng, offs[3] + n + 8, dt, rc, s_ + t_)
+    flags = (4 if beta0 else 0) | (VB if vnni else 0) | xflags
+    if poison or values == "special":
+        live = ed.live_masks((A.size, B.size, C.size, D.size), m, n, k, br, lda, ldb, ldc, sa, sb, offs, vnni=vnni,
+                             v=orc.lib().oracle_get_vnni_factor(), beta0=beta0, bias=bias, vnni_c=vnni_c)
+        if values == "special":
+            for arr, lv in zip((A, B, C, D), live):
+                ed.sprinkle_special(rng, arr, lv, dt, 6)
+        if poison:
+            for arr, lv in zip((A, B, C, D), live):
+                arr[~lv] = ed.poison_fill(arr.size, dt)[~lv]
     Cref = C.copy()
     for (r0, rr) in (row_blocks or [(0, m)]):
         if fused:
@@ -141,7 +165,7 @@ def gemm_case(rt, dt, m, n, k, br, lda=None, ldb=None, ldc=None, sa=None, sb=Non
             orc.brgemm(dt, rr, n, k, lda, ldb, ldc, sa, sb, flags, A, offs[0] + r0 * lda, B, offs[1], Cref,
                        offs[2] + r0 * ldc, br)
     Cmag = None
-    if dt == F32 and m * n * k * max(br, 1) <= 2 ** 28:  # |C| + sum |a||b| + |bias| for the element-wise bar
+    if values is None and dt == F32 and m * n * k * max(br, 1) <= 2 ** 28:  # |C| + sum |a||b| + |bias| for the element-wise bar
         Cmag = np.abs(C)
         for (r0, rr) in (row_blocks or [(0, m)]):
             orc.fused_brgemm(dt, rr, n, k, lda, ldb, ldc, sa, sb, flags, 0, 0, 4 if bias else 0, 1 if bias else 0,
@@ -171,20 +195,23 @@ def gemm_case(rt, dt, m, n, k, br, lda=None, ldb=None, ldc=None, sa=None, sb=Non
             rt.fused_brgemm(dt, h, A, offs[0], B, offs[1], got, offs[2], D, offs[3], br)
         else:
             rt.brgemm(dt, h, A, offs[0], B, offs[1], got, offs[2], br)
-    what = "brgemm[%s] dt%d m%d n%d k%d br%d lda%d ldb%d ldc%d sa%d sb%d beta0=%d bias=%d relu=%d" % (
-        name, dt, m, n, k, br, lda, ldb, ldc, sa, sb, beta0, bias, relu)
-    if row_blocks:
-        sel = np.concatenate([np.arange(offs[2] + r * ldc, offs[2] + r * ldc + n)
-                              for (r0, rr) in row_blocks for r in range(r0, r0 + rr)])
-        check_close(got[sel], Cref[sel], dt, what, None if Cmag is None else Cmag[sel], k * br)
+    what = "brgemm[%s] dt%d m%d n%d k%d br%d lda%d ldb%d ldc%d sa%d sb%d beta0=%d bias=%d relu=%d%s%s" % (
+        name, dt, m, n, k, br, lda, ldb, ldc, sa, sb, beta0, bias, relu, "" if values is None else " " + values,
+        " poisoned" if poison else "")
+    rows = np.concatenate([np.arange(r0, r0 + rr) for (r0, rr) in (row_blocks or [(0, m)])]).astype(np.int64)
+    win = (offs[2] + ed.c_live_index(rows[:, None], np.arange(n)[None, :], ldc, vnni_c)).reshape(-1)
+    if poison and values != "special":
+        assert np.isfinite(as_f32(Cref[win])).all(), what + ": the oracle read poisoned memory - the live mask is not tight"
+    if values is not None:
+        ed.check_bits(got[win], Cref[win], dt, what, special=values == "special")
     else:
-        win = np.concatenate([np.arange(offs[2] + i * ldc, offs[2] + i * ldc + n) for i in range(m)]) if m and n else np.arange(0)
         check_close(got[win], Cref[win], dt, what, None if Cmag is None else Cmag[win], k * br)
-    # bytes outside the m x n window (ldc padding, guard elements) must be untouched
+    # bytes outside the m x n window (ldc padding, guard elements) must be untouched - bit for bit (poison is NaN)
     mask = np.ones(C.size, dtype=bool)
-    for i in range(m):
-        mask[offs[2] + i * ldc: offs[2] + i * ldc + n] = False
-    assert np.array_equal(got[mask], C[mask]), what + ": wrote outside the output window"
+    mask[(offs[2] + ed.c_live_index(np.arange(m)[:, None], np.arange(n)[None, :], ldc, vnni_c)).reshape(-1)] = False
+    assert np.array_equal(ed.bits(got)[mask], ed.bits(C)[mask]), what + ": wrote outside the output window"
+    if expect is not None:
+        assert expect in name, (expect, name)
     return name
 
 
@@ -691,12 +718,8 @@ def test_binary_eltwise(rt, dt, kind, flags):
         dO = dev(O)
         rt.binary(dt, h, dev(L), 0, dev(R), 0, dO, 0)
         got = host(dO, O)
-        if kind == 4:  # division: device fp32 divide may differ from the host's in the last place
-            check_close(got, ref, dt, "binary div flags %d" % flags)
-            if dt == F32:
-                assert np.abs(got.astype(np.float64) - ref).max() <= 2.5e-7 * np.abs(ref).max()
-        else:
-            assert np.array_equal(got, ref), "binary kind %d flags %d (%d x %d)" % (kind, flags, m, n)
+        # division included: the gfx950 code divides with the correctly rounded v_div_scale / v_div_fmas / v_div_fixup sequence
+        assert np.array_equal(got, ref), "binary kind %d flags %d (%d x %d)" % (kind, flags, m, n)
 
 
 def test_binary_out_aliases_input(rt):
