@@ -13,6 +13,9 @@ Step = one pass of the hot path over one batch of synthetic input:
     unsharded result on every rank (`mlp.gathered_bit_identical`; the run exits 3 if it is false), the one-GPU step of
     the same run next to it (`mlp.one_gpu_same_run`). The weak-scaled C2 (one independent BRGEMM per GPU, no collective:
     the reference has no exchange step on this path) is reported under `c2_weak`.
+A plain run does only what the headline needs: set-up, spin-up, W warm-up steps, the K timed steps, the outputs of
+  --dump-outputs and the result line. Everything else (the other input stream, parity against the oracle, per-launch, PMC and
+  CPU figures, the other BASELINE configs, the per-rank MLP shares, other sizes and shardings at N > 1) runs with --full.
 Timing: inputs resident in HBM, W warm-up steps, then exactly K steps between
 barrier+synchronize pairs, max over ranks (nothing but the K invokes inside the wall-clock region); the
 HIP-event pair for the kernel-side time brackets an immediate repeat of the same K steps (see timed()). FLOPs are the reference's BENCH_TOTAL_FLOPS
@@ -47,6 +50,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=500)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the other input stream, parity against the oracle, "
+                         "per-launch and PMC figures, the CPU baseline, the other BASELINE configs, the per-rank MLP shares and, at "
+                         "N > 1, the bs=32768 and column-sharded variants")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-mlp", action="store_true")
     ap.add_argument("--graph", action="store_true",
@@ -56,8 +63,8 @@ def parse():
                     help="initialise RCCL and run the collectives even with one rank (exercises the N>1 code path)")
     ap.add_argument("--init", choices=["reference", "uniform"], default="reference",
                     help="input stream `value` is quoted on. reference: tpp-run's normal init stream (what the reference "
-                         "benchmarks run on); uniform: U[-1,1) (sign cancellation, highest switching power). The OTHER "
-                         "stream is always measured too and reported as roofline_uniform / roofline_reference")
+                         "benchmarks run on); uniform: U[-1,1) (sign cancellation, highest switching power). With --full "
+                         "the OTHER stream is measured too and reported as roofline_uniform / roofline_reference")
     ap.add_argument("--gather", choices=["peer", "rccl"], default="peer",
                     help="all-gather of the MLP output at N > 1: peer = every rank stores its rows into every peer's buffer through "
                          "IPC-mapped pointers (csrc/peer_gather.hip), falling back to RCCL if the buffers cannot be mapped; rccl = "
@@ -699,14 +706,15 @@ def main():
     mode = "invoke-loop"
     outputs = {}  # --dump-outputs: name -> host copy of what the last timed step produced
     other = "uniform" if args.init == "reference" else "reference"
-    for kind in (other, args.init):  # the stream `value` is quoted on runs last, right after its own warm-up
+    kinds = ((other,) if args.full else ()) + (args.init,)
+    for kind in kinds:  # the stream `value` is quoted on runs last, right after its own warm-up
         hA, hB, hC = inputs(kind)
         dA, dB, dC = (torch.from_numpy(x).cuda() for x in (hA, hB, hC))
 
         def step():
             rt.brgemm(F32, h, dA, 0, dB, 0, dC, 0, br)
 
-        spin_s = 0.06 if kind == args.init else 0.25  # the first stream also wakes the chip up after process start
+        spin_s = 0.25 if kind == kinds[0] else 0.06  # the first stream also wakes the chip up after process start
         spin_n = spin_up(step, sync, spin_s)
         warm(step, W, sync)
         wall, devs = timed(step, K, sync, barrier)
@@ -725,7 +733,7 @@ def main():
         if use_dist:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         runs[kind] = {"wall": float(t[0]), "devs": float(t[1]), "spin_up_s": spin_s, "spin_up_launches": spin_n,
-                      "parity": parity_figures(dC.cpu().numpy(), hA, hB, hC, m, n, k, br) if rank == 0 and world == 1 else None}
+                      "parity": parity_figures(dC.cpu().numpy(), hA, hB, hC, m, n, k, br) if args.full and rank == 0 and world == 1 else None}
     wall, devs = runs[args.init]["wall"], runs[args.init]["devs"]
     value = world * flops * K / wall / 1e9
     kernel_s = devs / K
@@ -740,7 +748,8 @@ def main():
 
     # ------------------------------------------------------------ C4: bf16 3-layer MLP, row-sharded + all-gather
     mlp = None
-    if not args.no_mlp:
+    # at N = 1 the MLP is a secondary figure: a plain run computes it only for --dump-outputs
+    if not args.no_mlp and (args.full or use_dist or args.dump_outputs):
         N = 1024
         hp = rt.unary_dispatch(pkg.UnaryKind.VNNI2, BF16, N, N, N, N, 0)
         # the reference's inputs: weights / biases = the dense constants of `mlir-gen --kernel=const --seed 123`
@@ -920,7 +929,7 @@ def main():
                                      "bit for bit; AND over the ranks" % (ref_kernel, sh.rows, shard_kernel))
             mlp["one_gpu_same_run"] = mlp_n1
             mlp["speedup_vs_one_gpu_same_run"] = round(mlp_n1["ms_per_step"] * 1e-3 / mstep, 3)
-        if world == 1:
+        if world == 1 and args.full:
             # what every rank of a world of 2 / 4 / 8 GPUs would run per step (its row share, no collective), measured on THIS GPU:
             # the one-launch chain and the same share as three launches; python path (this harness) and native (tools/mlp_probe)
             Ks = max(K, 200)  # (short steps: the synchronizes around a 20-step region would be 5-10 % of it)
@@ -946,7 +955,7 @@ def main():
             mlp["per_rank_step_note"] = ("per-rank share of the bs=4096 step for a world of N GPUs, run on one GPU: the scaling model of the "
                                          "row sharding WITHOUT the all-gather (strong-scaling speed-up of the compute part = "
                                          "chain_us[1] / chain_us[N])")
-        if use_dist and not one_device:
+        if use_dist and args.full and not one_device:
             # (not on the one-device test rig: two processes' chip-filling kernels time-slice ONE GPU there, and a gather kernel that
             # spins for a peer whose GEMM cannot get a compute unit meanwhile runs into its - bounded - wait: 2 of 9 runs)
             # the same MLP at a batch where compute dominates (8 x 4096 rows): what the sharding itself scales like
@@ -965,7 +974,7 @@ def main():
 
         # the other sharding of SURVEY.md 8(e): column blocks + an all-gather after EVERY layer; the
         # gathered [W][batch][N/W] activations feed the next layer as a batch-reduce over the rank blocks
-        if use_dist and N % world == 0:
+        if use_dist and args.full and N % world == 0:
             cs = pkg.ColumnShardedMlp(spec, rank, world, rt)
             gx = torch.Generator(device="cpu").manual_seed(11)
             Xf = (torch.randn(spec.batch, N, generator=gx) * 0.5).to(torch.bfloat16).cuda()  # same on every rank
@@ -988,7 +997,7 @@ def main():
 
     # ------------------------------------------------------------ the other BASELINE configs (N=1 only, short)
     others = None
-    if world == 1 and not args.no_mlp:
+    if world == 1 and args.full and not args.no_mlp:
         others = []
         Ko, Wo = max(200, K // 10), max(20, W // 10)  # (the two synchronizes around a timed region cost ~25 us: 50 launches of a 10 us kernel would read 5 % slow)
         # C3: fp32 fused_brgemm + bias + relu, MLP layer 1024->1024, bs=512
@@ -1271,17 +1280,18 @@ def main():
     traffic, traffic_source, traffic_detail = None, None, None
     if rank == 0 and world == 1:
         kname = "brgemm_f32"
-        if not args.no_pmc:
+        if args.full and not args.no_pmc:
             traffic, traffic_detail = live_traffic(kname, args.init)
             traffic_source = "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over tools/c2_probe in this run"
         if traffic is None:
             why = traffic_detail
             traffic, src = committed_traffic(kname)
-            traffic_source = "committed profile %s (%s)" % (src, why if why else "--no-pmc") if traffic is not None else None
+            traffic_source = "committed profile %s (%s)" % (src, why or ("--no-pmc" if args.full else "no PMC passes without --full")) if traffic is not None else None
             traffic_detail = None
-        mfma_busy = None if args.no_pmc else live_mfma_busy(kname, args.init, kernel_s * 1e6)
-        per_launch = per_launch_figures(args.init)
-        if not args.no_cpu_baseline:
+        if args.full:
+            mfma_busy = None if args.no_pmc else live_mfma_busy(kname, args.init, kernel_s * 1e6)
+            per_launch = per_launch_figures(args.init)
+        if args.full and not args.no_cpu_baseline:
             hA, hB, hC = inputs(args.init)
             cpu = cpu_baseline(args.cpu_seconds, hA, hB, hC)
             if others:  # the CPU port on the shapes of the reference's benchmark set, beside the GPU rows of other_configs
@@ -1337,11 +1347,12 @@ def main():
                        "launch": mode, "kernel": rt.kernel_name(h), "flops_per_step_per_gpu": flops,
                        "inputs": inputs_text[args.init]},
             "roofline": roof,
-            "roofline_" + other: roofline_of(other),
-            "parity": {args.init: runs[args.init]["parity"], other: runs[other]["parity"]},
             "per_launch": per_launch,
             "cpu_baseline": cpu,
         }
+        if args.full:
+            line["roofline_" + other] = roofline_of(other)
+            line["parity"] = {args.init: runs[args.init]["parity"], other: runs[other]["parity"]}
         if others:
             hp = [o for o in others if str(o.get("workload", "")).startswith("C2 through HOST pointers")]
             line["deployment"] = {

@@ -4,13 +4,13 @@
 # eltwise bandwidth. Results in gpurun_out/<tag>/.   usage: gpurun --timeout 2400 -- 'bash tools/gpu_official.sh r03_official1'
 TAG=${1:-official}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$PWD
 timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider -s > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 grep -E "passed|failed|error|\[parity\]|rc=|us per step" $OUT/pytest_gpu.log | tail -12
 timeout 600 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o bench -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > $R/$OUT/rocprof_stats_run.json 2> $R/$OUT/rocprof_stats.err )
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o bench -- python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > $R/$OUT/rocprof_stats_run.json 2> $R/$OUT/rocprof_stats.err )
 find /tmp/prof_stats -name "*kernel_stats.csv" -exec cp {} $OUT/rocprof_kernel_stats.csv \;
 # MFMA-busy passes (PMC alone) + kernel stats of the same commands: C2, C3, the C4 layer kernel, the chain kernels
 ( cd /tmp
@@ -40,7 +40,7 @@ timeout 900 python bench.py --refbench --refbench-json $OUT/refbench.json > $OUT
 timeout 300 python tools/split_sweep.py > $OUT/split_sweep.txt 2>&1
 # benchmarks/mlir/*.mlir (base/mha.json, pack.json) as xsmm call scripts: queue on / off, transpose folding on / off, 8 callers
 timeout 300 tools/tpp_replay --cases tools/scripts.cases 2>&1 | grep -v "^[0-9.e-]*$" > $OUT/mlir_scripts.txt
-TPP_BENCH_ONE_DEVICE=1 timeout 600 python bench.py --gpus 2 --steps 6 --warmup 3 > $OUT/bench_gpus2_rig.json 2> $OUT/bench_gpus2_rig.err
+TPP_BENCH_ONE_DEVICE=1 timeout 600 python bench.py --full --gpus 2 --steps 6 --warmup 3 > $OUT/bench_gpus2_rig.json 2> $OUT/bench_gpus2_rig.err
 python tools/sweep.py 2>/dev/null | grep -E "^(f32|bf16)" > $OUT/sweep.txt
 python tools/sweep.py big 2>/dev/null | grep -E "^(f32|bf16)" >> $OUT/sweep.txt
 python tools/sweep.py shards 2>/dev/null | grep -E "^bf16" >> $OUT/sweep.txt
