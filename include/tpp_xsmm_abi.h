@@ -202,7 +202,8 @@ TPP_XSMM_EXPORT int xsmm_hip_fused_brgemm_chain_invoke(int64_t dtype, int64_t n,
  * queued group - all within the 1e-5 bar, but the same invoke on the same data may return different last bits alone, in the first
  * pass of a loop and in its replays. On: no grid merge, no folded transposes, every size-dependent choice is taken as for a group of
  * one, a group holds invokes of one alignment class and one batch count only, single invokes of queue-sized tiles run on the kernel
- * their group runs on, and a chain call runs as one launch only on the tile its layers were planned on. DETERMINISM: run to run
+ * their group runs on, and a chain call runs as one launch only on the tile its layers were planned on. Relayout grids
+ * (xsmm_hip_set_relayout_grid) stay ON in strict mode: they copy raw words, and a copy's bits do not depend on the kernel. DETERMINISM: run to run
  * always (no floating-point atomics anywhere); call to call - alone / first queued pass / replay - under strict mode
  * (tests/test_strict_gpu.py). Choose the mode before the first queued invoke: returns the previous setting, -1 if the tile queue has
  * already recorded groups under the other one. */
@@ -325,6 +326,15 @@ TPP_XSMM_EXPORT int xsmm_hip_force_split(int workgroups_per_tile);
  *  Between a transpose invoke and the gemm invoke that consumes its temporary, no OTHER thread may write the transpose's
  * source: the folded gemm reads the source when it is enqueued, not when the transpose was invoked. */
 TPP_XSMM_EXPORT int xsmm_hip_set_fold_transpose(int enable);
+/* Relayout grids (TPP_HIP_RELAYOUT_GRID=0|1, default 1; tile queue + asynchronous mode only). A recorded queue group of ONE unary
+ * identity (f32 / bf16) or VNNI-2 (bf16) handle without broadcast flags - the per-block invokes a tensor.pack / unpack lowers to -
+ * whose items form at most 16 affine block grids, each writing one dense range, with pairwise disjoint input extents, is launched on every
+ * complete replay as ONE relayout-grid launch (16-byte accesses where bases and strides allow) instead of one workgroup per invoke;
+ * xsmm_hip_last_grouped_kernel then reads "relayout grid: ...". The result is the same bits (a copy of raw words: on in strict mode
+ * too). Any other group runs as before. set returns the previous setting; stats: [0] relayout grid launches, [1] the invokes they
+ * covered. */
+TPP_XSMM_EXPORT int xsmm_hip_set_relayout_grid(int enable);
+TPP_XSMM_EXPORT void xsmm_hip_relayout_grid_stats(int64_t out[2]);
 TPP_XSMM_EXPORT void xsmm_hip_fold_transpose_stats(int64_t out[3]);
 /* The VNNI blocking factor v of bf16 B operands ([k/v][ldb][v]) of gemm / brgemm / fused_brgemm handles dispatched FROM NOW ON with
  * the VNNI_B wire flag: 2 (default) or 4; also TPP_HIP_VNNI_FACTOR. The factor is not on the wire - the reference's compiler and its

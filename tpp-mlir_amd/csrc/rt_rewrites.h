@@ -168,6 +168,69 @@ inline void detect_quads(Segment &S, hipStream_t stream) {
   S.quad_state = 1;
 }
 
+// RELAYOUT GRIDS (rt_relayout.h says what qualifies and why). Called once per recording at its first complete replay, like
+// detect_quads: the run table is uploaded then (not while the stream is captured - look again at the next replay) and every later
+// complete replay launches from it. Stays on in strict mode (a copy's bits do not depend on the kernel).
+static bool relayout_grid_on() { return cfg().relayout_grid.load(std::memory_order_relaxed) != 0; }
+// the launch's text for xsmm_hip_last_grouped_kernel: interned, so that a reader never sees a segment's buffer being rewritten
+static const char *intern_text(const char *s) {
+  static std::mutex mu;
+  static std::unordered_map<std::string, int> texts; // (node-based: a key's characters never move)
+  std::lock_guard<std::mutex> lk(mu);
+  return texts.emplace(s, 0).first->first.c_str();
+}
+inline void detect_relayout(Segment &S, hipStream_t stream) {
+  S.rl_state = -1;
+  const size_t n = S.items.size();
+  const void *desc = S.items[0].desc;
+  if (n < 2 || *(const int *)desc != KIND_UNARY || !launch_relayout_grid) return; // (null: a host-only test build)
+  const UnaryDesc *d = (const UnaryDesc *)desc;
+  const bool f32 = d->dtype == DT_F32;
+  if (d->flags != 0 || d->m > 64 || d->n > 64 || !(d->op == XSMM_UNARY_IDENTITY || (d->op == XSMM_UNARY_VNNI2 && !f32))) return;
+  std::vector<RelayoutItem> io;
+  io.reserve(n);
+  for (const TraceItem &t : S.items) {
+    if (t.desc != desc || t.stream != S.items[0].stream || !t.w.A || !t.w.C) return;
+    io.push_back(RelayoutItem{(uintptr_t)t.w.A, (uintptr_t)t.w.C});
+  }
+  RelayoutRun runs[RELAYOUT_MAX_RUNS];
+  const int nr = relayout_decompose(d->op, f32 ? 4 : 2, d->m, d->n, d->ldi, d->ldo, std::move(io), runs, RELAYOUT_MAX_RUNS);
+  if (nr <= 0) return;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) (void)hipGetLastError();
+  else if (cs != hipStreamCaptureStatusNone) {
+    S.rl_state = 0; // (not now: look again at the next complete replay)
+    return;
+  }
+  int wg = 0; // one workgroup per block
+  for (int k = 0; k < nr; ++k) {
+    runs[k].wg0 = wg;
+    wg += runs[k].R * runs[k].C;
+  }
+  if (S.rl_used) { // the table carried another recording's runs: its last launch must be done (and, first, issued)
+    launcher_drain();
+    HIP_OK(hipStreamSynchronize(S.rl_stream));
+    S.rl_used = false;
+  }
+  if (!S.rl_host) {
+    HIP_OK(hipHostMalloc((void **)&S.rl_host, sizeof(RelayoutRun) * RELAYOUT_MAX_RUNS, hipHostMallocDefault));
+    HIP_OK(hipMalloc((void **)&S.rl_dev, sizeof(RelayoutRun) * RELAYOUT_MAX_RUNS));
+  }
+  std::copy(runs, runs + nr, S.rl_host);
+  HIP_OK(hipMemcpyAsync(S.rl_dev, S.rl_host, sizeof(RelayoutRun) * nr, hipMemcpyHostToDevice, stream));
+  S.rl_used = true; // (the copy reads rl_host)
+  S.rl_stream = stream;
+  int vec = 0;
+  for (int k = 0; k < nr; ++k) vec += runs[k].vec;
+  char text[160];
+  snprintf(text, sizeof(text), "relayout grid: %d run%s, %zu blocks of %ldx%ld, %s %s, %d of them 16-byte", nr, nr == 1 ? "" : "s", n, (long)d->m, (long)d->n,
+           d->op == XSMM_UNARY_VNNI2 ? "vnni2" : "identity", f32 ? "f32" : "bf16", vec);
+  S.rl_trace = intern_text(text);
+  S.rl_runs = nr;
+  S.rl_wg = wg;
+  S.rl_state = 1;
+}
+
 // ---- deferred transposes (round 5) ------------------------------------------------------------------------------------
 // A contraction whose B operand is transposed in memory reaches the runtime as TWO invokes per tile: xsmm.unary transpose into a
 // small temporary, then xsmm.gemm reading it (ConvertLinalgToXsmm; test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62 has the

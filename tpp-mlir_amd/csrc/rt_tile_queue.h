@@ -133,6 +133,7 @@ struct Footprint {
 
 // tile-queue counters (xsmm_hip_tile_queue_stats): launches, invokes queued with full bookkeeping / by replay, abandoned replays
 std::atomic<int64_t> g_q_launches{0}, g_q_checked{0}, g_q_replayed{0}, g_q_abandoned{0}, g_q_terminated{0};
+std::atomic<int64_t> g_rl_launches{0}, g_rl_items{0}; // relayout grid launches / the invokes they covered (xsmm_hip_relayout_grid_stats)
 // (bumped only by whoever owns the queue state at that moment - the inline queue's lock holder or the scheduler thread: a
 // plain load + store, not a locked read-modify-write on the enqueue path)
 inline void bump(std::atomic<int64_t> &c) { c.store(c.load(std::memory_order_relaxed) + 1, std::memory_order_relaxed); }
@@ -177,6 +178,14 @@ struct Segment {
   size_t quad_cap = 0;
   bool quad_used = false;
   hipStream_t quad_stream = nullptr;
+  // RELAYOUT GRID (detect_relayout in rt_rewrites.h): the group's identity / VNNI-2 unary invokes are rl_runs affine block grids - a
+  // complete replay is ONE launch of relayout.hip over rl_dev (rl_wg workgroups, one block each). 0: not looked at yet, 1: yes,
+  // -1: no. The run table travels with the segment like the quads' blocks and follows their rules.
+  int rl_state = 0, rl_runs = 0, rl_wg = 0;
+  RelayoutRun *rl_host = nullptr, *rl_dev = nullptr;
+  bool rl_used = false;
+  hipStream_t rl_stream = nullptr;
+  const char *rl_trace = nullptr; // xsmm_hip_last_grouped_kernel's text for the launch (interned: outlives the segment)
   // Called with the inline queue's lock held, once per RECORDING (a steady-state replay never comes here). The buffers are sized
   // for the largest group (TileQueue::CAP) the first time a segment needs them and then travel with it (store_recording swaps
   // segments, so at most NSEG + 1 sets exist per queue: allocation is a start-up cost, not a per-recording one); they live as long
@@ -285,6 +294,7 @@ struct Segment {
     dev_epoch = 0;
     grid_state = 0;
     quad_state = 0;
+    rl_state = 0;
   }
   int index_of(const void *d, const WorkItem &w, hipStream_t st) const {
     if (table.empty()) return -1;
@@ -302,6 +312,8 @@ struct Segment {
 
 inline void detect_grid(Segment &S); // rt_rewrites.h (GRID MERGE)
 inline void detect_quads(Segment &S, hipStream_t stream); // rt_rewrites.h (QUADS)
+inline void detect_relayout(Segment &S, hipStream_t stream); // rt_rewrites.h (RELAYOUT GRIDS)
+static bool relayout_grid_on();
 static bool grid_merge_on();
 extern std::atomic<const char *> g_last_merged;
 
@@ -488,6 +500,7 @@ struct TileQueue {
     LaunchReq r;
     r.stream = pending.stream;
     if (pending.kind == KIND_GEMM && S.grid_state != 1 && S.quad_state == 0) detect_quads(S, pending.stream);
+    if (pending.kind == KIND_UNARY && S.rl_state == 0 && relayout_grid_on()) detect_relayout(S, pending.stream);
     if (pending.kind == KIND_GEMM && S.grid_state == 1) {
       r.kind = -1;
       r.desc = S.grid_desc;
@@ -502,6 +515,17 @@ struct TileQueue {
       r.br = S.items[0].w.br;
       S.quad_used = true;
       S.quad_stream = pending.stream;
+    } else if (pending.kind == KIND_UNARY && S.rl_state == 1 && relayout_grid_on()) {
+      g_last_merged.store(S.rl_trace, std::memory_order_relaxed);
+      r.kind = -3;
+      r.desc = pending.desc;
+      r.list = (const WorkItem *)S.rl_dev;
+      r.n = S.rl_runs;
+      r.wgs = S.rl_wg;
+      S.rl_used = true;
+      S.rl_stream = pending.stream;
+      bump(g_rl_launches);
+      g_rl_items.store(g_rl_items.load(std::memory_order_relaxed) + pending.n, std::memory_order_relaxed);
     } else {
       g_last_merged.store(nullptr, std::memory_order_relaxed);
       r.kind = pending.kind;
@@ -599,7 +623,7 @@ struct TileQueue {
       if (!defer) issue_pending();
     } else {
       launcher_drain(); // (launches handed to the launch thread come first on the stream)
-      if (kind == KIND_GEMM) g_last_merged.store(nullptr, std::memory_order_relaxed);
+      g_last_merged.store(nullptr, std::memory_order_relaxed); // (every kind: a relayout grid sets it for unary groups too)
       if (kind == KIND_GEMM) HIP_OK(launch_gemm_grouped(*(const GemmDesc *)desc, pinned[slot], n, vec_ok, out_ok, pair_ok, pinned[slot][0].br, stream));
       else if (kind == KIND_UNARY) HIP_OK(launch_unary_grouped(*(const UnaryDesc *)desc, pinned[slot], n, stream));
       else HIP_OK(launch_binary_grouped(*(const BinaryDesc *)desc, pinned[slot], n, stream));

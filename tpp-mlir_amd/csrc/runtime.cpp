@@ -14,6 +14,7 @@
 #include "xsmm_desc.h"
 #include "chain_args.h"
 #include "host_cache.h"
+#include "rt_relayout.h" // relayout grids: affine runs of a recorded pack / unpack group (plain C++, outside the unit namespace)
 
 #include <dlfcn.h>
 #include <linux/futex.h>
@@ -48,7 +49,7 @@ namespace {
 #include "rt_tile_queue.h" // tile queue state: footprints, trace cache (segments), direct window, group bookkeeping
 #include "rt_scheduler.h"  // per-caller rings merged by ONE scheduler thread
 #include "rt_enqueue.h"    // the ways into the queue, caller state, enqueue_item (the per-invoke host path)
-#include "rt_rewrites.h"  // grid merge, deferred transposes
+#include "rt_rewrites.h"  // grid merge, quads, relayout grids, deferred transposes
 #include "rt_invoke.h"    // strict-mode items, host-cache scope, gemm_invoke_common
 #include "rt_chain.h"     // layer chains: launch, probation, journal, re-run
 
@@ -484,6 +485,15 @@ extern "C" int xsmm_hip_set_launch_thread(int enable) {
 extern "C" void xsmm_hip_launch_thread_stats(int64_t out[2]) {
   out[0] = launcher().handed.load(std::memory_order_relaxed);
   out[1] = launcher().running.load(std::memory_order_relaxed) ? 1 : 0;
+}
+// relayout grids (rt_relayout.h): returns the previous setting; out[0] = relayout grid launches, out[1] = the unary invokes they covered
+extern "C" int xsmm_hip_set_relayout_grid(int enable) {
+  flush_tile_queue(); // (drains it: a group already decided keeps its launch)
+  return cfg().relayout_grid.exchange(enable != 0);
+}
+extern "C" void xsmm_hip_relayout_grid_stats(int64_t out[2]) {
+  out[0] = g_rl_launches.load(std::memory_order_relaxed);
+  out[1] = g_rl_items.load(std::memory_order_relaxed);
 }
 extern "C" int xsmm_hip_set_fold_transpose(int enable) {
   flush_tile_queue(); // (launches a remembered transpose)

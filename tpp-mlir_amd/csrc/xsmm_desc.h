@@ -74,6 +74,17 @@ struct QuadItem {
   uint32_t da, db;
 };
 
+// One run of a RELAYOUT GRID (tile queue, rt_relayout.h): R x C blocks of one unary identity / VNNI-2 descriptor, block (r, c) reads
+// in + r in_r + c in_c and writes out + r out_r + c out_c (strides in ELEMENTS). wg0: the first workgroup of the run (runs in
+// ascending order); vec: bases and strides allow 16-byte accesses (else the kernel's element path).
+struct RelayoutRun {
+  const void *in;
+  void *out;
+  int64_t in_r, in_c, out_r, out_c;
+  int32_t R, C;
+  int32_t wg0, vec;
+};
+
 // ---- kernel launchers (all enqueue on `stream`, never synchronise) --------------
 // pointers are device pointers with element offsets already applied.
 hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C, const void *D,
@@ -121,5 +132,10 @@ hipError_t launch_binary(const BinaryDesc &d, const void *lhs, const void *rhs, 
 // n_items invokes of ONE unary / binary descriptor with m, n <= 64 in one launch
 hipError_t launch_unary_grouped(const UnaryDesc &d, const WorkItem *items, int n_items, hipStream_t stream);
 hipError_t launch_binary_grouped(const BinaryDesc &d, const WorkItem *items, int n_items, hipStream_t stream);
+// RELAYOUT GRIDS (relayout.hip): the blocks of n_runs runs (device array) of an identity (f32, bf16) or VNNI-2 (bf16) descriptor
+// in ONE launch of n_wg workgroups, one block each. Bit-exact word moves. Weak: the host-only sanitizer builds of runtime.cpp
+// (tests/tsan) link it without the gfx950 kernels - there it is null and the tile queue never chooses a relayout grid; the product
+// library always defines it (relayout.hip).
+__attribute__((weak)) hipError_t launch_relayout_grid(const UnaryDesc &d, const RelayoutRun *runs, int n_runs, int n_wg, hipStream_t stream);
 
 } // namespace tpp

@@ -111,6 +111,8 @@ _SIGNATURES = {
     "xsmm_hip_force_split": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_fold_transpose_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_relayout_grid": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_relayout_grid_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_vnni_factor": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_get_vnni_factor": (ctypes.c_int, []),
     "xsmm_hip_set_f32_precision": (ctypes.c_int, [ctypes.c_int]),
@@ -327,6 +329,16 @@ class XsmmRuntime:
         """(gemm invokes served from a transpose's source, remembered transposes dropped as dead, remembered transposes launched)"""
         out = (ctypes.c_int64 * 3)()
         self.lib.xsmm_hip_fold_transpose_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_relayout_grid(self, enable):
+        """replayed pack / unpack groups (identity / VNNI-2 block grids) as ONE relayout-grid launch (default on); returns the previous setting"""
+        return self.lib.xsmm_hip_set_relayout_grid(1 if enable else 0)
+
+    def relayout_grid_stats(self):
+        """(relayout grid launches, unary invokes they covered)"""
+        out = (ctypes.c_int64 * 2)()
+        self.lib.xsmm_hip_relayout_grid_stats(out)
         return tuple(int(v) for v in out)
 
     def set_vnni_factor(self, v):
