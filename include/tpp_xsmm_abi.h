@@ -326,6 +326,24 @@ TPP_XSMM_EXPORT int xsmm_hip_force_split(int workgroups_per_tile);
  *  Between a transpose invoke and the gemm invoke that consumes its temporary, no OTHER thread may write the transpose's
  * source: the folded gemm reads the source when it is enqueued, not when the transpose was invoked. */
 TPP_XSMM_EXPORT int xsmm_hip_set_fold_transpose(int enable);
+/* Epilogue fold (TPP_HIP_FOLD_EPILOGUE=0|1, default 1; tile queue + asynchronous mode, device operands only). The compiler fuses a
+ * gemm tile with its element-wise epilogue only as brgemm + binary add bcast_col + unary relu (CombineXsmmOp); every other epilogue -
+ * a bias alone, a relu alone, a residual add, a scale, other broadcasts - reaches the runtime as a gemm invoke followed by one or two
+ * element-wise invokes on that tile's output. A binary add / mul / sub / div (any broadcast of its OTHER operand, the tile in either
+ * position) or a unary identity / relu / zero without flags, on the same stream and dtype, whose input is exactly the latest value of
+ * one queued GEMM item (same address, leading dimension and m x n, no broadcast) joins that item's group as the next stage of its
+ * chain instead of flushing the group: at most two stages per item, stage s of every item the same handle in the same position, the
+ * other operand written by nothing queued, the output either the tile itself (in place) or touching nothing the group reads or writes.
+ * The group then runs as its GEMM launch plus ONE epilogue-program launch for all of its post-ops, and a recorded group replays that
+ * way. Every stage rounds at its own store with the element-wise op's own arithmetic: the same bits as the unfolded invokes (on in
+ * strict mode too). Anything else flushes as before. set returns the previous setting (with 0, recorded folded groups are no longer replayed);
+ * stats: [0] post-op invokes folded, [1] epilogue-program launches, [2] element-wise invokes on a queued GEMM group that flushed it
+ * because they were not eligible.
+ * Between a post-op invoke and the next synchronisation point (xsmm_hip_flush, a synchronize, leaving asynchronous mode) no OTHER
+ * thread may write the post-op's second operand (bias, residual, scale): the epilogue reads it when the group is launched, not when
+ * the post-op was invoked. */
+TPP_XSMM_EXPORT int xsmm_hip_set_fold_epilogue(int enable);
+TPP_XSMM_EXPORT void xsmm_hip_fold_epilogue_stats(int64_t out[3]);
 /* Relayout grids (TPP_HIP_RELAYOUT_GRID=0|1, default 1; tile queue + asynchronous mode only). A recorded queue group of ONE unary
  * identity (f32 / bf16) or VNNI-2 (bf16) handle without broadcast flags - the per-block invokes a tensor.pack / unpack lowers to -
  * whose items form at most 16 affine block grids, each writing one dense range, with pairwise disjoint input extents, is launched on every

@@ -11,6 +11,7 @@
 // IDENTITY / ZERO / TRANSPOSE / VNNI2 are bit-exact moves in the storage type
 // (XsmmRunnerUtils.cpp:29-59).
 #include "gemm_common.h"
+#include "eltwise_ops.h"
 #include "xsmm_desc.h"
 
 namespace tpp {
@@ -19,7 +20,6 @@ typedef unsigned int u32x4_e __attribute__((ext_vector_type(4)));
 
 enum : int64_t { U_IDENTITY = 1, U_ZERO = 2, U_RELU = 5, U_VNNI2 = 28, U_TRANSPOSE = 29 };
 enum : int64_t { UF_ROW = 2, UF_COL = 4, UF_SCALAR = 8 };
-enum : int64_t { B_ADD = 1, B_MUL = 2, B_SUB = 3, B_DIV = 4 };
 enum : int64_t { BF_ROW0 = 1, BF_ROW1 = 2, BF_COL0 = 4, BF_COL1 = 8, BF_SC0 = 16, BF_SC1 = 32 };
 enum : int { BC_NONE = 0, BC_ROW = 1, BC_COL = 2, BC_SCALAR = 3 };
 
@@ -116,8 +116,7 @@ __global__ __launch_bounds__(256) void unary_kernel(int op, int bc, int64_t m, i
     if (op == (int)U_RELU) {
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
-        const float f = Bits<T>::to_f32(x.v[e]);
-        x.v[e] = Bits<T>::from_f32(f > 0.0f ? f : 0.0f);
+        x.v[e] = Bits<T>::from_f32(ew_relu(Bits<T>::to_f32(x.v[e])));
       }
     }
     // (a pure fill - zero / scalar broadcast - keeps plain stores: nontemporal ones measured 7.4 -> 5.8 TB/s on a 256 MiB fill)
@@ -156,15 +155,7 @@ __global__ __launch_bounds__(256) void binary_kernel(int op, int bc0, int bc1, i
     Pack<T, VEC> x;
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-      const float a = Bits<T>::to_f32(l.v[e]), b = Bits<T>::to_f32(r.v[e]);
-      float c;
-      switch (op) {
-      case (int)B_ADD: c = a + b; break;
-      case (int)B_MUL: c = a * b; break;
-      case (int)B_SUB: c = a - b; break;
-      default: c = a / b; break;
-      }
-      x.v[e] = Bits<T>::from_f32(c);
+      x.v[e] = Bits<T>::from_f32(ew_binary(op, Bits<T>::to_f32(l.v[e]), Bits<T>::to_f32(r.v[e])));
     }
     store_stream<T, VEC, true>(out + o, x);
   };
@@ -319,8 +310,7 @@ __global__ __launch_bounds__(256) void unary_grouped_kernel(int op, int bc, int 
     if (op != (int)U_ZERO) {
       x = load_operand<T, 1>(in, bc, i, j, ldi).v[0];
       if (op == (int)U_RELU) {
-        const float f = Bits<T>::to_f32(x);
-        x = Bits<T>::from_f32(f > 0.0f ? f : 0.0f);
+        x = Bits<T>::from_f32(ew_relu(Bits<T>::to_f32(x)));
       }
     }
     out[i * ldo + j] = x;
@@ -337,15 +327,46 @@ __global__ __launch_bounds__(256) void binary_grouped_kernel(int op, int bc0, in
     const int i = idx / n, j = idx - i * n;
     const float a = Bits<T>::to_f32(load_operand<T, 1>(lhs, bc0, i, j, ldl).v[0]);
     const float b = Bits<T>::to_f32(load_operand<T, 1>(rhs, bc1, i, j, ldr).v[0]);
-    float c;
-    switch (op) {
-    case (int)B_ADD: c = a + b; break;
-    case (int)B_MUL: c = a * b; break;
-    case (int)B_SUB: c = a - b; break;
-    default: c = a / b; break;
-    }
-    out[i * ldo + j] = Bits<T>::from_f32(c);
+    out[i * ldo + j] = Bits<T>::from_f32(ew_binary(op, a, b));
   }
+}
+
+// EPILOGUE PROGRAM of a folded GEMM group (xsmm_desc.h PostProgram): workgroup b continues item b's output tile through the
+// program's post-ops. The value is kept in the storage type between stages and every stage is the arithmetic of the invoke it
+// stands for (binary_grouped_kernel / unary_grouped_kernel: f32 compute, one rounding at the stage's store, identity a bit move).
+// A stage whose output the next stage overwrites in place is not stored (same bytes once the launch is done).
+template <typename T>
+__global__ __launch_bounds__(256) void postop_grouped_kernel(PostProgram p, const PostItem *__restrict__ items) {
+  const PostItem it = items[blockIdx.x];
+  const T *c = (const T *)it.C;
+  const bool st0 = !(p.n > 1 && it.out[1] == it.out[0]);
+  for (int idx = threadIdx.x; idx < p.m * p.cols; idx += 256) {
+    const int i = idx / p.cols, j = idx - i * p.cols;
+    T x = c[i * p.ldc + j];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (s >= p.n) break;
+      const PostOp &o = p.op[s];
+      if (o.op == PO_ZERO) x = T(0);
+      else if (o.op == PO_RELU) x = Bits<T>::from_f32(ew_relu(Bits<T>::to_f32(x)));
+      else if (o.op != PO_IDENTITY) {
+        const float y = Bits<T>::to_f32(load_operand<T, 1>((const T *)it.other[s], o.bc, i, j, o.ld).v[0]), v = Bits<T>::to_f32(x);
+        x = Bits<T>::from_f32(o.pos == 0 ? ew_binary(o.op, v, y) : ew_binary(o.op, y, v));
+      }
+      if (s == 1 || st0) ((T *)it.out[s])[i * o.ldo + j] = x;
+    }
+  }
+}
+
+hipError_t launch_postop_grouped(const PostProgram &p, const PostItem *items, int n_items, hipStream_t s) {
+  if (n_items <= 0 || p.m <= 0 || p.cols <= 0) return hipSuccess;
+  if (p.n < 1 || p.n > 2 || p.m > 64 || p.cols > 64) return hipErrorInvalidValue;
+  for (int done = 0; done < n_items; done += 65535) { // (gridDim.x: one item per workgroup)
+    const int n = n_items - done < 65535 ? n_items - done : 65535;
+    if (p.dtype == DT_F32) hipLaunchKernelGGL((postop_grouped_kernel<float>), dim3((unsigned)n), dim3(256), 0, s, p, items + done);
+    else hipLaunchKernelGGL((postop_grouped_kernel<unsigned short>), dim3((unsigned)n), dim3(256), 0, s, p, items + done);
+  }
+  return hipGetLastError();
 }
 
 static inline int unary_bc(int64_t flags) {

@@ -38,6 +38,7 @@ struct Config {
   std::atomic<int> vnni_factor{2}; // blocking factor of VNNI B operands dispatched from now on (xsmm_hip_set_vnni_factor / TPP_HIP_VNNI_FACTOR)
   int trace = 0; // TPP_HIP_TRACE: 1 = one stderr line per dispatch + a roctx range per invoke, 2 = also one stderr line per invoke
   std::atomic<int> fold_transpose{1}; // TPP_HIP_FOLD_TRANSPOSE / xsmm_hip_set_fold_transpose: transposes that feed a gemm's B operand are folded into it
+  std::atomic<int> fold_epilogue{1};  // TPP_HIP_FOLD_EPILOGUE / xsmm_hip_set_fold_epilogue: element-wise invokes on a queued GEMM tile join its group (rt_tile_queue.h)
   std::atomic<int> relayout_grid{1};  // TPP_HIP_RELAYOUT_GRID / xsmm_hip_set_relayout_grid: replayed pack / unpack groups run as relayout grids (rt_relayout.h)
   // TPP_HIP_STRICT / xsmm_hip_set_strict (round 6): the kernel an invoke runs on is a function of its descriptor,
   // batch count and own pointer alignment only - no grid merge, no folded transposes, no kernel family chosen by the size of the
@@ -52,6 +53,7 @@ struct Config {
     }
     if (const char *e = getenv("TPP_HIP_FOLD_TRANSPOSE")) fold_transpose = atoi(e) != 0;
     if (const char *e = getenv("TPP_HIP_RELAYOUT_GRID")) relayout_grid = atoi(e) != 0;
+    if (const char *e = getenv("TPP_HIP_FOLD_EPILOGUE")) fold_epilogue = atoi(e) != 0;
     if (const char *e = getenv("TPP_HIP_ASYNC")) async = atoi(e) != 0;
     if (const char *e = getenv("TPP_HIP_TRACE")) trace = atoi(e);
     if (const char *e = getenv("TPP_HIP_VARIANT")) forced_variant = atoi(e);

@@ -143,7 +143,7 @@ __attribute__((always_inline)) inline bool enqueue_item(const void *desc, const 
               me->count = 0;
             }
             const uint32_t hint = me->hint;
-            if (hint < S.n_items && S.items[hint].same(desc, item, s) && S.mark_solo((int)hint)) {
+            if (hint < S.n_items && S.items[hint].same(desc, item, s) && S.order_ok((int)hint) && S.mark_solo((int)hint)) {
               ++me->count;
               me->hint = hint + 1;
               joined = true;
@@ -202,7 +202,7 @@ __attribute__((noinline)) bool enqueue_item_slow(const void *desc, const WorkIte
         int idx = -1;
         if (me->hint < S.items.size() && S.items[me->hint].same(desc, item, s)) idx = (int)me->hint;
         else idx = S.index_of(desc, item, s);
-        if (idx >= 0 && (solo ? S.mark_solo(idx) : S.mark(idx))) {
+        if (idx >= 0 && S.order_ok(idx) && (solo ? S.mark_solo(idx) : S.mark(idx))) {
           ++me->count;
           me->hint = (uint32_t)idx + 1;
           joined = true;

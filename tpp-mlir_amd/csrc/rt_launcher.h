@@ -29,12 +29,17 @@ struct LaunchReq {
   int wgs = 0;
   WorkItem w{};
   hipStream_t stream = nullptr;
+  const PostItem *post = nullptr; // KIND_GEMM: the group's epilogue program runs behind it over post[0 .. n) (rt_tile_queue.h)
+  PostProgram prog{};
 };
 inline void issue_launch(const LaunchReq &r) {
   if (r.kind == -1) HIP_OK(launch_gemm(*(const GemmDesc *)r.desc, r.w.A, r.w.B, r.w.C, r.w.D, r.w.br, r.stream));
   else if (r.kind == -2) HIP_OK(launch_gemm_quads(*(const GemmDesc *)r.desc, (const QuadItem *)r.list, r.n, r.br, r.stream));
   else if (r.kind == -3) HIP_OK(launch_relayout_grid(*(const UnaryDesc *)r.desc, (const RelayoutRun *)r.list, r.n, r.wgs, r.stream));
-  else if (r.kind == KIND_GEMM) HIP_OK(launch_gemm_grouped(*(const GemmDesc *)r.desc, r.list, r.n, r.vec_ok, r.out_ok, r.pair_ok, r.br, r.stream));
+  else if (r.kind == KIND_GEMM) {
+    HIP_OK(launch_gemm_grouped(*(const GemmDesc *)r.desc, r.list, r.n, r.vec_ok, r.out_ok, r.pair_ok, r.br, r.stream));
+    if (r.post) HIP_OK(launch_postop_grouped(r.prog, r.post, r.n, r.stream));
+  }
   else if (r.kind == KIND_UNARY) HIP_OK(launch_unary_grouped(*(const UnaryDesc *)r.desc, r.list, r.n, r.stream));
   else HIP_OK(launch_binary_grouped(*(const BinaryDesc *)r.desc, r.list, r.n, r.stream));
 }

@@ -133,6 +133,7 @@ struct Footprint {
 
 // tile-queue counters (xsmm_hip_tile_queue_stats): launches, invokes queued with full bookkeeping / by replay, abandoned replays
 std::atomic<int64_t> g_q_launches{0}, g_q_checked{0}, g_q_replayed{0}, g_q_abandoned{0}, g_q_terminated{0};
+std::atomic<int64_t> g_fe_folded{0}, g_fe_groups{0}, g_fe_declined{0}; // epilogue fold (xsmm_hip_fold_epilogue_stats)
 std::atomic<int64_t> g_rl_launches{0}, g_rl_items{0}; // relayout grid launches / the invokes they covered (xsmm_hip_relayout_grid_stats)
 // (bumped only by whoever owns the queue state at that moment - the inline queue's lock holder or the scheduler thread: a
 // plain load + store, not a locked read-modify-write on the enqueue path)
@@ -143,6 +144,7 @@ struct TraceItem {
   const void *desc = nullptr;
   WorkItem w{};
   hipStream_t stream = nullptr;
+  int depth = 0; // epilogue fold: 0 = a GEMM item (or any item of a plain group), s = the s-th post-op of the chain of one GEMM item
   bool same(const void *d, const WorkItem &x, hipStream_t s) const {
     return desc == d && w.A == x.A && w.B == x.B && w.C == x.C && w.D == x.D && w.br == x.br && stream == s;
   }
@@ -186,6 +188,15 @@ struct Segment {
   bool rl_used = false;
   hipStream_t rl_stream = nullptr;
   const char *rl_trace = nullptr; // xsmm_hip_last_grouped_kernel's text for the launch (interned: outlives the segment)
+  // EPILOGUE FOLD (TileQueue::try_fold): a GEMM group with post-ops. items hold the GEMM invokes (depth 0) and their post-ops; every
+  // GEMM item carries the whole program (post_n stages, recorded only then). parent[i]: the item whose value post-op i continues
+  // (-1: a GEMM item) - a post-op joins a replay only after its parent has (order_ok); child[i]: the next stage of i's chain.
+  int post_n = 0, n_gemm = 0;
+  int post_pos[2] = {0, 0};
+  PostProgram prog{};
+  std::vector<int32_t> parent, child;
+  PostItem *post_list = nullptr, *post_dev = nullptr; // the side array of a complete replay (pinned / device), next to list / list_dev
+  size_t post_cap = 0;
   // Called with the inline queue's lock held, once per RECORDING (a steady-state replay never comes here). The buffers are sized
   // for the largest group (TileQueue::CAP) the first time a segment needs them and then travel with it (store_recording swaps
   // segments, so at most NSEG + 1 sets exist per queue: allocation is a start-up cost, not a per-recording one); they live as long
@@ -202,6 +213,7 @@ struct Segment {
       HIP_OK(hipStreamSynchronize(list_stream));
     }
     list_used = false;
+    if (post_n) return ensure_post_list(stream, cap);
     if (list_cap < items.size()) {
       if (list) HIP_OK(hipHostFree(list));
       if (list_dev) HIP_OK(hipFree(list_dev));
@@ -215,6 +227,61 @@ struct Segment {
     list_stream = stream;
     list_valid = true;
     return true;
+  }
+  // the work list of a folded group: its GEMM items in recorded order, and each one's chain in the side array
+  bool ensure_post_list(hipStream_t stream, size_t cap) {
+    if (list_cap < items.size()) {
+      if (list) HIP_OK(hipHostFree(list));
+      if (list_dev) HIP_OK(hipFree(list_dev));
+      list_cap = items.size() < cap ? cap : items.size();
+      HIP_OK(hipHostMalloc((void **)&list, sizeof(WorkItem) * list_cap, hipHostMallocDefault));
+      HIP_OK(hipMalloc((void **)&list_dev, sizeof(WorkItem) * list_cap));
+    }
+    if (post_cap < items.size()) {
+      if (post_list) HIP_OK(hipHostFree(post_list));
+      if (post_dev) HIP_OK(hipFree(post_dev));
+      post_cap = items.size() < cap ? cap : items.size();
+      HIP_OK(hipHostMalloc((void **)&post_list, sizeof(PostItem) * post_cap, hipHostMallocDefault));
+      HIP_OK(hipMalloc((void **)&post_dev, sizeof(PostItem) * post_cap));
+    }
+    int k = 0;
+    for (size_t i = 0; i < items.size(); ++i) {
+      if (parent[i] >= 0) continue;
+      list[k] = items[i].w;
+      post_list[k] = chain_of((int)i);
+      ++k;
+    }
+    HIP_OK(hipMemcpyAsync(list_dev, list, sizeof(WorkItem) * k, hipMemcpyHostToDevice, stream));
+    HIP_OK(hipMemcpyAsync(post_dev, post_list, sizeof(PostItem) * k, hipMemcpyHostToDevice, stream));
+    list_used = true;
+    list_stream = stream;
+    list_valid = true;
+    return true;
+  }
+  // the value post-op t continues (as try_fold matched it): a binary's operand in position pos, a unary's input - a zero reads nothing
+  // and continues the tile it overwrites, whatever input pointer its invoke was given
+  static const void *post_input(const TraceItem &t, int pos) {
+    if (*(const int *)t.desc == KIND_BINARY) return pos == 0 ? t.w.A : t.w.B;
+    return ((const UnaryDesc *)t.desc)->op == XSMM_UNARY_ZERO ? t.w.C : t.w.A;
+  }
+  // the chain of GEMM item g as the epilogue kernel reads it; *level = its stages present (those marked in this round if `marked`)
+  PostItem chain_of(int g, bool marked = false, int *level = nullptr) const {
+    PostItem p{items[g].w.C, {nullptr, nullptr}, {nullptr, nullptr}};
+    int s = 0;
+    for (int c = child[g]; c >= 0 && s < 2; c = child[c], ++s) {
+      if (marked && __atomic_load_n(&seen[c], __ATOMIC_RELAXED) != round) break;
+      const TraceItem &t = items[c];
+      p.other[s] = *(const int *)t.desc == KIND_BINARY ? (post_pos[s] == 0 ? t.w.B : t.w.A) : nullptr;
+      p.out[s] = t.w.C;
+    }
+    if (level) *level = s;
+    return p;
+  }
+  // a post-op may join a replay only after the item it continues has joined (its value is computed in the same launch)
+  __attribute__((always_inline)) bool order_ok(int idx) const {
+    if (__builtin_expect(!post_n, 1)) return true;
+    const int32_t p = parent[idx];
+    return p < 0 || __atomic_load_n(&seen[p], __ATOMIC_RELAXED) == round;
   }
   // Proof that every recorded pointer is device memory, per synchronisation epoch (DeviceRanges): the (few) allocations that hold
   // them, collected the first time the group is replayed and re-verified - same base, same extent - once per epoch by whoever
@@ -288,6 +355,29 @@ struct Segment {
     }
     seen.assign(items.size(), 0);
     n_items = (uint32_t)items.size();
+    parent.clear();
+    child.clear();
+    n_gemm = (int)items.size();
+    if (post_n) { // the value a post-op continues is the output of the item one stage below it with that address
+      parent.assign(items.size(), -1);
+      child.assign(items.size(), -1);
+      std::unordered_map<uint64_t, int32_t> at; // (depth, output address) -> item (outputs of one stage are disjoint: try_fold)
+      auto key = [](int depth, const void *p) { return ((uint64_t)(uintptr_t)p << 2) | (uint64_t)depth; };
+      for (size_t i = 0; i < items.size(); ++i) at[key(items[i].depth, items[i].w.C)] = (int32_t)i;
+      n_gemm = 0;
+      for (size_t i = 0; i < items.size(); ++i) {
+        const TraceItem &t = items[i];
+        if (t.depth == 0) {
+          ++n_gemm;
+          continue;
+        }
+        const void *in = post_input(t, post_pos[t.depth - 1]);
+        auto f = at.find(key(t.depth - 1, in));
+        if (f == at.end()) die("tpp-xsmm-hip: internal error: a recorded post-op without the item it continues");
+        parent[i] = f->second;
+        child[f->second] = (int32_t)i;
+      }
+    }
     round = 0;
     list_valid = false;
     n_alloc = -1;
@@ -428,6 +518,18 @@ struct TileQueue {
   bool vec_ok = true, out_ok = true, pair_ok = true;
   int n = 0;
   Footprint reads, writes;
+  // EPILOGUE FOLD of the group being collected (try_fold): the program so far (post_n stages of the handles post_desc, the continued
+  // value in operand position post_pos), per work-list item its chain (post[i]) and the stages it has (have[i]), and the address of
+  // every item's latest value (tip) with its leading dimension (tip_ld). Built when the group's first post-op arrives (fold_on).
+  bool fold_on = false;
+  int post_n = 0;
+  const void *post_desc[2] = {nullptr, nullptr};
+  int post_pos[2] = {0, 0};
+  std::vector<PostItem> post;
+  std::vector<uint8_t> have;
+  std::vector<int64_t> tip_ld;
+  std::unordered_map<uintptr_t, int> tip;
+  PostItem *post_pinned[SLOTS] = {}; // side arrays next to pinned[] (same slot, same lifetime)
   // Work lists live in host-pinned (device-mapped) memory and every workgroup reads its 40-byte item over PCIe, once,
   // at its head. Moving the list to HBM with one hipMemcpyAsync in front of each grouped launch was built and
   // measured (profiles/r02_tile_queue_device_lists.txt): the copy costs 15-20 us of host time per flush on this
@@ -456,6 +558,50 @@ struct TileQueue {
     bool vec_ok = true, out_ok = true, pair_ok = true;
     hipStream_t stream = nullptr;
   } pending;
+  // the epilogue program of post-op stages `stages` of handles pd / positions pp behind GEMM descriptor g (a launch's kernel argument)
+  static PostProgram program(const GemmDesc &g, const void *const *pd, const int *pp, int stages) {
+    PostProgram r{};
+    r.n = stages;
+    r.m = (int)g.m;
+    r.cols = (int)g.n;
+    r.dtype = g.dtype;
+    r.ldc = g.ldc;
+    auto bc = [](int64_t f, int64_t row, int64_t col, int64_t sc) { return (f & sc) ? 3 : (f & row) ? 1 : (f & col) ? 2 : 0; };
+    for (int s = 0; s < stages; ++s) {
+      PostOp &o = r.op[s];
+      o.pos = pp[s];
+      if (*(const int *)pd[s] == KIND_BINARY) {
+        const BinaryDesc &b = *(const BinaryDesc *)pd[s];
+        o.op = (int)b.op; // (XSMM_BINARY_ADD .. DIV = PO_ADD .. PO_DIV)
+        o.bc = o.pos == 0 ? bc(b.flags, 2, 8, 32) : bc(b.flags, 1, 4, 16);
+        o.ld = o.pos == 0 ? b.ldi_rhs : b.ldi_lhs;
+        o.ldo = b.ldo;
+      } else {
+        const UnaryDesc &u = *(const UnaryDesc *)pd[s];
+        o.op = u.op == XSMM_UNARY_RELU ? PO_RELU : u.op == XSMM_UNARY_ZERO ? PO_ZERO : PO_IDENTITY;
+        o.bc = 0;
+        o.ld = 0;
+        o.ldo = u.ldo;
+      }
+    }
+    return r;
+  }
+  // a folded group gathered into pinned[slot] (its n GEMM items) and post / have: ONE GEMM launch, then one epilogue launch per
+  // number of stages present (normally one: every item has the whole program; fewer when the group ends between an item's stages)
+  void launch_folded(const std::vector<PostItem> &pp, const std::vector<uint8_t> &lv, int stages, const void *const *pd, const int *pos) {
+    HIP_OK(launch_gemm_grouped(*(const GemmDesc *)desc, pinned[slot], n, vec_ok, out_ok, pair_ok, pinned[slot][0].br, stream));
+    if (!post_pinned[slot]) HIP_OK(hipHostMalloc((void **)&post_pinned[slot], sizeof(PostItem) * CAP, hipHostMallocDefault));
+    int at = 0;
+    for (int L = stages; L >= 1; --L) {
+      const int first = at;
+      for (int i = 0; i < n; ++i)
+        if (lv[i] == L) post_pinned[slot][at++] = pp[i];
+      if (at == first) continue;
+      HIP_OK(launch_postop_grouped(program(*(const GemmDesc *)desc, pd, pos, L), post_pinned[slot] + first, at - first, stream));
+      bump(g_fe_groups);
+    }
+  }
+
   TileQueue() { segs.reserve(NSEG); } // callers inside a direct window hold pointers into segs: it never reallocates
 
   // no caller is inside the window any more on return; the lock-free arrivals are added to n
@@ -496,6 +642,27 @@ struct TileQueue {
     if (!pending.armed) return;
     pending.armed = false;
     Segment &S = segs[pending.seg];
+    if (pending.kind == KIND_GEMM && S.post_n) { // a folded group: its own list and epilogue program (grid merge and quads decline it)
+      g_last_merged.store(nullptr, std::memory_order_relaxed);
+      LaunchReq r;
+      r.stream = pending.stream;
+      r.kind = KIND_GEMM;
+      r.desc = pending.desc;
+      r.list = S.list_dev;
+      r.n = S.n_gemm;
+      r.vec_ok = pending.vec_ok, r.out_ok = pending.out_ok, r.pair_ok = pending.pair_ok;
+      r.br = S.list[0].br; // (a GEMM item's batch count, as the recording pass had it: items[] is sorted by output address and may
+                           // start with a post-op, whose br is 0 - and the batch hint takes part in choosing the kernel family)
+      r.post = S.post_dev;
+      r.prog = S.prog;
+      S.list_used = true;
+      S.list_stream = pending.stream;
+      bump(g_fe_groups);
+      if (dw && launcher().push(r)) return;
+      launcher_drain();
+      issue_launch(r);
+      return;
+    }
     if (pending.kind == KIND_GEMM && S.grid_state == 0) detect_grid(S);
     LaunchReq r;
     r.stream = pending.stream;
@@ -569,7 +736,13 @@ struct TileQueue {
       // the group is exactly what was replayed from segs[learn] and `next` conflicts with it: one more way that group ends
       Segment &S = segs[learn];
       if (S.terminators.size() < 64 && !S.is_terminator(next->desc, next->w, next->stream)) S.terminators.push_back(*next);
-    } else if (rec_open && rec.items.size() >= MIN_SEG) {
+    } else if (rec_open && rec.items.size() >= MIN_SEG && !(fold_on && post_n && std::count(have.begin(), have.end(), (uint8_t)post_n) != n)) {
+      rec.post_n = fold_on ? post_n : 0;
+      if (rec.post_n) {
+        rec.post_pos[0] = post_pos[0];
+        rec.post_pos[1] = post_pos[1];
+        rec.prog = program(*(const GemmDesc *)desc, post_desc, post_pos, post_n);
+      }
       rec.terminators.clear();
       if (next) rec.terminators.push_back(*next);
       rec.vec_ok = vec_ok;
@@ -612,6 +785,37 @@ struct TileQueue {
     const int rp = replay;
     // the recorded group, complete, and its device-resident list exists (not while capturing): launch from its own list
     const bool whole = rp >= 0 && n > 0 && (size_t)n == segs[rp].items.size() && segs[rp].list_valid;
+    if (rp >= 0 && n > 0 && !whole && segs[rp].post_n) { // a folded group in part: its GEMM items and the stages of their chains that arrived
+      const Segment &S = segs[rp];
+      std::vector<PostItem> pp;
+      std::vector<uint8_t> lv;
+      int k = 0, marks = 0;
+      for (size_t i = 0; i < S.items.size(); ++i) {
+        if (__atomic_load_n(&S.seen[i], __ATOMIC_RELAXED) != S.round) continue;
+        ++marks;
+        if (S.parent[i] >= 0) continue;
+        int level = 0;
+        pp.push_back(S.chain_of((int)i, true, &level));
+        lv.push_back((uint8_t)level);
+        pinned[slot][k++] = S.items[i].w;
+      }
+      if (marks != n) die("tpp-xsmm-hip: internal error: %d members marked, %d counted in a replayed group", marks, n);
+      const void *pd[2] = {nullptr, nullptr};
+      for (size_t i = 0; i < S.items.size(); ++i)
+        if (S.items[i].depth > 0) pd[S.items[i].depth - 1] = S.items[i].desc;
+      const int stages = S.post_n, pos[2] = {S.post_pos[0], S.post_pos[1]};
+      store_recording(next);
+      replay = -1;
+      g_fe_folded.store(g_fe_folded.load(std::memory_order_relaxed) + (marks - k), std::memory_order_relaxed); // (replayed post-ops)
+      n = k;
+      bump(g_q_launches);
+      launcher_drain();
+      g_last_merged.store(nullptr, std::memory_order_relaxed);
+      launch_folded(pp, lv, stages, pd, pos);
+      launched();
+      reset_group();
+      return;
+    }
     if (rp >= 0 && n > 0 && !whole) materialize();
     // (counts are exact: an arrival is counted by whoever's atomic exchange on the item's mark saw it unmarked - once per round)
     store_recording(next); // (never touches segs[rp] during a replay: nothing is being recorded)
@@ -619,21 +823,34 @@ struct TileQueue {
     if (n == 0) return;
     bump(g_q_launches);
     if (whole) {
+      if (segs[rp].post_n) g_fe_folded.store(g_fe_folded.load(std::memory_order_relaxed) + (n - segs[rp].n_gemm), std::memory_order_relaxed);
       pending = Pending{true, kind, desc, rp, n, vec_ok, out_ok, pair_ok, stream};
       if (!defer) issue_pending();
     } else {
       launcher_drain(); // (launches handed to the launch thread come first on the stream)
       g_last_merged.store(nullptr, std::memory_order_relaxed); // (every kind: a relayout grid sets it for unary groups too)
-      if (kind == KIND_GEMM) HIP_OK(launch_gemm_grouped(*(const GemmDesc *)desc, pinned[slot], n, vec_ok, out_ok, pair_ok, pinned[slot][0].br, stream));
+      if (kind == KIND_GEMM && fold_on && post_n) launch_folded(post, have, post_n, post_desc, post_pos);
+      else if (kind == KIND_GEMM) HIP_OK(launch_gemm_grouped(*(const GemmDesc *)desc, pinned[slot], n, vec_ok, out_ok, pair_ok, pinned[slot][0].br, stream));
       else if (kind == KIND_UNARY) HIP_OK(launch_unary_grouped(*(const UnaryDesc *)desc, pinned[slot], n, stream));
       else HIP_OK(launch_binary_grouped(*(const BinaryDesc *)desc, pinned[slot], n, stream));
       launched();
     }
+    reset_group();
+  }
+  void reset_group() {
     n = 0;
     desc = nullptr;
     vec_ok = out_ok = pair_ok = true;
     reads.clear();
     writes.clear();
+    if (fold_on) {
+      fold_on = false;
+      post_n = 0;
+      post.clear();
+      have.clear();
+      tip_ld.clear();
+      tip.clear();
+    }
   }
 };
 
@@ -679,9 +896,91 @@ inline void append_to_group(TileQueue &q, int kind, const void *desc, const Work
     q.backoff = q.backoff_next;
     if (q.backoff_next < 64) q.backoff_next *= 2;
   }
+  if (q.fold_on) {
+    q.post.push_back(PostItem{w.C, {nullptr, nullptr}, {nullptr, nullptr}});
+    q.have.push_back(0);
+    q.tip_ld.push_back(((const GemmDesc *)desc)->ldc);
+    q.tip[(uintptr_t)w.C] = q.n;
+  }
   q.pinned[q.slot][q.n++] = w;
   for (int i = 0; i < n_in; ++i) q.reads.insert(*in[i], anchor_in[i]);
   q.writes.insert(out, anchor_out);
+}
+// EPILOGUE FOLD: a binary / unary invoke whose input is exactly the latest value of one queued GEMM item joins the group as the next
+// stage of that item's chain instead of flushing it (the compiler's brgemm -> binary -> unary per tile that CombineXsmmOp leaves
+// unfused). Conditions: a GEMM group on the same stream and dtype; the continued operand unbroadcast with the item's address, leading
+// dimension and m x n; the kind an epilogue program has (binary add / mul / sub / div, any broadcast of the other operand; unary
+// identity / relu / zero with no flags); at most two stages per item, and stage s of every item the same handle in the same position;
+// the other operand written by nothing queued; the output either the item's tile itself (in place) or touching nothing the group reads
+// or writes. The value is rounded at every stage's store as the invoke would round it (eltwise_ops.h); a stage written in place is
+// stored once, the final value. Everything else flushes as before.
+inline bool try_fold(TileQueue &q, const void *desc, const WorkItem &w, hipStream_t stream, const QueuedOps &o, const uintptr_t *anchor_in,
+                     uintptr_t anchor_out) {
+  const GemmDesc &g = *(const GemmDesc *)q.desc;
+  if (stream != q.stream || g.vnni_c) return false;
+  const int kind = *(const int *)desc;
+  const void *in = nullptr;
+  int pos = 0, other = -1;
+  int64_t ld_in = 0, ldo = 0, m = 0, n = 0, dtype = 0;
+  if (kind == KIND_UNARY) {
+    const UnaryDesc &u = *(const UnaryDesc *)desc;
+    if (u.flags != 0 || (u.op != XSMM_UNARY_IDENTITY && u.op != XSMM_UNARY_RELU && u.op != XSMM_UNARY_ZERO)) return false;
+    in = u.op == XSMM_UNARY_ZERO ? w.C : w.A; // (a zero reads nothing: it continues the tile it overwrites)
+    ld_in = u.op == XSMM_UNARY_ZERO ? u.ldo : u.ldi;
+    ldo = u.ldo, m = u.m, n = u.n, dtype = u.dtype;
+  } else if (kind == KIND_BINARY) {
+    const BinaryDesc &b = *(const BinaryDesc *)desc;
+    if (b.op < XSMM_BINARY_ADD || b.op > XSMM_BINARY_DIV) return false;
+    ldo = b.ldo, m = b.m, n = b.n, dtype = b.dtype;
+    if (!(b.flags & (1 | 4 | 16)) && q.tip.count((uintptr_t)w.A)) in = w.A, ld_in = b.ldi_lhs, pos = 0, other = 1;
+    else if (!(b.flags & (2 | 8 | 32)) && q.tip.count((uintptr_t)w.B)) in = w.B, ld_in = b.ldi_rhs, pos = 1, other = 0;
+    else return false;
+  } else return false;
+  if (dtype != g.dtype || m != g.m || n != g.n) return false;
+  auto f = q.tip.find((uintptr_t)in);
+  if (f == q.tip.end()) return false;
+  const int i = f->second, k = q.have[i];
+  if (ld_in != q.tip_ld[i] || k >= 2 || k > q.post_n) return false;
+  if (k < q.post_n && (q.post_desc[k] != desc || q.post_pos[k] != pos)) return false; // another program: the group ends here
+  if (other >= 0 && q.writes.overlaps(o.op[other], anchor_in[other])) return false;
+  const Operand &out = o.op[o.out];
+  const bool in_place = w.C == in && ldo == ld_in;
+  if (!in_place && (q.writes.overlaps(out, anchor_out) || q.reads.overlaps(out, anchor_out) ||
+                    (other >= 0 && o.op[other].bytes && Footprint::bounding(o.op[other]).b < Footprint::bounding(out).e &&
+                     Footprint::bounding(out).b < Footprint::bounding(o.op[other]).e)))
+    return false;
+  if (k == q.post_n) {
+    q.post_desc[k] = desc;
+    q.post_pos[k] = pos;
+    ++q.post_n;
+  }
+  q.have[i] = (uint8_t)(k + 1);
+  q.post[i].other[k] = other >= 0 ? o.op[other].ptr : nullptr;
+  q.post[i].out[k] = w.C;
+  if (!in_place) {
+    q.tip.erase(f);
+    q.tip[(uintptr_t)w.C] = i;
+    q.writes.insert(out, anchor_out);
+  }
+  q.tip_ld[i] = ldo;
+  if (other >= 0) q.reads.insert(o.op[other], anchor_in[other]);
+  if (q.rec_open) q.rec.items.push_back(TraceItem{desc, w, stream, k + 1});
+  q.learn = -1;
+  bump(g_fe_folded);
+  return true;
+}
+// the group's first post-op: the per-item chains and the address map of the items' values
+inline void start_fold(TileQueue &q) {
+  q.fold_on = true;
+  q.post_n = 0;
+  q.post.assign(q.n, PostItem{});
+  q.have.assign(q.n, 0);
+  q.tip_ld.assign(q.n, ((const GemmDesc *)q.desc)->ldc);
+  q.tip.clear();
+  for (int i = 0; i < q.n; ++i) {
+    q.post[i].C = q.pinned[q.slot][i].C;
+    q.tip[(uintptr_t)q.pinned[q.slot][i].C] = i;
+  }
 }
 // the first invoke of a group on an empty queue: replay the recorded group it belongs to, if there is one
 inline bool try_start_replay(TileQueue &q, DeviceRanges &devmem, const void *desc, const WorkItem &w, hipStream_t stream) {
@@ -693,6 +992,8 @@ inline bool try_start_replay(TileQueue &q, DeviceRanges &devmem, const void *des
   const int idx = q.find_segment(desc, w, stream, &item);
   if (idx < 0) return false;
   Segment &S = q.segs[idx];
+  if (S.post_n && S.parent[item] >= 0) return false; // a post-op never opens its group (the item it continues is not queued)
+  if (S.post_n && !cfg().fold_epilogue.load(std::memory_order_relaxed)) return false; // the fold was switched off: the group is collected anew
   if (++S.round == 0) { // (wrapped: forget the marks)
     std::fill(S.seen.begin(), S.seen.end(), 0u);
     S.round = 1;
@@ -732,6 +1033,12 @@ __attribute__((always_inline)) inline void process_item(TileQueue &q, DeviceRang
   const Operand &out = o.op[o.out];
   const uintptr_t anchor_out = anchor(out);
   const int kind = *(const int *)desc;
+  if (kind != KIND_GEMM && q.n > 0 && q.kind == KIND_GEMM && q.replay < 0 && cfg().fold_epilogue.load(std::memory_order_relaxed) &&
+      launch_postop_grouped) { // (null in a host-only test build: nothing folds there)
+    if (!q.fold_on) start_fold(q);
+    if (try_fold(q, desc, w, stream, o, anchor_in, anchor_out)) return;
+    bump(g_fe_declined);
+  }
   // strict mode: a group holds invokes of ONE alignment class and ONE batch count - the grouped launch takes its operand path from
   // the AND of the members' alignment flags and its chunk count from the first member, so a mixed group would make a member's kernel
   // depend on its neighbours
@@ -769,7 +1076,7 @@ inline void submit_item(TileQueue &q, DeviceRanges &devmem, const void *desc, co
     int idx = -1;
     if (q.rpos < S.items.size() && S.items[q.rpos].same(desc, w, stream)) idx = (int)q.rpos;
     else idx = S.index_of(desc, w, stream);
-    if (idx >= 0 && S.mark(idx)) {
+    if (idx >= 0 && S.order_ok(idx) && S.mark(idx)) {
       ++q.n;
       q.rpos = (size_t)idx + 1;
       bump(g_q_replayed);
@@ -797,6 +1104,11 @@ inline void submit_item(TileQueue &q, DeviceRanges &devmem, const void *desc, co
       bump(g_q_terminated);
       q.flush(nullptr, true);
       q.backoff_next = 2;
+    } else if (S.post_n) { // a folded group's pattern left (or a post-op ahead of its item): launch what has arrived, and collect
+      bump(g_q_abandoned);  // the next groups without the cache (growing back-off) so that the new pattern is recorded and replaces
+      q.flush();            // this one - else every group it overlaps would start a replay and be abandoned again
+      q.backoff = q.backoff_next;
+      if (q.backoff_next < 64) q.backoff_next *= 2;
     } else { // neither a member nor a known terminator: make the bookkeeping catch up with what has been queued
       bump(g_q_abandoned);
       q.close_window();

@@ -507,6 +507,17 @@ extern "C" void xsmm_hip_fold_transpose_stats(int64_t out[3]) {
   }
   out[2] = g_dt_launched.load(std::memory_order_relaxed); // remembered transposes that were launched after all
 }
+// epilogue fold (rt_tile_queue.h try_fold): returns the previous setting. With the fold off, no queue - the inline one or the
+// scheduler thread's - replays a recorded folded group any more (try_start_replay): their post-ops flush like any other invoke.
+extern "C" int xsmm_hip_set_fold_epilogue(int enable) {
+  flush_tile_queue(); // (a group already collected keeps its launch; a replay in progress ends here)
+  return cfg().fold_epilogue.exchange(enable != 0);
+}
+extern "C" void xsmm_hip_fold_epilogue_stats(int64_t out[3]) {
+  out[0] = g_fe_folded.load(std::memory_order_relaxed);   // post-op invokes folded into a GEMM group (recorded, and replayed)
+  out[1] = g_fe_groups.load(std::memory_order_relaxed);   // epilogue-program launches behind a GEMM group
+  out[2] = g_fe_declined.load(std::memory_order_relaxed); // element-wise invokes on a GEMM group that flushed it instead (ineligible)
+}
 extern "C" int xsmm_hip_force_split(int v) { return tpp::force_gemm_split(v); }
 // the VNNI blocking factor of bf16 B operands dispatched from now on (2 or 4); returns the previous one, -1 for an invalid factor
 extern "C" int xsmm_hip_set_vnni_factor(int v) {

@@ -85,6 +85,35 @@ struct RelayoutRun {
   int32_t wg0, vec;
 };
 
+// EPILOGUE PROGRAMS (tile queue, rt_tile_queue.h "epilogue fold"): the element-wise invokes the compiler leaves behind a GEMM tile
+// (binary add / mul / sub / div with any broadcast of the other operand, unary identity / relu / zero) folded into the GEMM group they
+// follow. One program per launch - at most two post-ops, the same handles in the same order for every item; stage s continues the
+// value of stage s - 1 (stage 0 = the GEMM's stored output C) and rounds at its own store, as the invoke it replaces does.
+enum : int { PO_ADD = 1, PO_MUL = 2, PO_SUB = 3, PO_DIV = 4, PO_IDENTITY = 5, PO_RELU = 6, PO_ZERO = 7 };
+struct PostOp {
+  int op;     // PO_*
+  int pos;    // binary: operand position of the continued value (0 = lhs, 1 = rhs)
+  int bc;     // broadcast of the OTHER operand: 0 none, 1 row, 2 col, 3 scalar (eltwise.hip BC_*)
+  int pad;
+  int64_t ld;  // leading dimension of the other operand (elements)
+  int64_t ldo; // ... of the stage's output
+};
+struct PostProgram {
+  int n;          // post-ops (1 or 2)
+  int m, cols;    // tile shape = the GEMM's m x n
+  int pad;
+  int64_t dtype;  // DT_F32 / DT_BF16
+  int64_t ldc;    // leading dimension of the GEMM's output C
+  PostOp op[2];
+};
+// one GEMM item's chain: its output tile, the other operand and the output of each stage (a side array next to the work list -
+// WorkItem is not widened). out[s] == out[s + 1]: the stage is in place and only the later value is stored.
+struct PostItem {
+  const void *C;
+  const void *other[2];
+  void *out[2];
+};
+
 // ---- kernel launchers (all enqueue on `stream`, never synchronise) --------------
 // pointers are device pointers with element offsets already applied.
 hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C, const void *D,
@@ -132,6 +161,10 @@ hipError_t launch_binary(const BinaryDesc &d, const void *lhs, const void *rhs, 
 // n_items invokes of ONE unary / binary descriptor with m, n <= 64 in one launch
 hipError_t launch_unary_grouped(const UnaryDesc &d, const WorkItem *items, int n_items, hipStream_t stream);
 hipError_t launch_binary_grouped(const BinaryDesc &d, const WorkItem *items, int n_items, hipStream_t stream);
+// n_items epilogue programs (items: device-readable array of PostItem) in ONE launch, one workgroup per item (eltwise.hip). Runs
+// behind the GEMM group whose outputs it reads, on the same stream. Weak like launch_relayout_grid: the host-only sanitizer builds
+// (tests/tsan) link runtime.cpp without the gfx950 kernels.
+__attribute__((weak)) hipError_t launch_postop_grouped(const PostProgram &p, const PostItem *items, int n_items, hipStream_t stream);
 // RELAYOUT GRIDS (relayout.hip): the blocks of n_runs runs (device array) of an identity (f32, bf16) or VNNI-2 (bf16) descriptor
 // in ONE launch of n_wg workgroups, one block each. Bit-exact word moves. Weak: the host-only sanitizer builds of runtime.cpp
 // (tests/tsan) link it without the gfx950 kernels - there it is null and the tile queue never chooses a relayout grid; the product

@@ -111,6 +111,8 @@ _SIGNATURES = {
     "xsmm_hip_force_split": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_fold_transpose_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_fold_epilogue": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_fold_epilogue_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_relayout_grid": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_relayout_grid_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_vnni_factor": (ctypes.c_int, [ctypes.c_int]),
@@ -329,6 +331,16 @@ class XsmmRuntime:
         """(gemm invokes served from a transpose's source, remembered transposes dropped as dead, remembered transposes launched)"""
         out = (ctypes.c_int64 * 3)()
         self.lib.xsmm_hip_fold_transpose_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_fold_epilogue(self, enable):
+        """element-wise invokes on a queued GEMM tile folded into its group as an epilogue program (default on); returns the previous setting"""
+        return self.lib.xsmm_hip_set_fold_epilogue(1 if enable else 0)
+
+    def fold_epilogue_stats(self):
+        """(post-op invokes folded, epilogue-program launches, element-wise invokes on a GEMM group that flushed it instead)"""
+        out = (ctypes.c_int64 * 3)()
+        self.lib.xsmm_hip_fold_epilogue_stats(out)
         return tuple(int(v) for v in out)
 
     def set_relayout_grid(self, enable):
