@@ -10,6 +10,7 @@
 //     (so a launch that touches bytes another thread is using IS a data race TSAN reports).
 #include "../../tpp-mlir_amd/csrc/xsmm_desc.h"
 #include "../../tpp-mlir_amd/csrc/chain_args.h"
+#include "../../tpp-mlir_amd/csrc/gemm_plan.h"
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -126,7 +127,6 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A_, const void *B_, void *
   return hipSuccess;
 }
 // the bf16 chain kernel has no host stand-in: plan_gemm above refuses bf16, so try_chain_launch never gets this far
-bool bf16_fast_eligible(const GemmDesc &) { return false; }
 int bf16_lw_b_kind(const GemmDesc &) { return -1; }
 void blw_tile_dims(int, int *bm, int *bn) { *bm = *bn = 128; }
 hipError_t launch_bf16_chain(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }

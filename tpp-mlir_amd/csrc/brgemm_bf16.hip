@@ -729,35 +729,9 @@ template <int LW> static hipError_t launch_bf16_dma128(const GemmArgs &a, hipStr
   return hipGetLastError();
 }
 
-bool bf16_fast_eligible(const GemmDesc &d) {
-  if (d.dtype != DT_BF16 || !d.vnni_b || d.vnni_factor != 2) return false; // (VNNI-4 operands: bf16_vnni4_eligible, brgemm_f32.hip)
-  if (d.k <= 0 || d.k % BKH) return false;
-  if (d.m % 64 || d.n % 64) return false;
-  if ((d.lda & 7) || (d.ldb & 3) || (d.ldc & 7) || (d.stride_a & 7) || (d.stride_b & 7)) return false;
-  if (d.lda >= (1 << 22) || d.ldb >= (1 << 21) || d.ldc >= (1 << 22)) return false; // 32-bit lane offsets
-  return true;
-}
-
 hipError_t launch_bf16_dma256(const GemmArgs &a, hipStream_t s); // brgemm_bf16_dma256.hip
 
-// tile choice for an eligible descriptor: 0 = 64x64 register-staged, 1 = 128x128 DMA, 2 = 256x256 DMA.
-//  * 256 x 256 (LDS / L2 traffic per flop halves: measured 1.31-1.37 vs 0.88-1.03 PFLOP/s on 4096^3 ..
-//    8192^3) when its tile waves fill the 256 CUs well enough to keep that 1.4x: tiles run one per CU,
-//    so a grid of t tiles takes ceil(t / 256) rounds;
-//  * 128 x 128 as soon as the 64 x 64 family would need a second round of workgroups (more than 256 tiles of
-//    64 x 64 = more than 64 of 128 x 128): measured (n = 1024, K = 1024) the DMA kernel takes 9.2-9.4 us from 64
-//    to 256 tiles while the 64 x 64 family jumps from 9.1 to 12.8 us past one tile per CU;
-//  * 64 x 64 below that, so that more CUs have work.
-int pick_bf16_tile(const GemmDesc &d) {
-  constexpr int64_t t256_min = 240, t128_min = 65; // crossovers measured in profiles/r01_sweep_shapes.txt
-  const int64_t t256 = (d.m % 256 == 0 && d.n % 256 == 0) ? (d.m / 256) * (d.n / 256) : 0;
-  const int64_t t128 = (d.m % 128 == 0 && d.n % 128 == 0) ? (d.m / 128) * (d.n / 128) : 0;
-  auto fill = [](int64_t t) { return (double)t / (double)(((t + 255) / 256) * 256); }; // CU occupancy over the rounds
-  if (t256 >= t256_min && 1.4 * fill(t256) >= fill(t128)) return 2;
-  if (t128 >= t128_min) return 1;
-  return 0;
-}
-
+// tile (gemm_plan.cpp pick_bf16_tile): 0 = 64x64 register-staged, 1 = 128x128 DMA, 2 = 256x256 DMA
 hipError_t launch_gemm_bf16_fast(int tile, const GemmArgs &a, hipStream_t s) {
   if (tile == 2) return launch_bf16_dma256(a, s);
   // two loader waves; none / four were measured equal (profiles/r02_bf16_dma128_ablation.txt: the loop is bound by the

@@ -764,13 +764,6 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   return hipGetLastError();
 }
 
-// tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128
-void blw_tile_dims(int tile, int *bm, int *bn) {
-  static const int BMs[4] = {32, 64, 64, 128}, BNs[4] = {64, 64, 128, 128};
-  *bm = BMs[tile & 3];
-  *bn = BNs[tile & 3];
-}
-
 // Loader waves per tile (NLA + NLB), same-box A/B (profiles/r03_blw_loader_split.txt): 32x64 1 + 2 (1 + 1: +2 %, 2 + 2: +5 %),
 // 64x64 1 + 1 (1 + 2: +2 %, 2 + 2: +7 %), 64x128 1 + 2 (1 + 1: same, 2 + 4: +5 %), 128x128 1 + 1 (2 + 2, 1 + 2: same).
 // SUP = 2 (one workgroup barrier per TWO chunks) for the 32x64 and 64x64 tiles when every layer has an even chunk count.

@@ -25,6 +25,7 @@
 #include "gemm_common.h"
 #include "xsmm_desc.h"
 #include "chain_args.h"
+#include "gemm_plan.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -621,44 +622,9 @@ __global__ __launch_bounds__(256) void brgemm_grouped(GemmArgs p, const WorkItem
   }
 }
 
-// ---- host side ---------------------------------------------------------------
-enum GemmVariant : int {
-  V_F32_64x64 = 0,   // 4 waves 2x2x1
-  V_F32_64x32K2 = 1, // 4 waves 2x1x2
-  V_F32_32x32K4 = 2, // 4 waves 1x1x4
-  V_F32_128x64 = 3,  // 8 waves 4x2x1
-  V_F32_64x64K2 = 4, // 8 waves 2x2x2 (two waves per SIMD share every K chunk)
-  V_F32_LW_64x64 = 5,     // brgemm_f32_lw.hip: 4 MFMA waves 2x2x1 + 2 loader waves
-  V_F32_LW_64x64K2 = 6,   // 8 MFMA waves 2x2x2 + 2 loader waves
-  V_F32_LW_64x32K2 = 7,   // 8 MFMA waves 2x1x4 + 2 loader waves (K split over four groups since round 3; the name of the constant stayed)
-  V_GENERIC = 8,     // chosen per invoke when the fast preconditions fail
-  V_F32_LW_32x32K4 = 9,   // 4 MFMA waves 1x1x4 + 2 loader waves
-  V_F32_LW_128x64 = 10,   // 8 MFMA waves 4x2x1 + 2 x 2 loader waves, 3-slot ring (large outputs)
-  V_F32_LW16_32x16 = 11,  // brgemm_f32_lw16.hip: 32x16 tiles on v_mfma_f32_16x16x4_f32, 4 MFMA waves (K split) + 3 loader waves: outputs of at most one 32x16 tile per CU
-  V_F32_X6_64x64 = 12,    // brgemm_f32_x6.hip: the bf16x6 split on v_mfma_f32_32x32x16_bf16 (f32 descriptors dispatched under xsmm_hip_set_f32_precision(6)
-  V_F32_X6_64x32K2 = 13,  //   with this variant forced: plan_gemm); 4 waves, K split over the rest of them; 128x64 with 8 waves
-  V_F32_X6_32x32K4 = 14,
-  V_F32_X6_128x64 = 15,
-  V_BF16_FAST = 16,  // brgemm_bf16.hip: 64x64 register-staged
-  V_BF16_DMA128 = 17, // brgemm_bf16.hip: 128x128, LDS-DMA + loader waves
-  V_BF16_DMA256 = 18, // brgemm_bf16_dma256.hip: 256x256, LDS-DMA
-  V_BF16_SMALL32 = 19, // brgemm_bf16_small.hip: 32x32 tiles, 4 waves split K, fragments straight from global memory
-  V_BF16_LW_32x64 = 20,   // brgemm_bf16_lw.hip: loader-wave tiles for mid-size outputs (one workgroup per CU), 32x64 + K2
-  V_BF16_LW_64x64 = 21,
-  V_BF16_LW_64x128 = 22,
-  V_BF16_LW_128x128 = 23,
-  V_BF16_LWF_32x64 = 24,  // the same tiles for a FLAT bf16 B operand (no VNNI flag): the pair-row interleave happens in the B loader
-  V_BF16_LWF_64x64 = 25,
-  V_BF16_LWF_64x128 = 26,
-  V_BF16_LWF_128x128 = 27,
-  V_BF16_LW4_32x64 = 28,  // the same tiles for a VNNI-4 B operand [k/4][n][4] (xsmm_hip_set_vnni_factor(4)): a fragment is two 8-byte reads
-  V_BF16_LW4_64x64 = 29,
-  V_BF16_LW4_64x128 = 30,
-  V_BF16_LW4_128x128 = 31,
-};
-
+// ---- host side: carrying out the plans of gemm_plan.cpp ---------------------------------------------------------------------------
 template <int WM, int WN, int WK, bool DMA>
-static hipError_t launch_fast_t(const GemmArgs &a, hipStream_t s) {
+static hipError_t launch_fast(const GemmArgs &a, hipStream_t s) {
   constexpr int BM = 32 * WM, BN = 32 * WN, NT = 64 * WM * WN * WK;
   constexpr size_t lds = (size_t)NSTAGE * (BM * BK + BK * BN) * sizeof(float);
   static std::atomic<unsigned long long> lds_set{0};
@@ -679,19 +645,14 @@ static hipError_t launch_fast_t(const GemmArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int WM, int WN, int WK, bool DMA>
-static hipError_t launch_fast(const GemmArgs &a, hipStream_t s) {
-  return launch_fast_t<WM, WN, WK, DMA>(a, s);
-}
-
 hipError_t launch_gemm_bf16_fast(int tile, const GemmArgs &a, hipStream_t s); // brgemm_bf16.hip
 hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         // brgemm_f32_lw.hip (tile 4: 128x64, forced variant 10 only - it measures within 2 % of brgemm_f32_fast<128x64>)
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
 hipError_t launch_f32_lw16(int tile, const GemmArgs &a, const WorkItem *items, int n_items, bool grouped, hipStream_t s); // brgemm_f32_lw16.hip: tile 0 = 32x16
 hipError_t launch_f32_x6(int tile, const GemmArgs &a, bool vec, hipStream_t s); // brgemm_f32_x6.hip: tile = variant - V_F32_X6_64x64
-int pick_bf16_tile(const GemmDesc &d);
-bool bf16_fast_eligible(const GemmDesc &d);
+hipError_t launch_bf16_grouped64(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s); // brgemm_bf16.hip
+hipError_t launch_bf16_small32(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s, int split = 1); // brgemm_bf16_small.hip
 
 template <typename T, bool VNNI, bool VEC, int VF = 2>
 static hipError_t launch_grouped_t(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s) {
@@ -709,59 +670,7 @@ static hipError_t launch_grouped_t(const GemmArgs &a, const WorkItem *items, int
   return hipGetLastError();
 }
 
-#define g_num_cus device_cu_count() /* compute units of the current device (gemm_common.h) */
-constexpr int SPLIT_MAX_WG = 16; // = SPLIT_MAX of split_scratch.h
-
-hipError_t launch_bf16_grouped64(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s); // brgemm_bf16.hip
-hipError_t launch_bf16_small32(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s, int split = 1); // brgemm_bf16_small.hip
-// flat-B bf16 for the loader-wave tiles: 16-byte row pieces of A, B and C, 64-k chunks, 32-bit lane offsets
-static bool bf16_flat_eligible(const GemmDesc &d) {
-  return d.dtype == DT_BF16 && !d.vnni_b && !d.vnni_c && d.k > 0 && d.k % 64 == 0 && d.m % 32 == 0 && d.n % 64 == 0 &&
-         !((d.lda | d.ldb | d.ldc | d.stride_a | d.stride_b) & 7) && d.lda < (1 << 22) && d.ldb < (1 << 21) && d.ldc < (1 << 22);
-}
-// VNNI-4 B for the loader-wave tiles: k-group rows of 8 * ldb bytes in 16-byte pieces, 64-k chunks, 32-bit lane offsets
-static bool bf16_vnni4_eligible(const GemmDesc &d) {
-  return d.dtype == DT_BF16 && d.vnni_b && d.vnni_factor == 4 && !d.vnni_c && d.k > 0 && d.k % 64 == 0 && d.m % 32 == 0 && d.n % 64 == 0 &&
-         !((d.lda | d.ldc | d.stride_a | d.stride_b) & 7) && !(d.ldb & 1) && d.lda < (1 << 22) && d.ldb < (1 << 20) && d.ldc < (1 << 22);
-}
-static bool bf16_small_eligible(const GemmDesc &d) {
-  return d.dtype == DT_BF16 && d.vnni_b && d.vnni_factor == 2 && d.m % 32 == 0 && d.n % 32 == 0 && d.k > 0 && d.k % 16 == 0 && !(d.lda & 7) &&
-         !(d.stride_a & 7) && !(d.stride_b & 1) && !(d.ldc & 3);
-}
-
-// the f32 chain tile (brgemm_f32_lw.hip, launch_f32_chain) a whole-layer f32 descriptor was planned on: 1 / 2 / 3, or -1 (another
-// kernel family, a VNNI operand, k not in 64-k chunks ... - whatever pick_f32_variant sent elsewhere)
-int f32_chain_tile(const GemmDesc &d) {
-  if (gemm_on_x6(d)) return -1; // the bf16x6 split kernel: chains that hold such a call run call by call (it has no chain form)
-  if (d.dtype != DT_F32 || d.vnni_b || d.vnni_c || d.k <= 0 || d.k % BK) return -1;
-  // (the 32x32 + K4 tile - the reference's batch-256 layers, 3.4 us of MFMA work per tile - is NOT chained: measured 21.9 us per
-  // three-layer step as one launch against 20.6 as three, profiles/r04_f32_chain.txt: a seam is four dependent memory round trips
-  // - store drain, counter add, poll, A fetch - and 32 producers + 32 pollers share one counter line; the 64-row tiles gain 1-2.5 %)
-  switch (d.variant) {
-  case V_F32_LW_64x64K2: return 1;
-  case V_F32_LW_64x32K2: return 2;
-  default: return -1;
-  }
-}
-
-int bf16_lw_b_kind(const GemmDesc &d) {
-  if (d.dtype != DT_BF16 || d.vnni_c) return -1;
-  if (d.vnni_b && d.vnni_factor == 4) return bf16_vnni4_eligible(d) ? 4 : -1;
-  if (d.vnni_b) return bf16_fast_eligible(d) ? 0 : -1;
-  return bf16_flat_eligible(d) ? 2 : -1;
-}
-
-// How many workgroups share the batch-reduce range of ONE output tile (SPLIT kernels of brgemm_f32_lw.hip) - 1 = no split.
-// tile: 1 = 64x64 + K2, 2 = 64x32 + K4, 3 = 32x32 + K4; tiles: output tiles of the whole launch; chunks: 64-k chunks per tile.
-// Fitted to profiles/r05_split_sweep.txt (whole-layer calls of the reference's skinny benchmark shapes over tile x split count):
-//  * a workgroup alone on a CU needs c(tile) us per chunk (the matrix pipes' rate: 0.213 us for a 32x32x64 chunk);
-//  * a split costs R = 2.6-2.7 us whatever the count - three dependent trips to the memory side: partial tile written through
-//    and acknowledged, arrival counter, the other partials read back - so it pays only where it takes more than that off the K loop;
-//  * more workgroups than CUs never paid: 128 x 1024 x 4096 on 32x32 tiles 17.1 us unsplit, 12.9 (S = 2: 256 workgroups), 13.6 (S = 4:
-//    512), 15.6 (6), 20.6 (8) - every further round of workgroups pays its own prologue and hand-off.
-// Hence: the largest S with tiles * S <= CUs, if the K-loop time it saves exceeds R by a margin. The answer depends on the
-// descriptor, the batch count and the number of tiles in the launch only: the same call pattern always adds in the same order.
-// xsmm_hip_force_split / TPP_HIP_SPLIT: 0 / 1 = never split, n > 1 = always n (clamped to the chunks), -1 = this model.
+// xsmm_hip_force_split / TPP_HIP_SPLIT: 0 / 1 = never split, n > 1 = always n (clamped to the chunks), -1 = the split model (gemm_plan.cpp)
 static std::atomic<int> g_forced_split{[] {
   const char *e = getenv("TPP_HIP_SPLIT");
   return e ? atoi(e) : -1;
@@ -770,20 +679,9 @@ int force_gemm_split(int v) { return g_forced_split.exchange(v < -1 ? -1 : v); }
 static std::atomic<int> g_strict_kernels{0};
 int set_strict_kernels(int on) { return g_strict_kernels.exchange(on != 0); }
 bool strict_kernels() { return g_strict_kernels.load(std::memory_order_relaxed) != 0; }
-static int choose_f32_split(int tile, long long tiles, long long chunks) {
-  const int forced = g_forced_split.load(std::memory_order_relaxed);
-  if (tile < 1 || tile > 3 || tiles <= 0 || chunks < 2) return 1;
-  const long long smax = chunks < SPLIT_MAX_WG ? chunks : SPLIT_MAX_WG;
-  if (forced >= 0) return forced <= 1 ? 1 : (int)(forced < smax ? forced : smax);
-  const double c = tile == 1 ? 0.92 : tile == 2 ? 0.46 : 0.213;
-  long long S = g_num_cus / tiles;
-  if (S > smax) S = smax;
-  if (S > chunks / 4) S = chunks / 4; // at least four chunks per workgroup
-  if (S < 2) return 1;
-  const long long per = (chunks + S - 1) / S;
-  const double saved = c * (double)(chunks - per);
-  return saved > 2.7 + 0.8 ? (int)S : 1;
-}
+static GemmPlanEnv gemm_plan_env() { return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed)}; }
+bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, gemm_plan_env()); }
+bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, gemm_plan_env()); }
 
 // name of the kernel family of the most recent grouped GEMM launch (xsmm_hip_last_grouped_kernel: tests and tools/tpp_replay
 // report which kernel a tile-queue group ran on - the descriptor's own name is what a SINGLE invoke would run on)
@@ -793,626 +691,107 @@ const char *last_grouped_kernel() { return g_last_grouped.load(std::memory_order
 // descriptor's own kernel (xsmm_hip_kernel_name) ran
 static std::atomic<const char *> g_last_refined{""};
 const char *last_refined_kernel() { return g_last_refined.load(std::memory_order_relaxed); }
-#define note_grouped(name, ...) (g_last_grouped.store(name, std::memory_order_relaxed), (__VA_ARGS__))
-hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_items, bool vec_ok, bool out_ok, bool pair_ok,
-                               int64_t br_hint, hipStream_t stream) {
-  if (d.m <= 0 || d.n <= 0 || n_items <= 0) return hipSuccess;
-  if (gemm_on_x6(d)) return hipErrorInvalidValue; // the split kernel is never queued or grouped (try_enqueue, gemm_invoke_unqueued)
-  // n_dec: the number of items every size-dependent DECISION below is taken for. Normally the group's - the group is what fills the
-  // chip. In strict mode 1: a single invoke, the first pass of a queued group and its replays then all run on the same kernel.
-  const int64_t n_dec = strict_kernels() ? 1 : n_items;
-  GemmArgs a;
-  a.A = a.B = a.D = nullptr; a.C = nullptr;
-  a.lda = d.lda; a.ldb = d.ldb; a.ldc = d.ldc; a.stride_a = d.stride_a; a.stride_b = d.stride_b;
-  a.m = (int)d.m; a.n = (int)d.n; a.k = (int)d.k; a.br = 0;
-  a.ep = (d.beta0 ? EP_BETA0 : 0) | (d.bias ? EP_BIAS : 0) | (d.relu ? EP_RELU : 0) | (d.vnni_c ? EP_VNNI_C : 0);
-  a.tiles_m = a.tiles_n = 0;
-  a.vf = d.vnni_factor ? d.vnni_factor : 2;
-  a.split = 0; a.scratch = nullptr; a.split_cnt = nullptr;
-  a.b_trans = d.b_trans;
-  if (d.b_trans) { // B read transposed (a folded xsmm.unary transpose): the generic kernel's element-wise loads
-    if (d.dtype != DT_F32 || d.vnni_b) return hipErrorInvalidValue;
-    return note_grouped("brgemm_grouped<f32>, B read transposed", launch_grouped_t<float, false, false>(a, items, n_items, stream));
-  }
-  const bool tiles_ok = vec_ok && d.n % 4 == 0 && d.k % GK == 0; // 16-byte pieces; ragged m / n edges are predicated
-  const bool vec = vec_ok && d.n % 4 == 0 && d.k % 4 == 0 && d.dtype == DT_F32 && !d.vnni_b && !((d.lda | d.ldb | d.stride_a | d.stride_b) & 3) &&
-                   d.lda < (1 << 24) && d.ldb < (1 << 24); // (32-bit tile-relative lane offsets: 32 rows x ld x 4 B < 2^31)
-  // f32 tiles with k a multiple of 64 (mlir-gen --tiles=64,64,64, the most common setting of the reference's
-  // benchmark configs): the fast tile families in grouped mode, the largest tile that still yields about one
-  // workgroup per CU over the whole work list (the same rule as pick_f32_variant)
-  // ... and 32-k tiles (--tiles=32,32,32, the reference's MLP benchmark) when every batch count is even: the loader waves build a
-  // 64-k chunk from the blocks of two batch elements (brgemm_f32_lw.hip, pair mode)
-  const bool k_pairs = d.k == 32 && pair_ok && d.stride_a >= 0 && d.stride_b >= 0 && d.stride_a < (1 << 26) && d.stride_b < (1 << 26);
-  // (n that is not a multiple of 32 - the reference's --tiles=64,48,64 / 32,48,32 configs: the last 32-column tile of an item is
-  // ragged, the loader-wave kernels clamp its loads and mask its stores; needs the 16-byte output pieces of out_ok and ldc % 4)
-  // skinny groups - at most one 32x16 tile per CU over the whole work list: the half-width tiles (brgemm_f32_lw16.hip), every CU a
-  // workgroup without a hand-off. 64-k tiles, or 32-k tiles whose n is not a multiple of 32 with even batch counts (--tiles=32,48,32);
-  // plain 32x32x32 tiles stay on the pair kernel whatever the group size (a single invoke and its group add in the same order:
-  // what tools/queue_fuzz.py checks bit for bit)
-  {
-    const int l16_tile = 0;
-    const int64_t t16 = (d.m % 32 == 0 && d.n % 16 == 0) ? n_dec * (d.m / 32) * (d.n / 16) : 0;
-    const bool k_ok = (d.k % BK == 0 && d.k > 0) || (k_pairs && d.n % 32 != 0);
-    static const char *const l16_names[1][2] = {{"brgemm_f32_lw16<32x16,k4> grouped", "brgemm_f32_lw16<32x16,k4> grouped, 32-k pairs"}};
-    if (vec && out_ok && !d.generic_forced && t16 > 0 && t16 <= g_num_cus && k_ok && d.ldc % 4 == 0 && n_items <= 65535 && d.lda < (1 << 22) &&
-        d.ldb < (1 << 22) && d.ldc < (1 << 22) && (!d.bias || out_ok) &&
-        !((d.k == 32 ? br_hint / 2 : br_hint * (d.k / BK)) >= 48 && d.n % 32 == 0 && d.k % BK == 0)) // (long reductions: the split 32x32 tiles below, as launch_gemm)
-      return note_grouped(l16_names[l16_tile][d.k == 32], launch_f32_lw16(l16_tile, a, items, n_items, true, stream));
-  }
-  const bool n_ragged = d.n % 32 != 0;
-  const bool fam_ok = n_ragged ? (!d.generic_forced && d.n > 32 && (d.k % BK == 0 || k_pairs)) // (plan_gemm knows no tile for such an n: variant = generic)
-                               : ((d.k % BK == 0 && d.variant != V_GENERIC) || (k_pairs && !d.generic_forced));
-  if (vec && d.m % 32 == 0 && fam_ok && d.lda < (1 << 22) && d.ldb < (1 << 22) && d.ldc < (1 << 22)) {
-    const int64_t t64 = (d.m % 64 == 0 && d.n % 64 == 0) ? n_dec * (d.m / 64) * (d.n / 64) : 0;
-    const int64_t t6432 = (d.m % 64 == 0) ? n_dec * (d.m / 64) * ((d.n + 31) / 32) : 0;
-    if (n_items <= 65535 * 2) { // grid.x carries the item index (x split)
-      auto nm = [&](const char *plain, const char *pairs) { return d.k == 32 ? pairs : plain; };
-      // the loader-wave kernels (brgemm_f32_lw.hip) in grouped mode
-      if (t64 >= g_num_cus) return note_grouped(t64 >= 2 * g_num_cus ? nm("brgemm_f32_lw<64x64> grouped", "brgemm_f32_lw<64x64> grouped, 32-k pairs") : nm("brgemm_f32_lw<64x64,k2> grouped", "brgemm_f32_lw<64x64,k2> grouped, 32-k pairs"), launch_f32_lw_grouped(t64 >= 2 * g_num_cus ? 0 : 1, a, items, n_items, 1, stream));
-      const int64_t t32 = n_dec * (d.m / 32) * ((d.n + 31) / 32);
-      // (rounds of workgroups x per-chunk time, as pick_f32_variant: 1.5 rounds of 64x32 tiles lose to 3 half-rounds of 32x32 tiles)
-      if (t6432 >= g_num_cus && !(0.23 * 1.05 * (double)((t32 + g_num_cus - 1) / g_num_cus) < 0.46 * (double)((t6432 + g_num_cus - 1) / g_num_cus)))
-        return note_grouped(nm("brgemm_f32_lw<64x32,k4> grouped", "brgemm_f32_lw<64x32,k4> grouped, 32-k pairs"), launch_f32_lw_grouped(2, a, items, n_items, 1, stream));
-      // skinny groups (fewer 64x32 tiles than CUs): 32x32 tiles, and the batch-reduce range of a tile over several workgroups
-      // when the model says so (choose_f32_split: from the descriptor, the first item's batch count and the group's size)
-      const int64_t chunks = d.k == 32 ? br_hint / 2 : br_hint * (d.k / BK);
-      const int S = choose_f32_split(3, t32, chunks);
-      static const char *const split_names[2] = {"brgemm_f32_lw<32x32,k4> grouped, split", "brgemm_f32_lw<32x32,k4> grouped, 32-k pairs, split"};
-      if (S > 1) return note_grouped(split_names[d.k == 32], launch_f32_lw_grouped(3, a, items, n_items, S, stream));
-      return note_grouped(nm("brgemm_f32_lw<32x32,k4> grouped", "brgemm_f32_lw<32x32,k4> grouped, 32-k pairs"), launch_f32_lw_grouped(3, a, items, n_items, 1, stream));
-    }
-  }
-  // bf16 + VNNI-2 B with 16-byte loads: 8-element A pieces, pair-rows of B 16-byte aligned
-  const bool vec16x = d.dtype == DT_BF16 && d.vnni_b && !((d.lda | d.stride_a | d.stride_b) & 7) && d.lda < (1 << 21) && d.ldb < (1 << 21);
-  const bool vec16_4 = vec16x && d.vnni_factor == 4 && vec_ok && d.n % 2 == 0 && d.k % GK == 0 && !(d.ldb & 1); // VNNI-4: 16-byte pieces of 2 columns
-  const bool vec16 = tiles_ok && d.dtype == DT_BF16 && d.vnni_b && d.vnni_factor == 2 && !((d.lda | d.stride_a | d.stride_b) & 7) && !(d.ldb & 3) &&
-                     d.lda < (1 << 21) && d.ldb < (1 << 21); // (32-bit lane offsets)
-  // bf16 tile invokes with k a multiple of 64 and n a multiple of 64 (the reference's --tiles=64,64,64 / 32,64,64 bf16 rows): the
-  // LOADER-WAVE tiles in grouped mode (round 6, brgemm_bf16_lw.hip launch_bf16_lw_grouped) - what the same layer runs on as one
-  // whole-layer call. Tile by the model of pick_bf16_lw_tile over the group's workgroups: 32x64 + K2 (two workgroups per 64-row
-  // item) or 64x64. Against the two older grouped kernels (profiles/r06_bf16_sweep_before.txt, forced-variant rows): the loader-wave
-  // tiles win whenever the group fills 3/4 of the chip with 64x64 tiles (1024 x 1024 x 512: 5.1 us against 6.7) or the reduction is
-  // long (16 chunks or more: 128 x 4096 x 1024 5.3 against 9.4) or half the chip gets a 32x64 tile of at least 8 chunks (128 x 3072 x 768: 4.9 against 6.3; 1024 x 512 x 256, 4 chunks: 5.6 against 5.1);
-  // short reductions of small groups stay on the K-split kernel (128 x 768 x 768: 4.3 against 4.7).
-  {
-    const bool v2 = d.vnni_factor == 2, v4 = d.vnni_factor == 4;
-    const bool shape_ok = d.dtype == DT_BF16 && d.vnni_b && (v2 || v4) && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.k > 0 && d.k % BK == 0 &&
-                          d.m % 32 == 0 && d.n % 64 == 0 && !((d.lda | d.stride_a | d.stride_b | d.ldc) & 7) && !(d.ldb & (v2 ? 3 : 1)) &&
-                          d.lda < (1 << 21) && d.ldb < (1 << 20) && d.ldc < (1 << 22) && d.stride_a >= 0 && d.stride_b >= 0;
-    // RAGGED n (round 6): items whose n is 16 more than a multiple of 32 - the reference's --tiles=64,48,64 rows (fc / matmul 128x768x2304)
-    // - on the 32x32 + K2 instance: ceil(n / 32) column tiles per item, the last moved left to end at column n (it recomputes the 16
-    // columns it shares with its neighbour and stores its own 16: brgemm_bf16_lw.hip skip_cols). Skinny groups with a long reduction
-    // only, like the instance's other uses; everything else with such an n stays on the K-split kernel below.
-    {
-      const bool ragged_ok = d.dtype == DT_BF16 && d.vnni_b && (v2 || v4) && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.k > 0 && d.k % BK == 0 &&
-                             d.m % 32 == 0 && d.n % 32 == 16 && d.n >= 48 && !((d.lda | d.stride_a | d.stride_b | d.ldc) & 7) && !(d.ldb & (v2 ? 3 : 1)) &&
-                             d.lda < (1 << 21) && d.ldb < (1 << 20) && d.ldc < (1 << 22) && d.stride_a >= 0 && d.stride_b >= 0;
-      if (ragged_ok && vec_ok && out_ok && br_hint >= 1 && g_forced_split.load(std::memory_order_relaxed) < 0) {
-        const int64_t chunks = br_hint * (d.k / BK);
-        const int64_t wg4 = n_dec * (d.m / 32) * ((d.n + 31) / 32);
-        if (wg4 <= (int64_t)g_num_cus && chunks >= 16) {
-          ChainArgs c;
-          memset(&c, 0, sizeof(c));
-          c.lda = d.lda;
-          c.m = (int)d.m;
-          c.n = (int)d.n;
-          c.nlayers = 1;
-          c.L[0] = ChainLayer{nullptr, nullptr, nullptr, d.ldb, d.ldc, d.stride_a, d.stride_b, (int)d.k, (int)br_hint, a.ep, 0};
-          const bool even = ((d.k / BK) % 2 == 0) || pair_ok;
-          return note_grouped(v4 ? "brgemm_bf16_lw_vnni4<32x32,k2> grouped, ragged n" : "brgemm_bf16_lw<32x32,k2> grouped, ragged n",
-                              launch_bf16_lw_grouped(4, v4 ? 4 : 0, c, items, n_items, even, stream));
-        }
-      }
-    }
-    if (shape_ok && vec_ok && out_ok && br_hint >= 1 && g_forced_split.load(std::memory_order_relaxed) < 0) { // (a forced split count: the K-split kernel below)
-      const int64_t chunks = br_hint * (d.k / BK);
-      const int64_t t64 = d.m % 64 == 0 ? n_dec * (d.m / 64) * (d.n / 64) : 0;
-      const int64_t wg0 = n_dec * (d.m / 32) * (d.n / 64);
-      if (t64 * 4 >= 3 * (int64_t)g_num_cus || chunks >= 16 || (wg0 * 2 >= (int64_t)g_num_cus && chunks >= 8)) {
-        static const double ca[2] = {3.56, 3.75}, cb[2] = {0.098, 0.135};
-        const double c0 = (double)((wg0 + g_num_cus - 1) / g_num_cus) * (ca[0] + cb[0] * (double)chunks);
-        const double c1 = t64 > 0 ? (double)((t64 + g_num_cus - 1) / g_num_cus) * (ca[1] + cb[1] * (double)chunks) : 1e30;
-        int tile = c1 <= c0 ? 1 : 0;
-        // 32x32 + K2 (VNNI-2): twice the workgroups of the 32x64 tile pulling panels - for skinny groups with a long reduction, as
-        // launch_gemm does for the whole-layer call (one round of workgroups at most, 16 chunks or more; (a, b) = (3.52, 0.072) from
-        // 128 x 1024 x 1024 / x 4096 on that tile)
-        const int64_t wg4 = n_dec * (d.m / 32) * (d.n / 32);
-        if (wg4 <= (int64_t)g_num_cus && chunks >= 16 && 3.52 + 0.072 * (double)chunks < (c1 < c0 ? c1 : c0)) tile = 4;
-        ChainArgs c;
-        memset(&c, 0, sizeof(c));
-        c.lda = d.lda;
-        c.m = (int)d.m;
-        c.n = (int)d.n;
-        c.nlayers = 1;
-        c.L[0] = ChainLayer{nullptr, nullptr, nullptr, d.ldb, d.ldc, d.stride_a, d.stride_b, (int)d.k, (int)br_hint, a.ep, 0};
-        const bool even = ((d.k / BK) % 2 == 0) || pair_ok;
-        static const char *const names[2][2] = {{"brgemm_bf16_lw<32x64,k2> grouped", "brgemm_bf16_lw<64x64> grouped"},
-                                                {"brgemm_bf16_lw_vnni4<32x64,k2> grouped", "brgemm_bf16_lw_vnni4<64x64> grouped"}};
-        return note_grouped(tile == 4 ? (v4 ? "brgemm_bf16_lw_vnni4<32x32,k2> grouped" : "brgemm_bf16_lw<32x32,k2> grouped") : names[v4 ? 1 : 0][tile],
-                            launch_bf16_lw_grouped(tile, v4 ? 4 : 0, c, items, n_items, even, stream));
-      }
-    }
-  }
-  // bf16 tiles of 64x64 with k a multiple of 64: the 64x64 bf16 family in grouped mode (it stores 16-byte
-  // row pieces and reads the bias 8 bytes at a time: checked per item by the queue through out_ok)
-  // (whatever a SINGLE invoke of the handle would run on - a lone 64x64 tile is planned on the 32x32 K-split kernel -, the GROUP is
-  // what fills the chip: round 5, the reference's fc / matmul shapes as 64,64,64 tile invokes: 1024 x 2560 x 1024 30.4 us on 32x32
-  // tiles against 15 us whole-layer)
-  if (vec16 && out_ok && d.variant >= V_BF16_FAST && (d.variant != V_BF16_SMALL32 || !d.variant_forced) && !d.generic_forced && bf16_fast_eligible(d) &&
-      n_dec * (d.m / 64) * (d.n / 64) >= (3 * g_num_cus) / 4)
-    return note_grouped("brgemm_bf16_fast<64x64> grouped", launch_bf16_grouped64(a, items, n_items, stream));
-  // ... and the same family on a VNNI-4 B operand (--vnni=4 tile invokes: benchmarks/config/*/*_dp4_*; the generic kernel's MFMA path
-  // took 30 us for 1024 x 2560 x 1024 against 19.5 on VNNI-2)
-  if (vec16_4 && out_ok && !d.generic_forced && !d.vnni_c && d.k % BK == 0 && d.m % 64 == 0 && d.n % 64 == 0 && !((d.ldc | d.stride_b) & 7) && d.ldc < (1 << 22) &&
-      d.lda < (1 << 22) && d.ldb < (1 << 20) && n_dec * (d.m / 64) * (d.n / 64) >= (3 * g_num_cus) / 4)
-    return note_grouped("brgemm_bf16_fast_vnni4<64x64> grouped", launch_bf16_grouped64(a, items, n_items, stream));
-  // (VNNI-4 tile invokes - the compiler-native 32x32x32 tiles of a --vnni=4 pipeline, small groups of 64x64x64 tiles - on the same
-  // kernel: its B fragment is then two 8-byte loads; a single invoke of such a handle stays on the generic kernel's MFMA path.
-  // And tiles whose n is a multiple of 4 but not of 32 (--tiles=64,48,64): a masked last column tile instead of the generic kernel.)
-  const bool small_base = d.dtype == DT_BF16 && d.vnni_b && !d.vnni_c && !d.generic_forced && d.m % 32 == 0 && d.n >= 32 && d.n % 4 == 0 && d.k > 0 &&
-                          d.k % 16 == 0 && !(d.lda & 7) && !(d.stride_a & 7) && !(d.ldc & 3);
-  const bool small4 = small_base && d.vnni_factor == 4 && !(d.stride_b & 3);
-  const bool small_ragged = small_base && d.vnni_factor == 2 && d.n % 32 != 0 && !(d.stride_b & 1);
-  if (vec_ok && out_ok && ((d.variant != V_GENERIC && bf16_small_eligible(d)) || small_ragged || small4)) {
-    // skinny groups with a long reduction: the K steps of a tile over several workgroups (the kernel is a latency-bound stream: 0.047 us
-    // per 16-k step of a workgroup). Measured (profiles/r05_bf16_skinny_small_vs_lw.txt): it pays only while every workgroup still has
-    // a CU to itself - 128 x 1024 x 4096 as 64x64x64 tile invokes 12.0 -> 9.8 us at S = 2 (10.3 at 4, 13.1 at 8), 256 x 1024 x 4096
-    // 12.3 -> 14.2 at S = 2. Hence the largest count with tiles x S <= CUs and at least 32 steps per workgroup, if it saves more
-    // than the hand-off costs. xsmm_hip_force_split overrides.
-    const long long t32 = (long long)n_dec * (d.m / 32) * ((d.n + 31) / 32), steps = (long long)br_hint * (d.k / 16);
-    int S = 1;
-    const int forced = g_forced_split.load(std::memory_order_relaxed);
-    if (forced >= 0) S = forced <= 1 ? 1 : (int)(forced < 16 ? forced : 16);
-    else if (t32 > 0) {
-      long long c = (long long)g_num_cus / t32;
-      if (c > 16) c = 16;
-      if (c > steps / 32) c = steps / 32;
-      if (c >= 2 && 0.047 * (double)(steps - (steps + c - 1) / c) > 2.7 + 0.8) S = (int)c;
-    }
-    if (S > (int)steps) S = steps > 1 ? (int)steps : 1;
-    if (S > 1) return note_grouped(small4 ? "brgemm_bf16_small32_vnni4 grouped, split" : "brgemm_bf16_small32 grouped, split", launch_bf16_small32(a, items, n_items, stream, S));
-    return note_grouped(small4 ? "brgemm_bf16_small32_vnni4 grouped" : "brgemm_bf16_small32 grouped", launch_bf16_small32(a, items, n_items, stream));
-  }
-  if (d.dtype == DT_F32) return note_grouped("brgemm_grouped<f32>", vec ? launch_grouped_t<float, false, true>(a, items, n_items, stream)
-                                                                        : launch_grouped_t<float, false, false>(a, items, n_items, stream));
-  if (d.vnni_b && vec16_4) return note_grouped("brgemm_grouped<bf16,vnni4>", launch_grouped_t<unsigned short, true, true, 4>(a, items, n_items, stream)); // VNNI-4 on the bf16 MFMA path
-  if (d.vnni_b) return note_grouped("brgemm_grouped<bf16,vnni2>", vec16 ? launch_grouped_t<unsigned short, true, true>(a, items, n_items, stream)
-                                                                        : launch_grouped_t<unsigned short, true, false>(a, items, n_items, stream));
-  return note_grouped("brgemm_grouped<bf16,flat>", launch_grouped_t<unsigned short, false, false>(a, items, n_items, stream));
-}
 
-// QUADS (round 6; xsmm_desc.h QuadItem, brgemm_bf16_lw.hip GRP = 2): a group of 64x64 bf16 tile invokes that forms a grid of item rows and
-// item columns runs as 2 x 2 blocks on the 128x128 loader-wave tile when the tile model says so - the kernel the same layer gets as
-// ONE whole-layer call once it is large enough (pick_bf16_lw_tile). 1024 x 2560 x 1024 as 640 invokes: 3 rounds of 64x64 tiles
-// (15.3 us) against 160 workgroups of 128x128 (whole-layer call 10.2 us).
-static bool quads_shape_ok(const GemmDesc &d) {
-  const bool v2 = d.vnni_factor == 2 || d.vnni_factor == 0, v4 = d.vnni_factor == 4;
-  return d.dtype == DT_BF16 && d.vnni_b && (v2 || v4) && !d.vnni_c && !d.b_trans && !d.generic_forced && !d.variant_forced && d.m == 64 && d.n == 64 && d.k > 0 &&
-         d.k % BK == 0 && !((d.lda | d.stride_a | d.stride_b | d.ldc) & 7) && !(d.ldb & (v4 ? 1 : 3)) && d.lda < (1 << 21) && d.ldb < (1 << 20) &&
-         d.ldc < (1 << 22) && d.stride_a >= 0 && d.stride_b >= 0;
-}
-bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) {
-  if (strict_kernels() || !quads_shape_ok(d) || br < 1 || n_items < 4 || (n_items & 3) || g_forced_split.load(std::memory_order_relaxed) >= 0) return false;
-  const double chunks = (double)(br * (d.k / BK));
-  const int64_t cus = g_num_cus;
-  // (a, b) of the tile model: 64x64 (3.75, 0.135), 32x64 + K2 (3.56, 0.098) - what the grouped path would pick from - and 128x128 (6.06, 0.236)
-  const double c64 = (double)((n_items + cus - 1) / cus) * (3.75 + 0.135 * chunks), c32 = (double)((2 * (int64_t)n_items + cus - 1) / cus) * (3.56 + 0.098 * chunks);
-  const double cq = (double)((n_items / 4 + cus - 1) / cus) * (6.06 + 0.236 * chunks);
-  return cq * 1.05 < (c64 < c32 ? c64 : c32);
-}
-hipError_t launch_gemm_quads(const GemmDesc &d, const QuadItem *quads, int n_quads, int64_t br, hipStream_t stream) {
-  if (!quads_shape_ok(d) || br < 1 || n_quads <= 0) return hipErrorInvalidValue;
-  ChainArgs c;
-  memset(&c, 0, sizeof(c));
-  c.lda = d.lda;
-  c.m = 128;
-  c.n = 128;
-  c.nlayers = 1;
-  const int ep = (d.beta0 ? EP_BETA0 : 0) | (d.bias ? EP_BIAS : 0) | (d.relu ? EP_RELU : 0);
-  c.L[0] = ChainLayer{nullptr, nullptr, nullptr, d.ldb, d.ldc, d.stride_a, d.stride_b, (int)d.k, (int)br, ep, 0};
-  const bool v4 = d.vnni_factor == 4;
-  return note_grouped(v4 ? "brgemm_bf16_lw_vnni4<128x128> quads" : "brgemm_bf16_lw<128x128> quads", launch_bf16_lw_quads(v4 ? 4 : 0, c, quads, n_quads, stream));
-}
-
-
-static int pick_f32_variant(const GemmDesc &d) {
-  if (d.k <= 0 || d.k % BK) return V_GENERIC;
-  if ((d.lda | d.ldb | d.stride_a | d.stride_b) & 3) return V_GENERIC;
-  if (d.lda >= (1 << 22) || d.ldb >= (1 << 22) || d.ldc >= (1 << 22)) return V_GENERIC; // 32-bit lane offsets
-  const int64_t m = d.m, n = d.n;
-  auto tiles = [&](int bm, int bn) { return (m % bm == 0 && n % bn == 0) ? (m / bm) * (n / bn) : 0; };
-  // 64-row tiles run on the loader-wave kernels (brgemm_f32_lw.hip). Measured on C2 (256 tiles of 64x64, uniform
-  // [-1, 1) inputs, profiles/r02_f32_variants.txt): 64x64 with the K chunks split over two wave groups (two MFMA
-  // waves per SIMD cover each other's barrier stalls) 18.3 us, one group 18.7 us, the round-1 kernel 19.7-20.4 us.
-  // Outputs with at least one 64x64 tile per CU: 64x64 or 128x64 tiles, whichever needs less time over its rounds
-  // of workgroups (one per CU at a time). A 128x64 round takes ~1.85x a 64x64 round (measured, K = 1024: 32.7 vs
-  // 17.6 us), so 128x64 wins at 1280-2048 x 1024 (one round instead of two) and for large outputs (0.93x), and
-  // loses e.g. at 3072 x 1024 (two rounds against three).
-  // Skinny outputs - at most one 32x16 tile per CU (the reference's M = 128 shapes: 128 x 1024 = 256 tiles, 128 x 768 = 192): the
-  // half-width tiles of brgemm_f32_lw16.hip put a workgroup on every CU where 32x32 tiles would leave half the chip idle, and need
-  // no hand-off between workgroups (the SPLIT launches pay 2.6-2.7 us for one); profiles/r05_lw16_vs_split.txt
-  // (a 16x48 tile of the same family - 256 x 768 outputs are exactly 256 of them - was built and measured: 256 x 768 x 768 5.59 us
-  // against 5.48 on 192 tiles of 32x32, x 3072 14.9 against 13.7: 16 KiB of panel per 98 kflop chunk, the launch is bound by the
-  // L2 -> LDS traffic of all CUs together, ~16 TB/s; removed. profiles/r05_lw16_vs_split.txt)
-  if (d.ldc % 4 == 0 && tiles(32, 16) > 0 && tiles(32, 16) <= g_num_cus) return V_F32_LW16_32x16;
-  if (tiles(64, 64) >= g_num_cus) {
-    const int64_t r64 = (tiles(64, 64) + g_num_cus - 1) / g_num_cus, r128 = (tiles(128, 64) + g_num_cus - 1) / g_num_cus;
-    if (tiles(128, 64) > 0 && 1.85 * (double)r128 < (double)r64) return V_F32_128x64;
-    return V_F32_LW_64x64K2;
-  }
-  if (tiles(64, 32) >= g_num_cus) {
-    // one 64x32 workgroup per CU at a time (96 KiB of LDS), two 32x32 ones (64 KiB): rounds x per-chunk time. 256 x 3072 (384 tiles of
-    // 64x32 = 1.5 rounds) measured 15.9 us against 12.6 on 768 tiles of 32x32; where the rounds tie (C3: 256 / 512 tiles, 128 x 4096)
-    // the larger tile stays - same time, half the LDS traffic (profiles/r05_split_sweep.txt)
-    const int64_t r6432 = (tiles(64, 32) + g_num_cus - 1) / g_num_cus, r32 = (tiles(32, 32) + g_num_cus - 1) / g_num_cus;
-    if (tiles(32, 32) > 0 && 0.23 * 1.05 * (double)r32 < 0.46 * (double)r6432) return V_F32_LW_32x32K4;
-    return V_F32_LW_64x32K2;
-  }
-  if (tiles(32, 32) > 0 && tiles(32, 32) >= tiles(64, 64) * 2 && tiles(64, 32) < g_num_cus) return V_F32_LW_32x32K4;
-  if (tiles(64, 64) > 0) return V_F32_LW_64x64K2;
-  if (tiles(64, 32) > 0) return V_F32_LW_64x32K2;
-  if (tiles(32, 32) > 0) return V_F32_LW_32x32K4;
-  return V_GENERIC;
-}
-
-// Mid-size bf16 outputs: the loader-wave family (brgemm_bf16_lw.hip), the largest tile that still gives at least 3/4 of the CUs
-// a workgroup (one workgroup per CU: 160 KiB of LDS). Outputs too small for that even with 32x64 tiles stay with the 32x32 K-split
-// family (m = 256, n = 1024, K = 1024: 4.9 us against 5.7 on 128 tiles of 32x64, profiles/r03_sweep_shapes.txt).
-// Returns the tile index (0 .. 3) or -1.
-static int pick_bf16_lw_tile(const GemmDesc &d) {
-  // Gate (unchanged since round 3): some tile of the family gives at least 3/4 of the CUs a workgroup. Which tile, round 6 - fitted to the
-  // sweep of the reference's whole shape set over every tile (tools/bf16_sweep.py, profiles/r06_bf16_sweep.txt): a launch costs
-  // rounds x (a + b x chunks), rounds = ceil(tiles / CUs) (one workgroup per CU: a second round is a second kernel's worth), with
-  // (a, b) in us from the K = 1024 / K = 4096 pairs of the sweep: 32x64 (3.56, 0.098), 64x64 (3.75, 0.135), 64x128 (4.66, 0.204), 128x128
-  // (6.06, 0.236). The old rule - the LARGEST tile that still reaches 3/4 of the CUs - put 1024 x 2560 on 320 tiles of 64x128 (two
-  // rounds: 15.1 us) instead of 160 tiles of 128x128 (one round: 10.2 us). The batch count arrives with the invoke: priced at 16 chunks
-  // (K = 1024; the order of two candidates flips with K only when their round counts differ AND the sums are within a few percent).
-  static const double ca[4] = {3.56, 3.75, 4.66, 6.06}, cb[4] = {0.098, 0.135, 0.204, 0.236};
-  bool gate = false;
-  int best = -1;
-  double best_t = 0;
-  for (int t = 3; t >= 0; --t) {
-    int bm, bn;
-    blw_tile_dims(t, &bm, &bn);
-    if (d.m % bm || d.n % bn) continue;
-    const int64_t tiles = (d.m / bm) * (d.n / bn);
-    if (tiles * 4 >= 3 * (int64_t)g_num_cus) gate = true;
-    const double cost = (double)((tiles + g_num_cus - 1) / g_num_cus) * (ca[t] + cb[t] * 16.0);
-    if (best < 0 || cost < best_t) best = t, best_t = cost;
-  }
-  return gate ? best : -1;
-}
-
-static const char *variant_name(int v) {
-  switch (v) {
-  case V_BF16_LW_32x64: return "brgemm_bf16_lw<32x64,k2>";
-  case V_BF16_LW_64x64: return "brgemm_bf16_lw<64x64>";
-  case V_BF16_LW_64x128: return "brgemm_bf16_lw<64x128>";
-  case V_BF16_LW_128x128: return "brgemm_bf16_lw<128x128>";
-  case V_BF16_LWF_32x64: return "brgemm_bf16_lw_flatb<32x64,k2>";
-  case V_BF16_LWF_64x64: return "brgemm_bf16_lw_flatb<64x64>";
-  case V_BF16_LWF_64x128: return "brgemm_bf16_lw_flatb<64x128>";
-  case V_BF16_LWF_128x128: return "brgemm_bf16_lw_flatb<128x128>";
-  case V_BF16_LW4_32x64: return "brgemm_bf16_lw_vnni4<32x64,k2>";
-  case V_BF16_LW4_64x64: return "brgemm_bf16_lw_vnni4<64x64>";
-  case V_BF16_LW4_64x128: return "brgemm_bf16_lw_vnni4<64x128>";
-  case V_BF16_LW4_128x128: return "brgemm_bf16_lw_vnni4<128x128>";
-  case V_F32_64x64: return "brgemm_f32_fast<64x64,k1>";
-  case V_F32_64x32K2: return "brgemm_f32_fast<64x32,k2>";
-  case V_F32_32x32K4: return "brgemm_f32_fast<32x32,k4>";
-  case V_F32_128x64: return "brgemm_f32_fast<128x64,k1>";
-  case V_F32_64x64K2: return "brgemm_f32_fast<64x64,k2>";
-  case V_F32_LW_64x64: return "brgemm_f32_fast_lw<64x64,k1>";
-  case V_F32_LW_64x64K2: return "brgemm_f32_fast_lw<64x64,k2>";
-  case V_F32_LW_64x32K2: return "brgemm_f32_fast_lw<64x32,k4>";
-  case V_F32_LW_32x32K4: return "brgemm_f32_fast_lw<32x32,k4>";
-  case V_F32_LW_128x64: return "brgemm_f32_fast_lw<128x64,k1>";
-  case V_F32_LW16_32x16: return "brgemm_f32_lw16<32x16,k4>";
-  case V_F32_X6_64x64: return "brgemm_f32_bf16x6<64x64,k1>";
-  case V_F32_X6_64x32K2: return "brgemm_f32_bf16x6<64x32,k2>";
-  case V_F32_X6_32x32K4: return "brgemm_f32_bf16x6<32x32,k4>";
-  case V_F32_X6_128x64: return "brgemm_f32_bf16x6<128x64,k1>";
-  case V_BF16_FAST: return "brgemm_bf16_fast<64x64>";
-  case V_BF16_DMA128: return "brgemm_bf16_dma<128x128>";
-  case V_BF16_DMA256: return "brgemm_bf16_dma<256x256>";
-  case V_BF16_SMALL32: return "brgemm_bf16_small<32x32,k4>";
-  default: return "brgemm_grouped(generic)";
-  }
-}
-
-// shapes the bf16x6 split kernel takes: the f32 loader-wave family's preconditions (pick_f32_variant) plus ldc a multiple of 4
-static bool f32_x6_eligible(const GemmDesc &d) {
-  return d.k > 0 && d.k % BK == 0 && d.m % 32 == 0 && d.n % 32 == 0 && !((d.lda | d.ldb | d.ldc | d.stride_a | d.stride_b) & 3) &&
-         d.lda < (1 << 22) && d.ldb < (1 << 22) && d.ldc < (1 << 22);
-}
-
-// split tiles the planner picks by itself for a bf16x6 descriptor (64x64, 64x32 + K2, 32x32 + K4, 128x64): the ones that beat the exact
-// kernel of the same tile. None does yet (profiles/x6_first_ab.txt, kernel averages bf16x6 / exact: first version 1.25 - 4.36; with
-// loader waves doing the split 1.29 - 3.99, e.g. 4096^3 1312.54 against 1015.14 us, 1024x2560x1024 103.87 against 57.49 us): a
-// bf16x6 descriptor stays on the exact plan of mode 0 unless a split tile is forced (xsmm_hip_force_variant 12 .. 15).
-static const bool X6_AUTO[4] = {false, false, false, false};
-
-bool plan_gemm(GemmDesc &d, int forced_variant) {
-  int v = V_GENERIC;
-  if (d.vnni_c) forced_variant = V_GENERIC; // VNNI-2 C store: the generic kernel's epilogue only
-  if (d.dtype == DT_F32 && !d.vnni_b) v = pick_f32_variant(d);
-  else if (d.dtype == DT_BF16 && d.vnni_b && d.vnni_factor == 4) {
-    // VNNI-4 B ([k/4][n][4]: benchmarks/config/omp/mlir-bf16.json:68-100 `--vnni=4`): the loader-wave tiles with the VNNI-4 image
-    // (the largest tile that still gives 3/4 of the CUs a workgroup, else the smallest the shape divides); everything else - ragged
-    // shapes, k not a multiple of 64 (the compiler-native 32x32x32 tiles) - on the generic kernel's element path
-    if (bf16_vnni4_eligible(d)) {
-      int t = pick_bf16_lw_tile(d);
-      for (int c = 0; t < 0 && c < 4; ++c) {
-        int bm, bn;
-        blw_tile_dims(c, &bm, &bn);
-        if (d.m % bm == 0 && d.n % bn == 0) t = c;
-      }
-      if (t >= 0) v = V_BF16_LW4_32x64 + t;
-      if (forced_variant >= V_BF16_LW4_32x64 && forced_variant <= V_BF16_LW4_128x128) {
-        int bm, bn;
-        blw_tile_dims(forced_variant - V_BF16_LW4_32x64, &bm, &bn);
-        if (d.m % bm == 0 && d.n % bn == 0) v = forced_variant;
-      }
-    }
-  } else if (d.dtype == DT_BF16 && bf16_fast_eligible(d)) {
-    v = V_BF16_FAST + pick_bf16_tile(d);
-    // small outputs (e.g. the reference's --batch=256 layers): 32x32 tiles with K split over the waves give
-    // every CU a workgroup. Measured crossover with the 64x64 family (n = 1024, K = 1024): 5.1 vs 8.4 us at 64
-    // tiles of 64x64, 7.5 vs 8.5 at 128, 12.3 vs 8.9 at 256 (profiles/r01_sweep_shapes.txt)
-    if (v == V_BF16_FAST && bf16_small_eligible(d) && (d.m / 64) * (d.n / 64) < (3 * g_num_cus) / 4) v = V_BF16_SMALL32;
-    // mid-size outputs (the 64x64 / 32x32 families, or 128x128 tiles for fewer than 3/4 of the CUs): one loader-wave workgroup
-    // per CU. Measured (profiles/r03_sweep_shapes.txt, 1024-wide layer, K = 1024): see DESIGN.md 4.2.
-    const int64_t t128 = (d.m / 128) * (d.n / 128);
-    if (v == V_BF16_FAST || v == V_BF16_SMALL32 || (v == V_BF16_DMA128 && t128 * 4 < 3 * (int64_t)g_num_cus)) {
-      const int lw = pick_bf16_lw_tile(d);
-      // (round 6: the 128x128 loader-wave tile also where brgemm_bf16_dma128 used to stay - fewer than 3/4 of the CUs busy: 1024 x 2560 x
-      // 1024 = 160 tiles runs 10.2 us on it against 11.5 on dma128, profiles/r06_bf16_sweep_before.txt)
-      if (lw >= 0) v = V_BF16_LW_32x64 + lw;
-    } else if (v == V_BF16_DMA128 && t128 <= (int64_t)g_num_cus && pick_bf16_lw_tile(d) == 3) {
-      // ONE round of 128x128 tiles (the C4 layer 4096 x 1024, C5 2048 x 2048): since the end of round 3 the loader-wave tile is
-      // at least as fast as brgemm_bf16_dma128 there (same box, profiles/r03_write_through_c_stores.txt: C5 18.2 against 18.7 us,
-      // the C4 layer 10.4 against 10.6-11.5) - and it is the tile the 4096-row chain runs on. Several rounds: dma128 (not re-measured).
-      v = V_BF16_LW_128x128;
-    }
-    const int tile = forced_variant - V_BF16_FAST; // a forced bf16 tile is honoured if the shape divides it
-    if (tile >= 0 && tile <= 2 && d.m % (64 << tile) == 0 && d.n % (64 << tile) == 0) v = forced_variant;
-    if (forced_variant == V_BF16_SMALL32 && bf16_small_eligible(d)) v = forced_variant;
-    if (forced_variant >= V_BF16_LW_32x64 && forced_variant <= V_BF16_LW_128x128) {
-      int bm, bn;
-      blw_tile_dims(forced_variant - V_BF16_LW_32x64, &bm, &bn);
-      if (d.m % bm == 0 && d.n % bn == 0) v = forced_variant;
-    }
-  } else if (d.dtype == DT_BF16 && bf16_flat_eligible(d)) {
-    // flat B ([k][n] row-major, what xsmm.unary pack would have turned into VNNI-2): the loader-wave tiles with the interleave
-    // in the B loader. The largest tile that still gives 3/4 of the CUs a workgroup, else the smallest the shape divides
-    // (launch_gemm falls back to the generic kernel when an operand is not 16-byte aligned).
-    int t = pick_bf16_lw_tile(d);
-    for (int c = 0; t < 0 && c < 4; ++c) {
-      int bm, bn;
-      blw_tile_dims(c, &bm, &bn);
-      if (d.m % bm == 0 && d.n % bn == 0) t = c;
-    }
-    if (t >= 0) v = V_BF16_LWF_32x64 + t;
-    if (forced_variant >= V_BF16_LWF_32x64 && forced_variant <= V_BF16_LWF_128x128) {
-      int bm, bn;
-      blw_tile_dims(forced_variant - V_BF16_LWF_32x64, &bm, &bn);
-      if (d.m % bm == 0 && d.n % bn == 0) v = forced_variant;
-    }
-  } else if (d.dtype == DT_BF16 && bf16_small_eligible(d)) {
-    v = V_BF16_SMALL32; // k a multiple of 16 only (e.g. the compiler-native 32x32x32 tile), m or n a multiple of 32 only
-    if (forced_variant == V_BF16_LW_32x64) { // the 32x64 loader-wave tile needs m % 32 only (bf16_fast_eligible asks for 64)
-      GemmDesc e = d;
-      e.m = (d.m + 63) / 64 * 64;
-      if (d.m % 32 == 0 && d.n % 64 == 0 && bf16_fast_eligible(e)) v = forced_variant;
-    }
-  }
-  if (forced_variant >= 0 && d.dtype == DT_F32 && v != V_GENERIC) {
-    // honour the forced tile only if the shape divides it
-    const int bm[] = {64, 64, 32, 128, 64, 64, 64, 64}, bn[] = {64, 32, 32, 64, 64, 64, 64, 32};
-    if (forced_variant <= 7 && d.m % bm[forced_variant] == 0 && d.n % bn[forced_variant] == 0) v = forced_variant;
-    if (forced_variant == V_F32_LW_32x32K4 && d.m % 32 == 0 && d.n % 32 == 0) v = forced_variant;
-    if (forced_variant == V_F32_LW_128x64 && d.m % 128 == 0 && d.n % 64 == 0) v = forced_variant;
-    if (forced_variant == V_F32_LW16_32x16 && d.m % 32 == 0 && d.n % 16 == 0 && d.ldc % 4 == 0) v = forced_variant;
-    if (forced_variant == V_GENERIC) v = V_GENERIC;
-  } else if (forced_variant == V_GENERIC) {
-    v = V_GENERIC;
-  }
-  if (d.f32_prec == 6 && d.dtype == DT_F32 && !d.vnni_b && !d.vnni_c && f32_x6_eligible(d)) {
-    // bf16x6: the split kernel needs 64-k chunks, 16-byte row pieces, the 32-bit lane offsets and ldc a multiple of 4.
-    // It takes the output tile of the exact plan where the split tile of that size measured faster than the exact kernel (X6_AUTO: none
-    // yet); the skinny 32x16 tiles, the generic kernel and forced exact variants stay exact. A forced split tile (xsmm_hip_force_variant
-    // 12 .. 15) is honoured if the shape divides it.
-    const int fx = forced_variant - V_F32_X6_64x64;
-    if (fx >= 0 && fx <= 3) {
-      const int bm[] = {64, 64, 32, 128}, bn[] = {64, 32, 32, 64};
-      if (d.m % bm[fx] == 0 && d.n % bn[fx] == 0) v = forced_variant;
-    } else if (forced_variant < 0) {
-      int t = -1;
-      switch (v) {
-      case V_F32_64x64: case V_F32_64x64K2: case V_F32_LW_64x64: case V_F32_LW_64x64K2: t = 0; break;
-      case V_F32_64x32K2: case V_F32_LW_64x32K2: t = 1; break;
-      case V_F32_32x32K4: case V_F32_LW_32x32K4: t = 2; break;
-      case V_F32_128x64: case V_F32_LW_128x64: t = 3; break;
-      default: break;
-      }
-      if (t >= 0 && X6_AUTO[t]) v = V_F32_X6_64x64 + t;
-    }
-  }
-  d.variant = v;
-  d.generic_forced = forced_variant == V_GENERIC;
-  d.variant_forced = forced_variant >= 0 && v == forced_variant;
-  strncpy(d.name, variant_name(v), sizeof(d.name) - 1);
-  d.name[sizeof(d.name) - 1] = 0;
-  return true;
-}
-
-hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C, const void *D, int64_t br,
-                       hipStream_t stream) {
-  if (d.m <= 0 || d.n <= 0) return hipSuccess;
+static GemmArgs gemm_args(const GemmDesc &d, const void *A, const void *B, void *C, const void *D, int br) {
   GemmArgs a;
   a.A = A; a.B = B; a.C = C; a.D = D;
   a.lda = d.lda; a.ldb = d.ldb; a.ldc = d.ldc; a.stride_a = d.stride_a; a.stride_b = d.stride_b;
-  a.m = (int)d.m; a.n = (int)d.n; a.k = (int)d.k; a.br = (int)(br < 0 ? 0 : br);
+  a.m = (int)d.m; a.n = (int)d.n; a.k = (int)d.k; a.br = br;
   a.ep = (d.beta0 ? EP_BETA0 : 0) | (d.bias ? EP_BIAS : 0) | (d.relu ? EP_RELU : 0) | (d.vnni_c ? EP_VNNI_C : 0);
   a.tiles_m = a.tiles_n = 0;
   a.vf = d.vnni_factor ? d.vnni_factor : 2;
   a.split = 0; a.scratch = nullptr; a.split_cnt = nullptr;
   a.b_trans = d.b_trans;
-  int v = d.variant;
-  g_last_refined.store("", std::memory_order_relaxed);
-  if (d.b_trans) {
-    if (d.dtype != DT_F32 || d.vnni_b) return hipErrorInvalidValue;
-    return launch_grouped_t<float, false, false>(a, nullptr, 1, stream);
-  }
-  // bf16x6: the planned split tile whatever the batch count, split setting or pointer alignment (unaligned A / B: element loads)
-  if (v >= V_F32_X6_64x64 && v <= V_F32_X6_128x64)
-    return launch_f32_x6(v - V_F32_X6_64x64, a, ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0, stream);
-  const bool aligned16 = ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0;
-  if (v != V_GENERIC && !aligned16) v = V_GENERIC;
-  // the bf16 kernel stores 16-byte row pieces and reads the bias 8 bytes at a time
-  if (v >= V_BF16_FAST && v != V_BF16_SMALL32 && ((((uintptr_t)C) & 15) || (d.bias && (((uintptr_t)D) & 7)))) v = V_GENERIC;
-  if (v == V_BF16_SMALL32 && ((((uintptr_t)C) & 7) || (d.bias && (((uintptr_t)D) & 7)))) v = V_GENERIC;
-  // Small bf16 outputs with a LONG reduction: the 32x32 K-split kernel (fragments straight from global memory, two groups of loads
-  // in flight per wave) is latency-bound there - 128 x 1024 x 4096: 15.4 us against 9.8 on 64 loader-wave tiles of 32x64 and 8.1 on
-  // 128 tiles of 32x32 + K2 (the same kernel, twice the workgroups pulling panels). Crossovers (profiles/r05_bf16_skinny_small_vs_lw.txt):
-  // against the 32x32 + K2 instance - usable when the output is at most one 32x32 tile per CU - at K = 1024 (256 x 1024 x 1024: 4.78
-  // against 5.05 us, the reference's bs = 256 bf16 MLP as whole-layer calls 14.3 against 15.7; at K = 768 the K-split kernel still
-  // wins by 0.06-0.2 us), against the 32x64 tile between 1024 and 2048. The batch count arrives with the invoke, so this choice is
-  // made here and not at dispatch.
-  bool bf16_lw_32x32 = false;
-  if (v == V_BF16_SMALL32 && d.variant == V_BF16_SMALL32 && !d.generic_forced && d.k % 64 == 0 && d.m % 32 == 0 && d.n % 64 == 0 && !(((uintptr_t)C) & 15) &&
-      !(d.bias && (((uintptr_t)D) & 7)) && !d.variant_forced) {
-    const bool t32 = (d.m / 32) * (d.n / 32) <= (int64_t)g_num_cus;
-    const int64_t thr = t32 ? 1024 : 1536;
-    GemmDesc e = d;
-    e.m = (d.m + 63) / 64 * 64; // (bf16_fast_eligible asks for m % 64; these tiles need m % 32 only)
-    if ((int64_t)a.br * d.k >= thr && bf16_fast_eligible(e)) {
-      v = V_BF16_LW_32x64;
-      bf16_lw_32x32 = t32;
-      g_last_refined.store(t32 ? "brgemm_bf16_lw<32x32,k2> (long reduction)" : "brgemm_bf16_lw<32x64,k2> (long reduction)", std::memory_order_relaxed);
-    }
-  }
-  if (v >= V_BF16_LW_32x64 && v <= V_BF16_LW4_128x128 && a.br < 1) v = V_GENERIC; // empty batch (C = epilogue of nothing): the loader-wave kernels assume a chunk
-  switch (v) {
+  return a;
+}
+// the one-layer ChainArgs of the bf16 loader-wave launchers (brgemm_bf16_lw.hip); br: the batch count (grouped: the first item's), m x n:
+// the output (of one item, grouped; of a 2 x 2 block of items, quads)
+static ChainArgs one_layer(const GemmArgs &a, int br, int m, int n) {
+  ChainArgs c;
+  memset(&c, 0, sizeof(c));
+  c.A = a.A, c.lda = a.lda, c.m = m, c.n = n, c.nlayers = 1;
+  c.L[0] = ChainLayer{a.B, a.D, a.C, a.ldb, a.ldc, a.stride_a, a.stride_b, a.k, br, a.ep, 0};
+  return c;
+}
+
+// carries out a plan of gemm_plan.cpp. items / n_items: the work list (WorkItem, QuadItem for quads; nullptr and 1 for a single
+// invoke); br: the batch count of the loader-wave bf16 launches (a group's: the first item's)
+static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br, const void *items, int n_items, bool grouped, hipStream_t s) {
+  const WorkItem *wi = (const WorkItem *)items;
+  switch (p.launcher) {
+  case GL_NONE: return hipSuccess;
+  case GL_INVALID: return hipErrorInvalidValue;
   // LDS-DMA panels for every tile but the smallest: measured C2 +3 %, C3 +8 %, 4096^3 +3 %, 3 x 1024 MLP
   // at batch 512 / 1024 +5 % / +3 % over register staging. 32x32 tiles with 4 K-split waves have
   // 512-cycle chunks and short kernels: in a chain of dependent layers (3 x 1024 MLP, batch 256) the DMA
   // path's 2-chunk lead and slower prologue (an LDS-DMA instruction takes ~60 cycles to issue) cost more
   // than the ds_write path saves (32.4 vs 29.2 us); deeper rings (5-6 slots) made the prologue worse.
-  case V_F32_64x64: return launch_fast<2, 2, 1, true>(a, stream);
-  case V_F32_64x32K2: return launch_fast<2, 1, 2, true>(a, stream);
-  case V_F32_32x32K4: return launch_fast<1, 1, 4, false>(a, stream);
-  case V_F32_128x64: return launch_fast<4, 2, 1, true>(a, stream);
-  case V_F32_64x64K2: return launch_fast<2, 2, 2, true>(a, stream);
-  case V_F32_LW_64x64: return launch_f32_lw(0, a, stream);
-  case V_F32_LW_64x64K2:
-  case V_F32_LW_64x32K2:
-  case V_F32_LW_32x32K4: {
-    // skinny outputs (fewer tiles than CUs, a long batch-reduce): several workgroups per tile (choose_f32_split)
-    const int tile = v == V_F32_LW_32x32K4 ? 3 : v - V_F32_LW_64x64;
-    const int bm = tile == 3 ? 32 : 64, bn = tile == 1 ? 64 : 32;
-    const int S = choose_f32_split(tile, (long long)(d.m / bm) * (d.n / bn), (long long)a.br * (d.k / BK));
-    if (S > 1) {
-      const hipError_t e = launch_f32_lw_split(tile, a, S, stream);
-      if (e != hipErrorOutOfMemory && e != hipErrorInvalidValue) {
-        g_last_refined.store(tile == 1 ? "brgemm_f32_lw<64x64,k2>, split" : tile == 2 ? "brgemm_f32_lw<64x32,k4>, split" : "brgemm_f32_lw<32x32,k4>, split", std::memory_order_relaxed);
-        return e;
-      }
-      (void)hipGetLastError(); // no scratch block: the unsplit launch
+  case GL_F32_FAST:
+    switch (p.tile) {
+    case V_F32_64x64: return launch_fast<2, 2, 1, true>(a, s);
+    case V_F32_64x32K2: return launch_fast<2, 1, 2, true>(a, s);
+    case V_F32_32x32K4: return launch_fast<1, 1, 4, false>(a, s);
+    case V_F32_128x64: return launch_fast<4, 2, 1, true>(a, s);
+    case V_F32_64x64K2: return launch_fast<2, 2, 2, true>(a, s);
+    default: return hipErrorInvalidValue;
     }
-    return launch_f32_lw(tile, a, stream);
-  }
-  case V_F32_LW_128x64: return launch_f32_lw(4, a, stream);
-  case V_F32_LW16_32x16: {
-    if (((uintptr_t)C) & 15 || (d.bias && (((uintptr_t)D) & 15))) break; // 16-byte pieces of C and of the bias row: else the generic kernel below
-    // LONG reductions (K >= 3072): every XCD streams all of A besides its share of B on the half-width tiles and their chunk time
-    // rises by 40 % (128 x 1024 x 4096: 14.6 us); the 32x32 tiles with the k range shared between XCD-aligned workgroups fetch every
-    // byte once (12.8 us). The batch count arrives with the invoke, so this is decided here. (profiles/r05_lw16_vs_split.txt)
-    const long long chunks = (long long)a.br * (d.k / BK);
-    if (chunks >= 48 && !d.variant_forced && d.n % 32 == 0) {
-      const int S = choose_f32_split(3, (long long)(d.m / 32) * (d.n / 32), chunks);
-      if (S > 1) {
-        const hipError_t e = launch_f32_lw_split(3, a, S, stream);
-        if (e != hipErrorOutOfMemory && e != hipErrorInvalidValue) {
-          g_last_refined.store("brgemm_f32_lw<32x32,k4>, split (long reduction)", std::memory_order_relaxed);
-          return e;
-        }
-        (void)hipGetLastError();
-      }
+  case GL_F32_LW: return launch_f32_lw(p.tile, a, s);
+  case GL_F32_LW16: return launch_f32_lw16(p.tile, a, wi, n_items, grouped, s);
+  case GL_F32_LW_GROUPED: return launch_f32_lw_grouped(p.tile, a, wi, n_items, p.split, s);
+  case GL_F32_X6: return launch_f32_x6(p.tile, a, p.vec, s);
+  case GL_BF16_FAST: return launch_gemm_bf16_fast(p.tile, a, s);
+  case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split);
+  case GL_BF16_GROUPED64: return launch_bf16_grouped64(a, wi, n_items, s);
+  case GL_BF16_LW: return (p.b_kind == 4 ? launch_bf16_lw_vnni4 : p.b_kind == 2 ? launch_bf16_lw_flatb : launch_bf16_lw)(p.tile, one_layer(a, br, a.m, a.n), s);
+  case GL_BF16_LW_GROUPED: return launch_bf16_lw_grouped(p.tile, p.b_kind, one_layer(a, br, a.m, a.n), items, n_items, p.even, s);
+  case GL_BF16_LW_QUADS: return launch_bf16_lw_quads(p.b_kind, one_layer(a, br, 128, 128), items, n_items, s);
+  case GL_GENERIC:
+    switch (p.generic) {
+    case GG_F32: return launch_grouped_t<float, false, false>(a, wi, n_items, s);
+    case GG_F32_VEC: return launch_grouped_t<float, false, true>(a, wi, n_items, s);
+    case GG_BF16_VNNI2: return launch_grouped_t<unsigned short, true, false>(a, wi, n_items, s);
+    case GG_BF16_VNNI2_VEC: return launch_grouped_t<unsigned short, true, true>(a, wi, n_items, s);
+    case GG_BF16_VNNI4_VEC: return launch_grouped_t<unsigned short, true, true, 4>(a, wi, n_items, s);
+    case GG_BF16_FLAT: return launch_grouped_t<unsigned short, false, false>(a, wi, n_items, s);
     }
-    return launch_f32_lw16(0, a, nullptr, 1, false, stream);
   }
-  case V_BF16_FAST:
-  case V_BF16_DMA128:
-  case V_BF16_DMA256: return launch_gemm_bf16_fast(v - V_BF16_FAST, a, stream);
-  case V_BF16_SMALL32: return launch_bf16_small32(a, nullptr, 1, stream);
-  case V_BF16_LW_32x64:
-  case V_BF16_LW_64x64:
-  case V_BF16_LW_64x128:
-  case V_BF16_LW_128x128: {
-    ChainArgs c;
-    c.A = a.A; c.lda = a.lda; c.cnt = nullptr; c.err = nullptr; c.target = 0;
-    c.m = a.m; c.n = a.n; c.nlayers = 1; c.tiles_m = c.tiles_n = 0; c.xm = 0;
-    c.L[0] = ChainLayer{a.B, a.D, a.C, a.ldb, a.ldc, a.stride_a, a.stride_b, a.k, a.br, a.ep, 0};
-    return launch_bf16_lw(bf16_lw_32x32 ? 4 : v - V_BF16_LW_32x64, c, stream);
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C, const void *D, int64_t br,
+                       hipStream_t stream) {
+  const uintptr_t ab = (uintptr_t)A | (uintptr_t)B, c = (uintptr_t)C, dp = (uintptr_t)D;
+  const GemmLaunch p = plan_gemm_call(d, br, GemmAlign{!(ab & 15), !(c & 15), !(c & 7), !(dp & 7), !(dp & 15)}, gemm_plan_env());
+  if (p.launcher == GL_NONE) return hipSuccess;
+  const GemmArgs a = gemm_args(d, A, B, C, D, (int)(br < 0 ? 0 : br));
+  const char *text = p.text;
+  if (p.split > 1 && (p.launcher == GL_F32_LW || p.launcher == GL_F32_LW16)) { // a SPLIT launch (its scratch block may be missing)
+    const hipError_t e = launch_f32_lw_split(p.launcher == GL_F32_LW ? p.tile : 3, a, p.split, stream);
+    if (e != hipErrorOutOfMemory && e != hipErrorInvalidValue) return g_last_refined.store(text, std::memory_order_relaxed), e;
+    (void)hipGetLastError(); // no scratch block: the unsplit launch
+    text = "";
   }
-  case V_BF16_LW4_32x64:
-  case V_BF16_LW4_64x64:
-  case V_BF16_LW4_64x128:
-  case V_BF16_LW4_128x128: {
-    ChainArgs c;
-    c.A = a.A; c.lda = a.lda; c.cnt = nullptr; c.err = nullptr; c.target = 0;
-    c.m = a.m; c.n = a.n; c.nlayers = 1; c.tiles_m = c.tiles_n = 0; c.xm = 0;
-    c.L[0] = ChainLayer{a.B, a.D, a.C, a.ldb, a.ldc, a.stride_a, a.stride_b, a.k, a.br, a.ep, 0};
-    // (round 6) skinny outputs with a long reduction: the 32x32 + K2 instance, as for VNNI-2 operands above - at most one 32x32 tile
-    // per CU and K >= 1024: twice the workgroups of the 32x64 tile pulling panels (128 x 1024 x 4096: 9.3 -> 7.6 us)
-    if (v == V_BF16_LW4_32x64 && !d.variant_forced && !d.generic_forced && d.m % 32 == 0 && d.n % 32 == 0 &&
-        (d.m / 32) * (d.n / 32) <= (int64_t)g_num_cus && (int64_t)a.br * d.k >= 1024) {
-      g_last_refined.store("brgemm_bf16_lw_vnni4<32x32,k2> (long reduction)", std::memory_order_relaxed);
-      return launch_bf16_lw_vnni4(4, c, stream);
-    }
-    return launch_bf16_lw_vnni4(v - V_BF16_LW4_32x64, c, stream);
-  }
-  case V_BF16_LWF_32x64:
-  case V_BF16_LWF_64x64:
-  case V_BF16_LWF_64x128:
-  case V_BF16_LWF_128x128: {
-    ChainArgs c;
-    c.A = a.A; c.lda = a.lda; c.cnt = nullptr; c.err = nullptr; c.target = 0;
-    c.m = a.m; c.n = a.n; c.nlayers = 1; c.tiles_m = c.tiles_n = 0; c.xm = 0;
-    c.L[0] = ChainLayer{a.B, a.D, a.C, a.ldb, a.ldc, a.stride_a, a.stride_b, a.k, a.br, a.ep, 0};
-    return launch_bf16_lw_flatb(v - V_BF16_LWF_32x64, c, stream);
-  }
-  default: break;
-  }
-  // everything else: the grouped kernel with a single, inline work item
-  const bool tiles_ok = aligned16 && d.n % 4 == 0 && d.k % GK == 0; // ragged m / n edges are predicated
-  const bool vec = aligned16 && d.n % 4 == 0 && d.k % 4 == 0 && d.dtype == DT_F32 && !d.vnni_b && !((d.lda | d.ldb | d.stride_a | d.stride_b) & 3) &&
-                   d.lda < (1 << 24) && d.ldb < (1 << 24); // (32-bit tile-relative lane offsets)
-  const bool vec16x = d.dtype == DT_BF16 && d.vnni_b && !((d.lda | d.stride_a | d.stride_b) & 7) && d.lda < (1 << 21) && d.ldb < (1 << 21);
-  const bool vec16_4 = vec16x && d.vnni_factor == 4 && aligned16 && d.n % 2 == 0 && d.k % GK == 0 && !(d.ldb & 1); // VNNI-4: 16-byte pieces of 2 columns
-  const bool vec16 = tiles_ok && d.dtype == DT_BF16 && d.vnni_b && d.vnni_factor == 2 && !((d.lda | d.stride_a | d.stride_b) & 7) && !(d.ldb & 3) &&
-                     d.lda < (1 << 21) && d.ldb < (1 << 21); // (32-bit lane offsets)
-  // a SINGLE invoke of a 32-k f32 tile with an even batch count: the kernel its group would run on in the tile queue (the
-  // loader-wave pair mode, tile chosen as launch_gemm_grouped does for one item) - queue on and queue off then add in the same order
-  if (vec && !d.generic_forced && d.k == 32 && a.br >= 2 && !(a.br & 1) && d.m % 32 == 0 && d.n % 32 == 0 && d.stride_a >= 0 &&
-      d.stride_b >= 0 && d.stride_a < (1 << 26) && d.stride_b < (1 << 26) && d.lda < (1 << 22) && d.ldb < (1 << 22) && d.ldc < (1 << 22)) {
-    const int64_t t64 = (d.m % 64 == 0 && d.n % 64 == 0) ? (d.m / 64) * (d.n / 64) : 0;
-    const int64_t t6432 = (d.m % 64 == 0) ? (d.m / 64) * (d.n / 32) : 0;
-    if (t64 >= g_num_cus) return launch_f32_lw_grouped(t64 >= 2 * g_num_cus ? 0 : 1, a, nullptr, 1, 1, stream);
-    if (t6432 >= g_num_cus) return launch_f32_lw_grouped(2, a, nullptr, 1, 1, stream);
-    return launch_f32_lw_grouped(3, a, nullptr, 1, choose_f32_split(3, (d.m / 32) * (d.n / 32), a.br / 2), stream);
-  }
-  // a SINGLE invoke of a tile whose n ends inside a 32-column block (--tiles=64,48,64): the loader-wave kernel its group runs on
-  if (vec && !d.generic_forced && d.k % BK == 0 && a.br >= 1 && d.m % 32 == 0 && d.n > 32 && d.n % 32 != 0 && d.lda < (1 << 22) && d.ldb < (1 << 22) &&
-      d.ldc < (1 << 22))
-    return launch_f32_lw_grouped(3, a, nullptr, 1, choose_f32_split(3, (d.m / 32) * ((d.n + 31) / 32), (long long)a.br * (d.k / BK)), stream);
-  if (d.dtype == DT_F32) return vec ? launch_grouped_t<float, false, true>(a, nullptr, 1, stream)
-                                    : launch_grouped_t<float, false, false>(a, nullptr, 1, stream);
-  if (d.vnni_b && vec16_4) return launch_grouped_t<unsigned short, true, true, 4>(a, nullptr, 1, stream);
-  if (d.vnni_b) return vec16 ? launch_grouped_t<unsigned short, true, true>(a, nullptr, 1, stream)
-                             : launch_grouped_t<unsigned short, true, false>(a, nullptr, 1, stream);
-  return launch_grouped_t<unsigned short, false, false>(a, nullptr, 1, stream);
+  g_last_refined.store(text, std::memory_order_relaxed);
+  return run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+}
+
+hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_items, bool vec_ok, bool out_ok, bool pair_ok,
+                               int64_t br_hint, hipStream_t stream) {
+  const GemmLaunch p = plan_gemm_group(d, n_items, vec_ok, out_ok, pair_ok, br_hint, gemm_plan_env());
+  if (p.launcher == GL_NONE || p.launcher == GL_INVALID) return p.launcher == GL_NONE ? hipSuccess : hipErrorInvalidValue;
+  g_last_grouped.store(p.text, std::memory_order_relaxed);
+  return run_gemm_launch(p, gemm_args(d, nullptr, nullptr, nullptr, nullptr, 0), (int)br_hint, items, n_items, true, stream);
+}
+
+// QUADS (round 6; xsmm_desc.h QuadItem, brgemm_bf16_lw.hip GRP = 2): a group of 64x64 bf16 tile invokes that forms a grid of item rows and
+// item columns runs as 2 x 2 blocks on the 128x128 loader-wave tile when the tile model says so (gemm_quads_pay) - the kernel the same
+// layer gets as ONE whole-layer call once it is large enough. 1024 x 2560 x 1024 as 640 invokes: 3 rounds of 64x64 tiles (15.3 us)
+// against 160 workgroups of 128x128 (whole-layer call 10.2 us).
+hipError_t launch_gemm_quads(const GemmDesc &d, const QuadItem *quads, int n_quads, int64_t br, hipStream_t stream) {
+  const GemmLaunch p = plan_gemm_quads(d, n_quads, br);
+  if (p.launcher == GL_INVALID) return hipErrorInvalidValue;
+  g_last_grouped.store(p.text, std::memory_order_relaxed);
+  return run_gemm_launch(p, gemm_args(d, nullptr, nullptr, nullptr, nullptr, 0), (int)br, quads, n_quads, true, stream);
 }
 
 } // namespace tpp

@@ -782,14 +782,7 @@ template <int WM, int WN, int WK, int NL> static hipError_t launch_f32_chain_t(c
   return hipGetLastError();
 }
 
-// tile as in launch_f32_lw: 1 = 64x64 + K2, 2 = 64x32 + K4 (K-split tiles: 16-byte stores; 32x32 + K4 measured slower than three launches)
-bool f32_chain_tile_dims(int tile, int *bm, int *bn) {
-  switch (tile) {
-  case 1: *bm = 64, *bn = 64; return true;
-  case 2: *bm = 64, *bn = 32; return true;
-  default: return false;
-  }
-}
+// tile as in launch_f32_lw: 1 = 64x64 + K2, 2 = 64x32 + K4 (gemm_plan.h f32_chain_tile_dims)
 hipError_t launch_f32_chain(int tile, const ChainArgs &a, hipStream_t s) {
   switch (tile) {
   case 1: return launch_f32_chain_t<2, 2, 2, 2>(a, s);

@@ -42,8 +42,7 @@ struct ChainArgs {
 };
 static_assert(offsetof(ChainArgs, L) == 72, "the kernels' code depends on where the layer table lies");
 
-// tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128
-void blw_tile_dims(int tile, int *bm, int *bn);
+// tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (gemm_plan.h blw_tile_dims)
 hipError_t launch_bf16_lw(int tile, const ChainArgs &a, hipStream_t s);
 hipError_t launch_bf16_lw_flatb(int tile, const ChainArgs &a, hipStream_t s); // the same tiles, B operand flat [k][ldb] (no VNNI flag)
 hipError_t launch_bf16_lw_vnni4(int tile, const ChainArgs &a, hipStream_t s); // the same tiles, B operand VNNI-4 [k/4][ldb][4]
@@ -54,8 +53,7 @@ hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, cons
 // 2 x 2 blocks of 64x64 items on the 128x128 tile (quads: QuadItem[n_quads], xsmm_desc.h; a.m = a.n = 128, leading dimensions / strides / k the items')
 hipError_t launch_bf16_lw_quads(int b_kind, const ChainArgs &a, const void *quads, int n_quads, hipStream_t s);
 
-// f32 chains (brgemm_f32_lw.hip): tile 1 = 64x64 + K2, 2 = 64x32 + K4 - the 64-row K-split loader-wave tiles
-bool f32_chain_tile_dims(int tile, int *bm, int *bn);
+// f32 chains (brgemm_f32_lw.hip): tile 1 = 64x64 + K2, 2 = 64x32 + K4 - the 64-row K-split loader-wave tiles (gemm_plan.h f32_chain_tile_dims)
 hipError_t launch_f32_chain(int tile, const ChainArgs &a, hipStream_t s);
 
 } // namespace tpp

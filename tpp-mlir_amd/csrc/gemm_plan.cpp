@@ -1,0 +1,569 @@
+// gemm_plan.cpp - the GEMM kernel planner (gemm_plan.h): host-only, no kernels, no HIP runtime calls. Its choices, case by case, are
+// tests/golden/gemm_plan.txt (tests/test_gemm_plan.py): a change of a rule or a cost coefficient is a change of that table.
+#include "gemm_plan.h"
+#include <string.h>
+
+namespace tpp {
+
+constexpr int BK = 64;           // k per chunk of the tiled kernels (BK of brgemm_f32.hip, BKH of brgemm_bf16.hip, ...)
+constexpr int GK = 32;           // k per chunk of the generic kernel (brgemm_f32.hip brgemm_grouped)
+constexpr int SPLIT_MAX_WG = 16; // = SPLIT_MAX of split_scratch.h
+// what handing a tile's partial sums over between the workgroups of a SPLIT launch costs, in us: three dependent trips to the memory
+// side (partial tile written through and acknowledged, arrival counter, the other partials read back) - 2.6-2.7 us measured - and a margin
+constexpr double SPLIT_HANDOFF_US = 2.7 + 0.8;
+
+static int64_t rounds(int64_t workgroups, int64_t cus) { return (workgroups + cus - 1) / cus; } // of one workgroup per CU
+
+// the f32 loader-wave families (brgemm_f32_lw.hip, brgemm_f32_lw16.hip, brgemm_f32_x6.hip): 16-byte A / B row pieces, 32-bit lane offsets
+static bool f32_lw_operands_ok(const GemmDesc &d) {
+  return !((d.lda | d.ldb | d.stride_a | d.stride_b) & 3) && d.lda < (1 << 22) && d.ldb < (1 << 22) && d.ldc < (1 << 22);
+}
+// 32-k f32 tiles on the loader-wave kernels' pair mode (a 64-k chunk from the blocks of two batch elements): the strides in 32 bits
+static bool f32_pairs_ok(const GemmDesc &d) {
+  return d.k == 32 && d.stride_a >= 0 && d.stride_b >= 0 && d.stride_a < (1 << 26) && d.stride_b < (1 << 26);
+}
+// shapes the bf16x6 split kernel takes: the f32 loader-wave family's preconditions (pick_f32_variant) plus ldc a multiple of 4
+static bool f32_x6_eligible(const GemmDesc &d) {
+  return d.k > 0 && d.k % BK == 0 && d.m % 32 == 0 && d.n % 32 == 0 && !(d.ldc & 3) && f32_lw_operands_ok(d);
+}
+
+// bf16 + VNNI-2 B, k a multiple of 64, m and n of 64, 16-byte-aligned leading dimensions within the 32-bit lane offsets: what the
+// LDS-DMA bf16 tile families (brgemm_bf16.hip, brgemm_bf16_lw.hip) need
+static bool bf16_fast_eligible(const GemmDesc &d) { // (VNNI-4 operands: bf16_vnni4_eligible)
+  return d.dtype == DT_BF16 && d.vnni_b && d.vnni_factor == 2 && d.k > 0 && d.k % BK == 0 && d.m % 64 == 0 && d.n % 64 == 0 &&
+         !((d.lda | d.ldc | d.stride_a | d.stride_b) & 7) && !(d.ldb & 3) && d.lda < (1 << 22) && d.ldb < (1 << 21) && d.ldc < (1 << 22);
+}
+// flat-B bf16 for the loader-wave tiles: 16-byte row pieces of A, B and C, 64-k chunks, 32-bit lane offsets
+static bool bf16_flat_eligible(const GemmDesc &d) {
+  return d.dtype == DT_BF16 && !d.vnni_b && !d.vnni_c && d.k > 0 && d.k % 64 == 0 && d.m % 32 == 0 && d.n % 64 == 0 &&
+         !((d.lda | d.ldb | d.ldc | d.stride_a | d.stride_b) & 7) && d.lda < (1 << 22) && d.ldb < (1 << 21) && d.ldc < (1 << 22);
+}
+// VNNI-4 B for the loader-wave tiles: k-group rows of 8 * ldb bytes in 16-byte pieces, 64-k chunks, 32-bit lane offsets
+static bool bf16_vnni4_eligible(const GemmDesc &d) {
+  return d.dtype == DT_BF16 && d.vnni_b && d.vnni_factor == 4 && !d.vnni_c && d.k > 0 && d.k % 64 == 0 && d.m % 32 == 0 && d.n % 64 == 0 &&
+         !((d.lda | d.ldc | d.stride_a | d.stride_b) & 7) && !(d.ldb & 1) && d.lda < (1 << 22) && d.ldb < (1 << 20) && d.ldc < (1 << 22);
+}
+// item lists on the loader-wave tiles (brgemm_bf16_lw.hip launch_bf16_lw_grouped / launch_bf16_lw_quads; VNNI-2 or VNNI-4 B): the
+// operand limits those launches were written and measured with - tighter than the whole-layer tiles' (lda < 2^21 against 2^22, ldb
+// < 2^20 against 2^21 for VNNI-2), non-negative strides - and neither a forced kernel nor a VNNI C. n is the caller's.
+static bool bf16_lw_items_ok(const GemmDesc &d, bool v4) {
+  return d.dtype == DT_BF16 && d.vnni_b && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.k > 0 && d.k % BK == 0 && d.m % 32 == 0 &&
+         !((d.lda | d.stride_a | d.stride_b | d.ldc) & 7) && !(d.ldb & (v4 ? 1 : 3)) && d.lda < (1 << 21) && d.ldb < (1 << 20) &&
+         d.ldc < (1 << 22) && d.stride_a >= 0 && d.stride_b >= 0;
+}
+// the 32x32 K-split bf16 kernel (brgemm_bf16_small.hip): fragments straight from global memory, 16-k steps, 8-byte output pieces
+static bool bf16_small_operands_ok(const GemmDesc &d) {
+  return d.dtype == DT_BF16 && d.vnni_b && d.m % 32 == 0 && d.k > 0 && d.k % 16 == 0 && !(d.lda & 7) && !(d.stride_a & 7) && !(d.ldc & 3);
+}
+static bool bf16_small_eligible(const GemmDesc &d) {
+  return bf16_small_operands_ok(d) && d.vnni_factor == 2 && d.n % 32 == 0 && !(d.stride_b & 1);
+}
+// 2 x 2 blocks of 64x64 items on the 128x128 loader-wave tile (QUADS, launch_gemm_quads)
+static bool quads_shape_ok(const GemmDesc &d) {
+  const bool v2 = d.vnni_factor == 2 || d.vnni_factor == 0, v4 = d.vnni_factor == 4;
+  return (v2 || v4) && !d.b_trans && d.m == 64 && d.n == 64 && bf16_lw_items_ok(d, v4);
+}
+
+// the generic kernel (brgemm_f32.hip brgemm_grouped) and which 16-byte load paths it may take (vec_ok: every A and B 16-byte aligned):
+// vec f32 16-byte pieces (32-bit tile-relative lane offsets: 32 rows x ld x 4 B < 2^31); vec16 bf16 + VNNI-2 B, 8-element A pieces,
+// pair-rows of B 16-byte aligned; vec16_4 bf16 + VNNI-4 B, 16-byte pieces of 2 columns
+struct GenericOk { bool vec, vec16, vec16_4; };
+static GenericOk generic_ok(const GemmDesc &d, bool vec_ok) {
+  const bool tiles_ok = vec_ok && d.n % 4 == 0 && d.k % GK == 0; // ragged m / n edges are predicated
+  const bool vec16x = d.dtype == DT_BF16 && d.vnni_b && !((d.lda | d.stride_a | d.stride_b) & 7) && d.lda < (1 << 21) && d.ldb < (1 << 21);
+  GenericOk g;
+  g.vec = vec_ok && d.n % 4 == 0 && d.k % 4 == 0 && d.dtype == DT_F32 && !d.vnni_b && !((d.lda | d.ldb | d.stride_a | d.stride_b) & 3) &&
+          d.lda < (1 << 24) && d.ldb < (1 << 24);
+  g.vec16 = tiles_ok && vec16x && d.vnni_factor == 2 && !(d.ldb & 3);
+  g.vec16_4 = vec16x && d.vnni_factor == 4 && vec_ok && d.n % 2 == 0 && d.k % GK == 0 && !(d.ldb & 1);
+  return g;
+}
+static GemmGeneric generic_kernel(const GemmDesc &d, const GenericOk &g) { // (VNNI-4 B: on the bf16 MFMA path with 16-byte pieces only)
+  if (d.dtype == DT_F32) return g.vec ? GG_F32_VEC : GG_F32;
+  return !d.vnni_b ? GG_BF16_FLAT : g.vec16_4 ? GG_BF16_VNNI4_VEC : g.vec16 ? GG_BF16_VNNI2_VEC : GG_BF16_VNNI2;
+}
+
+// The bf16 loader-wave tiles (brgemm_bf16_lw.hip), fitted to the sweep of the reference's whole shape set over every tile
+// (tools/bf16_sweep.py, profiles/r06_bf16_sweep.txt): a launch costs rounds x (a + b x chunks), rounds = ceil(workgroups / CUs) (one
+// workgroup per CU: a second round is a second kernel's worth), (a, b) in us from the K = 1024 / K = 4096 pairs of the sweep. Tile index
+// as launch_bf16_lw: 0 = 32x64 + K2, 1 = 64x64, 2 = 64x128, 3 = 128x128, 4 = 32x32 + K2 (from 128 x 1024 x 1024 / x 4096 on that tile).
+static const double BLW_A[5] = {3.56, 3.75, 4.66, 6.06, 3.52}, BLW_B[5] = {0.098, 0.135, 0.204, 0.236, 0.072};
+static double blw_cost(int tile, int64_t rounds, double chunks) { return (double)rounds * (BLW_A[tile] + BLW_B[tile] * chunks); }
+
+// f32: rounds of workgroups x per-chunk time - one 64x32 workgroup per CU at a time (96 KiB of LDS), two 32x32 ones (64 KiB). 256 x
+// 3072 (384 tiles of 64x32 = 1.5 rounds) measured 15.9 us against 12.6 on 768 tiles of 32x32; where the rounds tie (C3: 256 / 512
+// tiles, 128 x 4096) the larger tile stays - same time, half the LDS traffic (profiles/r05_split_sweep.txt)
+static bool f32_32x32_beats_64x32(int64_t t32, int64_t t6432, int64_t cus) {
+  return 0.23 * 1.05 * (double)rounds(t32, cus) < 0.46 * (double)rounds(t6432, cus);
+}
+
+// How many workgroups share the batch-reduce range of ONE output tile (SPLIT kernels of brgemm_f32_lw.hip) - 1 = no split.
+// tile: 1 = 64x64 + K2, 2 = 64x32 + K4, 3 = 32x32 + K4; tiles: output tiles of the whole launch; chunks: 64-k chunks per tile.
+// Fitted to profiles/r05_split_sweep.txt (whole-layer calls of the reference's skinny benchmark shapes over tile x split count):
+//  * a workgroup alone on a CU needs c(tile) us per chunk (the matrix pipes' rate: 0.213 us for a 32x32x64 chunk);
+//  * a split costs the hand-off whatever the count, so it pays only where it takes more than that off the K loop;
+//  * more workgroups than CUs never paid: 128 x 1024 x 4096 on 32x32 tiles 17.1 us unsplit, 12.9 (S = 2: 256 workgroups), 13.6 (S = 4:
+//    512), 15.6 (6), 20.6 (8) - every further round of workgroups pays its own prologue and hand-off.
+// Hence: the largest S with tiles * S <= CUs, if the K-loop time it saves exceeds the hand-off. The answer depends on the
+// descriptor, the batch count and the number of tiles in the launch only: the same call pattern always adds in the same order.
+// xsmm_hip_force_split / TPP_HIP_SPLIT: 0 / 1 = never split, n > 1 = always n (clamped to the chunks), -1 = this model.
+static int choose_f32_split(int tile, long long tiles, long long chunks, const GemmPlanEnv &env) {
+  const int forced = env.forced_split;
+  if (tile < 1 || tile > 3 || tiles <= 0 || chunks < 2) return 1;
+  const long long smax = chunks < SPLIT_MAX_WG ? chunks : SPLIT_MAX_WG;
+  if (forced >= 0) return forced <= 1 ? 1 : (int)(forced < smax ? forced : smax);
+  const double c = tile == 1 ? 0.92 : tile == 2 ? 0.46 : 0.213;
+  long long S = env.cus / tiles;
+  if (S > smax) S = smax;
+  if (S > chunks / 4) S = chunks / 4; // at least four chunks per workgroup
+  if (S < 2) return 1;
+  const long long per = (chunks + S - 1) / S;
+  const double saved = c * (double)(chunks - per);
+  return saved > SPLIT_HANDOFF_US ? (int)S : 1;
+}
+
+// The 32x32 K-split bf16 kernel over several workgroups per tile, for skinny groups with a long reduction (the kernel is a
+// latency-bound stream: 0.047 us per 16-k step of a workgroup). Measured (profiles/r05_bf16_skinny_small_vs_lw.txt): it pays only
+// while every workgroup still has a CU to itself - 128 x 1024 x 4096 as 64x64x64 tile invokes 12.0 -> 9.8 us at S = 2 (10.3 at 4,
+// 13.1 at 8), 256 x 1024 x 4096 12.3 -> 14.2 at S = 2. Hence the largest count with tiles x S <= CUs and at least 32 steps per
+// workgroup, if it saves more than the hand-off costs. xsmm_hip_force_split overrides.
+static int choose_bf16_small_split(long long t32, long long steps, const GemmPlanEnv &env) {
+  int S = 1;
+  const int forced = env.forced_split;
+  if (forced >= 0) S = forced <= 1 ? 1 : (int)(forced < 16 ? forced : 16);
+  else if (t32 > 0) {
+    long long c = (long long)env.cus / t32;
+    if (c > 16) c = 16;
+    if (c > steps / 32) c = steps / 32;
+    if (c >= 2 && 0.047 * (double)(steps - (steps + c - 1) / c) > SPLIT_HANDOFF_US) S = (int)c;
+  }
+  if (S > (int)steps) S = steps > 1 ? (int)steps : 1;
+  return S;
+}
+
+static int pick_f32_variant(const GemmDesc &d, int64_t cus) {
+  if (d.k <= 0 || d.k % BK) return V_GENERIC;
+  if (!f32_lw_operands_ok(d)) return V_GENERIC;
+  const int64_t m = d.m, n = d.n;
+  auto tiles = [&](int bm, int bn) { return (m % bm == 0 && n % bn == 0) ? (m / bm) * (n / bn) : 0; };
+  // 64-row tiles run on the loader-wave kernels (brgemm_f32_lw.hip). Measured on C2 (256 tiles of 64x64, uniform
+  // [-1, 1) inputs, profiles/r02_f32_variants.txt): 64x64 with the K chunks split over two wave groups (two MFMA
+  // waves per SIMD cover each other's barrier stalls) 18.3 us, one group 18.7 us, the round-1 kernel 19.7-20.4 us.
+  // Outputs with at least one 64x64 tile per CU: 64x64 or 128x64 tiles, whichever needs less time over its rounds
+  // of workgroups (one per CU at a time). A 128x64 round takes ~1.85x a 64x64 round (measured, K = 1024: 32.7 vs
+  // 17.6 us), so 128x64 wins at 1280-2048 x 1024 (one round instead of two) and for large outputs (0.93x), and
+  // loses e.g. at 3072 x 1024 (two rounds against three).
+  // Skinny outputs - at most one 32x16 tile per CU (the reference's M = 128 shapes: 128 x 1024 = 256 tiles, 128 x 768 = 192): the
+  // half-width tiles of brgemm_f32_lw16.hip put a workgroup on every CU where 32x32 tiles would leave half the chip idle, and need
+  // no hand-off between workgroups (the SPLIT launches pay 2.6-2.7 us for one); profiles/r05_lw16_vs_split.txt
+  // (a 16x48 tile of the same family - 256 x 768 outputs are exactly 256 of them - was built and measured: 256 x 768 x 768 5.59 us
+  // against 5.48 on 192 tiles of 32x32, x 3072 14.9 against 13.7: 16 KiB of panel per 98 kflop chunk, the launch is bound by the
+  // L2 -> LDS traffic of all CUs together, ~16 TB/s; removed. profiles/r05_lw16_vs_split.txt)
+  if (d.ldc % 4 == 0 && tiles(32, 16) > 0 && tiles(32, 16) <= cus) return V_F32_LW16_32x16;
+  if (tiles(64, 64) >= cus) {
+    const int64_t r64 = rounds(tiles(64, 64), cus), r128 = rounds(tiles(128, 64), cus);
+    if (tiles(128, 64) > 0 && 1.85 * (double)r128 < (double)r64) return V_F32_128x64;
+    return V_F32_LW_64x64K2;
+  }
+  if (tiles(64, 32) >= cus) {
+    if (tiles(32, 32) > 0 && f32_32x32_beats_64x32(tiles(32, 32), tiles(64, 32), cus)) return V_F32_LW_32x32K4;
+    return V_F32_LW_64x32K2;
+  }
+  if (tiles(32, 32) > 0 && tiles(32, 32) >= tiles(64, 64) * 2 && tiles(64, 32) < cus) return V_F32_LW_32x32K4;
+  if (tiles(64, 64) > 0) return V_F32_LW_64x64K2;
+  if (tiles(64, 32) > 0) return V_F32_LW_64x32K2;
+  if (tiles(32, 32) > 0) return V_F32_LW_32x32K4;
+  return V_GENERIC;
+}
+
+// tile choice for an eligible descriptor: 0 = 64x64 register-staged, 1 = 128x128 DMA, 2 = 256x256 DMA.
+//  * 256 x 256 (LDS / L2 traffic per flop halves: measured 1.31-1.37 vs 0.88-1.03 PFLOP/s on 4096^3 ..
+//    8192^3) when its tile waves fill the 256 CUs well enough to keep that 1.4x: tiles run one per CU,
+//    so a grid of t tiles takes ceil(t / 256) rounds;
+//  * 128 x 128 as soon as the 64 x 64 family would need a second round of workgroups (more than 256 tiles of
+//    64 x 64 = more than 64 of 128 x 128): measured (n = 1024, K = 1024) the DMA kernel takes 9.2-9.4 us from 64
+//    to 256 tiles while the 64 x 64 family jumps from 9.1 to 12.8 us past one tile per CU;
+//  * 64 x 64 below that, so that more CUs have work.
+static int pick_bf16_tile(const GemmDesc &d) {
+  constexpr int64_t t256_min = 240, t128_min = 65; // crossovers measured in profiles/r01_sweep_shapes.txt
+  const int64_t t256 = (d.m % 256 == 0 && d.n % 256 == 0) ? (d.m / 256) * (d.n / 256) : 0;
+  const int64_t t128 = (d.m % 128 == 0 && d.n % 128 == 0) ? (d.m / 128) * (d.n / 128) : 0;
+  auto fill = [](int64_t t) { return (double)t / (double)(((t + 255) / 256) * 256); }; // CU occupancy over the rounds
+  if (t256 >= t256_min && 1.4 * fill(t256) >= fill(t128)) return 2;
+  if (t128 >= t128_min) return 1;
+  return 0;
+}
+
+static const int BLW_BM[4] = {32, 64, 64, 128}, BLW_BN[4] = {64, 64, 128, 128};
+void blw_tile_dims(int tile, int *bm, int *bn) { *bm = BLW_BM[tile & 3], *bn = BLW_BN[tile & 3]; }
+static bool blw_divides(const GemmDesc &d, int tile) { return d.m % BLW_BM[tile] == 0 && d.n % BLW_BN[tile] == 0; }
+
+// Mid-size bf16 outputs: the loader-wave family (brgemm_bf16_lw.hip), the largest tile that still gives at least 3/4 of the CUs
+// a workgroup (one workgroup per CU: 160 KiB of LDS). Outputs too small for that even with 32x64 tiles stay with the 32x32 K-split
+// family (m = 256, n = 1024, K = 1024: 4.9 us against 5.7 on 128 tiles of 32x64, profiles/r03_sweep_shapes.txt).
+// Returns the tile index (0 .. 3) or -1.
+static int pick_bf16_lw_tile(const GemmDesc &d, int64_t cus) {
+  // Gate (unchanged since round 3): some tile of the family gives at least 3/4 of the CUs a workgroup. Which tile, round 6: the
+  // cheapest by blw_cost. The old rule - the LARGEST tile that still reaches 3/4 of the CUs - put 1024 x 2560 on 320 tiles of 64x128
+  // (two rounds: 15.1 us) instead of 160 tiles of 128x128 (one round: 10.2 us). The batch count arrives with the invoke: priced at 16
+  // chunks (K = 1024; the order of two candidates flips with K only when their round counts differ AND the sums are within a few percent).
+  bool gate = false;
+  int best = -1;
+  double best_t = 0;
+  for (int t = 3; t >= 0; --t) {
+    if (!blw_divides(d, t)) continue;
+    const int64_t tiles = (d.m / BLW_BM[t]) * (d.n / BLW_BN[t]);
+    if (tiles * 4 >= 3 * cus) gate = true;
+    const double cost = blw_cost(t, rounds(tiles, cus), 16.0);
+    if (best < 0 || cost < best_t) best = t, best_t = cost;
+  }
+  return gate ? best : -1;
+}
+// flat-B / VNNI-4 images: pick_bf16_lw_tile's tile, else the smallest the shape divides; a forced tile if the shape divides it
+static int pick_bf16_lw_image_tile(const GemmDesc &d, int64_t cus, int first_variant, int forced_variant) {
+  int t = pick_bf16_lw_tile(d, cus);
+  for (int c = 0; t < 0 && c < 4; ++c)
+    if (blw_divides(d, c)) t = c;
+  if (forced_variant >= first_variant && forced_variant <= first_variant + 3 && blw_divides(d, forced_variant - first_variant)) return forced_variant;
+  return t >= 0 ? first_variant + t : V_GENERIC;
+}
+
+static const char *variant_name(int v) {
+  static const char *const names[32] = {
+      "brgemm_f32_fast<64x64,k1>", "brgemm_f32_fast<64x32,k2>", "brgemm_f32_fast<32x32,k4>", "brgemm_f32_fast<128x64,k1>",
+      "brgemm_f32_fast<64x64,k2>", "brgemm_f32_fast_lw<64x64,k1>", "brgemm_f32_fast_lw<64x64,k2>", "brgemm_f32_fast_lw<64x32,k4>",
+      "brgemm_grouped(generic)", "brgemm_f32_fast_lw<32x32,k4>", "brgemm_f32_fast_lw<128x64,k1>", "brgemm_f32_lw16<32x16,k4>",
+      "brgemm_f32_bf16x6<64x64,k1>", "brgemm_f32_bf16x6<64x32,k2>", "brgemm_f32_bf16x6<32x32,k4>", "brgemm_f32_bf16x6<128x64,k1>",
+      "brgemm_bf16_fast<64x64>", "brgemm_bf16_dma<128x128>", "brgemm_bf16_dma<256x256>", "brgemm_bf16_small<32x32,k4>",
+      "brgemm_bf16_lw<32x64,k2>", "brgemm_bf16_lw<64x64>", "brgemm_bf16_lw<64x128>", "brgemm_bf16_lw<128x128>",
+      "brgemm_bf16_lw_flatb<32x64,k2>", "brgemm_bf16_lw_flatb<64x64>", "brgemm_bf16_lw_flatb<64x128>", "brgemm_bf16_lw_flatb<128x128>",
+      "brgemm_bf16_lw_vnni4<32x64,k2>", "brgemm_bf16_lw_vnni4<64x64>", "brgemm_bf16_lw_vnni4<64x128>", "brgemm_bf16_lw_vnni4<128x128>"};
+  return v >= 0 && v < 32 ? names[v] : names[V_GENERIC];
+}
+
+// split tiles the planner picks by itself for a bf16x6 descriptor (64x64, 64x32 + K2, 32x32 + K4, 128x64): the ones that beat the exact
+// kernel of the same tile. None does yet (profiles/x6_first_ab.txt, kernel averages bf16x6 / exact: first version 1.25 - 4.36; with
+// loader waves doing the split 1.29 - 3.99, e.g. 4096^3 1312.54 against 1015.14 us, 1024x2560x1024 103.87 against 57.49 us): a
+// bf16x6 descriptor stays on the exact plan of mode 0 unless a split tile is forced (xsmm_hip_force_variant 12 .. 15).
+static const bool X6_AUTO[4] = {false, false, false, false};
+// output tiles of the f32 variants 0 .. 10 (8: the generic kernel, no tile)
+static const int F32_BM[11] = {64, 64, 32, 128, 64, 64, 64, 64, 0, 32, 128}, F32_BN[11] = {64, 32, 32, 64, 64, 64, 64, 32, 0, 32, 64};
+
+bool plan_gemm(GemmDesc &d, int forced_variant, const GemmPlanEnv &env) {
+  const int64_t cus = env.cus;
+  int v = V_GENERIC;
+  if (d.vnni_c) forced_variant = V_GENERIC; // VNNI-2 C store: the generic kernel's epilogue only
+  if (d.dtype == DT_F32 && !d.vnni_b) v = pick_f32_variant(d, cus);
+  else if (d.dtype == DT_BF16 && d.vnni_b && d.vnni_factor == 4) {
+    // VNNI-4 B ([k/4][n][4]: benchmarks/config/omp/mlir-bf16.json:68-100 `--vnni=4`): the loader-wave tiles with the VNNI-4 image;
+    // everything else - ragged shapes, k not a multiple of 64 (the compiler-native 32x32x32 tiles) - on the generic kernel's element path
+    if (bf16_vnni4_eligible(d)) v = pick_bf16_lw_image_tile(d, cus, V_BF16_LW4_32x64, forced_variant);
+  } else if (d.dtype == DT_BF16 && bf16_fast_eligible(d)) {
+    v = V_BF16_FAST + pick_bf16_tile(d);
+    // small outputs (e.g. the reference's --batch=256 layers): 32x32 tiles with K split over the waves give
+    // every CU a workgroup. Measured crossover with the 64x64 family (n = 1024, K = 1024): 5.1 vs 8.4 us at 64
+    // tiles of 64x64, 7.5 vs 8.5 at 128, 12.3 vs 8.9 at 256 (profiles/r01_sweep_shapes.txt)
+    if (v == V_BF16_FAST && bf16_small_eligible(d) && (d.m / 64) * (d.n / 64) < (3 * cus) / 4) v = V_BF16_SMALL32;
+    // mid-size outputs (the 64x64 / 32x32 families, or 128x128 tiles for fewer than 3/4 of the CUs): one loader-wave workgroup
+    // per CU. Measured (profiles/r03_sweep_shapes.txt, 1024-wide layer, K = 1024): see DESIGN.md 4.2.
+    const int64_t t128 = (d.m / 128) * (d.n / 128);
+    if (v == V_BF16_FAST || v == V_BF16_SMALL32 || (v == V_BF16_DMA128 && t128 * 4 < 3 * cus)) {
+      const int lw = pick_bf16_lw_tile(d, cus);
+      // (round 6: the 128x128 loader-wave tile also where brgemm_bf16_dma128 used to stay - fewer than 3/4 of the CUs busy: 1024 x 2560 x
+      // 1024 = 160 tiles runs 10.2 us on it against 11.5 on dma128, profiles/r06_bf16_sweep_before.txt)
+      if (lw >= 0) v = V_BF16_LW_32x64 + lw;
+    } else if (v == V_BF16_DMA128 && t128 <= cus && pick_bf16_lw_tile(d, cus) == 3) {
+      // ONE round of 128x128 tiles (the C4 layer 4096 x 1024, C5 2048 x 2048): since the end of round 3 the loader-wave tile is
+      // at least as fast as brgemm_bf16_dma128 there (same box, profiles/r03_write_through_c_stores.txt: C5 18.2 against 18.7 us,
+      // the C4 layer 10.4 against 10.6-11.5) - and it is the tile the 4096-row chain runs on. Several rounds: dma128 (not re-measured).
+      v = V_BF16_LW_128x128;
+    }
+    const int tile = forced_variant - V_BF16_FAST; // a forced bf16 tile is honoured if the shape divides it
+    if (tile >= 0 && tile <= 2 && d.m % (64 << tile) == 0 && d.n % (64 << tile) == 0) v = forced_variant;
+    if (forced_variant == V_BF16_SMALL32 && bf16_small_eligible(d)) v = forced_variant;
+    if (forced_variant >= V_BF16_LW_32x64 && forced_variant <= V_BF16_LW_128x128 && blw_divides(d, forced_variant - V_BF16_LW_32x64)) v = forced_variant;
+  } else if (d.dtype == DT_BF16 && bf16_flat_eligible(d)) {
+    // flat B ([k][n] row-major, what xsmm.unary pack would have turned into VNNI-2): the loader-wave tiles with the interleave
+    // in the B loader (launch_gemm falls back to the generic kernel when an operand is not 16-byte aligned).
+    v = pick_bf16_lw_image_tile(d, cus, V_BF16_LWF_32x64, forced_variant);
+  } else if (d.dtype == DT_BF16 && bf16_small_eligible(d)) {
+    v = V_BF16_SMALL32; // k a multiple of 16 only (e.g. the compiler-native 32x32x32 tile), m or n a multiple of 32 only
+    if (forced_variant == V_BF16_LW_32x64) { // the 32x64 loader-wave tile needs m % 32 only (bf16_fast_eligible asks for 64)
+      GemmDesc e = d;
+      e.m = (d.m + 63) / 64 * 64;
+      if (d.m % 32 == 0 && d.n % 64 == 0 && bf16_fast_eligible(e)) v = forced_variant;
+    }
+  }
+  if (forced_variant >= 0 && d.dtype == DT_F32 && v != V_GENERIC) {
+    // honour the forced tile only if the shape divides it
+    if (forced_variant <= V_F32_LW_128x64 && forced_variant != V_GENERIC && d.m % F32_BM[forced_variant] == 0 && d.n % F32_BN[forced_variant] == 0)
+      v = forced_variant;
+    if (forced_variant == V_F32_LW16_32x16 && d.m % 32 == 0 && d.n % 16 == 0 && d.ldc % 4 == 0) v = forced_variant;
+    if (forced_variant == V_GENERIC) v = V_GENERIC;
+  } else if (forced_variant == V_GENERIC) {
+    v = V_GENERIC;
+  }
+  if (d.f32_prec == 6 && d.dtype == DT_F32 && !d.vnni_b && !d.vnni_c && f32_x6_eligible(d)) {
+    // bf16x6: the split kernel needs 64-k chunks, 16-byte row pieces, the 32-bit lane offsets and ldc a multiple of 4.
+    // It takes the output tile of the exact plan where the split tile of that size measured faster than the exact kernel (X6_AUTO: none
+    // yet); the skinny 32x16 tiles, the generic kernel and forced exact variants stay exact. A forced split tile (xsmm_hip_force_variant
+    // 12 .. 15) is honoured if the shape divides it.
+    const int fx = forced_variant - V_F32_X6_64x64;
+    if (fx >= 0 && fx <= 3) {
+      if (d.m % F32_BM[fx] == 0 && d.n % F32_BN[fx] == 0) v = forced_variant; // (split tile fx has the shape of exact variant fx)
+    } else if (forced_variant < 0) { // (the split tile of the exact plan's size: 64x64, 64x32, 32x32, 128x64)
+      static const int x6_tile[11] = {0, 1, 2, 3, 0, 0, 0, 1, -1, 2, 3};
+      const int t = v <= V_F32_LW_128x64 ? x6_tile[v] : -1;
+      if (t >= 0 && X6_AUTO[t]) v = V_F32_X6_64x64 + t;
+    }
+  }
+  d.variant = v;
+  d.generic_forced = forced_variant == V_GENERIC;
+  d.variant_forced = forced_variant >= 0 && v == forced_variant;
+  strncpy(d.name, variant_name(v), sizeof(d.name) - 1);
+  d.name[sizeof(d.name) - 1] = 0;
+  return true;
+}
+
+// the f32 chain tile (brgemm_f32_lw.hip, launch_f32_chain) a whole-layer f32 descriptor was planned on: 1 / 2, or -1 (another
+// kernel family, a VNNI operand, k not in 64-k chunks ... - whatever pick_f32_variant sent elsewhere)
+int f32_chain_tile(const GemmDesc &d) {
+  if (gemm_on_x6(d)) return -1; // the bf16x6 split kernel: chains that hold such a call run call by call (it has no chain form)
+  if (d.dtype != DT_F32 || d.vnni_b || d.vnni_c || d.k <= 0 || d.k % BK) return -1;
+  // (the 32x32 + K4 tile - the reference's batch-256 layers, 3.4 us of MFMA work per tile - is NOT chained: measured 21.9 us per
+  // three-layer step as one launch against 20.6 as three, profiles/r04_f32_chain.txt: a seam is four dependent memory round trips
+  // - store drain, counter add, poll, A fetch - and 32 producers + 32 pollers share one counter line; the 64-row tiles gain 1-2.5 %)
+  return d.variant == V_F32_LW_64x64K2 ? 1 : d.variant == V_F32_LW_64x32K2 ? 2 : -1;
+}
+bool f32_chain_tile_dims(int tile, int *bm, int *bn) { return (tile == 1 || tile == 2) && (*bm = 64, *bn = tile == 1 ? 64 : 32, true); }
+
+int bf16_lw_b_kind(const GemmDesc &d) {
+  if (d.dtype != DT_BF16 || d.vnni_c) return -1;
+  if (d.vnni_b && d.vnni_factor == 4) return bf16_vnni4_eligible(d) ? 4 : -1;
+  if (d.vnni_b) return bf16_fast_eligible(d) ? 0 : -1;
+  return bf16_flat_eligible(d) ? 2 : -1;
+}
+
+static GemmLaunch launch(GemmLauncher l, int tile = 0, const char *text = "", int split = 1, int b_kind = 0, bool even = false) {
+  return GemmLaunch{l, tile, split, b_kind, even, false, GG_F32, text};
+}
+static GemmLaunch generic(GemmGeneric g, const char *text = "") { return GemmLaunch{GL_GENERIC, 0, 1, 0, false, false, g, text}; }
+
+GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al, const GemmPlanEnv &env) {
+  if (d.m <= 0 || d.n <= 0) return launch(GL_NONE);
+  const int64_t cus = env.cus;
+  const int br = (int)(br_in < 0 ? 0 : br_in);
+  int v = d.variant;
+  if (d.b_trans) return d.dtype != DT_F32 || d.vnni_b ? launch(GL_INVALID) : generic(GG_F32);
+  // bf16x6: the planned split tile whatever the batch count, split setting or pointer alignment (unaligned A / B: element loads)
+  if (gemm_on_x6(d))
+    return GemmLaunch{GL_F32_X6, v - V_F32_X6_64x64, 1, 0, false, al.ab16, GG_F32, ""};
+  if (v != V_GENERIC && !al.ab16) v = V_GENERIC;
+  // the bf16 kernel stores 16-byte row pieces and reads the bias 8 bytes at a time
+  const bool bias_ok8 = !d.bias || al.d8;
+  if (v >= V_BF16_FAST && v != V_BF16_SMALL32 && !(al.c16 && bias_ok8)) v = V_GENERIC;
+  if (v == V_BF16_SMALL32 && !(al.c8 && bias_ok8)) v = V_GENERIC;
+  // Small bf16 outputs with a LONG reduction: the 32x32 K-split kernel (fragments straight from global memory, two groups of loads
+  // in flight per wave) is latency-bound there - 128 x 1024 x 4096: 15.4 us against 9.8 on 64 loader-wave tiles of 32x64 and 8.1 on
+  // 128 tiles of 32x32 + K2 (the same kernel, twice the workgroups pulling panels). Crossovers (profiles/r05_bf16_skinny_small_vs_lw.txt):
+  // against the 32x32 + K2 instance - usable when the output is at most one 32x32 tile per CU - at K = 1024 (256 x 1024 x 1024: 4.78
+  // against 5.05 us, the reference's bs = 256 bf16 MLP as whole-layer calls 14.3 against 15.7; at K = 768 the K-split kernel still
+  // wins by 0.06-0.2 us), against the 32x64 tile between 1024 and 2048. The batch count arrives with the invoke, so this choice is
+  // made here and not at dispatch.
+  if (v == V_BF16_SMALL32 && d.variant == V_BF16_SMALL32 && !d.generic_forced && d.k % 64 == 0 && d.m % 32 == 0 && d.n % 64 == 0 && al.c16 &&
+      bias_ok8 && !d.variant_forced) {
+    const bool t32 = (d.m / 32) * (d.n / 32) <= cus;
+    const int64_t thr = t32 ? 1024 : 1536;
+    GemmDesc e = d;
+    e.m = (d.m + 63) / 64 * 64; // (bf16_fast_eligible asks for m % 64; these tiles need m % 32 only)
+    if ((int64_t)br * d.k >= thr && bf16_fast_eligible(e))
+      return t32 ? launch(GL_BF16_LW, 4, "brgemm_bf16_lw<32x32,k2> (long reduction)") : launch(GL_BF16_LW, 0, "brgemm_bf16_lw<32x64,k2> (long reduction)");
+  }
+  if (v >= V_BF16_LW_32x64 && v <= V_BF16_LW4_128x128 && br < 1) v = V_GENERIC; // empty batch (C = epilogue of nothing): the loader-wave kernels assume a chunk
+  if (v >= V_F32_64x64 && v <= V_F32_64x64K2) return launch(GL_F32_FAST, v);
+  if (v == V_F32_LW_64x64 || v == V_F32_LW_128x64) return launch(GL_F32_LW, v == V_F32_LW_64x64 ? 0 : 4);
+  if (v == V_F32_LW_64x64K2 || v == V_F32_LW_64x32K2 || v == V_F32_LW_32x32K4) {
+    // skinny outputs (fewer tiles than CUs, a long batch-reduce): several workgroups per tile (choose_f32_split)
+    static const char *const split_names[4] = {"", "brgemm_f32_lw<64x64,k2>, split", "brgemm_f32_lw<64x32,k4>, split", "brgemm_f32_lw<32x32,k4>, split"};
+    const int tile = v == V_F32_LW_32x32K4 ? 3 : v - V_F32_LW_64x64;
+    const int bm = tile == 3 ? 32 : 64, bn = tile == 1 ? 64 : 32;
+    const int S = choose_f32_split(tile, (long long)(d.m / bm) * (d.n / bn), (long long)br * (d.k / BK), env);
+    return launch(GL_F32_LW, tile, S > 1 ? split_names[tile] : "", S);
+  }
+  // (the half-width tiles store 16-byte pieces of C and of the bias row: else the generic kernel below)
+  if (v == V_F32_LW16_32x16 && al.c16 && (!d.bias || al.d16)) {
+    // LONG reductions (K >= 3072): every XCD streams all of A besides its share of B on the half-width tiles and their chunk time
+    // rises by 40 % (128 x 1024 x 4096: 14.6 us); the 32x32 tiles with the k range shared between XCD-aligned workgroups fetch every
+    // byte once (12.8 us). The batch count arrives with the invoke, so this is decided here. (profiles/r05_lw16_vs_split.txt)
+    const long long chunks = (long long)br * (d.k / BK);
+    const int S = chunks >= 48 && !d.variant_forced && d.n % 32 == 0 ? choose_f32_split(3, (long long)(d.m / 32) * (d.n / 32), chunks, env) : 1;
+    return launch(GL_F32_LW16, 0, S > 1 ? "brgemm_f32_lw<32x32,k4>, split (long reduction)" : "", S);
+  }
+  if (v >= V_BF16_FAST && v <= V_BF16_DMA256) return launch(GL_BF16_FAST, v - V_BF16_FAST);
+  if (v == V_BF16_SMALL32) return launch(GL_BF16_SMALL32);
+  if (v >= V_BF16_LW_32x64 && v <= V_BF16_LW_128x128) return launch(GL_BF16_LW, v - V_BF16_LW_32x64);
+  if (v >= V_BF16_LWF_32x64 && v <= V_BF16_LWF_128x128) return launch(GL_BF16_LW, v - V_BF16_LWF_32x64, "", 1, 2);
+  if (v >= V_BF16_LW4_32x64 && v <= V_BF16_LW4_128x128) {
+    // (round 6) skinny outputs with a long reduction: the 32x32 + K2 instance, as for VNNI-2 operands above - at most one 32x32 tile
+    // per CU and K >= 1024: twice the workgroups of the 32x64 tile pulling panels (128 x 1024 x 4096: 9.3 -> 7.6 us)
+    if (v == V_BF16_LW4_32x64 && !d.variant_forced && !d.generic_forced && d.m % 32 == 0 && d.n % 32 == 0 && (d.m / 32) * (d.n / 32) <= cus &&
+        (int64_t)br * d.k >= 1024)
+      return launch(GL_BF16_LW, 4, "brgemm_bf16_lw_vnni4<32x32,k2> (long reduction)", 1, 4);
+    return launch(GL_BF16_LW, v - V_BF16_LW4_32x64, "", 1, 4);
+  }
+  // everything else: the kernel of a group of this one invoke. Spelled out rather than plan_gemm_group(n_items = 1): a group of one
+  // tries the half-width lw16 tiles first, a single invoke keeps the pair / ragged 32x32 tile it has always run on.
+  const GenericOk g = generic_ok(d, al.ab16);
+  const bool f32_lw = g.vec && !d.generic_forced && d.m % 32 == 0 && f32_lw_operands_ok(d);
+  // a SINGLE invoke of a 32-k f32 tile with an even batch count: the kernel its group would run on in the tile queue (the
+  // loader-wave pair mode, tile chosen as plan_gemm_group does for one item) - queue on and queue off then add in the same order
+  if (f32_lw && f32_pairs_ok(d) && br >= 2 && !(br & 1) && d.n % 32 == 0) {
+    const int64_t t64 = (d.m % 64 == 0 && d.n % 64 == 0) ? (d.m / 64) * (d.n / 64) : 0;
+    const int64_t t6432 = (d.m % 64 == 0) ? (d.m / 64) * (d.n / 32) : 0;
+    if (t64 >= cus) return launch(GL_F32_LW_GROUPED, t64 >= 2 * cus ? 0 : 1);
+    if (t6432 >= cus) return launch(GL_F32_LW_GROUPED, 2);
+    return launch(GL_F32_LW_GROUPED, 3, "", choose_f32_split(3, (d.m / 32) * (d.n / 32), br / 2, env));
+  }
+  // a SINGLE invoke of a tile whose n ends inside a 32-column block (--tiles=64,48,64): the loader-wave kernel its group runs on
+  if (f32_lw && d.k % BK == 0 && br >= 1 && d.n > 32 && d.n % 32 != 0)
+    return launch(GL_F32_LW_GROUPED, 3, "", choose_f32_split(3, (d.m / 32) * ((d.n + 31) / 32), (long long)br * (d.k / BK), env));
+  return generic(generic_kernel(d, g));
+}
+
+GemmLaunch plan_gemm_group(const GemmDesc &d, int n_items, bool vec_ok, bool out_ok, bool pair_ok, int64_t br_hint, const GemmPlanEnv &env) {
+  if (d.m <= 0 || d.n <= 0 || n_items <= 0) return launch(GL_NONE);
+  if (gemm_on_x6(d)) return launch(GL_INVALID); // the split kernel is never queued or grouped (try_enqueue, gemm_invoke_unqueued)
+  const int64_t cus = env.cus;
+  // n_dec: the number of items every size-dependent DECISION below is taken for. Normally the group's - the group is what fills the
+  // chip. In strict mode 1: a single invoke, the first pass of a queued group and its replays then all run on the same kernel.
+  const int64_t n_dec = env.strict ? 1 : n_items;
+  if (d.b_trans) { // B read transposed (a folded xsmm.unary transpose): the generic kernel's element-wise loads
+    if (d.dtype != DT_F32 || d.vnni_b) return launch(GL_INVALID);
+    return generic(GG_F32, "brgemm_grouped<f32>, B read transposed");
+  }
+  const GenericOk g = generic_ok(d, vec_ok);
+  // f32 tiles with k a multiple of 64 (mlir-gen --tiles=64,64,64, the most common setting of the reference's
+  // benchmark configs): the fast tile families in grouped mode, the largest tile that still yields about one
+  // workgroup per CU over the whole work list (the same rule as pick_f32_variant)
+  // ... and 32-k tiles (--tiles=32,32,32, the reference's MLP benchmark) when every batch count is even: the loader waves build a
+  // 64-k chunk from the blocks of two batch elements (brgemm_f32_lw.hip, pair mode)
+  const bool k_pairs = pair_ok && f32_pairs_ok(d);
+  const bool f32_lw = g.vec && f32_lw_operands_ok(d);
+  // (n that is not a multiple of 32 - the reference's --tiles=64,48,64 / 32,48,32 configs: the last 32-column tile of an item is
+  // ragged, the loader-wave kernels clamp its loads and mask its stores; needs the 16-byte output pieces of out_ok and ldc % 4)
+  // skinny groups - at most one 32x16 tile per CU over the whole work list: the half-width tiles (brgemm_f32_lw16.hip), every CU a
+  // workgroup without a hand-off. 64-k tiles, or 32-k tiles whose n is not a multiple of 32 with even batch counts (--tiles=32,48,32);
+  // plain 32x32x32 tiles stay on the pair kernel whatever the group size (a single invoke and its group add in the same order:
+  // what tools/queue_fuzz.py checks bit for bit)
+  {
+    const int64_t t16 = (d.m % 32 == 0 && d.n % 16 == 0) ? n_dec * (d.m / 32) * (d.n / 16) : 0;
+    const bool k_ok = (d.k % BK == 0 && d.k > 0) || (k_pairs && d.n % 32 != 0);
+    if (f32_lw && out_ok && !d.generic_forced && t16 > 0 && t16 <= cus && k_ok && d.ldc % 4 == 0 && n_items <= 65535 &&
+        !((d.k == 32 ? br_hint / 2 : br_hint * (d.k / BK)) >= 48 && d.n % 32 == 0 && d.k % BK == 0)) // (long reductions: the split 32x32 tiles below, as plan_gemm_call)
+      return launch(GL_F32_LW16, 0, d.k == 32 ? "brgemm_f32_lw16<32x16,k4> grouped, 32-k pairs" : "brgemm_f32_lw16<32x16,k4> grouped");
+  }
+  const bool n_ragged = d.n % 32 != 0;
+  const bool fam_ok = n_ragged ? (!d.generic_forced && d.n > 32 && (d.k % BK == 0 || k_pairs)) // (plan_gemm knows no tile for such an n: variant = generic)
+                               : ((d.k % BK == 0 && d.variant != V_GENERIC) || (k_pairs && !d.generic_forced));
+  if (f32_lw && d.m % 32 == 0 && fam_ok && n_items <= 65535 * 2) { // (grid.x carries the item index: x split)
+    const bool pairs = d.k == 32;
+    const int64_t t64 = (d.m % 64 == 0 && d.n % 64 == 0) ? n_dec * (d.m / 64) * (d.n / 64) : 0;
+    const int64_t t6432 = (d.m % 64 == 0) ? n_dec * (d.m / 64) * ((d.n + 31) / 32) : 0;
+    const int64_t t32 = n_dec * (d.m / 32) * ((d.n + 31) / 32);
+    // the loader-wave kernels (brgemm_f32_lw.hip) in grouped mode
+    if (t64 >= 2 * cus) return launch(GL_F32_LW_GROUPED, 0, pairs ? "brgemm_f32_lw<64x64> grouped, 32-k pairs" : "brgemm_f32_lw<64x64> grouped");
+    if (t64 >= cus) return launch(GL_F32_LW_GROUPED, 1, pairs ? "brgemm_f32_lw<64x64,k2> grouped, 32-k pairs" : "brgemm_f32_lw<64x64,k2> grouped");
+    // (rounds of workgroups x per-chunk time, as pick_f32_variant: 1.5 rounds of 64x32 tiles lose to 3 half-rounds of 32x32 tiles)
+    if (t6432 >= cus && !f32_32x32_beats_64x32(t32, t6432, cus))
+      return launch(GL_F32_LW_GROUPED, 2, pairs ? "brgemm_f32_lw<64x32,k4> grouped, 32-k pairs" : "brgemm_f32_lw<64x32,k4> grouped");
+    // skinny groups (fewer 64x32 tiles than CUs): 32x32 tiles, and the batch-reduce range of a tile over several workgroups
+    // when the model says so (choose_f32_split: from the descriptor, the first item's batch count and the group's size)
+    const int64_t chunks = pairs ? br_hint / 2 : br_hint * (d.k / BK);
+    const int S = choose_f32_split(3, t32, chunks, env);
+    if (S > 1) return launch(GL_F32_LW_GROUPED, 3, pairs ? "brgemm_f32_lw<32x32,k4> grouped, 32-k pairs, split" : "brgemm_f32_lw<32x32,k4> grouped, split", S);
+    return launch(GL_F32_LW_GROUPED, 3, pairs ? "brgemm_f32_lw<32x32,k4> grouped, 32-k pairs" : "brgemm_f32_lw<32x32,k4> grouped");
+  }
+  // bf16 tile invokes with k a multiple of 64 and n a multiple of 64 (the reference's --tiles=64,64,64 / 32,64,64 bf16 rows): the
+  // LOADER-WAVE tiles in grouped mode (round 6, brgemm_bf16_lw.hip launch_bf16_lw_grouped) - what the same layer runs on as one
+  // whole-layer call. Tile by the blw_cost model over the group's workgroups: 32x64 + K2 (two workgroups per 64-row item) or 64x64.
+  // Against the two older grouped kernels (profiles/r06_bf16_sweep_before.txt, forced-variant rows): the loader-wave tiles win whenever
+  // the group fills 3/4 of the chip with 64x64 tiles (1024 x 1024 x 512: 5.1 us against 6.7) or the reduction is long (16 chunks or
+  // more: 128 x 4096 x 1024 5.3 against 9.4) or half the chip gets a 32x64 tile of at least 8 chunks (128 x 3072 x 768: 4.9 against
+  // 6.3; 1024 x 512 x 256, 4 chunks: 5.6 against 5.1); short reductions of small groups stay on the K-split kernel (128 x 768 x 768:
+  // 4.3 against 4.7). (A forced split count: the K-split kernel below.)
+  {
+    const bool v2 = d.vnni_factor == 2, v4 = d.vnni_factor == 4;
+    const bool lw_ok = (v2 || v4) && bf16_lw_items_ok(d, v4) && vec_ok && out_ok && br_hint >= 1 && env.forced_split < 0;
+    const int64_t chunks = br_hint * (d.k / BK);
+    const int b_kind = v4 ? 4 : 0;
+    const bool even = ((d.k / BK) % 2 == 0) || pair_ok;
+    // RAGGED n (round 6): items whose n is 16 more than a multiple of 32 - the reference's --tiles=64,48,64 rows (fc / matmul 128x768x2304)
+    // - on the 32x32 + K2 instance: ceil(n / 32) column tiles per item, the last moved left to end at column n (it recomputes the 16
+    // columns it shares with its neighbour and stores its own 16: brgemm_bf16_lw.hip skip_cols). Skinny groups with a long reduction
+    // only, like the instance's other uses; everything else with such an n stays on the K-split kernel below.
+    if (lw_ok && d.n % 32 == 16 && d.n >= 48 && n_dec * (d.m / 32) * ((d.n + 31) / 32) <= cus && chunks >= 16) {
+      return launch(GL_BF16_LW_GROUPED, 4, v4 ? "brgemm_bf16_lw_vnni4<32x32,k2> grouped, ragged n" : "brgemm_bf16_lw<32x32,k2> grouped, ragged n", 1, b_kind, even);
+    }
+    const int64_t t64 = d.m % 64 == 0 ? n_dec * (d.m / 64) * (d.n / 64) : 0;
+    const int64_t wg0 = n_dec * (d.m / 32) * (d.n / 64);
+    if (lw_ok && d.n % 64 == 0 && (t64 * 4 >= 3 * cus || chunks >= 16 || (wg0 * 2 >= cus && chunks >= 8))) {
+      const double c0 = blw_cost(0, rounds(wg0, cus), (double)chunks);
+      const double c1 = t64 > 0 ? blw_cost(1, rounds(t64, cus), (double)chunks) : 1e30;
+      int tile = c1 <= c0 ? 1 : 0;
+      // 32x32 + K2 (VNNI-2): twice the workgroups of the 32x64 tile pulling panels - for skinny groups with a long reduction, as
+      // plan_gemm_call does for the whole-layer call (one round of workgroups at most, 16 chunks or more)
+      if (n_dec * (d.m / 32) * (d.n / 32) <= cus && chunks >= 16 && blw_cost(4, 1, (double)chunks) < (c1 < c0 ? c1 : c0)) tile = 4;
+      static const char *const names[2][3] = {
+          {"brgemm_bf16_lw<32x64,k2> grouped", "brgemm_bf16_lw<64x64> grouped", "brgemm_bf16_lw<32x32,k2> grouped"},
+          {"brgemm_bf16_lw_vnni4<32x64,k2> grouped", "brgemm_bf16_lw_vnni4<64x64> grouped", "brgemm_bf16_lw_vnni4<32x32,k2> grouped"}};
+      return launch(GL_BF16_LW_GROUPED, tile, names[v4 ? 1 : 0][tile == 4 ? 2 : tile], 1, b_kind, even);
+    }
+  }
+  // bf16 tiles of 64x64 with k a multiple of 64: the 64x64 bf16 family in grouped mode (it stores 16-byte
+  // row pieces and reads the bias 8 bytes at a time: checked per item by the queue through out_ok)
+  // (whatever a SINGLE invoke of the handle would run on - a lone 64x64 tile is planned on the 32x32 K-split kernel -, the GROUP is
+  // what fills the chip: round 5, the reference's fc / matmul shapes as 64,64,64 tile invokes: 1024 x 2560 x 1024 30.4 us on 32x32
+  // tiles against 15 us whole-layer)
+  const bool fills64 = n_dec * (d.m / 64) * (d.n / 64) >= (3 * cus) / 4;
+  if (g.vec16 && out_ok && d.variant >= V_BF16_FAST && (d.variant != V_BF16_SMALL32 || !d.variant_forced) && !d.generic_forced && bf16_fast_eligible(d) && fills64)
+    return launch(GL_BF16_GROUPED64, 0, "brgemm_bf16_fast<64x64> grouped");
+  // ... and the same family on a VNNI-4 B operand (--vnni=4 tile invokes: benchmarks/config/*/*_dp4_*; the generic kernel's MFMA path
+  // took 30 us for 1024 x 2560 x 1024 against 19.5 on VNNI-2)
+  if (g.vec16_4 && out_ok && !d.generic_forced && !d.vnni_c && d.k % BK == 0 && d.m % 64 == 0 && d.n % 64 == 0 && !((d.ldc | d.stride_b) & 7) && d.ldc < (1 << 22) &&
+      d.lda < (1 << 22) && d.ldb < (1 << 20) && fills64)
+    return launch(GL_BF16_GROUPED64, 0, "brgemm_bf16_fast_vnni4<64x64> grouped");
+  // (VNNI-4 tile invokes - the compiler-native 32x32x32 tiles of a --vnni=4 pipeline, small groups of 64x64x64 tiles - on the same
+  // kernel: its B fragment is then two 8-byte loads; a single invoke of such a handle stays on the generic kernel's MFMA path.
+  // And tiles whose n is a multiple of 4 but not of 32 (--tiles=64,48,64): a masked last column tile instead of the generic kernel.)
+  const bool small_base = bf16_small_operands_ok(d) && !d.vnni_c && !d.generic_forced && d.n >= 32 && d.n % 4 == 0;
+  const bool small4 = small_base && d.vnni_factor == 4 && !(d.stride_b & 3);
+  const bool small_ragged = small_base && d.vnni_factor == 2 && d.n % 32 != 0 && !(d.stride_b & 1);
+  if (vec_ok && out_ok && ((d.variant != V_GENERIC && bf16_small_eligible(d)) || small_ragged || small4)) {
+    // skinny groups with a long reduction: the K steps of a tile over several workgroups (choose_bf16_small_split)
+    const int S = choose_bf16_small_split((long long)n_dec * (d.m / 32) * ((d.n + 31) / 32), (long long)br_hint * (d.k / 16), env);
+    const char *name = S > 1 ? (small4 ? "brgemm_bf16_small32_vnni4 grouped, split" : "brgemm_bf16_small32 grouped, split")
+                             : (small4 ? "brgemm_bf16_small32_vnni4 grouped" : "brgemm_bf16_small32 grouped");
+    return launch(GL_BF16_SMALL32, 0, name, S);
+  }
+  static const char *const names[] = {"brgemm_grouped<f32>", "brgemm_grouped<f32>", "brgemm_grouped<bf16,vnni2>", "brgemm_grouped<bf16,vnni2>",
+                                      "brgemm_grouped<bf16,vnni4>", "brgemm_grouped<bf16,flat>"};
+  return generic(generic_kernel(d, g), names[generic_kernel(d, g)]);
+}
+
+bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br, const GemmPlanEnv &env) {
+  if (env.strict || !quads_shape_ok(d) || br < 1 || n_items < 4 || (n_items & 3) || env.forced_split >= 0) return false;
+  const double chunks = (double)(br * (d.k / BK));
+  const int64_t cus = env.cus;
+  // the 64x64 and 32x64 + K2 tiles - what the grouped path would pick from - against 128x128 blocks of four items
+  const double c64 = blw_cost(1, rounds(n_items, cus), chunks), c32 = blw_cost(0, rounds(2 * (int64_t)n_items, cus), chunks);
+  const double cq = blw_cost(3, rounds(n_items / 4, cus), chunks);
+  return cq * 1.05 < (c64 < c32 ? c64 : c32);
+}
+
+GemmLaunch plan_gemm_quads(const GemmDesc &d, int n_quads, int64_t br) {
+  if (!quads_shape_ok(d) || br < 1 || n_quads <= 0) return launch(GL_INVALID);
+  const bool v4 = d.vnni_factor == 4;
+  return launch(GL_BF16_LW_QUADS, 0, v4 ? "brgemm_bf16_lw_vnni4<128x128> quads" : "brgemm_bf16_lw<128x128> quads", 1, v4 ? 4 : 0);
+}
+
+} // namespace tpp

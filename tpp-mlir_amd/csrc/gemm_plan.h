@@ -1,0 +1,106 @@
+// gemm_plan.h - which GEMM kernel runs a call: the variant a descriptor is planned on at dispatch (plan_gemm), the launch an invoke or a
+// tile-queue group gets (plan_gemm_call, plan_gemm_group), the descriptor facts the chain code asks about. Host-only, every input an
+// argument: the table of choices is checked on a CPU (tests/golden/gemm_plan.txt). brgemm_f32.hip carries a GemmLaunch out.
+#pragma once
+#include "xsmm_desc.h"
+
+namespace tpp {
+
+enum GemmVariant : int {
+  V_F32_64x64 = 0,   // brgemm_f32.hip register-staged tiles: 4 waves 2x2x1
+  V_F32_64x32K2 = 1, // 4 waves 2x1x2
+  V_F32_32x32K4 = 2, // 4 waves 1x1x4
+  V_F32_128x64 = 3,  // 8 waves 4x2x1
+  V_F32_64x64K2 = 4, // 8 waves 2x2x2 (two waves per SIMD share every K chunk)
+  V_F32_LW_64x64 = 5,     // brgemm_f32_lw.hip: 4 MFMA waves 2x2x1 + 2 loader waves
+  V_F32_LW_64x64K2 = 6,   // 8 MFMA waves 2x2x2 + 2 loader waves
+  V_F32_LW_64x32K2 = 7,   // 8 MFMA waves 2x1x4 + 2 loader waves (K split over four groups since round 3; the name of the constant stayed)
+  V_GENERIC = 8,     // chosen per invoke when the fast preconditions fail
+  V_F32_LW_32x32K4 = 9,   // 4 MFMA waves 1x1x4 + 2 loader waves
+  V_F32_LW_128x64 = 10,   // 8 MFMA waves 4x2x1 + 2 x 2 loader waves, 3-slot ring (large outputs)
+  V_F32_LW16_32x16 = 11,  // brgemm_f32_lw16.hip: 32x16 tiles on v_mfma_f32_16x16x4_f32, 4 MFMA waves (K split) + 3 loader waves: outputs of at most one 32x16 tile per CU
+  V_F32_X6_64x64 = 12,    // brgemm_f32_x6.hip: the bf16x6 split on v_mfma_f32_32x32x16_bf16 (f32 descriptors dispatched under xsmm_hip_set_f32_precision(6)
+  V_F32_X6_64x32K2 = 13,  //   with this variant forced: plan_gemm); 4 waves, K split over the rest of them; 128x64 with 8 waves
+  V_F32_X6_32x32K4 = 14,
+  V_F32_X6_128x64 = 15,
+  V_BF16_FAST = 16,  // brgemm_bf16.hip: 64x64 register-staged
+  V_BF16_DMA128 = 17, // brgemm_bf16.hip: 128x128, LDS-DMA + loader waves
+  V_BF16_DMA256 = 18, // brgemm_bf16_dma256.hip: 256x256, LDS-DMA
+  V_BF16_SMALL32 = 19, // brgemm_bf16_small.hip: 32x32 tiles, 4 waves split K, fragments straight from global memory
+  V_BF16_LW_32x64 = 20,   // brgemm_bf16_lw.hip: loader-wave tiles for mid-size outputs (one workgroup per CU), 32x64 + K2
+  V_BF16_LW_64x64 = 21,
+  V_BF16_LW_64x128 = 22,
+  V_BF16_LW_128x128 = 23,
+  V_BF16_LWF_32x64 = 24,  // the same tiles for a FLAT bf16 B operand (no VNNI flag): the pair-row interleave happens in the B loader
+  V_BF16_LWF_64x64 = 25,
+  V_BF16_LWF_64x128 = 26,
+  V_BF16_LWF_128x128 = 27,
+  V_BF16_LW4_32x64 = 28,  // the same tiles for a VNNI-4 B operand [k/4][n][4] (xsmm_hip_set_vnni_factor(4)): a fragment is two 8-byte reads
+  V_BF16_LW4_64x64 = 29,
+  V_BF16_LW4_64x128 = 30,
+  V_BF16_LW4_128x128 = 31,
+};
+
+// what the decisions read besides the descriptor: the device's compute units, xsmm_hip_set_strict and xsmm_hip_force_split (-1 = the
+// split model); brgemm_f32.hip gemm_plan_env fills it per call
+struct GemmPlanEnv { int cus; bool strict; int forced_split; };
+
+// pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
+struct GemmAlign { bool ab16, c16, c8, d8, d16; };
+
+// which launcher runs a call (brgemm_f32.hip run_gemm_launch) and with what
+enum GemmLauncher : int {
+  GL_NONE,            // nothing to compute (empty output or work list): hipSuccess
+  GL_INVALID,         // no kernel takes this call: hipErrorInvalidValue
+  GL_F32_FAST,        // brgemm_f32_fast (brgemm_f32.hip): tile = V_F32_64x64 .. V_F32_64x64K2
+  GL_F32_LW,          // launch_f32_lw(tile); split > 1: launch_f32_lw_split(tile, split) first
+  GL_F32_LW16,        // launch_f32_lw16(tile); split > 1: launch_f32_lw_split(3, split) first
+  GL_F32_LW_GROUPED,  // launch_f32_lw_grouped(tile, split)
+  GL_F32_X6,          // launch_f32_x6(tile, vec)
+  GL_BF16_FAST,       // launch_gemm_bf16_fast(tile)
+  GL_BF16_SMALL32,    // launch_bf16_small32(split)
+  GL_BF16_GROUPED64,  // launch_bf16_grouped64
+  GL_BF16_LW,         // launch_bf16_lw / _flatb / _vnni4 by b_kind (0 / 2 / 4), tile
+  GL_BF16_LW_GROUPED, // launch_bf16_lw_grouped(tile, b_kind, even)
+  GL_BF16_LW_QUADS,   // launch_bf16_lw_quads(b_kind)
+  GL_GENERIC,         // brgemm_grouped<T, VNNI, VEC, VF>: generic
+};
+// the instances of the generic kernel brgemm_grouped<T, VNNI, VEC, VF>: <float, false, false / true>, <unsigned short, true, false / true>,
+// <unsigned short, true, true, 4>, <unsigned short, false, false>
+enum GemmGeneric : int { GG_F32, GG_F32_VEC, GG_BF16_VNNI2, GG_BF16_VNNI2_VEC, GG_BF16_VNNI4_VEC, GG_BF16_FLAT };
+struct GemmLaunch {
+  GemmLauncher launcher;
+  int tile;        // the launcher's tile index
+  int split;       // workgroups per output tile (1 = none)
+  int b_kind;      // B image of the bf16 loader-wave tiles: 0 VNNI-2, 2 flat, 4 VNNI-4
+  bool even;       // GL_BF16_LW_GROUPED: every item has an even chunk count
+  bool vec;        // GL_F32_X6: A and B 16-byte aligned
+  GemmGeneric generic;
+  const char *text; // what xsmm_hip_last_refined_kernel (a call) / xsmm_hip_last_grouped_kernel (a group) reports, a static string
+};
+
+// fills d.variant / d.name / d.generic_forced / d.variant_forced; returns false if no kernel can run the descriptor
+bool plan_gemm(GemmDesc &d, int forced_variant, const GemmPlanEnv &env);
+// one invoke of a planned descriptor with batch count br (launch_gemm)
+GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br, const GemmAlign &al, const GemmPlanEnv &env);
+// n_items invokes of one descriptor in one launch (launch_gemm_grouped; vec_ok / out_ok / pair_ok / br_hint as there)
+GemmLaunch plan_gemm_group(const GemmDesc &d, int n_items, bool vec_ok, bool out_ok, bool pair_ok, int64_t br_hint, const GemmPlanEnv &env);
+// n_quads 2 x 2 blocks of 64x64 items on the 128x128 loader-wave tile (launch_gemm_quads)
+GemmLaunch plan_gemm_quads(const GemmDesc &d, int n_quads, int64_t br);
+// would the group run faster as 2 x 2 blocks (xsmm_desc.h gemm_quads_pay)
+bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br, const GemmPlanEnv &env);
+
+// planned on the bf16x6 split kernel (brgemm_f32_x6.hip: variants 12 .. 15). Such handles are never queued, grouped, chained or given a
+// folded transpose; a bf16x6 descriptor planned on an exact kernel (a shape the split kernel does not take) goes every way a mode-0 one goes
+inline bool gemm_on_x6(const GemmDesc &d) { return d.variant >= V_F32_X6_64x64 && d.variant <= V_F32_X6_128x64; }
+// which B image of the loader-wave bf16 tiles (brgemm_bf16_lw.hip) a descriptor's B operand needs - 0: VNNI-2, 2: flat [k][ldb],
+// 4: VNNI-4 - or -1 if the descriptor cannot run on those tiles (shape / alignment / lane-offset limits of the LDS-DMA panels)
+int bf16_lw_b_kind(const GemmDesc &d);
+// 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none
+int f32_chain_tile(const GemmDesc &d);
+// tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip)
+void blw_tile_dims(int tile, int *bm, int *bn);
+// f32 chain tiles as in launch_f32_lw: 1 = 64x64 + K2, 2 = 64x32 + K4 (K-split tiles: 16-byte stores; 32x32 + K4 measured slower than three launches)
+bool f32_chain_tile_dims(int tile, int *bm, int *bn);
+
+} // namespace tpp

@@ -182,7 +182,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (g.dtype != DT_BF16 || g.vnni_c || !g.beta0 || bf16_lw_b_kind(g) < 0 || bf16_lw_b_kind(g) != bf16_lw_b_kind(*d[0]))
       NOCHAIN("a call is not bf16 / beta 0 / aligned for the LDS-DMA tiles, or the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)");
     if (g.m != m || g.n != nn || br[i] < 1) NOCHAIN("the calls differ in m or n, or a batch is empty");
-    if (g.variant == GEMM_VARIANT_GENERIC) NOCHAIN("a call was dispatched to the generic kernel"); // (a forced generic kernel stays generic)
+    if (g.variant == V_GENERIC) NOCHAIN("a call was dispatched to the generic kernel"); // (a forced generic kernel stays generic)
     if (((uintptr_t)pa[i] | (uintptr_t)pb[i] | (uintptr_t)pc[i]) & 15) NOCHAIN("an operand is not 16-byte aligned");
     if (g.bias && (!pd[i] || ((uintptr_t)pd[i] & 7))) NOCHAIN("a bias operand is not 8-byte aligned");
     if (i > 0 && (pa[i] != pc[i - 1] || g.lda != d[i - 1]->ldc)) NOCHAIN("not a chain: a call does not read its predecessor's output");
@@ -206,7 +206,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   if (f32 && !fits(f32_tile)) NOCHAIN("more tiles than compute units");
   const int b_kind = f32 ? 0 : bf16_lw_b_kind(*d[0]);
   // (variants 20 .. 23 VNNI-2, 24 .. 27 flat B, 28 .. 31 VNNI-4: the same four tiles)
-  const int planned = d[0]->variant - (b_kind == 2 ? GEMM_VARIANT_BF16_LW0 + 4 : b_kind == 4 ? GEMM_VARIANT_BF16_LW4_0 : GEMM_VARIANT_BF16_LW0);
+  const int planned = d[0]->variant - (b_kind == 2 ? V_BF16_LWF_32x64 : b_kind == 4 ? V_BF16_LW4_32x64 : V_BF16_LW_32x64);
   bool same = !f32 && planned >= 0 && planned < 4;
   for (int i = 1; i < n && same; ++i) same = d[i]->variant == d[0]->variant;
   if (f32) tile = f32_tile;

@@ -69,7 +69,7 @@ inline void detect_grid(Segment &S) {
              (long)d->k, (long)M, (long)N, (long)d->k, (long)d->lda, (long)d->ldb, (long)d->ldc, g->name);
     return (void *)g;
   });
-  if (!ok || e->variant == GEMM_VARIANT_GENERIC) return; // (no fast tile for the merged shape: the grouped launch stays)
+  if (!ok || e->variant == V_GENERIC) return; // (no fast tile for the merged shape: the grouped launch stays)
   S.grid_desc = e;
   S.grid_w = WorkItem{(const void *)ua[0], (const void *)ub[0], (void *)c0, d->bias ? (const void *)d0 : nullptr, br};
   S.grid_state = 1;
@@ -410,7 +410,7 @@ const GemmDesc *dt_sibling(const GemmDesc *d, int64_t ld_src) {
     GemmDesc *e = new GemmDesc(*d);
     e->b_trans = 1;
     e->ldb = ld_src;
-    e->variant = GEMM_VARIANT_GENERIC;
+    e->variant = V_GENERIC;
     e->generic_forced = 1;
     snprintf(e->name, sizeof(e->name), "brgemm_grouped(generic), B read transposed");
     snprintf(e->trace, sizeof(e->trace), "gemm[%ld,%ld,%ld,%ld,(%ld)^T,%ld] dt%ld flags%ld %s (transpose folded)", (long)d->m, (long)d->n, (long)d->k,

@@ -13,6 +13,7 @@
 #include "../../include/tpp_xsmm_abi.h"
 #include "xsmm_desc.h"
 #include "chain_args.h"
+#include "gemm_plan.h"
 #include "host_cache.h"
 #include "rt_relayout.h" // relayout grids: affine runs of a recorded pack / unpack group (plain C++, outside the unit namespace)
 

@@ -26,7 +26,7 @@ struct GemmDesc {
                         // factor is not on the wire - the reference asks libxsmm_cpuid_dot_pack_factor, VNNIUtils.cpp:25-45)
   int f32_prec;         // f32 arithmetic: 0 = exact f32 MFMA, 6 = bf16x6 split (xsmm_hip_set_f32_precision at dispatch time; part of the
                         // descriptor key; 0 for bf16 descriptors). plan_gemm runs brgemm_f32_x6.hip where a split tile is forced and fits, else the exact kernel
-  int variant;          // kernel variant chosen at dispatch (see gemm_variants.h), -1 = by invoke
+  int variant;          // kernel variant chosen at dispatch (gemm_plan.h GemmVariant), -1 = by invoke
   int generic_forced;   // variant = generic because it was asked for (xsmm_hip_force_variant / a VNNI C store), not because no fast tile fits
   int variant_forced;   // variant is the one xsmm_hip_force_variant asked for: invoke-time refinements (batch-count dependent) leave it alone
   int b_trans;          // runtime-made sibling of a dispatched descriptor (never on the wire): B is read TRANSPOSED, B[k][j] = ptr[j * ldb + k] -
@@ -131,29 +131,15 @@ int force_gemm_split(int workgroups_per_tile); // xsmm_hip_force_split (brgemm_f
 // launch_gemm_grouped then takes every decision that depends on the size of the work list as if the list held ONE item.
 // QUADS: would a group of n_items invokes of `d` (batch count br each, all operands 16-byte aligned) run faster as n_items / 4
 // 2 x 2 blocks on the 128x128 loader-wave tile than as items on the grouped 64x64 / 32x64 tiles? (the tile model of pick_bf16_lw_tile;
-// bf16 VNNI-2 / VNNI-4, m = n = 64, k a multiple of 64; never in strict mode)
+// bf16 VNNI-2 / VNNI-4, m = n = 64, k a multiple of 64; never in strict mode; gemm_plan.h)
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br);
 hipError_t launch_gemm_quads(const GemmDesc &d, const QuadItem *quads, int n_quads, int64_t br, hipStream_t stream);
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
-int f32_chain_tile(const GemmDesc &d); // 1 / 2 / 3 = the f32 chain tile the descriptor was planned on, -1 = none (brgemm_f32.hip)
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)
 const char *last_refined_kernel(); // most recent launch_gemm: the kernel an invoke-time refinement chose, "" = the descriptor's own
-// fills d.variant / d.name; returns false if no kernel can run the descriptor
+// fills d.variant / d.name for this device (gemm_plan.h plan_gemm); returns false if no kernel can run the descriptor
 bool plan_gemm(GemmDesc &d, int forced_variant);
-constexpr int GEMM_VARIANT_BF16_LW0 = 20; // = V_BF16_LW_32x64: first of the four loader-wave bf16 tiles (brgemm_bf16_lw.hip)
-constexpr int GEMM_VARIANT_BF16_LW4_0 = 28; // = V_BF16_LW4_32x64: the same four tiles for a VNNI-4 B operand
-constexpr int GEMM_VARIANT_F32_X6_0 = 12; // = V_F32_X6_64x64: first of the four bf16x6 split tiles (brgemm_f32_x6.hip)
-constexpr int GEMM_VARIANT_GENERIC = 8;
-// planned on the bf16x6 split kernel (brgemm_f32_x6.hip: variants 12 .. 15). Such handles are never queued, grouped, chained or given a
-// folded transpose; a bf16x6 descriptor planned on an exact kernel (a shape the split kernel does not take) goes every way a mode-0 one goes
-inline bool gemm_on_x6(const GemmDesc &d) { return d.variant >= GEMM_VARIANT_F32_X6_0 && d.variant <= GEMM_VARIANT_F32_X6_0 + 3; } // = V_GENERIC of brgemm_f32.hip: the generic kernel was chosen (or forced) at dispatch
-// bf16 + VNNI-2 B, k a multiple of 64, m and n of 64, 16-byte-aligned leading dimensions within the 32-bit lane offsets: what the
-// LDS-DMA bf16 tile families (brgemm_bf16.hip, brgemm_bf16_lw.hip) need
-bool bf16_fast_eligible(const GemmDesc &d);
-// which B image of the loader-wave bf16 tiles (brgemm_bf16_lw.hip) a descriptor's B operand needs - 0: VNNI-2, 2: flat [k][ldb],
-// 4: VNNI-4 - or -1 if the descriptor cannot run on those tiles (shape / alignment / lane-offset limits of the LDS-DMA panels)
-int bf16_lw_b_kind(const GemmDesc &d);
 hipError_t launch_unary(const UnaryDesc &d, const void *in, float scalar, bool use_scalar, void *out,
                         hipStream_t stream);
 hipError_t launch_binary(const BinaryDesc &d, const void *lhs, const void *rhs, void *out,
