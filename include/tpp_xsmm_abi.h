@@ -275,8 +275,14 @@ TPP_XSMM_EXPORT int xsmm_hip_host_release(const void *ptr);
  * xsmm_hip_set_stream). ASYNCHRONOUS MODE CONTRACT with host operands: the lifetime rule above, and between two synchronisation
  * points the host neither reads outputs nor writes operands of the invokes in between (the runtime looks at an extent once per
  * synchronisation epoch; the tile queue then sees device pointers, so TPP_HIP_ASYNC=1 TPP_HIP_TILE_QUEUE=1 TPP_HIP_HOST_CACHE=1 runs
- * the compiler's tile invokes on host buffers as grouped launches). A range that was unmapped and mapped again, or cannot be tracked
- * (file-backed / shared mappings), falls back to the plain per-invoke mirror. Returns the previous setting, or -1 if the kernel
+ * the compiler's tile invokes on host buffers as grouped launches). xsmm_hip_set_stream counts as a synchronisation point when it
+ * changes the stream in asynchronous mode: the stream being left is drained, its outputs reach the host, a new epoch starts.
+ * THREADS: with the host cache on, a synchronisation point (any of the four, and xsmm_hip_set_host_cache(0)) must not run while
+ * ANOTHER thread is inside an invoke on host operands, or between that thread's invokes of one asynchronous region: the write-back
+ * protects partly covered pages again and marks them for upload, and the other thread's next invoke would upload host bytes over
+ * mirror bytes its own kernel wrote and that have not been written back yet. Join (or barrier) the calling threads first - the
+ * reference's harness synchronises from its single main thread behind the OpenMP region.
+ * A range that was unmapped and mapped again, or cannot be tracked (file-backed / shared mappings), falls back to the plain per-invoke mirror. Returns the previous setting, or -1 if the kernel
  * interface is missing (the cache stays off). Switching it off writes everything back and frees the mirrors.
  * _stats: out[0] extents, [1] mirror bytes, [2] bytes uploaded, [3] page-table scans, [4] bytes written back, [5] pages NOT written back
  * (their range changed hands or the host wrote them while a device write was pending), [6] extents created / grown / merged,

@@ -154,6 +154,18 @@ hipError_t launch_unary(const UnaryDesc &d, const void *in_, float scalar, bool 
       for (int64_t j = 0; j < d.n; ++j) out[j * d.ldo + i] = in[i * d.ldi + j];
     return hipSuccess;
   }
+  if (d.dtype == DT_BF16) { // identity / zero / relu on raw bf16 words (the host-cache driver's copy-path cases; no arithmetic)
+    if (use_scalar || (d.op != 1 && d.op != 2 && d.op != 5)) return hipErrorNotSupported;
+    const uint16_t *hi = (const uint16_t *)in_;
+    uint16_t *ho = (uint16_t *)out_;
+    for (int64_t i = 0; i < d.m; ++i)
+      for (int64_t j = 0; j < d.n; ++j) {
+        const uint16_t w = d.op == 2 ? 0 : hi[i * d.ldi + j];
+        const bool positive = !(w & 0x8000) && (w & 0x7fff) != 0 && !((w & 0x7f80) == 0x7f80 && (w & 0x7f)); // > 0, not NaN
+        ho[i * d.ldo + j] = d.op == 5 && !positive ? 0 : w;
+      }
+    return hipSuccess;
+  }
   for (int64_t i = 0; i < d.m; ++i)
     for (int64_t j = 0; j < d.n; ++j) {
       float v = d.op == 2 ? 0.0f : (use_scalar ? scalar : in[i * d.ldi + j]);
@@ -172,7 +184,9 @@ hipError_t launch_binary(const BinaryDesc &d, const void *l_, const void *r_, vo
   if (!g_compute) return hipSuccess;
   for (int64_t i = 0; i < d.m; ++i)
     for (int64_t j = 0; j < d.n; ++j) {
-      const float a = l[i * d.ldi_lhs + j], b = r[i * d.ldi_rhs + j];
+      // broadcast flags (XsmmEnum.td:58-70): ROW = one value per row, COL = one row of n values, SCALAR = one value
+      const float a = d.flags & 16 ? l[0] : d.flags & 4 ? l[j] : d.flags & 1 ? l[i * d.ldi_lhs] : l[i * d.ldi_lhs + j];
+      const float b = d.flags & 32 ? r[0] : d.flags & 8 ? r[j] : d.flags & 2 ? r[i * d.ldi_rhs] : r[i * d.ldi_rhs + j];
       out[i * d.ldo + j] = d.op == 1 ? a + b : d.op == 2 ? a * b : d.op == 3 ? a - b : a / b;
     }
   return hipSuccess;

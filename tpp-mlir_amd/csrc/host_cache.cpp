@@ -757,6 +757,12 @@ int translate(OpRef *ops, int n, bool async, uint64_t epoch, hipStream_t s) {
     if (!lost) break;
   }
   t.active.store(1, std::memory_order_seq_cst); // (under g_mu: no writer can be waiting)
+  // a grow / drop above deleted extents: the remembered ones go - ALL eight, not only the slots this invoke fills below (a two-operand
+  // invoke would otherwise stamp the new generation over slots 2 .. 7 that still name a deleted extent of an earlier GEMM)
+  if (t.mru_gen != g_struct_gen.load(std::memory_order_relaxed)) {
+    for (Extent *&m : t.mru) m = nullptr;
+    t.mru_gen = g_struct_gen.load(std::memory_order_relaxed);
+  }
   hits = 0;
   for (int i = 0; i < n; ++i)
     if (ext[i]) {
@@ -808,11 +814,38 @@ namespace {
 // userfaultfd-registered mapping makes the driver pin those pages one by one through the slow get_user_pages path (measured: 60 ms for
 // 4 MiB, against 80 us into an unregistered buffer). The caller has unprotected the pages (no write-protect fault per page) and has
 // drained the stream behind the kernels; this function returns with the host bytes in place.
+// staged_to_host: `len` device bytes at `src` to the host bytes at `host`, in pieces of at most one staging slot. Every device-to-host
+// copy through the staging buffer is one of these or a whole number of rows / pitches that fit a slot: no piece is larger than a slot.
+void staged_to_host(uintptr_t host, const char *src, size_t len, hipStream_t s) {
+  for (size_t off = 0; off < len;) {
+    const size_t n = std::min(len - off, Staging::SLOT);
+    int slot;
+    const auto t0 = std::chrono::steady_clock::now();
+    char *st = g_staging.acquire(&slot);
+    const auto t1 = std::chrono::steady_clock::now();
+    HC_HIP_OK(hipMemcpyAsync(st, src + off, n, hipMemcpyDeviceToHost, s));
+    HC_HIP_OK(hipStreamSynchronize(s));
+    const auto t2 = std::chrono::steady_clock::now();
+    memcpy((void *)(host + off), st, n);
+    if (g_trace >= 2)
+      fprintf(stderr, "[tpp-xsmm-hip host cache] copy_back %zu B: staging slot %.0f us, D2H %.0f us, memcpy %.0f us\n", n,
+              std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count(),
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t2).count());
+    g_staging.release(slot, s);
+    off += n;
+  }
+}
 void copy_back(Extent *e, uintptr_t host, size_t bytes, size_t rows, size_t row_bytes, size_t pitch, hipStream_t s) {
   const bool strided = rows && row_bytes < pitch;
-  if (strided && row_bytes * 4 < pitch) { // narrow rows (a tile of a wide matrix): gather the rows on the device side of the copy
+  if (!strided) {
+    staged_to_host(host, e->dev(host), bytes, s);
+  } else if (row_bytes > Staging::SLOT || (row_bytes * 4 >= pitch && pitch > Staging::SLOT)) {
+    // a row (or, where whole pitches would travel, a pitch) wider than a staging slot: row by row, each in slot-sized pieces
+    for (size_t r = 0; r < rows; ++r) staged_to_host(host + r * pitch, e->dev(host + r * pitch), row_bytes, s);
+  } else if (row_bytes * 4 < pitch) { // narrow rows (a tile of a wide matrix): gather the rows on the device side of the copy
+    const size_t per = Staging::SLOT / row_bytes; // >= 1: row_bytes <= SLOT here
     for (size_t r0 = 0; r0 < rows;) {
-      const size_t nr = std::min(rows - r0, Staging::SLOT / row_bytes);
+      const size_t nr = std::min(rows - r0, per);
       int slot;
       char *st = g_staging.acquire(&slot);
       HC_HIP_OK(hipMemcpy2DAsync(st, row_bytes, e->dev(host + r0 * pitch), pitch, row_bytes, nr, hipMemcpyDeviceToHost, s));
@@ -821,29 +854,18 @@ void copy_back(Extent *e, uintptr_t host, size_t bytes, size_t rows, size_t row_
       g_staging.release(slot, s);
       r0 += nr;
     }
-  } else { // dense, or rows that fill most of their pitch: whole spans through the staging buffer, only the written bytes to the host
-    for (size_t off = 0; off < bytes;) {
-      size_t len = std::min(bytes - off, Staging::SLOT);
-      if (strided && len < bytes - off) len = std::max<size_t>(len / pitch, 1) * pitch; // (whole rows per piece)
-      len = std::min(len, bytes - off);
+  } else { // rows that fill most of their pitch (pitch <= SLOT): whole pitches through the staging buffer, only the written bytes to the host
+    const size_t per = Staging::SLOT / pitch; // >= 1
+    for (size_t r0 = 0; r0 < rows;) {
+      const size_t nr = std::min(rows - r0, per);
+      const size_t len = std::min(nr * pitch, bytes - r0 * pitch); // (the last row ends at its row_bytes: nothing behind it is ours)
       int slot;
-      const auto t0 = std::chrono::steady_clock::now();
       char *st = g_staging.acquire(&slot);
-      const auto t1 = std::chrono::steady_clock::now();
-      HC_HIP_OK(hipMemcpyAsync(st, e->dev(host + off), len, hipMemcpyDeviceToHost, s));
+      HC_HIP_OK(hipMemcpyAsync(st, e->dev(host + r0 * pitch), len, hipMemcpyDeviceToHost, s));
       HC_HIP_OK(hipStreamSynchronize(s));
-      const auto t2 = std::chrono::steady_clock::now();
-      if (!strided) {
-        memcpy((void *)(host + off), st, len);
-      } else {
-        for (size_t r = 0; r * pitch < len; ++r) memcpy((void *)(host + off + r * pitch), st + r * pitch, std::min(row_bytes, len - r * pitch));
-      }
-      if (g_trace >= 2)
-        fprintf(stderr, "[tpp-xsmm-hip host cache] copy_back %zu B: staging slot %.0f us, D2H %.0f us, memcpy %.0f us\n", len,
-                std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count(),
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t2).count());
+      for (size_t r = 0; r < nr; ++r) memcpy((void *)(host + (r0 + r) * pitch), st + r * pitch, std::min(row_bytes, len - r * pitch));
       g_staging.release(slot, s);
-      off += len;
+      r0 += nr;
     }
   }
   e->arm(pg_floor(host), pg_ceil(host + bytes), false);
@@ -890,12 +912,7 @@ void complete(OpRef *ops, int n, bool async, uint64_t epoch, hipStream_t s) {
         if (!registered) {
           HC_HIP_OK(hipMemcpyAsync((void *)a, src + (a - h), b - a, hipMemcpyDeviceToHost, s));
         } else {
-          int slot;
-          char *st = g_staging.acquire(&slot);
-          HC_HIP_OK(hipMemcpyAsync(st, src + (a - h), b - a, hipMemcpyDeviceToHost, s));
-          HC_HIP_OK(hipStreamSynchronize(s));
-          memcpy((void *)a, st, b - a);
-          g_staging.release(slot, s);
+          staged_to_host(a, src + (a - h), b - a, s); // (an in-place invoke: the input's extent holds the inner pages too)
         }
         st_wb_bytes.fetch_add((int64_t)(b - a), std::memory_order_relaxed);
       };

@@ -313,6 +313,9 @@ extern "C" void xsmm_hip_set_stream(void *s) {
     HIP_OK(hipStreamSynchronize(old));
     check_chain_errors(old);
     hc::on_sync_point(old);
+    // a synchronisation point like the three above: a new epoch, so that the host cache polls its extents again (the host may have
+    // written operands) and lists written footprints again (on_sync_point has just emptied the lists)
+    g_devmem_epoch.fetch_add(1, std::memory_order_relaxed);
   }
 }
 extern "C" int xsmm_hip_set_tile_queue(int enable) {
