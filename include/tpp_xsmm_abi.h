@@ -316,6 +316,24 @@ TPP_XSMM_EXPORT void xsmm_hip_force_variant(int variant);
  * measurement switch): -1 = the model (default), 0 or 1 = never split, n > 1 = n workgroups per tile (at most 16 and at most the
  * number of 64-k chunks). Also TPP_HIP_SPLIT. Returns the previous setting. */
 TPP_XSMM_EXPORT int xsmm_hip_force_split(int workgroups_per_tile);
+/* Tail split (opt-in; also TPP_HIP_TAIL_SPLIT). The f32 loader-wave tiles run one workgroup per compute unit, so a whole-layer f32
+ * call of q * CUs + r output tiles runs q full rounds of workgroups and a last one that occupies r CUs for a whole K loop. With the
+ * tail split on, a call planned on one of the K-split tiles (64x64 + K2, 64x32 + K4, 32x32 + K4) with q >= 1 and 0 < r <= CUs / 2 runs
+ * as ONE launch in which the q * CUs tiles of the full rounds run unsplit and each of the r tail tiles is shared by S workgroups on the
+ * otherwise idle CUs, under the protocol of xsmm_hip_force_split (partials summed in split order by the workgroup that finishes last;
+ * nobody waits for anybody). mode 0 = off (default); 1 = the model: S = min(CUs / r, 16, chunks / 4) where chunks is the number of 64-k
+ * chunks of a tile, used if S >= 2 and the K-loop time it saves exceeds the hand-off; 2 .. 16 = that many workgroups per tail tile (at most
+ * the chunks) wherever r * S <= CUs (a test / measurement switch). Read per invoke; returns the previous setting, -1 (and changes
+ * nothing) for any other value. xsmm_hip_force_split >= 0 switches the tail split off. The choice depends on the descriptor, the batch
+ * count and the CU count only, so it is made in strict mode too. Results are run-to-run reproducible and within the f32 bars; body
+ * tiles have the bits of the unsplit launch, tail tiles those of a split launch with S workgroups - they differ from the unsplit launch
+ * in last bits on the tail tiles only. Without a scratch block, or on a stream that is being captured, the call runs unsplit
+ * (xsmm_hip_last_refined_kernel then reads ""; otherwise "..., tail split"). A chain launch is unaffected: chains already refuse grids
+ * larger than the chip.
+ * _stats: out[0] launches that ran with a split tail since process start; of the most recent one: [1] tail tiles, [2] workgroups per
+ * tail tile, [3] body tiles. */
+TPP_XSMM_EXPORT int xsmm_hip_set_tail_split(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_tail_split_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

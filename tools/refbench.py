@@ -95,7 +95,7 @@ def cases(only):
     return out
 
 
-def argv_of(c, n_iter, repeats=1, f32_precision="exact"):
+def argv_of(c, n_iter, repeats=1, f32_precision="exact", tail_split=0):
     if c.get("script"):
         return ["--script", c["script"], "--queue", "1", "-n", str(n_iter)]
     a = ["--batch", str(c["M"]), "--layers", ",".join(map(str, c["layers"])), "--kernel", c["kernel"], "-n", str(n_iter), "--queue", "1"]
@@ -111,6 +111,8 @@ def argv_of(c, n_iter, repeats=1, f32_precision="exact"):
         a += ["--bf16", "--vnni", c["dtype"][-1]]
     elif f32_precision != "exact":
         a += ["--f32-precision", f32_precision]
+    if tail_split and c["form"] == "whole" and c["dtype"] == "f32":
+        a += ["--tail-split", str(tail_split)]
     return a
 
 
@@ -133,6 +135,8 @@ def main():
     ap.add_argument("--json", default="")
     ap.add_argument("--f32-precision", default="exact", choices=["exact", "bf16x6"],
                     help="arithmetic of the f32 rows' dispatches (xsmm_hip_set_f32_precision): exact f32 MFMA or the bf16x6 split")
+    ap.add_argument("--tail-split", type=int, default=0, choices=range(17), metavar="0..16",
+                    help="xsmm_hip_set_tail_split for the f32 whole-layer rows: 0 off, 1 the model, 2 .. 16 workgroups per tail tile")
     ap.add_argument("--repeats", type=int, default=3, help="timed loops per row (own timer each): the row gets us_min / us_median / us_max and "
                     "the tile queue's abandoned-replay count (VERDICT r5 weak 9: a row must say whether its mean is typical)")
     args = ap.parse_args()
@@ -143,7 +147,7 @@ def main():
     cs = [c for c in cs if not c.get("script")] + [c for c in cs if c.get("script")]
     with tempfile.NamedTemporaryFile("w", suffix=".cases", delete=False) as f:
         for c in cs:
-            f.write(" ".join(argv_of(c, args.n, args.repeats, args.f32_precision)) + "\n")
+            f.write(" ".join(argv_of(c, args.n, args.repeats, args.f32_precision, args.tail_split)) + "\n")
         path = f.name
     r = subprocess.run([replay, "--cases", path], capture_output=True, text=True, timeout=3000)
     os.unlink(path)

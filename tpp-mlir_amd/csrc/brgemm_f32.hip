@@ -649,6 +649,7 @@ hipError_t launch_gemm_bf16_fast(int tile, const GemmArgs &a, hipStream_t s); //
 hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         // brgemm_f32_lw.hip (tile 4: 128x64, forced variant 10 only - it measures within 2 % of brgemm_f32_fast<128x64>)
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
+hipError_t launch_f32_lw_tail(int tile, const GemmArgs &a, int tail_tiles, int split, hipStream_t s); // the same
 hipError_t launch_f32_lw16(int tile, const GemmArgs &a, const WorkItem *items, int n_items, bool grouped, hipStream_t s); // brgemm_f32_lw16.hip: tile 0 = 32x16
 hipError_t launch_f32_x6(int tile, const GemmArgs &a, bool vec, hipStream_t s); // brgemm_f32_x6.hip: tile = variant - V_F32_X6_64x64
 hipError_t launch_bf16_grouped64(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s); // brgemm_bf16.hip
@@ -679,7 +680,9 @@ int force_gemm_split(int v) { return g_forced_split.exchange(v < -1 ? -1 : v); }
 static std::atomic<int> g_strict_kernels{0};
 int set_strict_kernels(int on) { return g_strict_kernels.exchange(on != 0); }
 bool strict_kernels() { return g_strict_kernels.load(std::memory_order_relaxed) != 0; }
-static GemmPlanEnv gemm_plan_env() { return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed)}; }
+static GemmPlanEnv gemm_plan_env() {
+  return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed), g_tail_split.load(std::memory_order_relaxed)};
+}
 bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, gemm_plan_env()); }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, gemm_plan_env()); }
 
@@ -702,6 +705,7 @@ static GemmArgs gemm_args(const GemmDesc &d, const void *A, const void *B, void 
   a.vf = d.vnni_factor ? d.vnni_factor : 2;
   a.split = 0; a.scratch = nullptr; a.split_cnt = nullptr;
   a.b_trans = d.b_trans;
+  a.tail_body = 0;
   return a;
 }
 // the one-layer ChainArgs of the bf16 loader-wave launchers (brgemm_bf16_lw.hip); br: the batch count (grouped: the first item's), m x n:
@@ -769,6 +773,21 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     const hipError_t e = launch_f32_lw_split(p.launcher == GL_F32_LW ? p.tile : 3, a, p.split, stream);
     if (e != hipErrorOutOfMemory && e != hipErrorInvalidValue) return g_last_refined.store(text, std::memory_order_relaxed), e;
     (void)hipGetLastError(); // no scratch block: the unsplit launch
+    text = "";
+  }
+  if (p.tail_tiles > 0 && p.launcher == GL_F32_LW) { // a launch with a split tail (xsmm_desc.h g_tail_split; its scratch block may be missing)
+    const hipError_t e = launch_f32_lw_tail(p.tile, a, p.tail_tiles, p.tail_split, stream);
+    if (e != hipErrorOutOfMemory && e != hipErrorInvalidValue) {
+      if (e == hipSuccess) {
+        const int64_t tiles = (d.m / (p.tile == 3 ? 32 : 64)) * (d.n / (p.tile == 1 ? 64 : 32));
+        g_tail_split_stats[1].store(p.tail_tiles, std::memory_order_relaxed);
+        g_tail_split_stats[2].store(p.tail_split, std::memory_order_relaxed);
+        g_tail_split_stats[3].store(tiles - p.tail_tiles, std::memory_order_relaxed);
+        g_tail_split_stats[0].fetch_add(1, std::memory_order_relaxed);
+      }
+      return g_last_refined.store(text, std::memory_order_relaxed), e;
+    }
+    (void)hipGetLastError(); // no scratch block: the plain launch
     text = "";
   }
   g_last_refined.store(text, std::memory_order_relaxed);

@@ -41,8 +41,23 @@ typedef __attribute__((address_space(1))) unsigned int g_u32_lw;
 // C (beta = 1), bias, relu, stores, and resets the counter. No workgroup ever waits for another one (no co-residency assumption).
 // GROUPED or SPLIT kernels also take n that is not a multiple of the tile width (the reference's --tiles=64,48,64 / 32,48,32):
 // the B loader clamps the column pieces, the epilogue masks its loads and stores; the plain kernel (C2, C3) carries none of this.
-template <int WM, int WN, int WK, bool GROUPED, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL, bool SPLIT = false>
+// TAIL (opt-in, xsmm_hip_set_tail_split; gemm_plan.cpp choose_f32_tail_split): a whole-layer call of q CUs + r tiles in ONE launch whose
+// first p.tail_body = q CUs workgroups each run one whole tile exactly as the plain kernel does (C joined at the start, all chunks,
+// direct epilogue: the plain launch's bits) and whose last r S workgroups run the r tiles of the partial last round under the SPLIT
+// protocol above, unchanged (chunk range [T s / S, T (s + 1) / S), park, count, the last arrival sums in split order: the bits of a
+// SPLIT launch with that S). Body or tail is a run-time, workgroup-uniform test - which is why this is an instance of its own and not
+// a mode of the plain kernel; it has the loader-wave counts of the plain instance of its tile, the body is most of the launch.
+// The grid is linear and workgroups go to the XCDs round robin (XCD = workgroup id mod 8), so the mapping rebuilds the plain
+// launcher's XCD blocks by hand: XCD x owns block x of the xm x xn blocks of tiles_m x tiles_n tiles the plain launcher would have
+// chosen, and walks it in the plain grid's order (column fastest). The first tail_body / 8 tiles of EVERY block are body tiles, the
+// rest of the block its tail tiles - each XCD's L2 keeps seeing one block of A rows and B columns through the whole launch, and the
+// S workgroups of a tail tile run on the XCD whose L2 already holds that block's panels, in [s][tile] order like the SPLIT grid (the
+// workgroups that start together share a k range). Shapes or CU counts that do not divide into 8 blocks: ONE block, the whole grid
+// (p.tiles_m x p.tiles_n is then the whole tile grid: that is how the kernel tells the two).
+template <int WM, int WN, int WK, bool GROUPED, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL, bool SPLIT = false, bool TAIL = false>
 __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(GemmArgs p, const WorkItem *__restrict__ items) {
+  static_assert(!TAIL || (!GROUPED && !SPLIT), "the tail split is an instance of its own");
+  constexpr bool MAYSPLIT = SPLIT || TAIL; // some workgroup of the launch shares its tile's batch-reduce range
   constexpr int NMW = WM * WN * WK; // MFMA waves
   constexpr int BM = 32 * WM, BN = 32 * WN;
   constexpr int A_STAGE = BM * LW_BK, B_STAGE = LW_BK * BN, SLOT = A_STAGE + B_STAGE; // floats
@@ -66,7 +81,24 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
   constexpr bool RAGN = GROUPED || SPLIT; // n may end inside the tile's last 32-column block (a multiple of 4)
   WorkItem it{p.A, p.B, p.C, p.D, (int64_t)p.br};
   int tm, tn, sp = 0, tile_id = 0;
-  if constexpr (SPLIT && GROUPED) {
+  bool is_tail = false; // TAIL: this workgroup shares a tail tile (else: it runs a whole body tile)
+  if constexpr (TAIL) {
+    const int per_block = p.tiles_m * p.tiles_n;                          // tiles of one block
+    const int xshift = (p.m / BM) * (p.n / BN) == per_block ? 0 : 3;      // one block, or the 8 XCD blocks
+    const int body_per = p.tail_body >> xshift, tail_per = per_block - body_per; // body and tail tiles of every block
+    const int u = (int)blockIdx.x, x = u & ((1 << xshift) - 1); // (tail_body is a multiple of the block count: x is the XCD for both kinds)
+    int lt = u >> xshift; // tile of block x, in the plain grid's order
+    is_tail = u >= p.tail_body;
+    if (is_tail) {
+      const int j = (u - p.tail_body) >> xshift, t = j % tail_per;
+      sp = j / tail_per;
+      tile_id = x * tail_per + t; // scratch block and arrival counter: tail tiles only
+      lt = body_per + t;
+    }
+    const int tz = lt / p.tiles_n;
+    tm = (x >> p.xn_shift) * p.tiles_m + tz;
+    tn = (x & ((1 << p.xn_shift) - 1)) * p.tiles_n + (lt - tz * p.tiles_n);
+  } else if constexpr (SPLIT && GROUPED) {
     // grid (items * S, tiles_n, tiles_m): x = item * S + s (the two block rows of a layer that share a B panel then meet on one XCD)
     const int item = (int)blockIdx.x / p.split;
     sp = (int)blockIdx.x - item * p.split;
@@ -101,9 +133,10 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
   const bool pair = GROUPED && p.k == 32;
   const int kchunks = pair ? 1 : p.k / LW_BK;
   const int Tall = pair ? (int)it.br / 2 : (int)it.br * kchunks;
-  // SPLIT: this workgroup's chunks [t_first, t_first + T) of the tile's Tall
-  const int t_first = SPLIT ? (int)(((long long)Tall * sp) / p.split) : 0;
-  const int T = SPLIT ? (int)(((long long)Tall * (sp + 1)) / p.split) - t_first : Tall;
+  // SPLIT: this workgroup's chunks [t_first, t_first + T) of the tile's Tall (TAIL: a body workgroup is the only one of its tile)
+  const int nsplit = TAIL && !is_tail ? 1 : p.split;
+  const int t_first = MAYSPLIT ? (int)(((long long)Tall * sp) / nsplit) : 0;
+  const int T = MAYSPLIT ? (int)(((long long)Tall * (sp + 1)) / nsplit) - t_first : Tall;
 
   if (wave >= NMW) {
     // ---- loader waves --------------------------------------------------------------------
@@ -134,7 +167,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
     int kc = 0;
     const int64_t d_in = isA ? (int64_t)LW_BK : (int64_t)LW_BK * p.ldb;
     const int64_t d_wrap = (isA ? p.stride_a : p.stride_b) * (pair ? 2 : 1) - (int64_t)(kchunks - 1) * d_in;
-    if constexpr (SPLIT) { // start at chunk t_first: batch element t_first / kchunks (pair mode: the pair t_first), k block t_first % kchunks
+    if constexpr (MAYSPLIT) { // start at chunk t_first: batch element t_first / kchunks (pair mode: the pair t_first), k block t_first % kchunks
       const int b0 = t_first / kchunks;
       kc = t_first - b0 * kchunks;
       g += (int64_t)b0 * (isA ? p.stride_a : p.stride_b) * (pair ? 2 : 1) + (int64_t)kc * d_in;
@@ -221,7 +254,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
   if constexpr (BIAS_EARLY) {
     if ((p.ep & EP_BIAS) && piece_ok) bias4 = *(const f32x4 *)((const float *)it.D + n0 + wn * 32 + 4 * (lane & 7));
   }
-  if (wk == 0 && !SPLIT) { // (SPLIT: C joins the ordered sum of the partials in the last workgroup's epilogue)
+  if (wk == 0 && !SPLIT && !(TAIL && is_tail)) { // (SPLIT: C joins the ordered sum of the partials in the last workgroup's epilogue)
     if (!(p.ep & EP_BETA0) && (!RAGN || ccol < p.n)) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
@@ -335,11 +368,11 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
       for (int g = 1; g < WK; ++g) v += *(const f32x4 *)(src + g * (WM * WN) * 1024);
       part[j] = v;
     }
-    if constexpr (SPLIT) {
+    if (MAYSPLIT && (!TAIL || is_tail)) {
       // park the partial tile: block [tile][split][piece], piece = (j * NMW + MFMA wave) * 64 + lane - every wave instruction writes
       // 1 KiB contiguous; the last workgroup reads the S blocks with the same lane mapping
       constexpr int TILE = BM * BN; // floats per partial
-      const int S = p.split;
+      const int S = nsplit;
       float *scr = p.scratch + (size_t)tile_id * S * TILE;
       const __amdgpu_buffer_rsrc_t rsrcS = __builtin_amdgcn_make_buffer_rsrc((void *)scr, 0, 0x7fffffff, 0x00020000);
       const unsigned pvo = (unsigned)((wave * 64 + lane) * 16);
@@ -377,7 +410,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
       const int q = 8 * (wk * IPG + j) + rsel;
       f32x4 v = part[j];
       const unsigned co = (unsigned)(((wm * 32 + q) * (int)p.ldc + wn * 32 + 4 * c4) * 4);
-      if constexpr (SPLIT) {
+      if (MAYSPLIT && (!TAIL || is_tail)) {
         if (!(p.ep & EP_BETA0) && piece_ok) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrcC, co, 0, 0));
       }
       v += bias4;
@@ -399,19 +432,11 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
   }
 }
 
-template <int WM, int WN, int WK, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL> static hipError_t launch_lw_t(const GemmArgs &a, hipStream_t s) {
-  constexpr int BM = 32 * WM, BN = 32 * WN, NT = 64 * (WM * WN * WK + NL + NLB);
-  constexpr size_t lds = (size_t)NSLOT * (BM * LW_BK + LW_BK * BN) * sizeof(float);
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  static std::atomic<unsigned long long> lds_set{0};
-  if (hipError_t e = ensure_dynamic_lds((const void *)brgemm_f32_lw<WM, WN, WK, false, NL, NSLOT, NLB>, (int)lds, lds_set); e != hipSuccess) return e;
-  GemmArgs args = a;
-  const int tiles_m = a.m / BM, tiles_n = a.n / BN;
-  dim3 grid;
-  // XCD-blocked grid: xm x xn = 8 XCD blocks of tiles_m/xm x tiles_n/xn tiles (blockIdx.x = the XCD: workgroups go to XCDs round
-  // robin). Each XCD's L2 then fetches m/xm rows of A and n/xn columns of B: the split that minimises m/xm + n/xn - 4 x 2 for
-  // square outputs (C2; ties keep it: rounds 1-3 had only this one), 2 x 4 for C3's 512 x 1024 and the batch-256 layers (-20 / -33 % of
-  // the L2 fill).
+// The XCD blocks of a whole-layer grid: xm x xn = 8 blocks of tiles_m/xm x tiles_n/xn tiles, one per XCD. Each XCD's L2 then fetches
+// m/xm rows of A and n/xn columns of B: the split that minimises m/xm + n/xn - 4 x 2 for square outputs (C2; ties keep it: rounds
+// 1-3 had only this one), 2 x 4 for C3's 512 x 1024 and the batch-256 layers (-20 / -33 % of the L2 fill). Returns xm, 0 = the
+// tile grid does not divide into 8 blocks.
+static int lw_xcd_blocks(const GemmArgs &a, int tiles_m, int tiles_n) {
   int xm = 0;
   long long best = -1;
   for (int c : {4, 2, 8, 1}) {
@@ -423,6 +448,20 @@ template <int WM, int WN, int WK, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL
       xm = c;
     }
   }
+  return xm;
+}
+
+template <int WM, int WN, int WK, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL> static hipError_t launch_lw_t(const GemmArgs &a, hipStream_t s) {
+  constexpr int BM = 32 * WM, BN = 32 * WN, NT = 64 * (WM * WN * WK + NL + NLB);
+  constexpr size_t lds = (size_t)NSLOT * (BM * LW_BK + LW_BK * BN) * sizeof(float);
+  static_assert(lds <= 160 * 1024, "LDS budget");
+  static std::atomic<unsigned long long> lds_set{0};
+  if (hipError_t e = ensure_dynamic_lds((const void *)brgemm_f32_lw<WM, WN, WK, false, NL, NSLOT, NLB>, (int)lds, lds_set); e != hipSuccess) return e;
+  GemmArgs args = a;
+  const int tiles_m = a.m / BM, tiles_n = a.n / BN;
+  dim3 grid;
+  // XCD-blocked grid (lw_xcd_blocks; blockIdx.x = the XCD: workgroups go to XCDs round robin)
+  const int xm = lw_xcd_blocks(a, tiles_m, tiles_n);
   args.xn_shift = 0;
   if (xm) {
     const int xn = 8 / xm;
@@ -474,6 +513,39 @@ template <int WM, int WN, int WK> static hipError_t launch_lw_split_t(const Gemm
   hipLaunchKernelGGL((brgemm_f32_lw<WM, WN, WK, false, 1, LW_NSLOT, 1, true>), dim3((unsigned)(tiles * S)), dim3(NT), lds, s, args, (const WorkItem *)nullptr);
   return hipGetLastError();
 }
+// whole-layer call with a split tail (kernel comment, TAIL): linear grid, the body workgroups first, then S per tail tile. Scratch
+// and counters for the tail tiles only. m, n multiples of the tile (the planner's tile choice); tail_tiles < tiles, S >= 2.
+template <int WM, int WN, int WK, int NL, int NLB> static hipError_t launch_lw_tail_t(const GemmArgs &a, int tail_tiles, int S, hipStream_t s) {
+  constexpr int BM = 32 * WM, BN = 32 * WN, NT = 64 * (WM * WN * WK + NL + NLB);
+  constexpr size_t lds = (size_t)LW_NSLOT * (BM * LW_BK + LW_BK * BN) * sizeof(float);
+  const int tiles_m = a.m / BM, tiles_n = a.n / BN;
+  const long long tiles = (long long)tiles_m * tiles_n, body = tiles - tail_tiles;
+  if (a.m % BM || a.n % BN || tail_tiles <= 0 || body <= 0 || S < 2 || S > SPLIT_MAX || body + (long long)tail_tiles * S > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  const SplitScratch *sc = split_scratch_for(s, tail_tiles, (long long)tail_tiles * S * BM * BN);
+  if (!sc) return hipErrorOutOfMemory; // the caller falls back to the plain launch
+  static std::atomic<unsigned long long> lds_set{0};
+  if (hipError_t e = ensure_dynamic_lds((const void *)brgemm_f32_lw<WM, WN, WK, false, NL, LW_NSLOT, NLB, false, true>, (int)lds, lds_set); e != hipSuccess) return e;
+  GemmArgs args = a;
+  const int xm = lw_xcd_blocks(a, tiles_m, tiles_n);
+  if (xm && body % 8 == 0 && tail_tiles % 8 == 0) { // every XCD block: body / 8 body tiles, then tail_tiles / 8 tail tiles
+    const int xn = 8 / xm;
+    args.tiles_m = tiles_m / xm;
+    args.tiles_n = tiles_n / xn;
+    args.xn_shift = xn == 8 ? 3 : xn == 4 ? 2 : xn == 2 ? 1 : 0;
+  } else {
+    args.tiles_m = tiles_m;
+    args.tiles_n = tiles_n;
+    args.xn_shift = 0;
+  }
+  args.split = S;
+  args.scratch = sc->partial;
+  args.split_cnt = sc->cnt;
+  args.tail_body = (int)body;
+  hipLaunchKernelGGL((brgemm_f32_lw<WM, WN, WK, false, NL, LW_NSLOT, NLB, false, true>), dim3((unsigned)(body + (long long)tail_tiles * S)), dim3(NT), lds, s, args,
+                     (const WorkItem *)nullptr);
+  return hipGetLastError();
+}
 // tile queue group: grid (items * S, tiles_n, tiles_m)
 template <int WM, int WN, int WK>
 static hipError_t launch_lw_grouped_split_t(const GemmArgs &a, const WorkItem *items, int n_items, int S, hipStream_t s) {
@@ -522,6 +594,17 @@ hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream
   case 1: return launch_lw_split_t<2, 2, 2>(a, split, s);
   case 2: return launch_lw_split_t<2, 1, 4>(a, split, s);
   case 3: return launch_lw_split_t<1, 1, 4>(a, split, s);
+  default: return hipErrorInvalidValue;
+  }
+}
+
+// whole-layer call whose last tail_tiles tiles run on `split` workgroups each; loader waves per tile as launch_f32_lw.
+// hipErrorOutOfMemory / hipErrorInvalidValue: not launched, use launch_f32_lw
+hipError_t launch_f32_lw_tail(int tile, const GemmArgs &a, int tail_tiles, int split, hipStream_t s) {
+  switch (tile) {
+  case 1: return launch_lw_tail_t<2, 2, 2, 2, 2>(a, tail_tiles, split, s);
+  case 2: return launch_lw_tail_t<2, 1, 4, 2, 1>(a, tail_tiles, split, s);
+  case 3: return launch_lw_tail_t<1, 1, 4, 1, 1>(a, tail_tiles, split, s);
   default: return hipErrorInvalidValue;
   }
 }

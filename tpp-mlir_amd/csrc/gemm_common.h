@@ -30,7 +30,9 @@ struct GemmArgs {
   float *scratch;
   unsigned *split_cnt;
   int b_trans;         // generic kernel: B[k][j] = B_ptr[j * ldb + k] (GemmDesc::b_trans)
+  int tail_body;       // brgemm_f32_lw TAIL instances: the first tail_body workgroups of the linear grid run whole tiles, the rest share the tail tiles
 };
+static_assert(sizeof(GemmArgs) == 136, "GemmArgs: the kernels that take a work list read it behind this block");
 
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short h) {
   return __uint_as_float(((unsigned int)h) << 16);

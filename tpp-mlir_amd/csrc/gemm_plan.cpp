@@ -107,19 +107,47 @@ static bool f32_32x32_beats_64x32(int64_t t32, int64_t t6432, int64_t cus) {
 // Hence: the largest S with tiles * S <= CUs, if the K-loop time it saves exceeds the hand-off. The answer depends on the
 // descriptor, the batch count and the number of tiles in the launch only: the same call pattern always adds in the same order.
 // xsmm_hip_force_split / TPP_HIP_SPLIT: 0 / 1 = never split, n > 1 = always n (clamped to the chunks), -1 = this model.
-static int choose_f32_split(int tile, long long tiles, long long chunks, const GemmPlanEnv &env) {
-  const int forced = env.forced_split;
-  if (tile < 1 || tile > 3 || tiles <= 0 || chunks < 2) return 1;
+// the model's answer when a tile may take at most `room` workgroups (1 = no split)
+static int f32_split_model(int tile, long long room, long long chunks) {
   const long long smax = chunks < SPLIT_MAX_WG ? chunks : SPLIT_MAX_WG;
-  if (forced >= 0) return forced <= 1 ? 1 : (int)(forced < smax ? forced : smax);
   const double c = tile == 1 ? 0.92 : tile == 2 ? 0.46 : 0.213;
-  long long S = env.cus / tiles;
+  long long S = room;
   if (S > smax) S = smax;
   if (S > chunks / 4) S = chunks / 4; // at least four chunks per workgroup
   if (S < 2) return 1;
   const long long per = (chunks + S - 1) / S;
   const double saved = c * (double)(chunks - per);
   return saved > SPLIT_HANDOFF_US ? (int)S : 1;
+}
+static int choose_f32_split(int tile, long long tiles, long long chunks, const GemmPlanEnv &env) {
+  const int forced = env.forced_split;
+  if (tile < 1 || tile > 3 || tiles <= 0 || chunks < 2) return 1;
+  const long long smax = chunks < SPLIT_MAX_WG ? chunks : SPLIT_MAX_WG;
+  if (forced >= 0) return forced <= 1 ? 1 : (int)(forced < smax ? forced : smax);
+  return f32_split_model(tile, env.cus / tiles, chunks);
+}
+
+// TAIL SPLIT (xsmm_hip_set_tail_split, opt-in): a launch of q CUs + r tiles, q >= 1, runs q full rounds of workgroups and a last one
+// that occupies r CUs for a whole K loop. With 0 < r <= CUs / 2 the r tiles of that round are split over the CUs it leaves idle, the
+// q CUs tiles in front of them run unsplit, all in one launch (brgemm_f32_lw.hip launch_f32_lw_tail). Mode 1: the split model above
+// with CUs / r workgroups of room per tail tile; mode n >= 2 (tests, measurements): n workgroups per tail tile (at most 16 and the
+// chunks) wherever r n <= CUs, no saving test. Off while a split count is forced. Returns the workgroups per tail tile (1 = no
+// tail split) and the tail tiles. Descriptor, batch count and CU count only, like the split: allowed in strict mode.
+static int choose_f32_tail_split(int tile, long long tiles, long long chunks, const GemmPlanEnv &env, int *tail_tiles) {
+  *tail_tiles = 0;
+  if (env.tail_split == 0 || env.forced_split >= 0 || tile < 1 || tile > 3 || env.cus <= 0 || tiles <= env.cus) return 1;
+  const long long r = tiles % env.cus;
+  if (r == 0 || r > env.cus / 2) return 1;
+  long long S;
+  if (env.tail_split == 1) S = f32_split_model(tile, env.cus / r, chunks);
+  else {
+    S = env.tail_split < SPLIT_MAX_WG ? env.tail_split : SPLIT_MAX_WG;
+    if (S > chunks) S = chunks;
+    if (r * S > env.cus) S = 1;
+  }
+  if (S < 2) return 1;
+  *tail_tiles = (int)r;
+  return (int)S;
 }
 
 // The 32x32 K-split bf16 kernel over several workgroups per tile, for skinny groups with a long reduction (the kernel is a
@@ -387,7 +415,17 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
     static const char *const split_names[4] = {"", "brgemm_f32_lw<64x64,k2>, split", "brgemm_f32_lw<64x32,k4>, split", "brgemm_f32_lw<32x32,k4>, split"};
     const int tile = v == V_F32_LW_32x32K4 ? 3 : v - V_F32_LW_64x64;
     const int bm = tile == 3 ? 32 : 64, bn = tile == 1 ? 64 : 32;
-    const int S = choose_f32_split(tile, (long long)(d.m / bm) * (d.n / bn), (long long)br * (d.k / BK), env);
+    const long long tiles = (long long)(d.m / bm) * (d.n / bn), chunks = (long long)br * (d.k / BK);
+    const int S = choose_f32_split(tile, tiles, chunks, env);
+    // more tiles than CUs and a partial last round: its tiles over the CUs it leaves idle, if asked for (choose_f32_tail_split)
+    static const char *const tail_names[4] = {"", "brgemm_f32_lw<64x64,k2>, tail split", "brgemm_f32_lw<64x32,k4>, tail split", "brgemm_f32_lw<32x32,k4>, tail split"};
+    int tail_tiles = 0;
+    const int tail_S = S == 1 ? choose_f32_tail_split(tile, tiles, chunks, env, &tail_tiles) : 1;
+    if (tail_S > 1) {
+      GemmLaunch l = launch(GL_F32_LW, tile, tail_names[tile], 1);
+      l.tail_tiles = tail_tiles, l.tail_split = tail_S;
+      return l;
+    }
     return launch(GL_F32_LW, tile, S > 1 ? split_names[tile] : "", S);
   }
   // (the half-width tiles store 16-byte pieces of C and of the bias row: else the generic kernel below)

@@ -523,6 +523,10 @@ extern "C" void xsmm_hip_fold_epilogue_stats(int64_t out[3]) {
   out[2] = g_fe_declined.load(std::memory_order_relaxed); // element-wise invokes on a GEMM group that flushed it instead (ineligible)
 }
 extern "C" int xsmm_hip_force_split(int v) { return tpp::force_gemm_split(v); }
+extern "C" int xsmm_hip_set_tail_split(int mode) { return mode < 0 || mode > 16 ? -1 : tpp::g_tail_split.exchange(mode); }
+extern "C" void xsmm_hip_tail_split_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_tail_split_stats[i].load(std::memory_order_relaxed);
+}
 // the VNNI blocking factor of bf16 B operands dispatched from now on (2 or 4); returns the previous one, -1 for an invalid factor
 extern "C" int xsmm_hip_set_vnni_factor(int v) {
   if (v != 2 && v != 4) return -1;

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <atomic>
 
 namespace tpp {
 
@@ -134,6 +136,16 @@ int force_gemm_split(int workgroups_per_tile); // xsmm_hip_force_split (brgemm_f
 // bf16 VNNI-2 / VNNI-4, m = n = 64, k a multiple of 64; never in strict mode; gemm_plan.h)
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br);
 hipError_t launch_gemm_quads(const GemmDesc &d, const QuadItem *quads, int n_quads, int64_t br, hipStream_t stream);
+// TAIL SPLIT (xsmm_hip_set_tail_split / TPP_HIP_TAIL_SPLIT; gemm_plan.cpp choose_f32_tail_split): 0 = off, 1 = the model, 2 .. 16 = that
+// many workgroups per tail tile. The setting and the counters of xsmm_hip_tail_split_stats live HERE, as inline variables: the ABI
+// layer (runtime.cpp) sets and reads them, the launch code (brgemm_f32.hip gemm_plan_env, launch_gemm) reads the setting per invoke
+// and counts - and the host-only builds of runtime.cpp (tests/tsan) link without any kernel file.
+inline std::atomic<int> g_tail_split{[] {
+  const char *e = getenv("TPP_HIP_TAIL_SPLIT");
+  const int v = e ? atoi(e) : 0;
+  return v >= 0 && v <= 16 ? v : 0;
+}()};
+inline std::atomic<int64_t> g_tail_split_stats[4]; // launches with a split tail; tail tiles, workgroups per tail tile, body tiles of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

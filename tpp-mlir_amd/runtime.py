@@ -109,6 +109,8 @@ _SIGNATURES = {
     "xsmm_hip_last_refined_kernel": (ctypes.c_char_p, []),
     "xsmm_hip_force_variant": (None, [ctypes.c_int]),
     "xsmm_hip_force_split": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_set_tail_split": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_tail_split_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_fold_transpose_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_epilogue": (ctypes.c_int, [ctypes.c_int]),
@@ -322,6 +324,17 @@ class XsmmRuntime:
     def force_split(self, workgroups_per_tile):
         """-1 the model, 0 / 1 never, n > 1: n workgroups share the batch-reduce range of one f32 output tile; returns the previous setting"""
         return self.lib.xsmm_hip_force_split(workgroups_per_tile)
+
+    def set_tail_split(self, mode):
+        """f32 whole-layer calls with a partial last round of workgroups: 0 off (default), 1 the model, 2 .. 16 that many workgroups per
+        tail tile; returns the previous setting, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_tail_split(mode)
+
+    def tail_split_stats(self):
+        """(launches with a split tail; tail tiles, workgroups per tail tile, body tiles of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_tail_split_stats(out)
+        return tuple(int(v) for v in out)
 
     def set_fold_transpose(self, enable):
         """transposes that feed a gemm's B operand folded into the gemm (default on); returns the previous setting"""
