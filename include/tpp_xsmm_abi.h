@@ -302,6 +302,14 @@ TPP_XSMM_EXPORT const char *xsmm_hip_last_grouped_kernel(void);
  * batch-reduce range of a tile split over several workgroups (xsmm_hip_force_split), small bf16 outputs with K >= 1536 on the 32x64
  * loader-wave tile. "" = the kernel xsmm_hip_kernel_name(handle) names ran. For tests, tools and profiles. */
 TPP_XSMM_EXPORT const char *xsmm_hip_last_refined_kernel(void);
+/* The kernel instance the most recent NON-queued unary / binary invoke launched, and that launch's total number of workgroups: which of
+ * the 16-byte and the element paths a shape / stride / alignment reached ("unary_kernel<f32,v4>", "unary_kernel<bf16,v1>",
+ * "binary_kernel<bf16,v8>"; ", flat" appended when contiguous operands ran as one long row), which transpose ("transpose_vec<f32,128x128>",
+ * "transpose_vec<bf16,64x64>", "transpose<f32>") and which VNNI-2 pack ("vnni2_rows4<wt>", "vnni2_rows4<plain>", "vnni2<v8>", "vnni2<v1>").
+ * "" / 0 before the first. The grouped launches of the tile queue do not report here, and a transpose that xsmm_hip_set_fold_transpose
+ * deferred has not launched yet. Static strings; for tests, tools and profiles. */
+TPP_XSMM_EXPORT const char *xsmm_hip_last_eltwise_kernel(void);
+TPP_XSMM_EXPORT int64_t xsmm_hip_last_eltwise_grid(void);
 /* Force a GEMM tile variant for A/B benchmarking and tests (-1 = automatic): f32 0..4 (64x64,
  * 64x32+K2, 32x32+K4, 128x64, 64x64+K2), 5..7 the loader-wave kernels (64x64, 64x64+K2, 64x32+K4), 8 generic, 9 / 10 loader-wave 32x32+K4 / 128x64, bf16 16 / 17 / 18 / 19 (64x64, 128x128, 256x256, 32x32 + K split),
  * 20 .. 23 the bf16 loader-wave tiles for mid-size outputs (32x64 + K split, 64x64, 64x128, 128x128).

@@ -66,7 +66,11 @@ template <typename T, int VEC> __device__ __forceinline__ Pack<T, VEC> load_stre
 template <typename T, int VEC> __device__ __forceinline__ void store_wt(T *p, const Pack<T, VEC> &v) {
   static_assert(sizeof(Pack<T, VEC>) == 16, "16-byte packs");
   const u32x4_e x = __builtin_bit_cast(u32x4_e, v);
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(x) : "memory");
+  // (the s_nop 1 belongs to the store: the compiler sees one opaque statement, not a 16-byte store, so it does not keep its own next
+  // VALU instruction off the data registers for the two wait states the store needs to read them. binary_kernel's body reused the
+  // first two data registers for the loop index one SALU instruction behind the store, and packs came out with the index in their
+  // first 8 bytes - only where the four-round body runs, above 12.6 M packs: tests/test_eltwise_paths_gpu.py)
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
 }
 template <typename T, int VEC, bool WT = false> __device__ __forceinline__ void store_stream(T *p, const Pack<T, VEC> &v) {
   if constexpr (sizeof(Pack<T, VEC>) == 16 && WT) store_wt<T, VEC>(p, v);
@@ -224,33 +228,11 @@ __global__ __launch_bounds__(256) void vnni2_kernel(int64_t m, int64_t n, int64_
   }
 }
 
-// Row-pair variant of the 16-byte path for matrices whose row pairs fit the grid's y dimension (every shape the
-// reference packs: weights of a layer): blockIdx.y = row pair, 256 lanes x 8 columns per block along x. No
-// grid-stride loop and no 64-bit division - at the C5 size (2048^2 bf16, 16 MiB moved in ~3 us) the kernel is a
-// single wave of blocks and the address arithmetic of the generic loop was a measurable part of it.
-__global__ __launch_bounds__(256) void vnni2_rows_kernel(int n8, int64_t ldi, int64_t ldo,
-                                                         const unsigned short *__restrict__ in,
-                                                         unsigned short *__restrict__ out) {
-  const int c = blockIdx.x * 256 + threadIdx.x; // 8-column piece
-  if (c >= n8) return;
-  const int64_t r = blockIdx.y;
-  const u32x4_e e = *(const u32x4_e *)(in + (2 * r) * ldi + 8 * (int64_t)c);
-  const u32x4_e o = *(const u32x4_e *)(in + (2 * r + 1) * ldi + 8 * (int64_t)c);
-  u32x4_e w0, w1; // dword q of the output = (even row element q, odd row element q)
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    w0[2 * q] = (e[q] & 0xffffu) | (o[q] << 16);
-    w0[2 * q + 1] = (e[q] >> 16) | (o[q] & 0xffff0000u);
-    w1[2 * q] = (e[q + 2] & 0xffffu) | (o[q + 2] << 16);
-    w1[2 * q + 1] = (e[q + 2] >> 16) | (o[q + 2] & 0xffff0000u);
-  }
-  u32x4_e *dst = (u32x4_e *)(out + r * (2 * ldo) + 16 * (int64_t)c);
-  dst[0] = w0;
-  dst[1] = w1;
-}
-
-// The same with ONE 16-byte output piece per lane (4 columns x 2 rows): two 8-byte loads, one 16-byte store - a wave's store
-// instruction writes 1 KiB of whole lines (the 8-column variant's two stores per lane each write half of every line), and twice as
+// Row-pair variant of the 16-byte path for matrices whose row pairs fit the grid's y dimension (every shape the reference packs:
+// weights of a layer): blockIdx.y = row pair, 256 lanes along x. No grid-stride loop and no 64-bit division - at the C5 size (2048^2
+// bf16, 16 MiB moved in ~3 us) the kernel is a single wave of blocks and the address arithmetic of the generic loop was a measurable
+// part of it. ONE 16-byte output piece per lane (4 columns x 2 rows): two 8-byte loads, one 16-byte store - a wave's store
+// instruction writes 1 KiB of whole lines (with 8 columns per lane, two stores per lane each write half of every line), and twice as
 // many lanes are in flight for the one round trip the kernel consists of.
 typedef unsigned int u32x2_e __attribute__((ext_vector_type(2)));
 template <int POLICY> // 0 plain, 2 nontemporal loads + write-through (sc1) stores
@@ -268,7 +250,7 @@ __global__ __launch_bounds__(256) void vnni2_rows4_kernel(int n4, int64_t ldi, i
   w[2] = (e[1] & 0xffffu) | (o[1] << 16);
   w[3] = (e[1] >> 16) | (o[1] & 0xffff0000u);
   u32x4_e *dst = (u32x4_e *)(out + r * (2 * ldo) + 8 * (int64_t)c);
-  if (POLICY == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(w) : "memory");
+  if (POLICY == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(w) : "memory"); // (s_nop: see store_wt)
   else *dst = w;
 }
 
@@ -408,6 +390,12 @@ static inline int grid_for(int64_t total) {
 }
 static inline bool aligned(const void *p, size_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
 
+// kernel instance and block count of this launch, for xsmm_hip_last_eltwise_kernel / _grid (xsmm_desc.h). Static strings.
+static inline void note_eltwise(const char *name, int64_t blocks) {
+  g_last_eltwise.store(name, std::memory_order_relaxed);
+  g_last_eltwise_grid.store(blocks, std::memory_order_relaxed);
+}
+
 // Vector variant for aligned full tiles: 16 bytes per lane on BOTH global sides. A 64x64 tile is
 // read with 16-byte row pieces into LDS (row pitch 64+PAD elements), then every lane gathers
 // VEC elements of one input column (VEC small LDS reads) and stores them as 16 contiguous bytes
@@ -469,6 +457,7 @@ static hipError_t launch_unary_t(const UnaryDesc &d, const void *in, float scala
     if (hipError_t e_ = ensure_dynamic_lds((const void *)transpose_vec_kernel<T, R, C>, lds_, set_); e_ != hipSuccess) return e_; \
     hipLaunchKernelGGL((transpose_vec_kernel<T, R, C>), dim3((unsigned)((d.m / (R)) * (d.n / (C)))), dim3(256), lds_, s, d.m, d.n, d.ldi, \
                        d.ldo, (const T *)in, (T *)out);                                                                   \
+    note_eltwise(sizeof(T) == 4 ? "transpose_vec<f32," #R "x" #C ">" : "transpose_vec<bf16," #R "x" #C ">", (d.m / (R)) * (d.n / (C))); \
   } while (0)
     // 128 x 128 tiles when the shape allows (f32: 512-byte row pieces on both sides, 64.5 KiB of LDS, two workgroups per CU - 8192^2
     // 4.9 -> 5.4 TB/s, 16384^2 5.2 -> 5.4 against 64 x 64; 64 x 128 / 128 x 64 landed in between; bf16 tiles of 256 x 128, 128 x 256
@@ -476,9 +465,11 @@ static hipError_t launch_unary_t(const UnaryDesc &d, const void *in, float scala
     if (vec_ok && d.m % 128 == 0 && d.n % 128 == 0) TPP_TRANSPOSE_LAUNCH(128, 128);
     else if (vec_ok && d.m % 64 == 0 && d.n % 64 == 0) TPP_TRANSPOSE_LAUNCH(64, 64);
 #undef TPP_TRANSPOSE_LAUNCH
-    else
+    else {
       hipLaunchKernelGGL((transpose_kernel<T>), dim3((unsigned)tiles), dim3(256), 0, s, d.m, d.n, d.ldi, d.ldo,
                          (const T *)in, (T *)out);
+      note_eltwise(sizeof(T) == 4 ? "transpose<f32>" : "transpose<bf16>", tiles);
+    }
     return hipGetLastError();
   }
   const bool reads = op != (int)U_ZERO && !use_scalar;
@@ -490,9 +481,14 @@ static hipError_t launch_unary_t(const UnaryDesc &d, const void *in, float scala
     const int64_t m_ = flat ? 1 : d.m, n_ = flat ? d.m * d.n : d.n;
     hipLaunchKernelGGL((unary_kernel<T, V>), dim3(grid_for(d.m * (d.n / V))), dim3(256), 0, s, op, bc, m_, n_,
                        flat ? n_ : d.ldi, flat ? n_ : d.ldo, (const T *)in, (T *)out, scalar, (int)use_scalar);
-  } else
+    note_eltwise(sizeof(T) == 4 ? (flat ? "unary_kernel<f32,v4>, flat" : "unary_kernel<f32,v4>")
+                                : (flat ? "unary_kernel<bf16,v8>, flat" : "unary_kernel<bf16,v8>"),
+                 grid_for(d.m * (d.n / V)));
+  } else {
     hipLaunchKernelGGL((unary_kernel<T, 1>), dim3(grid_for(d.m * d.n)), dim3(256), 0, s, op, bc, d.m, d.n, d.ldi,
                        d.ldo, (const T *)in, (T *)out, scalar, (int)use_scalar);
+    note_eltwise(sizeof(T) == 4 ? "unary_kernel<f32,v1>" : "unary_kernel<bf16,v1>", grid_for(d.m * d.n));
+  }
   return hipGetLastError();
 }
 
@@ -506,18 +502,19 @@ hipError_t launch_unary(const UnaryDesc &d, const void *in, float scalar, bool u
       // stores win up to 4096^2 (64 MiB moved: 10.5 -> 9.7 us) and lose beyond (8192^2: 37.4 -> 38.7 us); nontemporal STORES lose
       // everywhere (-6 .. -11 %).
       const dim3 g((unsigned)((d.n / 4 + 255) / 256), (unsigned)(d.m / 2));
-      if ((double)d.m * (double)d.n * 4.0 <= 64.0 * 1024 * 1024) hipLaunchKernelGGL(vnni2_rows4_kernel<2>, g, dim3(256), 0, s, (int)(d.n / 4), d.ldi, d.ldo, (const unsigned short *)in, (unsigned short *)out);
+      const bool wt = (double)d.m * (double)d.n * 4.0 <= 64.0 * 1024 * 1024;
+      if (wt) hipLaunchKernelGGL(vnni2_rows4_kernel<2>, g, dim3(256), 0, s, (int)(d.n / 4), d.ldi, d.ldo, (const unsigned short *)in, (unsigned short *)out);
       else hipLaunchKernelGGL(vnni2_rows4_kernel<0>, g, dim3(256), 0, s, (int)(d.n / 4), d.ldi, d.ldo, (const unsigned short *)in, (unsigned short *)out);
-    }
-    else if (vec && d.m / 2 <= 65535 && d.n / 8 < (1 << 30))
-      hipLaunchKernelGGL(vnni2_rows_kernel, dim3((unsigned)((d.n / 8 + 255) / 256), (unsigned)(d.m / 2)), dim3(256), 0, s,
-                         (int)(d.n / 8), d.ldi, d.ldo, (const unsigned short *)in, (unsigned short *)out);
-    else if (vec)
+      note_eltwise(wt ? "vnni2_rows4<wt>" : "vnni2_rows4<plain>", (int64_t)g.x * g.y);
+    } else if (vec) {
       hipLaunchKernelGGL((vnni2_kernel<8>), dim3(grid_for((d.m / 2) * (d.n / 8))), dim3(256), 0, s, d.m, d.n, d.ldi,
                          d.ldo, (const unsigned short *)in, (unsigned short *)out);
-    else
+      note_eltwise("vnni2<v8>", grid_for((d.m / 2) * (d.n / 8)));
+    } else {
       hipLaunchKernelGGL((vnni2_kernel<1>), dim3(grid_for((d.m / 2) * d.n)), dim3(256), 0, s, d.m, d.n, d.ldi, d.ldo,
                          (const unsigned short *)in, (unsigned short *)out);
+      note_eltwise("vnni2<v1>", grid_for((d.m / 2) * d.n));
+    }
     return hipGetLastError();
   }
   if (d.dtype == DT_F32) return launch_unary_t<float>(d, in, scalar, use_scalar, out, s);
@@ -542,9 +539,14 @@ static hipError_t launch_binary_t(const BinaryDesc &d, const void *lhs, const vo
     const int64_t m_ = flat ? 1 : d.m, n_ = flat ? d.m * d.n : d.n;
     hipLaunchKernelGGL((binary_kernel<T, V>), dim3(grid_for(d.m * (d.n / V))), dim3(256), 0, s, (int)d.op, bc0, bc1,
                        m_, n_, flat ? n_ : d.ldi_lhs, flat ? n_ : d.ldi_rhs, flat ? n_ : d.ldo, (const T *)lhs, (const T *)rhs, (T *)out);
-  } else
+    note_eltwise(sizeof(T) == 4 ? (flat ? "binary_kernel<f32,v4>, flat" : "binary_kernel<f32,v4>")
+                                : (flat ? "binary_kernel<bf16,v8>, flat" : "binary_kernel<bf16,v8>"),
+                 grid_for(d.m * (d.n / V)));
+  } else {
     hipLaunchKernelGGL((binary_kernel<T, 1>), dim3(grid_for(d.m * d.n)), dim3(256), 0, s, (int)d.op, bc0, bc1, d.m,
                        d.n, d.ldi_lhs, d.ldi_rhs, d.ldo, (const T *)lhs, (const T *)rhs, (T *)out);
+    note_eltwise(sizeof(T) == 4 ? "binary_kernel<f32,v1>" : "binary_kernel<bf16,v1>", grid_for(d.m * d.n));
+  }
   return hipGetLastError();
 }
 

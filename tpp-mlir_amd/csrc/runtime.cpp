@@ -457,6 +457,8 @@ extern "C" const char *xsmm_hip_last_grouped_kernel(void) {
   return m ? m : last_grouped_kernel();
 }
 extern "C" const char *xsmm_hip_last_refined_kernel(void) { return last_refined_kernel(); }
+extern "C" const char *xsmm_hip_last_eltwise_kernel(void) { return g_last_eltwise.load(std::memory_order_relaxed); }
+extern "C" int64_t xsmm_hip_last_eltwise_grid(void) { return g_last_eltwise_grid.load(std::memory_order_relaxed); }
 extern "C" void xsmm_hip_force_variant(int v) { cfg().forced_variant.store(v); }
 // strict mode (see Config::strict). Meant to be chosen before the first invoke (TPP_HIP_STRICT=1): groups recorded by the tile queue's
 // trace cache under the other setting would replay on the kernel they were recorded for - a change after the queue has recorded

@@ -156,6 +156,13 @@ hipError_t launch_unary(const UnaryDesc &d, const void *in, float scalar, bool u
                         hipStream_t stream);
 hipError_t launch_binary(const BinaryDesc &d, const void *lhs, const void *rhs, void *out,
                          hipStream_t stream);
+// most recent launch_unary / launch_binary: the kernel instance it ran (a static string such as "unary_kernel<f32,v4>, flat",
+// "transpose_vec<bf16,128x128>", "vnni2_rows4<wt>"; "" before the first) and the launch's total block count
+// (xsmm_hip_last_eltwise_kernel / _grid: tests assert which path a shape reached and derive every block's span from the grid; the
+// grouped kernels of the tile queue do not report). Inline variables like g_tail_split above: eltwise.hip stores, runtime.cpp reads,
+// and the host-only builds of runtime.cpp (tests/tsan) link without any kernel file. Relaxed accesses, as last_refined_kernel.
+inline std::atomic<const char *> g_last_eltwise{""};
+inline std::atomic<int64_t> g_last_eltwise_grid{0};
 // n_items invokes of ONE unary / binary descriptor with m, n <= 64 in one launch
 hipError_t launch_unary_grouped(const UnaryDesc &d, const WorkItem *items, int n_items, hipStream_t stream);
 hipError_t launch_binary_grouped(const BinaryDesc &d, const WorkItem *items, int n_items, hipStream_t stream);

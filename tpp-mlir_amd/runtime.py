@@ -107,6 +107,8 @@ _SIGNATURES = {
     "xsmm_hip_kernel_name": (ctypes.c_char_p, [I64]),
     "xsmm_hip_last_grouped_kernel": (ctypes.c_char_p, []),
     "xsmm_hip_last_refined_kernel": (ctypes.c_char_p, []),
+    "xsmm_hip_last_eltwise_kernel": (ctypes.c_char_p, []),
+    "xsmm_hip_last_eltwise_grid": (I64, []),
     "xsmm_hip_force_variant": (None, [ctypes.c_int]),
     "xsmm_hip_force_split": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_set_tail_split": (ctypes.c_int, [ctypes.c_int]),
@@ -317,6 +319,14 @@ class XsmmRuntime:
     def last_refined_kernel(self):
         """the kernel an invoke-time refinement chose for the most recent non-queued GEMM invoke, "" = the handle's own kernel"""
         return self.lib.xsmm_hip_last_refined_kernel().decode()
+
+    def last_eltwise_kernel(self):
+        """the kernel instance of the most recent non-queued unary / binary invoke, e.g. "unary_kernel<f32,v4>, flat" ("" before the first)"""
+        return self.lib.xsmm_hip_last_eltwise_kernel().decode()
+
+    def last_eltwise_grid(self):
+        """total workgroups of that launch"""
+        return int(self.lib.xsmm_hip_last_eltwise_grid())
 
     def force_variant(self, v):
         self.lib.xsmm_hip_force_variant(v)
