@@ -23,8 +23,7 @@
 //     the four groups' rows are 64 bytes apart = four different bank quarters (rows 4 g + s would all share one: 4-way conflicts).
 // One workgroup = 4 + RB + CB waves, 16 (RB + CB) KiB of LDS. GROUPED: tile-queue groups (grid (items, n / 16, m / 32)); k = 32 tiles with even batch
 // counts build a chunk from two batch elements like brgemm_f32_lw's pair mode.
-#include "gemm_common.h"
-#include "xsmm_desc.h"
+#include "brgemm_f32_lw_tile.h"
 #include <type_traits>
 
 namespace tpp {
@@ -107,19 +106,9 @@ __global__ __launch_bounds__(64 * (4 + RB + CB)) void brgemm_f32_lw16(GemmArgs p
     };
     auto wait_left = [&](int chunks) __attribute__((always_inline)) { // this wave's DMA of all but the `chunks` youngest chunks has landed (4 instructions per chunk)
       if (chunks == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if (chunks == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); // (the schedule asks for 0 or 1)
     };
-    if (T > 0) issue(0);
-    if (T > 1) issue(1);
-    wait_left(T > 1 ? 1 : 0);
-    __builtin_amdgcn_s_barrier(); // chunk 0 published
-    if (T > 2) issue(2);
-    for (int t = 0; t + 1 < T; ++t) {
-      wait_left(t + 2 < T ? 1 : 0); // chunk t + 1 has landed (chunk t + 2 may still fly)
-      __builtin_amdgcn_s_barrier();  // = the MFMA waves' mid-chunk barrier of chunk t: publishes t + 1, retires the slot of t - 1
-      if (t + 3 < T) issue((t + 3) % L16_NSLOT);
-    }
+    lw_loader_schedule<L16_NSLOT>(T, issue, wait_left); // (brgemm_f32_lw_tile.h: chunk 0 published first, then one barrier per chunk)
     return; // ended waves do not take part in later barriers
   }
 

@@ -1,0 +1,267 @@
+// brgemm_f32_lw_tile.h - the f32 loader-wave tile, written once: brgemm_f32_lw (one layer) and brgemm_f32_lw_chain (the layers of a
+// step in one launch) in brgemm_f32_lw.hip are built from these pieces, which is what makes the chain's results the separate
+// launches' bits - the same LDS images, the same schedule, the same order of additions. brgemm_f32_lw16.hip shares the loader schedule.
+// (The structure and why it is as it is: the head of brgemm_f32_lw.hip.)
+#pragma once
+#include "gemm_common.h"
+#include "xsmm_desc.h"
+#include <type_traits>
+
+namespace tpp {
+
+constexpr int LW_BK = 64;   // k per chunk
+constexpr int LW_NSLOT = 4; // LDS ring slots
+constexpr int LW_C_AUX = C_STORE_AUX; // write-through C stores (gemm_common.h)
+
+typedef __attribute__((address_space(3))) void lds_void_lw;
+// The ring = the launch's dynamic LDS; the K-group combine parks its partials in it. Named here and used by the pieces directly: handed
+// to them as a pointer argument the compiler kept one address register per (slot, k-block) where it now folds the slot offsets into
+// the ds_read immediates - 8 VGPRs more on the 64x64 tile (80 -> 88, one wave per SIMD less in the compiler's resource report).
+extern __shared__ __attribute__((aligned(16))) float smem_lw[];
+
+// The loader waves' schedule: issue(slot) requests the next chunk of the wave's panel into a ring slot, wait_left(n) returns when
+// all but the n youngest chunks of the wave's own DMA have landed.
+// Prologue: chunks 0 and 1 are requested, chunk 0 is PUBLISHED as soon as it has landed, chunk 2 follows behind the barrier.
+// (Round 2 requested all three first: an LDS-DMA instruction takes ~25 ns to issue, a chunk is 16 of them per loader - the MFMA
+// waves waited ~0.4 us for requests they would not need for two chunk times; a chunk is 0.92 us of MFMA here, so the loader has
+// all the time it needs behind the barrier. Stamped on the bf16 twin of this kernel: profiles/r03_chain_anatomy.txt.)
+template <int NSLOT, class Issue, class Wait> __device__ __forceinline__ void lw_loader_schedule(int T, Issue &&issue, Wait &&wait_left) {
+  if (T > 0) issue(0);
+  if (T > 1) issue(1);
+  wait_left(T > 1 ? 1 : 0);
+  __builtin_amdgcn_s_barrier(); // chunk 0 published
+  if (NSLOT > 3 && T > 2) issue(2); // (a 3-slot ring holds chunks t, t+1, t+2: nothing more before chunk 0 has been retired)
+  for (int t = 0; t + 1 < T; ++t) {
+    wait_left(NSLOT > 3 && t + 2 < T ? 1 : 0); // chunk t+1 has landed (4 slots: chunk t+2 may still fly)
+    __builtin_amdgcn_s_barrier();               // = the MFMA waves' mid-chunk barrier of chunk t
+    if (t + NSLOT - 1 < T) issue((t + NSLOT - 1) % NSLOT); // the slot of chunk t-1: every MFMA wave is past it
+  }
+}
+
+// The tile of WM x WN MFMA waves (each ONE 32x32 accumulator) x WK wave groups that split every 64-k chunk, on an NSLOT-deep ring.
+// NSLOT: 4; 3 for the 128x64 tile, whose 48 KiB slots would not fit four times.
+template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
+  static constexpr int NMW = WM * WN * WK; // MFMA waves
+  static constexpr int BM = 32 * WM, BN = 32 * WN;
+  static constexpr int A_STAGE = BM * LW_BK, B_STAGE = LW_BK * BN, SLOT = A_STAGE + B_STAGE; // floats
+  static constexpr int NA = BM / 4;      // DMA instructions (1 KiB each) per chunk of A: 4 rows x 64 k
+  static constexpr int RPI = 256 / BN;   // B rows per DMA instruction
+  static constexpr int NB = LW_BK / RPI; // DMA instructions per chunk of B
+  static constexpr int KB_PER_WAVE = 8 / WK, KB_HALF = KB_PER_WAVE / 2;
+  static constexpr int IPG = WK > 1 ? 4 / WK : 1; // K-split tiles: 16-byte store instructions per lane per group
+  static constexpr size_t LDS_BYTES = (size_t)NSLOT * SLOT * sizeof(float);
+  static_assert(KB_HALF >= 1, "tile outside the schedule's limits");
+  static_assert(NSLOT == 3 || NSLOT == 4, "ring depth");
+  static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+
+  // ---- loader waves: NL for the A panel, NLB for the B panel; wave `part` of a panel issues the instructions part, part + NL, ... ----
+  template <int NL, int NLB> struct Loader {
+    static_assert(NA % NL == 0 && NB % NLB == 0, "panel instructions divide over the loader waves");
+    static_assert(NA / NL <= 31 && NB / NLB <= 31, "tile outside the schedule's limits (vmcnt is 6 bits)");
+    bool isA;
+    int part, kc, kchunks;
+    unsigned voA[4], voA2[2], voB, stepA, stepB, pairB;
+    const float *g; // panel base of the chunk being fetched
+    int64_t d_in, d_batch, d_wrap;
+
+    // lw: loader wave 0 .. NL + NLB - 1 (the A loaders first). pair: a 64-k chunk is the 32-k blocks of TWO consecutive batch
+    // elements (brgemm_f32_lw, GROUPED). nvalid: columns of the tile that exist (a multiple of 4; >= BN: all).
+    __device__ __forceinline__ Loader(int lw, int lane, const float *A, const float *B, int m0, int n0, int lda, int ldb, int64_t stride_a,
+                                      int64_t stride_b, int kchunks_, bool pair, int nvalid)
+        : isA(lw < NL), part(lw < NL ? lw : lw - NL), kc(0), kchunks(kchunks_) {
+      // per-lane source offsets, constant for the whole panel stream. A instruction v covers rows 4v .. 4v+3
+      // (lane -> row 4v + lane/16, 16-byte piece lane%16, XOR-ed with row&15 = 4(v&3) + lane/16: the
+      // fragment read applies the same XOR); the 16-row group v>>2 goes into the scalar offset.
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = 4 * j + (lane >> 4), pc = (lane & 15) ^ r; // 16-byte piece of the chunk's row: k 4 pc .. 4 pc + 3
+        voA[j] = (unsigned)((r * lda + (pair ? (pc >> 3) * (int)stride_a + 4 * (pc & 7) : 4 * pc)) * 4);
+      }
+      // NL = 2: this wave's instructions have v & 3 = part and part + 2 (NL = 4: always part)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int r = 4 * (part + 2 * j) + (lane >> 4), pc = (lane & 15) ^ r;
+        voA2[j] = (unsigned)((r * lda + (pair ? (pc >> 3) * (int)stride_a + 4 * (pc & 7) : 4 * pc)) * 4);
+      }
+      // (a ragged last tile: the 16-byte column pieces beyond n re-read the tile's last valid piece - in bounds, and the columns
+      // they feed are never stored)
+      const int pieceB = nvalid < BN ? (lane % (BN / 4) < nvalid / 4 ? lane % (BN / 4) : nvalid / 4 - 1) : lane % (BN / 4);
+      voB = (unsigned)(((lane / (BN / 4)) * ldb + 4 * pieceB) * 4);
+      stepA = (unsigned)(16 * lda * 4), stepB = (unsigned)(RPI * ldb * 4);
+      pairB = pair ? (unsigned)(((int)stride_b - 32 * ldb) * 4) : 0u; // rows 32.. of a pair chunk: the second element
+      g = isA ? A + (int64_t)m0 * lda : B + n0;
+      d_in = isA ? (int64_t)LW_BK : (int64_t)LW_BK * ldb;
+      d_batch = (isA ? stride_a : stride_b) * (pair ? 2 : 1);
+      d_wrap = d_batch - (int64_t)(kchunks - 1) * d_in;
+    }
+    // start at chunk t_first: batch element t_first / kchunks (pair mode: the pair t_first), k block t_first % kchunks
+    __device__ __forceinline__ void start_at(int t_first) {
+      const int b0 = t_first / kchunks;
+      kc = t_first - b0 * kchunks;
+      g += (int64_t)b0 * d_batch + (int64_t)kc * d_in;
+    }
+    template <int AUX> __device__ __forceinline__ void load_a(float *base, __amdgpu_buffer_rsrc_t r) const {
+#pragma unroll
+      for (int i = 0; i < NA / NL; ++i) {
+        const int v = part + NL * i; // (NL = 2: v & 3 is part or part + 2 - both live in voA2)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_lw *)(base + v * 256), 16, NL == 1 ? voA[i & 3] : NL == 2 ? voA2[i & 1] : voA2[0],
+                                                 (unsigned)(v >> 2) * stepA, 0, AUX);
+      }
+    }
+    // request the next chunk of this wave's panel into ring slot `slot`. sc1 (MAY_SC1 instances only): the A rows were written by
+    // other workgroups of THIS launch, another XCD's L2 may hold them - the aux bits stay a compile-time constant of each load.
+    template <bool MAY_SC1 = false> __device__ __forceinline__ void issue(int slot, bool sc1 = false) {
+      float *base = smem_lw + slot * SLOT + (isA ? 0 : A_STAGE);
+      const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)g, 0, 0x7fffffff, 0x00020000);
+      if (isA) {
+        if (MAY_SC1 && sc1) load_a<16>(base, r);
+        else load_a<0>(base, r);
+      } else {
+#pragma unroll
+        for (int i = 0; i < NB / NLB; ++i) {
+          const int v = part + NLB * i;
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_lw *)(base + v * 256), 16, voB, (unsigned)v * stepB + (v * RPI >= 32 ? pairB : 0u), 0, 0);
+        }
+      }
+      if (++kc == kchunks) {
+        kc = 0;
+        g += d_wrap;
+      } else {
+        g += d_in;
+      }
+    }
+    // s_waitcnt vmcnt(n chunks of this wave's DMA may still be in flight), n = 0 or 1
+    __device__ __forceinline__ void wait_left(int chunks) const {
+      if (chunks == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      else if (isA) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NA / NL) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB / NLB) : "memory");
+    }
+  };
+
+  // ---- MFMA waves ----------------------------------------------------------------------------------------------------------
+  struct Wave { // role index wave = 0 .. NMW-1 -> K group wk, 32x32 block (wm, wn) = wmn of the tile
+    int wk, wmn, wm, wn, lane;
+    __device__ __forceinline__ Wave(int wave, int lane_) : wk(wave / (WM * WN)), wmn(wave % (WM * WN)), wm(wmn / WN), wn(wmn % WN), lane(lane_) {}
+  };
+
+  // The T > 0 chunks of one tile, from the "chunk 0 published" barrier (the caller's) to the last MFMA: one loop body per ring slot
+  // (slot offsets are immediates), ONE raw s_barrier per chunk in the middle of the chunk's MFMAs, no vector memory instruction.
+  static __device__ __forceinline__ void mfma_chunks(f32x16 &acc, int T, const Wave &w) {
+    // MFMA fragments of one k-block (8 k): 4 A values (one ds_read_b128) and 4 B values per lane;
+    // double-buffered so block q+1 is read while block q multiplies (brgemm_f32.hip has the layout notes)
+    f32x4 fa[2];
+    float fb[2][4];
+    const int li = w.lane & 31, lh = w.lane >> 5;
+    const int a_off = (w.wm * 32 + li) * LW_BK, b_off = w.wn * 32 + li;
+    auto frag_load = [&](int buf, int slot, int kb) __attribute__((always_inline)) {
+      const float *as = smem_lw + slot * SLOT + a_off;
+      const float *bs = smem_lw + slot * SLOT + A_STAGE + b_off;
+      fa[buf] = *(const f32x4 *)(as + (((2 * kb + lh) ^ (li & 15)) << 2));
+#pragma unroll
+      for (int s = 0; s < 4; ++s) fb[buf][s] = bs[(8 * kb + 4 * lh + s) * BN];
+    };
+    const int kbw = w.wk * KB_PER_WAVE;
+    // hn_c: does another chunk follow (= does this chunk carry the barrier)? 1: yes, a compile-time fact - the steady-state lap below
+    // is then ONE basic block (a conditional barrier or an exit test between two chunks is a block boundary: a branch, and a point
+    // where the compiler waits for every LDS read in flight); 2: decided at run time (the last lap)
+    auto chunk = [&](auto slot_c, auto hn_c, bool has_next_rt) __attribute__((always_inline)) {
+      constexpr int S = decltype(slot_c)::value, NS = (S + 1) % NSLOT;
+      const bool has_next = decltype(hn_c)::value == 1 ? true : has_next_rt;
+#pragma unroll
+      for (int q = 0; q < KB_PER_WAVE; ++q) {
+        const int cur = q & 1, nxt = cur ^ 1;
+        if (q + 1 < KB_PER_WAVE) frag_load(nxt, S, kbw + q + 1);
+        else frag_load(nxt, NS, kbw); // first block of chunk t+1 (published by this chunk's barrier; unused after the last chunk)
+        __builtin_amdgcn_sched_barrier(0); // the reads of step q+1 stay above the MFMAs of step q
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][s], fb[cur][s], acc, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (q == KB_HALF - 1 && has_next) {
+          __builtin_amdgcn_s_barrier(); // chunk t+1 published by the loaders; the slot of chunk t-1 retired
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      // the prefetched fragments of chunk t+1 are dead on the loop's exit path: without this the compiler sinks
+      // their reads into the next chunk's head, where the first MFMA then waits for them (the wait this
+      // implies sits behind the last step's four MFMAs: the reads are long back)
+      // (not inside the steady-state laps: there the next chunk follows in the same basic block, the sched_barriers keep the order,
+      // and the pin would only make the compiler wait for the prefetched fragments at the end of every chunk)
+      constexpr int PF = KB_PER_WAVE & 1;
+      if constexpr (decltype(hn_c)::value != 1)
+        asm volatile("" : "+v"(fa[PF]), "+v"(fb[PF][0]), "+v"(fb[PF][1]), "+v"(fb[PF][2]), "+v"(fb[PF][3]));
+    };
+    using S0 = std::integral_constant<int, 0>;
+    using S1 = std::integral_constant<int, 1>;
+    using S2 = std::integral_constant<int, 2>;
+    using S3 = std::integral_constant<int, 3>;
+    using HY = std::integral_constant<int, 1>;
+    using HR = std::integral_constant<int, 2>;
+
+    frag_load(0, 0, kbw);
+    int t = 0;
+    for (; t + NSLOT < T; t += NSLOT) { // whole laps of the ring that are followed by at least one more chunk
+      chunk(S0{}, HY{}, true);
+      chunk(S1{}, HY{}, true);
+      chunk(S2{}, HY{}, true);
+      if constexpr (NSLOT > 3) chunk(S3{}, HY{}, true);
+    }
+    for (;;) { // the last lap: 1 .. NSLOT chunks
+      chunk(S0{}, HR{}, t + 1 < T);
+      if (++t == T) break;
+      chunk(S1{}, HR{}, t + 1 < T);
+      if (++t == T) break;
+      chunk(S2{}, HR{}, t + 1 < T);
+      if (++t == T) break;
+      if constexpr (NSLOT > 3) {
+        chunk(S3{}, HR{}, t + 1 < T);
+        if (++t == T) break;
+      }
+    }
+  }
+
+  // ---- K-split tiles (WK > 1): combine the K groups through LDS and finish ----------------------------------------------------
+  // EVERY group parks its 32x32 partial, then group g finishes the accumulator registers [g * 16 / WK, (g + 1) * 16 / WK) of its
+  // tile - sum in group order (group 0 carries C when beta = 1), bias, relu, store. (With group 0 finishing alone the other
+  // groups' waves idled through 16 LDS reads + 16 stores per lane.) Two workgroup barriers: the ring is free, the partials are there.
+  static __device__ __forceinline__ void park_partials(const f32x16 &acc, const Wave &w) {
+    __syncthreads();
+    float *dst = smem_lw + (w.wk * (WM * WN) + w.wmn) * 1024 + w.lane; // WK * WM*WN * 1024 floats, fits in the ring
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dst[r * 64] = acc[r];
+    __syncthreads();
+  }
+  // The parked partials are [register r][lane = column li + 32 * lh]: four consecutive columns of one output row (r, lh) are
+  // 16 contiguous bytes. A lane finishes float4 pieces - 8 lanes x 16 B = one 128-byte row of the tile, a wave instruction 8
+  // rows - so a tile is 4 x 16-byte stores per lane split over the K groups, instead of 16 dword stores (round 2).
+  // Piece j of a lane: 16-byte column piece lane & 7 of row piece_row of the wave's 32x32 block.
+  static __device__ __forceinline__ int piece_row(const Wave &w, int j) { return 8 * (w.wk * IPG + j) + (w.lane >> 3); }
+  static __device__ __forceinline__ unsigned piece_off(const Wave &w, int j, int ldc) { // bytes from the tile's first element of C
+    return (unsigned)(((w.wm * 32 + piece_row(w, j)) * ldc + w.wn * 32 + 4 * (w.lane & 7)) * 4);
+  }
+  static __device__ __forceinline__ void sum_partials(f32x4 (&part)[IPG], const Wave &w) {
+#pragma unroll
+    for (int j = 0; j < IPG; ++j) {
+      const int q = piece_row(w, j); // row of the 32x32 tile: q = (r & 3) + 4 * lh + 8 * (r >> 2)
+      const int r = (q & 3) + 4 * (q >> 3), lh2 = (q >> 2) & 1;
+      const float *src = smem_lw + w.wmn * 1024 + r * 64 + lh2 * 32 + 4 * (w.lane & 7);
+      f32x4 v = *(const f32x4 *)src;
+#pragma unroll
+      for (int g = 1; g < WK; ++g) v += *(const f32x4 *)(src + g * (WM * WN) * 1024);
+      part[j] = v;
+    }
+  }
+  // bias, relu, 16-byte write-through stores (ok: this lane's column piece exists)
+  static __device__ __forceinline__ void finish(const f32x4 (&part)[IPG], f32x4 bias4, int ep, __amdgpu_buffer_rsrc_t rsrcC, int ldc, bool ok, const Wave &w) {
+#pragma unroll
+    for (int j = 0; j < IPG; ++j) {
+      f32x4 v = part[j] + bias4;
+      if (ep & EP_RELU) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
+      }
+      if (ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrcC, piece_off(w, j, ldc), 0, LW_C_AUX);
+    }
+  }
+};
+
+} // namespace tpp
