@@ -353,11 +353,23 @@ TPP_XSMM_EXPORT void xsmm_hip_tail_split_stats(int64_t out[4]);
  * every synchronisation point launch the remembered transpose first - whenever anything can look at the destination it holds what
  * the program wrote. Results of a folded gemm are those of the generic kernel on the same values. One remembered transpose per
  * calling thread (the reference's OpenMP callers own a temporary each); an invoke of another thread launches it first only if it
- * touches the destination or writes the source. 0 turns it off (also TPP_HIP_FOLD_TRANSPOSE=0); returns the previous setting.
- * stats: [0] gemm invokes served from a transpose's source, [1] remembered transposes dropped as dead, [2] launched after all.
+ * touches the destination or writes the source.
+ * mode (also TPP_HIP_FOLD_TRANSPOSE=0|1|2, read as a number): 0 = off; 1 = the above (default); 2 (opt-in) = the above, and
+ *  - a gemm of the same thread whose A operand is exactly the destination folds too: pa == destination and pb != destination, one
+ *    batch element, f32 without VNNI operands or bf16x6, m = the transpose's n, k = its m, lda = its ldo, m and k at most 64, B, C
+ *    and the bias off the destination, C off the transpose's source, not in strict mode. It reads A transposed from the SOURCE;
+ *    the remembered transpose stays and is replaced or launched exactly as for B. Such a gemm pays the full (not the inlined) host path;
+ *  - a folded gemm reads its operands with 16-byte loads when every A and B pointer of its group is 16-byte aligned, k, lda, ldb,
+ *    stride_a and stride_b are multiples of 4, lda and ldb are below 2^24 and, for a transposed A, m and n are multiples of 4;
+ *    otherwise element by element. The same bits either way, and for B the bits of mode 1.
+ *  xsmm_hip_last_grouped_kernel names the path: "brgemm_grouped<f32,v4>, B read transposed", "brgemm_grouped<f32,v4>, A read
+ *  transposed", "brgemm_grouped<f32>, A read transposed"; "brgemm_grouped<f32>, B read transposed" is the element path of B and the
+ *  only name mode 1 reports.
+ * Returns the previous mode (0, 1 or 2); any other value is refused with -1 and changes nothing.
+ * stats: [0] gemm invokes served from a transpose's source (through B or A), [1] remembered transposes dropped as dead, [2] launched after all.
  *  Between a transpose invoke and the gemm invoke that consumes its temporary, no OTHER thread may write the transpose's
  * source: the folded gemm reads the source when it is enqueued, not when the transpose was invoked. */
-TPP_XSMM_EXPORT int xsmm_hip_set_fold_transpose(int enable);
+TPP_XSMM_EXPORT int xsmm_hip_set_fold_transpose(int mode);
 /* Epilogue fold (TPP_HIP_FOLD_EPILOGUE=0|1, default 1; tile queue + asynchronous mode, device operands only). The compiler fuses a
  * gemm tile with its element-wise epilogue only as brgemm + binary add bcast_col + unary relu (CombineXsmmOp); every other epilogue -
  * a bias alone, a relu alone, a residual add, a scale, other broadcasts - reaches the runtime as a gemm invoke followed by one or two

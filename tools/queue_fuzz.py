@@ -3,7 +3,8 @@
 ops over a few device buffers are run repeatedly - from 1 to 6 caller threads with a barrier after every phase, with
 random synchronisation points, with mutations between repetitions - once through the queue and once with the queue off
 (every invoke its own launch, program order); the buffers must come out bit-identical. Measurement / assurance aid,
-not a test: `python tools/queue_fuzz.py [seconds] [seed]`."""
+not a test: `python tools/queue_fuzz.py [--fold MODE] [seconds] [seed]`. --fold 2 runs the programs under mode 2 of
+xsmm_hip_set_fold_transpose: half of the transpose + gemm pairs then feed the temporary to the gemm's A operand. The check is the same."""
 import importlib
 import os
 import sys
@@ -17,8 +18,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("tpp-mlir_amd")
 rt = pkg.get_runtime()
 F32 = 1
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+argv = sys.argv[1:]
+FOLD = 1
+if "--fold" in argv:
+    i = argv.index("--fold")
+    FOLD = int(argv[i + 1])
+    del argv[i:i + 2]
+    if FOLD not in (0, 1, 2):
+        sys.exit("queue_fuzz: --fold takes 0, 1 or 2")
+budget = float(argv[0]) if len(argv) > 0 else 60.0
+seed0 = int(argv[1]) if len(argv) > 1 else 1
 NBUF, NTILE = 5, 64
 copy = rt.unary_dispatch(1, F32, 32, 32, 32, 32, 0)
 relu = rt.unary_dispatch(5, F32, 32, 32, 32, 32, 0)
@@ -46,7 +55,10 @@ def issue(op, bufs):
         # 8: ONE temporary per calling thread in a scratch buffer that is not compared (transposes are dropped as dead)
         X, xt = (bufs[op[7]], dt) if kind == 7 else (bufs[NBUF], getattr(tls, "tid", 0))
         rt.unary(F32, transp, S, st * 1024, X, xt * 1024)
-        rt.gemm(F32, gemm1, S2, s2t * 1024, X, xt * 1024, D, dt * 1024)
+        if FOLD == 2 and dt & 1:  # the temporary as the A operand (folded under mode 2 only)
+            rt.gemm(F32, gemm1, X, xt * 1024, S2, s2t * 1024, D, dt * 1024)
+        else:
+            rt.gemm(F32, gemm1, S2, s2t * 1024, X, xt * 1024, D, dt * 1024)
         return
     if kind == 0:
         rt.unary(F32, copy, S, st * 1024, D, dt * 1024)
@@ -109,6 +121,7 @@ def run(phases, bufs, nthr, sync_after):
 t_end = time.time() + budget
 rounds = ops = 0
 seed = seed0
+fold_before = rt.set_fold_transpose(FOLD)
 stats0 = rt.tile_queue_stats()
 while time.time() < t_end:
     rng = np.random.default_rng(seed)
@@ -141,7 +154,8 @@ while time.time() < t_end:
                 phases[pi] = [(k, s, int(rng.integers(0, NTILE)), s2, s2t, d, t[6], x) for t in phases[pi]]
     rounds += 1
     seed += 1
+rt.set_fold_transpose(fold_before)
 st = tuple(b - a for a, b in zip(stats0, rt.tile_queue_stats()))
 print("queue_fuzz: %d programs (%d invokes through the queue) identical to the unqueued runs; queue launches %d, full bookkeeping %d, "
-      "replayed %d, terminated %d, abandoned %d; transposes: %d gemms served from a transpose's source, %d dropped as dead, %d launched late"
-      % ((rounds, ops) + st + rt.fold_transpose_stats()))
+      "replayed %d, terminated %d, abandoned %d; transposes: %d gemms served from a transpose's source, %d dropped as dead, %d launched late (fold mode %d)"
+      % ((rounds, ops) + st + rt.fold_transpose_stats() + (FOLD,)))

@@ -95,7 +95,10 @@ static int run_case(int argc, char **argv) {
     else if (a == "--print") print = true;
     else if (a == "--c1") c1 = true;
     else if (a == "--script") script = next(); // the call scripts of benchmarks/mlir/*.mlir (base/mha.json, base/pack.json): see run_script
-    else if (a == "--fold") fold = atoi(next()); // --script: xsmm_hip_set_fold_transpose (1 = default: transposes folded into the gemm they feed)
+    else if (a == "--fold") { // --script: xsmm_hip_set_fold_transpose (0 = off, 1 = default: transposes folded into the gemm whose B they feed, 2 = also A, 16-byte loads)
+      fold = atoi(next());
+      if (fold < 0 || fold > 2) { fprintf(stderr, "tpp_replay: --fold takes 0, 1 or 2\n"); return 2; }
+    }
     else if (a == "--bf16") bf16 = true; // mlir-gen --float-type=bf16 --vnni=2: bf16 storage, W in VNNI-2 blocks
     else if (a == "--vnni") vnni = atoi(next()); // --vnni=4 (benchmarks/config/*: the *_dp4_* rows): W in [K/4][N][4] blocks
     else if (a == "--kernel") kernel_args = std::string(next()) == "args"; // const (default): zero fill folded into BETA_0; args: C += ...
@@ -364,6 +367,8 @@ static int run_case(int argc, char **argv) {
 //   mha_qk          fp32-query-times-key.mlir       forall (64, 8): unary transpose [32,64,512,32] into a 64x32 temporary (memref.alloc in
 //                                                   the loop body: one per calling thread here), gemm [32,32,64,512,32,32] beta_0
 //   mha_sv          fp32-out-softmax-times-value.mlir  forall (64, 8): gemm [32,64,32,32,512,512] beta_0
+//   trans_a         (no file of the reference: ConvertLinalgToXsmm.cpp:797-805 "emit transpose for A" on the tiles of mha_sv) forall (64, 8):
+//                                                   unary transpose [32,32,512,32] into a 32x32 temporary, gemm [32,64,32,32,512,512] beta_0 reading it as A
 //   pack_a / pack_b / unpack_c   fp32-pack-gemm-operand-a-512x1024.mlir, -b-512x1024.mlir, fp32-unpack-gemm-operand-a-512x512.mlir
 // Constant / index fills with closed-form results, checked on the first run (parity against the oracle: tests/test_mha_scripts_gpu.py).
 static int run_script(const std::string &name, int queue, int64_t n_iter, int threads, int fold) {
@@ -429,6 +434,21 @@ static int run_script(const std::string &name, int queue, int64_t n_iter, int th
     };
     check = [=](const std::vector<float> &r) { for (float v : r) if (v != 16.0f) return false; return true; };
     flops = 67108864.0, invokes = 512;
+  } else if (name == "trans_a") {
+    float *P = dfill(Bt * S * E, cst(1.0f)), *V = dfill(Bt * S * E, cst(0.5f));
+    out = dfill(out_n = Bt * S * E, cst(-1.0f));
+    float *tmp = dfill((size_t)threads * S * S, cst(0.0f));
+    bufs = {P, V, out, tmp};
+    const int64_t ht = xsmm_unary_dispatch(XSMM_UNARY_TRANSPOSE, 1, S, S, E, S, 0);
+    const int64_t hg = xsmm_gemm_dispatch(1, S, D, S, S, E, E, XSMM_GEMM_FLAG_BETA_0);
+    kernel = [=]() {
+      par2(Bt, H, [=](int64_t b, int64_t hd, int th) {
+        xsmm_unary_invoke(1, ht, P, b * S * E + hd * D, tmp, th * S * S);
+        xsmm_gemm_invoke(1, hg, tmp, th * S * S, V, b * S * E + hd * D, out, b * S * E + hd * D);
+      });
+    };
+    check = [=](const std::vector<float> &r) { for (float v : r) if (v != 16.0f) return false; return true; };
+    flops = 67108864.0, invokes = 1024;
   } else if (name == "pack_a" || name == "pack_b" || name == "unpack_c") {
     // pack_a: [512][1024] -> [16][32][32][32];  pack_b: [1024][512] -> (outer_dims_perm [1,0]) [16 (n)][32 (k)][32][32];  unpack_c: [16][16][32][32] -> [512][512]
     const int64_t T = 32, R = name == "pack_b" ? 1024 : 512, Ccols = name == "pack_a" ? 1024 : 512;
@@ -474,8 +494,8 @@ static int run_script(const std::string &name, int queue, int64_t n_iter, int th
   const double mean = perf_stop_timer(t0) / (double)n_iter;
   if (queue) xsmm_hip_tile_queue_stats(q1);
   printf("%g\n", mean);
-  fprintf(stderr, "tpp_replay: script %s (%d invokes per call, %d calling thread(s)), queue %d: mean %.3f us (host side of the invokes %.3f us), %.1f GFLOP/s (BENCH_TOTAL_FLOPS %.0f), kernel %s; result checked; %.1f launches per call (per call: %.1f invokes with full bookkeeping, %.1f replayed, %.2f replays abandoned)\n",
-          name.c_str(), invokes, threads, queue, mean * 1e6, host_dt / (double)n_iter * 1e6, flops / mean / 1e9, flops,
+  fprintf(stderr, "tpp_replay: script %s (%d invokes per call, %d calling thread(s)), queue %d, fold %d: mean %.3f us (host side of the invokes %.3f us), %.1f GFLOP/s (BENCH_TOTAL_FLOPS %.0f), kernel %s; result checked; %.1f launches per call (per call: %.1f invokes with full bookkeeping, %.1f replayed, %.2f replays abandoned)\n",
+          name.c_str(), invokes, threads, queue, fold, mean * 1e6, host_dt / (double)n_iter * 1e6, flops / mean / 1e9, flops,
           queue && xsmm_hip_last_grouped_kernel()[0] ? xsmm_hip_last_grouped_kernel() : "(one launch per invoke)",
           queue ? (double)(q1[0] - q0[0]) / (double)n_iter : (double)invokes, (double)(q1[1] - q0[1]) / (double)n_iter,
           (double)(q1[2] - q0[2]) / (double)n_iter, (double)(q1[4] - q0[4]) / (double)n_iter);
@@ -485,11 +505,11 @@ static int run_script(const std::string &name, int queue, int64_t n_iter, int th
   xsmm_hip_synchronize();
   CHECK(hipMemcpy(res.data(), out, out_n * 4, hipMemcpyDeviceToHost));
   if (!no_check && !check(res)) { fprintf(stderr, "tpp_replay --script %s: WRONG RESULT after the timed calls\n", name.c_str()); return 1; }
-  if (name == "mha_qk") {
+  if (name == "mha_qk" || name == "trans_a") {
     int64_t f[3];
     xsmm_hip_fold_transpose_stats(f);
-    fprintf(stderr, "tpp_replay: transposes (process totals): %ld gemms served from a transpose's source, %ld transposes dropped as dead, %ld launched late; folding %s\n",
-            (long)f[0], (long)f[1], (long)f[2], fold ? "on" : "off");
+    fprintf(stderr, "tpp_replay: transposes (process totals): %ld gemms served from a transpose's source, %ld transposes dropped as dead, %ld launched late; folding %s (--fold %d)\n",
+            (long)f[0], (long)f[1], (long)f[2], fold ? "on" : "off", fold);
   }
   xsmm_hip_synchronize();
   for (float *p : bufs) CHECK(hipFree(p));

@@ -361,10 +361,23 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void brgemm_f32_fast(GemmArgs p,
 // bf16 products are exact in f32, accumulation is f32 - the reference's "f32 compute for
 // bf16" rule, XsmmRunnerUtils.cpp:127-129 - one rounding at the store), flat or VNNI-2 B.
 // VEC selects 16-byte loads when shape, strides and pointers allow.
+// FORM (f32, flat B): an operand is the SOURCE of a transpose the runtime folded into this gemm (rt_rewrites.h, mode 2 of
+// xsmm_hip_set_fold_transpose) and is read transposed. The two operands then swap their staging and LDS image, nothing else:
+//   FORM_BT  B[k][j] = src[j * ldb + k] is contiguous in k like a row of A: the 32 j-rows x 32 k of a chunk are loaded, clamped, cut off
+//            at k and laid out in LDS exactly as the A panel is, and a lane's fragment - four consecutive k of column li - is ONE
+//            16-byte read instead of four 4-byte reads 128 bytes apart;
+//   FORM_AT  A[i][k] = src[k * lda + i] is contiguous in m like a row of B: the 32 k-rows x 32 m of a chunk are staged and laid out
+//            as the B panel is (4-row pieces of m, a piece at or beyond m clamped to piece 0), a lane's fragment is four 4-byte reads
+//            one k-row apart.
+// The LDS footprint, the order of the MFMAs and the value each MFMA sees are those of the element path (VEC = false: FORM_AT by the
+// index expression below, a transposed B by the run-time branch on p.b_trans of the FORM_NONE instance): the same bits come out.
 constexpr int GK = 32; // k per chunk of the grouped kernel
+enum : int { FORM_NONE = 0, FORM_BT = 1, FORM_AT = 2 };
 
-template <typename T, bool VNNI, bool VEC, int VF = 2>
+template <typename T, bool VNNI, bool VEC, int VF = 2, int FORM = FORM_NONE>
 __global__ __launch_bounds__(256) void brgemm_grouped(GemmArgs p, const WorkItem *__restrict__ items) {
+  static_assert(FORM == FORM_NONE || (sizeof(T) == 4 && !VNNI), "transposed operands: f32, flat B");
+  static_assert(FORM != FORM_BT || VEC, "a transposed B on element loads is the FORM_NONE instance (p.b_trans)");
   extern __shared__ __attribute__((aligned(16))) float smem_g[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -400,8 +413,18 @@ __global__ __launch_bounds__(256) void brgemm_grouped(GemmArgs p, const WorkItem
       // offsets are relative to the TILE (the 64-bit descriptor base carries m0 * lda and n0): 32 rows x ld x 4 B stays below
       // 2^31 for every ld the launcher admits (< 2^24), whatever m is - an absolute row here would wrap past 2 GiB of A
       const int a_row = m0 + row < p.m ? row : p.m - 1 - m0, b_col = n0 + 4 * c4 < p.n ? 4 * c4 : 0;
-      voffA[u] = (unsigned)((a_row * (int)p.lda + 4 * c4) * 4);
-      voffB[u] = (unsigned)((row * (int)p.ldb + b_col) * 4);
+      if constexpr (FORM == FORM_AT) { // k-row `row`, rows m0 + 4 c4 .. + 3 of the tile
+        const int a_col = m0 + 4 * c4 < p.m ? 4 * c4 : 0;
+        voffA[u] = (unsigned)((row * (int)p.lda + a_col) * 4);
+      } else {
+        voffA[u] = (unsigned)((a_row * (int)p.lda + 4 * c4) * 4);
+      }
+      if constexpr (FORM == FORM_BT) { // column n0 + row (clamped like a row of A), k piece c4
+        const int b_row = n0 + row < p.n ? row : p.n - 1 - n0;
+        voffB[u] = (unsigned)((b_row * (int)p.ldb + 4 * c4) * 4);
+      } else {
+        voffB[u] = (unsigned)((row * (int)p.ldb + b_col) * 4);
+      }
     }
   }
   // live = false: the chunk does not exist. The f32 16-byte path then still ISSUES its loads, switched off through the buffer
@@ -414,17 +437,21 @@ __global__ __launch_bounds__(256) void brgemm_grouped(GemmArgs p, const WorkItem
     const int64_t abase = (int64_t)b * p.stride_a, bbase = (int64_t)b * p.stride_b;
     if constexpr (VEC && sizeof(T) == 4) {
       const int nrec = __builtin_amdgcn_readfirstlane(live ? 0x7fffffff : 0);
-      const __amdgpu_buffer_rsrc_t rA =
-          __builtin_amdgcn_make_buffer_rsrc((void *)((const float *)it.A + abase + (int64_t)m0 * p.lda + kk0), 0, nrec, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rB =
-          __builtin_amdgcn_make_buffer_rsrc((void *)((const float *)it.B + bbase + (int64_t)kk0 * p.ldb + n0), 0, nrec, 0x00020000);
+      // the chunk of this tile as the operand lies in memory: rows m0.. x k kk0.. of A (FORM_AT: k-rows kk0.. x m0..), k-rows kk0.. x
+      // columns n0.. of B (FORM_BT: rows n0.. x k kk0..)
+      constexpr bool AT = FORM == FORM_AT, BT = FORM == FORM_BT;
+      const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
+          (void *)((const float *)it.A + abase + (int64_t)(AT ? kk0 : m0) * p.lda + (AT ? m0 : kk0)), 0, nrec, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
+          (void *)((const float *)it.B + bbase + (int64_t)(BT ? n0 : kk0) * p.ldb + (BT ? kk0 : n0)), 0, nrec, 0x00020000);
       // k need only be a multiple of 4: in the last chunk of a batch element the 16-byte pieces at or beyond k (A: k piece c4, B: k
       // row) are requested at an offset past the descriptor's end and come back as zeros - no branch, no select on loaded data
       const int klim = p.k - kk0; // >= 32 in every chunk but a ragged last one
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int q = lane + 64 * u;
-        const unsigned oa = 4 * (q & 7) < klim ? voffA[u] : 0x80000000u, ob = (q >> 3) < klim ? voffB[u] : 0x80000000u;
+        // (k runs along the pieces of a row of A and of a transposed B, along the rows of B and of a transposed A)
+        const unsigned oa = (AT ? (q >> 3) : 4 * (q & 7)) < klim ? voffA[u] : 0x80000000u, ob = (BT ? 4 * (q & 7) : (q >> 3)) < klim ? voffB[u] : 0x80000000u;
         ra[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rA, oa, 0, 0));
         rb[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rB, ob, 0, 0));
       }
@@ -438,7 +465,8 @@ __global__ __launch_bounds__(256) void brgemm_grouped(GemmArgs p, const WorkItem
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int gr = m0 + row, gk = kk0 + 4 * c4 + e;
-          ra[u][e] = (gr < p.m && gk < p.k) ? Elem<T>::load(gA, abase + (int64_t)gr * p.lda + gk) : 0.0f;
+          // (FORM_AT: element [gr][gk] of A is element [gk][gr] of the transpose's source)
+          ra[u][e] = (gr < p.m && gk < p.k) ? Elem<T>::load(gA, abase + (FORM == FORM_AT ? (int64_t)gk * p.lda + gr : (int64_t)gr * p.lda + gk)) : 0.0f;
           const int bk = kk0 + row, bj = n0 + 4 * c4 + e;
           float v = 0.0f;
           if (bk < p.k && bj < p.n) {
@@ -461,8 +489,11 @@ __global__ __launch_bounds__(256) void brgemm_grouped(GemmArgs p, const WorkItem
     float *as = wl + buf * (2 * 32 * GK), *bs = as + 32 * GK;
     const int q = lane + 64 * u;
     const int row = q >> 3, krow = row, c4 = q & 7, c4b = c4;
-    *(f32x4 *)(as + row * GK + ((c4 ^ ((row >> 1) & 7)) << 2)) = ra[u]; // 128-byte rows: XOR on (row>>1)
-    *(f32x4 *)(bs + krow * 32 + 4 * c4b) = rb[u];
+    // (16-byte loads of a transposed operand arrive in the OTHER operand's shape and keep it: see FORM above)
+    if constexpr (VEC && FORM == FORM_AT) *(f32x4 *)(as + krow * 32 + 4 * c4b) = ra[u];
+    else *(f32x4 *)(as + row * GK + ((c4 ^ ((row >> 1) & 7)) << 2)) = ra[u]; // 128-byte rows: XOR on (row>>1)
+    if constexpr (VEC && FORM == FORM_BT) *(f32x4 *)(bs + row * GK + ((c4 ^ ((row >> 1) & 7)) << 2)) = rb[u];
+    else *(f32x4 *)(bs + krow * 32 + 4 * c4b) = rb[u];
   };
   auto swrite = [&](int buf, int set) __attribute__((always_inline)) {
 #pragma unroll
@@ -473,13 +504,24 @@ __global__ __launch_bounds__(256) void brgemm_grouped(GemmArgs p, const WorkItem
   // piece per k-block - a wave is alone on its SIMD here, so whatever is not overlapped inside the wave is idle matrix-core time
   // (before: 2300 cycles per chunk for 1024 cycles of MFMA).
   auto compute = [&](int buf, bool stage, int set) __attribute__((always_inline)) {
-    const float *as = wl + buf * (2 * 32 * GK) + li * GK, *bs = wl + buf * (2 * 32 * GK) + 32 * GK + li;
+    constexpr bool A_ROWS = !(VEC && FORM == FORM_AT), B_ROWS = VEC && FORM == FORM_BT; // image = 128-byte rows of k (else k-rows of 32)
+    const float *as = wl + buf * (2 * 32 * GK) + (A_ROWS ? li * GK : li), *bs = wl + buf * (2 * 32 * GK) + 32 * GK + (B_ROWS ? li * GK : li);
     f32x4 a4[2];
     float b4[2][4];
     auto frag = [&](int kb, int to) __attribute__((always_inline)) {
-      a4[to] = *(const f32x4 *)(as + (((2 * kb + lh) ^ ((li >> 1) & 7)) << 2));
+      if constexpr (A_ROWS) a4[to] = *(const f32x4 *)(as + (((2 * kb + lh) ^ ((li >> 1) & 7)) << 2));
+      else {
 #pragma unroll
-      for (int s = 0; s < 4; ++s) b4[to][s] = bs[(8 * kb + 4 * lh + s) * 32];
+        for (int s = 0; s < 4; ++s) a4[to][s] = as[(8 * kb + 4 * lh + s) * 32];
+      }
+      if constexpr (B_ROWS) {
+        const f32x4 b = *(const f32x4 *)(bs + (((2 * kb + lh) ^ ((li >> 1) & 7)) << 2));
+#pragma unroll
+        for (int s = 0; s < 4; ++s) b4[to][s] = b[s];
+      } else {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) b4[to][s] = bs[(8 * kb + 4 * lh + s) * 32];
+      }
     };
     frag(0, 0);
 #pragma unroll
@@ -655,10 +697,10 @@ hipError_t launch_f32_x6(int tile, const GemmArgs &a, bool vec, hipStream_t s); 
 hipError_t launch_bf16_grouped64(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s); // brgemm_bf16.hip
 hipError_t launch_bf16_small32(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s, int split = 1); // brgemm_bf16_small.hip
 
-template <typename T, bool VNNI, bool VEC, int VF = 2>
+template <typename T, bool VNNI, bool VEC, int VF = 2, int FORM = FORM_NONE>
 static hipError_t launch_grouped_t(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s) {
   constexpr size_t lds = 4 * 2 * 2 * 32 * GK * sizeof(float); // 64 KiB: 4 waves x 2 buffers x (A + B)
-  auto kern = brgemm_grouped<T, VNNI, VEC, VF>;
+  auto kern = brgemm_grouped<T, VNNI, VEC, VF, FORM>;
   static std::atomic<unsigned long long> lds_set{0};
   if (hipError_t e = ensure_dynamic_lds((const void *)kern, (int)lds, lds_set); e != hipSuccess) return e;
   GemmArgs args = a;
@@ -757,6 +799,9 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
     case GG_BF16_VNNI2_VEC: return launch_grouped_t<unsigned short, true, true>(a, wi, n_items, s);
     case GG_BF16_VNNI4_VEC: return launch_grouped_t<unsigned short, true, true, 4>(a, wi, n_items, s);
     case GG_BF16_FLAT: return launch_grouped_t<unsigned short, false, false>(a, wi, n_items, s);
+    case GG_F32_BT_VEC: return launch_grouped_t<float, false, true, 2, FORM_BT>(a, wi, n_items, s);
+    case GG_F32_AT_VEC: return launch_grouped_t<float, false, true, 2, FORM_AT>(a, wi, n_items, s);
+    case GG_F32_AT: return launch_grouped_t<float, false, false, 2, FORM_AT>(a, wi, n_items, s);
     }
   }
   return hipErrorInvalidValue;

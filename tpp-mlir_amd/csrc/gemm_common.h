@@ -29,7 +29,8 @@ struct GemmArgs {
   int split;
   float *scratch;
   unsigned *split_cnt;
-  int b_trans;         // generic kernel: B[k][j] = B_ptr[j * ldb + k] (GemmDesc::b_trans)
+  int b_trans;         // generic kernel: B[k][j] = B_ptr[j * ldb + k] (GemmDesc::b_trans). GemmDesc::a_trans has no field here: a transposed A is a
+                       // compile-time form of that kernel (brgemm_f32.hip FORM_AT), and this block has no padding left and keeps its size
   int tail_body;       // brgemm_f32_lw TAIL instances: the first tail_body workgroups of the linear grid run whole tiles, the rest share the tail tiles
 };
 static_assert(sizeof(GemmArgs) == 136, "GemmArgs: the kernels that take a work list read it behind this block");

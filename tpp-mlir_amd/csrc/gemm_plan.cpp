@@ -377,12 +377,28 @@ static GemmLaunch launch(GemmLauncher l, int tile = 0, const char *text = "", in
 }
 static GemmLaunch generic(GemmGeneric g, const char *text = "") { return GemmLaunch{GL_GENERIC, 0, 1, 0, false, false, g, text}; }
 
+// An operand read transposed (a folded xsmm.unary transpose, rt_rewrites.h): the generic kernel. A sibling made under mode 1 of
+// xsmm_hip_set_fold_transpose (B only) stays on the element-wise loads it has always had. A mode-2 sibling (GemmDesc::trans_mode)
+// runs on the 16-byte instance of its form when the lane offsets and pieces allow - every A and B pointer 16-byte aligned, k in
+// whole pieces, leading dimensions and strides in whole pieces and below 2^24 (32 rows x ld x 4 B < 2^31); a transposed A
+// is staged in 4-row pieces of m and its B operand in 4-column pieces of n, a transposed B needs nothing of n (columns are the
+// rows of its image) - and on the element instance of its form otherwise. text: what a GROUP reports ("" for a single call, as before).
+static GemmLaunch trans_launch(const GemmDesc &d, bool vec_ok, bool group) {
+  if (d.dtype != DT_F32 || d.vnni_b || (d.a_trans && (d.b_trans || d.vnni_c))) return launch(GL_INVALID);
+  const bool vec = d.trans_mode == 2 && vec_ok && d.k % 4 == 0 && !((d.lda | d.ldb | d.stride_a | d.stride_b) & 3) && d.lda < (1 << 24) &&
+                   d.ldb < (1 << 24) && (!d.a_trans || (d.m % 4 == 0 && d.n % 4 == 0));
+  if (d.a_trans) return vec ? generic(GG_F32_AT_VEC, group ? "brgemm_grouped<f32,v4>, A read transposed" : "")
+                            : generic(GG_F32_AT, group ? "brgemm_grouped<f32>, A read transposed" : "");
+  return vec ? generic(GG_F32_BT_VEC, group ? "brgemm_grouped<f32,v4>, B read transposed" : "")
+             : generic(GG_F32, group ? "brgemm_grouped<f32>, B read transposed" : "");
+}
+
 GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al, const GemmPlanEnv &env) {
   if (d.m <= 0 || d.n <= 0) return launch(GL_NONE);
   const int64_t cus = env.cus;
   const int br = (int)(br_in < 0 ? 0 : br_in);
   int v = d.variant;
-  if (d.b_trans) return d.dtype != DT_F32 || d.vnni_b ? launch(GL_INVALID) : generic(GG_F32);
+  if (d.b_trans || d.a_trans) return trans_launch(d, al.ab16, false);
   // bf16x6: the planned split tile whatever the batch count, split setting or pointer alignment (unaligned A / B: element loads)
   if (gemm_on_x6(d))
     return GemmLaunch{GL_F32_X6, v - V_F32_X6_64x64, 1, 0, false, al.ab16, GG_F32, ""};
@@ -475,10 +491,7 @@ GemmLaunch plan_gemm_group(const GemmDesc &d, int n_items, bool vec_ok, bool out
   // n_dec: the number of items every size-dependent DECISION below is taken for. Normally the group's - the group is what fills the
   // chip. In strict mode 1: a single invoke, the first pass of a queued group and its replays then all run on the same kernel.
   const int64_t n_dec = env.strict ? 1 : n_items;
-  if (d.b_trans) { // B read transposed (a folded xsmm.unary transpose): the generic kernel's element-wise loads
-    if (d.dtype != DT_F32 || d.vnni_b) return launch(GL_INVALID);
-    return generic(GG_F32, "brgemm_grouped<f32>, B read transposed");
-  }
+  if (d.b_trans || d.a_trans) return trans_launch(d, vec_ok, true);
   const GenericOk g = generic_ok(d, vec_ok);
   // f32 tiles with k a multiple of 64 (mlir-gen --tiles=64,64,64, the most common setting of the reference's
   // benchmark configs): the fast tile families in grouped mode, the largest tile that still yields about one

@@ -64,11 +64,12 @@ enum GemmLauncher : int {
   GL_BF16_LW,         // launch_bf16_lw / _flatb / _vnni4 by b_kind (0 / 2 / 4), tile
   GL_BF16_LW_GROUPED, // launch_bf16_lw_grouped(tile, b_kind, even)
   GL_BF16_LW_QUADS,   // launch_bf16_lw_quads(b_kind)
-  GL_GENERIC,         // brgemm_grouped<T, VNNI, VEC, VF>: generic
+  GL_GENERIC,         // brgemm_grouped<T, VNNI, VEC, VF, FORM>: generic
 };
 // the instances of the generic kernel brgemm_grouped<T, VNNI, VEC, VF>: <float, false, false / true>, <unsigned short, true, false / true>,
-// <unsigned short, true, true, 4>, <unsigned short, false, false>
-enum GemmGeneric : int { GG_F32, GG_F32_VEC, GG_BF16_VNNI2, GG_BF16_VNNI2_VEC, GG_BF16_VNNI4_VEC, GG_BF16_FLAT };
+// <unsigned short, true, true, 4>, <unsigned short, false, false>; and the f32 instances whose FORM argument says that an operand is
+// read transposed (mode 2 of xsmm_hip_set_fold_transpose): <float, false, true, 2, B transposed>, <float, false, true / false, 2, A transposed>
+enum GemmGeneric : int { GG_F32, GG_F32_VEC, GG_BF16_VNNI2, GG_BF16_VNNI2_VEC, GG_BF16_VNNI4_VEC, GG_BF16_FLAT, GG_F32_BT_VEC, GG_F32_AT_VEC, GG_F32_AT };
 struct GemmLaunch {
   GemmLauncher launcher;
   int tile;        // the launcher's tile index

@@ -37,7 +37,9 @@ struct Config {
   std::atomic<int> f32_precision{0}; // f32 arithmetic of descriptors dispatched from now on: 0 = exact, 6 = bf16x6 (xsmm_hip_set_f32_precision / TPP_HIP_F32_PRECISION)
   std::atomic<int> vnni_factor{2}; // blocking factor of VNNI B operands dispatched from now on (xsmm_hip_set_vnni_factor / TPP_HIP_VNNI_FACTOR)
   int trace = 0; // TPP_HIP_TRACE: 1 = one stderr line per dispatch + a roctx range per invoke, 2 = also one stderr line per invoke
-  std::atomic<int> fold_transpose{1}; // TPP_HIP_FOLD_TRANSPOSE / xsmm_hip_set_fold_transpose: transposes that feed a gemm's B operand are folded into it
+  // TPP_HIP_FOLD_TRANSPOSE / xsmm_hip_set_fold_transpose: 0 = off, 1 = transposes that feed a gemm's B operand are folded into it, 2 (opt-in) =
+  // also those that feed its A operand, and the folded gemms may read the source with 16-byte loads (rt_rewrites.h)
+  std::atomic<int> fold_transpose{1};
   std::atomic<int> fold_epilogue{1};  // TPP_HIP_FOLD_EPILOGUE / xsmm_hip_set_fold_epilogue: element-wise invokes on a queued GEMM tile join its group (rt_tile_queue.h)
   std::atomic<int> relayout_grid{1};  // TPP_HIP_RELAYOUT_GRID / xsmm_hip_set_relayout_grid: replayed pack / unpack groups run as relayout grids (rt_relayout.h)
   // TPP_HIP_STRICT / xsmm_hip_set_strict (round 6): the kernel an invoke runs on is a function of its descriptor,
@@ -51,7 +53,10 @@ struct Config {
       strict = atoi(e) != 0;
       tpp::set_strict_kernels(strict.load());
     }
-    if (const char *e = getenv("TPP_HIP_FOLD_TRANSPOSE")) fold_transpose = atoi(e) != 0;
+    if (const char *e = getenv("TPP_HIP_FOLD_TRANSPOSE")) {
+      if (atoi(e) >= 0 && atoi(e) <= 2) fold_transpose = atoi(e);
+      else fprintf(stderr, "[tpp-xsmm-hip] TPP_HIP_FOLD_TRANSPOSE=%s ignored: the mode is 0, 1 or 2\n", e);
+    }
     if (const char *e = getenv("TPP_HIP_RELAYOUT_GRID")) relayout_grid = atoi(e) != 0;
     if (const char *e = getenv("TPP_HIP_FOLD_EPILOGUE")) fold_epilogue = atoi(e) != 0;
     if (const char *e = getenv("TPP_HIP_ASYNC")) async = atoi(e) != 0;

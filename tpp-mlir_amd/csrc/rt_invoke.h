@@ -130,10 +130,11 @@ __attribute__((always_inline)) inline void gemm_invoke_common(const char *who, b
   if (g_dt_pending.load(std::memory_order_acquire)) { // a remembered transpose: this gemm reads its source instead, or it is launched now
     void *src = nullptr;
     const GemmDesc *sib = dt_gemm_fast(d, pa, pb, pc, pd, br, s, &src);
-    if (!sib) sib = dt_gemm(d, pa, pb, pc, pd, br, s, &src);
+    bool a_operand = false;
+    if (!sib) sib = dt_gemm(d, pa, pb, pc, pd, br, s, &src, &a_operand);
     if (sib) {
       d = sib;
-      pb = src;
+      (a_operand ? pa : pb) = src;
     }
   }
   if (cfg().tile_queue.load(std::memory_order_relaxed)) {

@@ -36,7 +36,7 @@ __attribute__((always_inline)) inline void gemm_operands(const GemmDesc *d, void
   if (d->vnni_c) C.shape(d->m / 2, (size_t)2 * d->n * es, (size_t)2 * d->ldc * es);
   else C.shape(d->m, (size_t)d->n * es, (size_t)d->ldc * es);
   if (br > 0 && d->k > 0) {
-    A.bytes = ((size_t)(br - 1) * d->stride_a + span(d->m, d->lda, d->k)) * es;
+    A.bytes = ((size_t)(br - 1) * d->stride_a + (d->a_trans ? span(d->k, d->lda, d->m) : span(d->m, d->lda, d->k))) * es;
     const int64_t vf = d->vnni_factor;
     const size_t bspan = d->vnni_b ? span((d->k + vf - 1) / vf, vf * d->ldb, vf * d->n) : d->b_trans ? span(d->n, d->ldb, d->k) : span(d->k, d->ldb, d->n);
     B.bytes = ((size_t)(br - 1) * d->stride_b + bspan) * es;

@@ -23,7 +23,7 @@ inline void detect_grid(Segment &S) {
   const void *desc = S.items[0].desc;
   if (*(const int *)desc != KIND_GEMM) return;
   const GemmDesc *d = (const GemmDesc *)desc;
-  if (d->dtype != DT_F32 || d->vnni_b || d->vnni_c || d->b_trans || d->generic_forced || d->variant_forced || d->m <= 0 || d->n <= 0 || d->k <= 0) return;
+  if (d->dtype != DT_F32 || d->vnni_b || d->vnni_c || d->b_trans || d->a_trans || d->generic_forced || d->variant_forced || d->m <= 0 || d->n <= 0 || d->k <= 0) return;
   const int64_t br = S.items[0].w.br;
   std::vector<uintptr_t> ua, ub;
   ua.reserve(n);
@@ -252,6 +252,13 @@ inline void detect_relayout(Segment &S, hipStream_t stream) {
 // Between a transpose's invoke and its launch only folded gemms of its own thread and invokes that touch neither its destination
 // nor (writing) its source run: the deferred launch reads what the immediate one would have read.
 // Summation order of a folded gemm = the generic kernel's (what a single invoke of the same gemm on the generic kernel adds).
+// MODE 2 (xsmm_hip_set_fold_transpose(2) / TPP_HIP_FOLD_TRANSPOSE=2, opt-in): the siblings are made under mode 2 - the planner may run
+// them on the 16-byte instances of the generic kernel (gemm_plan.cpp trans_launch), the same bits - and a gemm of the owning thread whose
+// A operand is exactly the destination (ConvertLinalgToXsmm.cpp:797-805 "emit transpose for A": m = the transpose's n, k = its m,
+// lda = ldo, B not the destination, one batch element, f32, m and k at most 64, B / C / bias off the destination, C off the source)
+// folds the same way, on a sibling that reads A transposed (GemmDesc::a_trans, lda = the source's). The record stays, and everything
+// said above about replacement, launches and the other threads holds for it unchanged. A gemm whose A is the temporary never takes
+// the inlined fast path (dt_gemm_fast knows B folds only): its host cost per invoke is dt_gemm's.
 struct DeferredTranspose {
   const UnaryDesc *d = nullptr;
   void *src = nullptr, *dst = nullptr;
@@ -262,6 +269,10 @@ struct DeferredTranspose {
   // synchronisation epoch by the full path (0: not); a source inside it needs no further look at the allocation table
   uintptr_t src_alloc_b = 0, src_alloc_e = 0;
   uint64_t valid_epoch = 0;
+  // mode 2, the last gemm descriptor folded through its A operand, apart from sib_of (dt_gemm_fast serves B folds only and must never
+  // meet an A sibling): its sibling and the footprints of its B / C / bias operands
+  const GemmDesc *asib_of = nullptr, *asib = nullptr;
+  size_t ab_bytes = 0, ac_bytes = 0, ad_bytes = 0;
 };
 struct alignas(64) DtSlot {
   // line 0 - what EVERY thread reads per invoke while records exist; written when a record appears or goes, not per tile:
@@ -404,23 +415,34 @@ DtSlot *dt_my_slot(bool claim) {
   }
   return nullptr; // more transposing threads than slots: this one's transposes are launched as they come
 }
-const GemmDesc *dt_sibling(const GemmDesc *d, int64_t ld_src) {
+// keyed by (descriptor, source ld, operand, mode); the mode-1 siblings (B only) keep the key they have always had
+const GemmDesc *dt_sibling(const GemmDesc *d, int64_t ld_src, bool a_operand = false, int mode = 1) {
   std::vector<int64_t> key = {KIND_GEMM, -29, (int64_t)(uintptr_t)d, ld_src};
+  if (a_operand || mode != 1) key.push_back(a_operand), key.push_back(mode);
   return (const GemmDesc *)intern(key, [&]() {
     GemmDesc *e = new GemmDesc(*d);
-    e->b_trans = 1;
-    e->ldb = ld_src;
+    e->b_trans = !a_operand;
+    e->a_trans = a_operand;
+    e->trans_mode = mode;
+    (a_operand ? e->lda : e->ldb) = ld_src;
     e->variant = V_GENERIC;
     e->generic_forced = 1;
-    snprintf(e->name, sizeof(e->name), "brgemm_grouped(generic), B read transposed");
-    snprintf(e->trace, sizeof(e->trace), "gemm[%ld,%ld,%ld,%ld,(%ld)^T,%ld] dt%ld flags%ld %s (transpose folded)", (long)d->m, (long)d->n, (long)d->k,
-             (long)d->lda, (long)ld_src, (long)d->ldc, (long)d->dtype, (long)d->wire_flags, e->name);
+    snprintf(e->name, sizeof(e->name), "brgemm_grouped(generic), %c read transposed", a_operand ? 'A' : 'B');
+    if (a_operand)
+      snprintf(e->trace, sizeof(e->trace), "gemm[%ld,%ld,%ld,(%ld)^T,%ld,%ld] dt%ld flags%ld %s (transpose folded)", (long)d->m, (long)d->n, (long)d->k,
+               (long)ld_src, (long)d->ldb, (long)d->ldc, (long)d->dtype, (long)d->wire_flags, e->name);
+    else
+      snprintf(e->trace, sizeof(e->trace), "gemm[%ld,%ld,%ld,%ld,(%ld)^T,%ld] dt%ld flags%ld %s (transpose folded)", (long)d->m, (long)d->n, (long)d->k,
+               (long)d->lda, (long)ld_src, (long)d->ldc, (long)d->dtype, (long)d->wire_flags, e->name);
     return (void *)e;
   });
 }
 // a gemm invoke while transposes are remembered: the sibling descriptor + the transpose's source if it folds into this thread's record
-// (which stays), else nullptr - this thread's record, and every other thread's record the gemm's operands touch, launched first
-const GemmDesc *dt_gemm(const GemmDesc *d, void *pa, void *pb, void *pc, void *pd, int64_t br, hipStream_t s, void **src) {
+// (which stays), else nullptr - this thread's record, and every other thread's record the gemm's operands touch, launched first.
+// *a_operand: the source replaces the gemm's A (mode 2), not its B
+const GemmDesc *dt_gemm(const GemmDesc *d, void *pa, void *pb, void *pc, void *pd, int64_t br, hipStream_t s, void **src, bool *a_operand) {
+  *a_operand = false;
+  const int mode = cfg().fold_transpose.load(std::memory_order_relaxed);
   const size_t es = esize(d->dtype);
   DtSlot *mine = dt_my_slot(false);
   const GemmDesc *sib = nullptr;
@@ -441,12 +463,33 @@ const GemmDesc *dt_gemm(const GemmDesc *d, void *pa, void *pb, void *pc, void *p
           if (!dt_overlap(pa, a_bytes, r.dst, dst_bytes) && !dt_overlap(pc, c_bytes, r.dst, dst_bytes) && !dt_overlap(pd, d_bytes, r.dst, dst_bytes) &&
               !dt_overlap(pc, c_bytes, r.src, src_bytes)) {
             if (!known) {
-              r.sib = dt_sibling(d, t->ldi);
+              r.sib = dt_sibling(d, t->ldi, false, mode == 2 ? 2 : 1);
               r.sib_of = d;
               r.a_bytes = a_bytes, r.c_bytes = c_bytes, r.d_bytes = d_bytes;
             }
             *src = r.src;
             sib = r.sib;
+            mine->folded.store(mine->folded.load(std::memory_order_relaxed) + 1, std::memory_order_relaxed);
+          }
+        }
+        // mode 2: the destination is the gemm's A operand (and not its B: both on the temporary is a gemm that reads the transpose twice,
+        // launched like any other). Strict mode needs no test here, as for B: dt_defer makes no record under it.
+        const bool aknown = r.asib_of == d;
+        if (!sib && mode == 2 && pa == r.dst && pb != r.dst && br == 1 && s == r.stream && queue_active() &&
+            (aknown || (d->dtype == DT_F32 && !gemm_on_x6(*d) && !d->vnni_b && !d->vnni_c && !d->b_trans && !d->a_trans && d->m == t->n && d->k == t->m &&
+                        d->lda == t->ldo && d->m <= 64 && d->k <= 64))) {
+          const size_t b_bytes = aknown ? r.ab_bytes : span(d->k, d->ldb, d->n) * 4, c_bytes = aknown ? r.ac_bytes : span(d->m, d->ldc, d->n) * 4,
+                       d_bytes = aknown ? r.ad_bytes : (d->bias ? (size_t)d->n * 4 : 0);
+          if (!dt_overlap(pb, b_bytes, r.dst, dst_bytes) && !dt_overlap(pc, c_bytes, r.dst, dst_bytes) && !dt_overlap(pd, d_bytes, r.dst, dst_bytes) &&
+              !dt_overlap(pc, c_bytes, r.src, src_bytes)) {
+            if (!aknown) {
+              r.asib = dt_sibling(d, t->ldi, true, 2);
+              r.asib_of = d;
+              r.ab_bytes = b_bytes, r.ac_bytes = c_bytes, r.ad_bytes = d_bytes;
+            }
+            *src = r.src;
+            sib = r.asib;
+            *a_operand = true;
             mine->folded.store(mine->folded.load(std::memory_order_relaxed) + 1, std::memory_order_relaxed);
           }
         }
@@ -456,11 +499,12 @@ const GemmDesc *dt_gemm(const GemmDesc *d, void *pa, void *pb, void *pc, void *p
   }
   if (g_dt_pending.load(std::memory_order_relaxed) > (sib ? 1 : 0)) { // other threads' records
     const GemmDesc *e = sib ? sib : d;
-    const void *b = sib ? *src : pb;
+    const void *a = *a_operand ? *src : pa, *b = sib && !*a_operand ? *src : pb;
     const int64_t vf = e->vnni_factor ? e->vnni_factor : 2;
     const size_t bspan = e->vnni_b ? span((e->k + vf - 1) / vf, vf * e->ldb, vf * e->n) : e->b_trans ? span(e->n, e->ldb, e->k) : span(e->k, e->ldb, e->n);
     const size_t nb = br > 0 ? (size_t)(br - 1) : 0;
-    const DtRange rd[4] = {dt_range(pa, (nb * e->stride_a + span(e->m, e->lda, e->k)) * es), dt_range(b, (nb * e->stride_b + bspan) * es),
+    const size_t aspan = e->a_trans ? span(e->k, e->lda, e->m) : span(e->m, e->lda, e->k);
+    const DtRange rd[4] = {dt_range(a, (nb * e->stride_a + aspan) * es), dt_range(b, (nb * e->stride_b + bspan) * es),
                            dt_range(pd, e->bias ? (size_t)e->n * es : 0), dt_range(pc, span(e->m, e->ldc, e->n) * es * (e->vnni_c ? 2 : 1))};
     dt_scan_foreign(mine, rd, 4, rd + 3, 1);
   }
@@ -508,6 +552,7 @@ __attribute__((always_inline)) inline bool dt_defer_fast(const UnaryDesc *d, voi
 }
 // ... and of the gemm that follows it, inlined into the gemm entry points: the descriptor this record folded last, B = the record's
 // destination, one batch element, the record's stream, no operand on the destination, C off the source - the sibling and the source.
+// B folds only (r.sib_of / r.sib never hold an A sibling): a gemm whose A is the temporary (mode 2) goes through dt_gemm every time.
 __attribute__((always_inline)) inline const GemmDesc *dt_gemm_fast(const GemmDesc *d, void *pa, void *pb, void *pc, void *pd, int64_t br, hipStream_t s, void **src) {
   CallerState *tl = tl_fast;
   if (!tl || tl->dt_slot < 0 || !membarrier_ok()) return nullptr;

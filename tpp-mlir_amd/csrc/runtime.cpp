@@ -501,9 +501,10 @@ extern "C" void xsmm_hip_relayout_grid_stats(int64_t out[2]) {
   out[0] = g_rl_launches.load(std::memory_order_relaxed);
   out[1] = g_rl_items.load(std::memory_order_relaxed);
 }
-extern "C" int xsmm_hip_set_fold_transpose(int enable) {
-  flush_tile_queue(); // (launches a remembered transpose)
-  return cfg().fold_transpose.exchange(enable != 0);
+extern "C" int xsmm_hip_set_fold_transpose(int mode) { // 0, 1 or 2 (rt_rewrites.h); anything else: -1, nothing changed
+  if (mode < 0 || mode > 2) return -1;
+  flush_tile_queue(); // (launches a remembered transpose: no record outlives the mode its siblings were made under)
+  return cfg().fold_transpose.exchange(mode);
 }
 extern "C" void xsmm_hip_fold_transpose_stats(int64_t out[3]) {
   out[0] = out[1] = 0;

@@ -32,7 +32,10 @@ struct GemmDesc {
   int generic_forced;   // variant = generic because it was asked for (xsmm_hip_force_variant / a VNNI C store), not because no fast tile fits
   int variant_forced;   // variant is the one xsmm_hip_force_variant asked for: invoke-time refinements (batch-count dependent) leave it alone
   int b_trans;          // runtime-made sibling of a dispatched descriptor (never on the wire): B is read TRANSPOSED, B[k][j] = ptr[j * ldb + k] -
-                        // the source of an xsmm.unary transpose that fed this gemm's B operand (runtime.cpp, deferred transposes); generic kernel only
+                        // the source of an xsmm.unary transpose that fed this gemm's B operand (rt_rewrites.h, deferred transposes); generic kernel only
+  int a_trans;          // the same for the A operand (mode 2 of xsmm_hip_set_fold_transpose only): A[i][k] = ptr[k * lda + i]; never together with b_trans
+  int trans_mode;       // the mode of xsmm_hip_set_fold_transpose a sibling was made under (1 or 2; 0: no sibling): a mode-2 sibling may run on
+                        // the 16-byte instances of the generic kernel (gemm_plan.cpp trans_launch), a mode-1 sibling never leaves the element path
   char name[64];        // kernel name for profiles
   char trace[160];      // dispatch tuple + kernel name as text (trace ranges)
 };

@@ -347,8 +347,12 @@ class XsmmRuntime:
         return tuple(int(v) for v in out)
 
     def set_fold_transpose(self, enable):
-        """transposes that feed a gemm's B operand folded into the gemm (default on); returns the previous setting"""
-        return self.lib.xsmm_hip_set_fold_transpose(1 if enable else 0)
+        """transposes that feed a gemm's B operand folded into the gemm (default on); the integer 2 (opt-in): also those that feed its
+        A operand, and 16-byte loads of the source where alignment allows. True / False are modes 1 / 0; an integer is passed on as it
+        is. Returns the previous mode (0, 1 or 2), or -1 for an integer the library refuses (anything but 0, 1, 2: nothing changes)"""
+        if isinstance(enable, bool) or enable is None:
+            return self.lib.xsmm_hip_set_fold_transpose(1 if enable else 0)
+        return self.lib.xsmm_hip_set_fold_transpose(int(enable))
 
     def fold_transpose_stats(self):
         """(gemm invokes served from a transpose's source, remembered transposes dropped as dead, remembered transposes launched)"""
