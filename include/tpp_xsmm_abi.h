@@ -342,6 +342,27 @@ TPP_XSMM_EXPORT int xsmm_hip_force_split(int workgroups_per_tile);
  * tail tile, [3] body tiles. */
 TPP_XSMM_EXPORT int xsmm_hip_set_tail_split(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_tail_split_stats(int64_t out[4]);
+/* Edge tiles (opt-in; also TPP_HIP_EDGE_TILES, read as a number). A whole-layer f32 call whose m or n is not a multiple of 32 is planned
+ * on the generic kernel. With edge tiles on, such a call runs on a loader-wave tile (64x64 + K2, 64x32 + K4, 32x32 + K4 or 128x64) all the
+ * same, as ONE launch of ceil(m / BM) x ceil(n / BN) workgroups: the last tile of a row or column of tiles is shifted back so that it
+ * ends at the matrix edge, computes a whole BM x BN block there and stores (and, with beta = 1, joins C for) only the rows and columns no
+ * other tile owns. Every element is computed from its own row of A and column of B in the order of the plain tile, so the result has
+ * the bits the same tile gives on the shape padded up to whole tiles; no load leaves rows [0, m) of A or columns [0, n) of B, no byte of
+ * C outside the m x n window is written. No scratch block, no counters: legal on a captured stream.
+ * A call takes edge tiles when all of this holds: f32, no VNNI operand, no transposed operand, not on the bf16x6 kernel, the generic
+ * kernel not forced, no tile divides m x n (the descriptor's kernel is the generic one), k a positive multiple of 64, batch count >= 1,
+ * lda / ldb / ldc / strides multiples of 4 and ld < 2^22, n a multiple of 4, A, B, C (and the bias row) 16-byte aligned, and m >= BM,
+ * n >= BN for the tile. Everything else runs as with the mode off - also every tile-queue group, chain and folded call.
+ * mode 0 = off (default); 1 = the tile rule of the divisible shapes (rounds of workgroups, a 128x64 round = 1.85 rounds of 64x64, a
+ * tile per CU before a larger tile) on ceil-divided tile counts; 6 / 7 / 9 / 10 = the tile of that kernel variant (64x64 + K2, 64x32 +
+ * K4, 32x32 + K4, 128x64) wherever it fits (a test / measurement switch). Read per invoke; returns the previous mode, -1 (and changes
+ * nothing) for any other value. A forced split count and the tail split do not apply to an edge launch. The choice depends on the
+ * descriptor, the batch count, the pointers' alignment and the CU count only, so it is made in strict mode too.
+ * xsmm_hip_last_refined_kernel reads "brgemm_f32_lw<64x64,k2>, edge tiles" (<64x32,k4>, <32x32,k4>, <128x64,k1>).
+ * _stats: out[0] edge launches since process start; of the most recent one: [1] tile rows, [2] tile columns, [3] the variant number
+ * of its tile (6, 7, 9, 10). */
+TPP_XSMM_EXPORT int xsmm_hip_set_edge_tiles(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_edge_tiles_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

@@ -68,7 +68,7 @@ int main(int argc, char **argv) {
 static int run_case(int argc, char **argv) {
   int64_t batch = 256, tile = 32, tile_n = 0, tile_k = 0, n_iter = 100;
   bool kernel_args = false; // mlir-gen --kernel=args: the output is an argument, the matmul accumulates into it (no BETA_0)
-  int vnni = 2, split = -1, tail_split = 0, variant = -1, repeats = 1, f32p = 0;
+  int vnni = 2, split = -1, tail_split = 0, edge_tiles = 0, variant = -1, repeats = 1, f32p = 0;
   int64_t block_pad = 0; // --block-pad P (experiments): P elements between consecutive packed blocks of A and of W (the block strides stop being powers of two)
   std::vector<int64_t> layers = {1024, 1024, 1024, 1024};
   bool bias = false, relu = false, whole = false, chain = false, print = false, c1 = false, rnd = false, bf16 = false, host_buffers = false;
@@ -104,6 +104,7 @@ static int run_case(int argc, char **argv) {
     else if (a == "--kernel") kernel_args = std::string(next()) == "args"; // const (default): zero fill folded into BETA_0; args: C += ...
     else if (a == "--split") split = atoi(next());     // xsmm_hip_force_split for this case (-1: the runtime's model)
     else if (a == "--tail-split") tail_split = atoi(next()); // xsmm_hip_set_tail_split for this case (0: off, 1: the model, 2 .. 16: workgroups per tail tile)
+    else if (a == "--edge-tiles") edge_tiles = atoi(next()); // xsmm_hip_set_edge_tiles for this case (0: off, 1: the tile rule, 6 / 7 / 9 / 10: that variant's tile)
     else if (a == "--variant") variant = atoi(next()); // xsmm_hip_force_variant at dispatch (-1: the runtime's choice)
     else if (a == "--f32-precision") { // xsmm_hip_set_f32_precision for this case's dispatches: exact (default) or bf16x6
       const std::string v = next();
@@ -213,11 +214,12 @@ static int run_case(int argc, char **argv) {
   if (!host_buffers) {
     xsmm_hip_force_split(split);
     if (xsmm_hip_set_tail_split(tail_split) < 0) { fprintf(stderr, "tpp_replay: --tail-split takes 0 .. 16, got %d\n", tail_split); return 2; }
+    if (xsmm_hip_set_edge_tiles(edge_tiles) < 0) { fprintf(stderr, "tpp_replay: --edge-tiles takes 0, 1, 6, 7, 9 or 10, got %d\n", edge_tiles); return 2; }
     xsmm_hip_force_variant(variant);
     xsmm_hip_set_async(1);
     xsmm_hip_set_tile_queue(queue);
-  } else if ((bf16 && vnni != 2) || split != -1 || tail_split != 0 || variant != -1 || chain || f32p) {
-    fprintf(stderr, "tpp_replay: --host-buffers takes its settings from the environment only (no --vnni 4 / --split / --tail-split / --variant / --chain / --f32-precision)\n");
+  } else if ((bf16 && vnni != 2) || split != -1 || tail_split != 0 || edge_tiles != 0 || variant != -1 || chain || f32p) {
+    fprintf(stderr, "tpp_replay: --host-buffers takes its settings from the environment only (no --vnni 4 / --split / --tail-split / --edge-tiles / --variant / --chain / --f32-precision)\n");
     return 2;
   }
   std::vector<int64_t> handle(L);
@@ -351,6 +353,7 @@ static int run_case(int argc, char **argv) {
   if (!host_buffers) xsmm_hip_set_f32_precision(old_f32p);
   xsmm_hip_force_split(-1);
   xsmm_hip_set_tail_split(0);
+  xsmm_hip_set_edge_tiles(0);
   for (void *p : act) CHECK(hipFree(p));
   for (void *p : W) CHECK(hipFree(p));
   for (void *p : B) CHECK(hipFree(p));

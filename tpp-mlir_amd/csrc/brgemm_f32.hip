@@ -692,6 +692,7 @@ hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         //
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
 hipError_t launch_f32_lw_tail(int tile, const GemmArgs &a, int tail_tiles, int split, hipStream_t s); // the same
+hipError_t launch_f32_lw_edge(int tile, const GemmArgs &a, hipStream_t s); // m or n not a multiple of the tile; hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw16(int tile, const GemmArgs &a, const WorkItem *items, int n_items, bool grouped, hipStream_t s); // brgemm_f32_lw16.hip: tile 0 = 32x16
 hipError_t launch_f32_x6(int tile, const GemmArgs &a, bool vec, hipStream_t s); // brgemm_f32_x6.hip: tile = variant - V_F32_X6_64x64
 hipError_t launch_bf16_grouped64(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s); // brgemm_bf16.hip
@@ -723,7 +724,8 @@ static std::atomic<int> g_strict_kernels{0};
 int set_strict_kernels(int on) { return g_strict_kernels.exchange(on != 0); }
 bool strict_kernels() { return g_strict_kernels.load(std::memory_order_relaxed) != 0; }
 static GemmPlanEnv gemm_plan_env() {
-  return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed), g_tail_split.load(std::memory_order_relaxed)};
+  return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed), g_tail_split.load(std::memory_order_relaxed),
+                     g_edge_tiles.load(std::memory_order_relaxed)};
 }
 bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, gemm_plan_env()); }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, gemm_plan_env()); }
@@ -781,7 +783,7 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
     case V_F32_64x64K2: return launch_fast<2, 2, 2, true>(a, s);
     default: return hipErrorInvalidValue;
     }
-  case GL_F32_LW: return launch_f32_lw(p.tile, a, s);
+  case GL_F32_LW: return p.edge ? launch_f32_lw_edge(p.tile, a, s) : launch_f32_lw(p.tile, a, s);
   case GL_F32_LW16: return launch_f32_lw16(p.tile, a, wi, n_items, grouped, s);
   case GL_F32_LW_GROUPED: return launch_f32_lw_grouped(p.tile, a, wi, n_items, p.split, s);
   case GL_F32_X6: return launch_f32_x6(p.tile, a, p.vec, s);
@@ -810,9 +812,27 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
 hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C, const void *D, int64_t br,
                        hipStream_t stream) {
   const uintptr_t ab = (uintptr_t)A | (uintptr_t)B, c = (uintptr_t)C, dp = (uintptr_t)D;
-  const GemmLaunch p = plan_gemm_call(d, br, GemmAlign{!(ab & 15), !(c & 15), !(c & 7), !(dp & 7), !(dp & 15)}, gemm_plan_env());
+  const GemmAlign al{!(ab & 15), !(c & 15), !(c & 7), !(dp & 7), !(dp & 15)};
+  GemmPlanEnv env = gemm_plan_env();
+  GemmLaunch p = plan_gemm_call(d, br, al, env);
   if (p.launcher == GL_NONE) return hipSuccess;
   const GemmArgs a = gemm_args(d, A, B, C, D, (int)(br < 0 ? 0 : br));
+  if (p.edge) { // a launch on edge tiles (xsmm_desc.h g_edge_tiles)
+    const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    if (e != hipErrorInvalidValue) {
+      if (e == hipSuccess) {
+        static const int bm[5] = {0, 64, 64, 32, 128}, bn[5] = {0, 64, 32, 32, 64}, variant[5] = {0, V_F32_LW_64x64K2, V_F32_LW_64x32K2, V_F32_LW_32x32K4, V_F32_LW_128x64};
+        g_edge_tiles_stats[1].store((d.m + bm[p.tile] - 1) / bm[p.tile], std::memory_order_relaxed);
+        g_edge_tiles_stats[2].store((d.n + bn[p.tile] - 1) / bn[p.tile], std::memory_order_relaxed);
+        g_edge_tiles_stats[3].store(variant[p.tile], std::memory_order_relaxed);
+        g_edge_tiles_stats[0].fetch_add(1, std::memory_order_relaxed);
+      }
+      return g_last_refined.store(p.text, std::memory_order_relaxed), e;
+    }
+    (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
+    env.edge_tiles = 0;
+    p = plan_gemm_call(d, br, al, env);
+  }
   const char *text = p.text;
   if (p.split > 1 && (p.launcher == GL_F32_LW || p.launcher == GL_F32_LW16)) { // a SPLIT launch (its scratch block may be missing)
     const hipError_t e = launch_f32_lw_split(p.launcher == GL_F32_LW ? p.tile : 3, a, p.split, stream);

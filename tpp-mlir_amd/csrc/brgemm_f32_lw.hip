@@ -328,6 +328,96 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + 2 * NL)) void brgemm_f32_lw_ch
   }
 }
 
+// ---- EDGE TILES: a whole-layer call whose m or n is not a multiple of the tile (opt-in, xsmm_hip_set_edge_tiles) ----------------
+// One workgroup per tile of the ceil(m / BM) x ceil(n / BN) grid, m >= BM, n >= BN, n a multiple of 4. A 32x32 MFMA accumulator computes
+// each output element from its own row of A and column of B, in an order that does not depend on where the tile sits - so the last
+// tile of a row or column of tiles is SHIFTED BACK inside the matrix: tile (tm, tn) computes the BM x BN block at m0 = min(tm BM, m -
+// BM), n0 = min(tn BN, n - BN) (n0 stays a multiple of 4: the 16-byte pieces of B, of the bias row and of C keep their alignment) and
+// OWNS rows >= tm BM - m0 and columns >= tn BN - n0 of it. Every load of the loader waves stays inside rows [0, m) of A and columns
+// [0, n) of B without a clamp in their issue loop; the LDS images, the chunk loop and the K-group combine are the tile's, untouched. The
+// epilogue joins C (beta = 1) and stores only what the tile owns: the rest of its block belongs to the neighbour, which may already have
+// rewritten it. No scratch block, no counters, no waiting - legal on a captured stream and in strict mode.
+// A kernel of its own around LwTile, like the chain kernel, and not a tenth template argument of brgemm_f32_lw: every instance of that
+// kernel keeps its symbol and its code (tests/test_tail_split_host.py finds the tail instances by their mangled names).
+template <int WM, int WN, int WK, int NL, int NSLOT, int NLB>
+__global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw_edge(GemmArgs p) {
+  using Tile = LwTile<WM, WN, WK, NSLOT>;
+  constexpr int NMW = Tile::NMW, BM = Tile::BM, BN = Tile::BN, IPG = Tile::IPG;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int hw_wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave = hw_wave < NL + NLB ? NMW + hw_wave : hw_wave - (NL + NLB); // loaders first, as in brgemm_f32_lw
+  // XCD-blocked (8, bn, bm) or plain (1, tiles_n, tiles_m) grid over the ceil-divided tile counts, as brgemm_f32_lw's
+  const int tm = (int)(blockIdx.x >> p.xn_shift) * p.tiles_m + (int)blockIdx.z;
+  const int tn = (int)(blockIdx.x & ((1u << p.xn_shift) - 1)) * p.tiles_n + (int)blockIdx.y;
+  const int m0 = tm * BM < p.m - BM ? tm * BM : p.m - BM, n0 = tn * BN < p.n - BN ? tn * BN : p.n - BN;
+  const int own_r = tm * BM - m0, own_c = tn * BN - n0; // 0, 0 for every tile but the last of a ragged row / column of tiles
+  const float *__restrict__ A = (const float *)p.A;
+  const float *__restrict__ B = (const float *)p.B;
+  float *__restrict__ C = (float *)p.C;
+  const int kchunks = p.k / LW_BK;
+  const int T = p.br * kchunks;
+
+  if (wave >= NMW) {
+    typename Tile::template Loader<NL, NLB> ld(wave - NMW, lane, A, B, m0, n0, (int)p.lda, (int)p.ldb, p.stride_a, p.stride_b, kchunks, false, BN);
+    lw_loader_schedule<NSLOT>(T, [&](int slot) __attribute__((always_inline)) { ld.issue(slot); },
+                              [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); });
+    return;
+  }
+
+  const typename Tile::Wave w(wave, lane);
+  const int wk = w.wk, wm = w.wm, wn = w.wn;
+  const int li = lane & 31, lh = lane >> 5;
+  const __amdgpu_buffer_rsrc_t rsrcC =
+      __builtin_amdgcn_make_buffer_rsrc((void *)(C + (int64_t)m0 * p.ldc + n0), 0, 0x7fffffff, 0x00020000);
+  const unsigned voffC = (unsigned)(((wm * 32 + 4 * lh) * (int)p.ldc + wn * 32 + li) * 4);
+  const unsigned ldcb = (unsigned)((int)p.ldc * 4);
+  // accumulator register r of a lane: row wm 32 + 4 lh + (r & 3) + 8 (r >> 2), column wn 32 + li of the tile
+  const bool col_owned = wn * 32 + li >= own_c;
+  const int row_first = own_r - (wm * 32 + 4 * lh); // register r is owned if (r & 3) + 8 (r >> 2) >= row_first
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  float bias = 0.0f;
+  if constexpr (WK == 1) {
+    if (p.ep & EP_BIAS) bias = ((const float *)p.D)[n0 + wn * 32 + li];
+  }
+  constexpr bool BIAS_EARLY = WK > 1 && WM * WN * WK <= 4; // (brgemm_f32_lw)
+  f32x4 bias4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  if constexpr (BIAS_EARLY) {
+    if (p.ep & EP_BIAS) bias4 = *(const f32x4 *)((const float *)p.D + n0 + wn * 32 + 4 * (lane & 7));
+  }
+  // beta = 1: C joins the chain of K group 0 - only where the tile owns it; elsewhere the neighbour may already have stored
+  if (wk == 0 && !(p.ep & EP_BETA0) && col_owned) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if ((r & 3) + 8 * (r >> 2) >= row_first)
+        acc[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrcC, voffC, (unsigned)((r & 3) + 8 * (r >> 2)) * ldcb, 0));
+  }
+
+  __builtin_amdgcn_s_barrier(); // chunk 0 published
+  __builtin_amdgcn_sched_barrier(0);
+  if (T > 0) Tile::mfma_chunks(acc, T, w);
+
+  if constexpr (WK > 1) {
+    Tile::park_partials(acc, w);
+    if constexpr (!BIAS_EARLY) {
+      if (p.ep & EP_BIAS) bias4 = *(const f32x4 *)((const float *)p.D + n0 + wn * 32 + 4 * (lane & 7));
+    }
+    f32x4 part[IPG];
+    Tile::sum_partials(part, w);
+    Tile::finish_owned(part, bias4, p.ep, rsrcC, (int)p.ldc, own_r, own_c, w);
+    return;
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float v = acc[r] + bias;
+    if (p.ep & EP_RELU) v = v > 0.0f ? v : 0.0f;
+    if (col_owned && (r & 3) + 8 * (r >> 2) >= row_first)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrcC, voffC, (unsigned)((r & 3) + 8 * (r >> 2)) * ldcb, LW_C_AUX);
+  }
+}
+
 // ---- launchers --------------------------------------------------------------------------------------------------------------
 // The XCD blocks of a whole-layer grid: xm x xn = 8 blocks of tiles_m/xm x tiles_n/xn tiles, one per XCD. Each XCD's L2 then fetches
 // m/xm rows of A and n/xn columns of B: the split that minimises m/xm + n/xn - 4 x 2 for square outputs (C2; ties keep it: rounds
@@ -381,6 +471,11 @@ template <int WM, int WN, int WK, int NL> struct LwChain {
   using Tile = LwTile<WM, WN, WK>;
   static constexpr int NT = 64 * (Tile::NMW + 2 * NL);
   static constexpr auto kernel = brgemm_f32_lw_chain<WM, WN, WK, NL>;
+};
+template <int WM, int WN, int WK, int NL, int NSLOT, int NLB> struct LwEdge {
+  using Tile = LwTile<WM, WN, WK, NSLOT>;
+  static constexpr int NT = 64 * (Tile::NMW + NL + NLB);
+  static constexpr auto kernel = brgemm_f32_lw_edge<WM, WN, WK, NL, NSLOT, NLB>;
 };
 template <class I, class... Args> static hipError_t lw_launch(dim3 grid, hipStream_t s, const Args &...args) {
   static std::atomic<unsigned long long> lds_set{0};
@@ -441,6 +536,17 @@ template <int WM, int WN, int WK, int NL, int NLB> static hipError_t launch_lw_t
   return lw_launch<I>(dim3((unsigned)(body + (long long)tail_tiles * S)), s, args, (const WorkItem *)nullptr);
 }
 
+// whole-layer call on EDGE tiles (brgemm_f32_lw_edge): ceil(m / BM) x ceil(n / BN) workgroups in XCD blocks where the tile counts divide
+template <int WM, int WN, int WK, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL> static hipError_t launch_lw_edge_t(const GemmArgs &a, hipStream_t s) {
+  using I = LwEdge<WM, WN, WK, NL, NSLOT, NLB>;
+  constexpr int BM = I::Tile::BM, BN = I::Tile::BN;
+  if (a.m < BM || a.n < BN || (a.n & 3) || a.k <= 0 || a.k % LW_BK || a.br < 1) return hipErrorInvalidValue;
+  GemmArgs args = a;
+  const bool blocks = lw_xcd_grid(args, (a.m + BM - 1) / BM, (a.n + BN - 1) / BN);
+  if (args.tiles_m > 65535 || args.tiles_n > 65535) return hipErrorInvalidValue;
+  return lw_launch<I>(dim3(blocks ? 8 : 1, args.tiles_n, args.tiles_m), s, args);
+}
+
 // tile as in launch_f32_lw; split > 1: that many workgroups per output tile (K-split tiles 1 .. 3 only); n may end inside the last tile
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s) {
   if (split > 1) {
@@ -479,6 +585,18 @@ hipError_t launch_f32_lw_tail(int tile, const GemmArgs &a, int tail_tiles, int s
   case 1: return launch_lw_tail_t<2, 2, 2, 2, 2>(a, tail_tiles, split, s);
   case 2: return launch_lw_tail_t<2, 1, 4, 2, 1>(a, tail_tiles, split, s);
   case 3: return launch_lw_tail_t<1, 1, 4, 1, 1>(a, tail_tiles, split, s);
+  default: return hipErrorInvalidValue;
+  }
+}
+
+// whole-layer call on edge tiles; tile and loader waves per tile as launch_f32_lw (1 .. 4). hipErrorInvalidValue: not launched - m or n
+// below the tile, n not a multiple of 4, k not in 64-k chunks, no batch
+hipError_t launch_f32_lw_edge(int tile, const GemmArgs &a, hipStream_t s) {
+  switch (tile) {
+  case 1: return launch_lw_edge_t<2, 2, 2, 2>(a, s);
+  case 2: return launch_lw_edge_t<2, 1, 4, 2, LW_NSLOT, 1>(a, s);
+  case 3: return launch_lw_edge_t<1, 1, 4>(a, s);
+  case 4: return launch_lw_edge_t<4, 2, 1, 2, 3>(a, s);
   default: return hipErrorInvalidValue;
   }
 }

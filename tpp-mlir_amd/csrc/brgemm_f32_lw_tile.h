@@ -262,6 +262,24 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
       if (ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrcC, piece_off(w, j, ldc), 0, LW_C_AUX);
     }
   }
+  // EDGE tiles (brgemm_f32_lw_edge): does the tile own this lane's piece j - rows >= own_r and columns >= own_c of the tile (own_c a
+  // multiple of 4: a 16-byte piece is owned whole or not at all)
+  static __device__ __forceinline__ bool piece_owned(const Wave &w, int j, int own_r, int own_c) {
+    return w.wm * 32 + piece_row(w, j) >= own_r && w.wn * 32 + 4 * (w.lane & 7) >= own_c;
+  }
+  // finish for an edge tile: the same values, stored only where the tile owns them
+  static __device__ __forceinline__ void finish_owned(const f32x4 (&part)[IPG], f32x4 bias4, int ep, __amdgpu_buffer_rsrc_t rsrcC, int ldc, int own_r, int own_c,
+                                                      const Wave &w) {
+#pragma unroll
+    for (int j = 0; j < IPG; ++j) {
+      f32x4 v = part[j] + bias4;
+      if (ep & EP_RELU) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
+      }
+      if (piece_owned(w, j, own_r, own_c)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrcC, piece_off(w, j, ldc), 0, LW_C_AUX);
+    }
+  }
 };
 
 } // namespace tpp

@@ -169,6 +169,37 @@ static int choose_bf16_small_split(long long t32, long long steps, const GemmPla
   return S;
 }
 
+// EDGE TILES (xsmm_hip_set_edge_tiles, opt-in): a whole-layer f32 call whose m or n no loader-wave tile divides - planned on the generic
+// kernel - on the loader-wave tiles all the same: the last tile of a row or column of tiles is shifted back inside the matrix and stores
+// only the elements no other tile owns (brgemm_f32_lw.hip brgemm_f32_lw_edge). A tile is a candidate when m >= BM and n >= BN. Mode 1:
+// the comparisons pick_f32_variant makes among 128x64, 64x64 + K2, 64x32 + K4 and 32x32 + K4 - rounds of workgroups, the 1.85x round of
+// 128x64, f32_32x32_beats_64x32, a tile per CU before a larger tile is taken - on CEIL-DIVIDED tile counts (the half-width tiles and
+// the split launches have no edge form). Modes 6, 7, 9, 10 (tests, measurements): that GemmVariant's tile. Returns the variant, -1 = none.
+// No rule of mode 1 is fitted to a ragged shape yet: profiles/edge_tiles_ab.txt.
+static int choose_f32_edge_variant(const GemmDesc &d, int mode, int64_t cus) {
+  const int64_t m = d.m, n = d.n;
+  auto tiles = [&](int bm, int bn) { return (m >= bm && n >= bn) ? ((m + bm - 1) / bm) * ((n + bn - 1) / bn) : 0; };
+  if (mode == V_F32_LW_64x64K2) return tiles(64, 64) > 0 ? mode : -1;
+  if (mode == V_F32_LW_64x32K2) return tiles(64, 32) > 0 ? mode : -1;
+  if (mode == V_F32_LW_32x32K4) return tiles(32, 32) > 0 ? mode : -1;
+  if (mode == V_F32_LW_128x64) return tiles(128, 64) > 0 ? mode : -1;
+  if (mode != 1) return -1;
+  if (tiles(64, 64) >= cus) {
+    const int64_t r64 = rounds(tiles(64, 64), cus), r128 = rounds(tiles(128, 64), cus);
+    if (tiles(128, 64) > 0 && 1.85 * (double)r128 < (double)r64) return V_F32_LW_128x64;
+    return V_F32_LW_64x64K2;
+  }
+  if (tiles(64, 32) >= cus) {
+    if (tiles(32, 32) > 0 && f32_32x32_beats_64x32(tiles(32, 32), tiles(64, 32), cus)) return V_F32_LW_32x32K4;
+    return V_F32_LW_64x32K2;
+  }
+  if (tiles(32, 32) > 0 && tiles(32, 32) >= tiles(64, 64) * 2 && tiles(64, 32) < cus) return V_F32_LW_32x32K4;
+  if (tiles(64, 64) > 0) return V_F32_LW_64x64K2;
+  if (tiles(64, 32) > 0) return V_F32_LW_64x32K2;
+  if (tiles(32, 32) > 0) return V_F32_LW_32x32K4;
+  return -1;
+}
+
 static int pick_f32_variant(const GemmDesc &d, int64_t cus) {
   if (d.k <= 0 || d.k % BK) return V_GENERIC;
   if (!f32_lw_operands_ok(d)) return V_GENERIC;
@@ -469,6 +500,21 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
   // tries the half-width lw16 tiles first, a single invoke keeps the pair / ragged 32x32 tile it has always run on.
   const GenericOk g = generic_ok(d, al.ab16);
   const bool f32_lw = g.vec && !d.generic_forced && d.m % 32 == 0 && f32_lw_operands_ok(d);
+  // edge tiles, if asked for (choose_f32_edge_variant): a call no tile divides. Decided here only - what is queued, grouped, chained or
+  // folded never sees it -, from the descriptor, the batch count, the pointers' alignment and the CU count: allowed in strict mode. A
+  // forced split count and the tail split do not apply. The launcher's own checks: launch_f32_lw_edge.
+  if (env.edge_tiles != 0 && d.dtype == DT_F32 && !d.vnni_b && !d.vnni_c && !d.generic_forced && d.variant == V_GENERIC && d.k > 0 &&
+      d.k % BK == 0 && br >= 1 && f32_lw_operands_ok(d) && d.ldc % 4 == 0 && d.n % 4 == 0 && al.ab16 && al.c16 && (!d.bias || al.d16)) {
+    static const char *const edge_names[5] = {"", "brgemm_f32_lw<64x64,k2>, edge tiles", "brgemm_f32_lw<64x32,k4>, edge tiles",
+                                              "brgemm_f32_lw<32x32,k4>, edge tiles", "brgemm_f32_lw<128x64,k1>, edge tiles"};
+    const int ev = choose_f32_edge_variant(d, env.edge_tiles, cus);
+    if (ev >= 0) {
+      const int tile = ev == V_F32_LW_128x64 ? 4 : ev == V_F32_LW_32x32K4 ? 3 : ev - V_F32_LW_64x64;
+      GemmLaunch l = launch(GL_F32_LW, tile, edge_names[tile]);
+      l.edge = true;
+      return l;
+    }
+  }
   // a SINGLE invoke of a 32-k f32 tile with an even batch count: the kernel its group would run on in the tile queue (the
   // loader-wave pair mode, tile chosen as plan_gemm_group does for one item) - queue on and queue off then add in the same order
   if (f32_lw && f32_pairs_ok(d) && br >= 2 && !(br & 1) && d.n % 32 == 0) {

@@ -527,6 +527,10 @@ extern "C" void xsmm_hip_fold_epilogue_stats(int64_t out[3]) {
 }
 extern "C" int xsmm_hip_force_split(int v) { return tpp::force_gemm_split(v); }
 extern "C" int xsmm_hip_set_tail_split(int mode) { return mode < 0 || mode > 16 ? -1 : tpp::g_tail_split.exchange(mode); }
+extern "C" int xsmm_hip_set_edge_tiles(int mode) { return tpp::edge_tiles_mode_ok(mode) ? tpp::g_edge_tiles.exchange(mode) : -1; }
+extern "C" void xsmm_hip_edge_tiles_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_tiles_stats[i].load(std::memory_order_relaxed);
+}
 extern "C" void xsmm_hip_tail_split_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_tail_split_stats[i].load(std::memory_order_relaxed);
 }

@@ -113,6 +113,8 @@ _SIGNATURES = {
     "xsmm_hip_force_split": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_set_tail_split": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_tail_split_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_edge_tiles": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_edge_tiles_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_fold_transpose_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_epilogue": (ctypes.c_int, [ctypes.c_int]),
@@ -344,6 +346,17 @@ class XsmmRuntime:
         """(launches with a split tail; tail tiles, workgroups per tail tile, body tiles of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_tail_split_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_edge_tiles(self, mode):
+        """f32 whole-layer calls whose m or n no tile divides, on the loader-wave tiles: 0 off (default), 1 the tile rule, 6 / 7 / 9 / 10
+        the tile of that kernel variant; returns the previous mode, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_edge_tiles(mode)
+
+    def edge_tiles_stats(self):
+        """(edge launches; tile rows, tile columns, variant number of the tile of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_edge_tiles_stats(out)
         return tuple(int(v) for v in out)
 
     def set_fold_transpose(self, enable):
