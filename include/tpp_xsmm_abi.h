@@ -360,7 +360,26 @@ TPP_XSMM_EXPORT void xsmm_hip_tail_split_stats(int64_t out[4]);
  * descriptor, the batch count, the pointers' alignment and the CU count only, so it is made in strict mode too.
  * xsmm_hip_last_refined_kernel reads "brgemm_f32_lw<64x64,k2>, edge tiles" (<64x32,k4>, <32x32,k4>, <128x64,k1>).
  * _stats: out[0] edge launches since process start; of the most recent one: [1] tile rows, [2] tile columns, [3] the variant number
- * of its tile (6, 7, 9, 10). */
+ * of its tile (6, 7, 9, 10).
+ * bf16 (modes 2 and 20 .. 23; modes 1, 6, 7, 9, 10 leave every bf16 call alone). A whole-layer bf16 call no loader-wave tile divides - m not a
+ * multiple of 32 or n not of 64 - is planned on the generic kernel or, with m and n multiples of 32, on the latency-bound 32x32 K-split
+ * kernel. Under these modes it runs on a bf16 loader-wave tile (32x64 + K2, 64x64, 64x128, 128x128; VNNI-2, flat or VNNI-4 B image) the
+ * same way: one launch of ceil(m / BM) x ceil(n / BN) workgroups, the last tile of a row or column of tiles shifted back to end at the
+ * matrix edge; it stores only the rows and 16-byte pieces no other tile owns (with beta = 1 it reads C for its whole block and drops what
+ * it does not own). The bits are those of the same tile on the shape padded up to whole tiles; no scratch, no counters, no waits.
+ * A call takes bf16 edge tiles when all of this holds: bf16, no VNNI C, no transposed operand, neither a variant nor the generic kernel
+ * forced, planned on the generic or the 32x32 K-split kernel, m % 32 != 0 or n % 64 != 0, a VNNI-2, flat or VNNI-4 B, the leading
+ * dimensions, strides and lane offsets that image's loader-wave tiles ask for (lda / ldc / strides multiples of 8, ldb of 4 / 8 / 2,
+ * lda, ldc < 2^22, ldb < 2^21 / 2^21 / 2^20), k a positive multiple of 64, batch count >= 1, n a multiple of 8, A, B and C 16-byte and
+ * a bias row 8-byte aligned, and m >= BM, n >= BN for the tile. Everything else - every tile-queue group, quad and chain too - runs as
+ * with the mode off.
+ * mode 2 = mode 1's rule for f32 calls AND, for bf16 calls, the cheapest tile that fits by the fitted model of the divisible shapes
+ * (rounds of workgroups over ceil-divided tile counts x (a + b x the call's 64-k chunks); ties to the larger tile); 20 / 21 / 22 / 23 =
+ * the bf16 tile 32x64 + K2 / 64x64 / 64x128 / 128x128 wherever it fits, whatever the B image (a test / measurement switch; f32 calls
+ * run as with the mode off).
+ * xsmm_hip_last_refined_kernel reads "brgemm_bf16_lw<64x64>, edge tiles" (<32x64,k2>, <64x128>, <128x128>; brgemm_bf16_lw_flatb<...> and
+ * brgemm_bf16_lw_vnni4<...> for the other images). _stats [3] is then the variant number of the tile WITH its image: 20 + t VNNI-2,
+ * 24 + t flat, 28 + t VNNI-4. */
 TPP_XSMM_EXPORT int xsmm_hip_set_edge_tiles(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_edge_tiles_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a

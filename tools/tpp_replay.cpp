@@ -100,11 +100,11 @@ static int run_case(int argc, char **argv) {
       if (fold < 0 || fold > 2) { fprintf(stderr, "tpp_replay: --fold takes 0, 1 or 2\n"); return 2; }
     }
     else if (a == "--bf16") bf16 = true; // mlir-gen --float-type=bf16 --vnni=2: bf16 storage, W in VNNI-2 blocks
-    else if (a == "--vnni") vnni = atoi(next()); // --vnni=4 (benchmarks/config/*: the *_dp4_* rows): W in [K/4][N][4] blocks
+    else if (a == "--vnni") vnni = atoi(next()); // --vnni=4 (benchmarks/config/*: the *_dp4_* rows): W in [K/4][N][4] blocks; --vnni 0: W flat [K][N] (no VNNI flag on the dispatch)
     else if (a == "--kernel") kernel_args = std::string(next()) == "args"; // const (default): zero fill folded into BETA_0; args: C += ...
     else if (a == "--split") split = atoi(next());     // xsmm_hip_force_split for this case (-1: the runtime's model)
     else if (a == "--tail-split") tail_split = atoi(next()); // xsmm_hip_set_tail_split for this case (0: off, 1: the model, 2 .. 16: workgroups per tail tile)
-    else if (a == "--edge-tiles") edge_tiles = atoi(next()); // xsmm_hip_set_edge_tiles for this case (0: off, 1: the tile rule, 6 / 7 / 9 / 10: that variant's tile)
+    else if (a == "--edge-tiles") edge_tiles = atoi(next()); // xsmm_hip_set_edge_tiles for this case (0: off, 1: the f32 tile rule, 6 / 7 / 9 / 10: that f32 variant's tile, 2: the f32 and bf16 rules, 20 .. 23: that bf16 tile)
     else if (a == "--variant") variant = atoi(next()); // xsmm_hip_force_variant at dispatch (-1: the runtime's choice)
     else if (a == "--f32-precision") { // xsmm_hip_set_f32_precision for this case's dispatches: exact (default) or bf16x6
       const std::string v = next();
@@ -206,15 +206,15 @@ static int run_case(int argc, char **argv) {
   for (int l = 0; l <= L; ++l) act[l] = dalloc(padx * (size_t)batch * layers[l], 1.0f);
   for (int l = 0; l < L; ++l) { W[l] = dalloc(padx * (size_t)layers[l] * layers[l + 1], 1.0f / (float)layers[l]); B[l] = dalloc((size_t)layers[l + 1], 0.5f); }
 
-  if (bf16) gflags |= XSMM_GEMM_WIRE_VNNI_B;
+  if (bf16 && vnni != 0) gflags |= XSMM_GEMM_WIRE_VNNI_B; // (--vnni 0: W flat [K][N], no VNNI flag - with constant fills the same bytes)
   // --host-buffers: NO xsmm_hip_* call before or inside the timed region - the program below is the reference's 13 + 2 symbols only,
   // the runtime's modes come from the environment (TPP_HIP_ASYNC / TPP_HIP_TILE_QUEUE / TPP_HIP_HOST_CACHE), like under an unmodified tpp-run
-  const int old_vf = host_buffers ? 2 : xsmm_hip_set_vnni_factor(bf16 ? vnni : 2);
+  const int old_vf = host_buffers ? 2 : xsmm_hip_set_vnni_factor(bf16 && vnni ? vnni : 2);
   const int old_f32p = host_buffers ? 0 : xsmm_hip_set_f32_precision(f32p);
   if (!host_buffers) {
     xsmm_hip_force_split(split);
     if (xsmm_hip_set_tail_split(tail_split) < 0) { fprintf(stderr, "tpp_replay: --tail-split takes 0 .. 16, got %d\n", tail_split); return 2; }
-    if (xsmm_hip_set_edge_tiles(edge_tiles) < 0) { fprintf(stderr, "tpp_replay: --edge-tiles takes 0, 1, 6, 7, 9 or 10, got %d\n", edge_tiles); return 2; }
+    if (xsmm_hip_set_edge_tiles(edge_tiles) < 0) { fprintf(stderr, "tpp_replay: --edge-tiles takes 0, 1, 2, 6, 7, 9, 10 or 20 .. 23, got %d\n", edge_tiles); return 2; }
     xsmm_hip_force_variant(variant);
     xsmm_hip_set_async(1);
     xsmm_hip_set_tile_queue(queue);

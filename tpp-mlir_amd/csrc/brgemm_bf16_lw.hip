@@ -82,6 +82,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
                                            const void *it_A = nullptr, const void *it_B = nullptr, int it_br = 0, unsigned q_delta = 0) {
   static_assert(GRP != 2 || (BM == 128 && BN == 128 && NL == 1 && (FB == 0 || FB == 4)), "quads: the 128x128 tile, one loader wave per panel, VNNI-2 / VNNI-4 B");
   chain_kernarg_t &p = *pp;
+  constexpr bool ITEMS = GRP == 1 || GRP == 2; // operands from an item (GRP = 3, edge tiles: the argument block's, as GRP = 0)
   constexpr int A_SLOT = BM * 128, SLOT = (BM + BN) * 128;
   // SUP = chunks per barrier (the unit everything below counts in: a "chunk" of this function is SUP 64-k chunks, a "slot" SUP
   // consecutive ring slots). SUP = 2 halves the barrier count and the loader's per-iteration scalar work for the small tiles, whose
@@ -113,7 +114,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
     kc = 0;                                                                                                            \
     if (IS_A) {                                                                                                        \
       const int64_t lda_ = (l) == 0 ? p.lda : p.L[(l) > 0 ? (l)-1 : 0].ldc;                                            \
-      const unsigned short *A_ = (const unsigned short *)(GRP ? it_A : (l) == 0 ? p.A : p.L[(l) > 0 ? (l)-1 : 0].C);    \
+      const unsigned short *A_ = (const unsigned short *)(ITEMS ? it_A : (l) == 0 ? p.A : p.L[(l) > 0 ? (l)-1 : 0].C);  \
       g = A_ + (int64_t)(m0 + 8 * part) * lda_;                                                                        \
       d_in = BLW_BK;                                                                                                   \
       d_wrap = p.L[l].stride_a - (int64_t)(kchunks - 1) * BLW_BK;                                                      \
@@ -129,7 +130,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       /* covers rows (512/BN)*v ..: lane -> row lane / (BN/8), 16-byte piece lane % (BN/8); the 64-byte blocks of a row are */ \
       /* XOR-swizzled with the row (BN = 128: row & 3, BN = 64: (row >> 1) & 1) on the SOURCE side, like the A panel */ \
       constexpr int RPT_ = 512 / BN, PPR_ = BN / 8;                                                                    \
-      g = (const unsigned short *)(GRP ? it_B : p.L[l].B) + n0 + (int64_t)part * RPT_ * p.L[l].ldb;                    \
+      g = (const unsigned short *)(ITEMS ? it_B : p.L[l].B) + n0 + (int64_t)part * RPT_ * p.L[l].ldb;                  \
       d_in = (int64_t)BLW_BK * p.L[l].ldb;                                                                             \
       d_wrap = p.L[l].stride_b - (int64_t)(kchunks - 1) * d_in;                                                        \
       const int row_ = lane / PPR_, piece_ = lane % PPR_;                                                              \
@@ -140,14 +141,14 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       /* VNNI-4 B ([k/4][ldb][4]): image = the chunk's 16 k-group rows of BN * 8 bytes as they are; instruction v covers */ \
       /* k-group rows (128/BN)*v ..: lane -> row lane / (BN/2), 16-byte piece lane % (BN/2). A fragment is two 8-byte reads. */ \
       constexpr int RPI4_ = 128 / BN, PPR4_ = BN / 2;                                                                  \
-      g = (const unsigned short *)(GRP ? it_B : p.L[l].B) + 4 * (int64_t)n0 + (int64_t)part * RPI4_ * 4 * p.L[l].ldb;  \
+      g = (const unsigned short *)(ITEMS ? it_B : p.L[l].B) + 4 * (int64_t)n0 + (int64_t)part * RPI4_ * 4 * p.L[l].ldb;\
       d_in = (int64_t)BLW_BK * p.L[l].ldb;                                                                             \
       d_wrap = p.L[l].stride_b - (int64_t)(kchunks - 1) * d_in;                                                        \
       vo0 = vo1 = (unsigned)((lane / PPR4_) * (int)p.L[l].ldb * 8 + ((lane % PPR4_) << 4));                            \
       if (GRP == 2) vo0 = vo1 = (unsigned)(((lane & 31) << 4)) + ((lane & 32) ? q_delta : 0u); /* 64 pieces = one k-group row: 32 per item */ \
       step = (unsigned)(NL * RPI4_ * (int)p.L[l].ldb * 8);                                                             \
     } else {                                                                                                           \
-      g = (const unsigned short *)(GRP ? it_B : p.L[l].B) + 2 * (int64_t)n0 + (int64_t)part * RPI * 2 * p.L[l].ldb;    \
+      g = (const unsigned short *)(ITEMS ? it_B : p.L[l].B) + 2 * (int64_t)n0 + (int64_t)part * RPI * 2 * p.L[l].ldb;  \
       d_in = (int64_t)(BLW_BK / 2) * 2 * p.L[l].ldb;                                                                   \
       d_wrap = p.L[l].stride_b - (int64_t)(kchunks - 1) * d_in;                                                        \
       /* instruction v covers pair-rows RPI*v ..: lane -> pair-row lane / (BN/4), 16-byte piece lane % (BN/4) */       \
@@ -189,7 +190,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   const bool poller = MULTI && IS_A && part == 0;
   int slot = 0, s0 = 0; // next ring slot to fill; slot of the current layer's chunk 0 (the layers follow each other through the ring)
   for (int lc = 0; lc < L; ++lc) {
-    const int T = (GRP ? it_br : p.L[lc].br) * (p.L[lc].k / BLW_BK) / SUP; // (a multiple of SUP: the launcher picks SUP = 1 otherwise)
+    const int T = (ITEMS ? it_br : p.L[lc].br) * (p.L[lc].k / BLW_BK) / SUP; // (a multiple of SUP: the launcher picks SUP = 1 otherwise)
     int pre = NSLOT - 2; // chunks of this layer already requested by the run-ahead of the previous layer's tail
     if (state_layer != lc) {
       BLW_LOAD_STATE(lc);
@@ -259,6 +260,10 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
 template <int WM, int WN, int WK, int TM, int TN, int NSLOT, int NLA, int NLB, int SUP, bool MULTI, int FLATB = 0, int GRP = 0>
 __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_lw(ChainArgs p_by_value) {
   static_assert(!GRP || !MULTI, "a grouped launch is a set of single layers");
+  static_assert(GRP >= 0 && GRP <= 3, "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles");
+  // operands and batch count from an item (GRP = 1, 2). GRP = 3 (EDGE TILES, a whole layer whose m or n the tile does not divide) has
+  // no items: everything from the argument block, as GRP = 0
+  constexpr bool ITEMS = GRP == 1 || GRP == 2;
   static_assert(GRP != 2 || (WM == 2 && WN == 2 && WK == 1 && TM == 2 && TN == 2), "quads: every MFMA wave owns one item's 64x64 output");
   chain_kernarg_t *pp = (chain_kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr(); // = &p_by_value (the only explicit argument)
   chain_kernarg_t &p = *pp;
@@ -317,7 +322,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
     q_da = w.da;
     q_db = w.db;
     tm = tn = 0;
-  } else if constexpr (GRP) {
+  } else if constexpr (GRP == 1) {
     // (plain order: workgroup b = the b-th tile of the list. Handing XCD x the x-th EIGHTH of the list - contiguous block rows of the
     // layer - was measured and is WORSE for the reference's shapes, 1024 x 2560 x 1024 15.0 -> 18.1 us: with row-major items and a
     // column count that is a multiple of 8 the plain order already gives every XCD its own eighth of the COLUMNS, i.e. of W, the
@@ -359,9 +364,14 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // gets ceil(n / BN) column tiles, the LAST one moved left to end at column n - it recomputes the columns it shares with its
   // neighbour (panels in bounds, no masking of loads) and stores only its own (skip_cols: the first columns of its tile are the
   // neighbour's). Everything else: skip_cols = 0.
-  const int m0 = tm * BM;
-  const int n0 = (GRP == 1 && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
+  // EDGE TILES (GRP = 3, xsmm_hip_set_edge_tiles): the grid is ceil(m / BM) x ceil(n / BN); the last tile of a row / column of tiles is
+  // moved up / left to end at row m / column n. Loaders, LDS images and the K loop see m0 and n0 only and stay inside rows [0, m) and
+  // columns [0, n); the tile stores the rows >= own_row and the 16-byte pieces at columns >= own_col of its block (TILE-relative: the
+  // tiles have several wave columns) - the others are the neighbour's. n0 is a multiple of 8 (the planner asks for n % 8 == 0).
+  const int m0 = (GRP == 3 && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
+  const int n0 = ((GRP == 1 || GRP == 3) && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
   [[maybe_unused]] const int skip_cols = tn * BN - n0;
+  [[maybe_unused]] const int own_row = tm * BM - m0, own_col = tn * BN - n0;
   const int L = MULTI ? p.nlayers : 1;
 
   if (wave >= NMW) {
@@ -518,9 +528,9 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   int s0 = 0; // ring slot of the current layer's chunk 0
   for (int l = 0; l < L; ++l) {
     const auto &Y = p.L[l];
-    const int T = (GRP ? it_br : Y.br) * (Y.k / BLW_BK);
+    const int T = (ITEMS ? it_br : Y.br) * (Y.k / BLW_BK);
     const int ep = Y.ep;
-    unsigned short *__restrict__ C = (unsigned short *)(GRP ? it_C : Y.C);
+    unsigned short *__restrict__ C = (unsigned short *)(ITEMS ? it_C : Y.C);
     const unsigned ldcb = (unsigned)((int)Y.ldc * 2);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -535,7 +545,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         biasw[j][g] = u32x2_lw{0u, 0u};
-        if (ep & EP_BIAS) biasw[j][g] = *(const u32x2_lw *)((const unsigned short *)(GRP ? it_D : Y.D) + n0 + ((GRP == 2 ? 0 : wn * TN) + j) * 32 + 8 * g + 4 * lh);
+        if (ep & EP_BIAS) biasw[j][g] = *(const u32x2_lw *)((const unsigned short *)(ITEMS ? it_D : Y.D) + n0 + ((GRP == 2 ? 0 : wn * TN) + j) * 32 + 8 * g + 4 * lh);
       }
     if (MULTI && NLA > 1 && l > 0) __builtin_amdgcn_s_barrier(); // S2 (the loaders' rendezvous after the seam wait)
     __builtin_amdgcn_s_barrier(); // P: chunk 0 published
@@ -706,6 +716,9 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
           const u32x4 v = *(const u32x4 *)(ot + row * ES + ch * 16);
           const unsigned voff = (unsigned)(32 * i + row) * ldcb + (unsigned)(ch * 16);
           if (GRP == 1 && ch * 8 < skip_cols) continue; // (a ragged item's last column tile: these columns are the neighbour tile's)
+          // (edge tiles: rows and 16-byte pieces in front of the tile's own are the neighbour's - a per-lane predicate on the store.
+          // The beta = 1 join above reads the whole block: it lies inside the matrix, and what is not owned is never stored)
+          if (GRP == 3 && (wm * 32 * TM + 32 * i + row < own_row || wn * 32 * TN + ch * 8 < own_col)) continue;
           if (MULTI && l + 1 < L) __builtin_amdgcn_raw_buffer_store_b128(v, rsrcC, voff, 0, 16); // sc1: write-through (hand-off)
           else __builtin_amdgcn_raw_buffer_store_b128(v, rsrcC, voff, 0, C_STORE_AUX); // (last layer / single layer: gemm_common.h)
         }
@@ -732,14 +745,15 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   static std::atomic<unsigned long long> lds_set{0};
   if (hipError_t e = ensure_dynamic_lds((const void *)kern, (int)lds, lds_set); e != hipSuccess) return e;
   ChainArgs args = a;
-  args.tiles_m = a.m / BM;
-  args.tiles_n = GRP == 1 ? (a.n + BN - 1) / BN : a.n / BN; // (grouped items: a ragged last column tile, see the kernel)
+  args.tiles_m = GRP == 3 ? (a.m + BM - 1) / BM : a.m / BM; // (edge tiles: ceil-divided both ways, m >= BM and n >= BN)
+  args.tiles_n = (GRP == 1 || GRP == 3) ? (a.n + BN - 1) / BN : a.n / BN; // (grouped items: a ragged last column tile, see the kernel)
   long long tiles = (long long)args.tiles_m * args.tiles_n;
+  if (GRP == 3 && (a.m < BM || a.n < BN)) return hipErrorInvalidValue;
   if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
   args.items = nullptr;
   args.item_subs = 0;
   args.pad_items = 0;
-  if constexpr (GRP) { // tiles_m x tiles_n workgroups per item (consecutive workgroups = the items in list order: neighbouring
+  if constexpr (GRP == 1 || GRP == 2) { // tiles_m x tiles_n workgroups per item (consecutive workgroups = the items in list order: neighbouring
                        // tiles of a layer share panels in the L2 of whichever XCD they land on)
     if (!items || n_items <= 0 || tiles * n_items > 0x7fffffffLL) return hipErrorInvalidValue;
     args.items = items;
@@ -822,6 +836,34 @@ hipError_t launch_bf16_lw_vnni4(int tile, const ChainArgs &a, hipStream_t s) {
   const bool sup2 = blw_sup2(a);
   if (tile == 4) return sup2 ? launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 2, false, 4>(a, s) : launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 1, false, 4>(a, s); // 32x32 + K2 (round 6)
   BLW_DISPATCH(false, 4)
+}
+
+// EDGE TILES (xsmm_hip_set_edge_tiles modes 2, 20 .. 23; gemm_plan.cpp choose_bf16_edge_tile): ONE whole layer whose m or n the tile does
+// not divide, on ceil(m / BM) x ceil(n / BN) workgroups of the same tile (GRP = 3: the last tile of a row / column of tiles ends at the
+// matrix edge and stores only what no other tile owns). tile 0 .. 3, b_kind 0 VNNI-2 / 2 flat / 4 VNNI-4; SUP = 2 as in the plain
+// launches. No scratch, no counters, no waits. hipErrorInvalidValue (nothing launched): m < BM, n < BN, no batch element, k < 64.
+hipError_t launch_bf16_lw_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s) {
+  static const int bm[4] = {32, 64, 64, 128}, bn[4] = {64, 64, 128, 128};
+  if (tile < 0 || tile > 3 || (b_kind != 0 && b_kind != 2 && b_kind != 4) || a.nlayers != 1) return hipErrorInvalidValue;
+  if (a.m < bm[tile] || a.n < bn[tile] || a.L[0].br < 1 || a.L[0].k < BLW_BK || a.L[0].k % BLW_BK) return hipErrorInvalidValue;
+  const bool sup2 = blw_sup2(a);
+#define BLW_EDGE(FB)                                                                         \
+  switch (tile * 2 + (sup2 ? 1 : 0)) {                                                       \
+  case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, FB, 3>(a, s);                \
+  case 1: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 2, false, FB, 3>(a, s);                \
+  case 2: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, FB, 3>(a, s);                \
+  case 3: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 2, false, FB, 3>(a, s);                \
+  case 4:                                                                                    \
+  case 5: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, false, FB, 3>(a, s);                \
+  default: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, false, FB, 3>(a, s);               \
+  }
+  if (b_kind == 2) {
+    BLW_EDGE(2)
+  } else if (b_kind == 4) {
+    BLW_EDGE(4)
+  }
+  BLW_EDGE(0)
+#undef BLW_EDGE
 }
 
 // Tile invokes of ONE bf16 descriptor as one launch on the loader-wave tiles (round 6, VERDICT r5 missing 3 / next 2b: the tile queue's

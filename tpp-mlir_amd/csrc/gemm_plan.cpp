@@ -176,6 +176,8 @@ static int choose_bf16_small_split(long long t32, long long steps, const GemmPla
 // 128x64, f32_32x32_beats_64x32, a tile per CU before a larger tile is taken - on CEIL-DIVIDED tile counts (the half-width tiles and
 // the split launches have no edge form). Modes 6, 7, 9, 10 (tests, measurements): that GemmVariant's tile. Returns the variant, -1 = none.
 // No rule of mode 1 is fitted to a ragged shape yet: profiles/edge_tiles_ab.txt.
+// (mode 2 = mode 1 for f32 + the bf16 rule, choose_bf16_edge_tile; modes 20 .. 23 force a bf16 tile and leave f32 calls as with the mode off)
+static int f32_edge_mode(int mode) { return mode == 2 ? 1 : mode >= 20 ? 0 : mode; }
 static int choose_f32_edge_variant(const GemmDesc &d, int mode, int64_t cus) {
   const int64_t m = d.m, n = d.n;
   auto tiles = [&](int bm, int bn) { return (m >= bm && n >= bn) ? ((m + bm - 1) / bm) * ((n + bn - 1) / bn) : 0; };
@@ -285,6 +287,35 @@ static int pick_bf16_lw_image_tile(const GemmDesc &d, int64_t cus, int first_var
     if (blw_divides(d, c)) t = c;
   if (forced_variant >= first_variant && forced_variant <= first_variant + 3 && blw_divides(d, forced_variant - first_variant)) return forced_variant;
   return t >= 0 ? first_variant + t : V_GENERIC;
+}
+
+// EDGE TILES, bf16 (xsmm_hip_set_edge_tiles modes 2 and 20 .. 23, opt-in): a whole-layer bf16 call no loader-wave tile divides - m not a
+// multiple of 32 or n not of 64: planned on the generic kernel or the 32x32 K-split kernel - on the loader-wave tiles all the same
+// (brgemm_bf16_lw.hip GRP = 3, launch_bf16_lw_edge). What the three B images ask of leading dimensions, strides and lane offsets is
+// bf16_fast_eligible / bf16_flat_eligible / bf16_vnni4_eligible without their m / n terms; returns the image (0 VNNI-2, 2 flat, 4 VNNI-4), -1 = none.
+static int bf16_edge_b_kind(const GemmDesc &d) {
+  if (d.dtype != DT_BF16 || d.vnni_c || d.k <= 0 || d.k % BK) return -1;
+  if ((d.lda | d.ldc | d.stride_a | d.stride_b) & 7 || d.lda >= (1 << 22) || d.ldc >= (1 << 22)) return -1;
+  if (d.vnni_b && d.vnni_factor == 2) return !(d.ldb & 3) && d.ldb < (1 << 21) ? 0 : -1;
+  if (d.vnni_b && d.vnni_factor == 4) return !(d.ldb & 1) && d.ldb < (1 << 20) ? 4 : -1;
+  if (!d.vnni_b) return !(d.ldb & 7) && d.ldb < (1 << 21) ? 2 : -1;
+  return -1;
+}
+// A tile is a candidate when m >= BM and n >= BN. Mode 2: the cheapest candidate by blw_cost - the divisible shapes' fitted model - over
+// the rounds of its CEIL-DIVIDED tile count, priced at the call's own chunk count; ties go to the larger tile. Modes 20 .. 23 (tests,
+// measurements): that tile. Returns the tile index 0 .. 3, -1 = none. The model is not fitted to ragged shapes: profiles/edge_tiles_bf16_ab.txt.
+static int choose_bf16_edge_tile(const GemmDesc &d, int mode, int64_t chunks, int64_t cus) {
+  auto tiles = [&](int t) { return (d.m >= BLW_BM[t] && d.n >= BLW_BN[t]) ? ((d.m + BLW_BM[t] - 1) / BLW_BM[t]) * ((d.n + BLW_BN[t] - 1) / BLW_BN[t]) : 0; };
+  if (mode >= V_BF16_LW_32x64 && mode <= V_BF16_LW_128x128) return tiles(mode - V_BF16_LW_32x64) > 0 ? mode - V_BF16_LW_32x64 : -1;
+  if (mode != 2) return -1;
+  int best = -1;
+  double best_t = 0;
+  for (int t = 3; t >= 0; --t) {
+    if (tiles(t) <= 0) continue;
+    const double cost = blw_cost(t, rounds(tiles(t), cus), (double)chunks);
+    if (best < 0 || cost < best_t) best = t, best_t = cost;
+  }
+  return best;
 }
 
 static const char *variant_name(int v) {
@@ -438,6 +469,27 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
   const bool bias_ok8 = !d.bias || al.d8;
   if (v >= V_BF16_FAST && v != V_BF16_SMALL32 && !(al.c16 && bias_ok8)) v = V_GENERIC;
   if (v == V_BF16_SMALL32 && !(al.c8 && bias_ok8)) v = V_GENERIC;
+  // bf16 edge tiles, if asked for (choose_bf16_edge_tile): a call no loader-wave tile divides, before the refinements of the 32x32 K-split
+  // kernel below. Decided here only - what is queued, grouped, chained or made a quad never sees it -, from the descriptor, the batch
+  // count, the pointers' alignment and the CU count: allowed in strict mode. n % 8 keeps the shifted column tile on 16 bytes of C, of a
+  // flat B and of the bias row. The launcher's own checks: launch_bf16_lw_edge.
+  if ((env.edge_tiles == 2 || (env.edge_tiles >= V_BF16_LW_32x64 && env.edge_tiles <= V_BF16_LW_128x128)) && d.dtype == DT_BF16 && !d.vnni_c &&
+      !d.generic_forced && !d.variant_forced && (d.variant == V_GENERIC || d.variant == V_BF16_SMALL32) && (d.m % 32 != 0 || d.n % 64 != 0) &&
+      d.n % 8 == 0 && br >= 1 && al.ab16 && al.c16 && bias_ok8) {
+    const int kind = bf16_edge_b_kind(d);
+    const int tile = kind >= 0 ? choose_bf16_edge_tile(d, env.edge_tiles, (int64_t)br * (d.k / BK), cus) : -1;
+    if (tile >= 0) {
+      static const char *const edge_names[3][4] = {
+          {"brgemm_bf16_lw<32x64,k2>, edge tiles", "brgemm_bf16_lw<64x64>, edge tiles", "brgemm_bf16_lw<64x128>, edge tiles", "brgemm_bf16_lw<128x128>, edge tiles"},
+          {"brgemm_bf16_lw_flatb<32x64,k2>, edge tiles", "brgemm_bf16_lw_flatb<64x64>, edge tiles", "brgemm_bf16_lw_flatb<64x128>, edge tiles",
+           "brgemm_bf16_lw_flatb<128x128>, edge tiles"},
+          {"brgemm_bf16_lw_vnni4<32x64,k2>, edge tiles", "brgemm_bf16_lw_vnni4<64x64>, edge tiles", "brgemm_bf16_lw_vnni4<64x128>, edge tiles",
+           "brgemm_bf16_lw_vnni4<128x128>, edge tiles"}};
+      GemmLaunch l = launch(GL_BF16_LW, tile, edge_names[kind / 2][tile], 1, kind);
+      l.edge = true;
+      return l;
+    }
+  }
   // Small bf16 outputs with a LONG reduction: the 32x32 K-split kernel (fragments straight from global memory, two groups of loads
   // in flight per wave) is latency-bound there - 128 x 1024 x 4096: 15.4 us against 9.8 on 64 loader-wave tiles of 32x64 and 8.1 on
   // 128 tiles of 32x32 + K2 (the same kernel, twice the workgroups pulling panels). Crossovers (profiles/r05_bf16_skinny_small_vs_lw.txt):
@@ -503,11 +555,11 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
   // edge tiles, if asked for (choose_f32_edge_variant): a call no tile divides. Decided here only - what is queued, grouped, chained or
   // folded never sees it -, from the descriptor, the batch count, the pointers' alignment and the CU count: allowed in strict mode. A
   // forced split count and the tail split do not apply. The launcher's own checks: launch_f32_lw_edge.
-  if (env.edge_tiles != 0 && d.dtype == DT_F32 && !d.vnni_b && !d.vnni_c && !d.generic_forced && d.variant == V_GENERIC && d.k > 0 &&
+  if (f32_edge_mode(env.edge_tiles) != 0 && d.dtype == DT_F32 && !d.vnni_b && !d.vnni_c && !d.generic_forced && d.variant == V_GENERIC && d.k > 0 &&
       d.k % BK == 0 && br >= 1 && f32_lw_operands_ok(d) && d.ldc % 4 == 0 && d.n % 4 == 0 && al.ab16 && al.c16 && (!d.bias || al.d16)) {
     static const char *const edge_names[5] = {"", "brgemm_f32_lw<64x64,k2>, edge tiles", "brgemm_f32_lw<64x32,k4>, edge tiles",
                                               "brgemm_f32_lw<32x32,k4>, edge tiles", "brgemm_f32_lw<128x64,k1>, edge tiles"};
-    const int ev = choose_f32_edge_variant(d, env.edge_tiles, cus);
+    const int ev = choose_f32_edge_variant(d, f32_edge_mode(env.edge_tiles), cus);
     if (ev >= 0) {
       const int tile = ev == V_F32_LW_128x64 ? 4 : ev == V_F32_LW_32x32K4 ? 3 : ev - V_F32_LW_64x64;
       GemmLaunch l = launch(GL_F32_LW, tile, edge_names[tile]);

@@ -43,7 +43,8 @@ enum GemmVariant : int {
 
 // what the decisions read besides the descriptor: the device's compute units, xsmm_hip_set_strict, xsmm_hip_force_split (-1 = the
 // split model) and xsmm_hip_set_tail_split (0 = off, 1 = the model, 2 .. 16 = that many workgroups per tail tile) and
-// xsmm_hip_set_edge_tiles (0 = off, 1 = the tile rule, 6 / 7 / 9 / 10 = that GemmVariant's tile); brgemm_f32.hip gemm_plan_env fills it per call
+// xsmm_hip_set_edge_tiles (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that f32 GemmVariant's tile, 2 = the f32 and the bf16 tile rule, 20 .. 23 =
+// that bf16 GemmVariant's tile); brgemm_f32.hip gemm_plan_env fills it per call
 struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
@@ -61,7 +62,7 @@ enum GemmLauncher : int {
   GL_BF16_FAST,       // launch_gemm_bf16_fast(tile)
   GL_BF16_SMALL32,    // launch_bf16_small32(split)
   GL_BF16_GROUPED64,  // launch_bf16_grouped64
-  GL_BF16_LW,         // launch_bf16_lw / _flatb / _vnni4 by b_kind (0 / 2 / 4), tile
+  GL_BF16_LW,         // launch_bf16_lw / _flatb / _vnni4 by b_kind (0 / 2 / 4), tile; edge: launch_bf16_lw_edge(tile, b_kind)
   GL_BF16_LW_GROUPED, // launch_bf16_lw_grouped(tile, b_kind, even)
   GL_BF16_LW_QUADS,   // launch_bf16_lw_quads(b_kind)
   GL_GENERIC,         // brgemm_grouped<T, VNNI, VEC, VF, FORM>: generic
@@ -83,8 +84,8 @@ struct GemmLaunch {
   // tail_split workgroups each, the tiles of the full rounds unsplit, all in one launch (0 / 1 = none)
   int tail_tiles = 0;
   int tail_split = 1;
-  // GL_F32_LW, edge tiles (xsmm_hip_set_edge_tiles): m or n is not a multiple of the tile - launch_f32_lw_edge(tile) on the ceil-divided
-  // tile grid; refused by the launcher: the launch the call has with the mode off
+  // GL_F32_LW / GL_BF16_LW, edge tiles (xsmm_hip_set_edge_tiles): m or n is not a multiple of the tile - launch_f32_lw_edge(tile) /
+  // launch_bf16_lw_edge(tile, b_kind) on the ceil-divided tile grid; refused by the launcher: the launch the call has with the mode off
   bool edge = false;
 };
 

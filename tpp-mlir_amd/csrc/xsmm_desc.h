@@ -149,9 +149,10 @@ inline std::atomic<int> g_tail_split{[] {
   return v >= 0 && v <= 16 ? v : 0;
 }()};
 inline std::atomic<int64_t> g_tail_split_stats[4]; // launches with a split tail; tail tiles, workgroups per tail tile, body tiles of the latest
-// EDGE TILES (xsmm_hip_set_edge_tiles / TPP_HIP_EDGE_TILES; gemm_plan.cpp choose_f32_edge_variant): 0 = off, 1 = the tile rule, 6 / 7 / 9 /
-// 10 = that GemmVariant's tile. Setting and counters (xsmm_hip_edge_tiles_stats) as inline variables, like the tail split's above.
-inline bool edge_tiles_mode_ok(int v) { return v == 0 || v == 1 || v == 6 || v == 7 || v == 9 || v == 10; }
+// EDGE TILES (xsmm_hip_set_edge_tiles / TPP_HIP_EDGE_TILES; gemm_plan.cpp choose_f32_edge_variant, choose_bf16_edge_tile): 0 = off, 1 = the
+// f32 tile rule, 6 / 7 / 9 / 10 = that f32 GemmVariant's tile; 2 = the tile rule for f32 (mode 1's) and for bf16, 20 .. 23 = that bf16
+// GemmVariant's tile (f32 as with the mode off). Setting and counters (xsmm_hip_edge_tiles_stats) as inline variables, like the tail split's above.
+inline bool edge_tiles_mode_ok(int v) { return v == 0 || v == 1 || v == 2 || v == 6 || v == 7 || v == 9 || v == 10 || (v >= 20 && v <= 23); }
 inline std::atomic<int> g_edge_tiles{[] {
   const char *e = getenv("TPP_HIP_EDGE_TILES");
   const int v = e ? atoi(e) : 0;

@@ -349,12 +349,14 @@ class XsmmRuntime:
         return tuple(int(v) for v in out)
 
     def set_edge_tiles(self, mode):
-        """f32 whole-layer calls whose m or n no tile divides, on the loader-wave tiles: 0 off (default), 1 the tile rule, 6 / 7 / 9 / 10
-        the tile of that kernel variant; returns the previous mode, -1 for a value it refuses"""
+        """whole-layer calls whose m or n no tile divides, on the loader-wave tiles: 0 off (default); f32: 1 the tile rule, 6 / 7 / 9 / 10
+        the tile of that kernel variant; 2 the tile rule for f32 (mode 1's) and for bf16; 20 / 21 / 22 / 23 the bf16 tile 32x64 + K2 /
+        64x64 / 64x128 / 128x128 whatever the B image (f32 as with the mode off); returns the previous mode, -1 for a value it refuses"""
         return self.lib.xsmm_hip_set_edge_tiles(mode)
 
     def edge_tiles_stats(self):
-        """(edge launches; tile rows, tile columns, variant number of the tile of the most recent one)"""
+        """(edge launches; tile rows, tile columns, variant number of the tile of the most recent one - bf16: with its B image, 20 + t
+        VNNI-2, 24 + t flat, 28 + t VNNI-4)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_edge_tiles_stats(out)
         return tuple(int(v) for v in out)
