@@ -382,6 +382,29 @@ TPP_XSMM_EXPORT void xsmm_hip_tail_split_stats(int64_t out[4]);
  * 24 + t flat, 28 + t VNNI-4. */
 TPP_XSMM_EXPORT int xsmm_hip_set_edge_tiles(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_edge_tiles_stats(int64_t out[4]);
+/* Ragged k (opt-in; also TPP_HIP_EDGE_K, read as a number). A whole-layer f32 call whose k is not a multiple of 64 - a 784-wide input
+ * layer, a 1000-wide hidden dimension - is planned on the generic kernel, whatever the edge-tile mode. With this switch on, a call with
+ * k >= 64 and k a multiple of 8 runs on a loader-wave tile (64x64 + K2, 64x32 + K4, 32x32 + K4 or 128x64) as ONE launch: every batch
+ * element is read as ceil(k / 64) chunks of 64, the LAST chunk shifted back to start at k - 64 so that it ends at k, and the MFMA waves
+ * skip the o = 64 - k % 64 k-values at its head that the chunk before it has multiplied (whole 8-k blocks; skipped, not multiplied by
+ * zero: an Inf or NaN there counts once, as data). No load leaves [0, k) of a row of A or rows [0, k) of a B element, nothing outside
+ * the m x n window of C is written. No scratch block, no counters: legal on a captured stream.
+ * A call is taken when all of this holds: f32, no VNNI operand, no transposed operand, not on the bf16x6 kernel, the generic kernel
+ * not forced, the descriptor's kernel is the generic one, k >= 64, k % 8 == 0, k % 64 != 0, batch count >= 1, lda / ldb / ldc / strides
+ * multiples of 4 and ld < 2^22, n a multiple of 4, A, B, C (and the bias row) 16-byte aligned, m >= BM and n >= BN for the tile - and,
+ * if that tile does not divide m and n, an f32 edge-tile mode (xsmm_hip_set_edge_tiles 1, 2, 6, 7, 9, 10) is on as well: the kernel
+ * then also shifts back its last tile row and column. Everything else runs as with the switch off - every tile-queue group, chain and
+ * folded call too.
+ * mode 0 = off (default); 1 = the tile rule of the edge tiles (the divisible shapes' rule on ceil-divided tile counts; a forcing
+ * edge-tile mode forces the tile); 6 / 7 / 9 / 10 = the tile of that kernel variant wherever it fits (a test / measurement switch).
+ * Read per invoke; returns the previous mode, -1 (and changes nothing) for any other value. A forced split count and the tail split
+ * do not apply. The choice depends on the descriptor, the batch count, the pointers' alignment and the CU count only: made in strict
+ * mode too. xsmm_hip_last_refined_kernel reads "brgemm_f32_lw<64x64,k2>, ragged k", or "..., edge tiles, ragged k" when m or n is
+ * ragged as well.
+ * _stats: out[0] ragged-k launches since process start; of the most recent one: [1] chunks per batch element, [2] o, [3] the variant
+ * number of its tile (6, 7, 9, 10). The edge-tile counters do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_edge_k(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_edge_k_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

@@ -68,7 +68,7 @@ int main(int argc, char **argv) {
 static int run_case(int argc, char **argv) {
   int64_t batch = 256, tile = 32, tile_n = 0, tile_k = 0, n_iter = 100;
   bool kernel_args = false; // mlir-gen --kernel=args: the output is an argument, the matmul accumulates into it (no BETA_0)
-  int vnni = 2, split = -1, tail_split = 0, edge_tiles = 0, variant = -1, repeats = 1, f32p = 0;
+  int vnni = 2, split = -1, tail_split = 0, edge_tiles = 0, edge_k = 0, variant = -1, repeats = 1, f32p = 0;
   int64_t block_pad = 0; // --block-pad P (experiments): P elements between consecutive packed blocks of A and of W (the block strides stop being powers of two)
   std::vector<int64_t> layers = {1024, 1024, 1024, 1024};
   bool bias = false, relu = false, whole = false, chain = false, print = false, c1 = false, rnd = false, bf16 = false, host_buffers = false;
@@ -105,6 +105,7 @@ static int run_case(int argc, char **argv) {
     else if (a == "--split") split = atoi(next());     // xsmm_hip_force_split for this case (-1: the runtime's model)
     else if (a == "--tail-split") tail_split = atoi(next()); // xsmm_hip_set_tail_split for this case (0: off, 1: the model, 2 .. 16: workgroups per tail tile)
     else if (a == "--edge-tiles") edge_tiles = atoi(next()); // xsmm_hip_set_edge_tiles for this case (0: off, 1: the f32 tile rule, 6 / 7 / 9 / 10: that f32 variant's tile, 2: the f32 and bf16 rules, 20 .. 23: that bf16 tile)
+    else if (a == "--edge-k") edge_k = atoi(next()); // xsmm_hip_set_edge_k for this case (0: off, 1: the tile rule, 6 / 7 / 9 / 10: that variant's tile)
     else if (a == "--variant") variant = atoi(next()); // xsmm_hip_force_variant at dispatch (-1: the runtime's choice)
     else if (a == "--f32-precision") { // xsmm_hip_set_f32_precision for this case's dispatches: exact (default) or bf16x6
       const std::string v = next();
@@ -215,19 +216,22 @@ static int run_case(int argc, char **argv) {
     xsmm_hip_force_split(split);
     if (xsmm_hip_set_tail_split(tail_split) < 0) { fprintf(stderr, "tpp_replay: --tail-split takes 0 .. 16, got %d\n", tail_split); return 2; }
     if (xsmm_hip_set_edge_tiles(edge_tiles) < 0) { fprintf(stderr, "tpp_replay: --edge-tiles takes 0, 1, 2, 6, 7, 9, 10 or 20 .. 23, got %d\n", edge_tiles); return 2; }
+    if (xsmm_hip_set_edge_k(edge_k) < 0) { fprintf(stderr, "tpp_replay: --edge-k takes 0, 1, 6, 7, 9 or 10, got %d\n", edge_k); return 2; }
     xsmm_hip_force_variant(variant);
     xsmm_hip_set_async(1);
     xsmm_hip_set_tile_queue(queue);
-  } else if ((bf16 && vnni != 2) || split != -1 || tail_split != 0 || edge_tiles != 0 || variant != -1 || chain || f32p) {
-    fprintf(stderr, "tpp_replay: --host-buffers takes its settings from the environment only (no --vnni 4 / --split / --tail-split / --edge-tiles / --variant / --chain / --f32-precision)\n");
+  } else if ((bf16 && vnni != 2) || split != -1 || tail_split != 0 || edge_tiles != 0 || edge_k != 0 || variant != -1 || chain || f32p) {
+    fprintf(stderr, "tpp_replay: --host-buffers takes its settings from the environment only (no --vnni 4 / --split / --tail-split / --edge-tiles / --edge-k / --variant / --chain / --f32-precision)\n");
     return 2;
   }
   std::vector<int64_t> handle(L);
   const int64_t tn = tile_n ? tile_n : tile, tk = tile_k ? tile_k : tile; // blocks: A [MB][KB][tm][tk], W [NB][KB][tk][tn], C [MB][NB][tm][tn]
   for (int l = 0; l < L; ++l) {
     const int64_t K = layers[l], N = layers[l + 1];
-    if (whole) // one dispatch per layer on the flat row-major tensors
-      handle[l] = xsmm_fused_brgemm_dispatch(dt, batch, N, 64, K, N, N, 64, 64 * N, gflags, 0, ukind, bflags, bkind);
+    if (whole) { // one dispatch per layer on the flat row-major tensors: 64-wide batch elements; a K that is no multiple of 64: one element
+      const int64_t wk = K % 64 ? K : 64;
+      handle[l] = xsmm_fused_brgemm_dispatch(dt, batch, N, wk, K, N, N, wk, wk * N, gflags, 0, ukind, bflags, bkind);
+    }
     else       // packed tiles: [MB][KB][t][t] x [NB][KB][t][t] -> [MB][NB][t][t]
       handle[l] = xsmm_fused_brgemm_dispatch(dt, tile, tn, tk, tk, tn, tn, tile * tk + block_pad, tk * tn + block_pad, gflags, 0, ukind, bflags, bkind);
   }
@@ -235,7 +239,7 @@ static int run_case(int argc, char **argv) {
   int chained = -1;
   std::vector<void *> pa(L), pb(L), pc(L), pd(L);
   std::vector<int64_t> z(L, 0), br(L);
-  for (int l = 0; l < L; ++l) pa[l] = act[l], pb[l] = W[l], pc[l] = act[l + 1], pd[l] = B[l], br[l] = layers[l] / 64;
+  for (int l = 0; l < L; ++l) pa[l] = act[l], pb[l] = W[l], pc[l] = act[l + 1], pd[l] = B[l], br[l] = layers[l] % 64 ? 1 : layers[l] / 64;
   auto kernel = [&]() {
     if (chain) {
       chained = xsmm_hip_fused_brgemm_chain_invoke(dt, L, handle.data(), pa.data(), z.data(), pb.data(), z.data(), pc.data(), z.data(), pd.data(),
@@ -245,7 +249,7 @@ static int run_case(int argc, char **argv) {
     for (int l = 0; l < L; ++l) {
       const int64_t K = layers[l], N = layers[l + 1];
       if (whole) {
-        xsmm_fused_brgemm_invoke(dt, handle[l], act[l], 0, W[l], 0, act[l + 1], 0, B[l], 0, K / 64);
+        xsmm_fused_brgemm_invoke(dt, handle[l], act[l], 0, W[l], 0, act[l + 1], 0, B[l], 0, br[l]);
       } else {
         const int64_t MB = batch / tile, NB = N / tn, KB = K / tk;
         auto run = [&](int64_t t0, int64_t t1) { // tiles [t0, t1) of the MB x NB grid, row-major (static schedule)
@@ -354,6 +358,7 @@ static int run_case(int argc, char **argv) {
   xsmm_hip_force_split(-1);
   xsmm_hip_set_tail_split(0);
   xsmm_hip_set_edge_tiles(0);
+  xsmm_hip_set_edge_k(0);
   for (void *p : act) CHECK(hipFree(p));
   for (void *p : W) CHECK(hipFree(p));
   for (void *p : B) CHECK(hipFree(p));

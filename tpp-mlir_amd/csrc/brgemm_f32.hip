@@ -26,6 +26,7 @@
 #include "xsmm_desc.h"
 #include "chain_args.h"
 #include "gemm_plan.h"
+#include "brgemm_f32_lw_kedge.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -693,6 +694,7 @@ hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *it
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
 hipError_t launch_f32_lw_tail(int tile, const GemmArgs &a, int tail_tiles, int split, hipStream_t s); // the same
 hipError_t launch_f32_lw_edge(int tile, const GemmArgs &a, hipStream_t s); // m or n not a multiple of the tile; hipErrorInvalidValue: not launched
+hipError_t launch_f32_lw_kedge(int tile, const GemmArgs &a, hipStream_t s); // k a multiple of 8 but not of 64 (m, n ragged or not); hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw16(int tile, const GemmArgs &a, const WorkItem *items, int n_items, bool grouped, hipStream_t s); // brgemm_f32_lw16.hip: tile 0 = 32x16
 hipError_t launch_f32_x6(int tile, const GemmArgs &a, bool vec, hipStream_t s); // brgemm_f32_x6.hip: tile = variant - V_F32_X6_64x64
 hipError_t launch_bf16_grouped64(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s); // brgemm_bf16.hip
@@ -725,7 +727,7 @@ int set_strict_kernels(int on) { return g_strict_kernels.exchange(on != 0); }
 bool strict_kernels() { return g_strict_kernels.load(std::memory_order_relaxed) != 0; }
 static GemmPlanEnv gemm_plan_env() {
   return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed), g_tail_split.load(std::memory_order_relaxed),
-                     g_edge_tiles.load(std::memory_order_relaxed)};
+                     g_edge_tiles.load(std::memory_order_relaxed), g_edge_k.load(std::memory_order_relaxed)};
 }
 bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, gemm_plan_env()); }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, gemm_plan_env()); }
@@ -783,7 +785,7 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
     case V_F32_64x64K2: return launch_fast<2, 2, 2, true>(a, s);
     default: return hipErrorInvalidValue;
     }
-  case GL_F32_LW: return p.edge ? launch_f32_lw_edge(p.tile, a, s) : launch_f32_lw(p.tile, a, s);
+  case GL_F32_LW: return p.edge_k ? launch_f32_lw_kedge(p.tile, a, s) : p.edge ? launch_f32_lw_edge(p.tile, a, s) : launch_f32_lw(p.tile, a, s);
   case GL_F32_LW16: return launch_f32_lw16(p.tile, a, wi, n_items, grouped, s);
   case GL_F32_LW_GROUPED: return launch_f32_lw_grouped(p.tile, a, wi, n_items, p.split, s);
   case GL_F32_X6: return launch_f32_x6(p.tile, a, p.vec, s);
@@ -819,6 +821,22 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   GemmLaunch p = plan_gemm_call(d, br, al, env);
   if (p.launcher == GL_NONE) return hipSuccess;
   const GemmArgs a = gemm_args(d, A, B, C, D, (int)(br < 0 ? 0 : br));
+  if (p.edge_k) { // a ragged-k launch (xsmm_desc.h g_edge_k; brgemm_f32_lw_kedge.h)
+    const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    if (e != hipErrorInvalidValue) {
+      if (e == hipSuccess) {
+        static const int variant[5] = {0, V_F32_LW_64x64K2, V_F32_LW_64x32K2, V_F32_LW_32x32K4, V_F32_LW_128x64};
+        g_edge_k_stats[1].store(kedge_chunks(a.k), std::memory_order_relaxed);
+        g_edge_k_stats[2].store(kedge_overlap(a.k), std::memory_order_relaxed);
+        g_edge_k_stats[3].store(variant[p.tile >= 0 && p.tile < 5 ? p.tile : 0], std::memory_order_relaxed);
+        g_edge_k_stats[0].fetch_add(1, std::memory_order_relaxed);
+      }
+      return g_last_refined.store(p.text, std::memory_order_relaxed), e;
+    }
+    (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
+    env.edge_k = 0;
+    p = plan_gemm_call(d, br, al, env);
+  }
   if (p.edge) { // a launch on edge tiles (xsmm_desc.h g_edge_tiles)
     const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
     if (e != hipErrorInvalidValue) {

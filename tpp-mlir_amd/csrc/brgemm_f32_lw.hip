@@ -418,6 +418,95 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw_
   }
 }
 
+// ---- RAGGED k: a whole-layer call whose k is not a multiple of 64 (opt-in, xsmm_hip_set_edge_k) ------------------------------------
+// k >= 64, k % 8 == 0, k % 64 != 0, at least one batch element. Every batch element is ceil(k / 64) chunks; the last one is SHIFTED
+// BACK to start at k - 64, so that it ends at k - no load leaves columns [0, k) of A or rows [0, k) of B, the start stays on 32
+// bytes - and the MFMA waves SKIP the k-blocks at its head that the chunk before it has multiplied (brgemm_f32_lw_kedge.h: the
+// schedule; Loader::issue_ragged, LwTile::mfma_chunks_ragged: the two places that know of it). Nothing is multiplied by zero: an Inf
+// or NaN in the overlap counts once, as data. The workgroup is otherwise the edge tile's, shifted-back last tile row and column and
+// ownership mask included (own_r = own_c = 0 when the tile divides m and n), so ONE kernel serves the ragged-k layer with divisible m
+// and n and the layer ragged in all three. A kernel of its own, its body the edge kernel's line for line but for the three marked
+// places: sharing the body as a function changed the code of the four edge instances, and no existing instance may change.
+template <int WM, int WN, int WK, int NL, int NSLOT, int NLB>
+__global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw_kedge(GemmArgs p) {
+  using Tile = LwTile<WM, WN, WK, NSLOT>;
+  constexpr int NMW = Tile::NMW, BM = Tile::BM, BN = Tile::BN, IPG = Tile::IPG;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int hw_wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave = hw_wave < NL + NLB ? NMW + hw_wave : hw_wave - (NL + NLB); // loaders first, as in brgemm_f32_lw
+  // the grid, the shifted-back last tile row / column and what the tile owns: brgemm_f32_lw_edge
+  const int tm = (int)(blockIdx.x >> p.xn_shift) * p.tiles_m + (int)blockIdx.z;
+  const int tn = (int)(blockIdx.x & ((1u << p.xn_shift) - 1)) * p.tiles_n + (int)blockIdx.y;
+  const int m0 = tm * BM < p.m - BM ? tm * BM : p.m - BM, n0 = tn * BN < p.n - BN ? tn * BN : p.n - BN;
+  const int own_r = tm * BM - m0, own_c = tn * BN - n0; // 0, 0 for every tile but the last of a ragged row / column of tiles
+  const float *__restrict__ A = (const float *)p.A;
+  const float *__restrict__ B = (const float *)p.B;
+  float *__restrict__ C = (float *)p.C;
+  const int kchunks = kedge_chunks(p.k); // >= 2
+  const int T = p.br * kchunks;
+
+  if (wave >= NMW) {
+    typename Tile::template Loader<NL, NLB> ld(wave - NMW, lane, A, B, m0, n0, (int)p.lda, (int)p.ldb, p.stride_a, p.stride_b, kchunks, false, BN);
+    ld.ragged_k(p.k);
+    lw_loader_schedule<NSLOT>(T, [&](int slot) __attribute__((always_inline)) { ld.issue_ragged(slot); },
+                              [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); });
+    return;
+  }
+
+  const typename Tile::Wave w(wave, lane);
+  const int wk = w.wk, wm = w.wm, wn = w.wn;
+  const int li = lane & 31, lh = lane >> 5;
+  const __amdgpu_buffer_rsrc_t rsrcC =
+      __builtin_amdgcn_make_buffer_rsrc((void *)(C + (int64_t)m0 * p.ldc + n0), 0, 0x7fffffff, 0x00020000);
+  const unsigned voffC = (unsigned)(((wm * 32 + 4 * lh) * (int)p.ldc + wn * 32 + li) * 4);
+  const unsigned ldcb = (unsigned)((int)p.ldc * 4);
+  // accumulator register r of a lane: row wm 32 + 4 lh + (r & 3) + 8 (r >> 2), column wn 32 + li of the tile
+  const bool col_owned = wn * 32 + li >= own_c;
+  const int row_first = own_r - (wm * 32 + 4 * lh); // register r is owned if (r & 3) + 8 (r >> 2) >= row_first
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  float bias = 0.0f;
+  if constexpr (WK == 1) {
+    if (p.ep & EP_BIAS) bias = ((const float *)p.D)[n0 + wn * 32 + li];
+  }
+  constexpr bool BIAS_EARLY = WK > 1 && WM * WN * WK <= 4; // (brgemm_f32_lw)
+  f32x4 bias4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  if constexpr (BIAS_EARLY) {
+    if (p.ep & EP_BIAS) bias4 = *(const f32x4 *)((const float *)p.D + n0 + wn * 32 + 4 * (lane & 7));
+  }
+  // beta = 1: C joins the chain of K group 0 - only where the tile owns it; elsewhere the neighbour may already have stored
+  if (wk == 0 && !(p.ep & EP_BETA0) && col_owned) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if ((r & 3) + 8 * (r >> 2) >= row_first)
+        acc[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrcC, voffC, (unsigned)((r & 3) + 8 * (r >> 2)) * ldcb, 0));
+  }
+
+  __builtin_amdgcn_s_barrier(); // chunk 0 published
+  __builtin_amdgcn_sched_barrier(0);
+  Tile::mfma_chunks_ragged(acc, T, kchunks, kedge_skip_blocks(p.k, kchunks - 1), w);
+
+  if constexpr (WK > 1) {
+    Tile::park_partials(acc, w);
+    if constexpr (!BIAS_EARLY) {
+      if (p.ep & EP_BIAS) bias4 = *(const f32x4 *)((const float *)p.D + n0 + wn * 32 + 4 * (lane & 7));
+    }
+    f32x4 part[IPG];
+    Tile::sum_partials(part, w);
+    Tile::finish_owned(part, bias4, p.ep, rsrcC, (int)p.ldc, own_r, own_c, w);
+    return;
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float v = acc[r] + bias;
+    if (p.ep & EP_RELU) v = v > 0.0f ? v : 0.0f;
+    if (col_owned && (r & 3) + 8 * (r >> 2) >= row_first)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrcC, voffC, (unsigned)((r & 3) + 8 * (r >> 2)) * ldcb, LW_C_AUX);
+  }
+}
+
 // ---- launchers --------------------------------------------------------------------------------------------------------------
 // The XCD blocks of a whole-layer grid: xm x xn = 8 blocks of tiles_m/xm x tiles_n/xn tiles, one per XCD. Each XCD's L2 then fetches
 // m/xm rows of A and n/xn columns of B: the split that minimises m/xm + n/xn - 4 x 2 for square outputs (C2; ties keep it: rounds
@@ -476,6 +565,11 @@ template <int WM, int WN, int WK, int NL, int NSLOT, int NLB> struct LwEdge {
   using Tile = LwTile<WM, WN, WK, NSLOT>;
   static constexpr int NT = 64 * (Tile::NMW + NL + NLB);
   static constexpr auto kernel = brgemm_f32_lw_edge<WM, WN, WK, NL, NSLOT, NLB>;
+};
+template <int WM, int WN, int WK, int NL, int NSLOT, int NLB> struct LwKEdge {
+  using Tile = LwTile<WM, WN, WK, NSLOT>;
+  static constexpr int NT = 64 * (Tile::NMW + NL + NLB);
+  static constexpr auto kernel = brgemm_f32_lw_kedge<WM, WN, WK, NL, NSLOT, NLB>;
 };
 template <class I, class... Args> static hipError_t lw_launch(dim3 grid, hipStream_t s, const Args &...args) {
   static std::atomic<unsigned long long> lds_set{0};
@@ -547,6 +641,17 @@ template <int WM, int WN, int WK, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL
   return lw_launch<I>(dim3(blocks ? 8 : 1, args.tiles_n, args.tiles_m), s, args);
 }
 
+// whole-layer call with a RAGGED k (brgemm_f32_lw_kedge): the edge launcher's grid
+template <int WM, int WN, int WK, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL> static hipError_t launch_lw_kedge_t(const GemmArgs &a, hipStream_t s) {
+  using I = LwKEdge<WM, WN, WK, NL, NSLOT, NLB>;
+  constexpr int BM = I::Tile::BM, BN = I::Tile::BN;
+  if (a.m < BM || a.n < BN || (a.n & 3) || !kedge_k_ok(a.k) || a.br < 1) return hipErrorInvalidValue;
+  GemmArgs args = a;
+  const bool blocks = lw_xcd_grid(args, (a.m + BM - 1) / BM, (a.n + BN - 1) / BN);
+  if (args.tiles_m > 65535 || args.tiles_n > 65535) return hipErrorInvalidValue;
+  return lw_launch<I>(dim3(blocks ? 8 : 1, args.tiles_n, args.tiles_m), s, args);
+}
+
 // tile as in launch_f32_lw; split > 1: that many workgroups per output tile (K-split tiles 1 .. 3 only); n may end inside the last tile
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s) {
   if (split > 1) {
@@ -597,6 +702,18 @@ hipError_t launch_f32_lw_edge(int tile, const GemmArgs &a, hipStream_t s) {
   case 2: return launch_lw_edge_t<2, 1, 4, 2, LW_NSLOT, 1>(a, s);
   case 3: return launch_lw_edge_t<1, 1, 4>(a, s);
   case 4: return launch_lw_edge_t<4, 2, 1, 2, 3>(a, s);
+  default: return hipErrorInvalidValue;
+  }
+}
+
+// whole-layer call with a ragged k; tile and loader waves per tile as launch_f32_lw_edge (1 .. 4). hipErrorInvalidValue: not launched -
+// k < 64, k not a multiple of 8, k a multiple of 64, m or n below the tile, n not a multiple of 4, no batch
+hipError_t launch_f32_lw_kedge(int tile, const GemmArgs &a, hipStream_t s) {
+  switch (tile) {
+  case 1: return launch_lw_kedge_t<2, 2, 2, 2>(a, s);
+  case 2: return launch_lw_kedge_t<2, 1, 4, 2, LW_NSLOT, 1>(a, s);
+  case 3: return launch_lw_kedge_t<1, 1, 4>(a, s);
+  case 4: return launch_lw_kedge_t<4, 2, 1, 2, 3>(a, s);
   default: return hipErrorInvalidValue;
   }
 }

@@ -3,6 +3,7 @@
 // launches' bits - the same LDS images, the same schedule, the same order of additions. brgemm_f32_lw16.hip shares the loader schedule.
 // (The structure and why it is as it is: the head of brgemm_f32_lw.hip.)
 #pragma once
+#include "brgemm_f32_lw_kedge.h"
 #include "gemm_common.h"
 #include "xsmm_desc.h"
 #include <type_traits>
@@ -12,6 +13,7 @@ namespace tpp {
 constexpr int LW_BK = 64;   // k per chunk
 constexpr int LW_NSLOT = 4; // LDS ring slots
 constexpr int LW_C_AUX = C_STORE_AUX; // write-through C stores (gemm_common.h)
+static_assert(KEDGE_BK == LW_BK, "the ragged-k schedule is written for this chunk");
 
 typedef __attribute__((address_space(3))) void lds_void_lw;
 // The ring = the launch's dynamic LDS; the K-group combine parks its partials in it. Named here and used by the pieces directly: handed
@@ -130,6 +132,19 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
         g += d_in;
       }
     }
+    // RAGGED k (brgemm_f32_lw_kedge; the schedule: brgemm_f32_lw_kedge.h): kchunks = kedge_chunks(k) >= 2, the last chunk of every batch
+    // element starts at k - 64. ragged_k once behind the constructor, then issue_ragged for issue: the advance into an element's last
+    // chunk is k % 64 instead of 64 (issue has added 64: d_fix takes the overlap back), the batch wrap starts from k - 64.
+    int64_t d_fix;
+    __device__ __forceinline__ void ragged_k(int k) {
+      const int64_t unit = d_in / LW_BK; // elements per k: 1 in A, ldb in B
+      d_fix = (int64_t)(kedge_step(k, kchunks - 2) - LW_BK) * unit;
+      d_wrap = d_batch - (int64_t)kedge_chunk_start(k, kchunks - 1) * unit;
+    }
+    __device__ __forceinline__ void issue_ragged(int slot) {
+      issue(slot);
+      if (kc == kchunks - 1) g += d_fix; // the chunk now due is the element's last
+    }
     // s_waitcnt vmcnt(n chunks of this wave's DMA may still be in flight), n = 0 or 1
     __device__ __forceinline__ void wait_left(int chunks) const {
       if (chunks == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -215,6 +230,84 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
       if constexpr (NSLOT > 3) {
         chunk(S3{}, HR{}, t + 1 < T);
         if (++t == T) break;
+      }
+    }
+  }
+
+  // RAGGED k (brgemm_f32_lw_kedge): mfma_chunks for batch elements of kchunks >= 2 chunks whose LAST chunk was fetched shifted back
+  // (Loader::issue_ragged) - the wave does not multiply k-block b of that chunk unless kedge_block_runs(b, skip), skip =
+  // kedge_skip_blocks: a wave-uniform test per k-block of the wave's share, around the four MFMAs only; the fragment reads (the slot
+  // holds valid data) and the chunk's barrier stay, also for a K group that skips its whole share. Laps of the ring that hold no last
+  // chunk are mfma_chunks' steady-state laps, one basic block; a lap with a last chunk in it goes chunk by chunk with the test.
+  static __device__ __forceinline__ void mfma_chunks_ragged(f32x16 &acc, int T, int kchunks, int skip, const Wave &w) {
+    f32x4 fa[2];
+    float fb[2][4];
+    const int li = w.lane & 31, lh = w.lane >> 5;
+    const int a_off = (w.wm * 32 + li) * LW_BK, b_off = w.wn * 32 + li;
+    auto frag_load = [&](int buf, int slot, int kb) __attribute__((always_inline)) {
+      const float *as = smem_lw + slot * SLOT + a_off;
+      const float *bs = smem_lw + slot * SLOT + A_STAGE + b_off;
+      fa[buf] = *(const f32x4 *)(as + (((2 * kb + lh) ^ (li & 15)) << 2));
+#pragma unroll
+      for (int s = 0; s < 4; ++s) fb[buf][s] = bs[(8 * kb + 4 * lh + s) * BN];
+    };
+    const int kbw = w.wk * KB_PER_WAVE;
+    // rag_c 0: a whole chunk that another follows (compile-time facts: mfma_chunks' HY chunk); 1: `first` blocks of the chunk are
+    // skipped (0: none), whether another chunk follows is decided at run time
+    auto chunk = [&](auto slot_c, auto rag_c, int first, bool has_next_rt) __attribute__((always_inline)) {
+      constexpr int S = decltype(slot_c)::value, NS = (S + 1) % NSLOT;
+      constexpr bool RAG = decltype(rag_c)::value != 0;
+      const bool has_next = RAG ? has_next_rt : true;
+#pragma unroll
+      for (int q = 0; q < KB_PER_WAVE; ++q) {
+        const int cur = q & 1, nxt = cur ^ 1;
+        if (q + 1 < KB_PER_WAVE) frag_load(nxt, S, kbw + q + 1);
+        else frag_load(nxt, NS, kbw);
+        __builtin_amdgcn_sched_barrier(0);
+        if (!RAG || kedge_block_runs(kbw + q, first)) {
+#pragma unroll
+          for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][s], fb[cur][s], acc, 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (q == KB_HALF - 1 && has_next) {
+          __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      constexpr int PF = KB_PER_WAVE & 1; // (mfma_chunks: the prefetched fragments are dead on an exit path)
+      if constexpr (RAG) asm volatile("" : "+v"(fa[PF]), "+v"(fb[PF][0]), "+v"(fb[PF][1]), "+v"(fb[PF][2]), "+v"(fb[PF][3]));
+    };
+    using S0 = std::integral_constant<int, 0>;
+    using S1 = std::integral_constant<int, 1>;
+    using S2 = std::integral_constant<int, 2>;
+    using S3 = std::integral_constant<int, 3>;
+    using R0 = std::integral_constant<int, 0>;
+    using R1 = std::integral_constant<int, 1>;
+
+    frag_load(0, 0, kbw);
+    int t = 0, c = 0; // chunk t of the tile = chunk c of its batch element; a lap starts on slot 0
+    for (;;) {
+      if (c + NSLOT < kchunks) { // chunks c .. c + NSLOT - 1 are whole and the element's last chunk is still to come
+        chunk(S0{}, R0{}, 0, true);
+        chunk(S1{}, R0{}, 0, true);
+        chunk(S2{}, R0{}, 0, true);
+        if constexpr (NSLOT > 3) chunk(S3{}, R0{}, 0, true);
+        t += NSLOT, c += NSLOT;
+        continue;
+      }
+      chunk(S0{}, R1{}, c + 1 == kchunks ? skip : 0, t + 1 < T);
+      if (++t == T) break;
+      if (++c == kchunks) c = 0;
+      chunk(S1{}, R1{}, c + 1 == kchunks ? skip : 0, t + 1 < T);
+      if (++t == T) break;
+      if (++c == kchunks) c = 0;
+      chunk(S2{}, R1{}, c + 1 == kchunks ? skip : 0, t + 1 < T);
+      if (++t == T) break;
+      if (++c == kchunks) c = 0;
+      if constexpr (NSLOT > 3) {
+        chunk(S3{}, R1{}, c + 1 == kchunks ? skip : 0, t + 1 < T);
+        if (++t == T) break;
+        if (++c == kchunks) c = 0;
       }
     }
   }

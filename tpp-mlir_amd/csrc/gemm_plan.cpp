@@ -1,6 +1,7 @@
 // gemm_plan.cpp - the GEMM kernel planner (gemm_plan.h): host-only, no kernels, no HIP runtime calls. Its choices, case by case, are
 // tests/golden/gemm_plan.txt (tests/test_gemm_plan.py): a change of a rule or a cost coefficient is a change of that table.
 #include "gemm_plan.h"
+#include "brgemm_f32_lw_kedge.h"
 #include <string.h>
 
 namespace tpp {
@@ -565,6 +566,30 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
       GemmLaunch l = launch(GL_F32_LW, tile, edge_names[tile]);
       l.edge = true;
       return l;
+    }
+  }
+  // ragged k, if asked for (xsmm_hip_set_edge_k; brgemm_f32_lw_kedge.h): k >= 64 a multiple of 8 but not of 64 - planned on the generic
+  // kernel - on a loader-wave tile whose last chunk per batch element is shifted back (brgemm_f32_lw.hip brgemm_f32_lw_kedge). The tile:
+  // the forced one (edge_k 6 / 7 / 9 / 10, else a forcing edge-tile mode), else choose_f32_edge_variant's rule - on ceil-divided counts
+  // it is the divisible shapes' rule too. A tile that does not divide m and n is taken only with the f32 edge tiles on as well: else
+  // the call stays where it is. Decided here only, like the edge tiles; a forced split count and the tail split do not apply.
+  if (env.edge_k != 0 && d.dtype == DT_F32 && !d.vnni_b && !d.vnni_c && !d.generic_forced && d.variant == V_GENERIC && kedge_k_ok(d.k) && br >= 1 &&
+      f32_lw_operands_ok(d) && d.ldc % 4 == 0 && d.n % 4 == 0 && al.ab16 && al.c16 && (!d.bias || al.d16)) {
+    static const char *const kedge_names[2][5] = {
+        {"", "brgemm_f32_lw<64x64,k2>, ragged k", "brgemm_f32_lw<64x32,k4>, ragged k", "brgemm_f32_lw<32x32,k4>, ragged k", "brgemm_f32_lw<128x64,k1>, ragged k"},
+        {"", "brgemm_f32_lw<64x64,k2>, edge tiles, ragged k", "brgemm_f32_lw<64x32,k4>, edge tiles, ragged k", "brgemm_f32_lw<32x32,k4>, edge tiles, ragged k",
+         "brgemm_f32_lw<128x64,k1>, edge tiles, ragged k"}};
+    static const int bm[5] = {0, 64, 64, 32, 128}, bn[5] = {0, 64, 32, 32, 64};
+    const int em = f32_edge_mode(env.edge_tiles);
+    const int ev = choose_f32_edge_variant(d, env.edge_k != 1 ? env.edge_k : em != 0 ? em : 1, cus);
+    if (ev >= 0) {
+      const int tile = ev == V_F32_LW_128x64 ? 4 : ev == V_F32_LW_32x32K4 ? 3 : ev - V_F32_LW_64x64;
+      const bool mn_ragged = d.m % bm[tile] != 0 || d.n % bn[tile] != 0;
+      if (!mn_ragged || em != 0) {
+        GemmLaunch l = launch(GL_F32_LW, tile, kedge_names[mn_ragged][tile]);
+        l.edge_k = true;
+        return l;
+      }
     }
   }
   // a SINGLE invoke of a 32-k f32 tile with an even batch count: the kernel its group would run on in the tile queue (the

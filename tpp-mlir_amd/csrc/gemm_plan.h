@@ -44,8 +44,9 @@ enum GemmVariant : int {
 // what the decisions read besides the descriptor: the device's compute units, xsmm_hip_set_strict, xsmm_hip_force_split (-1 = the
 // split model) and xsmm_hip_set_tail_split (0 = off, 1 = the model, 2 .. 16 = that many workgroups per tail tile) and
 // xsmm_hip_set_edge_tiles (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that f32 GemmVariant's tile, 2 = the f32 and the bf16 tile rule, 20 .. 23 =
-// that bf16 GemmVariant's tile); brgemm_f32.hip gemm_plan_env fills it per call
-struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; };
+// that bf16 GemmVariant's tile) and xsmm_hip_set_edge_k (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that GemmVariant's tile);
+// brgemm_f32.hip gemm_plan_env fills it per call
+struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
 struct GemmAlign { bool ab16, c16, c8, d8, d16; };
@@ -55,7 +56,7 @@ enum GemmLauncher : int {
   GL_NONE,            // nothing to compute (empty output or work list): hipSuccess
   GL_INVALID,         // no kernel takes this call: hipErrorInvalidValue
   GL_F32_FAST,        // brgemm_f32_fast (brgemm_f32.hip): tile = V_F32_64x64 .. V_F32_64x64K2
-  GL_F32_LW,          // launch_f32_lw(tile); split > 1: launch_f32_lw_split(tile, split) first; tail_tiles > 0: launch_f32_lw_tail first; edge: launch_f32_lw_edge(tile)
+  GL_F32_LW,          // launch_f32_lw(tile); split > 1: launch_f32_lw_split(tile, split) first; tail_tiles > 0: launch_f32_lw_tail first; edge: launch_f32_lw_edge(tile); edge_k: launch_f32_lw_kedge(tile)
   GL_F32_LW16,        // launch_f32_lw16(tile); split > 1: launch_f32_lw_split(3, split) first
   GL_F32_LW_GROUPED,  // launch_f32_lw_grouped(tile, split)
   GL_F32_X6,          // launch_f32_x6(tile, vec)
@@ -87,6 +88,9 @@ struct GemmLaunch {
   // GL_F32_LW / GL_BF16_LW, edge tiles (xsmm_hip_set_edge_tiles): m or n is not a multiple of the tile - launch_f32_lw_edge(tile) /
   // launch_bf16_lw_edge(tile, b_kind) on the ceil-divided tile grid; refused by the launcher: the launch the call has with the mode off
   bool edge = false;
+  // GL_F32_LW, ragged k (xsmm_hip_set_edge_k): k is a multiple of 8 but not of 64 - launch_f32_lw_kedge(tile) on the ceil-divided tile
+  // grid (m and n may be ragged too); refused by the launcher: the launch the call has with the mode off
+  bool edge_k = false;
 };
 
 // fills d.variant / d.name / d.generic_forced / d.variant_forced; returns false if no kernel can run the descriptor

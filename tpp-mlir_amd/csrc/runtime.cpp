@@ -531,6 +531,10 @@ extern "C" int xsmm_hip_set_edge_tiles(int mode) { return tpp::edge_tiles_mode_o
 extern "C" void xsmm_hip_edge_tiles_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_tiles_stats[i].load(std::memory_order_relaxed);
 }
+extern "C" int xsmm_hip_set_edge_k(int mode) { return tpp::edge_k_mode_ok(mode) ? tpp::g_edge_k.exchange(mode) : -1; }
+extern "C" void xsmm_hip_edge_k_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k_stats[i].load(std::memory_order_relaxed);
+}
 extern "C" void xsmm_hip_tail_split_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_tail_split_stats[i].load(std::memory_order_relaxed);
 }

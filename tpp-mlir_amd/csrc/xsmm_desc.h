@@ -159,6 +159,15 @@ inline std::atomic<int> g_edge_tiles{[] {
   return edge_tiles_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_edge_tiles_stats[4]; // edge launches; tile rows, tile columns, GemmVariant of the tile of the latest
+// RAGGED k (xsmm_hip_set_edge_k / TPP_HIP_EDGE_K; gemm_plan.cpp plan_gemm_call, brgemm_f32_lw_kedge.h): 0 = off, 1 = the tile rule, 6 / 7 /
+// 9 / 10 = that GemmVariant's tile. A switch of its own: the edge-tile modes leave a k that is not a multiple of 64 where it is.
+inline bool edge_k_mode_ok(int v) { return v == 0 || v == 1 || v == 6 || v == 7 || v == 9 || v == 10; }
+inline std::atomic<int> g_edge_k{[] {
+  const char *e = getenv("TPP_HIP_EDGE_K");
+  const int v = e ? atoi(e) : 0;
+  return edge_k_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_edge_k_stats[4]; // ragged-k launches; chunks per batch element, overlap o, GemmVariant of the tile of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

@@ -115,6 +115,8 @@ _SIGNATURES = {
     "xsmm_hip_tail_split_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_edge_tiles": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_edge_tiles_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_edge_k": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_edge_k_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_fold_transpose_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_epilogue": (ctypes.c_int, [ctypes.c_int]),
@@ -359,6 +361,17 @@ class XsmmRuntime:
         VNNI-2, 24 + t flat, 28 + t VNNI-4)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_edge_tiles_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_edge_k(self, mode):
+        """f32 whole-layer calls whose k is a multiple of 8 but not of 64 (k >= 64), on the loader-wave tiles: 0 off (default), 1 the tile
+        rule, 6 / 7 / 9 / 10 the tile of that kernel variant; returns the previous mode, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_edge_k(mode)
+
+    def edge_k_stats(self):
+        """(ragged-k launches; chunks per batch element, re-read k-values of the last chunk, variant number of the tile of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_edge_k_stats(out)
         return tuple(int(v) for v in out)
 
     def set_fold_transpose(self, enable):
