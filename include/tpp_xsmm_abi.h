@@ -405,6 +405,33 @@ TPP_XSMM_EXPORT void xsmm_hip_edge_tiles_stats(int64_t out[4]);
  * number of its tile (6, 7, 9, 10). The edge-tile counters do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_edge_k(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_edge_k_stats(int64_t out[4]);
+/* Ragged k, bf16 (opt-in; also TPP_HIP_EDGE_K_BF16, read as a number; a switch of its own: xsmm_hip_set_edge_k leaves every bf16 call
+ * where it is). A whole-layer bf16 call whose k is not a multiple of 64 - a 784-wide input layer, k = 400, 1200, 2000 - is planned on
+ * the generic or the 32x32 K-split kernel, whatever its m and n. With this switch on, a call with k >= 64 and k a multiple of 16 runs on
+ * a bf16 loader-wave tile (32x64 + K2, 64x64, 64x128 or 128x128) as ONE launch: every batch element is read as ceil(k / 64) chunks of
+ * 64, the LAST chunk shifted back to start at k - 64 so that it ends at k, and the MFMA waves skip the o = 64 - k % 64 k-values (16, 32
+ * or 48) at its head that the chunk before it has multiplied (whole 16-k MFMA steps; skipped, not multiplied by zero: an Inf or NaN
+ * there counts once, as data). No load leaves [0, k) of a row of A or k-rows [0, k) of a B element, nothing outside the m x n window
+ * of C is written. No scratch block, no counters: legal on a captured stream.
+ * A call is taken when all of this holds: bf16, no VNNI C, no transposed operand, neither a kernel variant nor the generic kernel
+ * forced, the descriptor's kernel is the generic or the 32x32 K-split one, k >= 64, k % 16 == 0, k % 64 != 0, batch count >= 1, n a
+ * multiple of 8, lda / ldc / strides multiples of 8 and lda, ldc < 2^22, ldb as its image asks (VNNI-2: a multiple of 4 below 2^21; flat:
+ * of 8 below 2^21; VNNI-4: of 2 below 2^20), A, B, C 16-byte and the bias row 8-byte aligned, m >= BM and n >= BN for the tile - and, if
+ * that tile does not divide m and n, a bf16 edge-tile mode (xsmm_hip_set_edge_tiles 2, 20 .. 23) is on as well: the kernel then also
+ * shifts back its last tile row and column. Everything else runs as with the switch off - every tile-queue group, quad, chain and
+ * folded call too; k % 16 != 0 (1000, 200, 72) and k < 64 stay where they are.
+ * mode 0 = off (default); 1 = the tile rule: the cheapest tile by the loader-wave cost model on ceil-divided tile counts among the
+ * tiles that fit and - with the bf16 edge tiles off - divide m and n (a forcing edge-tile mode forces the tile); 20 .. 23 = the tile
+ * 32x64 + K2 / 64x64 / 64x128 / 128x128 wherever it is such a candidate (a test / measurement switch).
+ * Read per invoke; returns the previous mode, -1 (and changes nothing) for any other value. The choice depends on the descriptor, the
+ * batch count, the pointers' alignment and the CU count only: made in strict mode too. xsmm_hip_last_refined_kernel reads
+ * "brgemm_bf16_lw<64x64>, ragged k", or "..., edge tiles, ragged k" when m or n is ragged as well (brgemm_bf16_lw_flatb / _vnni4 for
+ * a flat / VNNI-4 B).
+ * _stats: out[0] bf16 ragged-k launches since process start; of the most recent one: [1] chunks per batch element, [2] o, [3] the
+ * variant number of its tile with its B image (20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4). The edge-tile and the f32 ragged-k counters
+ * do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_edge_k_bf16(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_edge_k_bf16_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

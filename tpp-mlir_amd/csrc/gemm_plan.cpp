@@ -2,6 +2,7 @@
 // tests/golden/gemm_plan.txt (tests/test_gemm_plan.py): a change of a rule or a cost coefficient is a change of that table.
 #include "gemm_plan.h"
 #include "brgemm_f32_lw_kedge.h"
+#include "brgemm_bf16_lw_kedge.h"
 #include <string.h>
 
 namespace tpp {
@@ -294,8 +295,9 @@ static int pick_bf16_lw_image_tile(const GemmDesc &d, int64_t cus, int first_var
 // multiple of 32 or n not of 64: planned on the generic kernel or the 32x32 K-split kernel - on the loader-wave tiles all the same
 // (brgemm_bf16_lw.hip GRP = 3, launch_bf16_lw_edge). What the three B images ask of leading dimensions, strides and lane offsets is
 // bf16_fast_eligible / bf16_flat_eligible / bf16_vnni4_eligible without their m / n terms; returns the image (0 VNNI-2, 2 flat, 4 VNNI-4), -1 = none.
-static int bf16_edge_b_kind(const GemmDesc &d) {
-  if (d.dtype != DT_BF16 || d.vnni_c || d.k <= 0 || d.k % BK) return -1;
+// ragged_k (xsmm_hip_set_edge_k_bf16): the k % 64 term replaced by brgemm_bf16_lw_kedge.h's bkedge_k_ok.
+static int bf16_edge_b_kind(const GemmDesc &d, bool ragged_k = false) {
+  if (d.dtype != DT_BF16 || d.vnni_c || d.k <= 0 || (ragged_k ? !bkedge_k_ok(d.k) : d.k % BK != 0)) return -1;
   if ((d.lda | d.ldc | d.stride_a | d.stride_b) & 7 || d.lda >= (1 << 22) || d.ldc >= (1 << 22)) return -1;
   if (d.vnni_b && d.vnni_factor == 2) return !(d.ldb & 3) && d.ldb < (1 << 21) ? 0 : -1;
   if (d.vnni_b && d.vnni_factor == 4) return !(d.ldb & 1) && d.ldb < (1 << 20) ? 4 : -1;
@@ -309,6 +311,29 @@ static int choose_bf16_edge_tile(const GemmDesc &d, int mode, int64_t chunks, in
   auto tiles = [&](int t) { return (d.m >= BLW_BM[t] && d.n >= BLW_BN[t]) ? ((d.m + BLW_BM[t] - 1) / BLW_BM[t]) * ((d.n + BLW_BN[t] - 1) / BLW_BN[t]) : 0; };
   if (mode >= V_BF16_LW_32x64 && mode <= V_BF16_LW_128x128) return tiles(mode - V_BF16_LW_32x64) > 0 ? mode - V_BF16_LW_32x64 : -1;
   if (mode != 2) return -1;
+  int best = -1;
+  double best_t = 0;
+  for (int t = 3; t >= 0; --t) {
+    if (tiles(t) <= 0) continue;
+    const double cost = blw_cost(t, rounds(tiles(t), cus), (double)chunks);
+    if (best < 0 || cost < best_t) best = t, best_t = cost;
+  }
+  return best;
+}
+
+// RAGGED k, bf16 (xsmm_hip_set_edge_k_bf16, opt-in; brgemm_bf16_lw_kedge.h): a whole-layer bf16 call whose k is a multiple of 16 but not of
+// 64 (k >= 64) - planned on the generic or the 32x32 K-split kernel whatever its m and n - on a loader-wave tile (brgemm_bf16_lw.hip
+// GRP = 4, launch_bf16_lw_kedge). The tile: `forced` (0 .. 3) if there is one, else the cheapest candidate by blw_cost over the rounds of its
+// ceil-divided tile count, priced at br * ceil(k / 64) chunks; ties go to the larger tile. A candidate fits (m >= BM, n >= BN) and - unless
+// a bf16 edge-tile mode is on as well (edge_on: the kernel then shifts back its last tile row / column too) - divides m and n.
+// Returns the tile index 0 .. 3, -1 = none: the call stays where it is. Not fitted to ragged shapes: profiles/edge_k_bf16_ab.txt.
+static int choose_bf16_kedge_tile(const GemmDesc &d, int forced, bool edge_on, int64_t chunks, int64_t cus) {
+  auto tiles = [&](int t) -> int64_t {
+    if (d.m < BLW_BM[t] || d.n < BLW_BN[t]) return 0;
+    if (!edge_on && (d.m % BLW_BM[t] != 0 || d.n % BLW_BN[t] != 0)) return 0;
+    return ((d.m + BLW_BM[t] - 1) / BLW_BM[t]) * ((d.n + BLW_BN[t] - 1) / BLW_BN[t]);
+  };
+  if (forced >= 0) return forced <= 3 && tiles(forced) > 0 ? forced : -1;
   int best = -1;
   double best_t = 0;
   for (int t = 3; t >= 0; --t) {
@@ -488,6 +513,34 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
            "brgemm_bf16_lw_vnni4<128x128>, edge tiles"}};
       GemmLaunch l = launch(GL_BF16_LW, tile, edge_names[kind / 2][tile], 1, kind);
       l.edge = true;
+      return l;
+    }
+  }
+  // bf16 ragged k, if asked for (xsmm_hip_set_edge_k_bf16, a switch of its own; choose_bf16_kedge_tile): k >= 64 a multiple of 16 but not of
+  // 64. Decided here only, like the edge tiles, from the descriptor, the batch count, the pointers' alignment and the CU count: allowed
+  // in strict mode. The tile a forcing edge_k_bf16 value names, else the one a forcing edge-tile mode names, else the rule's; a tile that
+  // does not divide m and n needs a bf16 edge-tile mode on as well. The launcher's own checks: launch_bf16_lw_kedge.
+  if (env.edge_k_bf16 != 0 && d.dtype == DT_BF16 && !d.vnni_c && !d.generic_forced && !d.variant_forced &&
+      (d.variant == V_GENERIC || d.variant == V_BF16_SMALL32) && bkedge_k_ok(d.k) && d.n % 8 == 0 && br >= 1 && al.ab16 && al.c16 && bias_ok8) {
+    const bool force_e = env.edge_tiles >= V_BF16_LW_32x64 && env.edge_tiles <= V_BF16_LW_128x128;
+    const bool edge_on = env.edge_tiles == 2 || force_e;
+    const int forced = env.edge_k_bf16 >= V_BF16_LW_32x64 && env.edge_k_bf16 <= V_BF16_LW_128x128 ? env.edge_k_bf16 - V_BF16_LW_32x64
+                       : force_e ? env.edge_tiles - V_BF16_LW_32x64 : -1;
+    // The rule's gate (measured, profiles/edge_k_bf16_ab.txt: 256x1024x400 3.31 -> 4.27 us, 128x1024x80 3.12 -> 3.55 on the tiles): a call
+    // planned on the 32x32 K-split kernel whose 32x32 tiles fit ONE round of the CUs, with a reduction below that kernel's crossover
+    // against the loader-wave tiles (br * k < 1024, the long-reduction rule below), stays there. A forced tile is a forced tile.
+    const bool gated = forced < 0 && d.variant == V_BF16_SMALL32 && (d.m / 32) * (d.n / 32) <= cus && (int64_t)br * d.k < 1024;
+    const int kind = gated ? -1 : bf16_edge_b_kind(d, true);
+    const int tile = kind >= 0 ? choose_bf16_kedge_tile(d, forced, edge_on, (int64_t)br * bkedge_chunks((int)d.k), cus) : -1;
+    if (tile >= 0) {
+#define KE_NAMES(F, S) {"brgemm_bf16_lw" F "<32x64,k2>" S, "brgemm_bf16_lw" F "<64x64>" S, "brgemm_bf16_lw" F "<64x128>" S, "brgemm_bf16_lw" F "<128x128>" S}
+      static const char *const kedge_names[2][3][4] = {
+          {KE_NAMES("", ", ragged k"), KE_NAMES("_flatb", ", ragged k"), KE_NAMES("_vnni4", ", ragged k")},
+          {KE_NAMES("", ", edge tiles, ragged k"), KE_NAMES("_flatb", ", edge tiles, ragged k"), KE_NAMES("_vnni4", ", edge tiles, ragged k")}};
+#undef KE_NAMES
+      const bool mn_ragged = d.m % BLW_BM[tile] != 0 || d.n % BLW_BN[tile] != 0;
+      GemmLaunch l = launch(GL_BF16_LW, tile, kedge_names[mn_ragged][kind / 2][tile], 1, kind);
+      l.edge_k = true;
       return l;
     }
   }

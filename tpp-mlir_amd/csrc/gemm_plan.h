@@ -44,9 +44,9 @@ enum GemmVariant : int {
 // what the decisions read besides the descriptor: the device's compute units, xsmm_hip_set_strict, xsmm_hip_force_split (-1 = the
 // split model) and xsmm_hip_set_tail_split (0 = off, 1 = the model, 2 .. 16 = that many workgroups per tail tile) and
 // xsmm_hip_set_edge_tiles (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that f32 GemmVariant's tile, 2 = the f32 and the bf16 tile rule, 20 .. 23 =
-// that bf16 GemmVariant's tile) and xsmm_hip_set_edge_k (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that GemmVariant's tile);
-// brgemm_f32.hip gemm_plan_env fills it per call
-struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; };
+// that bf16 GemmVariant's tile) and xsmm_hip_set_edge_k (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that GemmVariant's tile) and
+// xsmm_hip_set_edge_k_bf16 (0 = off, 1 = the bf16 tile rule, 20 .. 23 = that bf16 GemmVariant's tile); brgemm_f32.hip gemm_plan_env fills it per call
+struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
 struct GemmAlign { bool ab16, c16, c8, d8, d16; };
@@ -63,7 +63,7 @@ enum GemmLauncher : int {
   GL_BF16_FAST,       // launch_gemm_bf16_fast(tile)
   GL_BF16_SMALL32,    // launch_bf16_small32(split)
   GL_BF16_GROUPED64,  // launch_bf16_grouped64
-  GL_BF16_LW,         // launch_bf16_lw / _flatb / _vnni4 by b_kind (0 / 2 / 4), tile; edge: launch_bf16_lw_edge(tile, b_kind)
+  GL_BF16_LW,         // launch_bf16_lw / _flatb / _vnni4 by b_kind (0 / 2 / 4), tile; edge: launch_bf16_lw_edge(tile, b_kind); edge_k: launch_bf16_lw_kedge(tile, b_kind)
   GL_BF16_LW_GROUPED, // launch_bf16_lw_grouped(tile, b_kind, even)
   GL_BF16_LW_QUADS,   // launch_bf16_lw_quads(b_kind)
   GL_GENERIC,         // brgemm_grouped<T, VNNI, VEC, VF, FORM>: generic
@@ -89,7 +89,8 @@ struct GemmLaunch {
   // launch_bf16_lw_edge(tile, b_kind) on the ceil-divided tile grid; refused by the launcher: the launch the call has with the mode off
   bool edge = false;
   // GL_F32_LW, ragged k (xsmm_hip_set_edge_k): k is a multiple of 8 but not of 64 - launch_f32_lw_kedge(tile) on the ceil-divided tile
-  // grid (m and n may be ragged too); refused by the launcher: the launch the call has with the mode off
+  // grid (m and n may be ragged too); refused by the launcher: the launch the call has with the mode off.
+  // GL_BF16_LW (xsmm_hip_set_edge_k_bf16): k is a multiple of 16 but not of 64 - launch_bf16_lw_kedge(tile, b_kind), the same way
   bool edge_k = false;
 };
 

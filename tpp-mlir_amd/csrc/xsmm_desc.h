@@ -168,6 +168,15 @@ inline std::atomic<int> g_edge_k{[] {
   return edge_k_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_edge_k_stats[4]; // ragged-k launches; chunks per batch element, overlap o, GemmVariant of the tile of the latest
+// RAGGED k, bf16 (xsmm_hip_set_edge_k_bf16 / TPP_HIP_EDGE_K_BF16; gemm_plan.cpp plan_gemm_call, brgemm_bf16_lw_kedge.h): 0 = off, 1 = the
+// tile rule, 20 .. 23 = that bf16 GemmVariant's tile. A switch of its own: xsmm_hip_set_edge_k leaves every bf16 call where it is.
+inline bool edge_k_bf16_mode_ok(int v) { return v == 0 || v == 1 || (v >= 20 && v <= 23); }
+inline std::atomic<int> g_edge_k_bf16{[] {
+  const char *e = getenv("TPP_HIP_EDGE_K_BF16");
+  const int v = e ? atoi(e) : 0;
+  return edge_k_bf16_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_edge_k_bf16_stats[4]; // bf16 ragged-k launches; chunks per batch element, overlap o, GemmVariant of the tile (with its B image) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)
