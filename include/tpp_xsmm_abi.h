@@ -432,6 +432,23 @@ TPP_XSMM_EXPORT void xsmm_hip_edge_k_stats(int64_t out[4]);
  * do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_edge_k_bf16(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_edge_k_bf16_stats(int64_t out[4]);
+/* Ragged-m layer chains, opt-in (environment: TPP_HIP_CHAIN_EDGE; default 0 = off): a switch of its own - the four ragged-layer switches
+ * above decide single calls and leave every decision of xsmm_hip_fused_brgemm_chain_invoke where it is. mode 1: a bf16 chain of 2 .. 8
+ * calls whose m is not a multiple of the tile's rows BM runs as ONE launch on ceil(m / BM) x n / BN workgroups - the last row block is
+ * shifted back to end at row m, stores only the rows no other block owns, and waits at every seam for both row blocks whose rows it
+ * reads - when everything else the chain launch asks holds as before (one kind of B operand, beta 0, equal m and n, device pointers,
+ * asynchronous mode, no stream capture, no output overlapping an operand, batch elements inside the predecessor's rows) and m >= BM,
+ * n % BN == 0, every k % 64 == 0 and ceil(m / BM) * (n / BN) <= the stream's compute units. The tile: the one
+ * xsmm_hip_set_edge_tiles(20 .. 23) names if it fits, else the smallest of the four that fits. Bit for bit the same calls made one by
+ * one on that tile. Call by call as before: strict mode (xsmm_hip_set_strict: the chain tile is no function of the descriptor alone),
+ * f32 chains, a ragged n or k, a forced kernel, m below every tile's rows - and every chain a tile's rows divide runs as with the switch
+ * off. The launch still needs the device to itself: a starved launch degrades exactly as a divisible one, through probation, the
+ * journal and the re-run (xsmm_hip_chain_status counts). Returns the previous value, -1 (nothing changed) for any other value.
+ * _stats: out[0] ragged chain launches since process start; of the most recent one: [1] tile rows ceil(m / BM), [2] tile columns
+ * n / BN, [3] the variant number of its tile with its B image (20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4), as
+ * xsmm_hip_edge_tiles_stats reports it. The edge-tile counters do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_edge(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_edge_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

@@ -37,6 +37,7 @@
 #include "xsmm_desc.h"
 #include "chain_args.h"
 #include "brgemm_bf16_lw_kedge.h"
+#include "brgemm_bf16_lw_chain_edge.h"
 #include <type_traits>
 
 namespace tpp {
@@ -89,6 +90,9 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   // A row and ldb elements of every B image (a pair-row is 2 k, a VNNI-4 group row 4 k, a flat row 1 k): the shifted start is a whole
   // number of image rows and a multiple of 16 bytes because k % 16 == 0.
   static_assert(GRP != 4 || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
+  // GRP = 5 (a CHAIN on edge ROW tiles, brgemm_bf16_lw_chain_edge.h): the argument block's operands as GRP = 0, m0 of the last row block
+  // shifted back by the kernel; the seam wait of a shifted block is for TWO row blocks' producers (below)
+  static_assert(GRP != 5 || (SUP == 1 && MULTI), "a ragged chain: a chain, one chunk per barrier");
   constexpr int A_SLOT = BM * 128, SLOT = (BM + BN) * 128;
   // SUP = chunks per barrier (the unit everything below counts in: a "chunk" of this function is SUP 64-k chunks, a "slot" SUP
   // consecutive ring slots). SUP = 2 halves the barrier count and the loader's per-iteration scalar work for the small tiles, whose
@@ -214,7 +218,29 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       pre = 0;
       slot = s0;
     }
-    if (poller && lc > 0) {
+    if constexpr (GRP == 5) {
+      if (poller && lc > 0) {
+        // RAGGED m: the rows [m0, m0 + BM) this block reads were stored by the row blocks first_block .. last_block of layer lc-1 - the
+        // block itself and, for the shifted last block, its upper neighbour as well (each block stores its OWN rows only). Every one
+        // of their counters must have reached the target; all the waits share ONE time bound and the one error word.
+        const int b_first = chain_edge_first_block(tm, p.tiles_m, p.m, BM), b_last = chain_edge_last_block(tm, p.tiles_m, p.m, BM);
+        const unsigned target = p.target;
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        for (int bw = b_first; bw <= b_last; ++bw) {
+          g_u32_lw *c = (g_u32_lw *)(p.cnt + ((size_t)(lc - 1) * p.tiles_m + bw) * CHAIN_CNT_STRIDE);
+          for (;;) {
+            const unsigned v = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((int)(v - target) >= 0) break;
+            if (__builtin_amdgcn_s_memrealtime() - t0 > CHAIN_TIMEOUT_TICKS) { // never hang the GPU: flag it and go on
+              if (lane == 0) __hip_atomic_store((g_u32_lw *)p.err, 1u + (unsigned)lc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+          }
+        }
+        asm volatile("" ::: "memory");
+      }
+    } else if (poller && lc > 0) {
       // every producer tile of row block tm of layer lc-1 has been stored (write-through) and drained
       g_u32_lw *c = (g_u32_lw *)(p.cnt + ((size_t)(lc - 1) * p.tiles_m + tm) * CHAIN_CNT_STRIDE);
       const unsigned target = p.target;
@@ -276,16 +302,20 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
 
 template <int WM, int WN, int WK, int TM, int TN, int NSLOT, int NLA, int NLB, int SUP, bool MULTI, int FLATB = 0, int GRP = 0>
 __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_lw(ChainArgs p_by_value) {
-  static_assert(!GRP || !MULTI, "a grouped launch is a set of single layers");
-  static_assert(GRP >= 0 && GRP <= 4, "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k");
+  static_assert(!GRP || !MULTI || GRP == 5, "a grouped launch is a set of single layers");
+  static_assert(GRP >= 0 && GRP <= 5, "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles");
   // operands and batch count from an item (GRP = 1, 2). GRP = 3 (EDGE TILES, a whole layer whose m or n the tile does not divide) has
   // no items: everything from the argument block, as GRP = 0
   constexpr bool ITEMS = GRP == 1 || GRP == 2;
   // GRP = 4 (RAGGED k, xsmm_hip_set_edge_k_bf16): GRP = 3 - with own_row = own_col = 0 a layer the tile divides - whose k is a multiple of
   // 16 but not of 64: the last chunk of every batch element is shifted back to end at k and the MFMA waves skip the k-steps it holds
   // again (brgemm_bf16_lw_kedge.h)
-  constexpr bool EDGE = GRP == 3 || GRP == 4;
+  // GRP = 5 (a CHAIN on edge ROW tiles, xsmm_hip_set_chain_edge): MULTI on ceil(m / BM) x n / BN workgroups - the last row block shifted
+  // back to start at m - BM, storing only its own rows (GRP = 3's row predicate; the columns are whole tiles), and waiting at every seam
+  // for the two row blocks whose rows it reads (blw_loader, brgemm_bf16_lw_chain_edge.h)
+  constexpr bool EDGE = GRP == 3 || GRP == 4 || GRP == 5;
   static_assert(GRP != 4 || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
+  static_assert(GRP != 5 || (SUP == 1 && MULTI), "a ragged chain: a chain, one chunk per barrier");
   static_assert(GRP != 2 || (WM == 2 && WN == 2 && WK == 1 && TM == 2 && TN == 2), "quads: every MFMA wave owns one item's 64x64 output");
   chain_kernarg_t *pp = (chain_kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr(); // = &p_by_value (the only explicit argument)
   chain_kernarg_t &p = *pp;
@@ -390,8 +420,8 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // moved up / left to end at row m / column n. Loaders, LDS images and the K loop see m0 and n0 only and stay inside rows [0, m) and
   // columns [0, n); the tile stores the rows >= own_row and the 16-byte pieces at columns >= own_col of its block (TILE-relative: the
   // tiles have several wave columns) - the others are the neighbour's. n0 is a multiple of 8 (the planner asks for n % 8 == 0).
-  const int m0 = (EDGE && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
-  const int n0 = ((GRP == 1 || EDGE) && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
+  const int m0 = GRP == 5 ? chain_edge_row0(tm, p.tiles_m, p.m, BM) : (EDGE && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
+  const int n0 = ((GRP == 1 || (EDGE && GRP != 5)) && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
   [[maybe_unused]] const int skip_cols = tn * BN - n0;
   [[maybe_unused]] const int own_row = tm * BM - m0, own_col = tn * BN - n0;
   const int L = MULTI ? p.nlayers : 1;
@@ -816,7 +846,8 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
           if (GRP == 1 && ch * 8 < skip_cols) continue; // (a ragged item's last column tile: these columns are the neighbour tile's)
           // (edge tiles: rows and 16-byte pieces in front of the tile's own are the neighbour's - a per-lane predicate on the store.
           // The beta = 1 join above reads the whole block: it lies inside the matrix, and what is not owned is never stored)
-          if (EDGE && (wm * 32 * TM + 32 * i + row < own_row || wn * 32 * TN + ch * 8 < own_col)) continue;
+          if (EDGE && GRP != 5 && (wm * 32 * TM + 32 * i + row < own_row || wn * 32 * TN + ch * 8 < own_col)) continue;
+          if (GRP == 5 && wm * 32 * TM + 32 * i + row < own_row) continue; // (a ragged chain: whole column tiles)
           if (MULTI && l + 1 < L) __builtin_amdgcn_raw_buffer_store_b128(v, rsrcC, voff, 0, 16); // sc1: write-through (hand-off)
           else __builtin_amdgcn_raw_buffer_store_b128(v, rsrcC, voff, 0, C_STORE_AUX); // (last layer / single layer: gemm_common.h)
         }
@@ -843,9 +874,9 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   static std::atomic<unsigned long long> lds_set{0};
   if (hipError_t e = ensure_dynamic_lds((const void *)kern, (int)lds, lds_set); e != hipSuccess) return e;
   ChainArgs args = a;
-  constexpr bool EDGE = GRP == 3 || GRP == 4;
+  constexpr bool EDGE = GRP == 3 || GRP == 4 || GRP == 5; // (5, a ragged chain: rows only - n % BN == 0 is the launcher's check)
   args.tiles_m = EDGE ? (a.m + BM - 1) / BM : a.m / BM; // (edge tiles: ceil-divided both ways, m >= BM and n >= BN)
-  args.tiles_n = (GRP == 1 || EDGE) ? (a.n + BN - 1) / BN : a.n / BN; // (grouped items: a ragged last column tile, see the kernel)
+  args.tiles_n = (GRP == 1 || (EDGE && GRP != 5)) ? (a.n + BN - 1) / BN : a.n / BN; // (grouped items: a ragged last column tile, see the kernel)
   long long tiles = (long long)args.tiles_m * args.tiles_n;
   if (EDGE && (a.m < BM || a.n < BN)) return hipErrorInvalidValue;
   if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -1033,6 +1064,33 @@ hipError_t launch_bf16_chain(int tile, int b_kind, const ChainArgs &a, hipStream
     BLW_DISPATCH(true, 4)
   }
   BLW_DISPATCH(true, 0)
+}
+
+// a RAGGED-m chain (xsmm_hip_set_chain_edge; gemm_plan.cpp plan_chain_edge, brgemm_bf16_lw_chain_edge.h): launch_bf16_chain's layers on
+// ceil(m / BM) x n / BN workgroups of tile 0 .. 3 (GRP = 5: the last row block shifted back to end at row m, storing its own rows only and
+// waiting at every seam for both row blocks whose rows it reads). The caller's guarantees are launch_bf16_chain's, with tiles counted
+// on the ceil-divided grid. One chunk per barrier only. hipErrorInvalidValue (nothing launched): m < BM, n % BN, a k % 64 or k < 64, an
+// empty batch, fewer than 2 or more than CH_MAXL layers.
+hipError_t launch_bf16_chain_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s) {
+  static const int bm[4] = {32, 64, 64, 128}, bn[4] = {64, 64, 128, 128};
+  if (tile < 0 || tile > 3 || (b_kind != 0 && b_kind != 2 && b_kind != 4) || a.nlayers < 2 || a.nlayers > CH_MAXL) return hipErrorInvalidValue;
+  if (a.m < bm[tile] || a.n < bn[tile] || a.n % bn[tile] != 0) return hipErrorInvalidValue;
+  for (int l = 0; l < a.nlayers; ++l)
+    if (a.L[l].br < 1 || a.L[l].k < BLW_BK || a.L[l].k % BLW_BK != 0) return hipErrorInvalidValue;
+#define BLW_CHAIN_EDGE(FB)                                                                   \
+  switch (tile) {                                                                            \
+  case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, true, FB, 5>(a, s);                 \
+  case 1: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, true, FB, 5>(a, s);                 \
+  case 2: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, true, FB, 5>(a, s);                 \
+  default: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, true, FB, 5>(a, s);                \
+  }
+  if (b_kind == 2) {
+    BLW_CHAIN_EDGE(2)
+  } else if (b_kind == 4) {
+    BLW_CHAIN_EDGE(4)
+  }
+  BLW_CHAIN_EDGE(0)
+#undef BLW_CHAIN_EDGE
 }
 
 } // namespace tpp

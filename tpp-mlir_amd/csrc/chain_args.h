@@ -50,6 +50,9 @@ hipError_t launch_bf16_chain(int tile, int b_kind, const ChainArgs &a, hipStream
 // one layer whose m or n the tile does not divide, on edge tiles (xsmm_hip_set_edge_tiles): tile 0 .. 3, b_kind 0 VNNI-2 / 2 flat / 4 VNNI-4;
 // hipErrorInvalidValue and nothing launched when m < BM, n < BN, the batch count < 1 or k < 64
 hipError_t launch_bf16_lw_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
+// a chain whose m the tile's rows do not divide (xsmm_hip_set_chain_edge; brgemm_bf16_lw_chain_edge.h): launch_bf16_chain on ceil(m / BM) x n / BN
+// workgroups; hipErrorInvalidValue and nothing launched when m < BM, n % BN, a k % 64 or a batch count < 1
+hipError_t launch_bf16_chain_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
 hipError_t launch_bf16_lw_kedge(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k (brgemm_bf16_lw_kedge.h); hipErrorInvalidValue: not launched
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2 (VNNI-2 only); b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)

@@ -460,6 +460,36 @@ int bf16_lw_b_kind(const GemmDesc &d) {
   return bf16_flat_eligible(d) ? 2 : -1;
 }
 
+int chain_edge_b_kind(const GemmDesc &d, int chain_edge, const char **why) {
+  const char *w = nullptr;
+  int kind = -1;
+  if (!chain_edge) w = "ragged chains are off (xsmm_hip_set_chain_edge)";
+  else if (d.dtype != DT_BF16) w = "a ragged chain is bf16: an f32 call";
+  else if (d.vnni_c || !d.beta0) w = "a call of a ragged chain stores a VNNI C or is not beta 0";
+  else if (d.generic_forced || d.variant_forced) w = "a call of a ragged chain was dispatched to a forced kernel";
+  else if ((kind = bf16_edge_b_kind(d)) < 0) w = "a call of a ragged chain has k not in 64-k chunks or an operand off the grid of the LDS-DMA tiles";
+  if (why) *why = w;
+  return w ? -1 : kind;
+}
+
+ChainEdgePlan plan_chain_edge(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, bool strict) {
+  if (strict) return ChainEdgePlan{-1, "strict mode: the tile of a ragged chain is not a function of the descriptor alone"};
+  if (nlayers < 2 || nlayers > 8) return ChainEdgePlan{-1, "fewer than 2 or more than 8 calls"};
+  for (int l = 0; l < nlayers; ++l)
+    if (k[l] < BK || k[l] % BK != 0 || br[l] < 1) return ChainEdgePlan{-1, "a layer of a ragged chain has k not in 64-k chunks, or an empty batch"};
+  auto fits = [&](int t) { return t >= 0 && t <= 3 && m >= BLW_BM[t] && n % BLW_BN[t] == 0 && ((m + BLW_BM[t] - 1) / BLW_BM[t]) * (n / BLW_BN[t]) <= cus; };
+  int tile = fits(forced_tile) ? forced_tile : -1;
+  for (int t = 0; t < 4 && tile < 0; ++t)
+    if (fits(t)) tile = t;
+  if (tile < 0) {
+    if (m < BLW_BM[0]) return ChainEdgePlan{-1, "a ragged chain's m is below every tile's rows"};
+    if (n % BLW_BN[0] != 0) return ChainEdgePlan{-1, "a ragged chain's n is not in whole column tiles"};
+    return ChainEdgePlan{-1, "more tiles than compute units"};
+  }
+  if (m % BLW_BM[tile] == 0) return ChainEdgePlan{-1, "the tile's rows divide m: not a ragged chain"};
+  return ChainEdgePlan{tile, ""};
+}
+
 static GemmLaunch launch(GemmLauncher l, int tile = 0, const char *text = "", int split = 1, int b_kind = 0, bool even = false) {
   return GemmLaunch{l, tile, split, b_kind, even, false, GG_F32, text};
 }

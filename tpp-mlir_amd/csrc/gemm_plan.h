@@ -111,6 +111,21 @@ inline bool gemm_on_x6(const GemmDesc &d) { return d.variant >= V_F32_X6_64x64 &
 // which B image of the loader-wave bf16 tiles (brgemm_bf16_lw.hip) a descriptor's B operand needs - 0: VNNI-2, 2: flat [k][ldb],
 // 4: VNNI-4 - or -1 if the descriptor cannot run on those tiles (shape / alignment / lane-offset limits of the LDS-DMA panels)
 int bf16_lw_b_kind(const GemmDesc &d);
+// RAGGED-m CHAINS (xsmm_hip_set_chain_edge; rt_chain.h try_chain_launch, brgemm_bf16_lw.hip launch_bf16_chain_edge). Host-only, no HIP calls:
+// tests/golden/gemm_plan_chain_edge.txt is the table of both functions' answers.
+// One call of a chain: the B image (0 VNNI-2, 2 flat, 4 VNNI-4) it would run with as a layer of a ragged-m chain - what bf16_lw_b_kind asks of
+// leading dimensions, strides and lane offsets without its m and n terms -, or -1 and *why: the switch is off, an f32 call, a VNNI C,
+// beta 1, a forced kernel (xsmm_hip_force_variant, the generic kernel included), k not in 64-k chunks, an operand off the LDS-DMA grid.
+int chain_edge_b_kind(const GemmDesc &d, int chain_edge, const char **why);
+// The tile of the ONE launch: m x n outputs per layer, nlayers layers of k[l] per batch element and br[l] batch elements, cus compute
+// units on the stream, forced_tile 0 .. 3 = the tile xsmm_hip_set_edge_tiles(20 .. 23) names (-1: none), strict = xsmm_hip_set_strict.
+// A tile FITS when m >= BM, n % BN == 0 and ceil(m / BM) * (n / BN) <= cus (every workgroup resident at once). The forced tile if it
+// fits, else the smallest of tiles 0 .. 3 that fits. tile = -1 and why = the NOCHAIN reason: strict mode (the chain tile is no function
+// of the descriptor alone), fewer than 2 or more than 8 layers, a k % 64 or an empty batch, no tile fits (m below every tile's rows, n
+// not in whole column tiles, more tiles than compute units), or the chosen tile's rows divide m (not a ragged chain: the divisible
+// chain's rules decide).
+struct ChainEdgePlan { int tile; const char *why; };
+ChainEdgePlan plan_chain_edge(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, bool strict);
 // 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none
 int f32_chain_tile(const GemmDesc &d);
 // tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip)

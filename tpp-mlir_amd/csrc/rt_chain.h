@@ -170,8 +170,22 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   // f32 chains (round 4): every call planned on the SAME K-split loader-wave tile (the launch is then bit-identical to the calls)
   const bool f32 = d[0]->dtype == DT_F32;
   const int f32_tile = f32 ? f32_chain_tile(*d[0]) : -1;
+  // RAGGED m (xsmm_hip_set_chain_edge, opt-in; gemm_plan.cpp plan_chain_edge): where the rules of the divisible chain below say no
+  // because of the SHAPE - a call no loader-wave tile divides (no B image by bf16_lw_b_kind, planned on the generic kernel), no tile
+  // whose rows divide m fits the compute units - a bf16 chain may still run as one launch on edge row tiles. `divisible` = the
+  // rules as they are with the switch off still hold; edge_kind = the B image of the ragged launch, edge_why = why there is none.
+  // With the switch off edge_on is false and every NOCHAIN below is taken exactly as before.
+  const int chain_edge = g_chain_edge.load(std::memory_order_relaxed);
+  const bool edge_on = !f32 && chain_edge != 0;
+  bool divisible = true;
+  const char *edge_why = nullptr;
+  const int edge_kind = edge_on ? chain_edge_b_kind(*d[0], chain_edge, &edge_why) : -1;
   for (int i = 0; i < n; ++i) {
     const GemmDesc &g = *d[i];
+    if (edge_on && !edge_why) {
+      const char *w = nullptr;
+      if (chain_edge_b_kind(g, chain_edge, &w) != edge_kind) edge_why = w ? w : "the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)";
+    }
     if (f32) {
       if (g.dtype != DT_F32 || !g.beta0 || f32_chain_tile(g) < 0 || f32_chain_tile(g) != f32_tile)
         NOCHAIN("an f32 call is not beta 0 / not planned on the K-split loader-wave tile of the first call");
@@ -179,10 +193,16 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
       if (g.ldc & 3) NOCHAIN("an f32 output's leading dimension is not a multiple of 4");
     } else
     // every layer the same kind of B operand (VNNI-2, flat or VNNI-4: the B image is a template parameter of the launch)
-    if (g.dtype != DT_BF16 || g.vnni_c || !g.beta0 || bf16_lw_b_kind(g) < 0 || bf16_lw_b_kind(g) != bf16_lw_b_kind(*d[0]))
-      NOCHAIN("a call is not bf16 / beta 0 / aligned for the LDS-DMA tiles, or the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)");
+    if (g.dtype != DT_BF16 || g.vnni_c || !g.beta0 || bf16_lw_b_kind(g) < 0 || bf16_lw_b_kind(g) != bf16_lw_b_kind(*d[0])) {
+      if (!edge_on || edge_why) // (edge_why: no ragged launch either - an f32 call, a VNNI C, beta 1, a forced kernel, k % 64, the operands' grid)
+        NOCHAIN("a call is not bf16 / beta 0 / aligned for the LDS-DMA tiles, or the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)");
+      divisible = false;
+    }
     if (g.m != m || g.n != nn || br[i] < 1) NOCHAIN("the calls differ in m or n, or a batch is empty");
-    if (g.variant == V_GENERIC) NOCHAIN("a call was dispatched to the generic kernel"); // (a forced generic kernel stays generic)
+    if (g.variant == V_GENERIC) { // (a forced generic kernel stays generic; one that is generic only because no tile divides m may run ragged)
+      if (!edge_on || edge_why || g.generic_forced) NOCHAIN("a call was dispatched to the generic kernel");
+      divisible = false;
+    }
     if (((uintptr_t)pa[i] | (uintptr_t)pb[i] | (uintptr_t)pc[i]) & 15) NOCHAIN("an operand is not 16-byte aligned");
     if (g.bias && (!pd[i] || ((uintptr_t)pd[i] & 7))) NOCHAIN("a bias operand is not 8-byte aligned");
     if (i > 0 && (pa[i] != pc[i - 1] || g.lda != d[i - 1]->ldc)) NOCHAIN("not a chain: a call does not read its predecessor's output");
@@ -193,6 +213,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (!devmem.is_device(pa[i], 0) || !devmem.is_device(pb[i], 1) || !devmem.is_device(pc[i], 2) || (g.bias && !devmem.is_device(pd[i], 3)))
       NOCHAIN("a host operand");
   }
+  if (!divisible && edge_why) NOCHAIN(edge_why);
   // The tile: all workgroups must be co-resident (one per CU by LDS), so the grid may not exceed the CUs. If every layer was planned
   // with the same loader-wave tile and that tile fits, use it - the launch is then bit-identical to the separate launches; else
   // the smallest tile that fits (most CUs busy).
@@ -204,18 +225,33 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     return m % bm == 0 && nn % bn == 0 && (m / bm) * (nn / bn) <= cus;
   };
   if (f32 && !fits(f32_tile)) NOCHAIN("more tiles than compute units");
-  const int b_kind = f32 ? 0 : bf16_lw_b_kind(*d[0]);
-  // (variants 20 .. 23 VNNI-2, 24 .. 27 flat B, 28 .. 31 VNNI-4: the same four tiles)
-  const int planned = d[0]->variant - (b_kind == 2 ? V_BF16_LWF_32x64 : b_kind == 4 ? V_BF16_LW4_32x64 : V_BF16_LW_32x64);
-  bool same = !f32 && planned >= 0 && planned < 4;
-  for (int i = 1; i < n && same; ++i) same = d[i]->variant == d[0]->variant;
-  if (f32) tile = f32_tile;
-  if (same && fits(planned)) tile = planned;
-  if (tile < 0 && cfg().strict.load(std::memory_order_relaxed)) NOCHAIN("strict mode: one launch only on the tile the layers were planned on");
-  for (int t = 0; t < 4 && tile < 0; ++t)
-    if (fits(t)) tile = t;
-  if (tile < 0) NOCHAIN("more tiles than compute units");
-  (void)fits(tile); // bm, bn of the chosen tile
+  int b_kind = f32 || !divisible ? 0 : bf16_lw_b_kind(*d[0]);
+  if (divisible) {
+    // (variants 20 .. 23 VNNI-2, 24 .. 27 flat B, 28 .. 31 VNNI-4: the same four tiles)
+    const int planned = d[0]->variant - (b_kind == 2 ? V_BF16_LWF_32x64 : b_kind == 4 ? V_BF16_LW4_32x64 : V_BF16_LW_32x64);
+    bool same = !f32 && planned >= 0 && planned < 4;
+    for (int i = 1; i < n && same; ++i) same = d[i]->variant == d[0]->variant;
+    if (f32) tile = f32_tile;
+    if (same && fits(planned)) tile = planned;
+    if (tile < 0 && cfg().strict.load(std::memory_order_relaxed)) NOCHAIN("strict mode: one launch only on the tile the layers were planned on");
+    for (int t = 0; t < 4 && tile < 0; ++t)
+      if (fits(t)) tile = t;
+    if (tile < 0 && (!edge_on || edge_why)) NOCHAIN("more tiles than compute units");
+  }
+  const bool ragged = tile < 0; // (only with the switch on: every path to here with it off has a tile)
+  if (ragged) {
+    // the ragged launch: the tile a forcing edge-tile mode names if it fits, else the smallest that fits - counted on the ceil-divided grid
+    int64_t ks[CH_MAXL], brs[CH_MAXL];
+    for (int i = 0; i < n; ++i) ks[i] = d[i]->k, brs[i] = br[i];
+    const int et = g_edge_tiles.load(std::memory_order_relaxed);
+    const ChainEdgePlan ep = plan_chain_edge(m, nn, n, ks, brs, cus, et >= V_BF16_LW_32x64 && et <= V_BF16_LW_128x128 ? et - V_BF16_LW_32x64 : -1,
+                                             cfg().strict.load(std::memory_order_relaxed));
+    if (ep.tile < 0) NOCHAIN(ep.why);
+    tile = ep.tile;
+    b_kind = edge_kind;
+  }
+  if (f32) (void)f32_chain_tile_dims(tile, &bm, &bn); // bm, bn of the chosen tile
+  else blw_tile_dims(tile, &bm, &bn);
   // no operand of the launch may overlap an output (a layer's input rows are read by other workgroups while later layers store)
   Operand A, B, C, D;
   struct Span { const void *p; size_t n; };
@@ -266,7 +302,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (g_chain_shared.load(std::memory_order_acquire)) return false; // (found a starved launch: call by call from here on)
   }
   std::lock_guard<std::mutex> lk(g_chain_mu);
-  ChainBlock &blk = chain_block(s, (int)(m / bm), (int)(nn / bn), n);
+  ChainBlock &blk = chain_block(s, (int)((m + bm - 1) / bm), (int)(nn / bn), n); // (a ragged chain: keyed on ceil(m / BM), the counters it uses)
   c.cnt = blk.cnt;
   c.err = blk.err; // probation launches: the block's word (checked right behind the launch)
   if (blk.verified >= 1) {
@@ -284,7 +320,13 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   }
   c.target = ++blk.epoch * (unsigned)blk.tiles_n;
   if (f32) HIP_OK(launch_f32_chain(tile, c, s));
-  else HIP_OK(launch_bf16_chain(tile, b_kind, c, s));
+  else if (ragged) {
+    HIP_OK(launch_bf16_chain_edge(tile, b_kind, c, s));
+    g_chain_edge_stats[1].store((m + bm - 1) / bm, std::memory_order_relaxed);
+    g_chain_edge_stats[2].store(nn / bn, std::memory_order_relaxed);
+    g_chain_edge_stats[3].store((b_kind == 4 ? V_BF16_LW4_32x64 : b_kind == 2 ? V_BF16_LWF_32x64 : V_BF16_LW_32x64) + tile, std::memory_order_relaxed);
+    g_chain_edge_stats[0].fetch_add(1, std::memory_order_relaxed);
+  } else HIP_OK(launch_bf16_chain(tile, b_kind, c, s));
   if (blk.verified < 1) {
     // probation (comment at ChainBlock): wait for this launch and look at its error word before anyone can consume its outputs
     HIP_OK(hipStreamSynchronize(s));

@@ -40,6 +40,20 @@
 
 using namespace tpp;
 
+// Ragged-m chains (rt_chain.h try_chain_launch; xsmm_hip_set_chain_edge): the planner's two functions live in gemm_plan.cpp, the launcher
+// in brgemm_bf16_lw.hip. The host-only builds of this file (tests/tsan and its kin) link neither - their kernel stand-ins predate the
+// switch -, so WEAK stand-ins that refuse are defined here: the library's link takes the real definitions, a host-only build these.
+namespace tpp {
+__attribute__((weak)) int chain_edge_b_kind(const GemmDesc &, int, const char **why) {
+  if (why) *why = "this build has no ragged-chain planner";
+  return -1;
+}
+__attribute__((weak)) ChainEdgePlan plan_chain_edge(int64_t, int64_t, int, const int64_t *, const int64_t *, int64_t, int, bool) {
+  return ChainEdgePlan{-1, "this build has no ragged-chain planner"};
+}
+__attribute__((weak)) hipError_t launch_bf16_chain_edge(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
+} // namespace tpp
+
 namespace {
 // The subsystems (each file says what it holds; ONE translation unit: see the note at the top of any of them):
 #include "rt_core.h"      // die / HIP_OK, Config + environment switches, tracing
@@ -538,6 +552,10 @@ extern "C" void xsmm_hip_edge_k_stats(int64_t out[4]) {
 extern "C" int xsmm_hip_set_edge_k_bf16(int mode) { return tpp::edge_k_bf16_mode_ok(mode) ? tpp::g_edge_k_bf16.exchange(mode) : -1; }
 extern "C" void xsmm_hip_edge_k_bf16_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k_bf16_stats[i].load(std::memory_order_relaxed);
+}
+extern "C" int xsmm_hip_set_chain_edge(int mode) { return tpp::chain_edge_mode_ok(mode) ? tpp::g_chain_edge.exchange(mode) : -1; }
+extern "C" void xsmm_hip_chain_edge_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_edge_stats[i].load(std::memory_order_relaxed);
 }
 extern "C" void xsmm_hip_tail_split_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_tail_split_stats[i].load(std::memory_order_relaxed);

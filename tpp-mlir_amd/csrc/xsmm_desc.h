@@ -177,6 +177,16 @@ inline std::atomic<int> g_edge_k_bf16{[] {
   return edge_k_bf16_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_edge_k_bf16_stats[4]; // bf16 ragged-k launches; chunks per batch element, overlap o, GemmVariant of the tile (with its B image) of the latest
+// RAGGED-m CHAINS (xsmm_hip_set_chain_edge / TPP_HIP_CHAIN_EDGE; gemm_plan.cpp plan_chain_edge, rt_chain.h try_chain_launch,
+// brgemm_bf16_lw_chain_edge.h): 0 = off, 1 = a bf16 chain whose m the tile's rows do not divide runs as one launch on edge row tiles. A
+// switch of its own: the four ragged-layer switches above decide single calls only and leave every chain decision where it is.
+inline bool chain_edge_mode_ok(int v) { return v == 0 || v == 1; }
+inline std::atomic<int> g_chain_edge{[] {
+  const char *e = getenv("TPP_HIP_CHAIN_EDGE");
+  const int v = e ? atoi(e) : 0;
+  return chain_edge_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_chain_edge_stats[4]; // ragged chain launches; tile rows, tile columns, GemmVariant of the tile (with its B image) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

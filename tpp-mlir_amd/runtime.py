@@ -119,6 +119,8 @@ _SIGNATURES = {
     "xsmm_hip_edge_k_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_edge_k_bf16": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_edge_k_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_chain_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_fold_transpose_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_epilogue": (ctypes.c_int, [ctypes.c_int]),
@@ -386,6 +388,18 @@ class XsmmRuntime:
         image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_edge_k_bf16_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_chain_edge(self, mode):
+        """bf16 layer chains whose m the tile's rows do not divide, as one launch on edge row tiles: 0 off (default), 1 on - the tile
+        set_edge_tiles(20 .. 23) names if it fits, else the smallest that fits; returns the previous value, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_chain_edge(mode)
+
+    def chain_edge_stats(self):
+        """(ragged chain launches; tile rows, tile columns, variant number of the tile with its B image - 20 + t VNNI-2, 24 + t flat,
+        28 + t VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_chain_edge_stats(out)
         return tuple(int(v) for v in out)
 
     def set_fold_transpose(self, enable):
