@@ -432,6 +432,22 @@ TPP_XSMM_EXPORT void xsmm_hip_edge_k_stats(int64_t out[4]);
  * do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_edge_k_bf16(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_edge_k_bf16_stats(int64_t out[4]);
+/* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
+ * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
+ * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two
+ * K groups), two workgroups to a CU. Every output element is computed exactly as before - the same two k-ordered chains, summed in the
+ * same order: bit for bit the result of the switch off. xsmm_hip_kernel_name and xsmm_hip_last_refined_kernel do not change. No scratch
+ * block, no counters, no waiting between workgroups: legal on a captured stream and in strict mode.
+ * A call is taken when all of this holds: it would run on launch_f32_lw's 64x64 + K2 tile as ONE plain launch (no split, forced or
+ * modelled; no tail split; not an edge-tile or ragged-k launch), m and n multiples of 64. Tile-queue groups and chain launches run as
+ * with the switch off.
+ * mode 0 = off; 1 = the rule (default): eligible calls with at least one 64x64 tile per compute unit, where the form measured faster
+ * (profiles/f32_halves_ab.txt); 2 = wherever eligible (a test / measurement switch). Read per invoke; returns the previous mode, -1
+ * (and changes nothing) for any other value.
+ * _stats: out[0] launches carried out as halves since process start; of the most recent one: [1] rows and [2] columns of 64x64 tiles;
+ * [3] 0. */
+TPP_XSMM_EXPORT int xsmm_hip_set_f32_halves(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_f32_halves_stats(int64_t out[4]);
 /* Ragged-m layer chains, opt-in (environment: TPP_HIP_CHAIN_EDGE; default 0 = off): a switch of its own - the four ragged-layer switches
  * above decide single calls and leave every decision of xsmm_hip_fused_brgemm_chain_invoke where it is. mode 1: a bf16 chain of 2 .. 8
  * calls whose m is not a multiple of the tile's rows BM runs as ONE launch on ceil(m / BM) x n / BN workgroups - the last row block is

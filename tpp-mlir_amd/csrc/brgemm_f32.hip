@@ -694,6 +694,7 @@ hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         //
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
 hipError_t launch_f32_lw_tail(int tile, const GemmArgs &a, int tail_tiles, int split, hipStream_t s); // the same
+hipError_t launch_f32_lw_halves(const GemmArgs &a, hipStream_t s); // tile 1 as two 64x32 + K2 workgroups per tile, the same bits; hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw_edge(int tile, const GemmArgs &a, hipStream_t s); // m or n not a multiple of the tile; hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw_kedge(int tile, const GemmArgs &a, hipStream_t s); // k a multiple of 8 but not of 64 (m, n ragged or not); hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw16(int tile, const GemmArgs &a, const WorkItem *items, int n_items, bool grouped, hipStream_t s); // brgemm_f32_lw16.hip: tile 0 = 32x16
@@ -729,7 +730,7 @@ bool strict_kernels() { return g_strict_kernels.load(std::memory_order_relaxed) 
 static GemmPlanEnv gemm_plan_env() {
   return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed), g_tail_split.load(std::memory_order_relaxed),
                      g_edge_tiles.load(std::memory_order_relaxed), g_edge_k.load(std::memory_order_relaxed),
-                     g_edge_k_bf16.load(std::memory_order_relaxed)};
+                     g_edge_k_bf16.load(std::memory_order_relaxed), g_f32_halves.load(std::memory_order_relaxed)};
 }
 bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, gemm_plan_env()); }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, gemm_plan_env()); }
@@ -898,6 +899,18 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     text = "";
   }
   g_last_refined.store(text, std::memory_order_relaxed);
+  if (p.halves && p.launcher == GL_F32_LW && p.tile == 1) { // the tiles as two halves each (xsmm_desc.h g_f32_halves): the same kernel name and text
+    const hipError_t e = launch_f32_lw_halves(a, stream);
+    if (e != hipErrorInvalidValue) {
+      if (e == hipSuccess) {
+        g_f32_halves_stats[1].store(d.m / 64, std::memory_order_relaxed);
+        g_f32_halves_stats[2].store(d.n / 64, std::memory_order_relaxed);
+        g_f32_halves_stats[0].fetch_add(1, std::memory_order_relaxed);
+      }
+      return e;
+    }
+    (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
+  }
   return run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
 }
 

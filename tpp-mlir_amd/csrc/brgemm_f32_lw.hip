@@ -652,6 +652,22 @@ template <int WM, int WN, int WK, int NL = 1, int NSLOT = LW_NSLOT, int NLB = NL
   return lw_launch<I>(dim3(blocks ? 8 : 1, args.tiles_n, args.tiles_m), s, args);
 }
 
+// ---- HALVES: a 64x64 + K2 layer as two 64x32 + K2 workgroups per output tile (xsmm_hip_set_f32_halves; gemm_plan.cpp choose_f32_halves) -
+// LwTile<2, 1, 2, 3>: 4 MFMA waves = the two K groups of ONE 32-column half of the 64x64 + K2 tile, on a 3-slot ring of 24 KiB slots
+// (72 KiB: two workgroups fit a CU's 160 KiB, 7 waves each). Every output element gets what the 64x64 + K2 tile gives it: K group 0's
+// chain over k 0..31 of every chunk, group 1's over k 32..63, summed in group order - the bits of launch_f32_lw(1). (The 64x32 + K4
+// tile of launch_f32_lw(2) splits a chunk four ways: other bits.) Each SIMD then holds one MFMA wave of each of two INDEPENDENT
+// workgroups - own barrier, own ring, own loaders - instead of two waves that meet the same barrier. No workgroup waits for another and
+// nothing requires the two to be co-resident. The grid is launch_lw_t's with BN = 32: the halves of a tile are neighbours along the
+// grid's y in one XCD block wherever the block's width in halves is even. m, n multiples of 64 (whole 64x64 tiles), k of 64.
+// hipErrorInvalidValue: not launched, use launch_f32_lw(1).
+hipError_t launch_f32_lw_halves(const GemmArgs &a, hipStream_t s) {
+  if (a.m <= 0 || a.n <= 0 || a.m % 64 || a.n % 64 || a.k <= 0 || a.k % LW_BK || a.br < 0) return hipErrorInvalidValue;
+  // loader waves: two for the A panel (16 requests per chunk) and one for B (8), every loader issues 8. C2, six alternating runs on one
+  // box (profiles/f32_halves_ab.txt): 17.17-17.22 us; one loader per panel 17.27-17.31; the 64x64 + K2 tile 17.63-17.67
+  return launch_lw_t<2, 1, 2, 2, 3, 1>(a, s);
+}
+
 // tile as in launch_f32_lw; split > 1: that many workgroups per output tile (K-split tiles 1 .. 3 only); n may end inside the last tile
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s) {
   if (split > 1) {
@@ -744,6 +760,8 @@ hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s) {
   case 0: return launch_lw_t<2, 2, 1>(a, s);
   // two loader waves per panel for the 8-wave tile (C2): the 16 + 16 requests of a chunk - above all of chunk 0, which every MFMA
   // wave waits for - go out in half the time; same-box A/B 18.10 -> 17.97 us. The 64x32 tile (C3) measured 1 % slower with them.
+  // (launch_f32_lw_halves above runs the same tiles as two 64x32 + K2 workgroups each, the same bits: C2 17.64 -> 17.19 us same-box;
+  // the planner's rule takes it wherever there is a tile per CU, this launch stays for everything else and as the fall-back)
   case 1: return launch_lw_t<2, 2, 2, 2>(a, s); // (four per panel: 18.25 us)
   // 64x32 with K split over FOUR wave groups: 8 MFMA waves = two per SIMD, like the 64x64 k2 tile - one wave's fragment reads and
   // barrier waits hide behind the other's MFMAs. C3 (512 x 1024 x 1024): 10.52 -> 10.21 us same-box against the K2 split (4 waves).

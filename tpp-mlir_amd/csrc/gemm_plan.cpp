@@ -152,6 +152,21 @@ static int choose_f32_tail_split(int tile, long long tiles, long long chunks, co
   return (int)S;
 }
 
+// HALVES (xsmm_hip_set_f32_halves; brgemm_f32_lw.hip launch_f32_lw_halves): a whole-layer call on the 64x64 + K2 tile whose every tile
+// runs as two independent 64x32 + K2 workgroups, two to a CU - the same bits, so the variant, the kernel name and the launch's text stay
+// what they are. Eligible: tile 1 with no split and no tail split (the caller's), m and n in whole 64x64 tiles; edge tiles and ragged k
+// are planned elsewhere and never come here, queued groups and chains do not go through plan_gemm_call. Mode 2 (tests, measurements):
+// wherever eligible. Mode 1, the rule: at least one tile per CU - every such class measured faster on one box
+// (profiles/f32_halves_ab.txt): one round (C2 17.64 -> 17.19 us in six of six alternating pairs, 1024 x 1024 x 512 10.57 -> 10.27), two
+// rounds (2048 x 1024 x 1024 33.98 -> 32.69), and most where the last round is partial, because a half is also half the scheduling
+// unit: 1.5 rounds (1024 x 1536 x 1024 33.62 -> 25.6), 2.5 rounds (1024 x 2560 x 1024 49.93 -> 41.26). Fewer tiles than CUs - a forced
+// tile only, the planner takes smaller tiles there - have not been measured and stay as they are.
+// Descriptor and CU count only: allowed in strict mode.
+static bool choose_f32_halves(int tile, const GemmDesc &d, long long tiles, const GemmPlanEnv &env) {
+  if (env.halves == 0 || tile != 1 || tiles <= 0 || d.m % 64 != 0 || d.n % 64 != 0) return false;
+  return env.halves == 2 || tiles >= env.cus;
+}
+
 // The 32x32 K-split bf16 kernel over several workgroups per tile, for skinny groups with a long reduction (the kernel is a
 // latency-bound stream: 0.047 us per 16-k step of a workgroup). Measured (profiles/r05_bf16_skinny_small_vs_lw.txt): it pays only
 // while every workgroup still has a CU to itself - 128 x 1024 x 4096 as 64x64x64 tile invokes 12.0 -> 9.8 us at S = 2 (10.3 at 4,
@@ -609,7 +624,9 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
       l.tail_tiles = tail_tiles, l.tail_split = tail_S;
       return l;
     }
-    return launch(GL_F32_LW, tile, S > 1 ? split_names[tile] : "", S);
+    GemmLaunch l = launch(GL_F32_LW, tile, S > 1 ? split_names[tile] : "", S);
+    l.halves = S == 1 && choose_f32_halves(tile, d, tiles, env);
+    return l;
   }
   // (the half-width tiles store 16-byte pieces of C and of the bias row: else the generic kernel below)
   if (v == V_F32_LW16_32x16 && al.c16 && (!d.bias || al.d16)) {

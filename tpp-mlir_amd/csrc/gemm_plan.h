@@ -45,8 +45,9 @@ enum GemmVariant : int {
 // split model) and xsmm_hip_set_tail_split (0 = off, 1 = the model, 2 .. 16 = that many workgroups per tail tile) and
 // xsmm_hip_set_edge_tiles (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that f32 GemmVariant's tile, 2 = the f32 and the bf16 tile rule, 20 .. 23 =
 // that bf16 GemmVariant's tile) and xsmm_hip_set_edge_k (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that GemmVariant's tile) and
-// xsmm_hip_set_edge_k_bf16 (0 = off, 1 = the bf16 tile rule, 20 .. 23 = that bf16 GemmVariant's tile); brgemm_f32.hip gemm_plan_env fills it per call
-struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; };
+// xsmm_hip_set_edge_k_bf16 (0 = off, 1 = the bf16 tile rule, 20 .. 23 = that bf16 GemmVariant's tile) and xsmm_hip_set_f32_halves (0 = off, 1 =
+// the rule, 2 = wherever eligible); brgemm_f32.hip gemm_plan_env fills it per call
+struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
 struct GemmAlign { bool ab16, c16, c8, d8, d16; };
@@ -56,7 +57,7 @@ enum GemmLauncher : int {
   GL_NONE,            // nothing to compute (empty output or work list): hipSuccess
   GL_INVALID,         // no kernel takes this call: hipErrorInvalidValue
   GL_F32_FAST,        // brgemm_f32_fast (brgemm_f32.hip): tile = V_F32_64x64 .. V_F32_64x64K2
-  GL_F32_LW,          // launch_f32_lw(tile); split > 1: launch_f32_lw_split(tile, split) first; tail_tiles > 0: launch_f32_lw_tail first; edge: launch_f32_lw_edge(tile); edge_k: launch_f32_lw_kedge(tile)
+  GL_F32_LW,          // launch_f32_lw(tile); halves: launch_f32_lw_halves first; split > 1: launch_f32_lw_split(tile, split) first; tail_tiles > 0: launch_f32_lw_tail first; edge: launch_f32_lw_edge(tile); edge_k: launch_f32_lw_kedge(tile)
   GL_F32_LW16,        // launch_f32_lw16(tile); split > 1: launch_f32_lw_split(3, split) first
   GL_F32_LW_GROUPED,  // launch_f32_lw_grouped(tile, split)
   GL_F32_X6,          // launch_f32_x6(tile, vec)
@@ -92,6 +93,9 @@ struct GemmLaunch {
   // grid (m and n may be ragged too); refused by the launcher: the launch the call has with the mode off.
   // GL_BF16_LW (xsmm_hip_set_edge_k_bf16): k is a multiple of 16 but not of 64 - launch_bf16_lw_kedge(tile, b_kind), the same way
   bool edge_k = false;
+  // GL_F32_LW, tile 1, halves (xsmm_hip_set_f32_halves): every 64x64 + K2 tile as two 64x32 + K2 workgroups - launch_f32_lw_halves, the
+  // same bits; refused by the launcher: launch_f32_lw(1). Variant, kernel name and text are those of the launch with the mode off.
+  bool halves = false;
 };
 
 // fills d.variant / d.name / d.generic_forced / d.variant_forced; returns false if no kernel can run the descriptor

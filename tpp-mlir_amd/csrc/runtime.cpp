@@ -549,6 +549,10 @@ extern "C" int xsmm_hip_set_edge_k(int mode) { return tpp::edge_k_mode_ok(mode) 
 extern "C" void xsmm_hip_edge_k_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k_stats[i].load(std::memory_order_relaxed);
 }
+extern "C" int xsmm_hip_set_f32_halves(int mode) { return tpp::f32_halves_mode_ok(mode) ? tpp::g_f32_halves.exchange(mode) : -1; }
+extern "C" void xsmm_hip_f32_halves_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_f32_halves_stats[i].load(std::memory_order_relaxed);
+}
 extern "C" int xsmm_hip_set_edge_k_bf16(int mode) { return tpp::edge_k_bf16_mode_ok(mode) ? tpp::g_edge_k_bf16.exchange(mode) : -1; }
 extern "C" void xsmm_hip_edge_k_bf16_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k_bf16_stats[i].load(std::memory_order_relaxed);

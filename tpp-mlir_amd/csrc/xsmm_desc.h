@@ -177,6 +177,16 @@ inline std::atomic<int> g_edge_k_bf16{[] {
   return edge_k_bf16_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_edge_k_bf16_stats[4]; // bf16 ragged-k launches; chunks per batch element, overlap o, GemmVariant of the tile (with its B image) of the latest
+// HALVES (xsmm_hip_set_f32_halves / TPP_HIP_F32_HALVES; gemm_plan.cpp choose_f32_halves, brgemm_f32_lw.hip launch_f32_lw_halves): 0 = off, 1 =
+// the rule (default: at least one 64x64 tile per CU), 2 = every eligible whole-layer call on the 64x64 + K2 f32 tile runs as two 64x32 + K2
+// workgroups per tile (the same bits).
+inline bool f32_halves_mode_ok(int v) { return v >= 0 && v <= 2; }
+inline std::atomic<int> g_f32_halves{[] {
+  const char *e = getenv("TPP_HIP_F32_HALVES");
+  const int v = e ? atoi(e) : 1;
+  return f32_halves_mode_ok(v) ? v : 1;
+}()};
+inline std::atomic<int64_t> g_f32_halves_stats[4]; // launches carried out as halves; tile rows, tile columns (64x64 tiles) of the latest, 0
 // RAGGED-m CHAINS (xsmm_hip_set_chain_edge / TPP_HIP_CHAIN_EDGE; gemm_plan.cpp plan_chain_edge, rt_chain.h try_chain_launch,
 // brgemm_bf16_lw_chain_edge.h): 0 = off, 1 = a bf16 chain whose m the tile's rows do not divide runs as one launch on edge row tiles. A
 // switch of its own: the four ragged-layer switches above decide single calls only and leave every chain decision where it is.

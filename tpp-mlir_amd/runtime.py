@@ -119,6 +119,8 @@ _SIGNATURES = {
     "xsmm_hip_edge_k_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_edge_k_bf16": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_edge_k_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_f32_halves": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_f32_halves_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
@@ -388,6 +390,17 @@ class XsmmRuntime:
         image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_edge_k_bf16_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_f32_halves(self, mode):
+        """f32 whole-layer calls on the 64x64 + K2 tile as two 64x32 + K2 workgroups per tile (the same bits): 0 off, 1 the rule
+        (default: at least one tile per compute unit), 2 wherever eligible; returns the previous mode, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_f32_halves(mode)
+
+    def f32_halves_stats(self):
+        """(launches carried out as halves; rows, columns of 64x64 tiles of the most recent one; 0)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_f32_halves_stats(out)
         return tuple(int(v) for v in out)
 
     def set_chain_edge(self, mode):
