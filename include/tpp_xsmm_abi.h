@@ -419,7 +419,7 @@ TPP_XSMM_EXPORT void xsmm_hip_edge_k_stats(int64_t out[4]);
  * of 8 below 2^21; VNNI-4: of 2 below 2^20), A, B, C 16-byte and the bias row 8-byte aligned, m >= BM and n >= BN for the tile - and, if
  * that tile does not divide m and n, a bf16 edge-tile mode (xsmm_hip_set_edge_tiles 2, 20 .. 23) is on as well: the kernel then also
  * shifts back its last tile row and column. Everything else runs as with the switch off - every tile-queue group, quad, chain and
- * folded call too; k % 16 != 0 (1000, 200, 72) and k < 64 stay where they are.
+ * folded call too; k % 16 != 0 (1000, 200, 72) and k < 64 stay where they are (k % 16 == 8: xsmm_hip_set_edge_k8_bf16 below).
  * mode 0 = off (default); 1 = the tile rule: the cheapest tile by the loader-wave cost model on ceil-divided tile counts among the
  * tiles that fit and - with the bf16 edge tiles off - divide m and n (a forcing edge-tile mode forces the tile); 20 .. 23 = the tile
  * 32x64 + K2 / 64x64 / 64x128 / 128x128 wherever it is such a candidate (a test / measurement switch).
@@ -432,6 +432,34 @@ TPP_XSMM_EXPORT void xsmm_hip_edge_k_stats(int64_t out[4]);
  * do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_edge_k_bf16(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_edge_k_bf16_stats(int64_t out[4]);
+/* Ragged k in half steps, bf16 (opt-in; also TPP_HIP_EDGE_K8_BF16, read as a number; a switch of its own: it and xsmm_hip_set_edge_k_bf16
+ * partition the lengths - k % 16 == 0 is that switch's only, k % 16 == 8 this one's only - and neither looks at the other's mode). A
+ * whole-layer bf16 call with k >= 64, k a multiple of 8 but not of 16 - a 1000-wide layer, k = 200, 72 - runs on a bf16 loader-wave tile
+ * (32x64 + K2, 64x64, 64x128 or 128x128) as ONE launch, read as ceil(k / 64) chunks per batch element with the LAST chunk shifted back to
+ * start at k - 64, exactly as under xsmm_hip_set_edge_k_bf16. The o = 64 - k % 64 k-values at its head that the chunk before it has
+ * multiplied are now 8, 24, 40 or 56: o / 16 whole 16-k MFMA steps, which are skipped, plus the LOWER half of one more step. In that one
+ * step the MFMA's operands are zero in the lanes that hold the lower eight k-values, on BOTH sides, so the half adds +0.0 products only:
+ * the result has the bits of a skip, and an Inf or NaN in the re-read region counts once, as data. No load leaves [0, k) of a row of A
+ * or k-rows [0, k) of a B element, nothing outside the m x n window of C is written. No scratch block, no counters: legal on a captured
+ * stream.
+ * A call is taken when all of this holds: bf16, no VNNI C, no transposed operand, neither a kernel variant nor the generic kernel
+ * forced, the descriptor's kernel is the generic or the 32x32 K-split one, k >= 64, k % 8 == 0, k % 16 != 0, batch count >= 1, n a
+ * multiple of 8, lda / ldc / strides multiples of 8 and lda, ldc < 2^22, ldb as its image asks (VNNI-2: a multiple of 4 below 2^21; flat:
+ * of 8 below 2^21; VNNI-4: of 2 below 2^20), A, B, C 16-byte and the bias row 8-byte aligned, m >= BM and n >= BN for the tile - and, if
+ * that tile does not divide m and n, a bf16 edge-tile mode (xsmm_hip_set_edge_tiles 2, 20 .. 23) is on as well. Everything else runs as
+ * with the switch off - every tile-queue group, quad, chain and folded call too; k % 8 != 0 and k < 64 stay where they are.
+ * mode 0 = off (default); 1 = the tile rule of xsmm_hip_set_edge_k_bf16 (a forcing edge-tile mode forces the tile), with its gate: a call
+ * on the 32x32 K-split kernel whose 32x32 tiles fit one round of the compute units and whose batch count x k is below 1024 stays;
+ * 20 .. 23 = the tile 32x64 + K2 / 64x64 / 64x128 / 128x128 wherever it is a candidate (a test / measurement switch).
+ * Read per invoke; returns the previous mode, -1 (and changes nothing) for any other value. The choice depends on the descriptor, the
+ * batch count, the pointers' alignment and the CU count only: made in strict mode too. xsmm_hip_last_refined_kernel reads
+ * "brgemm_bf16_lw<64x64>, ragged k, half step", or "..., edge tiles, ragged k, half step" when m or n is ragged as well
+ * (brgemm_bf16_lw_flatb / _vnni4 for a flat / VNNI-4 B).
+ * _stats: out[0] half-step launches since process start; of the most recent one: [1] chunks per batch element, [2] o, [3] the variant
+ * number of its tile with its B image (20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4). The counters of xsmm_hip_edge_k_bf16_stats,
+ * xsmm_hip_edge_k_stats and xsmm_hip_edge_tiles_stats do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_edge_k8_bf16(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_edge_k8_bf16_stats(int64_t out[4]);
 /* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
  * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
  * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two

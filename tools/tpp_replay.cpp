@@ -68,7 +68,7 @@ int main(int argc, char **argv) {
 static int run_case(int argc, char **argv) {
   int64_t batch = 256, tile = 32, tile_n = 0, tile_k = 0, n_iter = 100;
   bool kernel_args = false; // mlir-gen --kernel=args: the output is an argument, the matmul accumulates into it (no BETA_0)
-  int vnni = 2, split = -1, tail_split = 0, edge_tiles = 0, edge_k = 0, edge_k_bf16 = 0, variant = -1, repeats = 1, f32p = 0;
+  int vnni = 2, split = -1, tail_split = 0, edge_tiles = 0, edge_k = 0, edge_k_bf16 = 0, edge_k8_bf16 = 0, variant = -1, repeats = 1, f32p = 0;
   int64_t block_pad = 0; // --block-pad P (experiments): P elements between consecutive packed blocks of A and of W (the block strides stop being powers of two)
   std::vector<int64_t> layers = {1024, 1024, 1024, 1024};
   bool bias = false, relu = false, whole = false, chain = false, print = false, c1 = false, rnd = false, bf16 = false, host_buffers = false;
@@ -107,6 +107,7 @@ static int run_case(int argc, char **argv) {
     else if (a == "--edge-tiles") edge_tiles = atoi(next()); // xsmm_hip_set_edge_tiles for this case (0: off, 1: the f32 tile rule, 6 / 7 / 9 / 10: that f32 variant's tile, 2: the f32 and bf16 rules, 20 .. 23: that bf16 tile)
     else if (a == "--edge-k") edge_k = atoi(next()); // xsmm_hip_set_edge_k for this case (0: off, 1: the tile rule, 6 / 7 / 9 / 10: that variant's tile)
     else if (a == "--edge-k-bf16") edge_k_bf16 = atoi(next()); // xsmm_hip_set_edge_k_bf16 for this case (0: off, 1: the tile rule, 20 .. 23: that bf16 tile)
+    else if (a == "--edge-k8-bf16") edge_k8_bf16 = atoi(next()); // xsmm_hip_set_edge_k8_bf16 for this case (0: off, 1: the tile rule, 20 .. 23: that bf16 tile)
     else if (a == "--variant") variant = atoi(next()); // xsmm_hip_force_variant at dispatch (-1: the runtime's choice)
     else if (a == "--f32-precision") { // xsmm_hip_set_f32_precision for this case's dispatches: exact (default) or bf16x6
       const std::string v = next();
@@ -219,11 +220,12 @@ static int run_case(int argc, char **argv) {
     if (xsmm_hip_set_edge_tiles(edge_tiles) < 0) { fprintf(stderr, "tpp_replay: --edge-tiles takes 0, 1, 2, 6, 7, 9, 10 or 20 .. 23, got %d\n", edge_tiles); return 2; }
     if (xsmm_hip_set_edge_k(edge_k) < 0) { fprintf(stderr, "tpp_replay: --edge-k takes 0, 1, 6, 7, 9 or 10, got %d\n", edge_k); return 2; }
     if (xsmm_hip_set_edge_k_bf16(edge_k_bf16) < 0) { fprintf(stderr, "tpp_replay: --edge-k-bf16 takes 0, 1 or 20 .. 23, got %d\n", edge_k_bf16); return 2; }
+    if (xsmm_hip_set_edge_k8_bf16(edge_k8_bf16) < 0) { fprintf(stderr, "tpp_replay: --edge-k8-bf16 takes 0, 1 or 20 .. 23, got %d\n", edge_k8_bf16); return 2; }
     xsmm_hip_force_variant(variant);
     xsmm_hip_set_async(1);
     xsmm_hip_set_tile_queue(queue);
-  } else if ((bf16 && vnni != 2) || split != -1 || tail_split != 0 || edge_tiles != 0 || edge_k != 0 || edge_k_bf16 != 0 || variant != -1 || chain || f32p) {
-    fprintf(stderr, "tpp_replay: --host-buffers takes its settings from the environment only (no --vnni 4 / --split / --tail-split / --edge-tiles / --edge-k / --edge-k-bf16 / --variant / --chain / --f32-precision)\n");
+  } else if ((bf16 && vnni != 2) || split != -1 || tail_split != 0 || edge_tiles != 0 || edge_k != 0 || edge_k_bf16 != 0 || edge_k8_bf16 != 0 || variant != -1 || chain || f32p) {
+    fprintf(stderr, "tpp_replay: --host-buffers takes its settings from the environment only (no --vnni 4 / --split / --tail-split / --edge-tiles / --edge-k / --edge-k-bf16 / --edge-k8-bf16 / --variant / --chain / --f32-precision)\n");
     return 2;
   }
   std::vector<int64_t> handle(L);
@@ -362,6 +364,7 @@ static int run_case(int argc, char **argv) {
   xsmm_hip_set_edge_tiles(0);
   xsmm_hip_set_edge_k(0);
   xsmm_hip_set_edge_k_bf16(0);
+  xsmm_hip_set_edge_k8_bf16(0);
   for (void *p : act) CHECK(hipFree(p));
   for (void *p : W) CHECK(hipFree(p));
   for (void *p : B) CHECK(hipFree(p));

@@ -33,4 +33,21 @@ constexpr bool bkedge_step_runs(int s, int skip) { return s >= skip; }
 // into the last chunk; behind the last chunk comes the batch wrap: the element's stride less bkedge_chunk_start(k, last)
 constexpr int bkedge_step(int k, int c) { return bkedge_chunk_start(k, c + 1) - bkedge_chunk_start(k, c); }
 
+// HALF STEPS (brgemm_bf16_lw.hip GRP = 6, opt-in: xsmm_hip_set_edge_k8_bf16; tests/test_edge_k8_bf16_schedule.py): k >= 64, k % 8 == 0,
+// k % 16 != 0 (1000, 200, 72). Chunk count, chunk start, overlap and the loader's steps are the functions above (a shifted start k - 64 is
+// still 16 bytes into an A row and a whole number of pair-rows / VNNI-4 group rows / flat rows of B). The overlap o is now an ODD multiple
+// of 8 (8, 24, 40, 56): o / 16 whole k-steps of the last chunk plus the LOWER half of one more are multiplied already. In every operand
+// fragment lanes 0 .. 31 hold k-values 0 .. 7 of a k-step and lanes 32 .. 63 hold 8 .. 15, so in that one step the MFMA's operands are
+// zero in lanes 0 .. 31, on BOTH sides: the half contributes +0.0 products, and an Inf or NaN in it counts once, as data.
+constexpr int BKEDGE8_KH = 8; // k per half step
+constexpr bool bkedge8_k_ok(long long k) { return k >= BKEDGE_BK && k % BKEDGE8_KH == 0 && k % BKEDGE_KS != 0; }
+// half steps at the head of chunk c that are not multiplied (odd on a last chunk: 1, 3, 5 or 7)
+constexpr int bkedge8_skip_halves(int k, int c) { return c + 1 < bkedge_chunks(k) ? 0 : bkedge_overlap(k) / BKEDGE8_KH; }
+// what k-step s (0 .. 3) of a chunk with `skip_halves` skipped half steps does: BKEDGE8_NONE not run, BKEDGE8_UPPER its upper eight
+// k-values only (lanes 32 .. 63), BKEDGE8_WHOLE all sixteen
+constexpr int BKEDGE8_NONE = 0, BKEDGE8_UPPER = 1, BKEDGE8_WHOLE = 2;
+constexpr int bkedge8_step_part(int s, int skip_halves) {
+  return 2 * s + 2 <= skip_halves ? BKEDGE8_NONE : 2 * s + 1 == skip_halves ? BKEDGE8_UPPER : BKEDGE8_WHOLE;
+}
+
 } // namespace tpp

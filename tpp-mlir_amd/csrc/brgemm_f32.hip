@@ -730,7 +730,8 @@ bool strict_kernels() { return g_strict_kernels.load(std::memory_order_relaxed) 
 static GemmPlanEnv gemm_plan_env() {
   return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed), g_tail_split.load(std::memory_order_relaxed),
                      g_edge_tiles.load(std::memory_order_relaxed), g_edge_k.load(std::memory_order_relaxed),
-                     g_edge_k_bf16.load(std::memory_order_relaxed), g_f32_halves.load(std::memory_order_relaxed)};
+                     g_edge_k_bf16.load(std::memory_order_relaxed), g_f32_halves.load(std::memory_order_relaxed),
+                     g_edge_k8_bf16.load(std::memory_order_relaxed)};
 }
 bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, gemm_plan_env()); }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, gemm_plan_env()); }
@@ -796,6 +797,7 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
   case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split);
   case GL_BF16_GROUPED64: return launch_bf16_grouped64(a, wi, n_items, s);
   case GL_BF16_LW:
+    if (p.edge_k8) return launch_bf16_lw_kedge8(p.tile, p.b_kind, one_layer(a, br, a.m, a.n), s);
     if (p.edge_k) return launch_bf16_lw_kedge(p.tile, p.b_kind, one_layer(a, br, a.m, a.n), s);
     if (p.edge) return launch_bf16_lw_edge(p.tile, p.b_kind, one_layer(a, br, a.m, a.n), s);
     return (p.b_kind == 4 ? launch_bf16_lw_vnni4 : p.b_kind == 2 ? launch_bf16_lw_flatb : launch_bf16_lw)(p.tile, one_layer(a, br, a.m, a.n), s);
@@ -825,6 +827,21 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   GemmLaunch p = plan_gemm_call(d, br, al, env);
   if (p.launcher == GL_NONE) return hipSuccess;
   const GemmArgs a = gemm_args(d, A, B, C, D, (int)(br < 0 ? 0 : br));
+  if (p.edge_k8 && p.launcher == GL_BF16_LW) { // a bf16 half-step ragged-k launch (xsmm_desc.h g_edge_k8_bf16; brgemm_bf16_lw_kedge.h bkedge8_*)
+    const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    if (e != hipErrorInvalidValue) {
+      if (e == hipSuccess) { // the tile with its B image: 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4
+        g_edge_k8_bf16_stats[1].store(bkedge_chunks(a.k), std::memory_order_relaxed);
+        g_edge_k8_bf16_stats[2].store(bkedge_overlap(a.k), std::memory_order_relaxed);
+        g_edge_k8_bf16_stats[3].store((p.b_kind == 4 ? V_BF16_LW4_32x64 : p.b_kind == 2 ? V_BF16_LWF_32x64 : V_BF16_LW_32x64) + p.tile, std::memory_order_relaxed);
+        g_edge_k8_bf16_stats[0].fetch_add(1, std::memory_order_relaxed);
+      }
+      return g_last_refined.store(p.text, std::memory_order_relaxed), e;
+    }
+    (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
+    env.edge_k8_bf16 = 0;
+    p = plan_gemm_call(d, br, al, env);
+  }
   if (p.edge_k && p.launcher == GL_BF16_LW) { // a bf16 ragged-k launch (xsmm_desc.h g_edge_k_bf16; brgemm_bf16_lw_kedge.h)
     const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
     if (e != hipErrorInvalidValue) {

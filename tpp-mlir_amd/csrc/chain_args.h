@@ -54,6 +54,8 @@ hipError_t launch_bf16_lw_edge(int tile, int b_kind, const ChainArgs &a, hipStre
 // workgroups; hipErrorInvalidValue and nothing launched when m < BM, n % BN, a k % 64 or a batch count < 1
 hipError_t launch_bf16_chain_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
 hipError_t launch_bf16_lw_kedge(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k (brgemm_bf16_lw_kedge.h); hipErrorInvalidValue: not launched
+hipError_t launch_bf16_lw_kedge8(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k in half steps, k % 16 == 8 (bkedge8_*); refuses the same way
+hipError_t launch_bf16_lw_kedge8(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k in half steps, k % 16 == 8 (bkedge8_*); refuses the same way
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2 (VNNI-2 only); b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);

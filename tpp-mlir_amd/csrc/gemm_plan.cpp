@@ -310,9 +310,10 @@ static int pick_bf16_lw_image_tile(const GemmDesc &d, int64_t cus, int first_var
 // multiple of 32 or n not of 64: planned on the generic kernel or the 32x32 K-split kernel - on the loader-wave tiles all the same
 // (brgemm_bf16_lw.hip GRP = 3, launch_bf16_lw_edge). What the three B images ask of leading dimensions, strides and lane offsets is
 // bf16_fast_eligible / bf16_flat_eligible / bf16_vnni4_eligible without their m / n terms; returns the image (0 VNNI-2, 2 flat, 4 VNNI-4), -1 = none.
-// ragged_k (xsmm_hip_set_edge_k_bf16): the k % 64 term replaced by brgemm_bf16_lw_kedge.h's bkedge_k_ok.
-static int bf16_edge_b_kind(const GemmDesc &d, bool ragged_k = false) {
-  if (d.dtype != DT_BF16 || d.vnni_c || d.k <= 0 || (ragged_k ? !bkedge_k_ok(d.k) : d.k % BK != 0)) return -1;
+// ragged_k 1 (xsmm_hip_set_edge_k_bf16): the k % 64 term replaced by brgemm_bf16_lw_kedge.h's bkedge_k_ok; 2 (xsmm_hip_set_edge_k8_bf16): by
+// bkedge8_k_ok.
+static int bf16_edge_b_kind(const GemmDesc &d, int ragged_k = 0) {
+  if (d.dtype != DT_BF16 || d.vnni_c || d.k <= 0 || (ragged_k == 2 ? !bkedge8_k_ok(d.k) : ragged_k == 1 ? !bkedge_k_ok(d.k) : d.k % BK != 0)) return -1;
   if ((d.lda | d.ldc | d.stride_a | d.stride_b) & 7 || d.lda >= (1 << 22) || d.ldc >= (1 << 22)) return -1;
   if (d.vnni_b && d.vnni_factor == 2) return !(d.ldb & 3) && d.ldb < (1 << 21) ? 0 : -1;
   if (d.vnni_b && d.vnni_factor == 4) return !(d.ldb & 1) && d.ldb < (1 << 20) ? 4 : -1;
@@ -575,7 +576,7 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
     // planned on the 32x32 K-split kernel whose 32x32 tiles fit ONE round of the CUs, with a reduction below that kernel's crossover
     // against the loader-wave tiles (br * k < 1024, the long-reduction rule below), stays there. A forced tile is a forced tile.
     const bool gated = forced < 0 && d.variant == V_BF16_SMALL32 && (d.m / 32) * (d.n / 32) <= cus && (int64_t)br * d.k < 1024;
-    const int kind = gated ? -1 : bf16_edge_b_kind(d, true);
+    const int kind = gated ? -1 : bf16_edge_b_kind(d, 1);
     const int tile = kind >= 0 ? choose_bf16_kedge_tile(d, forced, edge_on, (int64_t)br * bkedge_chunks((int)d.k), cus) : -1;
     if (tile >= 0) {
 #define KE_NAMES(F, S) {"brgemm_bf16_lw" F "<32x64,k2>" S, "brgemm_bf16_lw" F "<64x64>" S, "brgemm_bf16_lw" F "<64x128>" S, "brgemm_bf16_lw" F "<128x128>" S}
@@ -586,6 +587,32 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
       const bool mn_ragged = d.m % BLW_BM[tile] != 0 || d.n % BLW_BN[tile] != 0;
       GemmLaunch l = launch(GL_BF16_LW, tile, kedge_names[mn_ragged][kind / 2][tile], 1, kind);
       l.edge_k = true;
+      return l;
+    }
+  }
+  // bf16 ragged k in HALF steps, if asked for (xsmm_hip_set_edge_k8_bf16, a switch of its own; brgemm_bf16_lw_kedge.h bkedge8_*): k >= 64 a
+  // multiple of 8 but not of 16 (1000, 200, 72). The block above with bkedge8_k_ok and env.edge_k8_bf16: the two switches partition the
+  // lengths (k % 16 == 0 / == 8) and neither looks at the other's mode. The launcher's own checks: launch_bf16_lw_kedge8.
+  if (env.edge_k8_bf16 != 0 && d.dtype == DT_BF16 && !d.vnni_c && !d.generic_forced && !d.variant_forced &&
+      (d.variant == V_GENERIC || d.variant == V_BF16_SMALL32) && bkedge8_k_ok(d.k) && d.n % 8 == 0 && br >= 1 && al.ab16 && al.c16 && bias_ok8) {
+    const bool force_e = env.edge_tiles >= V_BF16_LW_32x64 && env.edge_tiles <= V_BF16_LW_128x128;
+    const bool edge_on = env.edge_tiles == 2 || force_e;
+    const int forced = env.edge_k8_bf16 >= V_BF16_LW_32x64 && env.edge_k8_bf16 <= V_BF16_LW_128x128 ? env.edge_k8_bf16 - V_BF16_LW_32x64
+                       : force_e ? env.edge_tiles - V_BF16_LW_32x64 : -1;
+    // The gate of the block above, carried over unchanged; what was measured for these k: profiles/edge_k8_bf16_ab.txt.
+    const bool gated = forced < 0 && d.variant == V_BF16_SMALL32 && (d.m / 32) * (d.n / 32) <= cus && (int64_t)br * d.k < 1024;
+    const int kind = gated ? -1 : bf16_edge_b_kind(d, 2);
+    const int tile = kind >= 0 ? choose_bf16_kedge_tile(d, forced, edge_on, (int64_t)br * bkedge_chunks((int)d.k), cus) : -1;
+    if (tile >= 0) {
+#define KE_NAMES(F, S) {"brgemm_bf16_lw" F "<32x64,k2>" S, "brgemm_bf16_lw" F "<64x64>" S, "brgemm_bf16_lw" F "<64x128>" S, "brgemm_bf16_lw" F "<128x128>" S}
+      static const char *const kedge8_names[2][3][4] = {
+          {KE_NAMES("", ", ragged k, half step"), KE_NAMES("_flatb", ", ragged k, half step"), KE_NAMES("_vnni4", ", ragged k, half step")},
+          {KE_NAMES("", ", edge tiles, ragged k, half step"), KE_NAMES("_flatb", ", edge tiles, ragged k, half step"),
+           KE_NAMES("_vnni4", ", edge tiles, ragged k, half step")}};
+#undef KE_NAMES
+      const bool mn_ragged = d.m % BLW_BM[tile] != 0 || d.n % BLW_BN[tile] != 0;
+      GemmLaunch l = launch(GL_BF16_LW, tile, kedge8_names[mn_ragged][kind / 2][tile], 1, kind);
+      l.edge_k8 = true;
       return l;
     }
   }

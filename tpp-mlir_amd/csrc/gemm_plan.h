@@ -46,8 +46,9 @@ enum GemmVariant : int {
 // xsmm_hip_set_edge_tiles (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that f32 GemmVariant's tile, 2 = the f32 and the bf16 tile rule, 20 .. 23 =
 // that bf16 GemmVariant's tile) and xsmm_hip_set_edge_k (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that GemmVariant's tile) and
 // xsmm_hip_set_edge_k_bf16 (0 = off, 1 = the bf16 tile rule, 20 .. 23 = that bf16 GemmVariant's tile) and xsmm_hip_set_f32_halves (0 = off, 1 =
-// the rule, 2 = wherever eligible); brgemm_f32.hip gemm_plan_env fills it per call
-struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; };
+// the rule, 2 = wherever eligible) and xsmm_hip_set_edge_k8_bf16 (the values of edge_k_bf16, for k % 16 == 8); brgemm_f32.hip gemm_plan_env
+// fills it per call
+struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
 struct GemmAlign { bool ab16, c16, c8, d8, d16; };
@@ -93,6 +94,9 @@ struct GemmLaunch {
   // grid (m and n may be ragged too); refused by the launcher: the launch the call has with the mode off.
   // GL_BF16_LW (xsmm_hip_set_edge_k_bf16): k is a multiple of 16 but not of 64 - launch_bf16_lw_kedge(tile, b_kind), the same way
   bool edge_k = false;
+  // GL_BF16_LW, ragged k in half steps (xsmm_hip_set_edge_k8_bf16): k is a multiple of 8 but not of 16 - launch_bf16_lw_kedge8(tile,
+  // b_kind), refused the same way. Never set together with edge_k.
+  bool edge_k8 = false;
   // GL_F32_LW, tile 1, halves (xsmm_hip_set_f32_halves): every 64x64 + K2 tile as two 64x32 + K2 workgroups - launch_f32_lw_halves, the
   // same bits; refused by the launcher: launch_f32_lw(1). Variant, kernel name and text are those of the launch with the mode off.
   bool halves = false;

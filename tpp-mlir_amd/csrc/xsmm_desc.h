@@ -177,6 +177,14 @@ inline std::atomic<int> g_edge_k_bf16{[] {
   return edge_k_bf16_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_edge_k_bf16_stats[4]; // bf16 ragged-k launches; chunks per batch element, overlap o, GemmVariant of the tile (with its B image) of the latest
+// RAGGED k in HALF steps, bf16 (xsmm_hip_set_edge_k8_bf16 / TPP_HIP_EDGE_K8_BF16; brgemm_bf16_lw_kedge.h bkedge8_*): k % 16 == 8 (1000, 200,
+// 72). The values of g_edge_k_bf16, a switch of its own: the two partition the lengths and neither looks at the other's mode.
+inline std::atomic<int> g_edge_k8_bf16{[] {
+  const char *e = getenv("TPP_HIP_EDGE_K8_BF16");
+  const int v = e ? atoi(e) : 0;
+  return edge_k_bf16_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_edge_k8_bf16_stats[4]; // half-step launches; chunks per batch element, overlap o, GemmVariant of the tile (with its B image) of the latest
 // HALVES (xsmm_hip_set_f32_halves / TPP_HIP_F32_HALVES; gemm_plan.cpp choose_f32_halves, brgemm_f32_lw.hip launch_f32_lw_halves): 0 = off, 1 =
 // the rule (default: at least one 64x64 tile per CU), 2 = every eligible whole-layer call on the 64x64 + K2 f32 tile runs as two 64x32 + K2
 // workgroups per tile (the same bits).

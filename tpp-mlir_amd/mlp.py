@@ -57,14 +57,19 @@ def row_partition(batch, world, rank, granule=128):
 
 
 def layer_dispatch_args(spec, rows, k, n):
-    """argument tuple of xsmm_fused_brgemm_dispatch for one whole layer on `rows` rows"""
-    assert k % K_CHUNK == 0
+    """argument tuple of xsmm_fused_brgemm_dispatch for one whole layer on `rows` rows, and its batch count. A layer whose k is a
+    multiple of 64 is k / 64 batch elements of 64; any other k (1000, 784, 200) is ONE batch element of length k - the runtime's
+    ragged-k switches (set_edge_k, set_edge_k_bf16, set_edge_k8_bf16) put such a call on the loader-wave tiles, without them it runs on
+    the generic or the 32x32 K-split kernel. A bf16 layer's weights are VNNI-2 pairs of k: an odd k raises ValueError."""
+    if spec.vnni and k % 2:
+        raise ValueError("a bf16 layer needs an even k (VNNI-2 weights), got %d" % k)
+    kk, br = (K_CHUNK, k // K_CHUNK) if k % K_CHUNK == 0 else (k, 1)
     gemm_flags = GemmFlags.BETA_0 | (GemmFlags.VNNI_B if spec.vnni else 0)
-    return dict(dtype=spec.dtype, m=rows, n=n, k=K_CHUNK, lda=k, ldb=n, ldc=n, stride_a=K_CHUNK,
-                stride_b=K_CHUNK * n, gemm_flags=gemm_flags, unary_flags=0,
+    return dict(dtype=spec.dtype, m=rows, n=n, k=kk, lda=k, ldb=n, ldc=n, stride_a=kk,
+                stride_b=kk * n, gemm_flags=gemm_flags, unary_flags=0,
                 unary_kind=UnaryKind.RELU if spec.relu else UnaryKind.NONE,
                 binary_flags=BinaryFlags.BCAST_COL_IN_0 if spec.bias else BinaryFlags.NONE,
-                binary_kind=BinaryKind.ADD if spec.bias else BinaryKind.NONE), k // K_CHUNK
+                binary_kind=BinaryKind.ADD if spec.bias else BinaryKind.NONE), br
 
 
 class ShardedMlp:

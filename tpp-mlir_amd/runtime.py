@@ -119,6 +119,8 @@ _SIGNATURES = {
     "xsmm_hip_edge_k_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_edge_k_bf16": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_edge_k_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_edge_k8_bf16": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_edge_k8_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_f32_halves": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_f32_halves_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
@@ -390,6 +392,19 @@ class XsmmRuntime:
         image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_edge_k_bf16_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_edge_k8_bf16(self, mode):
+        """bf16 whole-layer calls whose k is a multiple of 8 but not of 16 (k >= 64: 1000, 200, 72), on the bf16 loader-wave tiles in half
+        steps: 0 off (default), 1 the tile rule, 20 .. 23 the tile 32x64 + K2 / 64x64 / 64x128 / 128x128; returns the previous mode, -1 for
+        a value it refuses"""
+        return self.lib.xsmm_hip_set_edge_k8_bf16(mode)
+
+    def edge_k8_bf16_stats(self):
+        """(half-step ragged-k launches; chunks per batch element, re-read k-values of the last chunk, variant number of the tile with
+        its B image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_edge_k8_bf16_stats(out)
         return tuple(int(v) for v in out)
 
     def set_f32_halves(self, mode):
