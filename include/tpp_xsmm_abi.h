@@ -493,6 +493,30 @@ TPP_XSMM_EXPORT void xsmm_hip_f32_halves_stats(int64_t out[4]);
  * xsmm_hip_edge_tiles_stats reports it. The edge-tile counters do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_chain_edge(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_chain_edge_stats(int64_t out[4]);
+/* Multi-round layer chains, opt-in (environment: TPP_HIP_CHAIN_ROUNDS; default 0 = off): a switch of its own - every other switch keeps its
+ * meaning. A chain launch needs every workgroup resident, so without this switch a bf16 chain runs as one launch only while its output
+ * tiles are no more than the stream's compute units (three 1024-wide layers: up to 4096 rows on 256 CUs) and call by call beyond. mode 1: a
+ * bf16 chain of 2 .. 8 calls that meets everything else the chain launch asks (one kind of B operand, beta 0, equal m and n, device
+ * pointers, asynchronous mode, no stream capture, no output overlapping an operand, batch elements inside the predecessor's rows) but has
+ * MORE tiles than compute units runs as ONE launch on G x n / BN resident workgroups: G row groups, workgroup (g, tn) computing the row
+ * blocks g, g + G, g + 2G, .. of every layer, layer by layer, and waiting at every seam for the counter of the row block it is about to
+ * read - a block its own row of workgroups stored R - 1 blocks earlier, R = ceil(tiles_m / G) rounds. The tile: the loader-wave tile all
+ * calls were planned on; if they share none, call by call in strict mode, else the largest tile whose rows divide m and whose columns
+ * divide n. The groups: Gmax = CUs / (n / BN) rounded down, R = ceil(tiles_m / Gmax), G = ceil(tiles_m / R) (8192 x 1024 on 256 CUs:
+ * 128x128 tiles, G = 32, R = 2; 4224 rows: G = 17, R = 2). Bit for bit the same calls made one by one on that tile, so strict mode takes
+ * the rule on the planned tile. Mode 1 takes at most TWO rounds: deeper chains measured slower than call by call (16384 rows +4.6 %, 32768
+ * rows +12.8 %, profiles/chain_rounds_ab.txt) and stay call by call. mode 1000 + G: force G row groups (1 <= G < tiles_m, G * (n / BN) <= CUs) - for tests and measurements; it
+ * is asked in front of the one-round rules and so also applies to a chain that would fit; a G that does not fit leaves every decision as
+ * with the switch off. Call by call (or as with the switch off) as before: f32 chains, a ragged m, n or k (xsmm_hip_set_chain_edge and
+ * this switch never combine: where a one-round ragged launch applies it is taken, and a ragged shape is never run in several rounds),
+ * a row of tiles wider than the compute units, a chain that fits in one round under mode 1 (today's chain kernel). The launch still
+ * needs the device to itself: a starved launch degrades exactly as every chain launch, through probation, the journal and the re-run
+ * (xsmm_hip_chain_status counts). Returns the previous value, -1 (nothing changed) for any other value.
+ * _stats: out[0] multi-round chain launches since process start; of the most recent one: [1] row groups G, [2] rounds R =
+ * ceil(tiles_m / G), [3] the variant number of its tile with its B image (20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4). The chain-edge
+ * and edge-tile counters do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_rounds(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_rounds_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

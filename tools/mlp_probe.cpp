@@ -3,6 +3,8 @@
 //   (a) three whole-layer xsmm_fused_brgemm_invoke launches (what round 2 measured), and
 //   (b) ONE xsmm_hip_fused_brgemm_chain_invoke (the persistent chain kernel when the runtime can run it as one launch),
 // stream time per step by HIP events over `iters` back-to-back steps after a spin-up, plus each single layer alone.
+// With TPP_HIP_CHAIN_ROUNDS set (xsmm_hip_set_chain_rounds) the line also says on how many row groups G and in how many rounds R the
+// chain's most recent multi-round launch ran, and on which tile.
 // Prints ONE JSON line per row count. rocprofv3 target for the chain kernel's duration (--only chain|layers).
 //   mlp_probe [--rows 512,1024,2048,4096] [--iters N] [--layers 3] [--width 1024] [--variant V] [--only chain|layers|all]
 #include "../include/tpp_xsmm_abi.h"
@@ -120,17 +122,22 @@ int main(int argc, char **argv) {
       return best;
     };
     double t_one = 0, t_layers = 0, t_chain = 0;
+    int64_t rs0[4], rs1[4];
+    xsmm_hip_chain_rounds_stats(rs0);
     if (only != "chain") {
       t_one = time_it(step_one);
       t_layers = time_it(step_layers);
     }
     if (only != "layers") t_chain = time_it(step_chain);
     xsmm_hip_synchronize();
+    xsmm_hip_chain_rounds_stats(rs1);
     const double flops = 2.0 * rows * N * K * layers;
     printf("{\"rows\": %d, \"layers\": %d, \"width\": %d, \"pad\": %d, \"kernel\": \"%s\", \"one_layer_us\": %.3f, \"per_layer_launches_us\": %.3f, "
-           "\"chain_us\": %.3f, \"chain_one_launch\": %s, \"chain_tflops\": %.1f, \"layers_tflops\": %.1f}\n",
+           "\"chain_us\": %.3f, \"chain_one_launch\": %s, \"chain_tflops\": %.1f, \"layers_tflops\": %.1f, "
+           "\"chain_rounds\": {\"launches\": %lld, \"groups\": %lld, \"rounds\": %lld, \"variant\": %lld}}\n",
            rows, layers, width, pad, xsmm_hip_kernel_name(h), t_one, t_layers, t_chain, fused ? "true" : "false",
-           t_chain > 0 ? flops / t_chain * 1e-6 : 0.0, t_layers > 0 ? flops / t_layers * 1e-6 : 0.0);
+           t_chain > 0 ? flops / t_chain * 1e-6 : 0.0, t_layers > 0 ? flops / t_layers * 1e-6 : 0.0, (long long)(rs1[0] - rs0[0]), (long long)rs1[1],
+           (long long)rs1[2], (long long)rs1[3]);
     fflush(stdout);
     CHECK(hipFree(x));
     for (int l = 0; l < layers; ++l) CHECK(hipFree(act[l]));

@@ -33,11 +33,21 @@
 //   is reset (no memset launch in front of the kernel). Every spin is bounded by s_memrealtime: on a timeout the
 //   workgroup sets *err and carries on (wrong numbers, never a hung GPU); the host checks *err at its sync points.
 //   Results are bit-identical to the same layers launched one by one (same tile, same k order, same rounding).
+//
+// SEVERAL ROUNDS (GRP = 7, xsmm_hip_set_chain_rounds; step maps in brgemm_bf16_lw_chain_rounds.h): a chain with MORE output tiles than
+// compute units on G x tiles_n resident workgroups. Workgroup (g, tn) owns the row blocks tm = g + r * G < tiles_m and walks them
+// layer-major - for l: for r: - one STEP (l, r) being the layer body above with tm and m0 = tm * BM taken from the step. Counters,
+// targets, the bounded wait and the error word are the chain's: cnt[l][tm] per row block, tiles_n arrivals per launch.
+//   Progress: step (l, r) of group g waits only for cnt[l-1][g + r * G], i.e. for step (l-1, r) of the workgroups (g, *). That step lies
+//   EARLIER in their own step order (layer-major), and every step a workgroup makes before it waits in turn only for still earlier
+//   steps of the same group. All G x tiles_n workgroups are resident, so by induction over the step order no wait is cyclic and each
+//   one ends. When a workgroup reaches block r of layer l + 1 its producers finished that block R - 1 steps ago: the poll falls through.
 #include "gemm_common.h"
 #include "xsmm_desc.h"
 #include "chain_args.h"
 #include "brgemm_bf16_lw_kedge.h"
 #include "brgemm_bf16_lw_chain_edge.h"
+#include "brgemm_bf16_lw_chain_rounds.h"
 #include <type_traits>
 
 namespace tpp {
@@ -96,6 +106,10 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   // GRP = 5 (a CHAIN on edge ROW tiles, brgemm_bf16_lw_chain_edge.h): the argument block's operands as GRP = 0, m0 of the last row block
   // shifted back by the kernel; the seam wait of a shifted block is for TWO row blocks' producers (below)
   static_assert(GRP != 5 || (SUP == 1 && MULTI), "a ragged chain: a chain, one chunk per barrier");
+  // GRP = 7 (a chain in SEVERAL ROUNDS, brgemm_bf16_lw_chain_rounds.h): `tm` arrives as the workgroup's row GROUP g; the loop below runs
+  // over STEPS (layer, round) and takes tm and m0 from the step. The A state is rebuilt per step (the row base moves); the B state per
+  // step too (the same layer's panels again, or the next layer's), ahead of the step wherever the run-ahead rule holds.
+  static_assert(GRP != 7 || (SUP == 1 && MULTI), "a multi-round chain: a chain, one chunk per barrier");
   constexpr int A_SLOT = BM * 128, SLOT = (BM + BN) * 128;
   // SUP = chunks per barrier (the unit everything below counts in: a "chunk" of this function is SUP 64-k chunks, a "slot" SUP
   // consecutive ring slots). SUP = 2 halves the barrier count and the loader's per-iteration scalar work for the small tiles, whose
@@ -213,10 +227,21 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   } while (0)
   const bool poller = MULTI && IS_A && part == 0;
   int slot = 0, s0 = 0; // next ring slot to fill; slot of the current layer's chunk 0 (the layers follow each other through the ring)
-  for (int lc = 0; lc < L; ++lc) {
+  constexpr int PRIMED = -2; // GRP = 7, a value of state_layer: the run-ahead of the step before loaded THIS step's state
+  // (ONE loop: GRP = 7 goes from step to step - tm from the group's first row block to its last, then the next layer -, every other
+  // launch from layer to layer)
+  for (int lc = 0; lc < L; GRP == 7 ? chain_rounds_next(tm, lc, p.groups, p.tiles_m) : (void)++lc) {
+    if constexpr (GRP == 7) m0 = tm * BM;
     const int T = (ITEMS ? it_br : p.L[lc].br) * (KEDGE ? bkedge_chunks(p.L[lc].k) : p.L[lc].k / BLW_BK) / SUP; // (a multiple of SUP: the launcher picks SUP = 1 otherwise)
     int pre = NSLOT - 2; // chunks of this layer already requested by the run-ahead of the previous layer's tail
-    if (state_layer != lc) {
+    if constexpr (GRP == 7) {
+      if (state_layer != PRIMED) {
+        BLW_LOAD_STATE(lc);
+        pre = 0;
+        slot = s0;
+      }
+      state_layer = -1;
+    } else if (state_layer != lc) {
       BLW_LOAD_STATE(lc);
       pre = 0;
       slot = s0;
@@ -281,6 +306,25 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       BLW_ISSUE(slot);
     }
     // the last NSLOT - 2 barriers of the layer: nothing of THIS layer is left to request
+    if constexpr (GRP == 7) {
+      // the next step: this layer's next row block (the same weight panels again), or the next layer's first
+      const bool more_rounds = chain_rounds_more(tm, p.groups, p.tiles_m);
+      if (ahead && (lc + 1 < L || more_rounds)) {
+        BLW_LOAD_STATE(more_rounds ? lc : lc + 1); // (the slot rotation carries over into the next step)
+        state_layer = PRIMED;
+        for (; t + 1 < T; ++t) {
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSLOT - 3) * PPL) : "memory");
+          __builtin_amdgcn_s_barrier();
+          BLW_ISSUE(slot);
+        }
+      } else {
+        for (; t + 1 < T; ++t) {
+          blw_wait_younger<PPL>(T - 2 - t);
+          __builtin_amdgcn_s_barrier();
+        }
+      }
+      if (lc + 1 == L && !more_rounds) return;
+    } else {
     if (MULTI && ahead && lc + 1 < L) {
       BLW_LOAD_STATE(lc + 1); // (the slot rotation carries over into the next layer)
       for (; t + 1 < T; ++t) {
@@ -295,6 +339,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       }
     }
     if (lc + 1 == L) return;
+    }
     if constexpr (WK > 1) __builtin_amdgcn_s_barrier(); // R1 (K groups combine)
     __builtin_amdgcn_s_barrier();                        // S1 (tile stored and drained)
     s0 = (s0 + T) % NSLOT;
@@ -305,8 +350,8 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
 
 template <int WM, int WN, int WK, int TM, int TN, int NSLOT, int NLA, int NLB, int SUP, bool MULTI, int FLATB = 0, int GRP = 0>
 __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_lw(ChainArgs p_by_value) {
-  static_assert(!GRP || !MULTI || GRP == 5, "a grouped launch is a set of single layers");
-  static_assert(GRP >= 0 && GRP <= 6, "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps");
+  static_assert(!GRP || !MULTI || GRP == 5 || GRP == 7, "a grouped launch is a set of single layers");
+  static_assert(GRP >= 0 && GRP <= 7, "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds");
   // operands and batch count from an item (GRP = 1, 2). GRP = 3 (EDGE TILES, a whole layer whose m or n the tile does not divide) has
   // no items: everything from the argument block, as GRP = 0
   constexpr bool ITEMS = GRP == 1 || GRP == 2;
@@ -322,7 +367,11 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   constexpr bool KEDGE = GRP == 4 || GRP == 6;
   constexpr bool EDGE = GRP == 3 || KEDGE || GRP == 5;
   static_assert(!KEDGE || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
+  // GRP = 7 (a chain in SEVERAL ROUNDS, xsmm_hip_set_chain_rounds): MULTI on p.groups x tiles_n workgroups, fewer than the output tiles -
+  // workgroup (g, tn) walks the row blocks g, g + groups, .. of every layer, layer-major (the file's header; brgemm_bf16_lw_chain_rounds.h).
+  // m and n in whole tiles: no edge predicate anywhere.
   static_assert(GRP != 5 || (SUP == 1 && MULTI), "a ragged chain: a chain, one chunk per barrier");
+  static_assert(GRP != 7 || (SUP == 1 && MULTI), "a multi-round chain: a chain, one chunk per barrier");
   static_assert(GRP != 2 || (WM == 2 && WN == 2 && WK == 1 && TM == 2 && TN == 2), "quads: every MFMA wave owns one item's 64x64 output");
   chain_kernarg_t *pp = (chain_kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr(); // = &p_by_value (the only explicit argument)
   chain_kernarg_t &p = *pp;
@@ -412,7 +461,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
     it_br = (int)w.br;
   } else if (p.xm > 0) {
     const int xn = 8 / p.xm, xcd = b & 7, j = b >> 3;
-    const int lm = p.tiles_m / p.xm, ln = p.tiles_n / xn; // tiles per XCD
+    const int lm = (GRP == 7 ? p.groups : p.tiles_m) / p.xm, ln = p.tiles_n / xn; // tiles per XCD (GRP = 7: row groups)
     tm = (xcd / xn) * lm + j / ln;
     tn = (xcd % xn) * ln + j % ln;
   } else {
@@ -427,7 +476,8 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // moved up / left to end at row m / column n. Loaders, LDS images and the K loop see m0 and n0 only and stay inside rows [0, m) and
   // columns [0, n); the tile stores the rows >= own_row and the 16-byte pieces at columns >= own_col of its block (TILE-relative: the
   // tiles have several wave columns) - the others are the neighbour's. n0 is a multiple of 8 (the planner asks for n % 8 == 0).
-  const int m0 = GRP == 5 ? chain_edge_row0(tm, p.tiles_m, p.m, BM) : (EDGE && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
+  // (GRP = 7: tm is the workgroup's row GROUP up to here; the step loops below and in blw_loader take tm and m0 from the step)
+  int m0 = GRP == 5 ? chain_edge_row0(tm, p.tiles_m, p.m, BM) : (EDGE && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
   const int n0 = ((GRP == 1 || (EDGE && GRP != 5)) && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
   [[maybe_unused]] const int skip_cols = tn * BN - n0;
   [[maybe_unused]] const int own_row = tm * BM - m0, own_col = tn * BN - n0;
@@ -624,7 +674,10 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   auto chunk = [&](auto par_c, auto hn_c, int slot, int t, int T) __attribute__((always_inline)) { chunk_ke(par_c, hn_c, slot, t, T, P0{}, 0); };
 
   int s0 = 0; // ring slot of the current layer's chunk 0
-  for (int l = 0; l < L; ++l) {
+  // (ONE loop: GRP = 7 goes from step to step - tm from the group's first row block to its last, then the next layer -, every other
+  // launch from layer to layer; blw_loader counts the same way)
+  for (int l = 0; l < L; GRP == 7 ? chain_rounds_next(tm, l, p.groups, p.tiles_m) : (void)++l) {
+    if constexpr (GRP == 7) m0 = tm * BM;
     const auto &Y = p.L[l];
     const int T = (ITEMS ? it_br : Y.br) * (KEDGE ? bkedge_chunks(Y.k) : Y.k / BLW_BK);
     const int ep = Y.ep;
@@ -886,7 +939,16 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
         }
       }
     }
-    if (l + 1 == L) break;
+    if (l + 1 == L && (GRP != 7 || !chain_rounds_more(tm, p.groups, p.tiles_m))) break;
+    if constexpr (GRP == 7) {
+      if (l + 1 == L) {
+        // a further row block of the LAST layer follows: nothing to publish and no store to drain - only the rendezvous behind every
+        // wave's epilogue (its staging tile in a retired A half has been read back) before the A loader requests the next step's panels
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier(); // S1
+        continue;
+      }
+    }
     if constexpr (MULTI) {
       // ---- seam: publish this tile to the row block's consumers ------------------------------------------------
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // EVERY storing wave drains its write-through stores
@@ -913,6 +975,16 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   long long tiles = (long long)args.tiles_m * args.tiles_n;
   if (EDGE && (a.m < BM || a.n < BN)) return hipErrorInvalidValue;
   if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+  // GRP = 7 (several rounds): a.groups row groups are resident, each a row of tiles_n workgroups; the grid and the XCD search below
+  // count row groups where the other launches count row blocks
+  int grid_m = args.tiles_m;
+  if constexpr (GRP == 7) {
+    if (a.m % BM != 0 || a.n % BN != 0 || a.groups < 1 || a.groups > args.tiles_m) return hipErrorInvalidValue;
+    grid_m = a.groups;
+    tiles = (long long)grid_m * args.tiles_n;
+  } else {
+    args.groups = 0;
+  }
   args.items = nullptr;
   args.item_subs = 0;
   args.pad_items = 0;
@@ -930,7 +1002,7 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   long long best = -1;
   for (int xm = 8; xm >= 1; xm >>= 1) {
     const int xn = 8 / xm;
-    if (args.tiles_m % xm || args.tiles_n % xn) continue;
+    if (grid_m % xm || args.tiles_n % xn) continue;
     const long long cost = (long long)xn * a.m + (long long)xm * a.n;
     if (best < 0 || cost < best) {
       best = cost;
@@ -1147,6 +1219,36 @@ hipError_t launch_bf16_chain_edge(int tile, int b_kind, const ChainArgs &a, hipS
   }
   BLW_CHAIN_EDGE(0)
 #undef BLW_CHAIN_EDGE
+}
+
+// a chain in SEVERAL ROUNDS (xsmm_hip_set_chain_rounds; gemm_plan.cpp plan_chain_rounds, brgemm_bf16_lw_chain_rounds.h): launch_bf16_chain's
+// layers on groups x n / BN resident workgroups of tile 0 .. 3 (GRP = 7: workgroup (g, tn) walks the row blocks g, g + groups, .. of
+// every layer, layer-major). The caller's guarantees are launch_bf16_chain's, with groups * (n / BN) <= compute units in place of tiles <=
+// compute units; the counters are the chain's, [nlayers - 1][m / BM]. One chunk per barrier only. hipErrorInvalidValue (nothing
+// launched): m % BM, n % BN, a k % 64 or k < 64, an empty batch, groups < 1, groups > m / BM, fewer than 2 or more than CH_MAXL layers.
+hipError_t launch_bf16_chain_rounds(int tile, int b_kind, int groups, const ChainArgs &a, hipStream_t s) {
+  static const int bm[4] = {32, 64, 64, 128}, bn[4] = {64, 64, 128, 128};
+  if (tile < 0 || tile > 3 || (b_kind != 0 && b_kind != 2 && b_kind != 4) || a.nlayers < 2 || a.nlayers > CH_MAXL) return hipErrorInvalidValue;
+  if (a.m < bm[tile] || a.n < bn[tile] || a.m % bm[tile] != 0 || a.n % bn[tile] != 0) return hipErrorInvalidValue;
+  if (groups < 1 || groups > a.m / bm[tile]) return hipErrorInvalidValue;
+  for (int l = 0; l < a.nlayers; ++l)
+    if (a.L[l].br < 1 || a.L[l].k < BLW_BK || a.L[l].k % BLW_BK != 0) return hipErrorInvalidValue;
+  ChainArgs c = a;
+  c.groups = groups;
+#define BLW_CHAIN_ROUNDS(FB)                                                                 \
+  switch (tile) {                                                                            \
+  case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, true, FB, 7>(c, s);                 \
+  case 1: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, true, FB, 7>(c, s);                 \
+  case 2: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, true, FB, 7>(c, s);                 \
+  default: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, true, FB, 7>(c, s);                \
+  }
+  if (b_kind == 2) {
+    BLW_CHAIN_ROUNDS(2)
+  } else if (b_kind == 4) {
+    BLW_CHAIN_ROUNDS(4)
+  }
+  BLW_CHAIN_ROUNDS(0)
+#undef BLW_CHAIN_ROUNDS
 }
 
 } // namespace tpp

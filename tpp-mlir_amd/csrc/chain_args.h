@@ -29,9 +29,10 @@ struct ChainArgs {
   int nlayers;
   int tiles_m, tiles_n; // filled by the launcher
   int xm;               // filled by the launcher: XCD grid xm x (8 / xm) over the tile grid, 0 = linear tile order
+  int groups;           // a multi-round chain (launch_bf16_chain_rounds): resident row groups G, the grid is G x tiles_n; 0 in every other launch
   // Unused. Keeps L at byte 72 of the argument block: without these bytes every L[] load moves and the compiler assigns
   // registers differently in the f32 chain kernels' K loop, a code change that would have to be measured on its own.
-  char reserved[12];
+  char reserved[8];
   ChainLayer L[CH_MAXL];
   // GROUPED launches (round 6, the tile queue's bf16 groups: launch_bf16_lw_grouped): a work list of tile invokes of ONE descriptor - every
   // workgroup takes A, B, C, D and the batch count of ITS item from the list, everything else (leading dimensions, strides, k, epilogue)
@@ -53,6 +54,10 @@ hipError_t launch_bf16_lw_edge(int tile, int b_kind, const ChainArgs &a, hipStre
 // a chain whose m the tile's rows do not divide (xsmm_hip_set_chain_edge; brgemm_bf16_lw_chain_edge.h): launch_bf16_chain on ceil(m / BM) x n / BN
 // workgroups; hipErrorInvalidValue and nothing launched when m < BM, n % BN, a k % 64 or a batch count < 1
 hipError_t launch_bf16_chain_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
+// a chain on FEWER resident workgroups than output tiles (xsmm_hip_set_chain_rounds; brgemm_bf16_lw_chain_rounds.h): groups x n / BN workgroups,
+// workgroup (g, tn) walks the row blocks g, g + groups, .. layer-major; hipErrorInvalidValue and nothing launched when m % BM, n % BN, a k % 64,
+// a batch count < 1, groups < 1 or groups > m / BM. The caller guarantees groups * (n / BN) <= the stream's compute units.
+hipError_t launch_bf16_chain_rounds(int tile, int b_kind, int groups, const ChainArgs &a, hipStream_t s);
 hipError_t launch_bf16_lw_kedge(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k (brgemm_bf16_lw_kedge.h); hipErrorInvalidValue: not launched
 hipError_t launch_bf16_lw_kedge8(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k in half steps, k % 16 == 8 (bkedge8_*); refuses the same way
 hipError_t launch_bf16_lw_kedge8(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k in half steps, k % 16 == 8 (bkedge8_*); refuses the same way

@@ -3,6 +3,7 @@
 #include "gemm_plan.h"
 #include "brgemm_f32_lw_kedge.h"
 #include "brgemm_bf16_lw_kedge.h"
+#include "brgemm_bf16_lw_chain_rounds.h"
 #include <string.h>
 
 namespace tpp {
@@ -504,6 +505,57 @@ ChainEdgePlan plan_chain_edge(int64_t m, int64_t n, int nlayers, const int64_t *
   }
   if (m % BLW_BM[tile] == 0) return ChainEdgePlan{-1, "the tile's rows divide m: not a ragged chain"};
   return ChainEdgePlan{tile, ""};
+}
+
+int chain_rounds_planned_tile(int n, const GemmDesc *const *d) {
+  for (int i = 0; i < n; ++i)
+    if (d[i]->dtype != DT_BF16) return -2;
+  if (n < 1) return -1;
+  const int v = d[0]->variant;
+  const int t = v >= V_BF16_LW4_32x64 ? v - V_BF16_LW4_32x64 : v >= V_BF16_LWF_32x64 ? v - V_BF16_LWF_32x64 : v - V_BF16_LW_32x64;
+  if (t < 0 || t > 3) return -1;
+  for (int i = 1; i < n; ++i)
+    if (d[i]->variant != d[0]->variant) return -1;
+  return t;
+}
+
+int chain_rounds_b_kind(const GemmDesc &d) {
+  if (d.dtype != DT_BF16 || d.vnni_c || !d.beta0 || d.generic_forced || d.variant == V_GENERIC) return -1;
+  return bf16_edge_b_kind(d);
+}
+
+ChainRoundsPlan plan_chain_rounds(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int mode, bool strict) {
+  auto no = [](const char *why) { return ChainRoundsPlan{-1, 0, why, false}; };
+  if (mode != 1 && !chain_rounds_mode_forced(mode)) return no("multi-round chains are off (xsmm_hip_set_chain_rounds)");
+  if (planned_tile < -1) return no("a multi-round chain is bf16: an f32 call");
+  if (nlayers < 2 || nlayers > 8) return no("fewer than 2 or more than 8 calls");
+  for (int l = 0; l < nlayers; ++l)
+    if (k[l] < BK || k[l] % BK != 0 || br[l] < 1) return no("a layer of a multi-round chain has k not in 64-k chunks, or an empty batch");
+  auto divides = [&](int t) { return t >= 0 && t <= 3 && m >= BLW_BM[t] && n >= BLW_BN[t] && m % BLW_BM[t] == 0 && n % BLW_BN[t] == 0; };
+  int tile = -1;
+  if (planned_tile >= 0) {
+    if (!divides(planned_tile)) return no("the planned tile does not divide a multi-round chain's m and n");
+    tile = planned_tile;
+  } else {
+    if (strict) return no("strict mode: the calls of a multi-round chain do not share one planned loader-wave tile");
+    for (int t = 3; t >= 0 && tile < 0; --t)
+      if (divides(t)) tile = t;
+    if (tile < 0) return no("a multi-round chain's m or n is not in whole tiles");
+  }
+  const int64_t tiles_m = m / BLW_BM[tile], tiles_n = n / BLW_BN[tile];
+  if (tiles_m > 0x7fffffff || tiles_n > 0x7fffffff) return no("more row blocks than a launch can count");
+  const int gmax = chain_rounds_max_groups((int)tiles_n, cus);
+  if (gmax < 1) return no("a row of tiles is wider than the compute units");
+  if (chain_rounds_mode_forced(mode)) {
+    const int64_t g = mode - 1000;
+    if (g < 1 || g >= tiles_m || g * tiles_n > cus) return no("the forced row groups do not fit: 1 <= G < tiles_m and G * tiles_n <= compute units");
+    return ChainRoundsPlan{tile, (int)g, "", false};
+  }
+  if (tiles_m <= gmax) return no("the chain fits in one round: not a multi-round chain");
+  const int groups = chain_rounds_groups((int)tiles_m, gmax);
+  if (chain_rounds_rounds((int)tiles_m, groups) > CHAIN_ROUNDS_GATE)
+    return ChainRoundsPlan{tile, groups, "gate: more than two rounds measured slower than call by call (profiles/chain_rounds_ab.txt)", true};
+  return ChainRoundsPlan{tile, groups, "", false};
 }
 
 static GemmLaunch launch(GemmLauncher l, int tile = 0, const char *text = "", int split = 1, int b_kind = 0, bool even = false) {

@@ -134,6 +134,38 @@ int chain_edge_b_kind(const GemmDesc &d, int chain_edge, const char **why);
 // chain's rules decide).
 struct ChainEdgePlan { int tile; const char *why; };
 ChainEdgePlan plan_chain_edge(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, bool strict);
+// MULTI-ROUND CHAINS (xsmm_hip_set_chain_rounds; rt_chain.h try_chain_launch, brgemm_bf16_lw.hip launch_bf16_chain_rounds, step maps in
+// brgemm_bf16_lw_chain_rounds.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_rounds.txt is the table of the function's answers.
+// A bf16 chain that meets every condition of the divisible chain but has MORE output tiles than compute units runs as one launch on
+// G x tiles_n resident workgroups, G row groups walking R = ceil(tiles_m / G) rounds of row blocks. m x n outputs per layer, nlayers layers
+// of k[l] per batch element and br[l] batch elements, cus compute units on the stream, planned_tile 0 .. 3 = the loader-wave tile ALL calls
+// were planned on (-1: they do not share one, -2: a call is not bf16 - chain_rounds_planned_tile), mode = the switch's value, strict =
+// xsmm_hip_set_strict.
+//   tile:   the planned tile; without one, refused in strict mode, else the largest tile whose rows divide m and whose columns divide n.
+//           (Strict mode may take the rule on the planned tile: the tile is the descriptors' own, and G changes no bit.)
+//   groups: Gmax = cus / tiles_n rounded down. mode 1 applies only where tiles_m > Gmax (a chain that fits is the divisible chain's):
+//           R = ceil(tiles_m / Gmax), G = ceil(tiles_m / R) - as few rounds as fit, balanced. mode 1000 + G: that G if 1 <= G < tiles_m and
+//           G * tiles_n <= cus.
+// tile = -1, groups = 0 and why = the reason: the switch off, an f32 call, fewer than 2 or more than 8 layers, a k % 64 or an empty batch, strict
+// mode without a shared tile, m or n not in whole tiles, a row of tiles wider than the compute units, a chain that fits in one round
+// (mode 1), a forced G that does not fit.
+// THE GATE (mode 1 only; measured, profiles/chain_rounds_ab.txt: three 1024-wide VNNI-2 layers on 256 CUs, call by call -> one launch:
+// 4224 rows R = 2 62.45 -> 49.35 us, 8192 rows R = 2 60.34 -> 53.81, but 16384 rows R = 4 99.61 -> 104.23 and 32768 rows R = 8
+// 193.09 -> 217.89 - the calls of such batches run on the 256x256 tile, which the chain has no form of): a chain of MORE THAN TWO
+// rounds stays call by call. The answer then still names the rule's tile and groups, with gated = true and why = the gate: the caller
+// does not launch. A forced G is not gated.
+struct ChainRoundsPlan { int tile; int groups; const char *why; bool gated; };
+constexpr int CHAIN_ROUNDS_GATE = 2; // most rounds mode 1 takes
+inline bool chain_rounds_mode_forced(int mode) { return mode > 1000; }
+// the loader-wave tile 0 .. 3 all n calls of a chain were planned on (variants 20 .. 23 VNNI-2, 24 .. 27 flat B, 28 .. 31 VNNI-4: the same
+// four tiles, one B image); -1: they do not share one; -2: a call is not bf16
+int chain_rounds_planned_tile(int n, const GemmDesc *const *d);
+// One call of a chain under a FORCED G, which is asked in front of the one-round rules: the B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the
+// call as a layer of the multi-round launch - what bf16_lw_b_kind asks of leading dimensions, strides and lane offsets WITHOUT its m and n
+// terms (the rule itself asks for m and n in whole tiles: 5 x 32 rows of VNNI-2 run on the 32x64 tile) - or -1: an f32 call, a VNNI C,
+// beta 1, the generic kernel, k not in 64-k chunks, an operand off the LDS-DMA grid.
+int chain_rounds_b_kind(const GemmDesc &d);
+ChainRoundsPlan plan_chain_rounds(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int mode, bool strict);
 // 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none
 int f32_chain_tile(const GemmDesc &d);
 // tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip)

@@ -180,6 +180,21 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   bool divisible = true;
   const char *edge_why = nullptr;
   const int edge_kind = edge_on ? chain_edge_b_kind(*d[0], chain_edge, &edge_why) : -1;
+  // SEVERAL ROUNDS (xsmm_hip_set_chain_rounds, opt-in; gemm_plan.cpp plan_chain_rounds): a bf16 chain that passes every rule of the
+  // divisible chain but the last one - more tiles than compute units - may run as one launch on G resident row groups. The rule is asked
+  // only where the rules below say "more tiles than compute units" - of the tile all calls were planned on, or of every tile -, a
+  // forced G (mode 1000 + G) in front of them. With the switch off rounds_mode is 0 and every NOCHAIN below is taken exactly as before.
+  const int rounds_mode = f32 ? 0 : g_chain_rounds.load(std::memory_order_relaxed);
+  int groups = 0; // > 0: the multi-round launch on that many row groups
+  const char *rounds_why = nullptr;
+  // A forced G is asked in front of the one-round rules, so also in front of their m and n terms (bf16_lw_b_kind: 64 rows for VNNI-2):
+  // rounds_kind = the B image every call has by chain_rounds_b_kind, -1 = none or not the same.
+  int rounds_kind = -1;
+  if (chain_rounds_mode_forced(rounds_mode)) {
+    rounds_kind = chain_rounds_b_kind(*d[0]);
+    for (int i = 1; i < n; ++i)
+      if (chain_rounds_b_kind(*d[i]) != rounds_kind) rounds_kind = -1;
+  }
   for (int i = 0; i < n; ++i) {
     const GemmDesc &g = *d[i];
     if (edge_on && !edge_why) {
@@ -194,7 +209,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     } else
     // every layer the same kind of B operand (VNNI-2, flat or VNNI-4: the B image is a template parameter of the launch)
     if (g.dtype != DT_BF16 || g.vnni_c || !g.beta0 || bf16_lw_b_kind(g) < 0 || bf16_lw_b_kind(g) != bf16_lw_b_kind(*d[0])) {
-      if (!edge_on || edge_why) // (edge_why: no ragged launch either - an f32 call, a VNNI C, beta 1, a forced kernel, k % 64, the operands' grid)
+      if ((!edge_on || edge_why) && rounds_kind < 0) // (edge_why: no ragged launch either - an f32 call, a VNNI C, beta 1, a forced kernel, k % 64, the operands' grid)
         NOCHAIN("a call is not bf16 / beta 0 / aligned for the LDS-DMA tiles, or the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)");
       divisible = false;
     }
@@ -213,7 +228,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (!devmem.is_device(pa[i], 0) || !devmem.is_device(pb[i], 1) || !devmem.is_device(pc[i], 2) || (g.bias && !devmem.is_device(pd[i], 3)))
       NOCHAIN("a host operand");
   }
-  if (!divisible && edge_why) NOCHAIN(edge_why);
+  if (!divisible && edge_why && rounds_kind < 0) NOCHAIN(edge_why);
   // The tile: all workgroups must be co-resident (one per CU by LDS), so the grid may not exceed the CUs. If every layer was planned
   // with the same loader-wave tile and that tile fits, use it - the launch is then bit-identical to the separate launches; else
   // the smallest tile that fits (most CUs busy).
@@ -226,29 +241,60 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   };
   if (f32 && !fits(f32_tile)) NOCHAIN("more tiles than compute units");
   int b_kind = f32 || !divisible ? 0 : bf16_lw_b_kind(*d[0]);
+  const bool strict = cfg().strict.load(std::memory_order_relaxed);
+  int shared_tile = -1; // the loader-wave tile ALL calls were planned on (bf16)
+  auto ask_rounds = [&]() { // the multi-round rule's tile and groups, or rounds_why
+    int64_t ks[CH_MAXL], brs[CH_MAXL];
+    for (int i = 0; i < n; ++i) ks[i] = d[i]->k, brs[i] = br[i];
+    const ChainRoundsPlan rp = plan_chain_rounds(m, nn, n, ks, brs, cus, shared_tile, rounds_mode, strict);
+    rounds_why = rp.why;
+    if (rp.tile < 0 || rp.gated) return; // (gated: the rule's answer is on record in why, nothing is launched)
+    tile = rp.tile;
+    groups = rp.groups;
+  };
+  if (!divisible && rounds_kind >= 0) { // (a forced G on calls only the one-round rules' m and n terms refuse)
+    shared_tile = chain_rounds_planned_tile(n, d);
+    ask_rounds();
+    if (tile >= 0) b_kind = rounds_kind;
+    else if (!edge_on || edge_why) NOCHAIN(rounds_why);
+  }
   if (divisible) {
     // (variants 20 .. 23 VNNI-2, 24 .. 27 flat B, 28 .. 31 VNNI-4: the same four tiles)
     const int planned = d[0]->variant - (b_kind == 2 ? V_BF16_LWF_32x64 : b_kind == 4 ? V_BF16_LW4_32x64 : V_BF16_LW_32x64);
     bool same = !f32 && planned >= 0 && planned < 4;
     for (int i = 1; i < n && same; ++i) same = d[i]->variant == d[0]->variant;
+    if (rounds_mode) shared_tile = chain_rounds_planned_tile(n, d); // (= same ? planned : -1 for a bf16 chain)
     if (f32) tile = f32_tile;
-    if (same && fits(planned)) tile = planned;
-    if (tile < 0 && cfg().strict.load(std::memory_order_relaxed)) NOCHAIN("strict mode: one launch only on the tile the layers were planned on");
+    if (chain_rounds_mode_forced(rounds_mode)) ask_rounds(); // (a forced G that does not fit: everything below as with the switch off)
+    if (tile < 0 && same && fits(planned)) tile = planned;
+    // the tile all calls were planned on has more tiles than compute units: several rounds on THAT tile - the descriptors' own, G
+    // changes no bit, so strict mode takes it too - in front of one round on another tile, whose bits need not be the calls'
+    if (tile < 0 && rounds_mode == 1 && same) ask_rounds();
+    if (tile < 0 && strict) NOCHAIN(rounds_why && rounds_mode == 1 ? rounds_why : "strict mode: one launch only on the tile the layers were planned on");
     for (int t = 0; t < 4 && tile < 0; ++t)
       if (fits(t)) tile = t;
-    if (tile < 0 && (!edge_on || edge_why)) NOCHAIN("more tiles than compute units");
+    if (tile < 0 && (!edge_on || edge_why)) {
+      if (rounds_mode == 1) ask_rounds();
+      if (tile < 0) NOCHAIN(rounds_mode == 1 ? rounds_why : "more tiles than compute units");
+    }
   }
-  const bool ragged = tile < 0; // (only with the switch on: every path to here with it off has a tile)
+  bool ragged = tile < 0; // (only with a switch on: every path to here with both off has a tile)
   if (ragged) {
     // the ragged launch: the tile a forcing edge-tile mode names if it fits, else the smallest that fits - counted on the ceil-divided grid
     int64_t ks[CH_MAXL], brs[CH_MAXL];
     for (int i = 0; i < n; ++i) ks[i] = d[i]->k, brs[i] = br[i];
     const int et = g_edge_tiles.load(std::memory_order_relaxed);
-    const ChainEdgePlan ep = plan_chain_edge(m, nn, n, ks, brs, cus, et >= V_BF16_LW_32x64 && et <= V_BF16_LW_128x128 ? et - V_BF16_LW_32x64 : -1,
-                                             cfg().strict.load(std::memory_order_relaxed));
-    if (ep.tile < 0) NOCHAIN(ep.why);
-    tile = ep.tile;
-    b_kind = edge_kind;
+    const ChainEdgePlan ep = plan_chain_edge(m, nn, n, ks, brs, cus, et >= V_BF16_LW_32x64 && et <= V_BF16_LW_128x128 ? et - V_BF16_LW_32x64 : -1, strict);
+    if (ep.tile >= 0) {
+      tile = ep.tile;
+      b_kind = edge_kind;
+    } else {
+      // the two switches never combine: the one-round ragged launch is asked first, and only a shape every tile of which divides - one
+      // the ragged rule has just refused - may run in several rounds
+      if (divisible && rounds_mode == 1) ask_rounds();
+      if (tile < 0) NOCHAIN(ep.why);
+      ragged = false;
+    }
   }
   if (f32) (void)f32_chain_tile_dims(tile, &bm, &bn); // bm, bn of the chosen tile
   else blw_tile_dims(tile, &bm, &bn);
@@ -320,7 +366,13 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   }
   c.target = ++blk.epoch * (unsigned)blk.tiles_n;
   if (f32) HIP_OK(launch_f32_chain(tile, c, s));
-  else if (ragged) {
+  else if (groups > 0) {
+    HIP_OK(launch_bf16_chain_rounds(tile, b_kind, groups, c, s));
+    g_chain_rounds_stats[1].store(groups, std::memory_order_relaxed);
+    g_chain_rounds_stats[2].store((m / bm + groups - 1) / groups, std::memory_order_relaxed);
+    g_chain_rounds_stats[3].store((b_kind == 4 ? V_BF16_LW4_32x64 : b_kind == 2 ? V_BF16_LWF_32x64 : V_BF16_LW_32x64) + tile, std::memory_order_relaxed);
+    g_chain_rounds_stats[0].fetch_add(1, std::memory_order_relaxed);
+  } else if (ragged) {
     HIP_OK(launch_bf16_chain_edge(tile, b_kind, c, s));
     g_chain_edge_stats[1].store((m + bm - 1) / bm, std::memory_order_relaxed);
     g_chain_edge_stats[2].store(nn / bn, std::memory_order_relaxed);

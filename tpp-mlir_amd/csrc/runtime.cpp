@@ -52,6 +52,13 @@ __attribute__((weak)) ChainEdgePlan plan_chain_edge(int64_t, int64_t, int, const
   return ChainEdgePlan{-1, "this build has no ragged-chain planner"};
 }
 __attribute__((weak)) hipError_t launch_bf16_chain_edge(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
+// (multi-round chains, xsmm_hip_set_chain_rounds: the same arrangement)
+__attribute__((weak)) int chain_rounds_planned_tile(int, const GemmDesc *const *) { return -1; }
+__attribute__((weak)) int chain_rounds_b_kind(const GemmDesc &) { return -1; }
+__attribute__((weak)) ChainRoundsPlan plan_chain_rounds(int64_t, int64_t, int, const int64_t *, const int64_t *, int64_t, int, int, bool) {
+  return ChainRoundsPlan{-1, 0, "this build has no multi-round-chain planner", false};
+}
+__attribute__((weak)) hipError_t launch_bf16_chain_rounds(int, int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 } // namespace tpp
 
 namespace {
@@ -564,6 +571,10 @@ extern "C" void xsmm_hip_chain_edge_stats(int64_t out[4]) {
 extern "C" int xsmm_hip_set_edge_k8_bf16(int mode) { return tpp::edge_k_bf16_mode_ok(mode) ? tpp::g_edge_k8_bf16.exchange(mode) : -1; }
 extern "C" void xsmm_hip_edge_k8_bf16_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k8_bf16_stats[i].load(std::memory_order_relaxed);
+}
+extern "C" int xsmm_hip_set_chain_rounds(int mode) { return tpp::chain_rounds_mode_ok(mode) ? tpp::g_chain_rounds.exchange(mode) : -1; }
+extern "C" void xsmm_hip_chain_rounds_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_rounds_stats[i].load(std::memory_order_relaxed);
 }
 extern "C" void xsmm_hip_tail_split_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_tail_split_stats[i].load(std::memory_order_relaxed);

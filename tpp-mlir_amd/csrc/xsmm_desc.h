@@ -205,6 +205,16 @@ inline std::atomic<int> g_chain_edge{[] {
   return chain_edge_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_chain_edge_stats[4]; // ragged chain launches; tile rows, tile columns, GemmVariant of the tile (with its B image) of the latest
+// MULTI-ROUND CHAINS (xsmm_hip_set_chain_rounds / TPP_HIP_CHAIN_ROUNDS; gemm_plan.cpp plan_chain_rounds, rt_chain.h try_chain_launch,
+// brgemm_bf16_lw_chain_rounds.h): 0 = off, 1 = a bf16 chain with more output tiles than compute units runs as one launch on G resident row
+// groups, G by rule; 1000 + G = force G row groups (tests and measurements; also for a chain that would fit in one round). A switch of its own.
+inline bool chain_rounds_mode_ok(int v) { return v == 0 || v == 1 || (v > 1000 && v <= 1000 + 0x10000); }
+inline std::atomic<int> g_chain_rounds{[] {
+  const char *e = getenv("TPP_HIP_CHAIN_ROUNDS");
+  const int v = e ? atoi(e) : 0;
+  return chain_rounds_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_chain_rounds_stats[4]; // multi-round chain launches; row groups G, rounds R, GemmVariant of the tile (with its B image) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

@@ -125,6 +125,8 @@ _SIGNATURES = {
     "xsmm_hip_f32_halves_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_chain_rounds": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_chain_rounds_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_fold_transpose_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_epilogue": (ctypes.c_int, [ctypes.c_int]),
@@ -428,6 +430,19 @@ class XsmmRuntime:
         28 + t VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_chain_edge_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_chain_rounds(self, mode):
+        """bf16 layer chains with more output tiles than compute units, as one launch on G resident row groups that walk R rounds of
+        row blocks: 0 off (default), 1 on - G by rule -, 1000 + G force G row groups (also for a chain that fits in one round); returns
+        the previous value, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_chain_rounds(mode)
+
+    def chain_rounds_stats(self):
+        """(multi-round chain launches; row groups G, rounds R = ceil(tiles_m / G), variant number of the tile with its B image - 20 + t
+        VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_chain_rounds_stats(out)
         return tuple(int(v) for v in out)
 
     def set_fold_transpose(self, enable):
