@@ -9,10 +9,8 @@ here from its issue. And, compile-only: the twelve multi-round instances exist i
 import difflib
 import os
 import re
-import shutil
 import subprocess
 import sys
-import tempfile
 
 import pytest
 
@@ -21,6 +19,7 @@ CSRC = os.path.join(ROOT, "tpp-mlir_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "gemm_plan_chain_rounds.txt")
 sys.path.insert(0, os.path.join(ROOT, "tpp-mlir_amd"))
 import build  # noqa: E402
+import blw_codeobj  # noqa: E402
 
 LINE = re.compile(r'^(\d+)x(\d+) k([\d,]+) br([\d,]+) (f32|bf16) vf(\d) f(-?\d+),(-?\d+) sw(\d+) st([01]) cus(\d+) : v(\d+),(-?\d+) pt(-?\d) \| '
                   r'tile(-?\d) G(\d+) R(\d+) g([01]) "([^"]*)"$')
@@ -191,21 +190,11 @@ def test_case_list_covers_what_the_issue_names(rows):
 def test_multi_round_instances_exist_and_use_no_scratch():
     """brgemm_bf16_lw<WM, WN, WK, TM, TN, NSLOT, NLA, NLB, 1, true, FLATB, 7>: the four tiles with the loader waves and ring of the divisible
     chain of each, one chunk per barrier only, the three B images - no scratch, no AGPRs, at most 256 VGPRs"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.fail("needs hipcc")
-    src = os.path.join(CSRC, "brgemm_bf16_lw.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c", src, "-o", os.path.join(tmp, "k.o"),
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", r.stderr)]
-    agprs = [int(x) for x in re.findall(r"AGPRs: (\d+)", r.stderr)]
-    assert len(names) == len(scratch) == len(vgprs) == len(agprs), (len(names), len(scratch), len(vgprs), len(agprs))
-    rounds = {n: (s, v, a) for n, s, v, a in zip(names, scratch, vgprs, agprs) if n.endswith("Li7EEEvNS_9ChainArgsE")}
-    tiles = ((1, 2, 2, 1, 1, 8, 1, 2, 1), (2, 2, 1, 1, 1, 8, 1, 1, 1), (2, 2, 1, 1, 2, 6, 1, 2, 1), (2, 2, 1, 2, 2, 4, 1, 1, 1))
+    rep = blw_codeobj.report()
+    rounds = {n: x for n, x in rep.items() if n.endswith("Li7EEEvNS_9ChainArgsE")}
+    # the four tiles' configurations as the launch table (brgemm_bf16_lw_launch.h) gives them to the divisible chain, one chunk per barrier
+    tiles = sorted({cfg + (1,) for mode, multi, tile, b_kind, sup, cfg, dims, sym in blw_codeobj.launch_table()[0] if (mode, multi) == (0, 1)})
+    assert len(tiles) == 4, tiles
     for args in tiles:
         for image in (0, 2, 4):
             want = "_ZN3tpp14brgemm_bf16_lwI" + "".join("Li%dE" % a for a in args) + "Lb1ELi%dELi7EEEvNS_9ChainArgsE" % image

@@ -129,7 +129,7 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A_, const void *B_, void *
 // the bf16 chain kernel has no host stand-in: plan_gemm above refuses bf16, so try_chain_launch never gets this far
 int bf16_lw_b_kind(const GemmDesc &) { return -1; }
 void blw_tile_dims(int, int *bm, int *bn) { *bm = *bn = 128; }
-hipError_t launch_bf16_chain(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_bf16_chain(int, int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 int f32_chain_tile(const GemmDesc &) { return -1; }
 int force_gemm_split(int) { return -1; }
 static bool g_fake_strict = false;

@@ -45,10 +45,11 @@
 #include "gemm_common.h"
 #include "xsmm_desc.h"
 #include "chain_args.h"
-#include "brgemm_bf16_lw_kedge.h"
+#include "brgemm_bf16_lw_launch.h"
 #include "brgemm_bf16_lw_chain_edge.h"
 #include "brgemm_bf16_lw_chain_rounds.h"
 #include <type_traits>
+#include <utility>
 
 namespace tpp {
 
@@ -58,6 +59,7 @@ typedef unsigned int u32x2_lw __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) unsigned int g_u32_lw;
 
 constexpr int BLW_BK = 64; // k per chunk
+static_assert(BLW_BK == BKEDGE_BK && BLW_MAXL == CH_MAXL, "brgemm_bf16_lw_launch.h counts chunks and layers the same way");
 // The kernel's argument block, read where it lies (kernarg segment, constant address space): the layer table is indexed at
 // run time, and a by-value / by-reference copy of the struct would be spilled to scratch (640 bytes per lane) for that.
 typedef const __attribute__((address_space(4))) ChainArgs chain_kernarg_t;
@@ -92,24 +94,23 @@ template <int PPL> __device__ __forceinline__ void blw_wait_younger(int younger)
 template <bool IS_A, int NL, int NLA, int NSLOT_C, int SUP, int BM, int BN, int WK, bool MULTI, int FB = 0, int GRP = 0>
 __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *smem, int lane, int m0, int n0, int tm, int L, int part,
                                            const void *it_A = nullptr, const void *it_B = nullptr, int it_br = 0, unsigned q_delta = 0) {
-  static_assert(GRP != 2 || (BM == 128 && BN == 128 && NL == 1 && (FB == 0 || FB == 4)), "quads: the 128x128 tile, one loader wave per panel, VNNI-2 / VNNI-4 B");
+  static_assert(GRP != BLW_QUADS || (BM == 128 && BN == 128 && NL == 1 && (FB == 0 || FB == 4)), "quads: the 128x128 tile, one loader wave per panel, VNNI-2 / VNNI-4 B");
+  static_assert(BlwModeCheck<GRP, MULTI, SUP>::ok, "mode, MULTI and SUP (brgemm_bf16_lw_launch.h)");
   chain_kernarg_t &p = *pp;
-  constexpr bool ITEMS = GRP == 1 || GRP == 2; // operands from an item (GRP = 3, edge tiles: the argument block's, as GRP = 0)
+  constexpr bool ITEMS = blw_items(GRP); // operands from an item (GRP = 3, edge tiles: the argument block's, as GRP = 0)
   // GRP = 4 (RAGGED k, brgemm_bf16_lw_kedge.h): GRP = 3 + a batch element of ceil(k / 64) chunks, the last one shifted back to start at
   // k - 64: the advance into it is k % 64 (d_last), the batch wrap the element's stride less (k - 64). One k-value is one element of an
   // A row and ldb elements of every B image (a pair-row is 2 k, a VNNI-4 group row 4 k, a flat row 1 k): the shifted start is a whole
   // number of image rows and a multiple of 16 bytes because k % 16 == 0.
   // GRP = 6 (RAGGED k in HALF steps): GRP = 4 to this function - k % 8 == 0 keeps the shifted start 16 bytes into an A row and on a whole
   // pair-row / group row / flat row of B.
-  constexpr bool KEDGE = GRP == 4 || GRP == 6;
-  static_assert(!KEDGE || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
+  constexpr bool KEDGE = blw_ragged_k(GRP);
   // GRP = 5 (a CHAIN on edge ROW tiles, brgemm_bf16_lw_chain_edge.h): the argument block's operands as GRP = 0, m0 of the last row block
   // shifted back by the kernel; the seam wait of a shifted block is for TWO row blocks' producers (below)
-  static_assert(GRP != 5 || (SUP == 1 && MULTI), "a ragged chain: a chain, one chunk per barrier");
   // GRP = 7 (a chain in SEVERAL ROUNDS, brgemm_bf16_lw_chain_rounds.h): `tm` arrives as the workgroup's row GROUP g; the loop below runs
   // over STEPS (layer, round) and takes tm and m0 from the step. The A state is rebuilt per step (the row base moves); the B state per
   // step too (the same layer's panels again, or the next layer's), ahead of the step wherever the run-ahead rule holds.
-  static_assert(GRP != 7 || (SUP == 1 && MULTI), "a multi-round chain: a chain, one chunk per barrier");
+  constexpr bool ROUNDS = GRP == BLW_CHAIN_ROUNDS;
   constexpr int A_SLOT = BM * 128, SLOT = (BM + BN) * 128;
   // SUP = chunks per barrier (the unit everything below counts in: a "chunk" of this function is SUP 64-k chunks, a "slot" SUP
   // consecutive ring slots). SUP = 2 halves the barrier count and the loader's per-iteration scalar work for the small tiles, whose
@@ -173,7 +174,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       d_in = (int64_t)BLW_BK * p.L[l].ldb;                                                                             \
       d_wrap = p.L[l].stride_b - (int64_t)(kchunks - 1) * d_in;                                                        \
       vo0 = vo1 = (unsigned)((lane / PPR4_) * (int)p.L[l].ldb * 8 + ((lane % PPR4_) << 4));                            \
-      if (GRP == 2) vo0 = vo1 = (unsigned)(((lane & 31) << 4)) + ((lane & 32) ? q_delta : 0u); /* 64 pieces = one k-group row: 32 per item */ \
+      if (GRP == BLW_QUADS) vo0 = vo1 = (unsigned)(((lane & 31) << 4)) + ((lane & 32) ? q_delta : 0u); /* 64 pieces = one k-group row: 32 per item */ \
       step = (unsigned)(NL * RPI4_ * (int)p.L[l].ldb * 8);                                                             \
     } else {                                                                                                           \
       g = (const unsigned short *)(ITEMS ? it_B : p.L[l].B) + 2 * (int64_t)n0 + (int64_t)part * RPI * 2 * p.L[l].ldb;  \
@@ -181,7 +182,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       d_wrap = p.L[l].stride_b - (int64_t)(kchunks - 1) * d_in;                                                        \
       /* instruction v covers pair-rows RPI*v ..: lane -> pair-row lane / (BN/4), 16-byte piece lane % (BN/4) */       \
       vo0 = vo1 = (unsigned)((lane / (BN / 4)) * (int)p.L[l].ldb * 4 + ((lane % (BN / 4)) << 4));                      \
-      if (GRP == 2) vo0 = vo1 = (unsigned)((lane >> 5) * (int)p.L[l].ldb * 4 + ((lane & 15) << 4)) + ((lane & 16) ? q_delta : 0u); /* 32 pieces = one pair-row: 16 per item */ \
+      if (GRP == BLW_QUADS) vo0 = vo1 = (unsigned)((lane >> 5) * (int)p.L[l].ldb * 4 + ((lane & 15) << 4)) + ((lane & 16) ? q_delta : 0u); /* 32 pieces = one pair-row: 16 per item */ \
       step = (unsigned)(NL * RPI * (int)p.L[l].ldb * 4);                                                               \
     }                                                                                                                  \
     /* one chunk per batch element (the compiler's 64-k tile invokes over packed blocks): EVERY advance is the wrap - the same   */ \
@@ -208,7 +209,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       } else {                                                                                                         \
         _Pragma("unroll") for (int v = 0; v < PPC; ++v)                                                                \
             __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (lds_void_b *)(base_ + v * NL * 1024), 16, (v & 1) ? vo1 : vo0,   \
-                                                     v * step + ((GRP == 2 && IS_A && v >= 8) ? q_delta : 0u), 0, 0);      \
+                                                     v * step + ((GRP == BLW_QUADS && IS_A && v >= 8) ? q_delta : 0u), 0, 0);      \
       }                                                                                                                \
       if (KEDGE) { /* +64 k,  + k % 64 into the element's last chunk, then the batch wrap */                       \
         ++kc;                                                                                                          \
@@ -230,11 +231,11 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   constexpr int PRIMED = -2; // GRP = 7, a value of state_layer: the run-ahead of the step before loaded THIS step's state
   // (ONE loop: GRP = 7 goes from step to step - tm from the group's first row block to its last, then the next layer -, every other
   // launch from layer to layer)
-  for (int lc = 0; lc < L; GRP == 7 ? chain_rounds_next(tm, lc, p.groups, p.tiles_m) : (void)++lc) {
-    if constexpr (GRP == 7) m0 = tm * BM;
+  for (int lc = 0; lc < L; ROUNDS ? chain_rounds_next(tm, lc, p.groups, p.tiles_m) : (void)++lc) {
+    if constexpr (ROUNDS) m0 = tm * BM;
     const int T = (ITEMS ? it_br : p.L[lc].br) * (KEDGE ? bkedge_chunks(p.L[lc].k) : p.L[lc].k / BLW_BK) / SUP; // (a multiple of SUP: the launcher picks SUP = 1 otherwise)
     int pre = NSLOT - 2; // chunks of this layer already requested by the run-ahead of the previous layer's tail
-    if constexpr (GRP == 7) {
+    if constexpr (ROUNDS) {
       if (state_layer != PRIMED) {
         BLW_LOAD_STATE(lc);
         pre = 0;
@@ -246,41 +247,26 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       pre = 0;
       slot = s0;
     }
-    if constexpr (GRP == 5) {
-      if (poller && lc > 0) {
-        // RAGGED m: the rows [m0, m0 + BM) this block reads were stored by the row blocks first_block .. last_block of layer lc-1 - the
-        // block itself and, for the shifted last block, its upper neighbour as well (each block stores its OWN rows only). Every one
-        // of their counters must have reached the target; all the waits share ONE time bound and the one error word.
-        const int b_first = chain_edge_first_block(tm, p.tiles_m, p.m, BM), b_last = chain_edge_last_block(tm, p.tiles_m, p.m, BM);
-        const unsigned target = p.target;
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        for (int bw = b_first; bw <= b_last; ++bw) {
-          g_u32_lw *c = (g_u32_lw *)(p.cnt + ((size_t)(lc - 1) * p.tiles_m + bw) * CHAIN_CNT_STRIDE);
-          for (;;) {
-            const unsigned v = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((int)(v - target) >= 0) break;
-            if (__builtin_amdgcn_s_memrealtime() - t0 > CHAIN_TIMEOUT_TICKS) { // never hang the GPU: flag it and go on
-              if (lane == 0) __hip_atomic_store((g_u32_lw *)p.err, 1u + (unsigned)lc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-          }
-        }
-        asm volatile("" ::: "memory");
-      }
-    } else if (poller && lc > 0) {
-      // every producer tile of row block tm of layer lc-1 has been stored (write-through) and drained
-      g_u32_lw *c = (g_u32_lw *)(p.cnt + ((size_t)(lc - 1) * p.tiles_m + tm) * CHAIN_CNT_STRIDE);
+    if (poller && lc > 0) {
+      // every producer tile of the rows [m0, m0 + BM) of layer lc-1 has been stored (write-through) and drained: the tiles of the row
+      // blocks b_first .. b_last - row block tm itself and, for the shifted last block of a RAGGED-m chain, its upper neighbour as well
+      // (each block stores its OWN rows only). Every one of their counters must have reached the target; all the waits share ONE time
+      // bound and the one error word.
+      const int b_first = GRP == BLW_CHAIN_EDGE ? chain_edge_first_block(tm, p.tiles_m, p.m, BM) : tm;
+      const int b_last = GRP == BLW_CHAIN_EDGE ? chain_edge_last_block(tm, p.tiles_m, p.m, BM) : tm;
       const unsigned target = p.target;
       const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      for (;;) {
-        const unsigned v = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((int)(v - target) >= 0) break;
-        if (__builtin_amdgcn_s_memrealtime() - t0 > CHAIN_TIMEOUT_TICKS) { // never hang the GPU: flag it and go on
-          if (lane == 0) __hip_atomic_store((g_u32_lw *)p.err, 1u + (unsigned)lc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
+      for (int bw = b_first; bw <= b_last; ++bw) {
+        g_u32_lw *c = (g_u32_lw *)(p.cnt + ((size_t)(lc - 1) * p.tiles_m + bw) * CHAIN_CNT_STRIDE);
+        for (;;) {
+          const unsigned v = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if ((int)(v - target) >= 0) break;
+          if (__builtin_amdgcn_s_memrealtime() - t0 > CHAIN_TIMEOUT_TICKS) { // never hang the GPU: flag it and go on
+            if (lane == 0) __hip_atomic_store((g_u32_lw *)p.err, 1u + (unsigned)lc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
         }
-        __builtin_amdgcn_s_sleep(1);
       }
       asm volatile("" ::: "memory");
     }
@@ -305,28 +291,12 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       __builtin_amdgcn_s_barrier();
       BLW_ISSUE(slot);
     }
-    // the last NSLOT - 2 barriers of the layer: nothing of THIS layer is left to request
-    if constexpr (GRP == 7) {
-      // the next step: this layer's next row block (the same weight panels again), or the next layer's first
-      const bool more_rounds = chain_rounds_more(tm, p.groups, p.tiles_m);
-      if (ahead && (lc + 1 < L || more_rounds)) {
-        BLW_LOAD_STATE(more_rounds ? lc : lc + 1); // (the slot rotation carries over into the next step)
-        state_layer = PRIMED;
-        for (; t + 1 < T; ++t) {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSLOT - 3) * PPL) : "memory");
-          __builtin_amdgcn_s_barrier();
-          BLW_ISSUE(slot);
-        }
-      } else {
-        for (; t + 1 < T; ++t) {
-          blw_wait_younger<PPL>(T - 2 - t);
-          __builtin_amdgcn_s_barrier();
-        }
-      }
-      if (lc + 1 == L && !more_rounds) return;
-    } else {
-    if (MULTI && ahead && lc + 1 < L) {
-      BLW_LOAD_STATE(lc + 1); // (the slot rotation carries over into the next layer)
+    // the last NSLOT - 2 barriers of the layer: nothing of THIS layer is left to request. The next step of a multi-round chain: this
+    // layer's next row block (the same weight panels again), or the next layer's first
+    const bool more_rounds = ROUNDS && chain_rounds_more(tm, p.groups, p.tiles_m);
+    if (MULTI && ahead && (lc + 1 < L || more_rounds)) {
+      BLW_LOAD_STATE(more_rounds ? lc : lc + 1); // (the slot rotation carries over into the next layer / step)
+      if constexpr (ROUNDS) state_layer = PRIMED;
       for (; t + 1 < T; ++t) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSLOT - 3) * PPL) : "memory");
         __builtin_amdgcn_s_barrier();
@@ -338,8 +308,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
         __builtin_amdgcn_s_barrier();
       }
     }
-    if (lc + 1 == L) return;
-    }
+    if (lc + 1 == L && !more_rounds) return;
     if constexpr (WK > 1) __builtin_amdgcn_s_barrier(); // R1 (K groups combine)
     __builtin_amdgcn_s_barrier();                        // S1 (tile stored and drained)
     s0 = (s0 + T) % NSLOT;
@@ -350,11 +319,10 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
 
 template <int WM, int WN, int WK, int TM, int TN, int NSLOT, int NLA, int NLB, int SUP, bool MULTI, int FLATB = 0, int GRP = 0>
 __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_lw(ChainArgs p_by_value) {
-  static_assert(!GRP || !MULTI || GRP == 5 || GRP == 7, "a grouped launch is a set of single layers");
-  static_assert(GRP >= 0 && GRP <= 7, "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds");
+  static_assert(BlwModeCheck<GRP, MULTI, SUP>::ok, "mode, MULTI and SUP (brgemm_bf16_lw_launch.h)");
   // operands and batch count from an item (GRP = 1, 2). GRP = 3 (EDGE TILES, a whole layer whose m or n the tile does not divide) has
   // no items: everything from the argument block, as GRP = 0
-  constexpr bool ITEMS = GRP == 1 || GRP == 2;
+  constexpr bool ITEMS = blw_items(GRP);
   // GRP = 4 (RAGGED k, xsmm_hip_set_edge_k_bf16): GRP = 3 - with own_row = own_col = 0 a layer the tile divides - whose k is a multiple of
   // 16 but not of 64: the last chunk of every batch element is shifted back to end at k and the MFMA waves skip the k-steps it holds
   // again (brgemm_bf16_lw_kedge.h)
@@ -364,15 +332,12 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // GRP = 6 (RAGGED k in HALF steps, xsmm_hip_set_edge_k8_bf16): GRP = 4 in every respect - edge rows and columns, ring, loader advance,
   // laps and pairs of untested bodies - for a k that is a multiple of 8 but not of 16: the overlap of the last chunk ends in the middle
   // of a k-step, and that one step multiplies its upper eight k-values only (chunk_ke below, KE = 2)
-  constexpr bool KEDGE = GRP == 4 || GRP == 6;
-  constexpr bool EDGE = GRP == 3 || KEDGE || GRP == 5;
-  static_assert(!KEDGE || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
+  constexpr bool KEDGE = blw_ragged_k(GRP), ROUNDS = GRP == BLW_CHAIN_ROUNDS;
+  constexpr bool EDGE_ROWS = blw_edge_rows(GRP), EDGE_COLS = blw_edge_cols(GRP); // (the last tile of a column / row of tiles is shifted back)
   // GRP = 7 (a chain in SEVERAL ROUNDS, xsmm_hip_set_chain_rounds): MULTI on p.groups x tiles_n workgroups, fewer than the output tiles -
   // workgroup (g, tn) walks the row blocks g, g + groups, .. of every layer, layer-major (the file's header; brgemm_bf16_lw_chain_rounds.h).
   // m and n in whole tiles: no edge predicate anywhere.
-  static_assert(GRP != 5 || (SUP == 1 && MULTI), "a ragged chain: a chain, one chunk per barrier");
-  static_assert(GRP != 7 || (SUP == 1 && MULTI), "a multi-round chain: a chain, one chunk per barrier");
-  static_assert(GRP != 2 || (WM == 2 && WN == 2 && WK == 1 && TM == 2 && TN == 2), "quads: every MFMA wave owns one item's 64x64 output");
+  static_assert(GRP != BLW_QUADS || (WM == 2 && WN == 2 && WK == 1 && TM == 2 && TN == 2), "quads: every MFMA wave owns one item's 64x64 output");
   chain_kernarg_t *pp = (chain_kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr(); // = &p_by_value (the only explicit argument)
   chain_kernarg_t &p = *pp;
   constexpr int NMW = WM * WN * WK, NOUT = WM * WN; // MFMA waves; waves that own output
@@ -416,7 +381,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   [[maybe_unused]] void *it_C = nullptr;
   [[maybe_unused]] int it_br = 0;
   [[maybe_unused]] unsigned q_da = 0, q_db = 0;
-  if constexpr (GRP == 2) {
+  if constexpr (GRP == BLW_QUADS) {
     // QUADS: workgroup b = the b-th 2 x 2 block of items. Panels: the upper-left item's A rows / B columns + the two distances; output
     // and bias: MFMA wave (wm, wn) owns item (wm, wn)'s 64x64 block outright (its own base pointer, the items' ldc)
     typedef const __attribute__((address_space(4))) QuadItem quad_c_t;
@@ -430,7 +395,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
     q_da = w.da;
     q_db = w.db;
     tm = tn = 0;
-  } else if constexpr (GRP == 1) {
+  } else if constexpr (GRP == BLW_ITEMS) {
     // (plain order: workgroup b = the b-th tile of the list. Handing XCD x the x-th EIGHTH of the list - contiguous block rows of the
     // layer - was measured and is WORSE for the reference's shapes, 1024 x 2560 x 1024 15.0 -> 18.1 us: with row-major items and a
     // column count that is a multiple of 8 the plain order already gives every XCD its own eighth of the COLUMNS, i.e. of W, the
@@ -461,7 +426,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
     it_br = (int)w.br;
   } else if (p.xm > 0) {
     const int xn = 8 / p.xm, xcd = b & 7, j = b >> 3;
-    const int lm = (GRP == 7 ? p.groups : p.tiles_m) / p.xm, ln = p.tiles_n / xn; // tiles per XCD (GRP = 7: row groups)
+    const int lm = (ROUNDS ? p.groups : p.tiles_m) / p.xm, ln = p.tiles_n / xn; // tiles per XCD (GRP = 7: row groups)
     tm = (xcd / xn) * lm + j / ln;
     tn = (xcd % xn) * ln + j % ln;
   } else {
@@ -477,8 +442,8 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // columns [0, n); the tile stores the rows >= own_row and the 16-byte pieces at columns >= own_col of its block (TILE-relative: the
   // tiles have several wave columns) - the others are the neighbour's. n0 is a multiple of 8 (the planner asks for n % 8 == 0).
   // (GRP = 7: tm is the workgroup's row GROUP up to here; the step loops below and in blw_loader take tm and m0 from the step)
-  int m0 = GRP == 5 ? chain_edge_row0(tm, p.tiles_m, p.m, BM) : (EDGE && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
-  const int n0 = ((GRP == 1 || (EDGE && GRP != 5)) && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
+  int m0 = GRP == BLW_CHAIN_EDGE ? chain_edge_row0(tm, p.tiles_m, p.m, BM) : (EDGE_ROWS && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
+  const int n0 = (EDGE_COLS && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
   [[maybe_unused]] const int skip_cols = tn * BN - n0;
   [[maybe_unused]] const int own_row = tm * BM - m0, own_col = tn * BN - n0;
   const int L = MULTI ? p.nlayers : 1;
@@ -676,8 +641,8 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   int s0 = 0; // ring slot of the current layer's chunk 0
   // (ONE loop: GRP = 7 goes from step to step - tm from the group's first row block to its last, then the next layer -, every other
   // launch from layer to layer; blw_loader counts the same way)
-  for (int l = 0; l < L; GRP == 7 ? chain_rounds_next(tm, l, p.groups, p.tiles_m) : (void)++l) {
-    if constexpr (GRP == 7) m0 = tm * BM;
+  for (int l = 0; l < L; ROUNDS ? chain_rounds_next(tm, l, p.groups, p.tiles_m) : (void)++l) {
+    if constexpr (ROUNDS) m0 = tm * BM;
     const auto &Y = p.L[l];
     const int T = (ITEMS ? it_br : Y.br) * (KEDGE ? bkedge_chunks(Y.k) : Y.k / BLW_BK);
     const int ep = Y.ep;
@@ -696,7 +661,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         biasw[j][g] = u32x2_lw{0u, 0u};
-        if (ep & EP_BIAS) biasw[j][g] = *(const u32x2_lw *)((const unsigned short *)(ITEMS ? it_D : Y.D) + n0 + ((GRP == 2 ? 0 : wn * TN) + j) * 32 + 8 * g + 4 * lh);
+        if (ep & EP_BIAS) biasw[j][g] = *(const u32x2_lw *)((const unsigned short *)(ITEMS ? it_D : Y.D) + n0 + ((GRP == BLW_QUADS ? 0 : wn * TN) + j) * 32 + 8 * g + 4 * lh);
       }
     if (MULTI && NLA > 1 && l > 0) __builtin_amdgcn_s_barrier(); // S2 (the loaders' rendezvous after the seam wait)
     __builtin_amdgcn_s_barrier(); // P: chunk 0 published
@@ -727,8 +692,8 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
         // kernel - single basic blocks -, the others and the layer's tail ask per step.
         // GRP = 6: skipl counts HALF steps and the tested bodies are the three-way ones (KE = 2); the loops are the same.
         const int kchunks = bkedge_chunks(p.L[l].k);
-        const int skipl = GRP == 6 ? bkedge8_skip_halves(p.L[l].k, kchunks - 1) : bkedge_skip_steps(p.L[l].k, kchunks - 1);
-        using KE_T = std::integral_constant<int, GRP == 6 ? 2 : 1>; // KE of the tested bodies
+        const int skipl = blw_half_steps(GRP) ? bkedge8_skip_halves(p.L[l].k, kchunks - 1) : bkedge_skip_steps(p.L[l].k, kchunks - 1);
+        using KE_T = std::integral_constant<int, blw_half_steps(GRP) ? 2 : 1>; // KE of the tested bodies
         int kc = 0;
         auto skip_next = [&]() __attribute__((always_inline)) {
           const bool last = kc + 1 == kchunks;
@@ -864,7 +829,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
       // lane (li, lh) owns row 32*i + li of the wave's row block i and, in registers 4g..4g+3 of tile (i, j),
       // columns 32*j + 8*g + 4*lh + (0..3)
       const __amdgpu_buffer_rsrc_t rsrcC = __builtin_amdgcn_make_buffer_rsrc(
-          (void *)(GRP == 2 ? C : C + (int64_t)(m0 + wm * 32 * TM) * Y.ldc + n0 + wn * 32 * TN), 0, 0x7fffffff, 0x00020000);
+          (void *)(GRP == BLW_QUADS ? C : C + (int64_t)(m0 + wm * 32 * TM) * Y.ldc + n0 + wn * 32 * TN), 0, 0x7fffffff, 0x00020000);
       if constexpr (!MULTI) {
         if (!(ep & EP_BETA0)) { // beta = 1: add C before the single rounding (8-byte loads, rare path)
 #pragma unroll
@@ -929,18 +894,18 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
           const int row = it * RPP + lane / LPR, ch = lane % LPR;
           const u32x4 v = *(const u32x4 *)(ot + row * ES + ch * 16);
           const unsigned voff = (unsigned)(32 * i + row) * ldcb + (unsigned)(ch * 16);
-          if (GRP == 1 && ch * 8 < skip_cols) continue; // (a ragged item's last column tile: these columns are the neighbour tile's)
+          if (GRP == BLW_ITEMS && ch * 8 < skip_cols) continue; // (a ragged item's last column tile: these columns are the neighbour tile's)
           // (edge tiles: rows and 16-byte pieces in front of the tile's own are the neighbour's - a per-lane predicate on the store.
           // The beta = 1 join above reads the whole block: it lies inside the matrix, and what is not owned is never stored)
-          if (EDGE && GRP != 5 && (wm * 32 * TM + 32 * i + row < own_row || wn * 32 * TN + ch * 8 < own_col)) continue;
-          if (GRP == 5 && wm * 32 * TM + 32 * i + row < own_row) continue; // (a ragged chain: whole column tiles)
+          // (a ragged chain: whole column tiles, the row term alone)
+          if (EDGE_ROWS && (wm * 32 * TM + 32 * i + row < own_row || (EDGE_COLS && wn * 32 * TN + ch * 8 < own_col))) continue;
           if (MULTI && l + 1 < L) __builtin_amdgcn_raw_buffer_store_b128(v, rsrcC, voff, 0, 16); // sc1: write-through (hand-off)
           else __builtin_amdgcn_raw_buffer_store_b128(v, rsrcC, voff, 0, C_STORE_AUX); // (last layer / single layer: gemm_common.h)
         }
       }
     }
-    if (l + 1 == L && (GRP != 7 || !chain_rounds_more(tm, p.groups, p.tiles_m))) break;
-    if constexpr (GRP == 7) {
+    if (l + 1 == L && (!ROUNDS || !chain_rounds_more(tm, p.groups, p.tiles_m))) break;
+    if constexpr (ROUNDS) {
       if (l + 1 == L) {
         // a further row block of the LAST layer follows: nothing to publish and no store to drain - only the rendezvous behind every
         // wave's epilogue (its staging tile in a retired A half has been read back) before the A loader requests the next step's panels
@@ -969,16 +934,16 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   static std::atomic<unsigned long long> lds_set{0};
   if (hipError_t e = ensure_dynamic_lds((const void *)kern, (int)lds, lds_set); e != hipSuccess) return e;
   ChainArgs args = a;
-  constexpr bool EDGE = GRP == 3 || GRP == 4 || GRP == 5 || GRP == 6; // (5, a ragged chain: rows only - n % BN == 0 is the launcher's check)
+  constexpr bool EDGE = blw_edge_rows(GRP); // (a ragged chain: rows only - n % BN == 0 is blw_launch_ok's check)
   args.tiles_m = EDGE ? (a.m + BM - 1) / BM : a.m / BM; // (edge tiles: ceil-divided both ways, m >= BM and n >= BN)
-  args.tiles_n = (GRP == 1 || (EDGE && GRP != 5)) ? (a.n + BN - 1) / BN : a.n / BN; // (grouped items: a ragged last column tile, see the kernel)
+  args.tiles_n = blw_edge_cols(GRP) ? (a.n + BN - 1) / BN : a.n / BN; // (grouped items: a ragged last column tile, see the kernel)
   long long tiles = (long long)args.tiles_m * args.tiles_n;
   if (EDGE && (a.m < BM || a.n < BN)) return hipErrorInvalidValue;
   if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
   // GRP = 7 (several rounds): a.groups row groups are resident, each a row of tiles_n workgroups; the grid and the XCD search below
   // count row groups where the other launches count row blocks
   int grid_m = args.tiles_m;
-  if constexpr (GRP == 7) {
+  if constexpr (GRP == BLW_CHAIN_ROUNDS) {
     if (a.m % BM != 0 || a.n % BN != 0 || a.groups < 1 || a.groups > args.tiles_m) return hipErrorInvalidValue;
     grid_m = a.groups;
     tiles = (long long)grid_m * args.tiles_n;
@@ -988,7 +953,7 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   args.items = nullptr;
   args.item_subs = 0;
   args.pad_items = 0;
-  if constexpr (GRP == 1 || GRP == 2) { // tiles_m x tiles_n workgroups per item (consecutive workgroups = the items in list order: neighbouring
+  if constexpr (blw_items(GRP)) { // tiles_m x tiles_n workgroups per item (consecutive workgroups = the items in list order: neighbouring
                        // tiles of a layer share panels in the L2 of whichever XCD they land on)
     if (!items || n_items <= 0 || tiles * n_items > 0x7fffffffLL) return hipErrorInvalidValue;
     args.items = items;
@@ -1013,162 +978,81 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   return hipGetLastError();
 }
 
-// Loader waves per tile (NLA + NLB), same-box A/B (profiles/r03_blw_loader_split.txt): 32x64 1 + 2 (1 + 1: +2 %, 2 + 2: +5 %),
-// 64x64 1 + 1 (1 + 2: +2 %, 2 + 2: +7 %), 64x128 1 + 2 (1 + 1: same, 2 + 4: +5 %), 128x128 1 + 1 (2 + 2, 1 + 2: same).
-// SUP = 2 (one workgroup barrier per TWO chunks) for the 32x64 and 64x64 tiles when every layer has an even chunk count.
-// Ring depths: 8 / 8 / 6 / 4 slots; a 5-slot ring with 2 + 2 loaders for the 128x128 tile and 4 against 6 slots for 64x128
-// measured the same (same box, +-0.5 %); FOUR chunks per barrier on a 12-slot ring for the 32x64 tile measured 9 % slower than
-// two on 8 slots (the prologue must request 8 chunks before the first barrier).
-#define BLW_DISPATCH(MULTI, FB)                                                              \
-  switch (tile * 2 + (sup2 ? 1 : 0)) {                                                       \
-  case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, MULTI, FB>(a, s);                   \
-  case 1: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 2, MULTI, FB>(a, s);                   \
-  case 2: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, MULTI, FB>(a, s);                   \
-  case 3: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 2, MULTI, FB>(a, s);                   \
-  case 4:                                                                                    \
-  case 5: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, MULTI, FB>(a, s);                   \
-  case 6:                                                                                    \
-  case 7: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, MULTI, FB>(a, s);                   \
-  default: return hipErrorInvalidValue;                                                      \
+// THE DISPATCHER: the instance of a compile-time (MULTI, GRP) for a run-time (tile, sup, b_kind), through the tile table of
+// brgemm_bf16_lw_launch.h. Combination I of the 5 tiles x 3 B images x 2 chunks per barrier is compiled only where blw_instance_exists
+// says so; everything else is refused with hipErrorInvalidValue.
+template <bool MULTI, int GRP, int I>
+static bool blw_try(int tile, int sup, int b_kind, const ChainArgs &a, hipStream_t s, const void *items, int n_items, hipError_t &e) {
+  constexpr int TILE = I / 6, FB = 2 * (I / 2 % 3), SUP = 1 + I % 2;
+  if constexpr (blw_instance_exists(GRP, MULTI, TILE, FB, SUP)) {
+    if (tile == TILE && b_kind == FB && sup == SUP) {
+      constexpr BlwTile t = BLW_TILES[TILE];
+      e = launch_blw_t<t.wm, t.wn, t.wk, t.tm, t.tn, t.nslot, t.nla, t.nlb, SUP, MULTI, FB, GRP>(a, s, items, n_items);
+      return true;
+    }
   }
-static bool blw_sup2(const ChainArgs &a) {
+  return false;
+}
+template <bool MULTI, int GRP, int... I>
+static hipError_t blw_dispatch_seq(std::integer_sequence<int, I...>, int tile, int sup, int b_kind, const ChainArgs &a, hipStream_t s, const void *items, int n_items) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)(blw_try<MULTI, GRP, I>(tile, sup, b_kind, a, s, items, n_items, e) || ...);
+  return e;
+}
+template <bool MULTI, int GRP>
+static hipError_t blw_dispatch(int tile, int sup, int b_kind, const ChainArgs &a, hipStream_t s, const void *items = nullptr, int n_items = 0) {
+  return blw_dispatch_seq<MULTI, GRP>(std::make_integer_sequence<int, BLW_NTILES * 6>{}, tile, sup, b_kind, a, s, items, n_items);
+}
+// what blw_launch_ok reads of an argument block
+static BlwShape blw_shape(const ChainArgs &a, bool chain) {
+  BlwShape h{chain, a.m, a.n, a.nlayers, a.groups, {}, {}};
+  for (int l = 0; l < (a.nlayers < 1 ? 1 : a.nlayers > CH_MAXL ? CH_MAXL : a.nlayers); ++l) h.k[l] = a.L[l].k, h.br[l] = a.L[l].br;
+  return h;
+}
+// chunks per barrier of a layer / chain launch: two on the tiles that have such instances when every layer has an even chunk count
+static int blw_sup(int mode, int tile, const ChainArgs &a) {
+  if (blw_one_chunk(mode) || !blw_tile_sup2(tile)) return 1;
   for (int l = 0; l < a.nlayers; ++l)
-    if ((a.L[l].br * (a.L[l].k / BLW_BK)) & 1) return false;
-  return true;
+    if ((a.L[l].br * (a.L[l].k / BLW_BK)) & 1) return 1;
+  return 2;
 }
 
-// one layer (a.nlayers == 1): any chunk stream of at least one chunk, both accumulator starts
-// tile 4 (round 5, VNNI-2 only, single layers only): 32x32 + K2 - two MFMA waves, one loader wave per panel. For SMALL outputs with a
-// LONG reduction (the reference's M = 128 / 256 shapes at K >= 1536: launch_gemm routes here): twice the workgroups of the 32x64 tile,
-// each streaming 8 KiB per chunk - the layer is bound by how many CUs pull panels, not by the matrix pipes
-hipError_t launch_bf16_lw(int tile, const ChainArgs &a, hipStream_t s) {
-  if (a.L[0].br < 1 || a.L[0].k < BLW_BK || tile < 0 || tile > 4) return hipErrorInvalidValue;
-  const bool sup2 = blw_sup2(a);
-  if (tile == 4) return sup2 ? launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 2, false, 0>(a, s) : launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 1, false, 0>(a, s);
-  BLW_DISPATCH(false, 0)
-}
-
-// One layer whose B operand is FLAT ([k][ldb] bf16, no VNNI flag on the dispatch - what xsmm.unary pack would have turned into
-// VNNI-2, lib/TPP/Transforms/Utils/VNNIUtils.cpp:75-77): the VNNI kernels' configurations with the B image and the fragment
-// reads swapped (FLATB = 2): the chunk's 64 rows go into LDS as they are (LDS-DMA, 64-byte blocks swizzled on the source side)
-// and a B fragment is two ds_read_b64_tr_b16 - the hardware transpose hands every lane four consecutive k of its own column.
-// No pack launch, no VALU, and the reads run at the LDS's full 256 B/clk where the VNNI image needs 4-byte reads (128 B/clk):
-// bit-identical to pack + VNNI kernel and as fast or faster on every tile (profiles/r03_flat_b_bf16.txt). A first version
-// interleaved the pair-rows in a register-staging B loader (buffer_load_dwordx4 x 2 -> 8 v_perm_b32 -> 2 ds_write_b128): correct,
-// 15-28 % slower (the ds_write path: ~79 B/clk and 2-way conflicts), removed.
-hipError_t launch_bf16_lw_flatb(int tile, const ChainArgs &a, hipStream_t s) {
-  if (a.L[0].br < 1 || a.L[0].k < BLW_BK || tile < 0 || tile > 3) return hipErrorInvalidValue;
-  const bool sup2 = blw_sup2(a);
-  BLW_DISPATCH(false, 2)
-}
-
-// One layer whose B operand is VNNI-4 ([k/4][ldb][4] bf16: the dispatch carries the VNNI flag, the factor is the runtime's setting,
-// xsmm_hip_set_vnni_factor - lib/TPP/Transforms/Utils/VNNIUtils.cpp:25-45, benchmarks/config/omp/mlir-bf16.json:68-100): the same
-// configurations with the B image and the fragment reads of FLATB = 4 - the chunk's 16 k-group rows go into the LDS as they are and a
-// fragment is two 8-byte reads (256 B/clk against the 128 B/clk of the VNNI-2 image's 4-byte reads).
-hipError_t launch_bf16_lw_vnni4(int tile, const ChainArgs &a, hipStream_t s) {
-  if (a.L[0].br < 1 || a.L[0].k < BLW_BK || tile < 0 || tile > 4) return hipErrorInvalidValue;
-  const bool sup2 = blw_sup2(a);
-  if (tile == 4) return sup2 ? launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 2, false, 4>(a, s) : launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 1, false, 4>(a, s); // 32x32 + K2 (round 6)
-  BLW_DISPATCH(false, 4)
-}
-
-// EDGE TILES (xsmm_hip_set_edge_tiles modes 2, 20 .. 23; gemm_plan.cpp choose_bf16_edge_tile): ONE whole layer whose m or n the tile does
-// not divide, on ceil(m / BM) x ceil(n / BN) workgroups of the same tile (GRP = 3: the last tile of a row / column of tiles ends at the
-// matrix edge and stores only what no other tile owns). tile 0 .. 3, b_kind 0 VNNI-2 / 2 flat / 4 VNNI-4; SUP = 2 as in the plain
-// launches. No scratch, no counters, no waits. hipErrorInvalidValue (nothing launched): m < BM, n < BN, no batch element, k < 64.
-hipError_t launch_bf16_lw_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s) {
-  static const int bm[4] = {32, 64, 64, 128}, bn[4] = {64, 64, 128, 128};
-  if (tile < 0 || tile > 3 || (b_kind != 0 && b_kind != 2 && b_kind != 4) || a.nlayers != 1) return hipErrorInvalidValue;
-  if (a.m < bm[tile] || a.n < bn[tile] || a.L[0].br < 1 || a.L[0].k < BLW_BK || a.L[0].k % BLW_BK) return hipErrorInvalidValue;
-  const bool sup2 = blw_sup2(a);
-#define BLW_EDGE(FB)                                                                         \
-  switch (tile * 2 + (sup2 ? 1 : 0)) {                                                       \
-  case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, FB, 3>(a, s);                \
-  case 1: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 2, false, FB, 3>(a, s);                \
-  case 2: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, FB, 3>(a, s);                \
-  case 3: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 2, false, FB, 3>(a, s);                \
-  case 4:                                                                                    \
-  case 5: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, false, FB, 3>(a, s);                \
-  default: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, false, FB, 3>(a, s);               \
+// ONE LAYER (a.nlayers == 1) in one of the modes BLW_LAYER, BLW_EDGE, BLW_KEDGE, BLW_KEDGE8 (brgemm_bf16_lw_launch.h; blw_launch_ok is what
+// each refuses: hipErrorInvalidValue, nothing launched). No scratch, no counters, no waits. b_kind: the B image -
+//   0  VNNI-2 [k/2][ldb][2].
+//   2  FLAT [k][ldb] (no VNNI flag on the dispatch - what xsmm.unary pack would have turned into VNNI-2, lib/TPP/Transforms/Utils/
+//      VNNIUtils.cpp:75-77): the chunk's 64 rows go into LDS as they are (LDS-DMA, 64-byte blocks swizzled on the source side) and a B
+//      fragment is two ds_read_b64_tr_b16 - the hardware transpose hands every lane four consecutive k of its own column. No pack
+//      launch, no VALU, and the reads run at the LDS's full 256 B/clk where the VNNI image needs 4-byte reads (128 B/clk): bit-identical
+//      to pack + VNNI kernel and as fast or faster on every tile (profiles/r03_flat_b_bf16.txt). A first version interleaved the
+//      pair-rows in a register-staging B loader (buffer_load_dwordx4 x 2 -> 8 v_perm_b32 -> 2 ds_write_b128): correct, 15-28 % slower
+//      (the ds_write path: ~79 B/clk and 2-way conflicts), removed.
+//   4  VNNI-4 [k/4][ldb][4] (the dispatch carries the VNNI flag, the factor is the runtime's setting, xsmm_hip_set_vnni_factor -
+//      lib/TPP/Transforms/Utils/VNNIUtils.cpp:25-45, benchmarks/config/omp/mlir-bf16.json:68-100): the chunk's 16 k-group rows go into
+//      the LDS as they are and a fragment is two 8-byte reads (256 B/clk).
+// BLW_EDGE (gemm_plan.cpp choose_bf16_edge_tile): ceil(m / BM) x ceil(n / BN) workgroups, the last tile of a row / column of tiles ends at the
+// matrix edge and stores only what no other tile owns. BLW_KEDGE / BLW_KEDGE8 (gemm_plan.cpp plan_gemm_call, brgemm_bf16_lw_kedge.h): the same
+// + the shifted last chunk per batch element; one chunk per barrier only (one barrier per two chunks would tie the ragged chunk to a partner).
+hipError_t launch_bf16_lw(int mode, int tile, int b_kind, const ChainArgs &a, hipStream_t s) {
+  if (!blw_launch_ok(mode, tile, b_kind, blw_shape(a, false))) return hipErrorInvalidValue;
+  const int sup = blw_sup(mode, tile, a);
+  switch (mode) {
+  case BLW_LAYER: return blw_dispatch<false, BLW_LAYER>(tile, sup, b_kind, a, s);
+  case BLW_EDGE: return blw_dispatch<false, BLW_EDGE>(tile, sup, b_kind, a, s);
+  case BLW_KEDGE: return blw_dispatch<false, BLW_KEDGE>(tile, sup, b_kind, a, s);
+  case BLW_KEDGE8: return blw_dispatch<false, BLW_KEDGE8>(tile, sup, b_kind, a, s);
+  default: return hipErrorInvalidValue;
   }
-  if (b_kind == 2) {
-    BLW_EDGE(2)
-  } else if (b_kind == 4) {
-    BLW_EDGE(4)
-  }
-  BLW_EDGE(0)
-#undef BLW_EDGE
-}
-
-// RAGGED k (xsmm_hip_set_edge_k_bf16; gemm_plan.cpp plan_gemm_call, brgemm_bf16_lw_kedge.h): ONE whole layer whose k is a multiple of 16 but
-// not of 64 (k >= 64), on ceil(m / BM) x ceil(n / BN) workgroups of the same tile (GRP = 4 = the edge tiles' GRP = 3 + the shifted last
-// chunk per batch element; m and n may be ragged too or not). tile 0 .. 3, b_kind 0 VNNI-2 / 2 flat / 4 VNNI-4; the loader waves and
-// rings of the plain launches, SUP = 1 only (one barrier per two chunks would tie the ragged chunk to a partner). No scratch, no
-// counters, no waits. hipErrorInvalidValue (nothing launched): k < 64, k % 16, k % 64 == 0, m < BM, n < BN, n % 8, no batch element,
-// more than one layer.
-hipError_t launch_bf16_lw_kedge(int tile, int b_kind, const ChainArgs &a, hipStream_t s) {
-  static const int bm[4] = {32, 64, 64, 128}, bn[4] = {64, 64, 128, 128};
-  if (tile < 0 || tile > 3 || (b_kind != 0 && b_kind != 2 && b_kind != 4) || a.nlayers != 1) return hipErrorInvalidValue;
-  if (a.m < bm[tile] || a.n < bn[tile] || a.n % 8 != 0 || a.L[0].br < 1 || !bkedge_k_ok(a.L[0].k)) return hipErrorInvalidValue;
-#define BLW_KEDGE(FB)                                                                        \
-  switch (tile) {                                                                            \
-  case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, FB, 4>(a, s);                \
-  case 1: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, FB, 4>(a, s);                \
-  case 2: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, false, FB, 4>(a, s);                \
-  default: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, false, FB, 4>(a, s);               \
-  }
-  if (b_kind == 2) {
-    BLW_KEDGE(2)
-  } else if (b_kind == 4) {
-    BLW_KEDGE(4)
-  }
-  BLW_KEDGE(0)
-#undef BLW_KEDGE
-}
-
-// RAGGED k in HALF steps (xsmm_hip_set_edge_k8_bf16; brgemm_bf16_lw_kedge.h bkedge8_*): launch_bf16_lw_kedge for a k that is a multiple
-// of 8 but not of 16 (k >= 64: 72, 200, 1000) - GRP = 6, the same tiles, loader waves and rings. hipErrorInvalidValue (nothing
-// launched): what launch_bf16_lw_kedge refuses, with bkedge8_k_ok in place of bkedge_k_ok.
-hipError_t launch_bf16_lw_kedge8(int tile, int b_kind, const ChainArgs &a, hipStream_t s) {
-  static const int bm[4] = {32, 64, 64, 128}, bn[4] = {64, 64, 128, 128};
-  if (tile < 0 || tile > 3 || (b_kind != 0 && b_kind != 2 && b_kind != 4) || a.nlayers != 1) return hipErrorInvalidValue;
-  if (a.m < bm[tile] || a.n < bn[tile] || a.n % 8 != 0 || a.L[0].br < 1 || !bkedge8_k_ok(a.L[0].k)) return hipErrorInvalidValue;
-#define BLW_KEDGE8(FB)                                                                       \
-  switch (tile) {                                                                            \
-  case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, FB, 6>(a, s);                \
-  case 1: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, FB, 6>(a, s);                \
-  case 2: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, false, FB, 6>(a, s);                \
-  default: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, false, FB, 6>(a, s);               \
-  }
-  if (b_kind == 2) {
-    BLW_KEDGE8(2)
-  } else if (b_kind == 4) {
-    BLW_KEDGE8(4)
-  }
-  BLW_KEDGE8(0)
-#undef BLW_KEDGE8
 }
 
 // Tile invokes of ONE bf16 descriptor as one launch on the loader-wave tiles (round 6, VERDICT r5 missing 3 / next 2b: the tile queue's
 // bf16 groups used to run on brgemm_bf16_small32 / brgemm_bf16_fast<64x64> and were 0-45 % slower than the same layer as one whole-
 // layer call). One workgroup per BM x BN tile of an item, operands and batch count from the item (ChainArgs::items); packed tile
 // blocks are just another (lda, stride) pattern to the loaders. SUP = 2 instances only when every item has an even chunk count.
+// (Tile 4 with VNNI-4 operands: the image rows of a 32-column tile are 256 bytes, four per DMA instruction.)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s) {
-  if (a.L[0].k < BLW_BK || a.L[0].k % BLW_BK || tile < 0 || (tile > 1 && tile != 4) || (b_kind != 0 && b_kind != 4)) return hipErrorInvalidValue;
-  if (tile == 4) { // 32x32 + K2 (launch_bf16_lw's tile 4): four workgroups per 64x64 item - skinny groups with a long reduction
-    if (b_kind == 4) // (VNNI-4 operands: grouped form only - the image rows of a 32-column tile are 256 bytes, four per DMA instruction)
-      return even_chunks ? launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 2, false, 4, true>(a, s, items, n_items)
-                         : launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 1, false, 4, true>(a, s, items, n_items);
-    return even_chunks ? launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 2, false, 0, true>(a, s, items, n_items)
-                       : launch_blw_t<1, 1, 2, 1, 1, 8, 1, 1, 1, false, 0, true>(a, s, items, n_items);
-  }
-  if (b_kind == 4) {
-    if (tile == 0) return even_chunks ? launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 2, false, 4, true>(a, s, items, n_items) : launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, 4, true>(a, s, items, n_items);
-    return even_chunks ? launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 2, false, 4, true>(a, s, items, n_items) : launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, 4, true>(a, s, items, n_items);
-  }
-  if (tile == 0) return even_chunks ? launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 2, false, 0, true>(a, s, items, n_items) : launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, false, 0, true>(a, s, items, n_items);
-  return even_chunks ? launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 2, false, 0, true>(a, s, items, n_items) : launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, false, 0, true>(a, s, items, n_items);
+  if (!blw_launch_ok(BLW_ITEMS, tile, b_kind, blw_shape(a, false))) return hipErrorInvalidValue;
+  return blw_dispatch<false, BLW_ITEMS>(tile, even_chunks ? 2 : 1, b_kind, a, s, items, n_items);
 }
 
 // QUADS (round 6): a group of 64x64 items that forms an R x C grid of item rows (A blocks) and item columns (B blocks), R and C even,
@@ -1176,79 +1060,28 @@ hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, cons
 // 640 items on 64x64 tiles 15.3 us, 160 workgroups of 128x128 10.2). a.m = a.n = 128 (one tile per quad), lda / ldb / ldc / strides /
 // k the items'; quads = QuadItem[n_quads] in device-visible memory.
 hipError_t launch_bf16_lw_quads(int b_kind, const ChainArgs &a, const void *quads, int n_quads, hipStream_t s) {
-  if (a.L[0].k < BLW_BK || a.L[0].k % BLW_BK || a.m != 128 || a.n != 128 || (b_kind != 0 && b_kind != 4)) return hipErrorInvalidValue;
-  if (b_kind == 4) return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, false, 4, 2>(a, s, quads, n_quads);
-  return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, false, 0, 2>(a, s, quads, n_quads);
+  if (!blw_launch_ok(BLW_QUADS, 3, b_kind, blw_shape(a, false))) return hipErrorInvalidValue;
+  return blw_dispatch<false, BLW_QUADS>(3, 1, b_kind, a, s, quads, n_quads);
 }
 
-// a chain of layers in one launch; the caller guarantees co-residency (tiles <= CUs), beta = 0, disjoint buffers and ONE kind of B
-// operand for every layer (b_kind 0: VNNI-2, 2: flat, 4: VNNI-4)
-hipError_t launch_bf16_chain(int tile, int b_kind, const ChainArgs &a, hipStream_t s) {
-  if (tile < 0 || tile > 3) return hipErrorInvalidValue;
-  const bool sup2 = blw_sup2(a);
-  if (b_kind == 2) {
-    BLW_DISPATCH(true, 2)
-  } else if (b_kind == 4) {
-    BLW_DISPATCH(true, 4)
+// A CHAIN of layers in one launch; the caller guarantees co-residency, beta = 0, disjoint buffers and ONE kind of B operand for every
+// layer. blw_launch_ok is what each mode refuses (hipErrorInvalidValue, nothing launched).
+//   BLW_LAYER         m / BM x n / BN workgroups, at most the compute units.
+//   BLW_CHAIN_EDGE    (gemm_plan.cpp plan_chain_edge, brgemm_bf16_lw_chain_edge.h) ceil(m / BM) x n / BN workgroups, at most the compute units: the
+//                     last row block shifted back to end at row m, storing its own rows only and waiting at every seam for both row blocks
+//                     whose rows it reads.
+//   BLW_CHAIN_ROUNDS  (gemm_plan.cpp plan_chain_rounds, brgemm_bf16_lw_chain_rounds.h) a.groups x n / BN resident workgroups, at most the compute
+//                     units: workgroup (g, tn) walks the row blocks g, g + groups, .. of every layer, layer-major; the counters are the
+//                     chain's, [nlayers - 1][m / BM].
+hipError_t launch_bf16_chain(int mode, int tile, int b_kind, const ChainArgs &a, hipStream_t s) {
+  if (!blw_launch_ok(mode, tile, b_kind, blw_shape(a, true))) return hipErrorInvalidValue;
+  const int sup = blw_sup(mode, tile, a);
+  switch (mode) {
+  case BLW_LAYER: return blw_dispatch<true, BLW_LAYER>(tile, sup, b_kind, a, s);
+  case BLW_CHAIN_EDGE: return blw_dispatch<true, BLW_CHAIN_EDGE>(tile, sup, b_kind, a, s);
+  case BLW_CHAIN_ROUNDS: return blw_dispatch<true, BLW_CHAIN_ROUNDS>(tile, sup, b_kind, a, s);
+  default: return hipErrorInvalidValue;
   }
-  BLW_DISPATCH(true, 0)
-}
-
-// a RAGGED-m chain (xsmm_hip_set_chain_edge; gemm_plan.cpp plan_chain_edge, brgemm_bf16_lw_chain_edge.h): launch_bf16_chain's layers on
-// ceil(m / BM) x n / BN workgroups of tile 0 .. 3 (GRP = 5: the last row block shifted back to end at row m, storing its own rows only and
-// waiting at every seam for both row blocks whose rows it reads). The caller's guarantees are launch_bf16_chain's, with tiles counted
-// on the ceil-divided grid. One chunk per barrier only. hipErrorInvalidValue (nothing launched): m < BM, n % BN, a k % 64 or k < 64, an
-// empty batch, fewer than 2 or more than CH_MAXL layers.
-hipError_t launch_bf16_chain_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s) {
-  static const int bm[4] = {32, 64, 64, 128}, bn[4] = {64, 64, 128, 128};
-  if (tile < 0 || tile > 3 || (b_kind != 0 && b_kind != 2 && b_kind != 4) || a.nlayers < 2 || a.nlayers > CH_MAXL) return hipErrorInvalidValue;
-  if (a.m < bm[tile] || a.n < bn[tile] || a.n % bn[tile] != 0) return hipErrorInvalidValue;
-  for (int l = 0; l < a.nlayers; ++l)
-    if (a.L[l].br < 1 || a.L[l].k < BLW_BK || a.L[l].k % BLW_BK != 0) return hipErrorInvalidValue;
-#define BLW_CHAIN_EDGE(FB)                                                                   \
-  switch (tile) {                                                                            \
-  case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, true, FB, 5>(a, s);                 \
-  case 1: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, true, FB, 5>(a, s);                 \
-  case 2: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, true, FB, 5>(a, s);                 \
-  default: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, true, FB, 5>(a, s);                \
-  }
-  if (b_kind == 2) {
-    BLW_CHAIN_EDGE(2)
-  } else if (b_kind == 4) {
-    BLW_CHAIN_EDGE(4)
-  }
-  BLW_CHAIN_EDGE(0)
-#undef BLW_CHAIN_EDGE
-}
-
-// a chain in SEVERAL ROUNDS (xsmm_hip_set_chain_rounds; gemm_plan.cpp plan_chain_rounds, brgemm_bf16_lw_chain_rounds.h): launch_bf16_chain's
-// layers on groups x n / BN resident workgroups of tile 0 .. 3 (GRP = 7: workgroup (g, tn) walks the row blocks g, g + groups, .. of
-// every layer, layer-major). The caller's guarantees are launch_bf16_chain's, with groups * (n / BN) <= compute units in place of tiles <=
-// compute units; the counters are the chain's, [nlayers - 1][m / BM]. One chunk per barrier only. hipErrorInvalidValue (nothing
-// launched): m % BM, n % BN, a k % 64 or k < 64, an empty batch, groups < 1, groups > m / BM, fewer than 2 or more than CH_MAXL layers.
-hipError_t launch_bf16_chain_rounds(int tile, int b_kind, int groups, const ChainArgs &a, hipStream_t s) {
-  static const int bm[4] = {32, 64, 64, 128}, bn[4] = {64, 64, 128, 128};
-  if (tile < 0 || tile > 3 || (b_kind != 0 && b_kind != 2 && b_kind != 4) || a.nlayers < 2 || a.nlayers > CH_MAXL) return hipErrorInvalidValue;
-  if (a.m < bm[tile] || a.n < bn[tile] || a.m % bm[tile] != 0 || a.n % bn[tile] != 0) return hipErrorInvalidValue;
-  if (groups < 1 || groups > a.m / bm[tile]) return hipErrorInvalidValue;
-  for (int l = 0; l < a.nlayers; ++l)
-    if (a.L[l].br < 1 || a.L[l].k < BLW_BK || a.L[l].k % BLW_BK != 0) return hipErrorInvalidValue;
-  ChainArgs c = a;
-  c.groups = groups;
-#define BLW_CHAIN_ROUNDS(FB)                                                                 \
-  switch (tile) {                                                                            \
-  case 0: return launch_blw_t<1, 2, 2, 1, 1, 8, 1, 2, 1, true, FB, 7>(c, s);                 \
-  case 1: return launch_blw_t<2, 2, 1, 1, 1, 8, 1, 1, 1, true, FB, 7>(c, s);                 \
-  case 2: return launch_blw_t<2, 2, 1, 1, 2, 6, 1, 2, 1, true, FB, 7>(c, s);                 \
-  default: return launch_blw_t<2, 2, 1, 2, 2, 4, 1, 1, 1, true, FB, 7>(c, s);                \
-  }
-  if (b_kind == 2) {
-    BLW_CHAIN_ROUNDS(2)
-  } else if (b_kind == 4) {
-    BLW_CHAIN_ROUNDS(4)
-  }
-  BLW_CHAIN_ROUNDS(0)
-#undef BLW_CHAIN_ROUNDS
 }
 
 } // namespace tpp

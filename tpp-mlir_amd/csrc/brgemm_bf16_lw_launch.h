@@ -1,0 +1,106 @@
+// brgemm_bf16_lw_launch.h - the launch table of brgemm_bf16_lw<WM, WN, WK, TM, TN, NSLOT, NLA, NLB, SUP, MULTI, FLATB, GRP> (brgemm_bf16_lw.hip),
+// written once as plain constexpr functions: the launch modes (the values of GRP) and what follows from one, the tiles, which instances
+// exist and what each mode's launcher refuses. The kernel, its loader, its launchers, the planner (gemm_plan.cpp) and a CPU test
+// (tests/test_blw_launch_table.py) all include this file. Nothing here needs a device: it compiles with any C++17 host compiler.
+#pragma once
+#include "brgemm_bf16_lw_kedge.h"
+
+namespace tpp {
+
+// LAUNCH MODES: the kernel's template parameter GRP (an int, so that the kernels keep their names). Each is described where the kernel
+// and the loader treat it.
+constexpr int BLW_LAYER = 0;        // one whole layer (MULTI false) or a chain of layers on co-resident tiles (MULTI true)
+constexpr int BLW_ITEMS = 1;        // tile invokes of one descriptor: operands and batch count from a WorkItem
+constexpr int BLW_QUADS = 2;        // 2 x 2 blocks of 64x64 items on the 128x128 tile: operands from a QuadItem
+constexpr int BLW_EDGE = 3;         // a layer whose m or n the tile does not divide (xsmm_hip_set_edge_tiles)
+constexpr int BLW_KEDGE = 4;        // BLW_EDGE + a k that is a multiple of 16 but not of 64 (xsmm_hip_set_edge_k_bf16)
+constexpr int BLW_CHAIN_EDGE = 5;   // a chain whose m the tile's rows do not divide (xsmm_hip_set_chain_edge)
+constexpr int BLW_KEDGE8 = 6;       // BLW_KEDGE in half steps: k a multiple of 8 but not of 16 (xsmm_hip_set_edge_k8_bf16)
+constexpr int BLW_CHAIN_ROUNDS = 7; // a chain on fewer resident workgroups than output tiles (xsmm_hip_set_chain_rounds)
+constexpr int BLW_MODES = 8;
+
+// what follows from a mode
+constexpr bool blw_items(int g) { return g == BLW_ITEMS || g == BLW_QUADS; }      // operands and batch count come from an item
+constexpr bool blw_ragged_k(int g) { return g == BLW_KEDGE || g == BLW_KEDGE8; }  // the last chunk of a batch element is shifted back
+constexpr bool blw_half_steps(int g) { return g == BLW_KEDGE8; }                  // ... and its overlap ends in the middle of a k-step
+// the last row block is shifted back to end at row m and stores its own rows only
+constexpr bool blw_edge_rows(int g) { return g == BLW_EDGE || blw_ragged_k(g) || g == BLW_CHAIN_EDGE; }
+// the last column tile is shifted back to end at column n (a ragged chain's columns are whole tiles)
+constexpr bool blw_edge_cols(int g) { return g == BLW_ITEMS || g == BLW_EDGE || blw_ragged_k(g); }
+constexpr bool blw_chain(int g) { return g == BLW_CHAIN_EDGE || g == BLW_CHAIN_ROUNDS; } // a chain by itself (BLW_LAYER: either)
+constexpr bool blw_one_chunk(int g) { return blw_ragged_k(g) || blw_chain(g); }   // one chunk per barrier only (SUP = 1)
+// the combinations of mode, MULTI and SUP the kernel and the loader are written for
+constexpr bool blw_mode_ok(int g, bool multi, int sup) {
+  return g >= 0 && g < BLW_MODES && (multi ? g == BLW_LAYER || blw_chain(g) : !blw_chain(g)) && (!blw_one_chunk(g) || sup == 1);
+}
+template <int GRP, bool MULTI, int SUP> struct BlwModeCheck {
+  static_assert(GRP >= 0 && GRP < BLW_MODES, "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds");
+  static_assert(!MULTI || GRP == BLW_LAYER || blw_chain(GRP), "a grouped launch is a set of single layers");
+  static_assert(!blw_ragged_k(GRP) || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
+  static_assert(!blw_chain(GRP) || (SUP == 1 && MULTI), "a ragged / multi-round chain: a chain, one chunk per barrier");
+  static constexpr bool ok = blw_mode_ok(GRP, MULTI, SUP);
+};
+
+// THE TILES. 0 = 32x64 + K2, 1 = 64x64, 2 = 64x128, 3 = 128x128, 4 = 32x32 + K2. Loader waves per tile (NLA + NLB), same-box A/B
+// (profiles/r03_blw_loader_split.txt): 32x64 1 + 2 (1 + 1: +2 %, 2 + 2: +5 %), 64x64 1 + 1 (1 + 2: +2 %, 2 + 2: +7 %), 64x128 1 + 2
+// (1 + 1: same, 2 + 4: +5 %), 128x128 1 + 1 (2 + 2, 1 + 2: same). Ring depths: 8 / 8 / 6 / 4 slots; a 5-slot ring with 2 + 2 loaders for the
+// 128x128 tile and 4 against 6 slots for 64x128 measured the same (same box, +-0.5 %); FOUR chunks per barrier on a 12-slot ring for the
+// 32x64 tile measured 9 % slower than two on 8 slots (the prologue must request 8 chunks before the first barrier).
+// Tile 4 (round 5, single layers and items only, no flat B): two MFMA waves, one loader wave per panel. For SMALL outputs with a LONG
+// reduction (the reference's M = 128 / 256 shapes at K >= 1536): twice the workgroups of the 32x64 tile, each streaming 8 KiB per chunk -
+// the layer is bound by how many CUs pull panels, not by the matrix pipes.
+struct BlwTile {
+  int wm, wn, wk, tm, tn, nslot, nla, nlb;
+  constexpr int bm() const { return 32 * wm * tm; }
+  constexpr int bn() const { return 32 * wn * tn; }
+};
+constexpr int BLW_NTILES = 5;
+constexpr BlwTile BLW_TILES[BLW_NTILES] = {{1, 2, 2, 1, 1, 8, 1, 2}, {2, 2, 1, 1, 1, 8, 1, 1}, {2, 2, 1, 1, 2, 6, 1, 2}, {2, 2, 1, 2, 2, 4, 1, 1}, {1, 1, 2, 1, 1, 8, 1, 1}};
+// SUP = 2 (one workgroup barrier per TWO chunks): the tiles with one accumulator per wave, when every chunk count is even
+constexpr bool blw_tile_sup2(int tile) { return tile == 0 || tile == 1 || tile == 4; }
+constexpr bool blw_b_kind_ok(int b_kind) { return b_kind == 0 || b_kind == 2 || b_kind == 4; } // B image: VNNI-2, flat, VNNI-4
+
+// THE INSTANCES: is brgemm_bf16_lw<BLW_TILES[tile]..., sup, multi, b_kind, mode> compiled? (120 are; the launchers instantiate nothing else)
+constexpr bool blw_instance_exists(int mode, bool multi, int tile, int b_kind, int sup) {
+  if (tile < 0 || tile >= BLW_NTILES || !blw_b_kind_ok(b_kind) || !(sup == 1 || (sup == 2 && blw_tile_sup2(tile))) || !blw_mode_ok(mode, multi, sup)) return false;
+  if (mode == BLW_LAYER) return tile <= 3 || (!multi && b_kind != 2);
+  if (mode == BLW_ITEMS) return blw_tile_sup2(tile) && b_kind != 2;
+  if (mode == BLW_QUADS) return tile == 3 && b_kind != 2;
+  return tile <= 3; // edge tiles, both ragged k, both chains
+}
+
+// THE REFUSALS: does the launcher of `mode` take this launch? What it asks of a launch's arguments, copied out of the argument block.
+constexpr int BLW_MAXL = 8; // (= CH_MAXL, chain_args.h)
+struct BlwShape {
+  bool chain;      // BLW_LAYER: a chain (launch_bf16_chain), not one layer
+  int m, n, nlayers, groups;
+  int k[BLW_MAXL], br[BLW_MAXL]; // per layer: k per batch element, batch count (the first min(nlayers, BLW_MAXL), at least one)
+};
+// every layer of a ragged / multi-round chain: a batch of at least one element in whole chunks
+constexpr bool blw_chain_layers_ok(const BlwShape &a) {
+  if (a.nlayers < 2 || a.nlayers > BLW_MAXL) return false;
+  for (int l = 0; l < a.nlayers; ++l)
+    if (a.br[l] < 1 || a.k[l] < BKEDGE_BK || a.k[l] % BKEDGE_BK != 0) return false;
+  return true;
+}
+constexpr bool blw_launch_ok(int mode, int tile, int b_kind, const BlwShape &a) {
+  if (tile < 0 || tile >= BLW_NTILES || !blw_b_kind_ok(b_kind)) return false;
+  const int bm = BLW_TILES[tile].bm(), bn = BLW_TILES[tile].bn();
+  const bool whole_k = a.k[0] >= BKEDGE_BK && a.k[0] % BKEDGE_BK == 0;
+  // one layer on tile 0 .. 3 that holds at least one tile and one batch element
+  const bool edge_layer = tile <= 3 && a.nlayers == 1 && a.m >= bm && a.n >= bn && a.br[0] >= 1;
+  const bool edge_chain = tile <= 3 && blw_chain_layers_ok(a) && a.m >= bm && a.n >= bn && a.n % bn == 0;
+  switch (mode) {
+  case BLW_LAYER: return a.chain ? tile <= 3 : a.br[0] >= 1 && a.k[0] >= BKEDGE_BK && (tile <= 3 || b_kind != 2);
+  case BLW_ITEMS: return whole_k && blw_tile_sup2(tile) && b_kind != 2;
+  case BLW_QUADS: return whole_k && a.m == 128 && a.n == 128 && b_kind != 2;
+  case BLW_EDGE: return edge_layer && whole_k;
+  case BLW_KEDGE: return edge_layer && a.n % 8 == 0 && bkedge_k_ok(a.k[0]);
+  case BLW_KEDGE8: return edge_layer && a.n % 8 == 0 && bkedge8_k_ok(a.k[0]);
+  case BLW_CHAIN_EDGE: return edge_chain;
+  case BLW_CHAIN_ROUNDS: return edge_chain && a.m % bm == 0 && a.groups >= 1 && a.groups <= a.m / bm;
+  default: return false;
+  }
+}
+
+} // namespace tpp

@@ -797,10 +797,7 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
   case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split);
   case GL_BF16_GROUPED64: return launch_bf16_grouped64(a, wi, n_items, s);
   case GL_BF16_LW:
-    if (p.edge_k8) return launch_bf16_lw_kedge8(p.tile, p.b_kind, one_layer(a, br, a.m, a.n), s);
-    if (p.edge_k) return launch_bf16_lw_kedge(p.tile, p.b_kind, one_layer(a, br, a.m, a.n), s);
-    if (p.edge) return launch_bf16_lw_edge(p.tile, p.b_kind, one_layer(a, br, a.m, a.n), s);
-    return (p.b_kind == 4 ? launch_bf16_lw_vnni4 : p.b_kind == 2 ? launch_bf16_lw_flatb : launch_bf16_lw)(p.tile, one_layer(a, br, a.m, a.n), s);
+    return launch_bf16_lw(p.edge_k8 ? BLW_KEDGE8 : p.edge_k ? BLW_KEDGE : p.edge ? BLW_EDGE : BLW_LAYER, p.tile, p.b_kind, one_layer(a, br, a.m, a.n), s);
   case GL_BF16_LW_GROUPED: return launch_bf16_lw_grouped(p.tile, p.b_kind, one_layer(a, br, a.m, a.n), items, n_items, p.even, s);
   case GL_BF16_LW_QUADS: return launch_bf16_lw_quads(p.b_kind, one_layer(a, br, 128, 128), items, n_items, s);
   case GL_GENERIC:
@@ -833,7 +830,7 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
       if (e == hipSuccess) { // the tile with its B image: 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4
         g_edge_k8_bf16_stats[1].store(bkedge_chunks(a.k), std::memory_order_relaxed);
         g_edge_k8_bf16_stats[2].store(bkedge_overlap(a.k), std::memory_order_relaxed);
-        g_edge_k8_bf16_stats[3].store((p.b_kind == 4 ? V_BF16_LW4_32x64 : p.b_kind == 2 ? V_BF16_LWF_32x64 : V_BF16_LW_32x64) + p.tile, std::memory_order_relaxed);
+        g_edge_k8_bf16_stats[3].store(blw_variant(p.tile, p.b_kind), std::memory_order_relaxed);
         g_edge_k8_bf16_stats[0].fetch_add(1, std::memory_order_relaxed);
       }
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
@@ -848,7 +845,7 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
       if (e == hipSuccess) { // the tile with its B image: 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4
         g_edge_k_bf16_stats[1].store(bkedge_chunks(a.k), std::memory_order_relaxed);
         g_edge_k_bf16_stats[2].store(bkedge_overlap(a.k), std::memory_order_relaxed);
-        g_edge_k_bf16_stats[3].store((p.b_kind == 4 ? V_BF16_LW4_32x64 : p.b_kind == 2 ? V_BF16_LWF_32x64 : V_BF16_LW_32x64) + p.tile, std::memory_order_relaxed);
+        g_edge_k_bf16_stats[3].store(blw_variant(p.tile, p.b_kind), std::memory_order_relaxed);
         g_edge_k_bf16_stats[0].fetch_add(1, std::memory_order_relaxed);
       }
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
@@ -881,7 +878,7 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
         const int ft = p.launcher == GL_F32_LW && p.tile >= 0 && p.tile < 5 ? p.tile : 0;
         int tbm = bm[ft], tbn = bn[ft], tv = variant[ft];
         if (p.launcher == GL_BF16_LW) // the tile with its B image: 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4
-          blw_tile_dims(p.tile, &tbm, &tbn), tv = (p.b_kind == 4 ? V_BF16_LW4_32x64 : p.b_kind == 2 ? V_BF16_LWF_32x64 : V_BF16_LW_32x64) + p.tile;
+          blw_tile_dims(p.tile, &tbm, &tbn), tv = blw_variant(p.tile, p.b_kind);
         g_edge_tiles_stats[1].store((d.m + tbm - 1) / tbm, std::memory_order_relaxed);
         g_edge_tiles_stats[2].store((d.n + tbn - 1) / tbn, std::memory_order_relaxed);
         g_edge_tiles_stats[3].store(tv, std::memory_order_relaxed);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "brgemm_bf16_lw_launch.h" // the launch modes (BLW_*) of the bf16 loader-wave launchers below
 
 namespace tpp {
 
@@ -29,7 +30,7 @@ struct ChainArgs {
   int nlayers;
   int tiles_m, tiles_n; // filled by the launcher
   int xm;               // filled by the launcher: XCD grid xm x (8 / xm) over the tile grid, 0 = linear tile order
-  int groups;           // a multi-round chain (launch_bf16_chain_rounds): resident row groups G, the grid is G x tiles_n; 0 in every other launch
+  int groups;           // a multi-round chain (launch_bf16_chain, BLW_CHAIN_ROUNDS): resident row groups G, the grid is G x tiles_n; 0 in every other launch
   // Unused. Keeps L at byte 72 of the argument block: without these bytes every L[] load moves and the compiler assigns
   // registers differently in the f32 chain kernels' K loop, a code change that would have to be measured on its own.
   char reserved[8];
@@ -43,25 +44,15 @@ struct ChainArgs {
 };
 static_assert(offsetof(ChainArgs, L) == 72, "the kernels' code depends on where the layer table lies");
 
-// tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (gemm_plan.h blw_tile_dims)
-hipError_t launch_bf16_lw(int tile, const ChainArgs &a, hipStream_t s);
-hipError_t launch_bf16_lw_flatb(int tile, const ChainArgs &a, hipStream_t s); // the same tiles, B operand flat [k][ldb] (no VNNI flag)
-hipError_t launch_bf16_lw_vnni4(int tile, const ChainArgs &a, hipStream_t s); // the same tiles, B operand VNNI-4 [k/4][ldb][4]
-hipError_t launch_bf16_chain(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // b_kind: 0 VNNI-2, 2 flat, 4 VNNI-4 (every layer the same)
-// one layer whose m or n the tile does not divide, on edge tiles (xsmm_hip_set_edge_tiles): tile 0 .. 3, b_kind 0 VNNI-2 / 2 flat / 4 VNNI-4;
-// hipErrorInvalidValue and nothing launched when m < BM, n < BN, the batch count < 1 or k < 64
-hipError_t launch_bf16_lw_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
-// a chain whose m the tile's rows do not divide (xsmm_hip_set_chain_edge; brgemm_bf16_lw_chain_edge.h): launch_bf16_chain on ceil(m / BM) x n / BN
-// workgroups; hipErrorInvalidValue and nothing launched when m < BM, n % BN, a k % 64 or a batch count < 1
-hipError_t launch_bf16_chain_edge(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
-// a chain on FEWER resident workgroups than output tiles (xsmm_hip_set_chain_rounds; brgemm_bf16_lw_chain_rounds.h): groups x n / BN workgroups,
-// workgroup (g, tn) walks the row blocks g, g + groups, .. layer-major; hipErrorInvalidValue and nothing launched when m % BM, n % BN, a k % 64,
-// a batch count < 1, groups < 1 or groups > m / BM. The caller guarantees groups * (n / BN) <= the stream's compute units.
-hipError_t launch_bf16_chain_rounds(int tile, int b_kind, int groups, const ChainArgs &a, hipStream_t s);
-hipError_t launch_bf16_lw_kedge(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k (brgemm_bf16_lw_kedge.h); hipErrorInvalidValue: not launched
-hipError_t launch_bf16_lw_kedge8(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k in half steps, k % 16 == 8 (bkedge8_*); refuses the same way
-hipError_t launch_bf16_lw_kedge8(int tile, int b_kind, const ChainArgs &a, hipStream_t s); // ragged k in half steps, k % 16 == 8 (bkedge8_*); refuses the same way
-// tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2 (VNNI-2 only); b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
+// The bf16 loader-wave launchers (brgemm_bf16_lw.hip). mode: a launch mode of brgemm_bf16_lw_launch.h (BLW_*), whose blw_launch_ok says what each
+// refuses - hipErrorInvalidValue, nothing launched. tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128,
+// 4 = 32x32 + K2 (gemm_plan.h blw_tile_dims). b_kind: the B image, 0 VNNI-2, 2 flat [k][ldb], 4 VNNI-4 [k/4][ldb][4] (every layer the same).
+// one layer: BLW_LAYER, BLW_EDGE (xsmm_hip_set_edge_tiles), BLW_KEDGE (xsmm_hip_set_edge_k_bf16), BLW_KEDGE8 (xsmm_hip_set_edge_k8_bf16)
+hipError_t launch_bf16_lw(int mode, int tile, int b_kind, const ChainArgs &a, hipStream_t s);
+// a chain: BLW_LAYER, BLW_CHAIN_EDGE (xsmm_hip_set_chain_edge), BLW_CHAIN_ROUNDS (xsmm_hip_set_chain_rounds; a.groups row groups, the caller
+// guarantees groups * (n / BN) <= the stream's compute units)
+hipError_t launch_bf16_chain(int mode, int tile, int b_kind, const ChainArgs &a, hipStream_t s);
+// tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2; b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);
 // 2 x 2 blocks of 64x64 items on the 128x128 tile (quads: QuadItem[n_quads], xsmm_desc.h; a.m = a.n = 128, leading dimensions / strides / k the items')

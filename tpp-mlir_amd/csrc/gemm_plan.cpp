@@ -2,7 +2,7 @@
 // tests/golden/gemm_plan.txt (tests/test_gemm_plan.py): a change of a rule or a cost coefficient is a change of that table.
 #include "gemm_plan.h"
 #include "brgemm_f32_lw_kedge.h"
-#include "brgemm_bf16_lw_kedge.h"
+#include "brgemm_bf16_lw_launch.h" // the tile table; brgemm_bf16_lw_kedge.h
 #include "brgemm_bf16_lw_chain_rounds.h"
 #include <string.h>
 
@@ -273,7 +273,8 @@ static int pick_bf16_tile(const GemmDesc &d) {
   return 0;
 }
 
-static const int BLW_BM[4] = {32, 64, 64, 128}, BLW_BN[4] = {64, 64, 128, 128};
+static const int BLW_BM[4] = {BLW_TILES[0].bm(), BLW_TILES[1].bm(), BLW_TILES[2].bm(), BLW_TILES[3].bm()}; // 32, 64, 64, 128
+static const int BLW_BN[4] = {BLW_TILES[0].bn(), BLW_TILES[1].bn(), BLW_TILES[2].bn(), BLW_TILES[3].bn()}; // 64, 64, 128, 128
 void blw_tile_dims(int tile, int *bm, int *bn) { *bm = BLW_BM[tile & 3], *bn = BLW_BN[tile & 3]; }
 static bool blw_divides(const GemmDesc &d, int tile) { return d.m % BLW_BM[tile] == 0 && d.n % BLW_BN[tile] == 0; }
 
@@ -309,7 +310,7 @@ static int pick_bf16_lw_image_tile(const GemmDesc &d, int64_t cus, int first_var
 
 // EDGE TILES, bf16 (xsmm_hip_set_edge_tiles modes 2 and 20 .. 23, opt-in): a whole-layer bf16 call no loader-wave tile divides - m not a
 // multiple of 32 or n not of 64: planned on the generic kernel or the 32x32 K-split kernel - on the loader-wave tiles all the same
-// (brgemm_bf16_lw.hip GRP = 3, launch_bf16_lw_edge). What the three B images ask of leading dimensions, strides and lane offsets is
+// (brgemm_bf16_lw.hip GRP = 3, launch_bf16_lw). What the three B images ask of leading dimensions, strides and lane offsets is
 // bf16_fast_eligible / bf16_flat_eligible / bf16_vnni4_eligible without their m / n terms; returns the image (0 VNNI-2, 2 flat, 4 VNNI-4), -1 = none.
 // ragged_k 1 (xsmm_hip_set_edge_k_bf16): the k % 64 term replaced by brgemm_bf16_lw_kedge.h's bkedge_k_ok; 2 (xsmm_hip_set_edge_k8_bf16): by
 // bkedge8_k_ok.
@@ -340,7 +341,7 @@ static int choose_bf16_edge_tile(const GemmDesc &d, int mode, int64_t chunks, in
 
 // RAGGED k, bf16 (xsmm_hip_set_edge_k_bf16, opt-in; brgemm_bf16_lw_kedge.h): a whole-layer bf16 call whose k is a multiple of 16 but not of
 // 64 (k >= 64) - planned on the generic or the 32x32 K-split kernel whatever its m and n - on a loader-wave tile (brgemm_bf16_lw.hip
-// GRP = 4, launch_bf16_lw_kedge). The tile: `forced` (0 .. 3) if there is one, else the cheapest candidate by blw_cost over the rounds of its
+// GRP = 4, launch_bf16_lw). The tile: `forced` (0 .. 3) if there is one, else the cheapest candidate by blw_cost over the rounds of its
 // ceil-divided tile count, priced at br * ceil(k / 64) chunks; ties go to the larger tile. A candidate fits (m >= BM, n >= BN) and - unless
 // a bf16 edge-tile mode is on as well (edge_on: the kernel then shifts back its last tile row / column too) - divides m and n.
 // Returns the tile index 0 .. 3, -1 = none: the call stays where it is. Not fitted to ragged shapes: profiles/edge_k_bf16_ab.txt.
@@ -596,7 +597,7 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
   // bf16 edge tiles, if asked for (choose_bf16_edge_tile): a call no loader-wave tile divides, before the refinements of the 32x32 K-split
   // kernel below. Decided here only - what is queued, grouped, chained or made a quad never sees it -, from the descriptor, the batch
   // count, the pointers' alignment and the CU count: allowed in strict mode. n % 8 keeps the shifted column tile on 16 bytes of C, of a
-  // flat B and of the bias row. The launcher's own checks: launch_bf16_lw_edge.
+  // flat B and of the bias row. The launcher's own checks: blw_launch_ok, BLW_EDGE.
   if ((env.edge_tiles == 2 || (env.edge_tiles >= V_BF16_LW_32x64 && env.edge_tiles <= V_BF16_LW_128x128)) && d.dtype == DT_BF16 && !d.vnni_c &&
       !d.generic_forced && !d.variant_forced && (d.variant == V_GENERIC || d.variant == V_BF16_SMALL32) && (d.m % 32 != 0 || d.n % 64 != 0) &&
       d.n % 8 == 0 && br >= 1 && al.ab16 && al.c16 && bias_ok8) {
@@ -617,7 +618,7 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
   // bf16 ragged k, if asked for (xsmm_hip_set_edge_k_bf16, a switch of its own; choose_bf16_kedge_tile): k >= 64 a multiple of 16 but not of
   // 64. Decided here only, like the edge tiles, from the descriptor, the batch count, the pointers' alignment and the CU count: allowed
   // in strict mode. The tile a forcing edge_k_bf16 value names, else the one a forcing edge-tile mode names, else the rule's; a tile that
-  // does not divide m and n needs a bf16 edge-tile mode on as well. The launcher's own checks: launch_bf16_lw_kedge.
+  // does not divide m and n needs a bf16 edge-tile mode on as well. The launcher's own checks: blw_launch_ok, BLW_KEDGE.
   if (env.edge_k_bf16 != 0 && d.dtype == DT_BF16 && !d.vnni_c && !d.generic_forced && !d.variant_forced &&
       (d.variant == V_GENERIC || d.variant == V_BF16_SMALL32) && bkedge_k_ok(d.k) && d.n % 8 == 0 && br >= 1 && al.ab16 && al.c16 && bias_ok8) {
     const bool force_e = env.edge_tiles >= V_BF16_LW_32x64 && env.edge_tiles <= V_BF16_LW_128x128;
@@ -644,7 +645,7 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
   }
   // bf16 ragged k in HALF steps, if asked for (xsmm_hip_set_edge_k8_bf16, a switch of its own; brgemm_bf16_lw_kedge.h bkedge8_*): k >= 64 a
   // multiple of 8 but not of 16 (1000, 200, 72). The block above with bkedge8_k_ok and env.edge_k8_bf16: the two switches partition the
-  // lengths (k % 16 == 0 / == 8) and neither looks at the other's mode. The launcher's own checks: launch_bf16_lw_kedge8.
+  // lengths (k % 16 == 0 / == 8) and neither looks at the other's mode. The launcher's own checks: blw_launch_ok, BLW_KEDGE8.
   if (env.edge_k8_bf16 != 0 && d.dtype == DT_BF16 && !d.vnni_c && !d.generic_forced && !d.variant_forced &&
       (d.variant == V_GENERIC || d.variant == V_BF16_SMALL32) && bkedge8_k_ok(d.k) && d.n % 8 == 0 && br >= 1 && al.ab16 && al.c16 && bias_ok8) {
     const bool force_e = env.edge_tiles >= V_BF16_LW_32x64 && env.edge_tiles <= V_BF16_LW_128x128;

@@ -65,7 +65,7 @@ enum GemmLauncher : int {
   GL_BF16_FAST,       // launch_gemm_bf16_fast(tile)
   GL_BF16_SMALL32,    // launch_bf16_small32(split)
   GL_BF16_GROUPED64,  // launch_bf16_grouped64
-  GL_BF16_LW,         // launch_bf16_lw / _flatb / _vnni4 by b_kind (0 / 2 / 4), tile; edge: launch_bf16_lw_edge(tile, b_kind); edge_k: launch_bf16_lw_kedge(tile, b_kind)
+  GL_BF16_LW,         // launch_bf16_lw(mode, tile, b_kind); mode (brgemm_bf16_lw_launch.h): BLW_LAYER; edge: BLW_EDGE; edge_k: BLW_KEDGE; edge_k8: BLW_KEDGE8
   GL_BF16_LW_GROUPED, // launch_bf16_lw_grouped(tile, b_kind, even)
   GL_BF16_LW_QUADS,   // launch_bf16_lw_quads(b_kind)
   GL_GENERIC,         // brgemm_grouped<T, VNNI, VEC, VF, FORM>: generic
@@ -88,13 +88,13 @@ struct GemmLaunch {
   int tail_tiles = 0;
   int tail_split = 1;
   // GL_F32_LW / GL_BF16_LW, edge tiles (xsmm_hip_set_edge_tiles): m or n is not a multiple of the tile - launch_f32_lw_edge(tile) /
-  // launch_bf16_lw_edge(tile, b_kind) on the ceil-divided tile grid; refused by the launcher: the launch the call has with the mode off
+  // launch_bf16_lw(BLW_EDGE, tile, b_kind) on the ceil-divided tile grid; refused by the launcher: the launch the call has with the mode off
   bool edge = false;
   // GL_F32_LW, ragged k (xsmm_hip_set_edge_k): k is a multiple of 8 but not of 64 - launch_f32_lw_kedge(tile) on the ceil-divided tile
   // grid (m and n may be ragged too); refused by the launcher: the launch the call has with the mode off.
-  // GL_BF16_LW (xsmm_hip_set_edge_k_bf16): k is a multiple of 16 but not of 64 - launch_bf16_lw_kedge(tile, b_kind), the same way
+  // GL_BF16_LW (xsmm_hip_set_edge_k_bf16): k is a multiple of 16 but not of 64 - launch_bf16_lw(BLW_KEDGE, tile, b_kind), the same way
   bool edge_k = false;
-  // GL_BF16_LW, ragged k in half steps (xsmm_hip_set_edge_k8_bf16): k is a multiple of 8 but not of 16 - launch_bf16_lw_kedge8(tile,
+  // GL_BF16_LW, ragged k in half steps (xsmm_hip_set_edge_k8_bf16): k is a multiple of 8 but not of 16 - launch_bf16_lw(BLW_KEDGE8, tile,
   // b_kind), refused the same way. Never set together with edge_k.
   bool edge_k8 = false;
   // GL_F32_LW, tile 1, halves (xsmm_hip_set_f32_halves): every 64x64 + K2 tile as two 64x32 + K2 workgroups - launch_f32_lw_halves, the
@@ -119,7 +119,7 @@ inline bool gemm_on_x6(const GemmDesc &d) { return d.variant >= V_F32_X6_64x64 &
 // which B image of the loader-wave bf16 tiles (brgemm_bf16_lw.hip) a descriptor's B operand needs - 0: VNNI-2, 2: flat [k][ldb],
 // 4: VNNI-4 - or -1 if the descriptor cannot run on those tiles (shape / alignment / lane-offset limits of the LDS-DMA panels)
 int bf16_lw_b_kind(const GemmDesc &d);
-// RAGGED-m CHAINS (xsmm_hip_set_chain_edge; rt_chain.h try_chain_launch, brgemm_bf16_lw.hip launch_bf16_chain_edge). Host-only, no HIP calls:
+// RAGGED-m CHAINS (xsmm_hip_set_chain_edge; rt_chain.h try_chain_launch, brgemm_bf16_lw.hip launch_bf16_chain, BLW_CHAIN_EDGE). Host-only, no HIP calls:
 // tests/golden/gemm_plan_chain_edge.txt is the table of both functions' answers.
 // One call of a chain: the B image (0 VNNI-2, 2 flat, 4 VNNI-4) it would run with as a layer of a ragged-m chain - what bf16_lw_b_kind asks of
 // leading dimensions, strides and lane offsets without its m and n terms -, or -1 and *why: the switch is off, an f32 call, a VNNI C,
@@ -134,7 +134,7 @@ int chain_edge_b_kind(const GemmDesc &d, int chain_edge, const char **why);
 // chain's rules decide).
 struct ChainEdgePlan { int tile; const char *why; };
 ChainEdgePlan plan_chain_edge(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, bool strict);
-// MULTI-ROUND CHAINS (xsmm_hip_set_chain_rounds; rt_chain.h try_chain_launch, brgemm_bf16_lw.hip launch_bf16_chain_rounds, step maps in
+// MULTI-ROUND CHAINS (xsmm_hip_set_chain_rounds; rt_chain.h try_chain_launch, brgemm_bf16_lw.hip launch_bf16_chain, BLW_CHAIN_ROUNDS, step maps in
 // brgemm_bf16_lw_chain_rounds.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_rounds.txt is the table of the function's answers.
 // A bf16 chain that meets every condition of the divisible chain but has MORE output tiles than compute units runs as one launch on
 // G x tiles_n resident workgroups, G row groups walking R = ceil(tiles_m / G) rounds of row blocks. m x n outputs per layer, nlayers layers
@@ -168,8 +168,11 @@ int chain_rounds_b_kind(const GemmDesc &d);
 ChainRoundsPlan plan_chain_rounds(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int mode, bool strict);
 // 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none
 int f32_chain_tile(const GemmDesc &d);
-// tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip)
+// tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip; BLW_TILES, brgemm_bf16_lw_launch.h)
 void blw_tile_dims(int tile, int *bm, int *bn);
+// the GemmVariant of loader-wave tile 0 .. 3 with B image b_kind (20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4), and the tile of such a variant
+inline int blw_variant(int tile, int b_kind) { return (b_kind == 4 ? V_BF16_LW4_32x64 : b_kind == 2 ? V_BF16_LWF_32x64 : V_BF16_LW_32x64) + tile; }
+inline int blw_variant_tile(int variant, int b_kind) { return variant - blw_variant(0, b_kind); }
 // f32 chain tiles as in launch_f32_lw: 1 = 64x64 + K2, 2 = 64x32 + K4 (K-split tiles: 16-byte stores; 32x32 + K4 measured slower than three launches)
 bool f32_chain_tile_dims(int tile, int *bm, int *bn);
 

@@ -260,7 +260,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   }
   if (divisible) {
     // (variants 20 .. 23 VNNI-2, 24 .. 27 flat B, 28 .. 31 VNNI-4: the same four tiles)
-    const int planned = d[0]->variant - (b_kind == 2 ? V_BF16_LWF_32x64 : b_kind == 4 ? V_BF16_LW4_32x64 : V_BF16_LW_32x64);
+    const int planned = blw_variant_tile(d[0]->variant, b_kind);
     bool same = !f32 && planned >= 0 && planned < 4;
     for (int i = 1; i < n && same; ++i) same = d[i]->variant == d[0]->variant;
     if (rounds_mode) shared_tile = chain_rounds_planned_tile(n, d); // (= same ? planned : -1 for a bf16 chain)
@@ -367,18 +367,19 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   c.target = ++blk.epoch * (unsigned)blk.tiles_n;
   if (f32) HIP_OK(launch_f32_chain(tile, c, s));
   else if (groups > 0) {
-    HIP_OK(launch_bf16_chain_rounds(tile, b_kind, groups, c, s));
+    c.groups = groups;
+    HIP_OK(launch_bf16_chain(BLW_CHAIN_ROUNDS, tile, b_kind, c, s));
     g_chain_rounds_stats[1].store(groups, std::memory_order_relaxed);
     g_chain_rounds_stats[2].store((m / bm + groups - 1) / groups, std::memory_order_relaxed);
-    g_chain_rounds_stats[3].store((b_kind == 4 ? V_BF16_LW4_32x64 : b_kind == 2 ? V_BF16_LWF_32x64 : V_BF16_LW_32x64) + tile, std::memory_order_relaxed);
+    g_chain_rounds_stats[3].store(blw_variant(tile, b_kind), std::memory_order_relaxed);
     g_chain_rounds_stats[0].fetch_add(1, std::memory_order_relaxed);
   } else if (ragged) {
-    HIP_OK(launch_bf16_chain_edge(tile, b_kind, c, s));
+    HIP_OK(launch_bf16_chain(BLW_CHAIN_EDGE, tile, b_kind, c, s));
     g_chain_edge_stats[1].store((m + bm - 1) / bm, std::memory_order_relaxed);
     g_chain_edge_stats[2].store(nn / bn, std::memory_order_relaxed);
-    g_chain_edge_stats[3].store((b_kind == 4 ? V_BF16_LW4_32x64 : b_kind == 2 ? V_BF16_LWF_32x64 : V_BF16_LW_32x64) + tile, std::memory_order_relaxed);
+    g_chain_edge_stats[3].store(blw_variant(tile, b_kind), std::memory_order_relaxed);
     g_chain_edge_stats[0].fetch_add(1, std::memory_order_relaxed);
-  } else HIP_OK(launch_bf16_chain(tile, b_kind, c, s));
+  } else HIP_OK(launch_bf16_chain(BLW_LAYER, tile, b_kind, c, s));
   if (blk.verified < 1) {
     // probation (comment at ChainBlock): wait for this launch and look at its error word before anyone can consume its outputs
     HIP_OK(hipStreamSynchronize(s));

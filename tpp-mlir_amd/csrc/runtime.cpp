@@ -40,10 +40,13 @@
 
 using namespace tpp;
 
-// Ragged-m chains (rt_chain.h try_chain_launch; xsmm_hip_set_chain_edge): the planner's two functions live in gemm_plan.cpp, the launcher
-// in brgemm_bf16_lw.hip. The host-only builds of this file (tests/tsan and its kin) link neither - their kernel stand-ins predate the
-// switch -, so WEAK stand-ins that refuse are defined here: the library's link takes the real definitions, a host-only build these.
+// Ragged-m chains (rt_chain.h try_chain_launch; xsmm_hip_set_chain_edge): the planner's two functions live in gemm_plan.cpp. The host-only
+// builds of this file (tests/tsan and its kin) do not link it - their kernel stand-ins predate the switch -, so WEAK stand-ins that
+// refuse are defined here: the library's link takes the real definitions, a host-only build these. The chain launcher with its mode
+// (chain_args.h; brgemm_bf16_lw.hip) has ONE such stand-in for the same reason: a host-only build whose own stand-in still has the
+// launcher's earlier signature links, and refuses every bf16 chain.
 namespace tpp {
+__attribute__((weak)) hipError_t launch_bf16_chain(int, int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 __attribute__((weak)) int chain_edge_b_kind(const GemmDesc &, int, const char **why) {
   if (why) *why = "this build has no ragged-chain planner";
   return -1;
@@ -51,14 +54,12 @@ __attribute__((weak)) int chain_edge_b_kind(const GemmDesc &, int, const char **
 __attribute__((weak)) ChainEdgePlan plan_chain_edge(int64_t, int64_t, int, const int64_t *, const int64_t *, int64_t, int, bool) {
   return ChainEdgePlan{-1, "this build has no ragged-chain planner"};
 }
-__attribute__((weak)) hipError_t launch_bf16_chain_edge(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 // (multi-round chains, xsmm_hip_set_chain_rounds: the same arrangement)
 __attribute__((weak)) int chain_rounds_planned_tile(int, const GemmDesc *const *) { return -1; }
 __attribute__((weak)) int chain_rounds_b_kind(const GemmDesc &) { return -1; }
 __attribute__((weak)) ChainRoundsPlan plan_chain_rounds(int64_t, int64_t, int, const int64_t *, const int64_t *, int64_t, int, int, bool) {
   return ChainRoundsPlan{-1, 0, "this build has no multi-round-chain planner", false};
 }
-__attribute__((weak)) hipError_t launch_bf16_chain_rounds(int, int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 } // namespace tpp
 
 namespace {
