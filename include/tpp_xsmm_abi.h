@@ -460,6 +460,25 @@ TPP_XSMM_EXPORT void xsmm_hip_edge_k_bf16_stats(int64_t out[4]);
  * xsmm_hip_edge_k_stats and xsmm_hip_edge_tiles_stats do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_edge_k8_bf16(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_edge_k8_bf16_stats(int64_t out[4]);
+/* Flat and VNNI-4 B on the 256x256 bf16 tile (opt-in; also TPP_HIP_DMA256_IMAGES, read as a number). brgemm_bf16_dma256, the 256x256
+ * LDS-DMA tile of large bf16 GEMMs, takes a VNNI-2 B; a large call with a flat [k][ldb] or a VNNI-4 [k/4][ldb][4] B runs on the 128x128
+ * loader-wave tile, which needs twice the LDS fill per flop. With this switch on, such a call runs on the 256x256 tile with the B image of
+ * its operand (kernel entry points brgemm_bf16_dma256_flatb / _vnni4: the same ring, A image, schedule and epilogue; flat rows are
+ * read by ds_read_b64_tr_b16, VNNI-4 k-group rows by 8-byte reads). Every output is one chain over k, in k order, on the same MFMA as on
+ * the loader-wave tile: bit for bit the result of the switch off. No scratch block, no counters: legal on a captured stream.
+ * A call is taken when all of this holds: bf16, flat or VNNI-4 B, no VNNI C, neither a kernel variant nor the generic kernel forced, the
+ * descriptor's kernel is a flat or VNNI-4 loader-wave tile, m and n multiples of 256, batch count >= 1, A, B, C 16-byte and the bias row
+ * 8-byte aligned. Everything else runs as with the switch off - every tile-queue group, quad and chain too.
+ * mode 0 = off (default); 1 = the rule that sends a VNNI-2 descriptor to the 256x256 tile (at least 240 tiles of 256x256 and the fill
+ * term of the tile choice) - every such row of both images measured faster (profiles/dma256_images_ab.txt); 2 = every eligible call (a
+ * test / measurement switch).
+ * Read per invoke; returns the previous mode, -1 (and changes nothing) for any other value. The choice depends on the descriptor, the
+ * batch count, the pointers' alignment and the CU count only: made in strict mode too. xsmm_hip_last_refined_kernel reads
+ * "brgemm_bf16_dma_flatb<256x256>" or "brgemm_bf16_dma_vnni4<256x256>".
+ * _stats: out[0] such launches since process start; of the most recent one: [1] tile rows, [2] tile columns, [3] the B image (2 flat,
+ * 4 VNNI-4). */
+TPP_XSMM_EXPORT int xsmm_hip_set_dma256_images(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_dma256_images_stats(int64_t out[4]);
 /* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
  * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
  * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two

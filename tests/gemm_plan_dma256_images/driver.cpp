@@ -1,0 +1,149 @@
+// driver.cpp - TEST INFRASTRUCTURE for tests/test_gemm_plan_dma256_images.py, never part of the product library.
+//
+// Steps whole-layer bf16 calls through the kernel planner (tpp-mlir_amd/csrc/gemm_plan.h) under the modes of xsmm_hip_set_dma256_images (0, 1,
+// 2) and prints, in the notation of tests/gemm_plan/driver.cpp without its descriptor numbers, one line per descriptor
+//   <form> <m>x<n>x<k> [ld<lda>,<ldb>,<ldc>] e<epilogue> f<forced> : <variant> <name> [gf] [vf] [bk<B image>]
+// and under it one line per call
+//   c br<batch> [a<A,B>/<C>/<D alignment>] [strict] : <launch, mode 0> | <mode 1> | <mode 2>
+// where the mode-0 launch comes from a GemmPlanEnv that never names the new field, and a mode-1 / mode-2 launch that is the mode-0 one field
+// by field prints as "-". A launch on the 256x256 tile with a B image prints as bf16_fast t2 b<image> "<text>".
+#include "gemm_plan.h"
+#include <stdio.h>
+#include <string.h>
+#include <string>
+
+using namespace tpp;
+
+namespace {
+
+const int CUS = 256;
+
+struct Form {
+  const char *name;
+  int vnni_b, vf, vnni_c;
+};
+const Form V2{"v2", 1, 2, 0}, V4{"v4", 1, 4, 0}, FLAT{"flat", 0, 0, 0}, VC{"vc", 1, 2, 1}, VC4{"vc4", 1, 4, 1};
+
+GemmDesc desc(const Form &f, int64_t m, int64_t n, int64_t k, const char *ep = "b", int forced = -1, int64_t lda = -1, int64_t ldb = -1, int64_t ldc = -1) {
+  GemmDesc d;
+  memset(&d, 0, sizeof(d));
+  d.kind = KIND_GEMM;
+  d.has_batch = 1;
+  d.dtype = DT_BF16;
+  d.m = m, d.n = n, d.k = k;
+  d.lda = lda >= 0 ? lda : k;
+  d.ldb = ldb >= 0 ? ldb : n;
+  d.ldc = ldc >= 0 ? ldc : n;
+  d.stride_a = m * k;
+  d.stride_b = k * n;
+  d.beta0 = strchr(ep, 'b') != nullptr;
+  d.bias = strchr(ep, 'B') != nullptr;
+  d.relu = strchr(ep, 'r') != nullptr;
+  d.fused = d.bias || d.relu;
+  d.vnni_b = f.vnni_b;
+  d.vnni_factor = f.vf;
+  d.vnni_c = f.vnni_c;
+  const bool ok = plan_gemm(d, forced, GemmPlanEnv{CUS, false, -1});
+  printf("%s %ldx%ldx%ld", f.name, (long)m, (long)n, (long)k);
+  if (lda >= 0 || ldb >= 0 || ldc >= 0) printf(" ld%ld,%ld,%ld", (long)d.lda, (long)d.ldb, (long)d.ldc);
+  printf(" e%s f%d : %s%d %s", *ep ? ep : "-", forced, ok ? "" : "!", d.variant, d.name);
+  if (d.generic_forced) printf(" gf");
+  if (d.variant_forced) printf(" vf");
+  if (bf16_lw_b_kind(d) >= 0) printf(" bk%d", bf16_lw_b_kind(d));
+  printf("\n");
+  return d;
+}
+
+const char *generic_name(GemmGeneric g) {
+  switch (g) {
+  case GG_BF16_VNNI2: return "<bf16,vnni2>";
+  case GG_BF16_VNNI2_VEC: return "<bf16,vnni2,vec>";
+  case GG_BF16_VNNI4_VEC: return "<bf16,vnni4,vec>";
+  case GG_BF16_FLAT: return "<bf16,flat>";
+  default: return "?";
+  }
+}
+
+std::string launch_text(const GemmLaunch &l) {
+  char buf[256];
+  switch (l.launcher) {
+  case GL_NONE: snprintf(buf, sizeof buf, "none"); break;
+  case GL_INVALID: snprintf(buf, sizeof buf, "invalid"); break;
+  case GL_BF16_FAST:
+    if (l.b_kind) snprintf(buf, sizeof buf, "bf16_fast t%d b%d", l.tile, l.b_kind);
+    else snprintf(buf, sizeof buf, "bf16_fast t%d", l.tile);
+    break;
+  case GL_BF16_SMALL32: snprintf(buf, sizeof buf, "bf16_small32 s%d", l.split); break;
+  case GL_BF16_LW: snprintf(buf, sizeof buf, "bf16_lw t%d b%d", l.tile, l.b_kind); break;
+  case GL_GENERIC: snprintf(buf, sizeof buf, "generic%s", generic_name(l.generic)); break;
+  default: snprintf(buf, sizeof buf, "other%d", (int)l.launcher); break;
+  }
+  std::string s = buf;
+  if (l.text && *l.text) s += std::string(" \"") + l.text + "\"";
+  if (l.edge || l.edge_k || l.edge_k8 || l.halves || l.tail_tiles || l.split != 1) s += " !flags";
+  return s;
+}
+
+// alignments in bytes: A and B, C, D
+void call(const GemmDesc &d, int64_t br, bool strict = false, int ab = 16, int c = 16, int dd = 16) {
+  const GemmAlign al{ab >= 16, c >= 16, c >= 8, dd >= 8, dd >= 16};
+  printf(" c br%ld", (long)br);
+  if (ab != 16 || c != 16 || dd != 16) printf(" a%d/%d/%d", ab, c, dd);
+  if (strict) printf(" strict");
+  const std::string off = launch_text(plan_gemm_call(d, br, al, GemmPlanEnv{CUS, strict, -1}));
+  printf(" : %s", off.c_str());
+  for (int mode = 1; mode <= 2; ++mode) {
+    GemmPlanEnv e{CUS, strict, -1};
+    e.dma256_images = mode;
+    const std::string on = launch_text(plan_gemm_call(d, br, al, e));
+    printf(" | %s", on == off ? "-" : on.c_str());
+  }
+  GemmPlanEnv e0{CUS, strict, -1};
+  e0.dma256_images = 0;
+  if (launch_text(plan_gemm_call(d, br, al, e0)) != off) printf(" !mode 0 differs from an environment without the field");
+  printf("\n");
+}
+
+void calls(const GemmDesc &d) {
+  call(d, 1);
+  call(d, 1, true);
+  call(d, 4);
+  call(d, 0);
+}
+
+} // namespace
+
+int main() {
+  const Form *forms[3] = {&V2, &V4, &FLAT};
+  static const int64_t shapes[][3] = {{4096, 4096, 4096}, {4096, 4096, 1024}, {3840, 4096, 1024}, {3584, 4096, 1024}, {16384, 1024, 1024},
+                                      {256, 256, 1024},   {512, 768, 1024},   {4100, 4096, 1024}, {8192, 8192, 1024}, {2048, 2048, 2048}};
+  for (const Form *f : forms)
+    for (auto &s : shapes) calls(desc(*f, s[0], s[1], s[2]));
+  // each misalignment, on a call with a bias row: A / B, C, the bias
+  for (const Form *f : forms) {
+    const GemmDesc d = desc(*f, 4096, 4096, 1024, "bBr");
+    calls(d);
+    call(d, 1, false, 8, 16, 16);
+    call(d, 1, false, 16, 8, 16);
+    call(d, 1, false, 16, 16, 4);
+    call(d, 1, false, 16, 16, 8);
+  }
+  // beta 1; leading dimensions wider than the rows
+  for (const Form *f : forms) {
+    calls(desc(*f, 4096, 4096, 1024, ""));
+    calls(desc(*f, 4096, 4096, 1024, "b", -1, 1032, 4104, 4112));
+  }
+  // forced variants: the descriptor's own tile, another tile, the generic kernel
+  calls(desc(V2, 4096, 4096, 4096, "b", V_BF16_DMA256));
+  calls(desc(V2, 4096, 4096, 4096, "b", V_BF16_LW_128x128));
+  calls(desc(V4, 4096, 4096, 4096, "b", V_BF16_LW4_128x128));
+  calls(desc(V4, 4096, 4096, 4096, "b", V_BF16_LW4_64x128));
+  calls(desc(FLAT, 4096, 4096, 4096, "b", V_BF16_LWF_128x128));
+  calls(desc(FLAT, 4096, 4096, 4096, "b", V_BF16_LWF_64x64));
+  calls(desc(FLAT, 4096, 4096, 4096, "b", V_GENERIC));
+  calls(desc(V4, 4096, 4096, 4096, "b", V_GENERIC));
+  // a VNNI C
+  calls(desc(VC, 4096, 4096, 1024));
+  calls(desc(VC4, 4096, 4096, 1024));
+  return 0;
+}

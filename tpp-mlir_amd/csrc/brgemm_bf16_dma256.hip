@@ -1,4 +1,4 @@
-// brgemm_bf16_dma256.hip - the large-shape member of the bf16 VNNI-2 BRGEMM family for gfx950:
+// brgemm_bf16_dma256.hip - the large-shape member of the bf16 BRGEMM family for gfx950:
 // 256 x 256 workgroup tiles, four waves of 128 x 128 (4 x 4 accumulator tiles of
 // v_mfma_f32_32x32x16_bf16 each), operands streamed global -> LDS by buffer_load ... lds (no
 // staging registers).
@@ -19,12 +19,19 @@
 //          address of the DMA and again by the fragment read: ds_read_b128 conflict-free.
 //   B    : the VNNI-2 pair-rows as they are; a lane's fragment (8 consecutive k of one column) is 4
 //          dwords one pair-row (1 KiB) apart: two ds_read2st64_b32.
+//          Opt-in (xsmm_hip_set_dma256_images; entry points brgemm_bf16_dma256_flatb / _vnni4): a FLAT B
+//          [k][ldb] - the chunk's 32 rows of 512 B, 64-byte blocks XORed with row & 3 on the DMA's source
+//          side, a fragment two ds_read_b64_tr_b16 - and a VNNI-4 B [k/4][ldb][4] - 8 k-group rows of
+//          2 KiB as they are, a fragment two ds_read_b64. A B slot is 16 KiB, a wave issues 4 of its 16
+//          one-KiB instructions and a fragment set is 12 LDS reads in all three images: one schedule.
+//          The maps, written once: brgemm_bf16_dma256_images.h (tests/test_dma256_images.py).
 //   sync : per chunk ONE s_waitcnt vmcnt (own DMA of chunk t+1 landed) + ONE raw s_barrier between its
 //          two K steps; never __syncthreads inside the loop (it would drain the DMA queue).
 //   out  : as the 128 x 128 kernel - operands swapped so a lane owns a row, bias / relu / one RNE
 //          rounding (v_cvt_pk_bf16_f32), permlane32 swap, per-wave LDS tile, coalesced 16-byte stores.
 #include "gemm_common.h"
 #include "xsmm_desc.h"
+#include "brgemm_bf16_dma256_images.h"
 #include <type_traits>
 
 namespace tpp {
@@ -32,9 +39,13 @@ namespace tpp {
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-__global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
-  constexpr int BM = 256, BN = 256, BK2 = 32, NSLOT = 4, TM = 4, TN = 4;
-  constexpr int A_SLOT = BM * BK2 * 2, B_SLOT = (BK2 / 2) * BN * 4, SLOT = A_SLOT + B_SLOT;
+// IMG: the B image (brgemm_bf16_dma256_images.h) - 0 VNNI-2, 2 flat, 4 VNNI-4. Everything but the B side of the DMA and of the fragment
+// reads is one text.
+template <int IMG>
+__device__ __forceinline__ void brgemm_bf16_dma256_body(const GemmArgs &p) {
+  static_assert(d256_image_ok(IMG), "0: VNNI-2 B image, 2: flat B image + transpose reads, 4: VNNI-4 B image + 8-byte reads");
+  constexpr int BM = D256_BM, BN = D256_BN, BK2 = D256_BK, NSLOT = 4, TM = 4, TN = 4;
+  constexpr int A_SLOT = D256_A_SLOT, B_SLOT = D256_B_SLOT, SLOT = A_SLOT + B_SLOT;
   constexpr int DMA_PER_CHUNK = 8; // per wave: 4 x 1 KiB of A + 4 x 1 KiB of B
   static_assert(SLOT == 32768, "ring slot");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_x[];
@@ -54,19 +65,20 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
 
   // per-lane source offsets of this wave's 8 DMA instructions (constant for the kernel):
   // A instruction v fills rows 16v .. 16v+15 (lane -> row 16v + lane/4, LDS piece lane%4),
-  // B instruction v fills pair-row v (lane -> columns 4*lane .. 4*lane+3)
+  // B instruction v fills pair-row v (lane -> columns 4*lane .. 4*lane+3); flat image: rows 2v, 2v+1, source blocks swizzled;
+  // VNNI-4 image: one half of k-group row v/2 (d256_b_dma_voff)
   unsigned voffA[4], voffB[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int v = wave * 4 + u;
     const int row = 16 * v + (lane >> 2), pos = lane & 3;
     voffA[u] = (unsigned)(row * (int)p.lda * 2 + ((pos ^ ((row >> 2) & 3)) << 4));
-    voffB[u] = (unsigned)(v * (int)p.ldb * 4 + (lane << 4));
+    voffB[u] = IMG == 0 ? (unsigned)(v * (int)p.ldb * 4 + (lane << 4)) : d256_b_dma_voff(IMG, v, lane, (int)p.ldb);
   }
-  const unsigned short *gA = A + (int64_t)m0 * p.lda, *gB = B + 2 * (int64_t)n0;
+  const unsigned short *gA = A + (int64_t)m0 * p.lda, *gB = B + d256_b_col_elems(IMG, n0);
   int kc = 0;
   const int64_t dA_wrap = p.stride_a - (int64_t)(kchunks - 1) * BK2;
-  const int64_t dB_in = (int64_t)(BK2 / 2) * 2 * p.ldb, dB_wrap = p.stride_b - (int64_t)(kchunks - 1) * dB_in;
+  const int64_t dB_in = d256_b_chunk_elems(p.ldb), dB_wrap = p.stride_b - (int64_t)(kchunks - 1) * dB_in;
   auto dma_piece = [&](int slot, int u) __attribute__((always_inline)) {
     unsigned char *base = smem_x + slot * SLOT + wave * 4096;
     if (u < 4) {
@@ -92,6 +104,12 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
   f32x16 acc[TM][TN];
   bf16x8_t af[2][TM];
   u32x4 bw[2][TN]; // B fragments as dwords: a fragment is filled by two 2-dword reads
+  // flat image: the halves of a fragment as the transpose reads deliver them. Those reads are inline assembly, because hipcc puts an
+  // s_waitcnt vmcnt(0) in front of a ds_read_b64_tr_b16 it knows of whenever one of this wave's LDS-DMA loads is in flight (it cannot
+  // tell the read from one of the bytes the DMA is writing) and so drained the DMA queue 20 times per steady lap. What the compiler does
+  // not know of it does not wait for either: flat_wait() below is the wait, written by hand.
+  typedef unsigned int u32x2q_t __attribute__((ext_vector_type(2)));
+  u32x2q_t bq[2][TN][2];
   // lane bases of the fragment reads (byte offsets inside a slot). One opaque base per column tile so
   // that the four pair-row reads of a fragment pair up as ds_read2st64_b32 (rows r, r+1) straight into
   // consecutive registers instead of being paired across tiles.
@@ -101,7 +119,7 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
   asm volatile("" : "+v"(a_lane[0]), "+v"(a_lane[1]));
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
-    b_lane[j] = A_SLOT + ((4 * lh) * BN + wn * 128 + j * 32 + li) * 4;
+    b_lane[j] = A_SLOT + (IMG == 0 ? ((4 * lh) * BN + wn * 128 + j * 32 + li) * 4 : d256_b_frag_lds(IMG, wn, j, 0, lane, 0));
     asm volatile("" : "+v"(b_lane[j]));
   }
   // One of the 12 LDS reads of a fragment set, in the order the MFMAs need them: A0, B0 (two halves),
@@ -114,9 +132,37 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
       af[buf][i] = *(const bf16x8_t *)(s + a_lane[ks] + i * (32 * 64));
     } else {
       const int j = (idx - 1) >> 1, h = (idx - 1) & 1;
-      const unsigned int *bp = (const unsigned int *)(s + b_lane[j] + (8 * ks) * BN * 4);
-      bw[buf][j][2 * h] = bp[(2 * h) * BN];
-      bw[buf][j][2 * h + 1] = bp[(2 * h + 1) * BN];
+      if constexpr (IMG == 0) {
+        const unsigned int *bp = (const unsigned int *)(s + b_lane[j] + (8 * ks) * BN * 4);
+        bw[buf][j][2 * h] = bp[(2 * h) * BN];
+        bw[buf][j][2 * h + 1] = bp[(2 * h + 1) * BN];
+      } else {
+        // four consecutive k of the lane's column per read: the hardware transpose of a [4 k][16 columns] block of the flat image (EXEC is
+        // all ones here: every branch around a fragment read is wave-uniform), 8 contiguous bytes of the VNNI-4 image
+        typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+        const unsigned char *bp = s + b_lane[j] + D256_KS_STEP * ks + D256_H_STEP * h;
+        if constexpr (IMG == 2) {
+          const unsigned la = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char *)bp;
+          asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(bq[buf][j][h]) : "v"(la));
+        } else {
+          const u32x2_t q = *(const u32x2_t *)bp;
+          bw[buf][j][2 * h] = q[0];
+          bw[buf][j][2 * h + 1] = q[1];
+        }
+      }
+    }
+  };
+  // Flat image, in front of the MFMAs of a K step: the eight transpose reads of fragment set `set` have landed. LDS reads return in
+  // order and a set is read as A0, B x 8, A1, A2, A3, so at most 3 outstanding means every B read is back (whatever else counts
+  // into lgkmcnt only makes the wait longer). The reads' results pass through the statement, so nothing uses them in front of it; the
+  // compiler's own counts for the A reads do not know of the transpose reads and are therefore never too lax.
+  auto flat_wait = [&](int set) __attribute__((always_inline)) {
+    if constexpr (IMG == 2) {
+      asm volatile("s_waitcnt lgkmcnt(3)"
+                   : "+v"(bq[set][0][0]), "+v"(bq[set][0][1]), "+v"(bq[set][1][0]), "+v"(bq[set][1][1]), "+v"(bq[set][2][0]), "+v"(bq[set][2][1]),
+                     "+v"(bq[set][3][0]), "+v"(bq[set][3][1]));
+#pragma unroll
+      for (int j = 0; j < TN; ++j) bw[set][j] = u32x4{bq[set][j][0][0], bq[set][j][0][1], bq[set][j][1][0], bq[set][j][1][1]};
     }
   };
   auto frag_load = [&](int buf, int slot, int ks) __attribute__((always_inline)) {
@@ -131,6 +177,7 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
   auto chunk = [&](auto steady_c, int slot, bool h1, bool h2, bool h3) __attribute__((always_inline)) {
     constexpr bool STEADY = decltype(steady_c)::value;
     // ---- K step 0 (fragments in set 0); set 1 <- K step 1 of this chunk, one read per MFMA
+    flat_wait(0);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -158,6 +205,7 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
     }
     // ---- K step 1 (set 1); set 0 <- K step 0 of chunk t+1; the DMA of chunk t+3 rides along, into
     // the slot chunk t-1 has left
+    flat_wait(1);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -206,11 +254,21 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
   // ---- epilogue ------------------------------------------------------------------------
   // lane (li, lh) owns row 32*i + li of wave-tile row block i and, in registers 4g..4g+3 of
   // tile (i, j), columns 32*j + 8*g + 4*lh + (0..3)
+  // The lane index is taken again HERE, from statements the compiler keeps where they stand: derived from threadIdx.x up front, the
+  // epilogue's lane offsets stayed live across the K loop, whose 256 accumulators + 64 fragment registers leave no room for them - four
+  // of them were spilled to scratch memory (20 bytes per lane) in the prologue and reloaded here. Once per part of the epilogue: a
+  // value that lives across the beta-1 block, which wants every register for the accumulators, is spilled again.
+  auto fresh_lane = []() __attribute__((always_inline)) {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+  };
   typedef unsigned int u32x2d __attribute__((ext_vector_type(2)));
   const __amdgpu_buffer_rsrc_t rsrcC = __builtin_amdgcn_make_buffer_rsrc(
       (void *)(C + (int64_t)(m0 + wm * 128) * p.ldc + n0 + wn * 128), 0, 0x7fffffff, 0x00020000);
   const unsigned ldcb = (unsigned)((int)p.ldc * 2);
   if (!(p.ep & EP_BETA0)) { // beta = 1: add C before the single rounding
+    const int lane1 = fresh_lane(), li = lane1 & 31, lh = lane1 >> 5;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -226,6 +284,8 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
         }
   }
   __syncthreads(); // every wave is done with the ring (all DMA landed): reuse it as per-wave output tiles
+  { // (a scope of its own: these names shadow the K loop's)
+  const int lane = fresh_lane(), li = lane & 31, lh = lane >> 5;
   const bool relu = (p.ep & EP_RELU) != 0;
   constexpr int ES = 272; // bytes per staged row: 128 bf16 + 16 B pad (conflict-free 16-byte accesses)
   unsigned char *ot = smem_x + wave * (64 * ES);
@@ -282,12 +342,20 @@ __global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) {
                                              (unsigned)(ih * 64 + it * 4) * ldcb, C_STORE_AUX);
     }
   }
+  }
 }
 
-hipError_t launch_bf16_dma256(const GemmArgs &a, hipStream_t s) {
+#undef TPP_DMA256_ADVANCE
+
+__global__ __launch_bounds__(256) void brgemm_bf16_dma256(GemmArgs p) { brgemm_bf16_dma256_body<0>(p); }
+__global__ __launch_bounds__(256) void brgemm_bf16_dma256_flatb(GemmArgs p) { brgemm_bf16_dma256_body<2>(p); }
+__global__ __launch_bounds__(256) void brgemm_bf16_dma256_vnni4(GemmArgs p) { brgemm_bf16_dma256_body<4>(p); }
+
+template <int IMG> static hipError_t launch_bf16_dma256_t(const GemmArgs &a, hipStream_t s) {
   constexpr size_t lds = 4 * 32768;
   static std::atomic<unsigned long long> lds_set{0};
-  if (hipError_t e = ensure_dynamic_lds((const void *)brgemm_bf16_dma256, (int)lds, lds_set); e != hipSuccess) return e;
+  void (*const kern)(GemmArgs) = IMG == 0 ? brgemm_bf16_dma256 : IMG == 2 ? brgemm_bf16_dma256_flatb : brgemm_bf16_dma256_vnni4;
+  if (hipError_t e = ensure_dynamic_lds((const void *)kern, (int)lds, lds_set); e != hipSuccess) return e;
   GemmArgs args = a;
   const int tiles_m = a.m / 256, tiles_n = a.n / 256;
   dim3 grid;
@@ -300,8 +368,22 @@ hipError_t launch_bf16_dma256(const GemmArgs &a, hipStream_t s) {
     if (tiles_m > 65535 || tiles_n > 65535) return hipErrorInvalidValue;
     grid = dim3(1, tiles_n, tiles_m);
   }
-  hipLaunchKernelGGL(brgemm_bf16_dma256, grid, dim3(256), lds, s, args);
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, args);
   return hipGetLastError();
+}
+
+hipError_t launch_bf16_dma256(const GemmArgs &a, hipStream_t s) { return launch_bf16_dma256_t<0>(a, s); }
+
+// The same tile with B image b_kind (0 VNNI-2, 2 flat, 4 VNNI-4; xsmm_hip_set_dma256_images, gemm_plan.cpp plan_gemm_call). Unlike the plain
+// launcher it checks what the kernel assumes and refuses everything else with hipErrorInvalidValue - the caller then runs the launch the
+// call has with the mode off: whole tiles, whole 32-k chunks, a batch element, 16-byte pieces at every DMA lane's source and at every row
+// of C, the 8-byte bias reads, the lane offsets in 31 bits.
+hipError_t launch_bf16_dma256_image(int b_kind, const GemmArgs &a, hipStream_t s) {
+  if (!d256_image_ok(b_kind) || a.m <= 0 || a.n <= 0 || a.m % D256_BM || a.n % D256_BN || a.k <= 0 || a.k % D256_BK || a.br < 1) return hipErrorInvalidValue;
+  if (!d256_b_ldb_ok(b_kind, a.ldb) || a.lda < a.k || a.ldc < a.n || ((a.lda | a.ldc | a.stride_a | a.stride_b) & 7) || a.lda >= (1 << 22) || a.ldc >= (1 << 22))
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.C) & 15) || ((a.ep & EP_BIAS) && (!a.D || ((uintptr_t)a.D & 7))) || (a.ep & EP_VNNI_C)) return hipErrorInvalidValue;
+  return b_kind == 0 ? launch_bf16_dma256_t<0>(a, s) : b_kind == 2 ? launch_bf16_dma256_t<2>(a, s) : launch_bf16_dma256_t<4>(a, s);
 }
 
 } // namespace tpp

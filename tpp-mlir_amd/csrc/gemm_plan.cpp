@@ -669,6 +669,29 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
       return l;
     }
   }
+  // FLAT and VNNI-4 B on the 256x256 tile, if asked for (xsmm_hip_set_dma256_images; brgemm_bf16_dma256.hip entry points _flatb / _vnni4,
+  // brgemm_bf16_dma256_images.h): a call planned - not forced - on a flat or VNNI-4 loader-wave tile whose m and n the 256x256 tile divides.
+  // Mode 1, the rule: where plan_gemm sends a VNNI-2 descriptor to this tile, pick_bf16_tile(d) == 2 (at least 240 tiles and the fill
+  // term); mode 2 (tests, measurements) takes every eligible call. Decided here only - what is queued, grouped, chained or made a quad
+  // never sees it -, from the descriptor, the batch count, the pointers' alignment and the CU count: allowed in strict mode. The launcher's
+  // own checks: launch_bf16_dma256_image; refused there, the call runs the launch it has with the mode off (launch_gemm).
+  // Measured (profiles/dma256_images_ab.txt: one box, 256 CUs, five alternating pairs off / on, us per call, 128x128 image tile -> this one;
+  // the VNNI-2 kernel on the same shapes in the same session: 104.14, 132.13, 34.33, 33.28, 35.83, 69.87):
+  //   VNNI-4: 4096^3 125.14 -> 104.36, 8192x8192x1024 191.56 -> 130.29, 4096x4096x1024 44.75 -> 34.38, 3840x4096x1024 (240 tiles) 44.86 ->
+  //           33.98, 16384x1024x1024 54.39 -> 35.15, 32768x1024x1024 84.85 -> 69.21
+  //   flat:   4096^3 130.50 -> 106.84, 8192x8192x1024 201.97 -> 133.68, 4096x4096x1024 44.86 -> 34.61, 3840x4096x1024 42.86 -> 34.29,
+  //           16384x1024x1024 56.38 -> 35.54, 32768x1024x1024 93.74 -> 69.77
+  // Every pair of every row is faster and both images run at the VNNI-2 kernel's times, so the VNNI-2 rule holds for both as it is and
+  // no row needs a gate. (The 32768-row rows: every run on this tile, 68.62 .. 70.17, is below every run off it, 76.02 .. 111.38, but that
+  // session's switch-off runs spread wider than the gain, so by the letter of the discipline the row shows no difference there; an earlier
+  // session had it faster, VNNI-4 74.52 -> 68.79.) Control, mode 2 on 64 tiles: 2048^3 flat 17.80 -> 42.76, VNNI-4 18.13 -> 41.75 - the fill
+  // term of pick_bf16_tile is needed.
+  if (env.dma256_images != 0 && d.dtype == DT_BF16 && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.variant >= V_BF16_LWF_32x64 &&
+      d.variant <= V_BF16_LW4_128x128 && d.m % 256 == 0 && d.n % 256 == 0 && br >= 1 && al.ab16 && al.c16 && bias_ok8) {
+    const int kind = bf16_lw_b_kind(d);
+    if ((kind == 2 || kind == 4) && (env.dma256_images == 2 || pick_bf16_tile(d) == 2))
+      return launch(GL_BF16_FAST, 2, kind == 2 ? "brgemm_bf16_dma_flatb<256x256>" : "brgemm_bf16_dma_vnni4<256x256>", 1, kind);
+  }
   // Small bf16 outputs with a LONG reduction: the 32x32 K-split kernel (fragments straight from global memory, two groups of loads
   // in flight per wave) is latency-bound there - 128 x 1024 x 4096: 15.4 us against 9.8 on 64 loader-wave tiles of 32x64 and 8.1 on
   // 128 tiles of 32x32 + K2 (the same kernel, twice the workgroups pulling panels). Crossovers (profiles/r05_bf16_skinny_small_vs_lw.txt):

@@ -46,9 +46,9 @@ enum GemmVariant : int {
 // xsmm_hip_set_edge_tiles (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that f32 GemmVariant's tile, 2 = the f32 and the bf16 tile rule, 20 .. 23 =
 // that bf16 GemmVariant's tile) and xsmm_hip_set_edge_k (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that GemmVariant's tile) and
 // xsmm_hip_set_edge_k_bf16 (0 = off, 1 = the bf16 tile rule, 20 .. 23 = that bf16 GemmVariant's tile) and xsmm_hip_set_f32_halves (0 = off, 1 =
-// the rule, 2 = wherever eligible) and xsmm_hip_set_edge_k8_bf16 (the values of edge_k_bf16, for k % 16 == 8); brgemm_f32.hip gemm_plan_env
-// fills it per call
-struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; };
+// the rule, 2 = wherever eligible) and xsmm_hip_set_edge_k8_bf16 (the values of edge_k_bf16, for k % 16 == 8) and xsmm_hip_set_dma256_images
+// (0 = off, 1 = the rule, 2 = wherever eligible); brgemm_f32.hip gemm_plan_env fills it per call
+struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
 struct GemmAlign { bool ab16, c16, c8, d8, d16; };
@@ -62,7 +62,7 @@ enum GemmLauncher : int {
   GL_F32_LW16,        // launch_f32_lw16(tile); split > 1: launch_f32_lw_split(3, split) first
   GL_F32_LW_GROUPED,  // launch_f32_lw_grouped(tile, split)
   GL_F32_X6,          // launch_f32_x6(tile, vec)
-  GL_BF16_FAST,       // launch_gemm_bf16_fast(tile)
+  GL_BF16_FAST,       // launch_gemm_bf16_fast(tile); b_kind 2 / 4 (xsmm_hip_set_dma256_images): launch_bf16_dma256_image(b_kind), tile 2 only
   GL_BF16_SMALL32,    // launch_bf16_small32(split)
   GL_BF16_GROUPED64,  // launch_bf16_grouped64
   GL_BF16_LW,         // launch_bf16_lw(mode, tile, b_kind); mode (brgemm_bf16_lw_launch.h): BLW_LAYER; edge: BLW_EDGE; edge_k: BLW_KEDGE; edge_k8: BLW_KEDGE8
@@ -78,7 +78,7 @@ struct GemmLaunch {
   GemmLauncher launcher;
   int tile;        // the launcher's tile index
   int split;       // workgroups per output tile (1 = none)
-  int b_kind;      // B image of the bf16 loader-wave tiles: 0 VNNI-2, 2 flat, 4 VNNI-4
+  int b_kind;      // B image of the bf16 loader-wave tiles and of the 256x256 tile: 0 VNNI-2, 2 flat, 4 VNNI-4
   bool even;       // GL_BF16_LW_GROUPED: every item has an even chunk count
   bool vec;        // GL_F32_X6: A and B 16-byte aligned
   GemmGeneric generic;

@@ -185,6 +185,16 @@ inline std::atomic<int> g_edge_k8_bf16{[] {
   return edge_k_bf16_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_edge_k8_bf16_stats[4]; // half-step launches; chunks per batch element, overlap o, GemmVariant of the tile (with its B image) of the latest
+// FLAT and VNNI-4 B on the 256x256 bf16 tile (xsmm_hip_set_dma256_images / TPP_HIP_DMA256_IMAGES; gemm_plan.cpp plan_gemm_call,
+// brgemm_bf16_dma256.hip launch_bf16_dma256_image, brgemm_bf16_dma256_images.h): 0 = off, 1 = the rule (where a VNNI-2 descriptor goes to that tile: at
+// least 240 tiles and the fill term), 2 = every eligible whole-layer call (tests, measurements).
+inline bool dma256_images_mode_ok(int v) { return v >= 0 && v <= 2; }
+inline std::atomic<int> g_dma256_images{[] {
+  const char *e = getenv("TPP_HIP_DMA256_IMAGES");
+  const int v = e ? atoi(e) : 0;
+  return dma256_images_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_dma256_images_stats[4]; // such launches; tile rows, tile columns (256x256 tiles), B image (2 flat, 4 VNNI-4) of the latest
 // HALVES (xsmm_hip_set_f32_halves / TPP_HIP_F32_HALVES; gemm_plan.cpp choose_f32_halves, brgemm_f32_lw.hip launch_f32_lw_halves): 0 = off, 1 =
 // the rule (default: at least one 64x64 tile per CU), 2 = every eligible whole-layer call on the 64x64 + K2 f32 tile runs as two 64x32 + K2
 // workgroups per tile (the same bits).

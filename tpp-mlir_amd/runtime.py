@@ -121,6 +121,8 @@ _SIGNATURES = {
     "xsmm_hip_edge_k_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_edge_k8_bf16": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_edge_k8_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_dma256_images": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_dma256_images_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_f32_halves": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_f32_halves_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
@@ -407,6 +409,17 @@ class XsmmRuntime:
         its B image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_edge_k8_bf16_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_dma256_images(self, mode):
+        """large bf16 whole-layer calls with a flat or VNNI-4 B on the 256x256 tile (the same bits): 0 off (default), 1 the rule that sends
+        a VNNI-2 call there (at least 240 tiles of 256x256), 2 wherever eligible; returns the previous mode, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_dma256_images(mode)
+
+    def dma256_images_stats(self):
+        """(launches of a flat or VNNI-4 B on the 256x256 tile; tile rows, tile columns, B image - 2 flat, 4 VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_dma256_images_stats(out)
         return tuple(int(v) for v in out)
 
     def set_f32_halves(self, mode):
