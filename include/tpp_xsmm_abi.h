@@ -536,6 +536,31 @@ TPP_XSMM_EXPORT void xsmm_hip_chain_edge_stats(int64_t out[4]);
  * and edge-tile counters do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_chain_rounds(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_chain_rounds_stats(int64_t out[4]);
+/* Ragged-width layer chains, opt-in (environment: TPP_HIP_CHAIN_RAGGED; default 0 = off): a switch of its own - no other switch changes
+ * meaning: xsmm_hip_set_chain_edge still takes 0 and 1 and still leaves a ragged n or k call by call. mode 1: a bf16 chain of 2 .. 8 calls
+ * runs as ONE launch on ceil(m / BM) x ceil(n / BN) workgroups when every call is beta 0, stores no VNNI C and is not forced to a kernel
+ * (the generic kernel included); all calls have the same m, n and B image (VNNI-2, flat or VNNI-4); every call's leading dimensions, strides
+ * and alignment are those the edge tiles ask (xsmm_hip_set_edge_tiles) with the k term replaced by "k >= 64 and k % 8 == 0" - per layer k
+ * may be whole (k % 64 == 0), a multiple of 16, or a multiple of 8; n % 8 == 0, m >= BM, n >= BN, every batch count >= 1; at least one of
+ * n % BN != 0 or some k % 64 != 0 holds (m may be ragged or not); ceil(m / BM) * ceil(n / BN) <= the stream's compute units; the runtime
+ * is not in strict mode - and everything else the chain launch asks holds as before (each call reads its predecessor's output, batch
+ * elements inside the predecessor's rows, device pointers, no overlaps, asynchronous mode, no stream capture). The rule is asked only
+ * where the other rules refuse because of n or k: a chain ragged in m alone stays xsmm_hip_set_chain_edge's, a divisible chain the plain
+ * chain's, and the multi-round switch never combines with this one (more tiles than compute units: call by call). The tile: the one
+ * xsmm_hip_set_edge_tiles(20 .. 23) names if it fits, else the smallest of the four that fits; the 64x128 tile has no VNNI-2 instance in
+ * this mode (it would need scratch) and is passed over for such chains. Rows as under xsmm_hip_set_chain_edge; the last column tile is
+ * shifted back to end at column n and stores only its own columns; every batch element of a layer is ceil(k / 64) chunks, the last one
+ * shifted back to end at k, the k-values it holds again skipped in half steps of 8. Bit for bit the same calls made one by one on that
+ * tile under xsmm_hip_set_edge_tiles / _edge_k_bf16 / _edge_k8_bf16 (the same k-values in the same order, one rounding). Two regions
+ * measured slower as one launch and stay call by call unless an edge-tile mode forces a tile (profiles/chain_ragged_ab.txt): a VNNI-2
+ * chain whose tile by the rule would be 64x128 and that would land on 128x128 (2000 rows x 1000: +13 %), and a chain with a whole-k layer
+ * of an even chunk count on the 32x64 or 64x64 tile (1024 rows x [1024, 1000, 1000]: +3.5 %). A starved launch
+ * degrades as every chain launch. Returns the previous value, -1 (nothing changed) for any other value.
+ * _stats: out[0] ragged-width chain launches since process start; of the most recent one: [1] tile rows ceil(m / BM), [2] tile columns
+ * ceil(n / BN), [3] the variant number of its tile with its B image (20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4). The chain-edge,
+ * chain-rounds and single-call edge counters do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_ragged(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_ragged_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

@@ -50,6 +50,7 @@
 #include "brgemm_bf16_lw_chain_rounds.h"
 #include <type_traits>
 #include <utility>
+#include "brgemm_bf16_lw_chain_ragged.h"
 
 namespace tpp {
 
@@ -104,7 +105,11 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   // number of image rows and a multiple of 16 bytes because k % 16 == 0.
   // GRP = 6 (RAGGED k in HALF steps): GRP = 4 to this function - k % 8 == 0 keeps the shifted start 16 bytes into an A row and on a whole
   // pair-row / group row / flat row of B.
-  constexpr bool KEDGE = blw_ragged_k(GRP);
+  // GRP = 8 (a RAGGED-WIDTH chain, brgemm_bf16_lw_chain_ragged.h): GRP = 5's rows and seam wait, GRP = 3's columns, and per LAYER GRP = 4's
+  // chunks - bkedge_chunks(k) per batch element, the last one shifted back; a whole k (k % 64 == 0) is the same walk with an advance of 64
+  // into the last chunk. The ring is carried from layer to layer (s0); the B loader does not run ahead across a seam in this mode.
+  constexpr bool CRAG = blw_chain_ragged(GRP);
+  constexpr bool KEDGE = blw_ragged_k(GRP) || CRAG;
   // GRP = 5 (a CHAIN on edge ROW tiles, brgemm_bf16_lw_chain_edge.h): the argument block's operands as GRP = 0, m0 of the last row block
   // shifted back by the kernel; the seam wait of a shifted block is for TWO row blocks' producers (below)
   // GRP = 7 (a chain in SEVERAL ROUNDS, brgemm_bf16_lw_chain_rounds.h): `tm` arrives as the workgroup's row GROUP g; the loop below runs
@@ -122,7 +127,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   static_assert(PPC >= 1 && (IS_A ? BM / 8 : BN / 8) % NL == 0 && (!IS_A || NL == 1 || NL % 2 == 0), "panel instructions divide over the loader waves");
   static_assert(NSLOT >= 3 && NSLOT_C % SUP == 0 && (NSLOT - 1) * PPL <= 63, "ring depth / vmcnt is 6 bits");
   bool ahead = false;
-  if (MULTI && !IS_A) {
+  if (MULTI && !IS_A && !CRAG) {
     ahead = true;
     for (int l = 0; l < L; ++l) {
       const int Tl = p.L[l].br * (p.L[l].k / BLW_BK) / SUP;
@@ -188,7 +193,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
     /* one chunk per batch element (the compiler's 64-k tile invokes over packed blocks): EVERY advance is the wrap - the same   */ \
     /* single add as the flat case, instead of a count-and-branch per chunk in the loader's instruction stream, which sets the */ \
     /* pace of the small tiles (32x32 + K2 grouped at K = 4096: 8.97 -> see profiles/r06_bf16_loader_advance_ab.txt)            */ \
-    if (kchunks == 1) d_in = d_wrap;                                                                                   \
+    if (!CRAG && kchunks == 1) d_in = d_wrap; /* (GRP = 8: d_in stays 64 k-values, per_k_ below is taken from it) */    \
     flat = d_wrap == d_in;                                                                                             \
     if constexpr (KEDGE) { /* d_in is  64 k-values in the panel's units: the batch elements never continue each other */ \
       const int64_t per_k_ = d_in / BLW_BK;                                                                            \
@@ -252,8 +257,8 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       // blocks b_first .. b_last - row block tm itself and, for the shifted last block of a RAGGED-m chain, its upper neighbour as well
       // (each block stores its OWN rows only). Every one of their counters must have reached the target; all the waits share ONE time
       // bound and the one error word.
-      const int b_first = GRP == BLW_CHAIN_EDGE ? chain_edge_first_block(tm, p.tiles_m, p.m, BM) : tm;
-      const int b_last = GRP == BLW_CHAIN_EDGE ? chain_edge_last_block(tm, p.tiles_m, p.m, BM) : tm;
+      const int b_first = GRP == BLW_CHAIN_EDGE || CRAG ? chain_edge_first_block(tm, p.tiles_m, p.m, BM) : tm;
+      const int b_last = GRP == BLW_CHAIN_EDGE || CRAG ? chain_edge_last_block(tm, p.tiles_m, p.m, BM) : tm;
       const unsigned target = p.target;
       const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
       for (int bw = b_first; bw <= b_last; ++bw) {
@@ -311,7 +316,8 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
     if (lc + 1 == L && !more_rounds) return;
     if constexpr (WK > 1) __builtin_amdgcn_s_barrier(); // R1 (K groups combine)
     __builtin_amdgcn_s_barrier();                        // S1 (tile stored and drained)
-    s0 = (s0 + T) % NSLOT;
+    if constexpr (CRAG) s0 = chain_ragged_next_s0(s0, p.L[lc].k, p.L[lc].br, NSLOT); // (the schedule's own function: the MFMA waves count the same way)
+    else s0 = (s0 + T) % NSLOT;
   }
 #undef BLW_ISSUE
 #undef BLW_LOAD_STATE
@@ -332,7 +338,12 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // GRP = 6 (RAGGED k in HALF steps, xsmm_hip_set_edge_k8_bf16): GRP = 4 in every respect - edge rows and columns, ring, loader advance,
   // laps and pairs of untested bodies - for a k that is a multiple of 8 but not of 16: the overlap of the last chunk ends in the middle
   // of a k-step, and that one step multiplies its upper eight k-values only (chunk_ke below, KE = 2)
-  constexpr bool KEDGE = blw_ragged_k(GRP), ROUNDS = GRP == BLW_CHAIN_ROUNDS;
+  // GRP = 8 (a RAGGED-WIDTH chain, xsmm_hip_set_chain_ragged; brgemm_bf16_lw_chain_ragged.h): MULTI on ceil(m / BM) x ceil(n / BN) workgroups -
+  // GRP = 5's rows and seam wait, GRP = 3's columns (the last column tile shifted back to n - BN, stores predicated on own_col, bias read at
+  // the shifted n0), and per layer GRP = 6's K loop with the LAYER's skip in half steps: 0 for a whole k (every step WHOLE: what the plain
+  // chain multiplies), even for k % 16 == 0, odd for k % 16 == 8 - one instance serves the three k classes. A layer starts at any ring slot.
+  constexpr bool CRAG = blw_chain_ragged(GRP);
+  constexpr bool KEDGE = blw_ragged_k(GRP) || CRAG, ROUNDS = GRP == BLW_CHAIN_ROUNDS;
   constexpr bool EDGE_ROWS = blw_edge_rows(GRP), EDGE_COLS = blw_edge_cols(GRP); // (the last tile of a column / row of tiles is shifted back)
   // GRP = 7 (a chain in SEVERAL ROUNDS, xsmm_hip_set_chain_rounds): MULTI on p.groups x tiles_n workgroups, fewer than the output tiles -
   // workgroup (g, tn) walks the row blocks g, g + groups, .. of every layer, layer-major (the file's header; brgemm_bf16_lw_chain_rounds.h).
@@ -442,7 +453,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // columns [0, n); the tile stores the rows >= own_row and the 16-byte pieces at columns >= own_col of its block (TILE-relative: the
   // tiles have several wave columns) - the others are the neighbour's. n0 is a multiple of 8 (the planner asks for n % 8 == 0).
   // (GRP = 7: tm is the workgroup's row GROUP up to here; the step loops below and in blw_loader take tm and m0 from the step)
-  int m0 = GRP == BLW_CHAIN_EDGE ? chain_edge_row0(tm, p.tiles_m, p.m, BM) : (EDGE_ROWS && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
+  int m0 = GRP == BLW_CHAIN_EDGE || CRAG ? chain_edge_row0(tm, p.tiles_m, p.m, BM) : (EDGE_ROWS && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
   const int n0 = (EDGE_COLS && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
   [[maybe_unused]] const int skip_cols = tn * BN - n0;
   [[maybe_unused]] const int own_row = tm * BM - m0, own_col = tn * BN - n0;
@@ -691,9 +702,14 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
         // and skips skipl k-steps. Laps of the ring / pairs of chunks that hold no last chunk run the untested bodies of the plain
         // kernel - single basic blocks -, the others and the layer's tail ask per step.
         // GRP = 6: skipl counts HALF steps and the tested bodies are the three-way ones (KE = 2); the loops are the same.
-        const int kchunks = bkedge_chunks(p.L[l].k);
-        const int skipl = blw_half_steps(GRP) ? bkedge8_skip_halves(p.L[l].k, kchunks - 1) : bkedge_skip_steps(p.L[l].k, kchunks - 1);
-        using KE_T = std::integral_constant<int, blw_half_steps(GRP) ? 2 : 1>; // KE of the tested bodies
+        // (GRP = 8: the chunks up to the next TESTED one - a whole-k layer has none, chain_ragged_test_period)
+        const int kchunks = CRAG ? chain_ragged_test_period(p.L[l].k, T) : bkedge_chunks(p.L[l].k);
+        // GRP = 8: a layer of a chain - kchunks and skipl are THIS layer's (skipl in half steps, 0 for a whole k), and slot starts at s0, any
+        // slot: the lap loop below begins only at slot 0 and the chunk-by-chunk loop walks there; the tiles with two fragment sets first
+        // run an odd first chunk on set 1, as the plain chain does.
+        const int skipl = CRAG ? chain_ragged_layer_skip(p.L[l].k)
+                          : blw_half_steps(GRP) ? bkedge8_skip_halves(p.L[l].k, kchunks - 1) : bkedge_skip_steps(p.L[l].k, kchunks - 1);
+        using KE_T = std::integral_constant<int, blw_half_steps(GRP) || CRAG ? 2 : 1>; // KE of the tested bodies
         int kc = 0;
         auto skip_next = [&]() __attribute__((always_inline)) {
           const bool last = kc + 1 == kchunks;
@@ -724,6 +740,15 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
           }
           chunk_ke(P0{}, N{}, slot, t, T, KE_T{}, skip_next());
         } else {
+          if constexpr (CRAG) {
+            // (an odd first slot: after a layer with an odd chunk count. With this body the 64x128 tile's VNNI-2 instance spills 76 bytes
+            // per lane - it is at 256 VGPRs as a plain chain already - and is left out of the mode's table, brgemm_bf16_lw_launch.h)
+            if (slot & 1) {
+              chunk_ke(P1{}, R{}, slot, t, T, KE_T{}, skip_next());
+              slot = next(slot);
+              ++t;
+            }
+          }
           while (t + 2 < T) {
             // (a loop of its own for the untested pairs: as the other arm of one loop's body they cost a copy of the accumulators per pair)
             while (t + 2 < T && kc + 2 < kchunks) {
@@ -800,7 +825,8 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
         }
       }
     }
-    s0 = (s0 + T) % NSLOT;
+    if constexpr (CRAG) s0 = chain_ragged_next_s0(s0, p.L[l].k, p.L[l].br, NSLOT);
+    else s0 = (s0 + T) % NSLOT;
     // the fragments prefetched past the end of the layer are dead: without this the compiler sinks their reads
 #pragma unroll
     for (int s = 0; s < (FULLPF ? NFB : PD); ++s) {
@@ -978,6 +1004,9 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   return hipGetLastError();
 }
 
+// (brgemm_bf16_lw_chain_ragged.hip includes this file for the kernel, the loader and launch_blw_t alone: the launchers and the 120 instances
+// of the launch table below are this translation unit's)
+#ifndef BLW_KERNEL_ONLY
 // THE DISPATCHER: the instance of a compile-time (MULTI, GRP) for a run-time (tile, sup, b_kind), through the tile table of
 // brgemm_bf16_lw_launch.h. Combination I of the 5 tiles x 3 B images x 2 chunks per barrier is compiled only where blw_instance_exists
 // says so; everything else is refused with hipErrorInvalidValue.
@@ -1083,5 +1112,6 @@ hipError_t launch_bf16_chain(int mode, int tile, int b_kind, const ChainArgs &a,
   default: return hipErrorInvalidValue;
   }
 }
+#endif // BLW_KERNEL_ONLY
 
 } // namespace tpp

@@ -4,6 +4,7 @@
 // (tests/test_blw_launch_table.py) all include this file. Nothing here needs a device: it compiles with any C++17 host compiler.
 #pragma once
 #include "brgemm_bf16_lw_kedge.h"
+#include "brgemm_bf16_lw_chain_ragged.h"
 
 namespace tpp {
 
@@ -18,27 +19,32 @@ constexpr int BLW_CHAIN_EDGE = 5;   // a chain whose m the tile's rows do not di
 constexpr int BLW_KEDGE8 = 6;       // BLW_KEDGE in half steps: k a multiple of 8 but not of 16 (xsmm_hip_set_edge_k8_bf16)
 constexpr int BLW_CHAIN_ROUNDS = 7; // a chain on fewer resident workgroups than output tiles (xsmm_hip_set_chain_rounds)
 constexpr int BLW_MODES = 8;
+// A ragged-WIDTH chain (xsmm_hip_set_chain_ragged): a mode BESIDE the table - blw_instance_exists and blw_launch_ok go on refusing it, its
+// instances live in a translation unit of their own (brgemm_bf16_lw_chain_ragged.hip) and have their own predicates at the end of this file
+constexpr int BLW_CHAIN_RAGGED = 8; // a chain with a ragged n and / or a k that is a multiple of 8 but not of 64 in some layer
 
 // what follows from a mode
 constexpr bool blw_items(int g) { return g == BLW_ITEMS || g == BLW_QUADS; }      // operands and batch count come from an item
 constexpr bool blw_ragged_k(int g) { return g == BLW_KEDGE || g == BLW_KEDGE8; }  // the last chunk of a batch element is shifted back
+constexpr bool blw_chain_ragged(int g) { return g == BLW_CHAIN_RAGGED; }         // every layer its own k class, tested in half steps
 constexpr bool blw_half_steps(int g) { return g == BLW_KEDGE8; }                  // ... and its overlap ends in the middle of a k-step
 // the last row block is shifted back to end at row m and stores its own rows only
-constexpr bool blw_edge_rows(int g) { return g == BLW_EDGE || blw_ragged_k(g) || g == BLW_CHAIN_EDGE; }
-// the last column tile is shifted back to end at column n (a ragged chain's columns are whole tiles)
-constexpr bool blw_edge_cols(int g) { return g == BLW_ITEMS || g == BLW_EDGE || blw_ragged_k(g); }
+constexpr bool blw_edge_rows(int g) { return g == BLW_EDGE || blw_ragged_k(g) || g == BLW_CHAIN_EDGE || blw_chain_ragged(g); }
+// the last column tile is shifted back to end at column n (a ragged-m chain's columns are whole tiles, a ragged-width chain's are not)
+constexpr bool blw_edge_cols(int g) { return g == BLW_ITEMS || g == BLW_EDGE || blw_ragged_k(g) || blw_chain_ragged(g); }
 constexpr bool blw_chain(int g) { return g == BLW_CHAIN_EDGE || g == BLW_CHAIN_ROUNDS; } // a chain by itself (BLW_LAYER: either)
-constexpr bool blw_one_chunk(int g) { return blw_ragged_k(g) || blw_chain(g); }   // one chunk per barrier only (SUP = 1)
+constexpr bool blw_one_chunk(int g) { return blw_ragged_k(g) || blw_chain(g) || blw_chain_ragged(g); }   // one chunk per barrier only (SUP = 1)
 // the combinations of mode, MULTI and SUP the kernel and the loader are written for
 constexpr bool blw_mode_ok(int g, bool multi, int sup) {
   return g >= 0 && g < BLW_MODES && (multi ? g == BLW_LAYER || blw_chain(g) : !blw_chain(g)) && (!blw_one_chunk(g) || sup == 1);
 }
 template <int GRP, bool MULTI, int SUP> struct BlwModeCheck {
-  static_assert(GRP >= 0 && GRP < BLW_MODES, "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds");
-  static_assert(!MULTI || GRP == BLW_LAYER || blw_chain(GRP), "a grouped launch is a set of single layers");
+  static_assert((GRP >= 0 && GRP < BLW_MODES) || blw_chain_ragged(GRP), "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds, 8: a ragged-width chain");
+  static_assert(!MULTI || GRP == BLW_LAYER || blw_chain(GRP) || blw_chain_ragged(GRP), "a grouped launch is a set of single layers");
   static_assert(!blw_ragged_k(GRP) || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
   static_assert(!blw_chain(GRP) || (SUP == 1 && MULTI), "a ragged / multi-round chain: a chain, one chunk per barrier");
-  static constexpr bool ok = blw_mode_ok(GRP, MULTI, SUP);
+  static_assert(!blw_chain_ragged(GRP) || (SUP == 1 && MULTI), "a ragged-width chain: a chain, one chunk per barrier");
+  static constexpr bool ok = blw_chain_ragged(GRP) ? MULTI && SUP == 1 : blw_mode_ok(GRP, MULTI, SUP);
 };
 
 // THE TILES. 0 = 32x64 + K2, 1 = 64x64, 2 = 64x128, 3 = 128x128, 4 = 32x32 + K2. Loader waves per tile (NLA + NLB), same-box A/B
@@ -101,6 +107,24 @@ constexpr bool blw_launch_ok(int mode, int tile, int b_kind, const BlwShape &a) 
   case BLW_CHAIN_ROUNDS: return edge_chain && a.m % bm == 0 && a.groups >= 1 && a.groups <= a.m / bm;
   default: return false;
   }
+}
+
+// THE RAGGED-WIDTH CHAIN (BLW_CHAIN_RAGGED, brgemm_bf16_lw_chain_ragged.hip): MULTI, one chunk per barrier. Is the instance of (tile, b_kind)
+// compiled? Tiles 0 .. 3 with the three B images, less ONE: the 64x128 tile with the VNNI-2 image needs 76 bytes of scratch per lane in
+// this mode (its plain chain instance is at 256 VGPRs already; the body for a layer that starts at an odd ring slot tips it over), so it
+// does not exist - eleven instances, none with scratch. The planner (gemm_plan.cpp plan_chain_ragged) never names it.
+constexpr bool blw_chain_ragged_instance_exists(int tile, int b_kind) { return tile >= 0 && tile <= 3 && blw_b_kind_ok(b_kind) && !(tile == 2 && b_kind == 0); }
+// ... and what its launcher refuses: 2 .. 8 layers, every one a batch of at least one element with k >= 64 and k % 8 == 0; m >= BM, n >= BN,
+// n % 8 == 0; ragged in n or in some layer's k (a chain ragged in m alone is BLW_CHAIN_EDGE's, a divisible one BLW_LAYER's)
+constexpr bool blw_chain_ragged_launch_ok(int tile, int b_kind, const BlwShape &a) {
+  if (!blw_chain_ragged_instance_exists(tile, b_kind) || a.nlayers < 2 || a.nlayers > BLW_MAXL) return false;
+  const int bm = BLW_TILES[tile].bm(), bn = BLW_TILES[tile].bn();
+  bool ragged = a.n % bn != 0;
+  for (int l = 0; l < a.nlayers; ++l) {
+    if (a.br[l] < 1 || !chain_ragged_k_ok(a.k[l])) return false;
+    if (a.k[l] % BKEDGE_BK != 0) ragged = true;
+  }
+  return ragged && a.m >= bm && a.n >= bn && a.n % 8 == 0;
 }
 
 } // namespace tpp

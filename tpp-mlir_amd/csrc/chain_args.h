@@ -52,6 +52,9 @@ hipError_t launch_bf16_lw(int mode, int tile, int b_kind, const ChainArgs &a, hi
 // a chain: BLW_LAYER, BLW_CHAIN_EDGE (xsmm_hip_set_chain_edge), BLW_CHAIN_ROUNDS (xsmm_hip_set_chain_rounds; a.groups row groups, the caller
 // guarantees groups * (n / BN) <= the stream's compute units)
 hipError_t launch_bf16_chain(int mode, int tile, int b_kind, const ChainArgs &a, hipStream_t s);
+// a ragged-WIDTH chain (brgemm_bf16_lw_chain_ragged.hip, BLW_CHAIN_RAGGED, xsmm_hip_set_chain_ragged): ceil(m / BM) x ceil(n / BN) workgroups,
+// at most the stream's compute units (the caller's guarantee); per layer k >= 64 and k % 8 == 0; blw_chain_ragged_launch_ok is what it refuses
+hipError_t launch_bf16_chain_ragged(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2; b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);

@@ -508,6 +508,61 @@ ChainEdgePlan plan_chain_edge(int64_t m, int64_t n, int nlayers, const int64_t *
   return ChainEdgePlan{tile, ""};
 }
 
+int chain_ragged_b_kind(const GemmDesc &d, int chain_ragged, const char **why) {
+  const char *w = nullptr;
+  int kind = -1;
+  if (!chain_ragged) w = "ragged-width chains are off (xsmm_hip_set_chain_ragged)";
+  else if (d.dtype != DT_BF16) w = "a ragged-width chain is bf16: an f32 call";
+  else if (d.vnni_c || !d.beta0) w = "a call of a ragged-width chain stores a VNNI C or is not beta 0";
+  else if (d.generic_forced || d.variant_forced) w = "a call of a ragged-width chain was dispatched to a forced kernel";
+  else if (!chain_ragged_k_ok(d.k)) w = "a call of a ragged-width chain has k below 64 or not a multiple of 8";
+  else {
+    GemmDesc e = d; // bf16_edge_b_kind's terms for leading dimensions, strides and lane offsets; its k term is the one above
+    e.k = BK;
+    if ((kind = bf16_edge_b_kind(e)) < 0) w = "a call of a ragged-width chain has an operand off the grid of the LDS-DMA tiles";
+  }
+  if (why) *why = w;
+  return w ? -1 : kind;
+}
+
+ChainRaggedPlan plan_chain_ragged(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, int b_kind, int mode, bool strict) {
+  if (mode != 1) return ChainRaggedPlan{-1, "ragged-width chains are off (xsmm_hip_set_chain_ragged)"};
+  if (strict) return ChainRaggedPlan{-1, "strict mode: the tile of a ragged-width chain is not a function of the descriptor alone"};
+  if (nlayers < 2 || nlayers > 8) return ChainRaggedPlan{-1, "fewer than 2 or more than 8 calls"};
+  bool k_ragged = false;
+  for (int l = 0; l < nlayers; ++l) {
+    if (!chain_ragged_k_ok(k[l]) || br[l] < 1) return ChainRaggedPlan{-1, "a layer of a ragged-width chain has k below 64 or not a multiple of 8, or an empty batch"};
+    if (k[l] % BK != 0) k_ragged = true;
+  }
+  if (n % 8 != 0) return ChainRaggedPlan{-1, "a ragged-width chain's n is not a multiple of 8"};
+  auto tiles = [&](int t) { return ((m + BLW_BM[t] - 1) / BLW_BM[t]) * ((n + BLW_BN[t] - 1) / BLW_BN[t]); };
+  auto fits = [&](int t) { return t >= 0 && t <= 3 && blw_chain_ragged_instance_exists(t, b_kind) && m >= BLW_BM[t] && n >= BLW_BN[t] && tiles(t) <= cus; };
+  int tile = fits(forced_tile) ? forced_tile : -1;
+  const bool forced = forced_tile >= 0 && forced_tile <= 3; // (tests and measurements: under a forcing edge-tile mode nothing is gated, whichever tile fits)
+  for (int t = 0; t < 4 && tile < 0; ++t)
+    if (fits(t)) tile = t;
+  if (tile >= 0 && !k_ragged && n % BLW_BN[tile] == 0) return ChainRaggedPlan{-1, "the tile's columns divide n and every k is in 64-k chunks: not a ragged-width chain"};
+  // THE GATE (measured, profiles/chain_ragged_ab.txt: 2000 rows of three 1000-wide VNNI-2 layers on 256 CUs, call by call 30.98 -> one
+  // launch 35.07 us): a chain whose tile by the rule would be 64x128 - it fits, no smaller tile does - but whose B image has no instance
+  // of that tile (VNNI-2: it would need scratch) lands on 128x128 with half the workgroups, while its separate calls run on 64x128. It
+  // stays call by call. Not under a forcing edge-tile mode.
+  if (!forced && tile == 3 && !blw_chain_ragged_instance_exists(2, b_kind) && blw_b_kind_ok(b_kind) && m >= BLW_BM[2] && n >= BLW_BN[2] && tiles(2) <= cus)
+    return ChainRaggedPlan{-1, "gate: the rule's 64x128 tile has no instance for this B image and 128x128 in its place measured slower than call by call (profiles/chain_ragged_ab.txt)"};
+  // THE SECOND GATE (same file: 1024 rows x [1024, 1000, 1000], layer 0 sixteen batch elements of 64, call by call 14.37 -> one launch 14.87 us,
+  // every pair slower): a whole-k layer with an even chunk count runs as a single call with TWO chunks per barrier on the 32x64 and 64x64
+  // tiles (blw_tile_sup2), this mode has one chunk per barrier only. A chain with such a layer on such a tile stays call by call.
+  if (!forced && tile >= 0 && blw_tile_sup2(tile))
+    for (int l = 0; l < nlayers; ++l)
+      if (k[l] % BK == 0 && ((br[l] * (k[l] / BK)) & 1) == 0)
+        return ChainRaggedPlan{-1, "gate: a whole-k layer that runs two chunks per barrier as a single call measured slower in a ragged-width chain (profiles/chain_ragged_ab.txt)"};
+  if (tile < 0) {
+    if (!blw_b_kind_ok(b_kind)) return ChainRaggedPlan{-1, "the calls of a ragged-width chain do not share one B image"};
+    if (m < BLW_BM[0] || n < BLW_BN[0]) return ChainRaggedPlan{-1, "a ragged-width chain's m or n is below every tile"};
+    return ChainRaggedPlan{-1, "more tiles than compute units (a ragged-width chain runs in one round)"};
+  }
+  return ChainRaggedPlan{tile, ""};
+}
+
 int chain_rounds_planned_tile(int n, const GemmDesc *const *d) {
   for (int i = 0; i < n; ++i)
     if (d[i]->dtype != DT_BF16) return -2;

@@ -134,6 +134,25 @@ int chain_edge_b_kind(const GemmDesc &d, int chain_edge, const char **why);
 // chain's rules decide).
 struct ChainEdgePlan { int tile; const char *why; };
 ChainEdgePlan plan_chain_edge(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, bool strict);
+// RAGGED-WIDTH CHAINS (xsmm_hip_set_chain_ragged; rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_ragged.hip launch_bf16_chain_ragged,
+// BLW_CHAIN_RAGGED, schedule in brgemm_bf16_lw_chain_ragged.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_ragged.txt is the table of
+// both functions' answers.
+// One call of a chain: the B image (0 VNNI-2, 2 flat, 4 VNNI-4) it would run with as a layer of a ragged-width chain - what chain_edge_b_kind
+// asks, with the k term replaced by "k >= 64 and k % 8 == 0" (whole, a multiple of 16, or a multiple of 8 per layer) -, or -1 and *why: the
+// switch is off, an f32 call, a VNNI C, beta 1, a forced kernel (the generic kernel included), such a k, an operand off the LDS-DMA grid.
+int chain_ragged_b_kind(const GemmDesc &d, int chain_ragged, const char **why);
+// The tile of the ONE launch: arguments as plan_chain_edge's + mode = the switch's value and b_kind = the B image every call has. A tile
+// FITS when its instance exists (blw_chain_ragged_instance_exists: not 64x128 with VNNI-2), m >= BM, n >= BN and ceil(m / BM) * ceil(n / BN)
+// <= cus. The forced tile if it fits, else the smallest of tiles 0 .. 3 that fits. tile = -1 and why = the reason: the switch off, strict
+// mode, fewer than 2 or more than 8 layers, a k below 64 or not a multiple of 8, an empty batch, n % 8 != 0, no tile fits (m or n below
+// every tile, more tiles than compute units - the multi-round switch never combines with this one), or nothing is ragged in width on the
+// chosen tile - n % BN == 0 and every k % 64 == 0: a chain ragged in m alone is plan_chain_edge's, a divisible one the plain chain's.
+// THE GATE (measured, profiles/chain_ragged_ab.txt): a chain whose tile by the rule would be 64x128 but whose B image has no instance of it
+// (VNNI-2) and that would land on 128x128 stays call by call - 2000 rows x 1000 ran 13 % slower as one launch there; and a chain with a whole-k layer of an even chunk count on the
+// 32x64 or 64x64 tile stays call by call too - that layer runs two chunks per barrier as a single call, one in this mode: 1024 rows x [1024,
+// 1000, 1000] ran 3.5 % slower. Under a forcing edge-tile mode (forced_tile >= 0: tests, measurements) nothing is gated.
+struct ChainRaggedPlan { int tile; const char *why; };
+ChainRaggedPlan plan_chain_ragged(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, int b_kind, int mode, bool strict);
 // MULTI-ROUND CHAINS (xsmm_hip_set_chain_rounds; rt_chain.h try_chain_launch, brgemm_bf16_lw.hip launch_bf16_chain, BLW_CHAIN_ROUNDS, step maps in
 // brgemm_bf16_lw_chain_rounds.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_rounds.txt is the table of the function's answers.
 // A bf16 chain that meets every condition of the divisible chain but has MORE output tiles than compute units runs as one launch on

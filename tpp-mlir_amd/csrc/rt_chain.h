@@ -195,6 +195,34 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     for (int i = 1; i < n; ++i)
       if (chain_rounds_b_kind(*d[i]) != rounds_kind) rounds_kind = -1;
   }
+  // RAGGED WIDTH (xsmm_hip_set_chain_ragged, opt-in; gemm_plan.cpp plan_chain_ragged): asked only where the rules below end in NOCHAIN
+  // because of n or k - a call no loader-wave tile takes (k % 64, n % 64, planned on the generic kernel), no ragged-m launch (edge_why: a
+  // k % 64), plan_chain_edge's refusal (n not in whole column tiles). ragged_w() is the rule's answer, asked at most once: every call
+  // passes chain_ragged_b_kind with the same B image and plan_chain_ragged names a tile. ragw = the launch is the ragged-width one. With
+  // the switch off ragged_w() is false without a look at the calls and every NOCHAIN below is taken exactly as before.
+  const int chain_ragged = f32 ? 0 : g_chain_ragged.load(std::memory_order_relaxed);
+  int ragw_state = chain_ragged ? -1 : 0, ragw_tile = -1, ragw_kind = -1; // -1 not asked yet, 0 no, 1 yes
+  bool ragw = false;
+  auto ragged_w = [&]() {
+    if (ragw_state >= 0) return ragw_state == 1;
+    ragw_state = 0;
+    const char *w = nullptr;
+    ragw_kind = chain_ragged_b_kind(*d[0], chain_ragged, &w);
+    for (int i = 1; i < n && ragw_kind >= 0; ++i)
+      if (chain_ragged_b_kind(*d[i], chain_ragged, &w) != ragw_kind || d[i]->m != m || d[i]->n != nn) ragw_kind = -1; // (calls that differ in m or n: the loop below says so)
+    if (ragw_kind >= 0) {
+      int64_t ks[CH_MAXL], brs[CH_MAXL];
+      for (int i = 0; i < n; ++i) ks[i] = d[i]->k, brs[i] = br[i];
+      const int et = g_edge_tiles.load(std::memory_order_relaxed);
+      const ChainRaggedPlan rp = plan_chain_ragged(m, nn, n, ks, brs, stream_cus(s), et >= V_BF16_LW_32x64 && et <= V_BF16_LW_128x128 ? et - V_BF16_LW_32x64 : -1,
+                                                   ragw_kind, chain_ragged, cfg().strict.load(std::memory_order_relaxed));
+      w = rp.why;
+      ragw_tile = rp.tile;
+      if (rp.tile >= 0) ragw_state = 1;
+    }
+    if (!ragw_state && cfg().trace) fprintf(stderr, "[tpp-xsmm-hip] fused_brgemm_chain: no ragged-width launch (%s)\n", w ? w : "the calls' B operands differ in kind");
+    return ragw_state == 1;
+  };
   for (int i = 0; i < n; ++i) {
     const GemmDesc &g = *d[i];
     if (edge_on && !edge_why) {
@@ -209,13 +237,18 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     } else
     // every layer the same kind of B operand (VNNI-2, flat or VNNI-4: the B image is a template parameter of the launch)
     if (g.dtype != DT_BF16 || g.vnni_c || !g.beta0 || bf16_lw_b_kind(g) < 0 || bf16_lw_b_kind(g) != bf16_lw_b_kind(*d[0])) {
-      if ((!edge_on || edge_why) && rounds_kind < 0) // (edge_why: no ragged launch either - an f32 call, a VNNI C, beta 1, a forced kernel, k % 64, the operands' grid)
-        NOCHAIN("a call is not bf16 / beta 0 / aligned for the LDS-DMA tiles, or the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)");
+      if ((!edge_on || edge_why) && rounds_kind < 0 && !ragw) { // (edge_why: no ragged launch either - an f32 call, a VNNI C, beta 1, a forced kernel, k % 64, the operands' grid)
+        if (ragged_w()) ragw = true;
+        else NOCHAIN("a call is not bf16 / beta 0 / aligned for the LDS-DMA tiles, or the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)");
+      }
       divisible = false;
     }
     if (g.m != m || g.n != nn || br[i] < 1) NOCHAIN("the calls differ in m or n, or a batch is empty");
     if (g.variant == V_GENERIC) { // (a forced generic kernel stays generic; one that is generic only because no tile divides m may run ragged)
-      if (!edge_on || edge_why || g.generic_forced) NOCHAIN("a call was dispatched to the generic kernel");
+      if ((!edge_on || edge_why || g.generic_forced) && !ragw) {
+        if (!g.generic_forced && ragged_w()) ragw = true;
+        else NOCHAIN("a call was dispatched to the generic kernel");
+      }
       divisible = false;
     }
     if (((uintptr_t)pa[i] | (uintptr_t)pb[i] | (uintptr_t)pc[i]) & 15) NOCHAIN("an operand is not 16-byte aligned");
@@ -228,7 +261,10 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (!devmem.is_device(pa[i], 0) || !devmem.is_device(pb[i], 1) || !devmem.is_device(pc[i], 2) || (g.bias && !devmem.is_device(pd[i], 3)))
       NOCHAIN("a host operand");
   }
-  if (!divisible && edge_why && rounds_kind < 0) NOCHAIN(edge_why);
+  if (!divisible && edge_why && rounds_kind < 0 && !ragw) {
+    if (ragged_w()) ragw = true;
+    else NOCHAIN(edge_why);
+  }
   // The tile: all workgroups must be co-resident (one per CU by LDS), so the grid may not exceed the CUs. If every layer was planned
   // with the same loader-wave tile and that tile fits, use it - the launch is then bit-identical to the separate launches; else
   // the smallest tile that fits (most CUs busy).
@@ -252,7 +288,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     tile = rp.tile;
     groups = rp.groups;
   };
-  if (!divisible && rounds_kind >= 0) { // (a forced G on calls only the one-round rules' m and n terms refuse)
+  if (!ragw && !divisible && rounds_kind >= 0) { // (a forced G on calls only the one-round rules' m and n terms refuse)
     shared_tile = chain_rounds_planned_tile(n, d);
     ask_rounds();
     if (tile >= 0) b_kind = rounds_kind;
@@ -278,6 +314,10 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
       if (tile < 0) NOCHAIN(rounds_mode == 1 ? rounds_why : "more tiles than compute units");
     }
   }
+  if (ragw) { // the ragged-width launch: the rule's tile and the calls' B image
+    tile = ragw_tile;
+    b_kind = ragw_kind;
+  }
   bool ragged = tile < 0; // (only with a switch on: every path to here with both off has a tile)
   if (ragged) {
     // the ragged launch: the tile a forcing edge-tile mode names if it fits, else the smallest that fits - counted on the ceil-divided grid
@@ -292,6 +332,11 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
       // the two switches never combine: the one-round ragged launch is asked first, and only a shape every tile of which divides - one
       // the ragged rule has just refused - may run in several rounds
       if (divisible && rounds_mode == 1) ask_rounds();
+      if (tile < 0 && !divisible && ragged_w()) { // (plan_chain_edge's refusal of calls no tile divides: n not in whole column tiles)
+        ragw = true;
+        tile = ragw_tile;
+        b_kind = ragw_kind;
+      }
       if (tile < 0) NOCHAIN(ep.why);
       ragged = false;
     }
@@ -348,7 +393,8 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (g_chain_shared.load(std::memory_order_acquire)) return false; // (found a starved launch: call by call from here on)
   }
   std::lock_guard<std::mutex> lk(g_chain_mu);
-  ChainBlock &blk = chain_block(s, (int)((m + bm - 1) / bm), (int)(nn / bn), n); // (a ragged chain: keyed on ceil(m / BM), the counters it uses)
+  // (a ragged chain: keyed on ceil(m / BM), the counters it uses; a ragged-width chain on ceil(n / BN) as well - the arrivals per counter)
+  ChainBlock &blk = chain_block(s, (int)((m + bm - 1) / bm), (int)(ragw ? (nn + bn - 1) / bn : nn / bn), n);
   c.cnt = blk.cnt;
   c.err = blk.err; // probation launches: the block's word (checked right behind the launch)
   if (blk.verified >= 1) {
@@ -366,7 +412,13 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   }
   c.target = ++blk.epoch * (unsigned)blk.tiles_n;
   if (f32) HIP_OK(launch_f32_chain(tile, c, s));
-  else if (groups > 0) {
+  else if (ragw) {
+    HIP_OK(launch_bf16_chain_ragged(tile, b_kind, c, s));
+    g_chain_ragged_stats[1].store((m + bm - 1) / bm, std::memory_order_relaxed);
+    g_chain_ragged_stats[2].store((nn + bn - 1) / bn, std::memory_order_relaxed);
+    g_chain_ragged_stats[3].store(blw_variant(tile, b_kind), std::memory_order_relaxed);
+    g_chain_ragged_stats[0].fetch_add(1, std::memory_order_relaxed);
+  } else if (groups > 0) {
     c.groups = groups;
     HIP_OK(launch_bf16_chain(BLW_CHAIN_ROUNDS, tile, b_kind, c, s));
     g_chain_rounds_stats[1].store(groups, std::memory_order_relaxed);

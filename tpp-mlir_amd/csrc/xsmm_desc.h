@@ -225,6 +225,17 @@ inline std::atomic<int> g_chain_rounds{[] {
   return chain_rounds_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_chain_rounds_stats[4]; // multi-round chain launches; row groups G, rounds R, GemmVariant of the tile (with its B image) of the latest
+// RAGGED-WIDTH CHAINS (xsmm_hip_set_chain_ragged / TPP_HIP_CHAIN_RAGGED; gemm_plan.cpp plan_chain_ragged, rt_chain.h try_chain_launch,
+// brgemm_bf16_lw_chain_ragged.h): 0 = off, 1 = a bf16 chain with a ragged n and / or a layer whose k is a multiple of 8 but not of 64 runs as
+// one launch on edge tiles with every layer's last chunk shifted back. A switch of its own: xsmm_hip_set_chain_edge keeps ragged-m-only
+// chains, the multi-round switch never combines with this one, the single-call ragged switches decide single calls only.
+inline bool chain_ragged_mode_ok(int v) { return v == 0 || v == 1; }
+inline std::atomic<int> g_chain_ragged{[] {
+  const char *e = getenv("TPP_HIP_CHAIN_RAGGED");
+  const int v = e ? atoi(e) : 0;
+  return chain_ragged_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_chain_ragged_stats[4]; // ragged-width chain launches; tile rows, tile columns (both ceil-divided), GemmVariant of the tile (with its B image) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

@@ -127,6 +127,8 @@ _SIGNATURES = {
     "xsmm_hip_f32_halves_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_chain_ragged": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_chain_ragged_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_rounds": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_rounds_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
@@ -443,6 +445,19 @@ class XsmmRuntime:
         28 + t VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_chain_edge_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_chain_ragged(self, mode):
+        """bf16 layer chains with a ragged n and / or a layer whose k is a multiple of 8 but not of 64 (1000-wide MLPs), as one launch on
+        edge tiles with every layer's last chunk shifted back: 0 off (default), 1 on - the tile set_edge_tiles(20 .. 23) names if it
+        fits, else the smallest that fits; returns the previous value, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_chain_ragged(mode)
+
+    def chain_ragged_stats(self):
+        """(ragged-width chain launches; tile rows ceil(m / BM), tile columns ceil(n / BN), variant number of the tile with its B image -
+        20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_chain_ragged_stats(out)
         return tuple(int(v) for v in out)
 
     def set_chain_rounds(self, mode):
