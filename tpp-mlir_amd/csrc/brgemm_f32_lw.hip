@@ -112,8 +112,15 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
   }
   const int m0 = tm * BM, n0 = tn * BN;
   const int nvalid = RAGN ? p.n - n0 : BN; // columns of this tile that exist (>= BN everywhere but in a ragged last tile)
-  const float *__restrict__ A = (const float *)it.A;
-  const float *__restrict__ B = (const float *)it.B;
+  // what the loader path reads of the arguments is fetched HERE, with the batch that the role test above needs - behind the branch
+  // the loaders paid a second, dependent argument-fetch round trip in front of their first request (the empty asm: the values exist
+  // from here on, the compiler cannot sink their loads into the branch)
+  const float *A_ = (const float *)it.A, *B_ = (const float *)it.B;
+  int lda = (int)p.lda, ldb = (int)p.ldb;
+  int64_t stride_a = p.stride_a, stride_b = p.stride_b;
+  asm volatile("" : "+s"(A_), "+s"(B_), "+s"(lda), "+s"(ldb), "+s"(stride_a), "+s"(stride_b));
+  const float *__restrict__ A = A_;
+  const float *__restrict__ B = B_;
   float *__restrict__ C = (float *)it.C;
   // GROUPED, k = 32 (the compiler's 32^3 tiles, mlir-gen --tiles=32,32,32): a 64-k chunk is the 32-k blocks of TWO consecutive
   // batch elements (even batch counts only: launch_gemm_grouped checks) - k 0..31 of the chunk image from element 2t, k 32..63
@@ -128,10 +135,17 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
 
   if (wave >= NMW) {
     // ---- loader waves --------------------------------------------------------------------
-    typename Tile::template Loader<NL, NLB> ld(wave - NMW, lane, A, B, m0, n0, (int)p.lda, (int)p.ldb, p.stride_a, p.stride_b, kchunks, pair, nvalid);
-    if constexpr (MAYSPLIT) ld.start_at(t_first);
+    typename Tile::template Loader<NL, NLB> ld(wave - NMW, lane, A, B, m0, n0, lda, ldb, stride_a, stride_b, kchunks, pair, nvalid);
+    if constexpr (MAYSPLIT) { // (the first chunk of a shared tile is not chunk 0: the whole setup before the first request)
+      ld.finish_setup();
+      ld.start_at(t_first);
+    }
     lw_loader_schedule<NSLOT>(T, [&](int slot) __attribute__((always_inline)) { ld.issue(slot); },
-                              [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); });
+                              [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); },
+                              [&]() __attribute__((always_inline)) {
+                                if constexpr (MAYSPLIT) ld.issue(0);
+                                else ld.issue_first();
+                              });
     return; // ended waves do not take part in later barriers
   }
 
@@ -173,17 +187,23 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
     }
   }
 
+  // the chunk loop's and the epilogue's address setup: above the barrier (brgemm_f32_lw_tile.h mfma_setup, tail_setup)
+  const auto fr = Tile::mfma_setup(w);
+  // (the SPLIT instances run at 99 .. 106 VGPRs: their epilogue keeps its addresses where they were)
+  const auto tl = Tile::template tail_setup<!SPLIT>(w, (int)p.ldc);
+  const int Tp = Tile::pin_chunks(T);
+
   __builtin_amdgcn_s_barrier(); // chunk 0 published
   __builtin_amdgcn_sched_barrier(0);
-  if (T > 0) Tile::mfma_chunks(acc, T, w);
+  if (Tp > 0) Tile::mfma_chunks(acc, Tp, fr);
 
   if constexpr (WK > 1) {
-    Tile::park_partials(acc, w);
+    Tile::park_partials(acc, tl);
     if constexpr (!BIAS_EARLY) {
       if ((p.ep & EP_BIAS) && piece_ok) bias4 = *(const f32x4 *)((const float *)it.D + n0 + wn * 32 + 4 * (lane & 7));
     }
     f32x4 part[IPG];
-    Tile::sum_partials(part, w);
+    Tile::sum_partials(part, tl);
     if (MAYSPLIT && (!TAIL || is_tail)) {
       // park the partial tile: block [tile][split][piece], piece = (j * NMW + MFMA wave) * 64 + lane - every wave instruction writes
       // 1 KiB contiguous; the last workgroup reads the S blocks with the same lane mapping
@@ -222,10 +242,10 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw(
       }
 #pragma unroll
       for (int j = 0; j < IPG; ++j) { // ... + C (beta = 1)
-        if (!(p.ep & EP_BETA0) && piece_ok) part[j] += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrcC, Tile::piece_off(w, j, (int)p.ldc), 0, 0));
+        if (!(p.ep & EP_BETA0) && piece_ok) part[j] += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrcC, Tile::tail_off(tl, j), 0, 0));
       }
     }
-    Tile::finish(part, bias4, p.ep, rsrcC, (int)p.ldc, piece_ok, w);
+    Tile::finish(part, bias4, p.ep, rsrcC, piece_ok, tl);
     return;
   }
 #pragma unroll
@@ -293,7 +313,8 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + 2 * NL)) void brgemm_f32_lw_ch
         asm volatile("" ::: "memory");
       }
       lw_loader_schedule<LW_NSLOT>(Y.br * kchunks, [&](int slot) __attribute__((always_inline)) { ld.template issue<true>(slot, sc1); },
-                                   [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); }); // P, T - 1 mid-chunk barriers
+                                   [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); }, // P, T - 1 mid-chunk barriers
+                                   [&]() __attribute__((always_inline)) { ld.template issue_first<true>(sc1); });
       __builtin_amdgcn_s_barrier(); // R1
       __builtin_amdgcn_s_barrier(); // R2
       if (l + 1 < L) __builtin_amdgcn_s_barrier(); // S1
@@ -303,6 +324,10 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + 2 * NL)) void brgemm_f32_lw_ch
 
   // ---- MFMA waves ------------------------------------------------------------------------------------------------
   const typename Tile::Wave w(wave, lane);
+  // (the fragment addresses are the same for every layer: the ring restarts at slot 0. Held across the seams they cost the 64x64 + K2
+  // instance a wave per SIMD in the compiler's resource report: that instance keeps the setup where it was)
+  constexpr bool CHAIN_PIN = !(WM == 2 && WN == 2);
+  const auto fr = Tile::template mfma_setup<CHAIN_PIN>(w);
   for (int l = 0; l < L; ++l) {
     const ChainLayer &Y = p.L[l];
     const int ldc = (int)Y.ldc;
@@ -310,15 +335,17 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + 2 * NL)) void brgemm_f32_lw_ch
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    const auto tl = Tile::template tail_setup<CHAIN_PIN>(w, ldc); // at every seam: above the barrier, as in brgemm_f32_lw
+    const int T = Tile::template pin_chunks<CHAIN_PIN>(Y.br * (Y.k / LW_BK));
     __builtin_amdgcn_s_barrier(); // P
     __builtin_amdgcn_sched_barrier(0);
-    Tile::mfma_chunks(acc, Y.br * (Y.k / LW_BK), w);
+    Tile::mfma_chunks(acc, T, fr);
     // combine the K groups and store, exactly as brgemm_f32_lw does (group order; bias; relu; 16-byte write-through stores)
-    Tile::park_partials(acc, w); // R1, R2
+    Tile::park_partials(acc, tl); // R1, R2
     f32x4 bias4 = {0.0f, 0.0f, 0.0f, 0.0f}, part[Tile::IPG];
     if (Y.ep & EP_BIAS) bias4 = *(const f32x4 *)((const float *)Y.D + n0 + w.wn * 32 + 4 * (lane & 7));
-    Tile::sum_partials(part, w);
-    Tile::finish(part, bias4, Y.ep, rsrcC, ldc, true, w);
+    Tile::sum_partials(part, tl);
+    Tile::finish(part, bias4, Y.ep, rsrcC, true, tl);
     if (l + 1 == L) break;
     // ---- seam: publish this tile to the row block's consumers ---------------------------------------------------
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); // every storing wave drains its write-through stores (and is done with the parked partials)
@@ -352,16 +379,22 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw_
   const int tn = (int)(blockIdx.x & ((1u << p.xn_shift) - 1)) * p.tiles_n + (int)blockIdx.y;
   const int m0 = tm * BM < p.m - BM ? tm * BM : p.m - BM, n0 = tn * BN < p.n - BN ? tn * BN : p.n - BN;
   const int own_r = tm * BM - m0, own_c = tn * BN - n0; // 0, 0 for every tile but the last of a ragged row / column of tiles
-  const float *__restrict__ A = (const float *)p.A;
-  const float *__restrict__ B = (const float *)p.B;
+  // (the loader path's arguments in one batch above the role branch: brgemm_f32_lw)
+  const float *A_ = (const float *)p.A, *B_ = (const float *)p.B;
+  int lda = (int)p.lda, ldb = (int)p.ldb;
+  int64_t stride_a = p.stride_a, stride_b = p.stride_b;
+  asm volatile("" : "+s"(A_), "+s"(B_), "+s"(lda), "+s"(ldb), "+s"(stride_a), "+s"(stride_b));
+  const float *__restrict__ A = A_;
+  const float *__restrict__ B = B_;
   float *__restrict__ C = (float *)p.C;
   const int kchunks = p.k / LW_BK;
   const int T = p.br * kchunks;
 
   if (wave >= NMW) {
-    typename Tile::template Loader<NL, NLB> ld(wave - NMW, lane, A, B, m0, n0, (int)p.lda, (int)p.ldb, p.stride_a, p.stride_b, kchunks, false, BN);
+    typename Tile::template Loader<NL, NLB> ld(wave - NMW, lane, A, B, m0, n0, lda, ldb, stride_a, stride_b, kchunks, false, BN);
     lw_loader_schedule<NSLOT>(T, [&](int slot) __attribute__((always_inline)) { ld.issue(slot); },
-                              [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); });
+                              [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); },
+                              [&]() __attribute__((always_inline)) { ld.issue_first(); });
     return;
   }
 
@@ -395,18 +428,22 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw_
         acc[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrcC, voffC, (unsigned)((r & 3) + 8 * (r >> 2)) * ldcb, 0));
   }
 
+  const auto fr = Tile::mfma_setup(w); // (above the barrier: brgemm_f32_lw)
+  const auto tl = Tile::tail_setup(w, (int)p.ldc);
+  const int Tp = Tile::pin_chunks(T);
+
   __builtin_amdgcn_s_barrier(); // chunk 0 published
   __builtin_amdgcn_sched_barrier(0);
-  if (T > 0) Tile::mfma_chunks(acc, T, w);
+  if (Tp > 0) Tile::mfma_chunks(acc, Tp, fr);
 
   if constexpr (WK > 1) {
-    Tile::park_partials(acc, w);
+    Tile::park_partials(acc, tl);
     if constexpr (!BIAS_EARLY) {
       if (p.ep & EP_BIAS) bias4 = *(const f32x4 *)((const float *)p.D + n0 + wn * 32 + 4 * (lane & 7));
     }
     f32x4 part[IPG];
-    Tile::sum_partials(part, w);
-    Tile::finish_owned(part, bias4, p.ep, rsrcC, (int)p.ldc, own_r, own_c, w);
+    Tile::sum_partials(part, tl);
+    Tile::finish_owned(part, bias4, p.ep, rsrcC, own_r, own_c, w, tl);
     return;
   }
 #pragma unroll
@@ -440,17 +477,22 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw_
   const int tn = (int)(blockIdx.x & ((1u << p.xn_shift) - 1)) * p.tiles_n + (int)blockIdx.y;
   const int m0 = tm * BM < p.m - BM ? tm * BM : p.m - BM, n0 = tn * BN < p.n - BN ? tn * BN : p.n - BN;
   const int own_r = tm * BM - m0, own_c = tn * BN - n0; // 0, 0 for every tile but the last of a ragged row / column of tiles
-  const float *__restrict__ A = (const float *)p.A;
-  const float *__restrict__ B = (const float *)p.B;
+  // (the loader path's arguments in one batch above the role branch: brgemm_f32_lw)
+  const float *A_ = (const float *)p.A, *B_ = (const float *)p.B;
+  int lda = (int)p.lda, ldb = (int)p.ldb;
+  int64_t stride_a = p.stride_a, stride_b = p.stride_b;
+  asm volatile("" : "+s"(A_), "+s"(B_), "+s"(lda), "+s"(ldb), "+s"(stride_a), "+s"(stride_b));
+  const float *__restrict__ A = A_;
+  const float *__restrict__ B = B_;
   float *__restrict__ C = (float *)p.C;
   const int kchunks = kedge_chunks(p.k); // >= 2
   const int T = p.br * kchunks;
 
   if (wave >= NMW) {
-    typename Tile::template Loader<NL, NLB> ld(wave - NMW, lane, A, B, m0, n0, (int)p.lda, (int)p.ldb, p.stride_a, p.stride_b, kchunks, false, BN);
-    ld.ragged_k(p.k);
+    typename Tile::template Loader<NL, NLB> ld(wave - NMW, lane, A, B, m0, n0, lda, ldb, stride_a, stride_b, kchunks, false, BN);
     lw_loader_schedule<NSLOT>(T, [&](int slot) __attribute__((always_inline)) { ld.issue_ragged(slot); },
-                              [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); });
+                              [&](int chunks) __attribute__((always_inline)) { ld.wait_left(chunks); },
+                              [&]() __attribute__((always_inline)) { ld.issue_first_ragged(p.k); });
     return;
   }
 
@@ -484,18 +526,23 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NL + NLB)) void brgemm_f32_lw_
         acc[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrcC, voffC, (unsigned)((r & 3) + 8 * (r >> 2)) * ldcb, 0));
   }
 
+  // (not pinned above the barrier: the ragged laps need the registers - brgemm_f32_lw_tile.h mfma_setup)
+  const auto fr = Tile::template mfma_setup<false>(w);
+  const auto tl = Tile::template tail_setup<false>(w, (int)p.ldc);
+  const int Tp = T;
+
   __builtin_amdgcn_s_barrier(); // chunk 0 published
   __builtin_amdgcn_sched_barrier(0);
-  Tile::mfma_chunks_ragged(acc, T, kchunks, kedge_skip_blocks(p.k, kchunks - 1), w);
+  Tile::mfma_chunks_ragged(acc, Tp, kchunks, kedge_skip_blocks(p.k, kchunks - 1), fr);
 
   if constexpr (WK > 1) {
-    Tile::park_partials(acc, w);
+    Tile::park_partials(acc, tl);
     if constexpr (!BIAS_EARLY) {
       if (p.ep & EP_BIAS) bias4 = *(const f32x4 *)((const float *)p.D + n0 + wn * 32 + 4 * (lane & 7));
     }
     f32x4 part[IPG];
-    Tile::sum_partials(part, w);
-    Tile::finish_owned(part, bias4, p.ep, rsrcC, (int)p.ldc, own_r, own_c, w);
+    Tile::sum_partials(part, tl);
+    Tile::finish_owned(part, bias4, p.ep, rsrcC, own_r, own_c, w, tl);
     return;
   }
 #pragma unroll

@@ -27,8 +27,11 @@ extern __shared__ __attribute__((aligned(16))) float smem_lw[];
 // (Round 2 requested all three first: an LDS-DMA instruction takes ~25 ns to issue, a chunk is 16 of them per loader - the MFMA
 // waves waited ~0.4 us for requests they would not need for two chunk times; a chunk is 0.92 us of MFMA here, so the loader has
 // all the time it needs behind the barrier. Stamped on the bf16 twin of this kernel: profiles/r03_chain_anatomy.txt.)
-template <int NSLOT, class Issue, class Wait> __device__ __forceinline__ void lw_loader_schedule(int T, Issue &&issue, Wait &&wait_left) {
-  if (T > 0) issue(0);
+// first(): the request of chunk 0 into slot 0, for a loader that finishes its own setup behind it (Loader::issue_first) - the same
+// request in the same place of the schedule.
+template <int NSLOT, class Issue, class Wait, class First>
+__device__ __forceinline__ void lw_loader_schedule(int T, Issue &&issue, Wait &&wait_left, First &&first) {
+  if (T > 0) first();
   if (T > 1) issue(1);
   wait_left(T > 1 ? 1 : 0);
   __builtin_amdgcn_s_barrier(); // chunk 0 published
@@ -39,6 +42,18 @@ template <int NSLOT, class Issue, class Wait> __device__ __forceinline__ void lw
     if (t + NSLOT - 1 < T) issue((t + NSLOT - 1) % NSLOT); // the slot of chunk t-1: every MFMA wave is past it
   }
 }
+
+template <int NSLOT, class Issue, class Wait> __device__ __forceinline__ void lw_loader_schedule(int T, Issue &&issue, Wait &&wait_left) {
+  lw_loader_schedule<NSLOT>(T, issue, wait_left, [&]() __attribute__((always_inline)) { issue(0); });
+}
+
+// LDS byte address of a float of the ring, and back: the MFMA waves' setup (LwTile::mfma_setup, tail_setup) keeps addresses as plain
+// 32-bit numbers, which an empty asm can pin in a VGPR.
+typedef __attribute__((address_space(3))) float lds_float_lw;
+typedef __attribute__((address_space(3))) f32x4 lds_f32x4_lw;
+__device__ __forceinline__ unsigned lw_lds_addr(const float *p) { return (unsigned)(__SIZE_TYPE__)(const lds_float_lw *)p; }
+__device__ __forceinline__ lds_float_lw *lw_lds_float(unsigned a) { return (lds_float_lw *)(__SIZE_TYPE__)a; }
+__device__ __forceinline__ const lds_f32x4_lw *lw_lds_f32x4(unsigned a) { return (const lds_f32x4_lw *)(__SIZE_TYPE__)a; }
 
 // The tile of WM x WN MFMA waves (each ONE 32x32 accumulator) x WK wave groups that split every 64-k chunk, on an NSLOT-deep ring.
 // NSLOT: 4; 3 for the 128x64 tile, whose 48 KiB slots would not fit four times.
@@ -68,33 +83,55 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
 
     // lw: loader wave 0 .. NL + NLB - 1 (the A loaders first). pair: a 64-k chunk is the 32-k blocks of TWO consecutive batch
     // elements (brgemm_f32_lw, GROUPED). nvalid: columns of the tile that exist (a multiple of 4; >= BN: all).
+    // The constructor computes what the FIRST request needs and nothing else - the panel base, the lane offsets and steps of the
+    // wave's own panel: that request starts the longest latency of the launch, every instruction in front of it is on the critical
+    // path of every workgroup. What only the advance to the next chunk needs (d_in, d_batch, d_wrap: 64-bit multiplies) is
+    // finish_setup(), which issue_first() runs BEHIND the request.
     __device__ __forceinline__ Loader(int lw, int lane, const float *A, const float *B, int m0, int n0, int lda, int ldb, int64_t stride_a,
                                       int64_t stride_b, int kchunks_, bool pair, int nvalid)
         : isA(lw < NL), part(lw < NL ? lw : lw - NL), kc(0), kchunks(kchunks_) {
-      // per-lane source offsets, constant for the whole panel stream. A instruction v covers rows 4v .. 4v+3
-      // (lane -> row 4v + lane/16, 16-byte piece lane%16, XOR-ed with row&15 = 4(v&3) + lane/16: the
-      // fragment read applies the same XOR); the 16-row group v>>2 goes into the scalar offset.
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = 4 * j + (lane >> 4), pc = (lane & 15) ^ r; // 16-byte piece of the chunk's row: k 4 pc .. 4 pc + 3
-        voA[j] = (unsigned)((r * lda + (pair ? (pc >> 3) * (int)stride_a + 4 * (pc & 7) : 4 * pc)) * 4);
-      }
-      // NL = 2: this wave's instructions have v & 3 = part and part + 2 (NL = 4: always part)
+      for (int j = 0; j < 4; ++j) voA[j] = 0u;
+      voA2[0] = voA2[1] = voB = stepA = stepB = pairB = 0u;
+      if (isA) {
+        g = A + (int64_t)m0 * lda;
+        // per-lane source offsets, constant for the whole panel stream. A instruction v covers rows 4v .. 4v+3
+        // (lane -> row 4v + lane/16, 16-byte piece lane%16, XOR-ed with row&15 = 4(v&3) + lane/16: the
+        // fragment read applies the same XOR); the 16-row group v>>2 goes into the scalar offset.
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int r = 4 * (part + 2 * j) + (lane >> 4), pc = (lane & 15) ^ r;
-        voA2[j] = (unsigned)((r * lda + (pair ? (pc >> 3) * (int)stride_a + 4 * (pc & 7) : 4 * pc)) * 4);
+        for (int j = 0; j < 4; ++j) {
+          const int r = 4 * j + (lane >> 4), pc = (lane & 15) ^ r; // 16-byte piece of the chunk's row: k 4 pc .. 4 pc + 3
+          voA[j] = (unsigned)((r * lda + (pair ? (pc >> 3) * (int)stride_a + 4 * (pc & 7) : 4 * pc)) * 4);
+        }
+        // NL = 2: this wave's instructions have v & 3 = part and part + 2 (NL = 4: always part)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int r = 4 * (part + 2 * j) + (lane >> 4), pc = (lane & 15) ^ r;
+          voA2[j] = (unsigned)((r * lda + (pair ? (pc >> 3) * (int)stride_a + 4 * (pc & 7) : 4 * pc)) * 4);
+        }
+        stepA = (unsigned)(16 * lda * 4);
+      } else {
+        g = B + n0;
+        // (a ragged last tile: the 16-byte column pieces beyond n re-read the tile's last valid piece - in bounds, and the columns
+        // they feed are never stored)
+        const int pieceB = nvalid < BN ? (lane % (BN / 4) < nvalid / 4 ? lane % (BN / 4) : nvalid / 4 - 1) : lane % (BN / 4);
+        voB = (unsigned)(((lane / (BN / 4)) * ldb + 4 * pieceB) * 4);
+        stepB = (unsigned)(RPI * ldb * 4);
+        pairB = pair ? (unsigned)(((int)stride_b - 32 * ldb) * 4) : 0u; // rows 32.. of a pair chunk: the second element
       }
-      // (a ragged last tile: the 16-byte column pieces beyond n re-read the tile's last valid piece - in bounds, and the columns
-      // they feed are never stored)
-      const int pieceB = nvalid < BN ? (lane % (BN / 4) < nvalid / 4 ? lane % (BN / 4) : nvalid / 4 - 1) : lane % (BN / 4);
-      voB = (unsigned)(((lane / (BN / 4)) * ldb + 4 * pieceB) * 4);
-      stepA = (unsigned)(16 * lda * 4), stepB = (unsigned)(RPI * ldb * 4);
-      pairB = pair ? (unsigned)(((int)stride_b - 32 * ldb) * 4) : 0u; // rows 32.. of a pair chunk: the second element
-      g = isA ? A + (int64_t)m0 * lda : B + n0;
-      d_in = isA ? (int64_t)LW_BK : (int64_t)LW_BK * ldb;
-      d_batch = (isA ? stride_a : stride_b) * (pair ? 2 : 1);
-      d_wrap = d_batch - (int64_t)(kchunks - 1) * d_in;
+      ldb_ = ldb, stride_a_ = stride_a, stride_b_ = stride_b, pair_ = pair;
+    }
+    int ldb_;
+    int64_t stride_a_, stride_b_;
+    bool pair_;
+    // the rest of the setup: how the panel base advances. The empty asm makes kchunks a value that exists only from here on, so the
+    // compiler cannot lift the multiplies back above the request that issue_first() has just made.
+    __device__ __forceinline__ void finish_setup() {
+      int kch = kchunks;
+      asm volatile("" : "+s"(kch));
+      d_in = isA ? (int64_t)LW_BK : (int64_t)LW_BK * ldb_;
+      d_batch = (isA ? stride_a_ : stride_b_) * (pair_ ? 2 : 1);
+      d_wrap = d_batch - (int64_t)(kch - 1) * d_in;
     }
     // start at chunk t_first: batch element t_first / kchunks (pair mode: the pair t_first), k block t_first % kchunks
     __device__ __forceinline__ void start_at(int t_first) {
@@ -113,6 +150,16 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
     // request the next chunk of this wave's panel into ring slot `slot`. sc1 (MAY_SC1 instances only): the A rows were written by
     // other workgroups of THIS launch, another XCD's L2 may hold them - the aux bits stay a compile-time constant of each load.
     template <bool MAY_SC1 = false> __device__ __forceinline__ void issue(int slot, bool sc1 = false) {
+      request<MAY_SC1>(slot, sc1);
+      advance();
+    }
+    // the first request of a fresh loader (chunk 0 into slot 0), the rest of the setup behind it
+    template <bool MAY_SC1 = false> __device__ __forceinline__ void issue_first(bool sc1 = false) {
+      request<MAY_SC1>(0, sc1);
+      finish_setup();
+      advance();
+    }
+    template <bool MAY_SC1> __device__ __forceinline__ void request(int slot, bool sc1) const {
       float *base = smem_lw + slot * SLOT + (isA ? 0 : A_STAGE);
       const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)g, 0, 0x7fffffff, 0x00020000);
       if (isA) {
@@ -125,6 +172,8 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
           __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_lw *)(base + v * 256), 16, voB, (unsigned)v * stepB + (v * RPI >= 32 ? pairB : 0u), 0, 0);
         }
       }
+    }
+    __device__ __forceinline__ void advance() {
       if (++kc == kchunks) {
         kc = 0;
         g += d_wrap;
@@ -133,7 +182,7 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
       }
     }
     // RAGGED k (brgemm_f32_lw_kedge; the schedule: brgemm_f32_lw_kedge.h): kchunks = kedge_chunks(k) >= 2, the last chunk of every batch
-    // element starts at k - 64. ragged_k once behind the constructor, then issue_ragged for issue: the advance into an element's last
+    // element starts at k - 64. ragged_k once behind finish_setup (issue_first_ragged), then issue_ragged for issue: the advance into an element's last
     // chunk is k % 64 instead of 64 (issue has added 64: d_fix takes the overlap back), the batch wrap starts from k - 64.
     int64_t d_fix;
     __device__ __forceinline__ void ragged_k(int k) {
@@ -144,6 +193,14 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
     __device__ __forceinline__ void issue_ragged(int slot) {
       issue(slot);
       if (kc == kchunks - 1) g += d_fix; // the chunk now due is the element's last
+    }
+    // the first request of a fresh ragged-k loader: finish_setup and ragged_k behind it
+    __device__ __forceinline__ void issue_first_ragged(int k) {
+      request<false>(0, false);
+      finish_setup();
+      ragged_k(k);
+      advance();
+      if (kc == kchunks - 1) g += d_fix;
     }
     // s_waitcnt vmcnt(n chunks of this wave's DMA may still be in flight), n = 0 or 1
     __device__ __forceinline__ void wait_left(int chunks) const {
@@ -161,21 +218,73 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
 
   // The T > 0 chunks of one tile, from the "chunk 0 published" barrier (the caller's) to the last MFMA: one loop body per ring slot
   // (slot offsets are immediates), ONE raw s_barrier per chunk in the middle of the chunk's MFMAs, no vector memory instruction.
-  static __device__ __forceinline__ void mfma_chunks(f32x16 &acc, int T, const Wave &w) {
+  // The setup of the chunk loop - where this lane's fragments lie in the ring - depends on the wave and the lane only, not on chunk 0:
+  // mfma_setup() runs ABOVE the "chunk 0 published" barrier, while the wave waits for the loaders anyway, and pins every address in a
+  // register (an empty asm the compiler cannot look through: it would otherwise sink the arithmetic to the first use, below the
+  // barrier, where every CU pays for it in every launch with the data already there). Below the barrier stay the fragment reads.
+  // a[g][q]: LDS byte address of the lane's 16-byte A piece of k-block q of the wave's share, ring slot g * A_SPG - the A_SPG slots
+  // that the 16-bit offset of a ds_read_b128 reaches from there are immediates; b[slot][q]: its first B value of that block (the
+  // other three: rows + 1 .. 3, offsets of the ds_read2_b32) - the registers the compiler has always kept for the steady-state lap.
+  // PIN = false: nothing is computed ahead, load() is the expression the tile has always had and the compiler places the arithmetic
+  // as it always has - for the instances where holding every address costs a wave per SIMD in the compiler's resource report: the
+  // WK = 1 tiles (8 k-blocks per wave: 48 and 40 addresses) and the ragged-k kernels (profiles/f32_lw_head_tail_isa.txt).
+  static constexpr int A_SPG = (65535 - 15) / (SLOT * 4) + 1, A_GRP = (NSLOT + A_SPG - 1) / A_SPG;
+  static constexpr bool PIN_DEFAULT = WK > 1;
+  template <bool PIN> struct Frags {
+    unsigned a[PIN ? A_GRP : 1][KB_PER_WAVE], b[PIN ? NSLOT : 1][KB_PER_WAVE]; // (PIN only)
+    int kbw;                                                                    // first k-block of the wave's share of a chunk
+    int li, lh, a_off, b_off;                                                   // (PIN = false only)
+    __device__ __forceinline__ void load(f32x4 &fa, float (&fb)[4], int slot, int q) const { // q: k-block of the wave's share
+      if constexpr (PIN) {
+        fa = *lw_lds_f32x4(a[slot / A_SPG][q] + (unsigned)((slot % A_SPG) * SLOT * 4));
+        const lds_float_lw *bs = lw_lds_float(b[slot][q]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) fb[s] = bs[s * BN];
+      } else {
+        const int kb = kbw + q;
+        const float *as = smem_lw + slot * SLOT + a_off;
+        const float *bs = smem_lw + slot * SLOT + A_STAGE + b_off;
+        fa = *(const f32x4 *)(as + (((2 * kb + lh) ^ (li & 15)) << 2));
+#pragma unroll
+        for (int s = 0; s < 4; ++s) fb[s] = bs[(8 * kb + 4 * lh + s) * BN];
+      }
+    }
+  };
+  template <bool PIN = PIN_DEFAULT> static __device__ __forceinline__ Frags<PIN> mfma_setup(const Wave &w) {
+    Frags<PIN> f = {};
+    f.li = w.lane & 31, f.lh = w.lane >> 5;
+    f.a_off = (w.wm * 32 + f.li) * LW_BK, f.b_off = w.wn * 32 + f.li;
+    f.kbw = w.wk * KB_PER_WAVE;
+    if constexpr (PIN) {
+#pragma unroll
+      for (int q = 0; q < KB_PER_WAVE; ++q) {
+        const int kb = f.kbw + q;
+#pragma unroll
+        for (int g = 0; g < A_GRP; ++g) {
+          f.a[g][q] = lw_lds_addr(smem_lw + g * A_SPG * SLOT + f.a_off + (((2 * kb + f.lh) ^ (f.li & 15)) << 2));
+          asm volatile("" : "+v"(f.a[g][q]));
+        }
+#pragma unroll
+        for (int slot = 0; slot < NSLOT; ++slot) {
+          f.b[slot][q] = lw_lds_addr(smem_lw + slot * SLOT + A_STAGE + f.b_off + (8 * kb + 4 * f.lh) * BN);
+          asm volatile("" : "+v"(f.b[slot][q]));
+        }
+      }
+    }
+    return f;
+  }
+  // the chunk count of a tile, pinned like the addresses: the lap tests that need only T are decided above the barrier
+  template <bool PIN = PIN_DEFAULT> static __device__ __forceinline__ int pin_chunks(int T) {
+    if constexpr (PIN) asm volatile("" : "+s"(T));
+    return T;
+  }
+
+  template <bool PIN> static __device__ __forceinline__ void mfma_chunks(f32x16 &acc, int T, const Frags<PIN> &f) {
     // MFMA fragments of one k-block (8 k): 4 A values (one ds_read_b128) and 4 B values per lane;
     // double-buffered so block q+1 is read while block q multiplies (brgemm_f32.hip has the layout notes)
     f32x4 fa[2];
     float fb[2][4];
-    const int li = w.lane & 31, lh = w.lane >> 5;
-    const int a_off = (w.wm * 32 + li) * LW_BK, b_off = w.wn * 32 + li;
-    auto frag_load = [&](int buf, int slot, int kb) __attribute__((always_inline)) {
-      const float *as = smem_lw + slot * SLOT + a_off;
-      const float *bs = smem_lw + slot * SLOT + A_STAGE + b_off;
-      fa[buf] = *(const f32x4 *)(as + (((2 * kb + lh) ^ (li & 15)) << 2));
-#pragma unroll
-      for (int s = 0; s < 4; ++s) fb[buf][s] = bs[(8 * kb + 4 * lh + s) * BN];
-    };
-    const int kbw = w.wk * KB_PER_WAVE;
+    auto frag_load = [&](int buf, int slot, int q) __attribute__((always_inline)) { f.load(fa[buf], fb[buf], slot, q); }; // q: block of the wave's share
     // hn_c: does another chunk follow (= does this chunk carry the barrier)? 1: yes, a compile-time fact - the steady-state lap below
     // is then ONE basic block (a conditional barrier or an exit test between two chunks is a block boundary: a branch, and a point
     // where the compiler waits for every LDS read in flight); 2: decided at run time (the last lap)
@@ -185,8 +294,8 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
 #pragma unroll
       for (int q = 0; q < KB_PER_WAVE; ++q) {
         const int cur = q & 1, nxt = cur ^ 1;
-        if (q + 1 < KB_PER_WAVE) frag_load(nxt, S, kbw + q + 1);
-        else frag_load(nxt, NS, kbw); // first block of chunk t+1 (published by this chunk's barrier; unused after the last chunk)
+        if (q + 1 < KB_PER_WAVE) frag_load(nxt, S, q + 1);
+        else frag_load(nxt, NS, 0); // first block of chunk t+1 (published by this chunk's barrier; unused after the last chunk)
         __builtin_amdgcn_sched_barrier(0); // the reads of step q+1 stay above the MFMAs of step q
 #pragma unroll
         for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][s], fb[cur][s], acc, 0, 0, 0);
@@ -212,7 +321,7 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
     using HY = std::integral_constant<int, 1>;
     using HR = std::integral_constant<int, 2>;
 
-    frag_load(0, 0, kbw);
+    frag_load(0, 0, 0);
     int t = 0;
     for (; t + NSLOT < T; t += NSLOT) { // whole laps of the ring that are followed by at least one more chunk
       chunk(S0{}, HY{}, true);
@@ -239,19 +348,11 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
   // kedge_skip_blocks: a wave-uniform test per k-block of the wave's share, around the four MFMAs only; the fragment reads (the slot
   // holds valid data) and the chunk's barrier stay, also for a K group that skips its whole share. Laps of the ring that hold no last
   // chunk are mfma_chunks' steady-state laps, one basic block; a lap with a last chunk in it goes chunk by chunk with the test.
-  static __device__ __forceinline__ void mfma_chunks_ragged(f32x16 &acc, int T, int kchunks, int skip, const Wave &w) {
+  template <bool PIN> static __device__ __forceinline__ void mfma_chunks_ragged(f32x16 &acc, int T, int kchunks, int skip, const Frags<PIN> &f) {
     f32x4 fa[2];
     float fb[2][4];
-    const int li = w.lane & 31, lh = w.lane >> 5;
-    const int a_off = (w.wm * 32 + li) * LW_BK, b_off = w.wn * 32 + li;
-    auto frag_load = [&](int buf, int slot, int kb) __attribute__((always_inline)) {
-      const float *as = smem_lw + slot * SLOT + a_off;
-      const float *bs = smem_lw + slot * SLOT + A_STAGE + b_off;
-      fa[buf] = *(const f32x4 *)(as + (((2 * kb + lh) ^ (li & 15)) << 2));
-#pragma unroll
-      for (int s = 0; s < 4; ++s) fb[buf][s] = bs[(8 * kb + 4 * lh + s) * BN];
-    };
-    const int kbw = w.wk * KB_PER_WAVE;
+    auto frag_load = [&](int buf, int slot, int q) __attribute__((always_inline)) { f.load(fa[buf], fb[buf], slot, q); };
+    const int kbw = f.kbw;
     // rag_c 0: a whole chunk that another follows (compile-time facts: mfma_chunks' HY chunk); 1: `first` blocks of the chunk are
     // skipped (0: none), whether another chunk follows is decided at run time
     auto chunk = [&](auto slot_c, auto rag_c, int first, bool has_next_rt) __attribute__((always_inline)) {
@@ -261,8 +362,8 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
 #pragma unroll
       for (int q = 0; q < KB_PER_WAVE; ++q) {
         const int cur = q & 1, nxt = cur ^ 1;
-        if (q + 1 < KB_PER_WAVE) frag_load(nxt, S, kbw + q + 1);
-        else frag_load(nxt, NS, kbw);
+        if (q + 1 < KB_PER_WAVE) frag_load(nxt, S, q + 1);
+        else frag_load(nxt, NS, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (!RAG || kedge_block_runs(kbw + q, first)) {
 #pragma unroll
@@ -284,7 +385,7 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
     using R0 = std::integral_constant<int, 0>;
     using R1 = std::integral_constant<int, 1>;
 
-    frag_load(0, 0, kbw);
+    frag_load(0, 0, 0);
     int t = 0, c = 0; // chunk t of the tile = chunk c of its batch element; a lap starts on slot 0
     for (;;) {
       if (c + NSLOT < kchunks) { // chunks c .. c + NSLOT - 1 are whole and the element's last chunk is still to come
@@ -316,11 +417,49 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
   // EVERY group parks its 32x32 partial, then group g finishes the accumulator registers [g * 16 / WK, (g + 1) * 16 / WK) of its
   // tile - sum in group order (group 0 carries C when beta = 1), bias, relu, store. (With group 0 finishing alone the other
   // groups' waves idled through 16 LDS reads + 16 stores per lane.) Two workgroup barriers: the ring is free, the partials are there.
-  static __device__ __forceinline__ void park_partials(const f32x16 &acc, const Wave &w) {
-    __syncthreads();
-    float *dst = smem_lw + (w.wk * (WM * WN) + w.wmn) * 1024 + w.lane; // WK * WM*WN * 1024 floats, fits in the ring
+  // Where the wave parks, what it sums and where it stores depends on the lane, the wave's role and ldc only: tail_setup() runs with
+  // mfma_setup() above the "chunk 0 published" barrier and pins the addresses, so that between the last MFMA and the stores there
+  // are the two barriers, the LDS traffic and the additions, and no multiply by ldc. A handful of registers held across the loop.
+  // PIN = false (the ragged-k kernels, the split instances, the 64x64 chain instance): nothing ahead, the expressions the tile has
+  // always had.
+  template <bool PIN> struct Tail {
+    unsigned park;     // LDS byte address of the lane's first parked value
+    unsigned src[IPG]; // ... of piece j of K group 0's partial (group g: + g * WM*WN * 4096, an immediate)
+    unsigned off[IPG]; // piece_off(w, j, ldc)
+    Wave w;            // (PIN = false only)
+    int ldc;
+  };
+  template <bool PIN = true> static __device__ __forceinline__ Tail<PIN> tail_setup(const Wave &w, int ldc) {
+    Tail<PIN> t = {0u, {}, {}, w, ldc};
+    if constexpr (PIN && WK > 1) { // (WK = 1: no combine, the epilogue stores from the accumulator registers)
+      t.park = lw_lds_addr(smem_lw + (w.wk * (WM * WN) + w.wmn) * 1024 + w.lane); // WK * WM*WN * 1024 floats, fits in the ring
+      asm volatile("" : "+v"(t.park));
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dst[r * 64] = acc[r];
+      for (int j = 0; j < IPG; ++j) {
+        const int q = piece_row(w, j); // row of the 32x32 tile: q = (r & 3) + 4 * lh + 8 * (r >> 2)
+        const int r = (q & 3) + 4 * (q >> 3), lh2 = (q >> 2) & 1;
+        t.src[j] = lw_lds_addr(smem_lw + w.wmn * 1024 + r * 64 + lh2 * 32 + 4 * (w.lane & 7));
+        t.off[j] = piece_off(w, j, ldc);
+        asm volatile("" : "+v"(t.src[j]), "+v"(t.off[j]));
+      }
+    }
+    return t;
+  }
+  template <bool PIN> static __device__ __forceinline__ unsigned tail_off(const Tail<PIN> &t, int j) {
+    if constexpr (PIN) return t.off[j];
+    else return piece_off(t.w, j, t.ldc);
+  }
+  template <bool PIN> static __device__ __forceinline__ void park_partials(const f32x16 &acc, const Tail<PIN> &t) {
+    __syncthreads();
+    if constexpr (PIN) {
+      lds_float_lw *dst = lw_lds_float(t.park);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dst[r * 64] = acc[r];
+    } else {
+      float *dst = smem_lw + (t.w.wk * (WM * WN) + t.w.wmn) * 1024 + t.w.lane;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dst[r * 64] = acc[r];
+    }
     __syncthreads();
   }
   // The parked partials are [register r][lane = column li + 32 * lh]: four consecutive columns of one output row (r, lh) are
@@ -331,20 +470,29 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
   static __device__ __forceinline__ unsigned piece_off(const Wave &w, int j, int ldc) { // bytes from the tile's first element of C
     return (unsigned)(((w.wm * 32 + piece_row(w, j)) * ldc + w.wn * 32 + 4 * (w.lane & 7)) * 4);
   }
-  static __device__ __forceinline__ void sum_partials(f32x4 (&part)[IPG], const Wave &w) {
+  template <bool PIN> static __device__ __forceinline__ void sum_partials(f32x4 (&part)[IPG], const Tail<PIN> &t) {
 #pragma unroll
     for (int j = 0; j < IPG; ++j) {
-      const int q = piece_row(w, j); // row of the 32x32 tile: q = (r & 3) + 4 * lh + 8 * (r >> 2)
-      const int r = (q & 3) + 4 * (q >> 3), lh2 = (q >> 2) & 1;
-      const float *src = smem_lw + w.wmn * 1024 + r * 64 + lh2 * 32 + 4 * (w.lane & 7);
-      f32x4 v = *(const f32x4 *)src;
+      if constexpr (PIN) {
+        const lds_f32x4_lw *src = lw_lds_f32x4(t.src[j]);
+        f32x4 v = *src;
 #pragma unroll
-      for (int g = 1; g < WK; ++g) v += *(const f32x4 *)(src + g * (WM * WN) * 1024);
-      part[j] = v;
+        for (int g = 1; g < WK; ++g) v += src[g * (WM * WN) * 256];
+        part[j] = v;
+      } else {
+        const int q = piece_row(t.w, j); // row of the 32x32 tile: q = (r & 3) + 4 * lh + 8 * (r >> 2)
+        const int r = (q & 3) + 4 * (q >> 3), lh2 = (q >> 2) & 1;
+        const float *src = smem_lw + t.w.wmn * 1024 + r * 64 + lh2 * 32 + 4 * (t.w.lane & 7);
+        f32x4 v = *(const f32x4 *)src;
+#pragma unroll
+        for (int g = 1; g < WK; ++g) v += *(const f32x4 *)(src + g * (WM * WN) * 1024);
+        part[j] = v;
+      }
     }
   }
   // bias, relu, 16-byte write-through stores (ok: this lane's column piece exists)
-  static __device__ __forceinline__ void finish(const f32x4 (&part)[IPG], f32x4 bias4, int ep, __amdgpu_buffer_rsrc_t rsrcC, int ldc, bool ok, const Wave &w) {
+  template <bool PIN>
+  static __device__ __forceinline__ void finish(const f32x4 (&part)[IPG], f32x4 bias4, int ep, __amdgpu_buffer_rsrc_t rsrcC, bool ok, const Tail<PIN> &t) {
 #pragma unroll
     for (int j = 0; j < IPG; ++j) {
       f32x4 v = part[j] + bias4;
@@ -352,7 +500,7 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
       }
-      if (ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrcC, piece_off(w, j, ldc), 0, LW_C_AUX);
+      if (ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrcC, tail_off(t, j), 0, LW_C_AUX);
     }
   }
   // EDGE tiles (brgemm_f32_lw_edge): does the tile own this lane's piece j - rows >= own_r and columns >= own_c of the tile (own_c a
@@ -361,8 +509,9 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
     return w.wm * 32 + piece_row(w, j) >= own_r && w.wn * 32 + 4 * (w.lane & 7) >= own_c;
   }
   // finish for an edge tile: the same values, stored only where the tile owns them
-  static __device__ __forceinline__ void finish_owned(const f32x4 (&part)[IPG], f32x4 bias4, int ep, __amdgpu_buffer_rsrc_t rsrcC, int ldc, int own_r, int own_c,
-                                                      const Wave &w) {
+  template <bool PIN>
+  static __device__ __forceinline__ void finish_owned(const f32x4 (&part)[IPG], f32x4 bias4, int ep, __amdgpu_buffer_rsrc_t rsrcC, int own_r, int own_c,
+                                                      const Wave &w, const Tail<PIN> &t) {
 #pragma unroll
     for (int j = 0; j < IPG; ++j) {
       f32x4 v = part[j] + bias4;
@@ -370,7 +519,7 @@ template <int WM, int WN, int WK, int NSLOT = LW_NSLOT> struct LwTile {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
       }
-      if (piece_owned(w, j, own_r, own_c)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrcC, piece_off(w, j, ldc), 0, LW_C_AUX);
+      if (piece_owned(w, j, own_r, own_c)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrcC, tail_off(t, j), 0, LW_C_AUX);
     }
   }
 };
