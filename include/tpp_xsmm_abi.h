@@ -561,6 +561,24 @@ TPP_XSMM_EXPORT void xsmm_hip_chain_rounds_stats(int64_t out[4]);
  * chain-rounds and single-call edge counters do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_chain_ragged(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_chain_ragged_stats(int64_t out[4]);
+/* Mixed-width layer chains, opt-in (environment: TPP_HIP_CHAIN_WIDTHS; default 0 = off): a switch of its own - no other switch changes
+ * meaning. The chain contract asks for the same m AND n in every call; mode 1 widens it: a bf16 chain of 2 .. 8 calls whose n differ in at
+ * least two calls runs as ONE launch on m / BM x max_l(n_l / BN) workgroups when all calls have the same m; every call is beta 0, stores
+ * no VNNI C, was not dispatched to the generic kernel and has the same B image (VNNI-2, flat or VNNI-4) of the loader-wave tiles; every
+ * k >= 64 and a multiple of 64, every batch count >= 1; BM divides m and BN divides every n_l; m / BM * max_l(n_l / BN) <= the stream's
+ * compute units - and everything else the chain launch asks holds as before (each call reads its predecessor's output, batch elements
+ * inside the predecessor's rows, device pointers, no overlaps, asynchronous mode, no stream capture). The tile: the loader-wave tile ALL
+ * calls were dispatched on if it fits - the launch then has the bits of the calls made one by one, so strict mode takes it -, otherwise
+ * (never in strict mode) the smallest tile that fits. Workgroup (tm, tn) computes tile (tm, tn) of every layer with a column tile tn and
+ * sits out the others; the counter of layer l and row block tm receives n_l / BN arrivals per launch. The rule is asked only where the
+ * calls differ in n: equal widths stay the plain chain's; a ragged m, n or k together with different widths, more tiles than compute
+ * units, and f32 stay call by call whatever the other chain switches say. A starved launch degrades as every chain launch. Returns the
+ * previous value, -1 (nothing changed) for any other value.
+ * _stats: out[0] mixed-width chain launches since process start; of the most recent one: [1] row blocks m / BM, [2] column tiles of the
+ * widest layer max_l(n_l / BN), [3] the variant number of its tile with its B image (20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4). The
+ * counters of the other chain modes and of the single-call edge switches do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_widths(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_widths_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

@@ -42,6 +42,11 @@
 //   EARLIER in their own step order (layer-major), and every step a workgroup makes before it waits in turn only for still earlier
 //   steps of the same group. All G x tiles_n workgroups are resident, so by induction over the step order no wait is cyclic and each
 //   one ends. When a workgroup reaches block r of layer l + 1 its producers finished that block R - 1 steps ago: the poll falls through.
+//
+// MIXED WIDTHS (GRP = 9, xsmm_hip_set_chain_widths; schedule in brgemm_bf16_lw_chain_widths.h, instances in brgemm_bf16_lw_chain_widths.hip): a
+// chain whose layers differ in n on m / BM x max_l(n(l) / BN) workgroups. Workgroup (tm, tn) sits out the layers without a column tile tn.
+//   Progress: an active layer l > 0 waits only for cnt[l-1][tm], whose n(l-1) / BN producers are resident and wait in turn only for
+//   counters of layer l - 2: by induction over the layers no wait is cyclic. A workgroup's counters need not be its own layers'.
 #include "gemm_common.h"
 #include "xsmm_desc.h"
 #include "chain_args.h"
@@ -110,6 +115,10 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   // into the last chunk. The ring is carried from layer to layer (s0); the B loader does not run ahead across a seam in this mode.
   constexpr bool CRAG = blw_chain_ragged(GRP);
   constexpr bool KEDGE = blw_ragged_k(GRP) || CRAG;
+  // GRP = 9 (a MIXED-WIDTH chain, brgemm_bf16_lw_chain_widths.h): GRP = 0's chain in which layer lc has p.L[lc].pad columns: this wave skips
+  // a layer without a column tile at n0 - no barrier, no ring slot, s0 stays -, waits for epoch * (n(lc - 1) / BN) arrivals in front of every
+  // active layer lc > 0, and the B loaders' run-ahead goes to the workgroup's next ACTIVE layer. The MFMA waves count the same way.
+  constexpr bool CWID = blw_chain_widths(GRP);
   // GRP = 5 (a CHAIN on edge ROW tiles, brgemm_bf16_lw_chain_edge.h): the argument block's operands as GRP = 0, m0 of the last row block
   // shifted back by the kernel; the seam wait of a shifted block is for TWO row blocks' producers (below)
   // GRP = 7 (a chain in SEVERAL ROUNDS, brgemm_bf16_lw_chain_rounds.h): `tm` arrives as the workgroup's row GROUP g; the loop below runs
@@ -238,6 +247,9 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   // launch from layer to layer)
   for (int lc = 0; lc < L; ROUNDS ? chain_rounds_next(tm, lc, p.groups, p.tiles_m) : (void)++lc) {
     if constexpr (ROUNDS) m0 = tm * BM;
+    if constexpr (CWID) {
+      if (!chain_widths_active(n0 / BN, p.L[lc].pad, BN)) continue; // (uniform over the workgroup: n0 and the layer's n)
+    }
     const int T = (ITEMS ? it_br : p.L[lc].br) * (KEDGE ? bkedge_chunks(p.L[lc].k) : p.L[lc].k / BLW_BK) / SUP; // (a multiple of SUP: the launcher picks SUP = 1 otherwise)
     int pre = NSLOT - 2; // chunks of this layer already requested by the run-ahead of the previous layer's tail
     if constexpr (ROUNDS) {
@@ -259,7 +271,9 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       // bound and the one error word.
       const int b_first = GRP == BLW_CHAIN_EDGE || CRAG ? chain_edge_first_block(tm, p.tiles_m, p.m, BM) : tm;
       const int b_last = GRP == BLW_CHAIN_EDGE || CRAG ? chain_edge_last_block(tm, p.tiles_m, p.m, BM) : tm;
-      const unsigned target = p.target;
+      // (GRP = 9: p.target is the epoch, the producers of layer lc - 1 are that layer's column tiles)
+      unsigned target = p.target;
+      if constexpr (CWID) target = chain_widths_target(p.target, p.L[lc > 0 ? lc - 1 : 0].pad, BN);
       const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
       for (int bw = b_first; bw <= b_last; ++bw) {
         g_u32_lw *c = (g_u32_lw *)(p.cnt + ((size_t)(lc - 1) * p.tiles_m + bw) * CHAIN_CNT_STRIDE);
@@ -299,7 +313,24 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
     // the last NSLOT - 2 barriers of the layer: nothing of THIS layer is left to request. The next step of a multi-round chain: this
     // layer's next row block (the same weight panels again), or the next layer's first
     const bool more_rounds = ROUNDS && chain_rounds_more(tm, p.groups, p.tiles_m);
-    if (MULTI && ahead && (lc + 1 < L || more_rounds)) {
+    if constexpr (CWID) {
+      // GRP = 9: the run-ahead loads this workgroup's next ACTIVE layer (L = none: the else arm's loop). A statement of its own, so that
+      // the other modes' code below is the text it was.
+      const int nxt = chain_widths_next(n0 / BN, lc, L, BN, [&](int l_) { return p.L[l_].pad; });
+      if (ahead && nxt < L) {
+        BLW_LOAD_STATE(nxt);
+        for (; t + 1 < T; ++t) {
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSLOT - 3) * PPL) : "memory");
+          __builtin_amdgcn_s_barrier();
+          BLW_ISSUE(slot);
+        }
+      } else {
+        for (; t + 1 < T; ++t) {
+          blw_wait_younger<PPL>(T - 2 - t);
+          __builtin_amdgcn_s_barrier();
+        }
+      }
+    } else if (MULTI && ahead && (lc + 1 < L || more_rounds)) {
       BLW_LOAD_STATE(more_rounds ? lc : lc + 1); // (the slot rotation carries over into the next layer / step)
       if constexpr (ROUNDS) state_layer = PRIMED;
       for (; t + 1 < T; ++t) {
@@ -344,6 +375,11 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // chain multiplies), even for k % 16 == 0, odd for k % 16 == 8 - one instance serves the three k classes. A layer starts at any ring slot.
   constexpr bool CRAG = blw_chain_ragged(GRP);
   constexpr bool KEDGE = blw_ragged_k(GRP) || CRAG, ROUNDS = GRP == BLW_CHAIN_ROUNDS;
+  // GRP = 9 (a MIXED-WIDTH chain, xsmm_hip_set_chain_widths; brgemm_bf16_lw_chain_widths.h): GRP = 0's chain on m / BM x max_l(n(l) / BN)
+  // workgroups, n(l) = p.L[l].pad. Workgroup (tm, tn) computes tile (tm, tn) of the layers with a column tile tn and skips the others - all
+  // its waves alike, without a barrier or a ring slot. After every active layer but the chain's last it runs the whole seam (drain, R1, S1,
+  // one arrival at cnt[l][tm]), also when no further layer is active for it. p.target is the epoch (blw_loader).
+  constexpr bool CWID = blw_chain_widths(GRP);
   constexpr bool EDGE_ROWS = blw_edge_rows(GRP), EDGE_COLS = blw_edge_cols(GRP); // (the last tile of a column / row of tiles is shifted back)
   // GRP = 7 (a chain in SEVERAL ROUNDS, xsmm_hip_set_chain_rounds): MULTI on p.groups x tiles_n workgroups, fewer than the output tiles -
   // workgroup (g, tn) walks the row blocks g, g + groups, .. of every layer, layer-major (the file's header; brgemm_bf16_lw_chain_rounds.h).
@@ -654,6 +690,9 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // launch from layer to layer; blw_loader counts the same way)
   for (int l = 0; l < L; ROUNDS ? chain_rounds_next(tm, l, p.groups, p.tiles_m) : (void)++l) {
     if constexpr (ROUNDS) m0 = tm * BM;
+    if constexpr (CWID) {
+      if (!chain_widths_active(tn, p.L[l].pad, BN)) continue; // (the loaders skip the same layers: n0 = tn * BN)
+    }
     const auto &Y = p.L[l];
     const int T = (ITEMS ? it_br : Y.br) * (KEDGE ? bkedge_chunks(Y.k) : Y.k / BLW_BK);
     const int ep = Y.ep;

@@ -5,6 +5,7 @@
 #pragma once
 #include "brgemm_bf16_lw_kedge.h"
 #include "brgemm_bf16_lw_chain_ragged.h"
+#include "brgemm_bf16_lw_chain_widths.h"
 
 namespace tpp {
 
@@ -22,11 +23,14 @@ constexpr int BLW_MODES = 8;
 // A ragged-WIDTH chain (xsmm_hip_set_chain_ragged): a mode BESIDE the table - blw_instance_exists and blw_launch_ok go on refusing it, its
 // instances live in a translation unit of their own (brgemm_bf16_lw_chain_ragged.hip) and have their own predicates at the end of this file
 constexpr int BLW_CHAIN_RAGGED = 8; // a chain with a ragged n and / or a k that is a multiple of 8 but not of 64 in some layer
+// A MIXED-WIDTH chain (xsmm_hip_set_chain_widths): beside the table in the same way (brgemm_bf16_lw_chain_widths.hip, predicates at the end)
+constexpr int BLW_CHAIN_WIDTHS = 9; // a chain whose layers differ in n: a workgroup sits out the layers that have no column tile for it
 
 // what follows from a mode
 constexpr bool blw_items(int g) { return g == BLW_ITEMS || g == BLW_QUADS; }      // operands and batch count come from an item
 constexpr bool blw_ragged_k(int g) { return g == BLW_KEDGE || g == BLW_KEDGE8; }  // the last chunk of a batch element is shifted back
 constexpr bool blw_chain_ragged(int g) { return g == BLW_CHAIN_RAGGED; }         // every layer its own k class, tested in half steps
+constexpr bool blw_chain_widths(int g) { return g == BLW_CHAIN_WIDTHS; }         // per-layer n in the argument block, skipped layers
 constexpr bool blw_half_steps(int g) { return g == BLW_KEDGE8; }                  // ... and its overlap ends in the middle of a k-step
 // the last row block is shifted back to end at row m and stores its own rows only
 constexpr bool blw_edge_rows(int g) { return g == BLW_EDGE || blw_ragged_k(g) || g == BLW_CHAIN_EDGE || blw_chain_ragged(g); }
@@ -39,12 +43,13 @@ constexpr bool blw_mode_ok(int g, bool multi, int sup) {
   return g >= 0 && g < BLW_MODES && (multi ? g == BLW_LAYER || blw_chain(g) : !blw_chain(g)) && (!blw_one_chunk(g) || sup == 1);
 }
 template <int GRP, bool MULTI, int SUP> struct BlwModeCheck {
-  static_assert((GRP >= 0 && GRP < BLW_MODES) || blw_chain_ragged(GRP), "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds, 8: a ragged-width chain");
-  static_assert(!MULTI || GRP == BLW_LAYER || blw_chain(GRP) || blw_chain_ragged(GRP), "a grouped launch is a set of single layers");
+  static_assert((GRP >= 0 && GRP < BLW_MODES) || blw_chain_ragged(GRP) || blw_chain_widths(GRP), "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds, 8: a ragged-width chain, 9: a mixed-width chain");
+  static_assert(!MULTI || GRP == BLW_LAYER || blw_chain(GRP) || blw_chain_ragged(GRP) || blw_chain_widths(GRP), "a grouped launch is a set of single layers");
   static_assert(!blw_ragged_k(GRP) || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
   static_assert(!blw_chain(GRP) || (SUP == 1 && MULTI), "a ragged / multi-round chain: a chain, one chunk per barrier");
   static_assert(!blw_chain_ragged(GRP) || (SUP == 1 && MULTI), "a ragged-width chain: a chain, one chunk per barrier");
-  static constexpr bool ok = blw_chain_ragged(GRP) ? MULTI && SUP == 1 : blw_mode_ok(GRP, MULTI, SUP);
+  static_assert(!blw_chain_widths(GRP) || (MULTI && (SUP == 1 || SUP == 2)), "a mixed-width chain: a chain, one or two chunks per barrier");
+  static constexpr bool ok = blw_chain_ragged(GRP) ? MULTI && SUP == 1 : blw_chain_widths(GRP) ? MULTI && (SUP == 1 || SUP == 2) : blw_mode_ok(GRP, MULTI, SUP);
 };
 
 // THE TILES. 0 = 32x64 + K2, 1 = 64x64, 2 = 64x128, 3 = 128x128, 4 = 32x32 + K2. Loader waves per tile (NLA + NLB), same-box A/B
@@ -125,6 +130,31 @@ constexpr bool blw_chain_ragged_launch_ok(int tile, int b_kind, const BlwShape &
     if (a.k[l] % BKEDGE_BK != 0) ragged = true;
   }
   return ragged && a.m >= bm && a.n >= bn && a.n % 8 == 0;
+}
+
+// THE MIXED-WIDTH CHAIN (BLW_CHAIN_WIDTHS, brgemm_bf16_lw_chain_widths.hip; schedule in brgemm_bf16_lw_chain_widths.h): MULTI. Is the instance of
+// (tile, b_kind, sup) compiled? Tiles 0 .. 3 with the three B images at one chunk per barrier, tiles 0 and 1 at two as well - the plain
+// chain's eighteen, none with scratch.
+constexpr bool blw_chain_widths_instance_exists(int tile, int b_kind, int sup) {
+  return tile >= 0 && tile <= 3 && blw_b_kind_ok(b_kind) && (sup == 1 || (sup == 2 && blw_tile_sup2(tile)));
+}
+// ... and what its launcher refuses, over a shape with per-layer widths: 2 .. 8 layers, every one a batch of at least one element in whole
+// 64-k chunks and n(l) >= BN columns in whole column tiles; m in whole row blocks; at least two layers differ in n (an equal-width chain is
+// BLW_LAYER's)
+struct BlwWidthsShape {
+  int m, nlayers;
+  int n[BLW_MAXL], k[BLW_MAXL], br[BLW_MAXL]; // per layer (the first min(nlayers, BLW_MAXL))
+};
+constexpr bool blw_chain_widths_launch_ok(int tile, int b_kind, const BlwWidthsShape &a) {
+  if (!blw_chain_widths_instance_exists(tile, b_kind, 1) || a.nlayers < 2 || a.nlayers > BLW_MAXL) return false;
+  const int bm = BLW_TILES[tile].bm(), bn = BLW_TILES[tile].bn();
+  bool differ = false;
+  for (int l = 0; l < a.nlayers; ++l) {
+    if (a.br[l] < 1 || a.k[l] < BKEDGE_BK || a.k[l] % BKEDGE_BK != 0) return false;
+    if (a.n[l] < bn || a.n[l] % bn != 0) return false;
+    if (a.n[l] != a.n[0]) differ = true;
+  }
+  return differ && a.m >= bm && a.m % bm == 0;
 }
 
 } // namespace tpp

@@ -17,7 +17,7 @@ struct ChainLayer {
   const void *D;   // bias row (EP_BIAS)
   void *C;         // output [m][ldc]; the A operand of the next layer
   int64_t ldb, ldc, stride_a, stride_b; // elements (stride_a applies to this layer's A = previous C / the chain input)
-  int k, br, ep, pad;                   // k per batch element (multiple of 64), batch count, EP_* bits
+  int k, br, ep, pad;                   // k per batch element (multiple of 64), batch count, EP_* bits; pad: 0 - a mixed-width chain: the layer's n
 };
 
 struct ChainArgs {
@@ -25,8 +25,8 @@ struct ChainArgs {
   int64_t lda;
   unsigned *cnt;   // chain mode: arrival counters [nlayers - 1][tiles_m] (CHAIN_CNT_STRIDE words apart), monotonic across launches
   unsigned *err;   // chain mode: set to 1 + layer by a workgroup whose hand-off wait timed out
-  unsigned target; // chain mode: value every counter reaches in this launch (epoch * tiles_n)
-  int m, n;        // rows and columns of every layer's output
+  unsigned target; // chain mode: value every counter reaches in this launch (epoch * tiles_n); a mixed-width chain: the epoch itself
+  int m, n;        // rows and columns of every layer's output (a mixed-width chain: n of the widest layer, L[l].pad per layer)
   int nlayers;
   int tiles_m, tiles_n; // filled by the launcher
   int xm;               // filled by the launcher: XCD grid xm x (8 / xm) over the tile grid, 0 = linear tile order
@@ -55,6 +55,10 @@ hipError_t launch_bf16_chain(int mode, int tile, int b_kind, const ChainArgs &a,
 // a ragged-WIDTH chain (brgemm_bf16_lw_chain_ragged.hip, BLW_CHAIN_RAGGED, xsmm_hip_set_chain_ragged): ceil(m / BM) x ceil(n / BN) workgroups,
 // at most the stream's compute units (the caller's guarantee); per layer k >= 64 and k % 8 == 0; blw_chain_ragged_launch_ok is what it refuses
 hipError_t launch_bf16_chain_ragged(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
+// a MIXED-WIDTH chain (brgemm_bf16_lw_chain_widths.hip, BLW_CHAIN_WIDTHS, xsmm_hip_set_chain_widths): layer l has a.L[l].pad columns, a.n is
+// the widest layer's (the grid: m / BM x a.n / BN workgroups, at most the stream's compute units - the caller's guarantee) and a.target
+// the launch's EPOCH: cnt[l][*] reaches epoch * (a.L[l].pad / BN). blw_chain_widths_launch_ok is what it refuses
+hipError_t launch_bf16_chain_widths(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2; b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);

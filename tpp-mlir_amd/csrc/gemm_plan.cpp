@@ -575,6 +575,52 @@ int chain_rounds_planned_tile(int n, const GemmDesc *const *d) {
   return t;
 }
 
+ChainWidthsPlan plan_chain_widths(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int b_kind, int mode, bool strict) {
+  auto no = [](const char *why) { return ChainWidthsPlan{-1, why}; };
+  if (mode != 1) return no("mixed-width chains are off (xsmm_hip_set_chain_widths)");
+  if (planned_tile < -1) return no("a mixed-width chain is bf16: an f32 call");
+  if (nlayers < 2 || nlayers > 8) return no("fewer than 2 or more than 8 calls");
+  if (!blw_b_kind_ok(b_kind)) return no("the calls of a mixed-width chain do not share one B image of the loader-wave tiles");
+  bool differ = false;
+  int64_t widest = 0;
+  for (int l = 0; l < nlayers; ++l) {
+    if (k[l] < BK || k[l] % BK != 0 || br[l] < 1) return no("a layer of a mixed-width chain has k not in 64-k chunks, or an empty batch");
+    if (n[l] != n[0]) differ = true;
+    if (n[l] > widest) widest = n[l];
+  }
+  if (!differ) return no("every call has the same n: not a mixed-width chain");
+  auto divides = [&](int t) {
+    if (t < 0 || t > 3 || m < BLW_BM[t] || m % BLW_BM[t] != 0) return false;
+    for (int l = 0; l < nlayers; ++l)
+      if (n[l] < BLW_BN[t] || n[l] % BLW_BN[t] != 0) return false;
+    return true;
+  };
+  auto fits = [&](int t) { return divides(t) && blw_chain_widths_instance_exists(t, b_kind, 1) && (m / BLW_BM[t]) * (widest / BLW_BN[t]) <= cus; };
+  if (fits(planned_tile)) return ChainWidthsPlan{planned_tile, ""};
+  if (strict) return no("strict mode: one launch only on the tile all calls were dispatched on");
+  // THE GATE (measured, profiles/chain_widths_ab.txt: VNNI-2 on 256 CUs, call by call -> one launch, every pair slower: 1024 rows x [1024,
+  // 4096, 1024] 29.17 -> 38.39 us on 128x128, 256 rows of the same 16.86 -> 19.82 on 64x64, 2048 rows x [1024, 2048, 1024] 25.58 -> 26.56
+  // on 128x128, 1024 rows x [1024, 2048, 1024, 2048, 1024] 35.40 -> 38.60 on 64x128; the funnel [1024, 512, 256, 128], whose launch
+  // runs on the smallest tile, 16.39 -> 11.80): the widest layer decides the launch's tile, and a layer that ALONE fits a smaller one -
+  // its separate call covers the chip with more, smaller tiles, in the launch it keeps a fraction of the grid busy on the large one -
+  // makes the chain slower. Such a chain stays call by call. A tile all calls were dispatched on (above) is not gated: the separate
+  // calls run on that tile too.
+  auto alone_fits = [&](int t, int l) {
+    return blw_chain_widths_instance_exists(t, b_kind, 1) && m >= BLW_BM[t] && m % BLW_BM[t] == 0 && n[l] >= BLW_BN[t] && n[l] % BLW_BN[t] == 0 &&
+           (m / BLW_BM[t]) * (n[l] / BLW_BN[t]) <= cus;
+  };
+  for (int t = 0; t < 4; ++t) {
+    if (!fits(t)) continue;
+    for (int l = 0; l < nlayers; ++l)
+      for (int s = 0; s < t; ++s)
+        if (alone_fits(s, l)) return no("gate: a layer fits a smaller tile alone than the widest layer leaves the launch - measured slower as one launch (profiles/chain_widths_ab.txt)");
+    return ChainWidthsPlan{t, ""};
+  }
+  for (int t = 0; t < 4; ++t)
+    if (divides(t)) return no("more tiles than compute units (a mixed-width chain runs in one round)");
+  return no("no tile divides m and every n (a ragged shape stays call by call with different widths)");
+}
+
 int chain_rounds_b_kind(const GemmDesc &d) {
   if (d.dtype != DT_BF16 || d.vnni_c || !d.beta0 || d.generic_forced || d.variant == V_GENERIC) return -1;
   return bf16_edge_b_kind(d);

@@ -185,6 +185,24 @@ int chain_rounds_planned_tile(int n, const GemmDesc *const *d);
 // beta 1, the generic kernel, k not in 64-k chunks, an operand off the LDS-DMA grid.
 int chain_rounds_b_kind(const GemmDesc &d);
 ChainRoundsPlan plan_chain_rounds(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int mode, bool strict);
+// MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths; rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_widths.hip launch_bf16_chain_widths,
+// BLW_CHAIN_WIDTHS, schedule in brgemm_bf16_lw_chain_widths.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_widths.txt is the table
+// of the function's answers. A bf16 chain of 2 .. 8 calls with the same m whose n differ runs as one launch on m / BM x max_l(n[l] / BN)
+// workgroups. n[l], k[l], br[l]: layer l's columns, k per batch element and batch count; cus: compute units on the stream; planned_tile
+// 0 .. 3 = the loader-wave tile ALL calls were dispatched on (-1: they do not share one, -2: a call is not bf16 - chain_rounds_planned_tile);
+// b_kind = the B image every call has by bf16_lw_b_kind (-1: none, or not one); mode = the switch's value; strict = xsmm_hip_set_strict.
+// A tile FITS when BM divides m, BN divides every n[l] and m / BM * max_l(n[l] / BN) <= cus. The tile: the planned one if it fits (the
+// launch then has the calls' bits: strict mode takes it too); without one, refused in strict mode, else the smallest tile that fits.
+// tile = -1 and why = the reason: the switch off, an f32 call, fewer than 2 or more than 8 layers, no shared B image, a k not in 64-k
+// chunks or an empty batch, every n equal (the plain chain's), strict mode without a planned tile that fits, m or an n no tile divides
+// (ragged shapes never combine with different widths), more tiles than compute units (nor do several rounds).
+// THE GATE (measured, profiles/chain_widths_ab.txt): where the tile is the smallest that fits - not one all calls were dispatched on - and
+// some layer ALONE (m x n[l]) fits a smaller tile, the chain stays call by call: that layer's separate call covers the chip with more,
+// smaller tiles, in the launch it keeps a fraction of the grid busy on the widest layer's tile. 1024 and 256 rows x [1024, 4096, 1024],
+// 2048 rows x [1024, 2048, 1024] and 1024 rows x [1024, 2048, 1024, 2048, 1024] ran 32 %, 18 %, 4 % and 9 % slower as one launch; the
+// funnel [1024, 512, 256, 128], on the smallest tile, 28 % faster.
+struct ChainWidthsPlan { int tile; const char *why; };
+ChainWidthsPlan plan_chain_widths(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int b_kind, int mode, bool strict);
 // 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none
 int f32_chain_tile(const GemmDesc &d);
 // tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip; BLW_TILES, brgemm_bf16_lw_launch.h)

@@ -16,6 +16,9 @@ struct ChainBlock {
   unsigned *err; // pinned host
   unsigned epoch;
   int verified;  // launches of this block that were checked synchronously and had every hand-off succeed (probation, see below)
+  // a mixed-width chain (xsmm_hip_set_chain_widths): column tiles PER LAYER - part of the key, since a launch adds tiles_l[l] to the counters
+  // of layer l (tiles_n is the widest layer's: the grid). All zero in every other block: there every layer has tiles_n.
+  int tiles_l[CH_MAXL];
 };
 // A STARVED chain launch (another process, or another stream's LDS-heavy kernel, held compute units while it ran: not every
 // workgroup became resident, a consumer's bounded wait ran out, the error word is set) used to end the process. Round 5 (VERDICT r4
@@ -55,10 +58,13 @@ std::mutex g_chain_mu;
 std::vector<ChainBlock> g_chain_blocks;
 std::atomic<int> g_chain_launched{0}; // chain launches since the last check of the err words
 
-ChainBlock &chain_block(hipStream_t s, int tiles_m, int tiles_n, int nlayers) { // under g_chain_mu
+ChainBlock &chain_block(hipStream_t s, int tiles_m, int tiles_n, int nlayers, const int *tiles_l = nullptr) { // under g_chain_mu
+  int key_l[CH_MAXL] = {};
+  for (int l = 0; tiles_l && l < nlayers && l < CH_MAXL; ++l) key_l[l] = tiles_l[l];
   for (ChainBlock &b : g_chain_blocks)
-    if (b.stream == s && b.tiles_m == tiles_m && b.tiles_n == tiles_n && b.nlayers == nlayers) return b;
-  ChainBlock b{s, tiles_m, tiles_n, nlayers, nullptr, nullptr, 0, 0};
+    if (b.stream == s && b.tiles_m == tiles_m && b.tiles_n == tiles_n && b.nlayers == nlayers && !memcmp(b.tiles_l, key_l, sizeof(key_l))) return b;
+  ChainBlock b{s, tiles_m, tiles_n, nlayers, nullptr, nullptr, 0, 0, {}};
+  memcpy(b.tiles_l, key_l, sizeof(key_l));
   const size_t bytes = sizeof(unsigned) * (size_t)(CH_MAXL - 1) * (size_t)tiles_m * CHAIN_CNT_STRIDE;
   HIP_OK(hipMalloc((void **)&b.cnt, bytes));
   HIP_OK(hipMemset(b.cnt, 0, bytes));
@@ -223,6 +229,36 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (!ragw_state && cfg().trace) fprintf(stderr, "[tpp-xsmm-hip] fused_brgemm_chain: no ragged-width launch (%s)\n", w ? w : "the calls' B operands differ in kind");
     return ragw_state == 1;
   };
+  // MIXED WIDTHS (xsmm_hip_set_chain_widths, opt-in; gemm_plan.cpp plan_chain_widths): asked only where the loop below would end in NOCHAIN
+  // because two calls differ in n (a difference in m, or an empty batch, still refuses). widths_w() is the rule's answer, asked at most
+  // once: every call is bf16, beta 0, stores no VNNI C, was not dispatched to the generic kernel and has the same B image by
+  // bf16_lw_b_kind - the terms of the divisible chain, which every call must ALSO pass in the loop below (a ragged call ends the launch:
+  // `divisible`) -, the same m and a batch, and plan_chain_widths names a tile. widw = the launch is the mixed-width one. With the
+  // switch off widths_w() is false without a look at the calls and the NOCHAIN is taken exactly as before.
+  const int chain_widths = f32 ? 0 : g_chain_widths.load(std::memory_order_relaxed);
+  int widw_state = chain_widths ? -1 : 0, widw_tile = -1, widw_kind = -1; // -1 not asked yet, 0 no, 1 yes
+  bool widw = false;
+  auto widths_w = [&]() {
+    if (widw_state >= 0) return widw_state == 1;
+    widw_state = 0;
+    const char *w = "a call differs in m, has an empty batch, is not bf16 / beta 0 / on a loader-wave tile, or the calls' B operands differ in kind";
+    widw_kind = bf16_lw_b_kind(*d[0]);
+    for (int i = 0; i < n && widw_kind >= 0; ++i) {
+      const GemmDesc &g = *d[i];
+      if (g.dtype != DT_BF16 || g.vnni_c || !g.beta0 || g.variant == V_GENERIC || bf16_lw_b_kind(g) != widw_kind || g.m != m || br[i] < 1) widw_kind = -1;
+    }
+    if (widw_kind >= 0) {
+      int64_t ns[CH_MAXL], ks[CH_MAXL], brs[CH_MAXL];
+      for (int i = 0; i < n; ++i) ns[i] = d[i]->n, ks[i] = d[i]->k, brs[i] = br[i];
+      const ChainWidthsPlan wp = plan_chain_widths(m, n, ns, ks, brs, stream_cus(s), chain_rounds_planned_tile(n, d), widw_kind, chain_widths,
+                                                   cfg().strict.load(std::memory_order_relaxed));
+      w = wp.why;
+      widw_tile = wp.tile;
+      if (wp.tile >= 0) widw_state = 1;
+    }
+    if (!widw_state && cfg().trace) fprintf(stderr, "[tpp-xsmm-hip] fused_brgemm_chain: no mixed-width launch (%s)\n", w);
+    return widw_state == 1;
+  };
   for (int i = 0; i < n; ++i) {
     const GemmDesc &g = *d[i];
     if (edge_on && !edge_why) {
@@ -243,7 +279,8 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
       }
       divisible = false;
     }
-    if (g.m != m || g.n != nn || br[i] < 1) NOCHAIN("the calls differ in m or n, or a batch is empty");
+    if (g.m != m || br[i] < 1 || (g.n != nn && !widths_w())) NOCHAIN("the calls differ in m or n, or a batch is empty");
+    if (g.n != nn) widw = true;
     if (g.variant == V_GENERIC) { // (a forced generic kernel stays generic; one that is generic only because no tile divides m may run ragged)
       if ((!edge_on || edge_why || g.generic_forced) && !ragw) {
         if (!g.generic_forced && ragged_w()) ragw = true;
@@ -294,7 +331,8 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (tile >= 0) b_kind = rounds_kind;
     else if (!edge_on || edge_why) NOCHAIN(rounds_why);
   }
-  if (divisible) {
+  if (widw && (!divisible || ragw)) NOCHAIN("the calls differ in n and one of them is ragged: different widths combine with no other chain mode");
+  if (divisible && !widw) {
     // (variants 20 .. 23 VNNI-2, 24 .. 27 flat B, 28 .. 31 VNNI-4: the same four tiles)
     const int planned = blw_variant_tile(d[0]->variant, b_kind);
     bool same = !f32 && planned >= 0 && planned < 4;
@@ -317,6 +355,10 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   if (ragw) { // the ragged-width launch: the rule's tile and the calls' B image
     tile = ragw_tile;
     b_kind = ragw_kind;
+  }
+  if (widw) { // the mixed-width launch: the rule's tile (whole tiles of m and of every n, the widest layer's grid within the compute units)
+    tile = widw_tile;
+    b_kind = widw_kind;
   }
   bool ragged = tile < 0; // (only with a switch on: every path to here with both off has a tile)
   if (ragged) {
@@ -376,7 +418,14 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   c.nlayers = n;
   for (int i = 0; i < n; ++i)
     c.L[i] = ChainLayer{pb[i], pd[i], pc[i], d[i]->ldb, d[i]->ldc, d[i]->stride_a, d[i]->stride_b, (int)d[i]->k, (int)br[i],
-                        EP_BETA0 | (d[i]->bias ? EP_BIAS : 0) | (d[i]->relu ? EP_RELU : 0), 0};
+                        EP_BETA0 | (d[i]->bias ? EP_BIAS : 0) | (d[i]->relu ? EP_RELU : 0), widw ? (int)d[i]->n : 0};
+  int widw_tiles[CH_MAXL] = {}; // a mixed-width chain: column tiles per layer; the grid is the widest layer's
+  if (widw) {
+    for (int i = 0; i < n; ++i) {
+      widw_tiles[i] = (int)(d[i]->n / bn);
+      if (d[i]->n > c.n) c.n = (int)d[i]->n;
+    }
+  }
   // the pool of error words is about to run dry (hundreds of launches without a synchronisation): synchronise and check here
   // instead of ever dropping a journal entry
   if (g_chain_journaled.load(std::memory_order_relaxed) >= CHAIN_ERR_POOL - 8) {
@@ -394,7 +443,10 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   }
   std::lock_guard<std::mutex> lk(g_chain_mu);
   // (a ragged chain: keyed on ceil(m / BM), the counters it uses; a ragged-width chain on ceil(n / BN) as well - the arrivals per counter)
-  ChainBlock &blk = chain_block(s, (int)((m + bm - 1) / bm), (int)(ragw ? (nn + bn - 1) / bn : nn / bn), n);
+  // (a mixed-width chain: on the widest layer's column tiles AND every layer's own - two chains with one grid but different inner widths
+  // add different numbers to a layer's counters and may not share them)
+  ChainBlock &blk = widw ? chain_block(s, (int)(m / bm), c.n / bn, n, widw_tiles)
+                         : chain_block(s, (int)((m + bm - 1) / bm), (int)(ragw ? (nn + bn - 1) / bn : nn / bn), n);
   c.cnt = blk.cnt;
   c.err = blk.err; // probation launches: the block's word (checked right behind the launch)
   if (blk.verified >= 1) {
@@ -411,8 +463,15 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     g_chain_err_free.pop_back();
   }
   c.target = ++blk.epoch * (unsigned)blk.tiles_n;
+  if (widw) c.target = blk.epoch; // (the kernel multiplies by the producing layer's column tiles: chain_widths_target)
   if (f32) HIP_OK(launch_f32_chain(tile, c, s));
-  else if (ragw) {
+  else if (widw) {
+    HIP_OK(launch_bf16_chain_widths(tile, b_kind, c, s));
+    g_chain_widths_stats[1].store(m / bm, std::memory_order_relaxed);
+    g_chain_widths_stats[2].store(c.n / bn, std::memory_order_relaxed);
+    g_chain_widths_stats[3].store(blw_variant(tile, b_kind), std::memory_order_relaxed);
+    g_chain_widths_stats[0].fetch_add(1, std::memory_order_relaxed);
+  } else if (ragw) {
     HIP_OK(launch_bf16_chain_ragged(tile, b_kind, c, s));
     g_chain_ragged_stats[1].store((m + bm - 1) / bm, std::memory_order_relaxed);
     g_chain_ragged_stats[2].store((nn + bn - 1) / bn, std::memory_order_relaxed);

@@ -236,6 +236,17 @@ inline std::atomic<int> g_chain_ragged{[] {
   return chain_ragged_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_chain_ragged_stats[4]; // ragged-width chain launches; tile rows, tile columns (both ceil-divided), GemmVariant of the tile (with its B image) of the latest
+// MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths / TPP_HIP_CHAIN_WIDTHS; gemm_plan.cpp plan_chain_widths, rt_chain.h try_chain_launch,
+// brgemm_bf16_lw_chain_widths.h): 0 = off, 1 = a divisible bf16 chain whose layers differ in n (1024-4096-1024) runs as one launch on
+// m / BM x max_l(n_l / BN) workgroups, each sitting out the layers that have no column tile for it. A switch of its own: equal widths stay
+// the plain chain's, and a ragged m, n or k or several rounds never combine with different widths.
+inline bool chain_widths_mode_ok(int v) { return v == 0 || v == 1; }
+inline std::atomic<int> g_chain_widths{[] {
+  const char *e = getenv("TPP_HIP_CHAIN_WIDTHS");
+  const int v = e ? atoi(e) : 0;
+  return chain_widths_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_chain_widths_stats[4]; // mixed-width chain launches; row blocks, the widest layer's column tiles, GemmVariant of the tile (with its B image) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

@@ -129,6 +129,8 @@ _SIGNATURES = {
     "xsmm_hip_chain_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_ragged": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_ragged_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_chain_widths": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_chain_widths_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_rounds": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_rounds_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
@@ -458,6 +460,19 @@ class XsmmRuntime:
         20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_chain_ragged_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_chain_widths(self, mode):
+        """bf16 layer chains whose layers differ in n (1024-4096-1024, funnels), as one launch on m / BM x max_l(n_l / BN) workgroups, each
+        sitting out the layers that have no column tile for it: 0 off (default), 1 on - the tile all calls were dispatched on if it
+        fits, else (not in strict mode) the smallest that fits; returns the previous value, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_chain_widths(mode)
+
+    def chain_widths_stats(self):
+        """(mixed-width chain launches; row blocks m / BM, column tiles of the widest layer, variant number of the tile with its B image -
+        20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_chain_widths_stats(out)
         return tuple(int(v) for v in out)
 
     def set_chain_rounds(self, mode):
