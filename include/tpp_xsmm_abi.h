@@ -579,6 +579,30 @@ TPP_XSMM_EXPORT void xsmm_hip_chain_ragged_stats(int64_t out[4]);
  * counters of the other chain modes and of the single-call edge switches do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_chain_widths(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_chain_widths_stats(int64_t out[4]);
+/* Column rounds of mixed-width layer chains, opt-in (environment: TPP_HIP_CHAIN_WIDTH_ROUNDS, read as a number; default 0 = off): a switch
+ * of its own - xsmm_hip_set_chain_widths and every other switch keep their meaning. Mode 1: a chain that passes what
+ * xsmm_hip_set_chain_widths(1) asks of the calls (bf16, 2 .. 8 calls, the same m, at least two different n, beta 0, no VNNI C, not the
+ * generic kernel, one B image of the loader-wave tiles, every k >= 64 and a multiple of 64, every batch count >= 1, BM divides m and BN
+ * every n_l) runs as ONE launch on m / BM x W resident workgroups, 1 <= W < max_l T_l with T_l = n_l / BN and m / BM * W <= the stream's
+ * compute units: workgroup (tm, c) walks the column tiles c, c + W, .. of every layer that has them, layer by layer, and sits out a
+ * layer with T_l <= c. So a chain whose widest layer has more tiles than compute units (4096 rows x [1024, 4096, 1024]), which the
+ * one-round launch refuses, runs as one launch. W for a tile: Wfit = min(max T - 1, compute units / (m / BM)), R = ceil(max T / Wfit),
+ * W = ceil(max T / R). The tile: the loader-wave tile ALL calls were dispatched on if it fits with its W - the launch then has the bits of
+ * the calls made one by one, so strict mode takes it -, otherwise (never in strict mode) the tile with the smallest K-loop time
+ * sum_l ceil(T_l / W) * (the tile's fitted time per 64-k chunk) * batch_l * k_l / 64, ties to the larger tile. Where
+ * xsmm_hip_set_chain_widths(1) is on as well and takes the chain, its one-round launch runs as before; this rule is asked where that one
+ * refuses or gates, or is off. THE GATE: what measured slower than call by call stays call by call in mode 1
+ * (profiles/chain_width_rounds_ab.txt; gemm_plan.h chain_width_rounds_gated names the regions and quotes the rows).
+ * Mode 1000 + W (W >= 1; a test and measurement switch): that W on the tile all calls were dispatched on, without one on the smallest tile
+ * that fits with it; asked in front of xsmm_hip_set_chain_widths' rule, never gated; a W that does not fit (W >= max T included) leaves
+ * every decision as with the switch off. A ragged m, n or k, f32 and synchronous mode stay call by call whatever the other switches say.
+ * A starved launch degrades as every chain launch. Returns the previous value, -1 (nothing changed) for any value other than 0, 1 and
+ * 1000 + W.
+ * _stats: out[0] column-round launches since process start; of the most recent one: [1] row blocks m / BM, [2] workgroup columns W,
+ * [3] the variant number of its tile with its B image (20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4). The counters of the other chain modes
+ * and of the single-call edge switches do not move on these launches, nor this one on theirs. */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_width_rounds(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_width_rounds_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

@@ -125,6 +125,12 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   // over STEPS (layer, round) and takes tm and m0 from the step. The A state is rebuilt per step (the row base moves); the B state per
   // step too (the same layer's panels again, or the next layer's), ahead of the step wherever the run-ahead rule holds.
   constexpr bool ROUNDS = GRP == BLW_CHAIN_ROUNDS;
+  // GRP = 10 (a mixed-width chain in COLUMN ROUNDS, brgemm_bf16_lw_chain_wrounds.h): GRP = 9 on p.groups workgroup columns. n0 arrives as the
+  // column GROUP's first tile; the loop below runs over STEPS (layer, column tile) as GRP = 7's does over (layer, row block) and takes tn
+  // and n0 from the step. Both states are rebuilt per step; the B loaders run ahead into the next step, the A loaders never do (the
+  // epilogue's staging tiles lie in the A halves such a run-ahead would fill). The seam wait stands in front of every step.
+  constexpr bool WRND = blw_chain_wrounds(GRP);
+  [[maybe_unused]] int tn = n0 / BN; // (GRP = 10: the step's column tile)
   constexpr int A_SLOT = BM * 128, SLOT = (BM + BN) * 128;
   // SUP = chunks per barrier (the unit everything below counts in: a "chunk" of this function is SUP 64-k chunks, a "slot" SUP
   // consecutive ring slots). SUP = 2 halves the barrier count and the loader's per-iteration scalar work for the small tiles, whose
@@ -245,14 +251,18 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   constexpr int PRIMED = -2; // GRP = 7, a value of state_layer: the run-ahead of the step before loaded THIS step's state
   // (ONE loop: GRP = 7 goes from step to step - tm from the group's first row block to its last, then the next layer -, every other
   // launch from layer to layer)
-  for (int lc = 0; lc < L; ROUNDS ? chain_rounds_next(tm, lc, p.groups, p.tiles_m) : (void)++lc) {
+  for (int lc = 0; lc < L; ROUNDS ? chain_rounds_next(tm, lc, p.groups, p.tiles_m) : WRND ? chain_wrounds_next(tn, lc, p.groups, p.L[lc].pad / BN) : (void)++lc) {
     if constexpr (ROUNDS) m0 = tm * BM;
     if constexpr (CWID) {
       if (!chain_widths_active(n0 / BN, p.L[lc].pad, BN)) continue; // (uniform over the workgroup: n0 and the layer's n)
     }
+    if constexpr (WRND) {
+      if (!chain_widths_active(tn, p.L[lc].pad, BN)) continue; // (the group sits the layer out: the increment above goes to the next layer)
+      n0 = tn * BN;
+    }
     const int T = (ITEMS ? it_br : p.L[lc].br) * (KEDGE ? bkedge_chunks(p.L[lc].k) : p.L[lc].k / BLW_BK) / SUP; // (a multiple of SUP: the launcher picks SUP = 1 otherwise)
     int pre = NSLOT - 2; // chunks of this layer already requested by the run-ahead of the previous layer's tail
-    if constexpr (ROUNDS) {
+    if constexpr (ROUNDS || WRND) {
       if (state_layer != PRIMED) {
         BLW_LOAD_STATE(lc);
         pre = 0;
@@ -274,6 +284,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       // (GRP = 9: p.target is the epoch, the producers of layer lc - 1 are that layer's column tiles)
       unsigned target = p.target;
       if constexpr (CWID) target = chain_widths_target(p.target, p.L[lc > 0 ? lc - 1 : 0].pad, BN);
+      if constexpr (WRND) target = chain_widths_target(p.target, p.L[lc > 0 ? lc - 1 : 0].pad, BN); // (GRP = 10: the same counters)
       const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
       for (int bw = b_first; bw <= b_last; ++bw) {
         g_u32_lw *c = (g_u32_lw *)(p.cnt + ((size_t)(lc - 1) * p.tiles_m + bw) * CHAIN_CNT_STRIDE);
@@ -312,8 +323,28 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
     }
     // the last NSLOT - 2 barriers of the layer: nothing of THIS layer is left to request. The next step of a multi-round chain: this
     // layer's next row block (the same weight panels again), or the next layer's first
-    const bool more_rounds = ROUNDS && chain_rounds_more(tm, p.groups, p.tiles_m);
-    if constexpr (CWID) {
+    const bool more_rounds = (ROUNDS && chain_rounds_more(tm, p.groups, p.tiles_m)) || (WRND && chain_wrounds_more(tn, p.groups, p.L[lc].pad / BN));
+    if constexpr (WRND) {
+      // GRP = 10: the run-ahead loads this workgroup's NEXT STEP - the group's next column tile of this layer, or the first tile of its next
+      // active layer (L = none: the else arm's loop). n0 is the next step's from here on: nothing below reads it, the loop's head sets it again.
+      const int ntn = more_rounds ? tn + p.groups : chain_wrounds_group(tn, p.groups);
+      const int nxt = more_rounds ? lc : chain_widths_next(ntn, lc, L, BN, [&](int l_) { return p.L[l_].pad; });
+      if (ahead && nxt < L) {
+        n0 = ntn * BN;
+        BLW_LOAD_STATE(nxt);
+        state_layer = PRIMED;
+        for (; t + 1 < T; ++t) {
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSLOT - 3) * PPL) : "memory");
+          __builtin_amdgcn_s_barrier();
+          BLW_ISSUE(slot);
+        }
+      } else {
+        for (; t + 1 < T; ++t) {
+          blw_wait_younger<PPL>(T - 2 - t);
+          __builtin_amdgcn_s_barrier();
+        }
+      }
+    } else if constexpr (CWID) {
       // GRP = 9: the run-ahead loads this workgroup's next ACTIVE layer (L = none: the else arm's loop). A statement of its own, so that
       // the other modes' code below is the text it was.
       const int nxt = chain_widths_next(n0 / BN, lc, L, BN, [&](int l_) { return p.L[l_].pad; });
@@ -380,6 +411,11 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // its waves alike, without a barrier or a ring slot. After every active layer but the chain's last it runs the whole seam (drain, R1, S1,
   // one arrival at cnt[l][tm]), also when no further layer is active for it. p.target is the epoch (blw_loader).
   constexpr bool CWID = blw_chain_widths(GRP);
+  // GRP = 10 (a mixed-width chain in COLUMN ROUNDS, xsmm_hip_set_chain_width_rounds; brgemm_bf16_lw_chain_wrounds.h): GRP = 9 on m / BM x p.groups
+  // workgroups, fewer columns than the widest layer has column tiles. Workgroup (tm, c) walks the column tiles c, c + groups, .. of every
+  // layer that has them, layer-major; every step is GRP = 9's active layer with tn and n0 taken from the step, and runs the whole seam
+  // (one arrival at cnt[l][tm]) unless its layer is the chain's last. p.target is the epoch; p.tiles_n stays the widest layer's.
+  constexpr bool WRND = blw_chain_wrounds(GRP);
   constexpr bool EDGE_ROWS = blw_edge_rows(GRP), EDGE_COLS = blw_edge_cols(GRP); // (the last tile of a column / row of tiles is shifted back)
   // GRP = 7 (a chain in SEVERAL ROUNDS, xsmm_hip_set_chain_rounds): MULTI on p.groups x tiles_n workgroups, fewer than the output tiles -
   // workgroup (g, tn) walks the row blocks g, g + groups, .. of every layer, layer-major (the file's header; brgemm_bf16_lw_chain_rounds.h).
@@ -471,6 +507,17 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
     it_C = w.C;
     it_D = w.D;
     it_br = (int)w.br;
+  } else if constexpr (WRND) {
+    // (the grid is tiles_m x p.groups: the XCD grid and the linear order count column GROUPS where the other launches count column tiles)
+    if (p.xm > 0) {
+      const int xn = 8 / p.xm, xcd = b & 7, j = b >> 3;
+      const int lm = p.tiles_m / p.xm, ln = p.groups / xn;
+      tm = (xcd / xn) * lm + j / ln;
+      tn = (xcd % xn) * ln + j % ln;
+    } else {
+      tm = b / p.groups;
+      tn = b - tm * p.groups;
+    }
   } else if (p.xm > 0) {
     const int xn = 8 / p.xm, xcd = b & 7, j = b >> 3;
     const int lm = (ROUNDS ? p.groups : p.tiles_m) / p.xm, ln = p.tiles_n / xn; // tiles per XCD (GRP = 7: row groups)
@@ -490,7 +537,7 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // tiles have several wave columns) - the others are the neighbour's. n0 is a multiple of 8 (the planner asks for n % 8 == 0).
   // (GRP = 7: tm is the workgroup's row GROUP up to here; the step loops below and in blw_loader take tm and m0 from the step)
   int m0 = GRP == BLW_CHAIN_EDGE || CRAG ? chain_edge_row0(tm, p.tiles_m, p.m, BM) : (EDGE_ROWS && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
-  const int n0 = (EDGE_COLS && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN;
+  int n0 = (EDGE_COLS && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN; // (GRP = 10: the column group's first tile; the step loops take n0 from the step)
   [[maybe_unused]] const int skip_cols = tn * BN - n0;
   [[maybe_unused]] const int own_row = tm * BM - m0, own_col = tn * BN - n0;
   const int L = MULTI ? p.nlayers : 1;
@@ -688,10 +735,14 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   int s0 = 0; // ring slot of the current layer's chunk 0
   // (ONE loop: GRP = 7 goes from step to step - tm from the group's first row block to its last, then the next layer -, every other
   // launch from layer to layer; blw_loader counts the same way)
-  for (int l = 0; l < L; ROUNDS ? chain_rounds_next(tm, l, p.groups, p.tiles_m) : (void)++l) {
+  for (int l = 0; l < L; ROUNDS ? chain_rounds_next(tm, l, p.groups, p.tiles_m) : WRND ? chain_wrounds_next(tn, l, p.groups, p.L[l].pad / BN) : (void)++l) {
     if constexpr (ROUNDS) m0 = tm * BM;
     if constexpr (CWID) {
       if (!chain_widths_active(tn, p.L[l].pad, BN)) continue; // (the loaders skip the same layers: n0 = tn * BN)
+    }
+    if constexpr (WRND) {
+      if (!chain_widths_active(tn, p.L[l].pad, BN)) continue; // (the group sits the layer out; blw_loader walks the same steps)
+      n0 = tn * BN;
     }
     const auto &Y = p.L[l];
     const int T = (ITEMS ? it_br : Y.br) * (KEDGE ? bkedge_chunks(Y.k) : Y.k / BLW_BK);
@@ -969,6 +1020,15 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
         }
       }
     }
+    if constexpr (WRND) {
+      if (l + 1 == L) {
+        if (!chain_wrounds_more(tn, p.groups, p.L[l].pad / BN)) break;
+        // a further column tile of the LAST layer follows: GRP = 7's rendezvous below, nothing to publish
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier(); // S1
+        continue;
+      }
+    }
     if (l + 1 == L && (!ROUNDS || !chain_rounds_more(tm, p.groups, p.tiles_m))) break;
     if constexpr (ROUNDS) {
       if (l + 1 == L) {
@@ -1008,10 +1068,16 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   // GRP = 7 (several rounds): a.groups row groups are resident, each a row of tiles_n workgroups; the grid and the XCD search below
   // count row groups where the other launches count row blocks
   int grid_m = args.tiles_m;
+  [[maybe_unused]] int grid_n = args.tiles_n;
   if constexpr (GRP == BLW_CHAIN_ROUNDS) {
     if (a.m % BM != 0 || a.n % BN != 0 || a.groups < 1 || a.groups > args.tiles_m) return hipErrorInvalidValue;
     grid_m = a.groups;
     tiles = (long long)grid_m * args.tiles_n;
+  } else if constexpr (blw_chain_wrounds(GRP)) {
+    // GRP = 10 (column rounds): a.groups workgroup COLUMNS are resident; tiles_n stays the widest layer's column tiles
+    if (a.groups < 1 || a.groups >= args.tiles_n) return hipErrorInvalidValue;
+    grid_n = a.groups;
+    tiles = (long long)grid_m * grid_n;
   } else {
     args.groups = 0;
   }
@@ -1032,7 +1098,7 @@ static hipError_t launch_blw_t(const ChainArgs &a, hipStream_t s, const void *it
   long long best = -1;
   for (int xm = 8; xm >= 1; xm >>= 1) {
     const int xn = 8 / xm;
-    if (grid_m % xm || args.tiles_n % xn) continue;
+    if (grid_m % xm || (blw_chain_wrounds(GRP) ? grid_n : args.tiles_n) % xn) continue;
     const long long cost = (long long)xn * a.m + (long long)xm * a.n;
     if (best < 0 || cost < best) {
       best = cost;

@@ -6,6 +6,7 @@
 #include "brgemm_bf16_lw_kedge.h"
 #include "brgemm_bf16_lw_chain_ragged.h"
 #include "brgemm_bf16_lw_chain_widths.h"
+#include "brgemm_bf16_lw_chain_wrounds.h"
 
 namespace tpp {
 
@@ -25,12 +26,15 @@ constexpr int BLW_MODES = 8;
 constexpr int BLW_CHAIN_RAGGED = 8; // a chain with a ragged n and / or a k that is a multiple of 8 but not of 64 in some layer
 // A MIXED-WIDTH chain (xsmm_hip_set_chain_widths): beside the table in the same way (brgemm_bf16_lw_chain_widths.hip, predicates at the end)
 constexpr int BLW_CHAIN_WIDTHS = 9; // a chain whose layers differ in n: a workgroup sits out the layers that have no column tile for it
+// A mixed-width chain in COLUMN ROUNDS (xsmm_hip_set_chain_width_rounds): beside the table too (brgemm_bf16_lw_chain_wrounds.hip, predicates at the end)
+constexpr int BLW_CHAIN_WROUNDS = 10; // BLW_CHAIN_WIDTHS on fewer resident workgroup columns than the widest layer has column tiles
 
 // what follows from a mode
 constexpr bool blw_items(int g) { return g == BLW_ITEMS || g == BLW_QUADS; }      // operands and batch count come from an item
 constexpr bool blw_ragged_k(int g) { return g == BLW_KEDGE || g == BLW_KEDGE8; }  // the last chunk of a batch element is shifted back
 constexpr bool blw_chain_ragged(int g) { return g == BLW_CHAIN_RAGGED; }         // every layer its own k class, tested in half steps
 constexpr bool blw_chain_widths(int g) { return g == BLW_CHAIN_WIDTHS; }         // per-layer n in the argument block, skipped layers
+constexpr bool blw_chain_wrounds(int g) { return g == BLW_CHAIN_WROUNDS; }       // ... and a workgroup walks several column tiles of a layer
 constexpr bool blw_half_steps(int g) { return g == BLW_KEDGE8; }                  // ... and its overlap ends in the middle of a k-step
 // the last row block is shifted back to end at row m and stores its own rows only
 constexpr bool blw_edge_rows(int g) { return g == BLW_EDGE || blw_ragged_k(g) || g == BLW_CHAIN_EDGE || blw_chain_ragged(g); }
@@ -43,13 +47,14 @@ constexpr bool blw_mode_ok(int g, bool multi, int sup) {
   return g >= 0 && g < BLW_MODES && (multi ? g == BLW_LAYER || blw_chain(g) : !blw_chain(g)) && (!blw_one_chunk(g) || sup == 1);
 }
 template <int GRP, bool MULTI, int SUP> struct BlwModeCheck {
-  static_assert((GRP >= 0 && GRP < BLW_MODES) || blw_chain_ragged(GRP) || blw_chain_widths(GRP), "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds, 8: a ragged-width chain, 9: a mixed-width chain");
-  static_assert(!MULTI || GRP == BLW_LAYER || blw_chain(GRP) || blw_chain_ragged(GRP) || blw_chain_widths(GRP), "a grouped launch is a set of single layers");
+  static_assert((GRP >= 0 && GRP < BLW_MODES) || blw_chain_ragged(GRP) || blw_chain_widths(GRP) || blw_chain_wrounds(GRP), "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds, 8: a ragged-width chain, 9: a mixed-width chain, 10: a mixed-width chain in column rounds");
+  static_assert(!MULTI || GRP == BLW_LAYER || blw_chain(GRP) || blw_chain_ragged(GRP) || blw_chain_widths(GRP) || blw_chain_wrounds(GRP), "a grouped launch is a set of single layers");
   static_assert(!blw_ragged_k(GRP) || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
   static_assert(!blw_chain(GRP) || (SUP == 1 && MULTI), "a ragged / multi-round chain: a chain, one chunk per barrier");
   static_assert(!blw_chain_ragged(GRP) || (SUP == 1 && MULTI), "a ragged-width chain: a chain, one chunk per barrier");
   static_assert(!blw_chain_widths(GRP) || (MULTI && (SUP == 1 || SUP == 2)), "a mixed-width chain: a chain, one or two chunks per barrier");
-  static constexpr bool ok = blw_chain_ragged(GRP) ? MULTI && SUP == 1 : blw_chain_widths(GRP) ? MULTI && (SUP == 1 || SUP == 2) : blw_mode_ok(GRP, MULTI, SUP);
+  static_assert(!blw_chain_wrounds(GRP) || (SUP == 1 && MULTI), "a mixed-width chain in column rounds: a chain, one chunk per barrier");
+  static constexpr bool ok = blw_chain_ragged(GRP) || blw_chain_wrounds(GRP) ? MULTI && SUP == 1 : blw_chain_widths(GRP) ? MULTI && (SUP == 1 || SUP == 2) : blw_mode_ok(GRP, MULTI, SUP);
 };
 
 // THE TILES. 0 = 32x64 + K2, 1 = 64x64, 2 = 64x128, 3 = 128x128, 4 = 32x32 + K2. Loader waves per tile (NLA + NLB), same-box A/B
@@ -155,6 +160,19 @@ constexpr bool blw_chain_widths_launch_ok(int tile, int b_kind, const BlwWidthsS
     if (a.n[l] != a.n[0]) differ = true;
   }
   return differ && a.m >= bm && a.m % bm == 0;
+}
+
+// THE MIXED-WIDTH CHAIN IN COLUMN ROUNDS (BLW_CHAIN_WROUNDS, brgemm_bf16_lw_chain_wrounds.hip; schedule in brgemm_bf16_lw_chain_wrounds.h): MULTI,
+// one chunk per barrier. Is the instance of (tile, b_kind) compiled? Tiles 0 .. 3 with the three B images - twelve, none with scratch.
+constexpr bool blw_chain_wrounds_instance_exists(int tile, int b_kind) { return tile >= 0 && tile <= 3 && blw_b_kind_ok(b_kind); }
+// ... and what its launcher refuses: everything the mixed-width chain's does, and a number of column groups that is not
+// 1 <= groups < max_l(n(l) / BN) (as many groups as the widest layer has column tiles is BLW_CHAIN_WIDTHS's launch)
+constexpr bool blw_chain_wrounds_launch_ok(int tile, int b_kind, const BlwWidthsShape &a, int groups) {
+  if (!blw_chain_wrounds_instance_exists(tile, b_kind) || !blw_chain_widths_launch_ok(tile, b_kind, a)) return false;
+  int maxT = 0;
+  for (int l = 0; l < a.nlayers; ++l)
+    if (a.n[l] / BLW_TILES[tile].bn() > maxT) maxT = a.n[l] / BLW_TILES[tile].bn();
+  return groups >= 1 && groups < maxT;
 }
 
 } // namespace tpp

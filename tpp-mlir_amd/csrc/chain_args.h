@@ -30,7 +30,7 @@ struct ChainArgs {
   int nlayers;
   int tiles_m, tiles_n; // filled by the launcher
   int xm;               // filled by the launcher: XCD grid xm x (8 / xm) over the tile grid, 0 = linear tile order
-  int groups;           // a multi-round chain (launch_bf16_chain, BLW_CHAIN_ROUNDS): resident row groups G, the grid is G x tiles_n; 0 in every other launch
+  int groups;           // a multi-round chain (launch_bf16_chain, BLW_CHAIN_ROUNDS): resident row groups G, the grid is G x tiles_n; column rounds (launch_bf16_chain_wrounds): resident workgroup columns W; 0 in every other launch
   // Unused. Keeps L at byte 72 of the argument block: without these bytes every L[] load moves and the compiler assigns
   // registers differently in the f32 chain kernels' K loop, a code change that would have to be measured on its own.
   char reserved[8];
@@ -59,6 +59,10 @@ hipError_t launch_bf16_chain_ragged(int tile, int b_kind, const ChainArgs &a, hi
 // the widest layer's (the grid: m / BM x a.n / BN workgroups, at most the stream's compute units - the caller's guarantee) and a.target
 // the launch's EPOCH: cnt[l][*] reaches epoch * (a.L[l].pad / BN). blw_chain_widths_launch_ok is what it refuses
 hipError_t launch_bf16_chain_widths(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
+// a mixed-width chain in COLUMN ROUNDS (brgemm_bf16_lw_chain_wrounds.hip, BLW_CHAIN_WROUNDS, xsmm_hip_set_chain_width_rounds): the arguments of
+// launch_bf16_chain_widths + a.groups = W resident workgroup columns, 1 <= W < a.n / BN (the grid: m / BM x W workgroups, at most the
+// stream's compute units - the caller's guarantee). blw_chain_wrounds_launch_ok is what it refuses
+hipError_t launch_bf16_chain_wrounds(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2; b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);

@@ -621,6 +621,83 @@ ChainWidthsPlan plan_chain_widths(int64_t m, int nlayers, const int64_t *n, cons
   return no("no tile divides m and every n (a ragged shape stays call by call with different widths)");
 }
 
+ChainWidthRoundsPlan plan_chain_width_rounds(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int b_kind, int mode, bool strict) {
+  auto no = [](const char *why) { return ChainWidthRoundsPlan{-1, 0, why, false}; };
+  const bool forced = chain_width_rounds_mode_forced(mode);
+  if (mode != 1 && !forced) return no("column rounds of mixed-width chains are off (xsmm_hip_set_chain_width_rounds)");
+  if (planned_tile < -1) return no("a mixed-width chain is bf16: an f32 call");
+  if (nlayers < 2 || nlayers > 8) return no("fewer than 2 or more than 8 calls");
+  if (!blw_b_kind_ok(b_kind)) return no("the calls of a mixed-width chain do not share one B image of the loader-wave tiles");
+  bool differ = false;
+  int64_t widest = 0;
+  for (int l = 0; l < nlayers; ++l) {
+    if (k[l] < BK || k[l] % BK != 0) return no("a layer of a mixed-width chain has k not in 64-k chunks");
+    if (br[l] < 1) return no("a layer of a mixed-width chain has an empty batch");
+    if (n[l] != n[0]) differ = true;
+    if (n[l] > widest) widest = n[l];
+  }
+  if (!differ) return no("every call has the same n: not a mixed-width chain");
+  auto divides = [&](int t) {
+    if (t < 0 || t > 3 || m < BLW_BM[t] || m % BLW_BM[t] != 0 || m / BLW_BM[t] > 0x7fffffff) return false;
+    for (int l = 0; l < nlayers; ++l)
+      if (n[l] < BLW_BN[t] || n[l] % BLW_BN[t] != 0 || n[l] / BLW_BN[t] > 0x7fffffff) return false;
+    return true;
+  };
+  auto max_t = [&](int t) { return (int)(widest / BLW_BN[t]); };
+  auto fits = [&](int t, int64_t w) {
+    return divides(t) && blw_chain_wrounds_instance_exists(t, b_kind) && w >= 1 && w < max_t(t) && (m / BLW_BM[t]) * w <= cus;
+  };
+  // the rule's W of a tile that divides: as few rounds of the widest layer as fit, balanced (0: none fits)
+  auto balanced = [&](int t) {
+    const int wfit = chain_wrounds_max_groups(max_t(t), (int)(m / BLW_BM[t]), cus);
+    return wfit < 1 ? 0 : chain_wrounds_groups(max_t(t), wfit);
+  };
+  if (planned_tile < 0 && strict) return no("strict mode: the calls of a mixed-width chain do not share one planned loader-wave tile");
+  if (forced) {
+    const int64_t w = mode - 1000;
+    int tile = -1;
+    if (planned_tile >= 0) tile = fits(planned_tile, w) ? planned_tile : -1;
+    else
+      for (int t = 0; t < 4 && tile < 0; ++t)
+        if (fits(t, w)) tile = t;
+    if (tile < 0) return no("the forced column groups do not fit: whole tiles, 1 <= W < max_l(n_l / BN) and m / BM * W <= compute units");
+    return ChainWidthRoundsPlan{tile, (int)w, "", false};
+  }
+  int tile = -1;
+  if (planned_tile >= 0 && divides(planned_tile) && fits(planned_tile, balanced(planned_tile))) tile = planned_tile;
+  const bool planned = tile >= 0;
+  if (tile < 0 && strict) return no("strict mode: column rounds only on the tile all calls were dispatched on");
+  if (tile < 0) {
+    // the K-loop time by the fitted per-chunk rates: sum_l rounds(l) * BLW_B[tile] * br_l * k_l / 64; ties go to the larger tile
+    double best = 0;
+    for (int t = 0; t < 4; ++t) {
+      if (!divides(t) || !fits(t, balanced(t))) continue;
+      const int w = balanced(t);
+      double cost = 0;
+      for (int l = 0; l < nlayers; ++l) cost += (double)chain_wrounds_rounds((int)(n[l] / BLW_BN[t]), w) * BLW_B[t] * (double)br[l] * (double)(k[l] / BK);
+      if (tile < 0 || cost <= best) tile = t, best = cost;
+    }
+  }
+  if (tile < 0) {
+    bool any = false, rows = false;
+    for (int t = 0; t < 4; ++t)
+      if (divides(t)) {
+        any = true;
+        if (m / BLW_BM[t] <= cus) rows = true;
+      }
+    if (!any) return no("no tile divides m and every n (a ragged shape stays call by call with different widths)");
+    if (!rows) return no("more row blocks than compute units: not one column of workgroups fits");
+    return no("nothing to round: no W below the widest layer's column tiles fits");
+  }
+  const int w = balanced(tile);
+  // THE GATE (measured, profiles/chain_width_rounds_ab.txt; the rows are quoted in gemm_plan.h): on a tile of the rule's own choice no chain
+  // gained - 1024-4096-1024 at 256, 1024, 2048 and 4096 rows ran +28 %, +33 %, +9 % and +7 %, the funnel +2 % in one session and -4 % in
+  // the next -, on a tile all calls were dispatched on the launch gained 1 .. 2 % in every session
+  if (!planned)
+    return ChainWidthRoundsPlan{tile, w, "gate: not on a tile all calls were dispatched on - measured slower in column rounds than call by call (profiles/chain_width_rounds_ab.txt)", true};
+  return ChainWidthRoundsPlan{tile, w, "", false};
+}
+
 int chain_rounds_b_kind(const GemmDesc &d) {
   if (d.dtype != DT_BF16 || d.vnni_c || !d.beta0 || d.generic_forced || d.variant == V_GENERIC) return -1;
   return bf16_edge_b_kind(d);

@@ -203,6 +203,39 @@ ChainRoundsPlan plan_chain_rounds(int64_t m, int64_t n, int nlayers, const int64
 // funnel [1024, 512, 256, 128], on the smallest tile, 28 % faster.
 struct ChainWidthsPlan { int tile; const char *why; };
 ChainWidthsPlan plan_chain_widths(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int b_kind, int mode, bool strict);
+// MIXED-WIDTH CHAINS IN COLUMN ROUNDS (xsmm_hip_set_chain_width_rounds; rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_wrounds.hip
+// launch_bf16_chain_wrounds, BLW_CHAIN_WROUNDS, schedule in brgemm_bf16_lw_chain_wrounds.h). Host-only, no HIP calls:
+// tests/golden/gemm_plan_chain_width_rounds.txt is the table of the function's answers. The mixed-width chain above on m / BM x W resident
+// workgroups, 1 <= W < max_l(n[l] / BN): a workgroup walks several column tiles of a wide layer and one (or none) of a narrow one. The
+// arguments are plan_chain_widths'. A tile FITS with W when BM divides m, BN divides every n[l], 1 <= W < max_l T_l (T_l = n[l] / BN) and
+// m / BM * W <= cus. The tile's BALANCED W: Wfit = min(max T - 1, cus / (m / BM)), R = ceil(max T / Wfit), W = ceil(max T / R).
+//   mode 1:        the planned tile if it fits with its balanced W (the launch then has the calls' bits: strict mode takes it too); else,
+//                  never in strict mode, of the tiles 0 .. 3 that fit with their balanced W the one with the smallest
+//                  sum_l ceil(T_l / W) * BLW_B[tile] * br[l] * k[l] / 64 - the K-loop time by the fitted per-chunk rates -, ties to the
+//                  larger tile. A chain whose widest layer would fit in one round is offered too (R = 2).
+//   mode 1000 + W: that W on the planned tile, without one on the smallest tile that fits with it. Never gated. A W that does not fit is a
+//                  refusal: the caller decides as with the switch off.
+// tile = -1, groups = 0 and why = the reason: the switch off, an f32 call, fewer than 2 or more than 8 layers, no shared B image, a k not
+// in 64-k chunks, an empty batch, every n equal, strict mode without a planned tile (or with one that does not fit), m or an n no tile
+// divides (ragged shapes never combine with this mode), more row blocks than compute units (no W >= 1 fits), nothing to round (no W < max T
+// fits), a forced W that does not fit.
+// THE GATE (mode 1 only; measured, profiles/chain_width_rounds_ab.txt: VNNI-2 on 256 CUs, call by call -> one launch in column rounds, us
+// per step; n[] as the rule sees it - the block 1024 -> 4096 -> 1024 is the two calls n = [4096, 1024]). On a tile of the rule's OWN
+// choice - not one all calls were dispatched on - no chain gained: n = [4096, 1024] at 256 rows 16.85 -> 21.60 (32x64, 8 x 32, two rounds
+// of the wide layer), at 1024 rows 25.61 -> 34.04 (64x64, 16 x 16, four), at 2048 rows 44.19 -> 48.29 (128x128, 16 x 16, two), at 4096 rows
+// 64.20 -> 68.65 (128x128, 32 x 8, four); 2048 rows x [2048, 1024] 22.68 -> 25.69 (64x128, 32 x 8); 1024 rows x [2048, 1024, 2048, 1024]
+// 33.97 -> 37.98 (64x64, 16 x 16) - slower in every pair; the funnel 1024 rows x [512, 256, 128] (32x64, 32 x 4) ran 15.96 -> 16.24 in one
+// session, slower in every pair, and 17.30 -> 16.56 in the next, faster in every pair (the launch took about the same time, the separate
+// calls did not). The separate calls run every layer on the tile that suits it; the launch pins all of them to one, and every step pays a seam
+// of about 2.4 us (the A panels of a step are requested behind its predecessor's epilogue) where a saved launch is worth about the
+// tile's fixed cost (3.6 .. 6.1 us). So: WITHOUT A TILE ALL CALLS WERE DISPATCHED ON THE CHAIN STAYS CALL BY CALL. On such a tile the
+// separate calls run on that tile too, and the launch gained in both sessions: 1024 rows x [4096, 1024] on 64x64 at the rule's W = 16
+// 34.85 -> 34.08, 35.96 -> 35.18 and 36.23 -> 35.84 in three sessions (every pair); not gated. (W = 8 on the same tile: 35.92 -> 64.17 - fewer, longer
+// walks cost more than they save; the rule takes the largest W that fits.) A gated answer still names the rule's tile and groups, with
+// gated = true and why = the gate: the caller does not launch. A forced W is not gated.
+struct ChainWidthRoundsPlan { int tile; int groups; const char *why; bool gated; };
+inline bool chain_width_rounds_mode_forced(int mode) { return mode > 1000; }
+ChainWidthRoundsPlan plan_chain_width_rounds(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int b_kind, int mode, bool strict);
 // 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none
 int f32_chain_tile(const GemmDesc &d);
 // tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip; BLW_TILES, brgemm_bf16_lw_launch.h)

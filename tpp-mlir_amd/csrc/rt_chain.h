@@ -236,7 +236,12 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   // `divisible`) -, the same m and a batch, and plan_chain_widths names a tile. widw = the launch is the mixed-width one. With the
   // switch off widths_w() is false without a look at the calls and the NOCHAIN is taken exactly as before.
   const int chain_widths = f32 ? 0 : g_chain_widths.load(std::memory_order_relaxed);
-  int widw_state = chain_widths ? -1 : 0, widw_tile = -1, widw_kind = -1; // -1 not asked yet, 0 no, 1 yes
+  // COLUMN ROUNDS (xsmm_hip_set_chain_width_rounds, opt-in; gemm_plan.cpp plan_chain_width_rounds): the same question about the same calls,
+  // answered inside widths_w(): a forced W (1000 + W) in front of plan_chain_widths, the rule (1) where plan_chain_widths refuses or gates
+  // or its switch is off. widw_groups > 0 = the launch is the column-round one on that many workgroup columns. With both switches off
+  // widths_w() is false without a look at the calls.
+  const int width_rounds = f32 ? 0 : g_chain_width_rounds.load(std::memory_order_relaxed);
+  int widw_state = chain_widths || width_rounds ? -1 : 0, widw_tile = -1, widw_kind = -1, widw_groups = 0; // -1 not asked yet, 0 no, 1 yes
   bool widw = false;
   auto widths_w = [&]() {
     if (widw_state >= 0) return widw_state == 1;
@@ -250,11 +255,32 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (widw_kind >= 0) {
       int64_t ns[CH_MAXL], ks[CH_MAXL], brs[CH_MAXL];
       for (int i = 0; i < n; ++i) ns[i] = d[i]->n, ks[i] = d[i]->k, brs[i] = br[i];
-      const ChainWidthsPlan wp = plan_chain_widths(m, n, ns, ks, brs, stream_cus(s), chain_rounds_planned_tile(n, d), widw_kind, chain_widths,
-                                                   cfg().strict.load(std::memory_order_relaxed));
-      w = wp.why;
-      widw_tile = wp.tile;
-      if (wp.tile >= 0) widw_state = 1;
+      const int planned = chain_rounds_planned_tile(n, d);
+      const bool strict_ = cfg().strict.load(std::memory_order_relaxed);
+      auto ask_width_rounds = [&]() {
+        // (mode 1 without a tile all calls were dispatched on: plan_chain_width_rounds' gate, or a refusal in front of it - never a launch.
+        // Answered here, without asking for the stream's compute units: on a launch-bound chain the runtime calls behind stream_cus
+        // showed - 1024 rows x [1024, 512, 256, 128], gated, call by call with the switch off / on 16.38 / 17.06 us per step in every pair;
+        // with this answer 18.65 / 18.65 in a later session, profiles/chain_width_rounds_ab.txt)
+        if (width_rounds == 1 && planned < 0) {
+          w = "column rounds by rule only on a tile all calls were dispatched on (plan_chain_width_rounds' gate)";
+          return;
+        }
+        const ChainWidthRoundsPlan rp = plan_chain_width_rounds(m, n, ns, ks, brs, stream_cus(s), planned, widw_kind, width_rounds, strict_);
+        w = rp.why;
+        if (rp.tile < 0 || rp.gated) return; // (gated: the rule's answer is on record in why, nothing is launched)
+        widw_tile = rp.tile;
+        widw_groups = rp.groups;
+        widw_state = 1;
+      };
+      if (chain_width_rounds_mode_forced(width_rounds)) ask_width_rounds(); // (a forced W that does not fit: everything below as with the switch off)
+      if (!widw_state && chain_widths) {
+        const ChainWidthsPlan wp = plan_chain_widths(m, n, ns, ks, brs, stream_cus(s), planned, widw_kind, chain_widths, strict_);
+        w = wp.why;
+        widw_tile = wp.tile;
+        if (wp.tile >= 0) widw_state = 1;
+      }
+      if (!widw_state && width_rounds == 1) ask_width_rounds();
     }
     if (!widw_state && cfg().trace) fprintf(stderr, "[tpp-xsmm-hip] fused_brgemm_chain: no mixed-width launch (%s)\n", w);
     return widw_state == 1;
@@ -465,7 +491,14 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   c.target = ++blk.epoch * (unsigned)blk.tiles_n;
   if (widw) c.target = blk.epoch; // (the kernel multiplies by the producing layer's column tiles: chain_widths_target)
   if (f32) HIP_OK(launch_f32_chain(tile, c, s));
-  else if (widw) {
+  else if (widw && widw_groups > 0) {
+    c.groups = widw_groups;
+    HIP_OK(launch_bf16_chain_wrounds(tile, b_kind, c, s));
+    g_chain_width_rounds_stats[1].store(m / bm, std::memory_order_relaxed);
+    g_chain_width_rounds_stats[2].store(widw_groups, std::memory_order_relaxed);
+    g_chain_width_rounds_stats[3].store(blw_variant(tile, b_kind), std::memory_order_relaxed);
+    g_chain_width_rounds_stats[0].fetch_add(1, std::memory_order_relaxed);
+  } else if (widw) {
     HIP_OK(launch_bf16_chain_widths(tile, b_kind, c, s));
     g_chain_widths_stats[1].store(m / bm, std::memory_order_relaxed);
     g_chain_widths_stats[2].store(c.n / bn, std::memory_order_relaxed);

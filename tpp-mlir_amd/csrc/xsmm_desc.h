@@ -247,6 +247,17 @@ inline std::atomic<int> g_chain_widths{[] {
   return chain_widths_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_chain_widths_stats[4]; // mixed-width chain launches; row blocks, the widest layer's column tiles, GemmVariant of the tile (with its B image) of the latest
+// COLUMN ROUNDS OF MIXED-WIDTH CHAINS (xsmm_hip_set_chain_width_rounds / TPP_HIP_CHAIN_WIDTH_ROUNDS; gemm_plan.cpp plan_chain_width_rounds,
+// rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_wrounds.h): 0 = off, 1 = a divisible bf16 chain whose layers differ in n runs as one launch
+// on m / BM x W resident workgroups, W by rule below the widest layer's column tiles - a workgroup walks several column tiles of a wide
+// layer -, 1000 + W = that W (a test / measurement switch). A switch of its own: xsmm_hip_set_chain_widths keeps its meaning.
+inline bool chain_width_rounds_mode_ok(int v) { return v == 0 || v == 1 || (v > 1000 && v <= 1000 + 0x10000); }
+inline std::atomic<int> g_chain_width_rounds{[] {
+  const char *e = getenv("TPP_HIP_CHAIN_WIDTH_ROUNDS");
+  const int v = e ? atoi(e) : 0;
+  return chain_width_rounds_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_chain_width_rounds_stats[4]; // column-round launches; row blocks, resident workgroup columns W, GemmVariant of the tile (with its B image) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

@@ -131,6 +131,8 @@ _SIGNATURES = {
     "xsmm_hip_chain_ragged_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_widths": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_widths_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_chain_width_rounds": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_chain_width_rounds_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_rounds": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_rounds_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
@@ -473,6 +475,20 @@ class XsmmRuntime:
         20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_chain_widths_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_chain_width_rounds(self, mode):
+        """bf16 layer chains whose layers differ in n on m / BM x W resident workgroups, W below the widest layer's column tiles: a
+        workgroup walks several column tiles of a wide layer and one (or none) of a narrow one. 0 off (default), 1 on - tile and W by
+        rule, what measured slower gated back to call by call -, 1000 + W force W workgroup columns (never gated); returns the previous
+        value, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_chain_width_rounds(mode)
+
+    def chain_width_rounds_stats(self):
+        """(column-round launches; row blocks m / BM, workgroup columns W, variant number of the tile with its B image - 20 + t VNNI-2,
+        24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_chain_width_rounds_stats(out)
         return tuple(int(v) for v in out)
 
     def set_chain_rounds(self, mode):
