@@ -603,6 +603,31 @@ TPP_XSMM_EXPORT void xsmm_hip_chain_widths_stats(int64_t out[4]);
  * and of the single-call edge switches do not move on these launches, nor this one on theirs. */
 TPP_XSMM_EXPORT int xsmm_hip_set_chain_width_rounds(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_chain_width_rounds_stats(int64_t out[4]);
+/* Ragged mixed-width layer chains, opt-in (environment: TPP_HIP_CHAIN_WIDTHS_RAGGED; default 0 = off): a switch of its own - no other switch
+ * changes meaning, and none of their counters moves on these launches. Mode 1: a bf16 chain of 2 .. 8 calls with the same m and at least
+ * two different n that NO tile divides entirely - a ragged m, a ragged n_l or a k_l that is no multiple of 64: 784-512-256-128, a funnel on
+ * 1000 rows - runs as ONE launch on ceil(m / BM) x max_l ceil(n_l / BN) workgroups (launch mode 11 of the loader-wave tile) when every call
+ * is beta 0, stores no VNNI C, was not dispatched to a forced kernel (the generic kernel included) and has the same B image (VNNI-2, flat
+ * or VNNI-4) with the leading dimensions, strides and alignment the edge tiles ask of it; every k >= 64 and k % 8 == 0, every batch count
+ * >= 1, every n_l % 8 == 0; m >= BM and every n_l >= BN; ceil(m / BM) * max_l ceil(n_l / BN) <= the stream's compute units; not in strict
+ * mode - and everything else the chain launch asks holds as before (each call reads its predecessor's output with lda = ldc, batch elements
+ * inside the predecessor's rows, device pointers, no overlaps, asynchronous mode, no stream capture). Refused, so call by call: f32, an n
+ * or k that is no multiple of 8, k < 64, m or an n_l below every tile, more tiles than compute units, a forced kernel, synchronous mode,
+ * calls that differ in m.
+ * Bits: those of the same calls made one by one on the launch's tile under xsmm_hip_set_edge_tiles / _edge_k_bf16 / _edge_k8_bf16(20 + t):
+ * the same k-values in the same order, one rounding per layer; no load outside rows [0, m) of A or k-rows [0, k) / columns [0, n_l) of B,
+ * no byte outside any layer's m x n_l window written.
+ * The partition (the descriptors alone decide): a chain SOME tile divides entirely (BM | m, BN | every n_l, every k_l % 64 == 0) is
+ * xsmm_hip_set_chain_widths' / _width_rounds', or call by call with those off - never this switch's; equal widths are the other three chain
+ * switches' as before. The tile: the one xsmm_hip_set_edge_tiles(20 .. 23) names if it fits and has an instance (64x128 with the VNNI-2
+ * image has none: it would need scratch), else the smallest tile that fits and has one.
+ * The gate (structural, xsmm_hip_set_chain_widths'): a chain in which some layer alone fits a smaller tile than the launch's stays call by
+ * call unless an edge-tile mode forces the tile (profiles/chain_widths_ragged_ab.txt holds the measurement). A starved launch degrades as
+ * every chain launch. Returns the previous value, -1 (nothing changed) for any other value.
+ * _stats: out[0] ragged mixed-width launches since process start; of the most recent one: [1] row blocks ceil(m / BM), [2] column tiles of
+ * the widest layer max_l ceil(n_l / BN), [3] the variant number of its tile with its B image (20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4). */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_widths_ragged(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_widths_ragged_stats(int64_t out[4]);
 /* Transposes folded into the gemm they feed (tile queue on, asynchronous mode, device operands, f32). A contraction with a
  * transposed B operand reaches the runtime as xsmm.unary transpose into a small temporary + xsmm.gemm reading it, per tile and with
  * ONE temporary per caller (test/Conversion/LinalgToXsmm/linalg-to-gemm.mlir:46-62, the lowering of

@@ -47,6 +47,11 @@
 // chain whose layers differ in n on m / BM x max_l(n(l) / BN) workgroups. Workgroup (tm, tn) sits out the layers without a column tile tn.
 //   Progress: an active layer l > 0 waits only for cnt[l-1][tm], whose n(l-1) / BN producers are resident and wait in turn only for
 //   counters of layer l - 2: by induction over the layers no wait is cyclic. A workgroup's counters need not be its own layers'.
+//
+// RAGGED MIXED WIDTHS (GRP = 11, xsmm_hip_set_chain_widths_ragged; schedule in brgemm_bf16_lw_chain_wragged.h, instances in
+// brgemm_bf16_lw_chain_wragged.hip): GRP = 9's sat-out layers on GRP = 8's layers - any m >= BM, per layer any n(l) >= BN and k(l) >= 64 in
+// multiples of 8 - on ceil(m / BM) x max_l ceil(n(l) / BN) workgroups. The column shift is the layer's, cnt[l][tm] receives ceil(n(l) / BN)
+// arrivals, the wait is on one or two row blocks, the ring is carried through the active layers; no run-ahead. Progress: as GRP = 9.
 #include "gemm_common.h"
 #include "xsmm_desc.h"
 #include "chain_args.h"
@@ -113,7 +118,12 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
   // GRP = 8 (a RAGGED-WIDTH chain, brgemm_bf16_lw_chain_ragged.h): GRP = 5's rows and seam wait, GRP = 3's columns, and per LAYER GRP = 4's
   // chunks - bkedge_chunks(k) per batch element, the last one shifted back; a whole k (k % 64 == 0) is the same walk with an advance of 64
   // into the last chunk. The ring is carried from layer to layer (s0); the B loader does not run ahead across a seam in this mode.
-  constexpr bool CRAG = blw_chain_ragged(GRP);
+  // GRP = 11 (a RAGGED MIXED-WIDTH chain, brgemm_bf16_lw_chain_wragged.h): GRP = 8 in all of that - rows, seam wait over one or two row blocks,
+  // the chunk walk, the carried ring, no run-ahead - with GRP = 9's layers: layer lc has p.L[lc].pad columns, this wave sits out a layer
+  // without a column tile tn, and the column shift is the LAYER's (n0 is set at every active layer; it arrives as tn * BN). The target is
+  // epoch * ceil(n(lc - 1) / BN). Statements of its own below (WRAG), beside GRP = 9's.
+  constexpr bool WRAG = blw_chain_wragged(GRP);
+  constexpr bool CRAG = blw_chain_ragged(GRP) || WRAG;
   constexpr bool KEDGE = blw_ragged_k(GRP) || CRAG;
   // GRP = 9 (a MIXED-WIDTH chain, brgemm_bf16_lw_chain_widths.h): GRP = 0's chain in which layer lc has p.L[lc].pad columns: this wave skips
   // a layer without a column tile at n0 - no barrier, no ring slot, s0 stays -, waits for epoch * (n(lc - 1) / BN) arrivals in front of every
@@ -260,6 +270,10 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       if (!chain_widths_active(tn, p.L[lc].pad, BN)) continue; // (the group sits the layer out: the increment above goes to the next layer)
       n0 = tn * BN;
     }
+    if constexpr (WRAG) {
+      if (!chain_wragged_active(tn, p.L[lc].pad, BN)) continue; // (uniform over the workgroup; s0 stays)
+      n0 = chain_ragged_col0(tn, p.L[lc].pad, BN);              // (this layer's shift: BLW_LOAD_STATE below reads it)
+    }
     const int T = (ITEMS ? it_br : p.L[lc].br) * (KEDGE ? bkedge_chunks(p.L[lc].k) : p.L[lc].k / BLW_BK) / SUP; // (a multiple of SUP: the launcher picks SUP = 1 otherwise)
     int pre = NSLOT - 2; // chunks of this layer already requested by the run-ahead of the previous layer's tail
     if constexpr (ROUNDS || WRND) {
@@ -285,6 +299,7 @@ __device__ __forceinline__ void blw_loader(chain_kernarg_t *pp, unsigned char *s
       unsigned target = p.target;
       if constexpr (CWID) target = chain_widths_target(p.target, p.L[lc > 0 ? lc - 1 : 0].pad, BN);
       if constexpr (WRND) target = chain_widths_target(p.target, p.L[lc > 0 ? lc - 1 : 0].pad, BN); // (GRP = 10: the same counters)
+      if constexpr (WRAG) target = chain_wragged_target(p.target, p.L[lc > 0 ? lc - 1 : 0].pad, BN); // (GRP = 11: ceil-divided column tiles, on every block bw below)
       const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
       for (int bw = b_first; bw <= b_last; ++bw) {
         g_u32_lw *c = (g_u32_lw *)(p.cnt + ((size_t)(lc - 1) * p.tiles_m + bw) * CHAIN_CNT_STRIDE);
@@ -404,7 +419,12 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   // GRP = 5's rows and seam wait, GRP = 3's columns (the last column tile shifted back to n - BN, stores predicated on own_col, bias read at
   // the shifted n0), and per layer GRP = 6's K loop with the LAYER's skip in half steps: 0 for a whole k (every step WHOLE: what the plain
   // chain multiplies), even for k % 16 == 0, odd for k % 16 == 8 - one instance serves the three k classes. A layer starts at any ring slot.
-  constexpr bool CRAG = blw_chain_ragged(GRP);
+  // GRP = 11 (a RAGGED MIXED-WIDTH chain, xsmm_hip_set_chain_widths_ragged; brgemm_bf16_lw_chain_wragged.h): GRP = 8 on ceil(m / BM) x
+  // max_l ceil(n(l) / BN) workgroups, n(l) = p.L[l].pad, with GRP = 9's sat-out layers. Per LAYER: whether the workgroup is active, its first
+  // column n0 and its first own column (the same tile is the shifted last one of one layer and an interior one of the next) - so the bias
+  // offset, the output base and the store predicate; s0 moves on active layers only, by the ragged chunk count. p.target is the epoch.
+  constexpr bool WRAG = blw_chain_wragged(GRP);
+  constexpr bool CRAG = blw_chain_ragged(GRP) || WRAG;
   constexpr bool KEDGE = blw_ragged_k(GRP) || CRAG, ROUNDS = GRP == BLW_CHAIN_ROUNDS;
   // GRP = 9 (a MIXED-WIDTH chain, xsmm_hip_set_chain_widths; brgemm_bf16_lw_chain_widths.h): GRP = 0's chain on m / BM x max_l(n(l) / BN)
   // workgroups, n(l) = p.L[l].pad. Workgroup (tm, tn) computes tile (tm, tn) of the layers with a column tile tn and skips the others - all
@@ -539,7 +559,9 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
   int m0 = GRP == BLW_CHAIN_EDGE || CRAG ? chain_edge_row0(tm, p.tiles_m, p.m, BM) : (EDGE_ROWS && (tm + 1) * BM > p.m) ? p.m - BM : tm * BM;
   int n0 = (EDGE_COLS && (tn + 1) * BN > p.n) ? p.n - BN : tn * BN; // (GRP = 10: the column group's first tile; the step loops take n0 from the step)
   [[maybe_unused]] const int skip_cols = tn * BN - n0;
-  [[maybe_unused]] const int own_row = tm * BM - m0, own_col = tn * BN - n0;
+  [[maybe_unused]] const int own_row = tm * BM - m0;
+  [[maybe_unused]] int own_col = tn * BN - n0; // (GRP = 11: the layer's, set with n0 at every active layer)
+  if constexpr (WRAG) n0 = tn * BN; // (p.n is the widest layer's: no layer's shift. The loaders derive tn from it)
   const int L = MULTI ? p.nlayers : 1;
 
   if (wave >= NMW) {
@@ -743,6 +765,11 @@ __global__ __launch_bounds__(64 * (WM * WN * WK + NLA + NLB)) void brgemm_bf16_l
     if constexpr (WRND) {
       if (!chain_widths_active(tn, p.L[l].pad, BN)) continue; // (the group sits the layer out; blw_loader walks the same steps)
       n0 = tn * BN;
+    }
+    if constexpr (WRAG) {
+      if (!chain_wragged_active(tn, p.L[l].pad, BN)) continue; // (the loaders skip the same layers; s0 stays)
+      n0 = chain_ragged_col0(tn, p.L[l].pad, BN);               // this layer's shift: bias offset, output base ..
+      own_col = chain_ragged_own_col(tn, p.L[l].pad, BN);       // .. and the 16-byte pieces the tile stores
     }
     const auto &Y = p.L[l];
     const int T = (ITEMS ? it_br : Y.br) * (KEDGE ? bkedge_chunks(Y.k) : Y.k / BLW_BK);

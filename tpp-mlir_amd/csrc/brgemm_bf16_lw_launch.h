@@ -7,6 +7,7 @@
 #include "brgemm_bf16_lw_chain_ragged.h"
 #include "brgemm_bf16_lw_chain_widths.h"
 #include "brgemm_bf16_lw_chain_wrounds.h"
+#include "brgemm_bf16_lw_chain_wragged.h"
 
 namespace tpp {
 
@@ -28,6 +29,8 @@ constexpr int BLW_CHAIN_RAGGED = 8; // a chain with a ragged n and / or a k that
 constexpr int BLW_CHAIN_WIDTHS = 9; // a chain whose layers differ in n: a workgroup sits out the layers that have no column tile for it
 // A mixed-width chain in COLUMN ROUNDS (xsmm_hip_set_chain_width_rounds): beside the table too (brgemm_bf16_lw_chain_wrounds.hip, predicates at the end)
 constexpr int BLW_CHAIN_WROUNDS = 10; // BLW_CHAIN_WIDTHS on fewer resident workgroup columns than the widest layer has column tiles
+// A RAGGED mixed-width chain (xsmm_hip_set_chain_widths_ragged): beside the table too (brgemm_bf16_lw_chain_wragged.hip, predicates at the end)
+constexpr int BLW_CHAIN_WRAGGED = 11; // BLW_CHAIN_WIDTHS with BLW_CHAIN_RAGGED's layers: any m >= BM, per layer any n(l) >= BN and k >= 64 in multiples of 8
 
 // what follows from a mode
 constexpr bool blw_items(int g) { return g == BLW_ITEMS || g == BLW_QUADS; }      // operands and batch count come from an item
@@ -35,26 +38,28 @@ constexpr bool blw_ragged_k(int g) { return g == BLW_KEDGE || g == BLW_KEDGE8; }
 constexpr bool blw_chain_ragged(int g) { return g == BLW_CHAIN_RAGGED; }         // every layer its own k class, tested in half steps
 constexpr bool blw_chain_widths(int g) { return g == BLW_CHAIN_WIDTHS; }         // per-layer n in the argument block, skipped layers
 constexpr bool blw_chain_wrounds(int g) { return g == BLW_CHAIN_WROUNDS; }       // ... and a workgroup walks several column tiles of a layer
+constexpr bool blw_chain_wragged(int g) { return g == BLW_CHAIN_WRAGGED; }       // per-layer n AND per-layer column shifts, k classes and a carried ring
 constexpr bool blw_half_steps(int g) { return g == BLW_KEDGE8; }                  // ... and its overlap ends in the middle of a k-step
 // the last row block is shifted back to end at row m and stores its own rows only
-constexpr bool blw_edge_rows(int g) { return g == BLW_EDGE || blw_ragged_k(g) || g == BLW_CHAIN_EDGE || blw_chain_ragged(g); }
+constexpr bool blw_edge_rows(int g) { return g == BLW_EDGE || blw_ragged_k(g) || g == BLW_CHAIN_EDGE || blw_chain_ragged(g) || blw_chain_wragged(g); }
 // the last column tile is shifted back to end at column n (a ragged-m chain's columns are whole tiles, a ragged-width chain's are not)
-constexpr bool blw_edge_cols(int g) { return g == BLW_ITEMS || g == BLW_EDGE || blw_ragged_k(g) || blw_chain_ragged(g); }
+constexpr bool blw_edge_cols(int g) { return g == BLW_ITEMS || g == BLW_EDGE || blw_ragged_k(g) || blw_chain_ragged(g) || blw_chain_wragged(g); }
 constexpr bool blw_chain(int g) { return g == BLW_CHAIN_EDGE || g == BLW_CHAIN_ROUNDS; } // a chain by itself (BLW_LAYER: either)
-constexpr bool blw_one_chunk(int g) { return blw_ragged_k(g) || blw_chain(g) || blw_chain_ragged(g); }   // one chunk per barrier only (SUP = 1)
+constexpr bool blw_one_chunk(int g) { return blw_ragged_k(g) || blw_chain(g) || blw_chain_ragged(g) || blw_chain_wragged(g); }   // one chunk per barrier only (SUP = 1)
 // the combinations of mode, MULTI and SUP the kernel and the loader are written for
 constexpr bool blw_mode_ok(int g, bool multi, int sup) {
   return g >= 0 && g < BLW_MODES && (multi ? g == BLW_LAYER || blw_chain(g) : !blw_chain(g)) && (!blw_one_chunk(g) || sup == 1);
 }
 template <int GRP, bool MULTI, int SUP> struct BlwModeCheck {
-  static_assert((GRP >= 0 && GRP < BLW_MODES) || blw_chain_ragged(GRP) || blw_chain_widths(GRP) || blw_chain_wrounds(GRP), "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds, 8: a ragged-width chain, 9: a mixed-width chain, 10: a mixed-width chain in column rounds");
-  static_assert(!MULTI || GRP == BLW_LAYER || blw_chain(GRP) || blw_chain_ragged(GRP) || blw_chain_widths(GRP) || blw_chain_wrounds(GRP), "a grouped launch is a set of single layers");
+  static_assert((GRP >= 0 && GRP < BLW_MODES) || blw_chain_ragged(GRP) || blw_chain_widths(GRP) || blw_chain_wrounds(GRP) || blw_chain_wragged(GRP), "0: a layer / chain, 1: items, 2: quads, 3: a layer on edge tiles, 4: edge tiles + a ragged k, 5: a chain on edge row tiles, 6: 4 in half steps, 7: a chain in several rounds, 8: a ragged-width chain, 9: a mixed-width chain, 10: a mixed-width chain in column rounds, 11: a ragged mixed-width chain");
+  static_assert(!MULTI || GRP == BLW_LAYER || blw_chain(GRP) || blw_chain_ragged(GRP) || blw_chain_widths(GRP) || blw_chain_wrounds(GRP) || blw_chain_wragged(GRP), "a grouped launch is a set of single layers");
   static_assert(!blw_ragged_k(GRP) || (SUP == 1 && !MULTI), "ragged k: one layer, one chunk per barrier");
   static_assert(!blw_chain(GRP) || (SUP == 1 && MULTI), "a ragged / multi-round chain: a chain, one chunk per barrier");
   static_assert(!blw_chain_ragged(GRP) || (SUP == 1 && MULTI), "a ragged-width chain: a chain, one chunk per barrier");
   static_assert(!blw_chain_widths(GRP) || (MULTI && (SUP == 1 || SUP == 2)), "a mixed-width chain: a chain, one or two chunks per barrier");
   static_assert(!blw_chain_wrounds(GRP) || (SUP == 1 && MULTI), "a mixed-width chain in column rounds: a chain, one chunk per barrier");
-  static constexpr bool ok = blw_chain_ragged(GRP) || blw_chain_wrounds(GRP) ? MULTI && SUP == 1 : blw_chain_widths(GRP) ? MULTI && (SUP == 1 || SUP == 2) : blw_mode_ok(GRP, MULTI, SUP);
+  static_assert(!blw_chain_wragged(GRP) || (SUP == 1 && MULTI), "a ragged mixed-width chain: a chain, one chunk per barrier");
+  static constexpr bool ok = blw_chain_ragged(GRP) || blw_chain_wrounds(GRP) || blw_chain_wragged(GRP) ? MULTI && SUP == 1 : blw_chain_widths(GRP) ? MULTI && (SUP == 1 || SUP == 2) : blw_mode_ok(GRP, MULTI, SUP);
 };
 
 // THE TILES. 0 = 32x64 + K2, 1 = 64x64, 2 = 64x128, 3 = 128x128, 4 = 32x32 + K2. Loader waves per tile (NLA + NLB), same-box A/B
@@ -173,6 +178,29 @@ constexpr bool blw_chain_wrounds_launch_ok(int tile, int b_kind, const BlwWidths
   for (int l = 0; l < a.nlayers; ++l)
     if (a.n[l] / BLW_TILES[tile].bn() > maxT) maxT = a.n[l] / BLW_TILES[tile].bn();
   return groups >= 1 && groups < maxT;
+}
+
+// THE RAGGED MIXED-WIDTH CHAIN (BLW_CHAIN_WRAGGED, brgemm_bf16_lw_chain_wragged.hip; schedule in brgemm_bf16_lw_chain_wragged.h): MULTI, one chunk
+// per barrier. Is the instance of (tile, b_kind) compiled? Tiles 0 .. 3 with the three B images, less ONE: the 64x128 tile with the VNNI-2
+// image, which needs 72 bytes of scratch per lane in this mode (17 spilled VGPRs) as it needs 76 in BLW_CHAIN_RAGGED (the body for a layer that
+// starts at an odd ring slot tips its 256 VGPRs over), so it does not exist - eleven instances, none with scratch. The planner (gemm_plan.cpp plan_chain_widths_ragged)
+// passes that tile over.
+constexpr bool blw_chain_wragged_instance_exists(int tile, int b_kind) { return tile >= 0 && tile <= 3 && blw_b_kind_ok(b_kind) && !(tile == 2 && b_kind == 0); }
+// ... and what its launcher refuses, over a shape with per-layer widths: 2 .. 8 layers, every one a batch of at least one element with
+// k >= 64 and k % 8 == 0 and n(l) >= BN columns, n(l) % 8 == 0; m >= BM; at least two layers differ in n (an equal-width chain is
+// BLW_CHAIN_RAGGED's, BLW_CHAIN_EDGE's or BLW_LAYER's); and something ragged on this tile - BM does not divide m, BN does not divide some
+// n(l), or some k(l) % 64 != 0 (a chain the tile divides entirely is BLW_CHAIN_WIDTHS')
+constexpr bool blw_chain_wragged_launch_ok(int tile, int b_kind, const BlwWidthsShape &a) {
+  if (!blw_chain_wragged_instance_exists(tile, b_kind) || a.nlayers < 2 || a.nlayers > BLW_MAXL) return false;
+  const int bm = BLW_TILES[tile].bm(), bn = BLW_TILES[tile].bn();
+  bool differ = false, ragged = a.m % bm != 0;
+  for (int l = 0; l < a.nlayers; ++l) {
+    if (a.br[l] < 1 || !chain_ragged_k_ok(a.k[l])) return false;
+    if (a.n[l] < bn || a.n[l] % 8 != 0) return false;
+    if (a.n[l] != a.n[0]) differ = true;
+    if (a.n[l] % bn != 0 || a.k[l] % BKEDGE_BK != 0) ragged = true;
+  }
+  return differ && ragged && a.m >= bm;
 }
 
 } // namespace tpp

@@ -63,6 +63,11 @@ hipError_t launch_bf16_chain_widths(int tile, int b_kind, const ChainArgs &a, hi
 // launch_bf16_chain_widths + a.groups = W resident workgroup columns, 1 <= W < a.n / BN (the grid: m / BM x W workgroups, at most the
 // stream's compute units - the caller's guarantee). blw_chain_wrounds_launch_ok is what it refuses
 hipError_t launch_bf16_chain_wrounds(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
+// a RAGGED mixed-width chain (brgemm_bf16_lw_chain_wragged.hip, BLW_CHAIN_WRAGGED, xsmm_hip_set_chain_widths_ragged): launch_bf16_chain_widths'
+// arguments with any m >= BM, n(l) >= BN in multiples of 8 and k(l) >= 64 in multiples of 8; the grid is ceil(m / BM) x ceil(a.n / BN)
+// workgroups, at most the stream's compute units - the caller's guarantee -, cnt[l][*] reaches epoch * ceil(a.L[l].pad / BN).
+// blw_chain_wragged_launch_ok is what it refuses
+hipError_t launch_bf16_chain_wragged(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2; b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);

@@ -698,6 +698,82 @@ ChainWidthRoundsPlan plan_chain_width_rounds(int64_t m, int nlayers, const int64
   return ChainWidthRoundsPlan{tile, w, "", false};
 }
 
+int chain_widths_ragged_b_kind(const GemmDesc &d, int mode, const char **why) {
+  const char *w = nullptr;
+  int kind = -1;
+  if (mode != 1) w = "ragged mixed-width chains are off (xsmm_hip_set_chain_widths_ragged)";
+  else if (d.dtype != DT_BF16) w = "a ragged mixed-width chain is bf16: an f32 call";
+  else if (d.vnni_c || !d.beta0) w = "a call of a ragged mixed-width chain stores a VNNI C or is not beta 0";
+  else if (d.generic_forced || d.variant_forced) w = "a call of a ragged mixed-width chain was dispatched to a forced kernel";
+  else if (!chain_ragged_k_ok(d.k)) w = "a call of a ragged mixed-width chain has k below 64 or not a multiple of 8";
+  else {
+    GemmDesc e = d; // bf16_edge_b_kind's terms for leading dimensions, strides and lane offsets; its k term is the one above
+    e.k = BK;
+    if ((kind = bf16_edge_b_kind(e)) < 0) w = "a call of a ragged mixed-width chain has an operand off the grid of the LDS-DMA tiles";
+  }
+  if (why) *why = w;
+  return w ? -1 : kind;
+}
+
+ChainWidthsRaggedPlan plan_chain_widths_ragged(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, int b_kind, int mode, bool strict) {
+  auto no = [](const char *why) { return ChainWidthsRaggedPlan{-1, why, false}; };
+  if (mode != 1) return no("ragged mixed-width chains are off (xsmm_hip_set_chain_widths_ragged)");
+  if (strict) return no("strict mode: the tile of a ragged mixed-width chain is not a function of the descriptor alone");
+  if (nlayers < 2 || nlayers > 8) return no("fewer than 2 or more than 8 calls");
+  if (!blw_b_kind_ok(b_kind)) return no("the calls of a ragged mixed-width chain do not share one B image of the loader-wave tiles");
+  bool differ = false;
+  int64_t widest = 0;
+  for (int l = 0; l < nlayers; ++l) {
+    if (!chain_ragged_k_ok(k[l]) || br[l] < 1) return no("a layer of a ragged mixed-width chain has k below 64 or not a multiple of 8, or an empty batch");
+    if (n[l] % 8 != 0) return no("a layer of a ragged mixed-width chain has an n that is not a multiple of 8");
+    if (n[l] != n[0]) differ = true;
+    if (n[l] > widest) widest = n[l];
+  }
+  if (!differ) return no("every call has the same n: the equal-width chain switches decide");
+  // THE PARTITION (the descriptors alone, no switch): a chain SOME tile divides entirely - BM | m, BN | every n(l), every k(l) % 64 == 0 -
+  // is the mixed-width chain's (xsmm_hip_set_chain_widths / _width_rounds), or call by call with those off; never this rule's
+  auto holds = [&](int t) { // m and every n(l) hold at least one tile
+    if (t < 0 || t > 3 || m < BLW_BM[t]) return false;
+    for (int l = 0; l < nlayers; ++l)
+      if (n[l] < BLW_BN[t]) return false;
+    return true;
+  };
+  auto entire = [&](int t) {
+    if (!holds(t) || m % BLW_BM[t] != 0) return false;
+    for (int l = 0; l < nlayers; ++l)
+      if (n[l] % BLW_BN[t] != 0 || k[l] % BK != 0) return false;
+    return true;
+  };
+  for (int t = 0; t < 4; ++t)
+    if (entire(t)) return no("a tile divides m, every n and every k entirely: the mixed-width chain's (xsmm_hip_set_chain_widths), not a ragged one");
+  auto ceil_div = [](int64_t a, int64_t b) { return (a + b - 1) / b; };
+  auto tiles = [&](int t) { return ceil_div(m, BLW_BM[t]) * ceil_div(widest, BLW_BN[t]); };
+  // (64x128 with the VNNI-2 image has no instance - it would need scratch, blw_chain_wragged_instance_exists - and is passed over)
+  auto fits = [&](int t) { return holds(t) && blw_chain_wragged_instance_exists(t, b_kind) && tiles(t) <= cus; };
+  const bool forced = forced_tile >= 0 && forced_tile <= 3; // (tests and measurements: under a forcing edge-tile mode nothing is gated, whichever tile fits)
+  int tile = fits(forced_tile) ? forced_tile : -1;
+  for (int t = 0; t < 4 && tile < 0; ++t)
+    if (fits(t)) tile = t;
+  if (tile < 0) {
+    if (!holds(0)) return no("a ragged mixed-width chain's m or some n is below every tile");
+    return no("more tiles than compute units (a ragged mixed-width chain runs in one round)");
+  }
+  // THE STRUCTURAL GATE (plan_chain_widths', measured there - profiles/chain_widths_ab.txt - and again here, profiles/chain_widths_ragged_ab.txt):
+  // the widest layer decides the launch's tile; a layer that ALONE fits a smaller one covers the chip with more, smaller tiles as a separate
+  // call and keeps a fraction of the grid busy on the large tile in the launch. Such a chain stays call by call. Not under a forcing
+  // edge-tile mode.
+  if (!forced) {
+    auto alone_fits = [&](int t, int l) {
+      return blw_chain_wragged_instance_exists(t, b_kind) && m >= BLW_BM[t] && n[l] >= BLW_BN[t] && ceil_div(m, BLW_BM[t]) * ceil_div(n[l], BLW_BN[t]) <= cus;
+    };
+    for (int l = 0; l < nlayers; ++l)
+      for (int s = 0; s < tile; ++s)
+        if (alone_fits(s, l))
+          return ChainWidthsRaggedPlan{tile, "gate: a layer fits a smaller tile alone than the widest layer leaves the launch - slower as one launch (profiles/chain_widths_ab.txt, profiles/chain_widths_ragged_ab.txt)", true};
+  }
+  return ChainWidthsRaggedPlan{tile, "", false};
+}
+
 int chain_rounds_b_kind(const GemmDesc &d) {
   if (d.dtype != DT_BF16 || d.vnni_c || !d.beta0 || d.generic_forced || d.variant == V_GENERIC) return -1;
   return bf16_edge_b_kind(d);

@@ -236,6 +236,32 @@ ChainWidthsPlan plan_chain_widths(int64_t m, int nlayers, const int64_t *n, cons
 struct ChainWidthRoundsPlan { int tile; int groups; const char *why; bool gated; };
 inline bool chain_width_rounds_mode_forced(int mode) { return mode > 1000; }
 ChainWidthRoundsPlan plan_chain_width_rounds(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int b_kind, int mode, bool strict);
+// RAGGED MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths_ragged; rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_wragged.hip
+// launch_bf16_chain_wragged, BLW_CHAIN_WRAGGED, schedule in brgemm_bf16_lw_chain_wragged.h). Host-only, no HIP calls:
+// tests/golden/gemm_plan_chain_widths_ragged.txt is the table of both functions' answers.
+// One call of a chain: chain_ragged_b_kind's question under this switch - the B image (0 VNNI-2, 2 flat, 4 VNNI-4) the call would run with
+// as a layer, or -1 and *why: the switch is off, an f32 call, a VNNI C, beta 1, a forced kernel (the generic kernel included), k below 64
+// or not a multiple of 8, an operand off the LDS-DMA grid of the edge tiles.
+int chain_widths_ragged_b_kind(const GemmDesc &d, int mode, const char **why);
+// The tile of the ONE launch on ceil(m / BM) x max_l ceil(n[l] / BN) workgroups: arguments as plan_chain_widths', with forced_tile 0 .. 3 =
+// the tile xsmm_hip_set_edge_tiles(20 .. 23) names (-1: none) in place of the planned tile, and b_kind = the B image every call has by
+// chain_widths_ragged_b_kind. Takes 2 .. 8 layers with at least two different n, every k >= 64 and k % 8 == 0, every batch >= 1, every
+// n[l] % 8 == 0, not in strict mode. THE PARTITION: a chain SOME tile divides entirely (BM | m, BN | every n[l], every k[l] % 64 == 0) is
+// never this rule's - it is plan_chain_widths' / plan_chain_width_rounds', or call by call with those off -, and equal widths are the other
+// three chain switches'. A tile FITS when m >= BM, every n[l] >= BN, its instance exists (blw_chain_wragged_instance_exists: not 64x128
+// with VNNI-2, which would need scratch - that tile is passed over) and ceil(m / BM) * max_l ceil(n[l] / BN) <= cus. The forced tile if it
+// fits, else the smallest that fits. tile = -1 and why = the reason: the switch off, strict mode, the layer count, no shared B image, such a
+// k or an empty batch, an n % 8, every n equal, a chain some tile divides entirely, m or an n below every tile, more tiles than compute units.
+// THE GATE (structural, plan_chain_widths': a chain in which some layer ALONE fits a smaller tile than the launch's stays call by call,
+// unless an edge-tile mode forces the tile). Measured here too (profiles/chain_widths_ragged_ab.txt: VNNI-2 on 256 CUs, us per step): the
+// widening chain 1000 rows x n = [2000, 1000] would launch on 128x128 (8 x 16; 64x128 has no VNNI-2 instance) while n = 1000 alone fits
+// 64x64 - forced onto 128x128 the launch takes 29.79 against 30.93 for calls pinned to that tile, but the calls on the planner's own tiles
+// take 21.79: +36.7 % as one launch. Gated, it runs 21.79 / 21.80 with the switch off / on. The six ungated rows - the funnels n = [512, 256,
+// 128] at 1024 and 1000 rows with k0 = 784 and 1024, 512 rows x [256, 64, 256, 784], 1000 rows x [504, 248], 200 rows x [136, 72, 200], all
+// on 32x64 - gained 15.9 .. 32.2 % in every pair: no further gate. A gated answer still names the rule's tile, with gated = true and
+// why = the gate: the caller does not launch.
+struct ChainWidthsRaggedPlan { int tile; const char *why; bool gated; };
+ChainWidthsRaggedPlan plan_chain_widths_ragged(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, int b_kind, int mode, bool strict);
 // 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none
 int f32_chain_tile(const GemmDesc &d);
 // tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip; BLW_TILES, brgemm_bf16_lw_launch.h)

@@ -285,6 +285,40 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (!widw_state && cfg().trace) fprintf(stderr, "[tpp-xsmm-hip] fused_brgemm_chain: no mixed-width launch (%s)\n", w);
     return widw_state == 1;
   };
+  // RAGGED MIXED WIDTHS (xsmm_hip_set_chain_widths_ragged, opt-in; gemm_plan.cpp plan_chain_widths_ragged): asked where the loop below meets
+  // calls that differ in n and the mixed-width rules above do not take the chain - at the n term itself, or earlier at a call no loader-wave
+  // tile takes (k % 64, a ragged m or n) -, and where the launch would end in "different widths combine with no other chain mode".
+  // wragged_w() is the rule's answer, asked at most once: the calls differ in n, every call passes chain_widths_ragged_b_kind with the same B
+  // image, has the same m and a batch, and plan_chain_widths_ragged names a tile without a gate. wragw = the launch is the ragged mixed-width
+  // one: the shape terms below are the rule's then, everything else the chain contract asks is checked as for every launch. With the
+  // switch off wragged_w() is false without a look at the calls and every NOCHAIN below is taken exactly as before.
+  const int chain_wragged = f32 ? 0 : g_chain_widths_ragged.load(std::memory_order_relaxed);
+  int wragw_state = chain_wragged ? -1 : 0, wragw_tile = -1, wragw_kind = -1; // -1 not asked yet, 0 no, 1 yes
+  bool wragw = false;
+  auto wragged_w = [&]() {
+    if (wragw_state >= 0) return wragw_state == 1;
+    wragw_state = 0;
+    const char *w = nullptr;
+    bool differ = false;
+    for (int i = 1; i < n; ++i)
+      if (d[i]->n != nn) differ = true;
+    if (!differ) w = "every call has the same n: the equal-width chain switches decide";
+    else wragw_kind = chain_widths_ragged_b_kind(*d[0], chain_wragged, &w);
+    for (int i = 0; i < n && wragw_kind >= 0; ++i)
+      if (chain_widths_ragged_b_kind(*d[i], chain_wragged, &w) != wragw_kind || d[i]->m != m || br[i] < 1) wragw_kind = -1;
+    if (wragw_kind >= 0) {
+      int64_t ns[CH_MAXL], ks[CH_MAXL], brs[CH_MAXL];
+      for (int i = 0; i < n; ++i) ns[i] = d[i]->n, ks[i] = d[i]->k, brs[i] = br[i];
+      const int et = g_edge_tiles.load(std::memory_order_relaxed);
+      const ChainWidthsRaggedPlan rp = plan_chain_widths_ragged(m, n, ns, ks, brs, stream_cus(s), et >= V_BF16_LW_32x64 && et <= V_BF16_LW_128x128 ? et - V_BF16_LW_32x64 : -1,
+                                                                wragw_kind, chain_wragged, cfg().strict.load(std::memory_order_relaxed));
+      w = rp.why;
+      wragw_tile = rp.tile;
+      if (rp.tile >= 0 && !rp.gated) wragw_state = 1; // (gated: the rule's answer is on record in why, nothing is launched)
+    }
+    if (!wragw_state && cfg().trace) fprintf(stderr, "[tpp-xsmm-hip] fused_brgemm_chain: no ragged mixed-width launch (%s)\n", w ? w : "the calls differ in m, have an empty batch, or their B operands differ in kind");
+    return wragw_state == 1;
+  };
   for (int i = 0; i < n; ++i) {
     const GemmDesc &g = *d[i];
     if (edge_on && !edge_why) {
@@ -299,17 +333,22 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     } else
     // every layer the same kind of B operand (VNNI-2, flat or VNNI-4: the B image is a template parameter of the launch)
     if (g.dtype != DT_BF16 || g.vnni_c || !g.beta0 || bf16_lw_b_kind(g) < 0 || bf16_lw_b_kind(g) != bf16_lw_b_kind(*d[0])) {
-      if ((!edge_on || edge_why) && rounds_kind < 0 && !ragw) { // (edge_why: no ragged launch either - an f32 call, a VNNI C, beta 1, a forced kernel, k % 64, the operands' grid)
+      if ((!edge_on || edge_why) && rounds_kind < 0 && !ragw && !wragw) { // (edge_why: no ragged launch either - an f32 call, a VNNI C, beta 1, a forced kernel, k % 64, the operands' grid)
         if (ragged_w()) ragw = true;
+        else if (wragged_w()) wragw = true;
         else NOCHAIN("a call is not bf16 / beta 0 / aligned for the LDS-DMA tiles, or the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)");
       }
       divisible = false;
     }
-    if (g.m != m || br[i] < 1 || (g.n != nn && !widths_w())) NOCHAIN("the calls differ in m or n, or a batch is empty");
-    if (g.n != nn) widw = true;
+    if (g.m != m || br[i] < 1 || (g.n != nn && !wragw && !widths_w() && !wragged_w())) NOCHAIN("the calls differ in m or n, or a batch is empty");
+    if (g.n != nn && !wragw) {
+      if (widw_state == 1) widw = true;
+      else wragw = true; // (the mixed-width rules do not take the chain, the ragged mixed-width rule does)
+    }
     if (g.variant == V_GENERIC) { // (a forced generic kernel stays generic; one that is generic only because no tile divides m may run ragged)
-      if ((!edge_on || edge_why || g.generic_forced) && !ragw) {
+      if ((!edge_on || edge_why || g.generic_forced) && !ragw && !wragw) {
         if (!g.generic_forced && ragged_w()) ragw = true;
+        else if (!g.generic_forced && wragged_w()) wragw = true;
         else NOCHAIN("a call was dispatched to the generic kernel");
       }
       divisible = false;
@@ -324,8 +363,9 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (!devmem.is_device(pa[i], 0) || !devmem.is_device(pb[i], 1) || !devmem.is_device(pc[i], 2) || (g.bias && !devmem.is_device(pd[i], 3)))
       NOCHAIN("a host operand");
   }
-  if (!divisible && edge_why && rounds_kind < 0 && !ragw) {
+  if (!divisible && edge_why && rounds_kind < 0 && !ragw && !wragw) {
     if (ragged_w()) ragw = true;
+    else if (wragged_w()) wragw = true;
     else NOCHAIN(edge_why);
   }
   // The tile: all workgroups must be co-resident (one per CU by LDS), so the grid may not exceed the CUs. If every layer was planned
@@ -351,14 +391,18 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     tile = rp.tile;
     groups = rp.groups;
   };
-  if (!ragw && !divisible && rounds_kind >= 0) { // (a forced G on calls only the one-round rules' m and n terms refuse)
+  if (!ragw && !wragw && !divisible && rounds_kind >= 0) { // (a forced G on calls only the one-round rules' m and n terms refuse)
     shared_tile = chain_rounds_planned_tile(n, d);
     ask_rounds();
     if (tile >= 0) b_kind = rounds_kind;
     else if (!edge_on || edge_why) NOCHAIN(rounds_why);
   }
-  if (widw && (!divisible || ragw)) NOCHAIN("the calls differ in n and one of them is ragged: different widths combine with no other chain mode");
-  if (divisible && !widw) {
+  if (widw && !wragw && (!divisible || ragw)) {
+    if (wragged_w()) wragw = true; // (the rule of the combination, asked instead of the refusal - only with its switch on)
+    else NOCHAIN("the calls differ in n and one of them is ragged: different widths combine with no other chain mode");
+  }
+  if (wragw) widw = ragw = false; // (one launch form: the ragged mixed-width one)
+  if (divisible && !widw && !wragw) {
     // (variants 20 .. 23 VNNI-2, 24 .. 27 flat B, 28 .. 31 VNNI-4: the same four tiles)
     const int planned = blw_variant_tile(d[0]->variant, b_kind);
     bool same = !f32 && planned >= 0 && planned < 4;
@@ -385,6 +429,11 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   if (widw) { // the mixed-width launch: the rule's tile (whole tiles of m and of every n, the widest layer's grid within the compute units)
     tile = widw_tile;
     b_kind = widw_kind;
+  }
+  if (wragw) { // the ragged mixed-width launch: the rule's tile (ceil-divided both ways, the widest layer's grid within the compute units)
+    tile = wragw_tile;
+    b_kind = wragw_kind;
+    groups = 0;
   }
   bool ragged = tile < 0; // (only with a switch on: every path to here with both off has a tile)
   if (ragged) {
@@ -444,11 +493,17 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   c.nlayers = n;
   for (int i = 0; i < n; ++i)
     c.L[i] = ChainLayer{pb[i], pd[i], pc[i], d[i]->ldb, d[i]->ldc, d[i]->stride_a, d[i]->stride_b, (int)d[i]->k, (int)br[i],
-                        EP_BETA0 | (d[i]->bias ? EP_BIAS : 0) | (d[i]->relu ? EP_RELU : 0), widw ? (int)d[i]->n : 0};
+                        EP_BETA0 | (d[i]->bias ? EP_BIAS : 0) | (d[i]->relu ? EP_RELU : 0), widw || wragw ? (int)d[i]->n : 0};
   int widw_tiles[CH_MAXL] = {}; // a mixed-width chain: column tiles per layer; the grid is the widest layer's
   if (widw) {
     for (int i = 0; i < n; ++i) {
       widw_tiles[i] = (int)(d[i]->n / bn);
+      if (d[i]->n > c.n) c.n = (int)d[i]->n;
+    }
+  }
+  if (wragw) { // (a ragged mixed-width chain: the same key, ceil-divided - the arrivals a launch adds to layer i's counters)
+    for (int i = 0; i < n; ++i) {
+      widw_tiles[i] = (int)((d[i]->n + bn - 1) / bn);
       if (d[i]->n > c.n) c.n = (int)d[i]->n;
     }
   }
@@ -471,7 +526,8 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   // (a ragged chain: keyed on ceil(m / BM), the counters it uses; a ragged-width chain on ceil(n / BN) as well - the arrivals per counter)
   // (a mixed-width chain: on the widest layer's column tiles AND every layer's own - two chains with one grid but different inner widths
   // add different numbers to a layer's counters and may not share them)
-  ChainBlock &blk = widw ? chain_block(s, (int)(m / bm), c.n / bn, n, widw_tiles)
+  ChainBlock &blk = wragw ? chain_block(s, (int)((m + bm - 1) / bm), (c.n + bn - 1) / bn, n, widw_tiles)
+                    : widw ? chain_block(s, (int)(m / bm), c.n / bn, n, widw_tiles)
                          : chain_block(s, (int)((m + bm - 1) / bm), (int)(ragw ? (nn + bn - 1) / bn : nn / bn), n);
   c.cnt = blk.cnt;
   c.err = blk.err; // probation launches: the block's word (checked right behind the launch)
@@ -489,8 +545,15 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     g_chain_err_free.pop_back();
   }
   c.target = ++blk.epoch * (unsigned)blk.tiles_n;
-  if (widw) c.target = blk.epoch; // (the kernel multiplies by the producing layer's column tiles: chain_widths_target)
+  if (widw || wragw) c.target = blk.epoch; // (the kernel multiplies by the producing layer's column tiles: chain_widths_target / chain_wragged_target)
   if (f32) HIP_OK(launch_f32_chain(tile, c, s));
+  else if (wragw) {
+    HIP_OK(launch_bf16_chain_wragged(tile, b_kind, c, s));
+    g_chain_widths_ragged_stats[1].store((m + bm - 1) / bm, std::memory_order_relaxed);
+    g_chain_widths_ragged_stats[2].store((c.n + bn - 1) / bn, std::memory_order_relaxed);
+    g_chain_widths_ragged_stats[3].store(blw_variant(tile, b_kind), std::memory_order_relaxed);
+    g_chain_widths_ragged_stats[0].fetch_add(1, std::memory_order_relaxed);
+  }
   else if (widw && widw_groups > 0) {
     c.groups = widw_groups;
     HIP_OK(launch_bf16_chain_wrounds(tile, b_kind, c, s));

@@ -73,6 +73,15 @@ __attribute__((weak)) hipError_t launch_bf16_chain_wrounds(int, int, const Chain
 __attribute__((weak)) ChainWidthRoundsPlan plan_chain_width_rounds(int64_t, int, const int64_t *, const int64_t *, const int64_t *, int64_t, int, int, int, bool) {
   return ChainWidthRoundsPlan{-1, 0, "this build has no column-round planner", false};
 }
+// (ragged mixed-width chains, xsmm_hip_set_chain_widths_ragged: the same arrangement - brgemm_bf16_lw_chain_wragged.hip)
+__attribute__((weak)) hipError_t launch_bf16_chain_wragged(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
+__attribute__((weak)) int chain_widths_ragged_b_kind(const GemmDesc &, int, const char **why) {
+  if (why) *why = "this build has no ragged mixed-width planner";
+  return -1;
+}
+__attribute__((weak)) ChainWidthsRaggedPlan plan_chain_widths_ragged(int64_t, int, const int64_t *, const int64_t *, const int64_t *, int64_t, int, int, int, bool) {
+  return ChainWidthsRaggedPlan{-1, "this build has no ragged mixed-width planner", false};
+}
 // (multi-round chains, xsmm_hip_set_chain_rounds: the same arrangement)
 __attribute__((weak)) int chain_rounds_planned_tile(int, const GemmDesc *const *) { return -1; }
 __attribute__((weak)) int chain_rounds_b_kind(const GemmDesc &) { return -1; }
@@ -607,6 +616,10 @@ extern "C" void xsmm_hip_chain_widths_stats(int64_t out[4]) {
 extern "C" int xsmm_hip_set_chain_width_rounds(int mode) { return tpp::chain_width_rounds_mode_ok(mode) ? tpp::g_chain_width_rounds.exchange(mode) : -1; }
 extern "C" void xsmm_hip_chain_width_rounds_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_width_rounds_stats[i].load(std::memory_order_relaxed);
+}
+extern "C" int xsmm_hip_set_chain_widths_ragged(int mode) { return tpp::chain_widths_ragged_mode_ok(mode) ? tpp::g_chain_widths_ragged.exchange(mode) : -1; }
+extern "C" void xsmm_hip_chain_widths_ragged_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_widths_ragged_stats[i].load(std::memory_order_relaxed);
 }
 extern "C" int xsmm_hip_set_chain_rounds(int mode) { return tpp::chain_rounds_mode_ok(mode) ? tpp::g_chain_rounds.exchange(mode) : -1; }
 extern "C" void xsmm_hip_chain_rounds_stats(int64_t out[4]) {

@@ -258,6 +258,17 @@ inline std::atomic<int> g_chain_width_rounds{[] {
   return chain_width_rounds_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_chain_width_rounds_stats[4]; // column-round launches; row blocks, resident workgroup columns W, GemmVariant of the tile (with its B image) of the latest
+// RAGGED MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths_ragged / TPP_HIP_CHAIN_WIDTHS_RAGGED; gemm_plan.cpp plan_chain_widths_ragged, rt_chain.h
+// try_chain_launch, brgemm_bf16_lw_chain_wragged.h): 0 = off, 1 = a bf16 chain whose layers differ in n AND that no tile divides entirely - a
+// ragged m, some ragged n(l), some k(l) % 64 != 0: 784-512-256-128 - runs as one launch on ceil(m / BM) x max_l ceil(n_l / BN) workgroups. A
+// switch of its own: a chain some tile divides entirely stays xsmm_hip_set_chain_widths', equal widths the other chain switches'.
+inline bool chain_widths_ragged_mode_ok(int v) { return v == 0 || v == 1; }
+inline std::atomic<int> g_chain_widths_ragged{[] {
+  const char *e = getenv("TPP_HIP_CHAIN_WIDTHS_RAGGED");
+  const int v = e ? atoi(e) : 0;
+  return chain_widths_ragged_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_chain_widths_ragged_stats[4]; // ragged mixed-width launches; row blocks, the widest layer's column tiles (both ceil-divided), GemmVariant of the tile (with its B image) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

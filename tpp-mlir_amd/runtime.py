@@ -133,6 +133,8 @@ _SIGNATURES = {
     "xsmm_hip_chain_widths_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_width_rounds": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_width_rounds_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_chain_widths_ragged": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_chain_widths_ragged_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_rounds": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_rounds_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
@@ -489,6 +491,20 @@ class XsmmRuntime:
         24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_chain_width_rounds_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_chain_widths_ragged(self, mode):
+        """bf16 layer chains whose layers differ in n and that no tile divides entirely - a ragged m, a ragged n in some layer, a k that
+        is a multiple of 8 but not of 64 (784-512-256-128) - as one launch on ceil(m / BM) x max_l ceil(n_l / BN) workgroups: 0 off
+        (default), 1 on - the tile set_edge_tiles(20 .. 23) names if it fits, else the smallest that fits; a chain some tile divides
+        entirely stays set_chain_widths'; returns the previous value, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_chain_widths_ragged(mode)
+
+    def chain_widths_ragged_stats(self):
+        """(ragged mixed-width chain launches; row blocks ceil(m / BM), column tiles of the widest layer max_l ceil(n_l / BN), variant
+        number of the tile with its B image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_chain_widths_ragged_stats(out)
         return tuple(int(v) for v in out)
 
     def set_chain_rounds(self, mode):
