@@ -479,6 +479,29 @@ TPP_XSMM_EXPORT void xsmm_hip_edge_k8_bf16_stats(int64_t out[4]);
  * 4 VNNI-4). */
 TPP_XSMM_EXPORT int xsmm_hip_set_dma256_images(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_dma256_images_stats(int64_t out[4]);
+/* Edge tiles on the 256x256 bf16 tile (opt-in; also TPP_HIP_DMA256_EDGE, read as a number). The 256x256 tile takes a call only when 256
+ * divides m and n; a large call that misses this by a few rows or columns (4000 x 4096, 4096 x 4000, 8000 x 8000) runs on a much smaller
+ * tile or on the generic kernel. With this switch on, such a call runs on ceil(m / 256) x ceil(n / 256) workgroups of the 256x256 tile
+ * (kernel entry points brgemm_bf16_dma256_edge / _edge_flatb / _edge_vnni4: the same ring, images, schedule and K loop). The last tile row
+ * starts at row m - 256 and the last tile column at column n - 256; a shifted tile computes all its elements and stores only the rows
+ * and columns no other tile owns. Every output is one chain over k, in k order, on the same MFMA with one rounding: bit for bit what the
+ * divisible kernel gives on the problem padded to whole tiles. No scratch block, no counters: legal on a captured stream.
+ * A call is taken when all of this holds: bf16, no VNNI C, neither a kernel variant nor the generic kernel forced, m >= 256, n >= 256, m
+ * or n not a multiple of 256, n % 8 == 0, k % 32 == 0, batch count >= 1, A, B, C 16-byte and the bias row 8-byte aligned, B VNNI-2, flat or
+ * VNNI-4 with leading dimensions and strides on the grid of the LDS-DMA tiles. Everything else runs as with the switch off - every
+ * tile-queue group, quad and chain too. The switch reads no other switch and covers flat and VNNI-4 B by itself.
+ * mode 0 = off (default); 1 = the rule: at least 240 ceil-divided tiles of 256x256, and 1.4 x their occupancy of the compute units over
+ * the rounds at least that of the ceil-divided 128x128 tiles - measured (profiles/dma256_edge_ab.txt, K = 1024, every switch off /
+ * xsmm_hip_set_edge_tiles(2) -> on): 4000x4096 154.3 / 152.9 -> 35.0 us, 4096x4000 214.1 / 45.3 -> 36.0, 5000x5000 412.6 / 85.1 -> 64.8,
+ * 8000x8000 350.7 / 346.4 -> 135.0, 16000x1024 49.0 / 49.2 -> 38.7, flat and VNNI-4 B alike; the occupancy term refuses 4100x4096 (272
+ * tiles, a partial second round: 52.0 us on the 128x128 edge tile, 58.3 here); 2 = every eligible call (a test / measurement switch).
+ * Read per invoke; returns the previous mode, -1 (and changes nothing) for any other value. The choice depends on the descriptor, the
+ * batch count, the pointers' alignment and the CU count only: made in strict mode too. xsmm_hip_last_refined_kernel reads
+ * "brgemm_bf16_dma<256x256>, edge tiles", "brgemm_bf16_dma_flatb<256x256>, edge tiles" or "brgemm_bf16_dma_vnni4<256x256>, edge tiles".
+ * _stats: out[0] such launches since process start; of the most recent one: [1] tile rows, [2] tile columns (ceil-divided), [3] the B
+ * image (0 VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_dma256_edge(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_dma256_edge_stats(int64_t out[4]);
 /* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
  * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
  * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two

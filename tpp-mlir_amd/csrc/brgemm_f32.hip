@@ -28,6 +28,7 @@
 #include "gemm_plan.h"
 #include "brgemm_f32_lw_kedge.h"
 #include "brgemm_bf16_lw_kedge.h"
+#include "brgemm_bf16_dma256_edge.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -691,6 +692,7 @@ static hipError_t launch_fast(const GemmArgs &a, hipStream_t s) {
 
 hipError_t launch_gemm_bf16_fast(int tile, const GemmArgs &a, hipStream_t s); // brgemm_bf16.hip
 hipError_t launch_bf16_dma256_image(int b_kind, const GemmArgs &a, hipStream_t s); // brgemm_bf16_dma256.hip
+hipError_t launch_bf16_dma256_edge(int b_kind, const GemmArgs &a, hipStream_t s); // brgemm_bf16_dma256_edge.hip: m or n not a multiple of 256; hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         // brgemm_f32_lw.hip (tile 4: 128x64, forced variant 10 only - it measures within 2 % of brgemm_f32_fast<128x64>)
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
@@ -732,7 +734,8 @@ static GemmPlanEnv gemm_plan_env() {
   return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed), g_tail_split.load(std::memory_order_relaxed),
                      g_edge_tiles.load(std::memory_order_relaxed), g_edge_k.load(std::memory_order_relaxed),
                      g_edge_k_bf16.load(std::memory_order_relaxed), g_f32_halves.load(std::memory_order_relaxed),
-                     g_edge_k8_bf16.load(std::memory_order_relaxed), g_dma256_images.load(std::memory_order_relaxed)};
+                     g_edge_k8_bf16.load(std::memory_order_relaxed), g_dma256_images.load(std::memory_order_relaxed),
+                     g_dma256_edge.load(std::memory_order_relaxed)};
 }
 bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, gemm_plan_env()); }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, gemm_plan_env()); }
@@ -794,7 +797,9 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
   case GL_F32_LW16: return launch_f32_lw16(p.tile, a, wi, n_items, grouped, s);
   case GL_F32_LW_GROUPED: return launch_f32_lw_grouped(p.tile, a, wi, n_items, p.split, s);
   case GL_F32_X6: return launch_f32_x6(p.tile, a, p.vec, s);
-  case GL_BF16_FAST: return p.b_kind != 0 ? (p.tile == 2 ? launch_bf16_dma256_image(p.b_kind, a, s) : hipErrorInvalidValue) : launch_gemm_bf16_fast(p.tile, a, s);
+  case GL_BF16_FAST:
+    if (p.edge) return p.tile == 2 ? launch_bf16_dma256_edge(p.b_kind, a, s) : hipErrorInvalidValue;
+    return p.b_kind != 0 ? (p.tile == 2 ? launch_bf16_dma256_image(p.b_kind, a, s) : hipErrorInvalidValue) : launch_gemm_bf16_fast(p.tile, a, s);
   case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split);
   case GL_BF16_GROUPED64: return launch_bf16_grouped64(a, wi, n_items, s);
   case GL_BF16_LW:
@@ -825,6 +830,21 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   GemmLaunch p = plan_gemm_call(d, br, al, env);
   if (p.launcher == GL_NONE) return hipSuccess;
   const GemmArgs a = gemm_args(d, A, B, C, D, (int)(br < 0 ? 0 : br));
+  if (p.launcher == GL_BF16_FAST && p.edge) { // edge tiles on the 256x256 tile (xsmm_desc.h g_dma256_edge; brgemm_bf16_dma256_edge.h)
+    const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    if (e != hipErrorInvalidValue) {
+      if (e == hipSuccess) {
+        g_dma256_edge_stats[1].store(d256e_tiles((int)d.m), std::memory_order_relaxed);
+        g_dma256_edge_stats[2].store(d256e_tiles((int)d.n), std::memory_order_relaxed);
+        g_dma256_edge_stats[3].store(p.b_kind, std::memory_order_relaxed);
+        g_dma256_edge_stats[0].fetch_add(1, std::memory_order_relaxed);
+      }
+      return g_last_refined.store(p.text, std::memory_order_relaxed), e;
+    }
+    (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
+    env.dma256_edge = 0;
+    p = plan_gemm_call(d, br, al, env);
+  }
   if (p.launcher == GL_BF16_FAST && p.b_kind != 0) { // a flat or VNNI-4 B on the 256x256 tile (xsmm_desc.h g_dma256_images; brgemm_bf16_dma256_images.h)
     const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
     if (e != hipErrorInvalidValue) {

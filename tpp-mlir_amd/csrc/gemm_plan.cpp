@@ -313,9 +313,11 @@ static int pick_bf16_lw_image_tile(const GemmDesc &d, int64_t cus, int first_var
 // (brgemm_bf16_lw.hip GRP = 3, launch_bf16_lw). What the three B images ask of leading dimensions, strides and lane offsets is
 // bf16_fast_eligible / bf16_flat_eligible / bf16_vnni4_eligible without their m / n terms; returns the image (0 VNNI-2, 2 flat, 4 VNNI-4), -1 = none.
 // ragged_k 1 (xsmm_hip_set_edge_k_bf16): the k % 64 term replaced by brgemm_bf16_lw_kedge.h's bkedge_k_ok; 2 (xsmm_hip_set_edge_k8_bf16): by
-// bkedge8_k_ok.
+// bkedge8_k_ok; 3 (xsmm_hip_set_dma256_edge): by k % 32, the chunk of the 256x256 tile.
 static int bf16_edge_b_kind(const GemmDesc &d, int ragged_k = 0) {
-  if (d.dtype != DT_BF16 || d.vnni_c || d.k <= 0 || (ragged_k == 2 ? !bkedge8_k_ok(d.k) : ragged_k == 1 ? !bkedge_k_ok(d.k) : d.k % BK != 0)) return -1;
+  if (d.dtype != DT_BF16 || d.vnni_c || d.k <= 0 ||
+      (ragged_k == 3 ? d.k % 32 != 0 : ragged_k == 2 ? !bkedge8_k_ok(d.k) : ragged_k == 1 ? !bkedge_k_ok(d.k) : d.k % BK != 0))
+    return -1;
   if ((d.lda | d.ldc | d.stride_a | d.stride_b) & 7 || d.lda >= (1 << 22) || d.ldc >= (1 << 22)) return -1;
   if (d.vnni_b && d.vnni_factor == 2) return !(d.ldb & 3) && d.ldb < (1 << 21) ? 0 : -1;
   if (d.vnni_b && d.vnni_factor == 4) return !(d.ldb & 1) && d.ldb < (1 << 20) ? 4 : -1;
@@ -337,6 +339,24 @@ static int choose_bf16_edge_tile(const GemmDesc &d, int mode, int64_t chunks, in
     if (best < 0 || cost < best_t) best = t, best_t = cost;
   }
   return best;
+}
+
+// EDGE TILES on the 256x256 tile (xsmm_hip_set_dma256_edge mode 1, opt-in; brgemm_bf16_dma256_edge.h): pick_bf16_tile's rule for the 256x256
+// tile on CEIL-DIVIDED tile counts - at least 240 tiles of 256x256, and 1.4 x their CU occupancy over the rounds at least that of the
+// ceil-divided 128x128 tiles.
+// Measured (profiles/dma256_edge_ab.txt: one box, 256 CUs, K = 1024, beta 0 + bias + relu, five alternating rounds, us per call, every switch
+// off / xsmm_hip_set_edge_tiles(2) -> this tile):
+//   VNNI-2: 4000x4096 154.28 / 152.89 -> 35.03, 4096x4000 214.08 / 45.27 -> 35.96, 5000x5000 412.55 / 85.06 -> 64.76, 8000x8000 350.71 /
+//           346.40 -> 135.03, 16000x1024 (63 x 4 tiles) 49.02 / 49.20 -> 38.73
+//   flat:   4000x4096 119.10 / 118.32 -> 35.67, 8000x8000 352.75 / 347.39 -> 136.11;  VNNI-4: 119.39 / 118.36 -> 35.51, 344.87 / 342.03 -> 134.27
+// each faster in 5 of 5 rounds against both. The gate: 4100x4096, 17 x 16 = 272 tiles - a second round with 16 tiles in it - 164.78 / 52.03
+// -> 58.26: slower than the 128x128 edge tile in 5 of 5 rounds. The fill term refuses it as it stands (1.4 * 272 / 512 = 0.74 < 1056 /
+// 1280 = 0.83), so no further gate is needed: mode 1 takes every measured row that gained and no other. Not measured: K other than 1024.
+static bool dma256_edge_rule(const GemmDesc &d) {
+  auto cdiv = [](int64_t x, int64_t t) { return (x + t - 1) / t; };
+  const int64_t t256 = cdiv(d.m, 256) * cdiv(d.n, 256), t128 = cdiv(d.m, 128) * cdiv(d.n, 128);
+  auto fill = [](int64_t t) { return (double)t / (double)(((t + 255) / 256) * 256); }; // CU occupancy over the rounds
+  return t256 >= 240 && 1.4 * fill(t256) >= fill(t128);
 }
 
 // RAGGED k, bf16 (xsmm_hip_set_edge_k_bf16, opt-in; brgemm_bf16_lw_kedge.h): a whole-layer bf16 call whose k is a multiple of 16 but not of
@@ -848,6 +868,24 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
   const bool bias_ok8 = !d.bias || al.d8;
   if (v >= V_BF16_FAST && v != V_BF16_SMALL32 && !(al.c16 && bias_ok8)) v = V_GENERIC;
   if (v == V_BF16_SMALL32 && !(al.c8 && bias_ok8)) v = V_GENERIC;
+  // Edge tiles on the 256x256 tile, if asked for (xsmm_hip_set_dma256_edge, a switch of its own; brgemm_bf16_dma256_edge.hip,
+  // brgemm_bf16_dma256_edge.h): a large call - m, n >= 256 - whose m or n the 256x256 tile does not divide, whatever kernel it is planned -
+  // not forced - on and whichever of the three B images it has, on the ceil-divided grid of that tile. Mode 1: dma256_edge_rule; mode 2
+  // (tests, measurements): every eligible call. Asked before the loader-wave edge tiles and read by no other switch. Decided here only -
+  // what is queued, grouped, chained or made a quad never sees it -, from the descriptor, the batch count, the pointers' alignment and the CU
+  // count: allowed in strict mode. n % 8 keeps the shifted column tile on 16 bytes of C, of every B image and of the bias row. The launcher's
+  // own checks: launch_bf16_dma256_edge; refused there, the call runs the launch it has with the mode off (launch_gemm).
+  if (env.dma256_edge != 0 && d.dtype == DT_BF16 && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.m >= 256 && d.n >= 256 &&
+      (d.m % 256 != 0 || d.n % 256 != 0) && d.n % 8 == 0 && d.k % 32 == 0 && br >= 1 && al.ab16 && al.c16 && bias_ok8) {
+    const int kind = bf16_edge_b_kind(d, 3);
+    if (kind >= 0 && (env.dma256_edge == 2 || dma256_edge_rule(d))) {
+      static const char *const names[3] = {"brgemm_bf16_dma<256x256>, edge tiles", "brgemm_bf16_dma_flatb<256x256>, edge tiles",
+                                           "brgemm_bf16_dma_vnni4<256x256>, edge tiles"};
+      GemmLaunch l = launch(GL_BF16_FAST, 2, names[kind / 2], 1, kind);
+      l.edge = true;
+      return l;
+    }
+  }
   // bf16 edge tiles, if asked for (choose_bf16_edge_tile): a call no loader-wave tile divides, before the refinements of the 32x32 K-split
   // kernel below. Decided here only - what is queued, grouped, chained or made a quad never sees it -, from the descriptor, the batch
   // count, the pointers' alignment and the CU count: allowed in strict mode. n % 8 keeps the shifted column tile on 16 bytes of C, of a

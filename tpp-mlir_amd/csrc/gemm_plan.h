@@ -47,8 +47,8 @@ enum GemmVariant : int {
 // that bf16 GemmVariant's tile) and xsmm_hip_set_edge_k (0 = off, 1 = the f32 tile rule, 6 / 7 / 9 / 10 = that GemmVariant's tile) and
 // xsmm_hip_set_edge_k_bf16 (0 = off, 1 = the bf16 tile rule, 20 .. 23 = that bf16 GemmVariant's tile) and xsmm_hip_set_f32_halves (0 = off, 1 =
 // the rule, 2 = wherever eligible) and xsmm_hip_set_edge_k8_bf16 (the values of edge_k_bf16, for k % 16 == 8) and xsmm_hip_set_dma256_images
-// (0 = off, 1 = the rule, 2 = wherever eligible); brgemm_f32.hip gemm_plan_env fills it per call
-struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; };
+// (0 = off, 1 = the rule, 2 = wherever eligible) and xsmm_hip_set_dma256_edge (the same values); brgemm_f32.hip gemm_plan_env fills it per call
+struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; int dma256_edge = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
 struct GemmAlign { bool ab16, c16, c8, d8, d16; };
@@ -62,7 +62,7 @@ enum GemmLauncher : int {
   GL_F32_LW16,        // launch_f32_lw16(tile); split > 1: launch_f32_lw_split(3, split) first
   GL_F32_LW_GROUPED,  // launch_f32_lw_grouped(tile, split)
   GL_F32_X6,          // launch_f32_x6(tile, vec)
-  GL_BF16_FAST,       // launch_gemm_bf16_fast(tile); b_kind 2 / 4 (xsmm_hip_set_dma256_images): launch_bf16_dma256_image(b_kind), tile 2 only
+  GL_BF16_FAST,       // launch_gemm_bf16_fast(tile); b_kind 2 / 4 (xsmm_hip_set_dma256_images): launch_bf16_dma256_image(b_kind), tile 2 only; edge (xsmm_hip_set_dma256_edge): launch_bf16_dma256_edge(b_kind), tile 2 only
   GL_BF16_SMALL32,    // launch_bf16_small32(split)
   GL_BF16_GROUPED64,  // launch_bf16_grouped64
   GL_BF16_LW,         // launch_bf16_lw(mode, tile, b_kind); mode (brgemm_bf16_lw_launch.h): BLW_LAYER; edge: BLW_EDGE; edge_k: BLW_KEDGE; edge_k8: BLW_KEDGE8
@@ -88,7 +88,8 @@ struct GemmLaunch {
   int tail_tiles = 0;
   int tail_split = 1;
   // GL_F32_LW / GL_BF16_LW, edge tiles (xsmm_hip_set_edge_tiles): m or n is not a multiple of the tile - launch_f32_lw_edge(tile) /
-  // launch_bf16_lw(BLW_EDGE, tile, b_kind) on the ceil-divided tile grid; refused by the launcher: the launch the call has with the mode off
+  // launch_bf16_lw(BLW_EDGE, tile, b_kind) on the ceil-divided tile grid; refused by the launcher: the launch the call has with the mode off.
+  // GL_BF16_FAST, tile 2 (xsmm_hip_set_dma256_edge): m or n is not a multiple of 256 - launch_bf16_dma256_edge(b_kind), refused the same way
   bool edge = false;
   // GL_F32_LW, ragged k (xsmm_hip_set_edge_k): k is a multiple of 8 but not of 64 - launch_f32_lw_kedge(tile) on the ceil-divided tile
   // grid (m and n may be ragged too); refused by the launcher: the launch the call has with the mode off.

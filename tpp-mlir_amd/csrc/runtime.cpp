@@ -601,6 +601,10 @@ extern "C" int xsmm_hip_set_dma256_images(int mode) { return tpp::dma256_images_
 extern "C" void xsmm_hip_dma256_images_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_dma256_images_stats[i].load(std::memory_order_relaxed);
 }
+extern "C" int xsmm_hip_set_dma256_edge(int mode) { return tpp::dma256_edge_mode_ok(mode) ? tpp::g_dma256_edge.exchange(mode) : -1; }
+extern "C" void xsmm_hip_dma256_edge_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_dma256_edge_stats[i].load(std::memory_order_relaxed);
+}
 extern "C" int xsmm_hip_set_edge_k8_bf16(int mode) { return tpp::edge_k_bf16_mode_ok(mode) ? tpp::g_edge_k8_bf16.exchange(mode) : -1; }
 extern "C" void xsmm_hip_edge_k8_bf16_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k8_bf16_stats[i].load(std::memory_order_relaxed);

@@ -195,6 +195,16 @@ inline std::atomic<int> g_dma256_images{[] {
   return dma256_images_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_dma256_images_stats[4]; // such launches; tile rows, tile columns (256x256 tiles), B image (2 flat, 4 VNNI-4) of the latest
+// EDGE TILES on the 256x256 bf16 tile (xsmm_hip_set_dma256_edge / TPP_HIP_DMA256_EDGE; gemm_plan.cpp plan_gemm_call, brgemm_bf16_dma256_edge.hip
+// launch_bf16_dma256_edge, brgemm_bf16_dma256_edge.h): 0 = off, 1 = the rule (gemm_plan.cpp dma256_edge_rule), 2 = every eligible whole-layer call
+// (m, n >= 256, m or n not a multiple of 256; tests, measurements).
+inline bool dma256_edge_mode_ok(int v) { return v >= 0 && v <= 2; }
+inline std::atomic<int> g_dma256_edge{[] {
+  const char *e = getenv("TPP_HIP_DMA256_EDGE");
+  const int v = e ? atoi(e) : 0;
+  return dma256_edge_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_dma256_edge_stats[4]; // such launches; tile rows, tile columns (ceil-divided), B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
 // HALVES (xsmm_hip_set_f32_halves / TPP_HIP_F32_HALVES; gemm_plan.cpp choose_f32_halves, brgemm_f32_lw.hip launch_f32_lw_halves): 0 = off, 1 =
 // the rule (default: at least one 64x64 tile per CU), 2 = every eligible whole-layer call on the 64x64 + K2 f32 tile runs as two 64x32 + K2
 // workgroups per tile (the same bits).

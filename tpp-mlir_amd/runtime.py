@@ -123,6 +123,8 @@ _SIGNATURES = {
     "xsmm_hip_edge_k8_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_dma256_images": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_dma256_images_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_dma256_edge": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_dma256_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_f32_halves": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_f32_halves_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
@@ -428,6 +430,17 @@ class XsmmRuntime:
         """(launches of a flat or VNNI-4 B on the 256x256 tile; tile rows, tile columns, B image - 2 flat, 4 VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_dma256_images_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_dma256_edge(self, mode):
+        """large bf16 whole-layer calls whose m or n is not a multiple of 256 (m, n >= 256, n % 8 == 0, k % 32 == 0) on edge tiles of the
+        256x256 tile (the same bits): 0 off (default), 1 the rule, 2 wherever eligible; returns the previous mode, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_dma256_edge(mode)
+
+    def dma256_edge_stats(self):
+        """(edge-tile launches on the 256x256 tile; tile rows, tile columns, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_dma256_edge_stats(out)
         return tuple(int(v) for v in out)
 
     def set_f32_halves(self, mode):
