@@ -502,6 +502,31 @@ TPP_XSMM_EXPORT void xsmm_hip_dma256_images_stats(int64_t out[4]);
  * image (0 VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_dma256_edge(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_dma256_edge_stats(int64_t out[4]);
+/* Layer chains on the 256x256 bf16 tile (opt-in; also TPP_HIP_CHAIN_DMA256, read as a number). Every chain form above is a form of the
+ * loader-wave tiles (32x64 .. 128x128); a chain whose calls run on the 256x256 LDS-DMA tile - 16384 rows x 1024 columns are exactly 256
+ * such tiles - ran call by call. With this switch on, xsmm_hip_fused_brgemm_chain_invoke runs such a chain as ONE launch of that tile's
+ * chain kernel (entry points brgemm_bf16_dma256_chain / _chain_flatb / _chain_vnni4: the same ring, images, schedule, K loop and epilogue):
+ * G x n / 256 resident workgroups, workgroup (g, tn) computes tile (tm, tn) of every layer for the row blocks tm = g, g + G, .. of its
+ * group, layer by layer; G = m / 256 when the grid fits the compute units (one round), fewer otherwise. The hand-off between layers is
+ * the chain's: write-through stores, a counter per row block that only grows, a bounded wait that ends in the error word, never in a
+ * hang; probation, the journal and the re-run of a starved launch are the ones described at xsmm_hip_fused_brgemm_chain_invoke. Every
+ * output is computed as the same call on the 256x256 tile computes it: bit for bit the separate calls on that tile.
+ * A chain is eligible when all of this holds: 2 .. 8 calls, all bf16 and beta 0 with the same m and n, 256 dividing both, no VNNI C, not
+ * the forced generic kernel, one B image (VNNI-2, flat or VNNI-4) with leading dimensions and strides on the tile's grid, every k a
+ * multiple of 32, every batch count >= 1, n / 256 at most the stream's compute units - and what every chain launch asks: asynchronous
+ * mode, no stream capture, A, B, C 16-byte and bias rows 8-byte aligned, each call reading its predecessor's output, batch elements
+ * inside their rows, device operands, no overlaps. Everything else - and every chain with the mode 0 - is decided exactly as without
+ * this switch: it is asked first, no other switch reads it, and it reads no other mode but xsmm_hip_set_dma256_images' in mode 1.
+ * mode 0 = off (default); 1 = the rule: an eligible chain EVERY call of which runs on the 256x256 tile as a single call today - VNNI-2:
+ * dispatched on that tile; flat / VNNI-4: xsmm_hip_set_dma256_images is non-zero and takes the call - subject to the measured gate of
+ * gemm_plan.h plan_chain_dma256 (profiles/chain_dma256_ab.txt); 2 = every eligible chain (a test / measurement switch); 1000 + G = every
+ * eligible chain on G row groups, 1 <= G <= m / 256 and G * n / 256 at most the compute units (likewise). Read per invoke; returns the
+ * previous mode, -1 (and changes nothing) for any other value. Strict mode takes a chain only where every call was dispatched on the
+ * tile: the launch then has the separate calls' bits.
+ * _stats: out[0] such launches since process start; of the most recent one: [1] resident row groups G (m / 256 in one round), [2]
+ * rounds ceil(m / 256 / G), [3] the B image (0 VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_dma256(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_dma256_stats(int64_t out[4]);
 /* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
  * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
  * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two

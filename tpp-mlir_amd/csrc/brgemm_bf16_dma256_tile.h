@@ -1,5 +1,7 @@
 // brgemm_bf16_dma256_tile.h - the 256 x 256 bf16 tile, written once: the body of the kernels of brgemm_bf16_dma256.hip (whole tiles) and of
-// brgemm_bf16_dma256_edge.hip (EDGE: a ceil-divided grid whose last tile row / column is shifted back, brgemm_bf16_dma256_edge.h).
+// brgemm_bf16_dma256_edge.hip (EDGE: a ceil-divided grid whose last tile row / column is shifted back, brgemm_bf16_dma256_edge.h) and the layer
+// step of the chain kernels of brgemm_bf16_dma256_chain.hip (CHAIN: a chain of whole-layer calls in one launch, xsmm_hip_set_chain_dma256 -
+// the body is called once per layer and row block, the seam between two layers is that file's; brgemm_bf16_dma256_chain.h).
 //
 // The large-shape member of the bf16 BRGEMM family for gfx950:
 // 256 x 256 workgroup tiles, four waves of 128 x 128 (4 x 4 accumulator tiles of
@@ -37,6 +39,7 @@
 #include "xsmm_desc.h"
 #include "brgemm_bf16_dma256_images.h"
 #include "brgemm_bf16_dma256_edge.h"
+#include "chain_args.h"
 #include <type_traits>
 
 namespace tpp {
@@ -49,8 +52,20 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 // EDGE (brgemm_bf16_dma256_edge.h): m and n need not be multiples of 256 (m, n >= 256, n % 8 == 0). The grid is ceil-divided, the last tile
 // row / column starts at m - 256 / n - 256 and the epilogue stores a 16-byte piece only if no other tile owns it. Ring, images, schedule
 // and K loop are the same text; false compiles to the kernel without the parameter.
-template <int IMG, bool EDGE>
-__device__ __forceinline__ void brgemm_bf16_dma256_body(const GemmArgs &p) {
+// the lane index from statements the compiler keeps where they stand (see the epilogue's fresh_lane)
+__device__ __forceinline__ int d256_fresh_lane() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
+// CHAIN (brgemm_bf16_dma256_chain.hip, xsmm_hip_set_chain_dma256): the body as ONE LAYER STEP of a layer chain - the caller hands in the layer's
+// arguments and the step's tile (ctm, ctn) instead of the block index, and calls the body once per step: offsets, wrap deltas, accumulators,
+// prologue, K loop and epilogue are all taken anew from p at the top of each call. The A operand of a later layer was stored by other
+// workgroups of the same launch: every LDS-DMA load of A carries sc1 (the L1 is bypassed; the aux field is an immediate, so layer 0 pays
+// it too). The seam itself - drain, barrier, counter - is the caller's. false compiles to the kernel without the parameter.
+template <int IMG, bool EDGE, bool CHAIN = false>
+__device__ __forceinline__ void brgemm_bf16_dma256_body(const GemmArgs &p, int ctm = 0, int ctn = 0, int cwave = 0, int cl = 0) {
   static_assert(d256_image_ok(IMG), "0: VNNI-2 B image, 2: flat B image + transpose reads, 4: VNNI-4 B image + 8-byte reads");
   constexpr int BM = D256_BM, BN = D256_BN, BK2 = D256_BK, NSLOT = 4, TM = 4, TN = 4;
   constexpr int A_SLOT = D256_A_SLOT, B_SLOT = D256_B_SLOT, SLOT = A_SLOT + B_SLOT;
@@ -58,12 +73,14 @@ __device__ __forceinline__ void brgemm_bf16_dma256_body(const GemmArgs &p) {
   static_assert(SLOT == 32768, "ring slot");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_x[];
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // (CHAIN: the lane index is taken anew in every step and the wave index comes from the caller, in a scalar register - a thread index that
+  // lives across the K loop for the next step's offsets is a register this kernel does not have)
+  const int tid = CHAIN ? cwave * 64 + d256_fresh_lane() : (int)threadIdx.x, lane = tid & 63;
+  const int wave = CHAIN ? cwave : __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int li = lane & 31, lh = lane >> 5;
-  const int tm = (int)(blockIdx.x >> 1) * p.tiles_m + (int)blockIdx.z;
-  const int tn = (int)(blockIdx.x & 1) * p.tiles_n + (int)blockIdx.y;
+  const int tm = CHAIN ? ctm : (int)(blockIdx.x >> 1) * p.tiles_m + (int)blockIdx.z;
+  const int tn = CHAIN ? ctn : (int)(blockIdx.x & 1) * p.tiles_n + (int)blockIdx.y;
   const int m0 = EDGE ? d256e_origin(tm, p.m) : tm * BM, n0 = EDGE ? d256e_origin(tn, p.n) : tn * BN; // wave-uniform: from the block index
   const unsigned short *__restrict__ A = (const unsigned short *)p.A;
   const unsigned short *__restrict__ B = (const unsigned short *)p.B;
@@ -91,7 +108,7 @@ __device__ __forceinline__ void brgemm_bf16_dma256_body(const GemmArgs &p) {
     unsigned char *base = smem_x + slot * SLOT + wave * 4096;
     if (u < 4) {
       const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void *)gA, 0, 0x7fffffff, 0x00020000);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void_t *)(base + u * 1024), 16, voffA[u], 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void_t *)(base + u * 1024), 16, voffA[u], 0, 0, CHAIN ? 16 : 0);
     } else {
       const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void *)gB, 0, 0x7fffffff, 0x00020000);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_void_t *)(base + A_SLOT + (u - 4) * 1024), 16, voffB[u - 4], 0, 0, 0);
@@ -272,10 +289,28 @@ __device__ __forceinline__ void brgemm_bf16_dma256_body(const GemmArgs &p) {
     return l;
   };
   typedef unsigned int u32x2d __attribute__((ext_vector_type(2)));
+  // What the epilogue takes from the arguments. CHAIN: read HERE, from the layer's entry in the kernarg segment, through a layer index the
+  // compiler cannot see through - loaded in front of the K loop these seven scalar registers stay live across it, and that loop with the
+  // chain's own state beside it has none to spare (they were spilled). (Without CHAIN every D256_EP is the argument itself, read where
+  // the text names it.)
+  [[maybe_unused]] unsigned short *cC = nullptr;
+  [[maybe_unused]] const void *cD = nullptr;
+  [[maybe_unused]] int64_t cldc = 0;
+  [[maybe_unused]] int cep = 0;
+  if constexpr (CHAIN) {
+    int el = cl;
+    asm volatile("" : "+s"(el));
+    const __attribute__((address_space(4))) ChainArgs &q = *(const __attribute__((address_space(4))) ChainArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    cC = (unsigned short *)q.L[el].C;
+    cD = q.L[el].D;
+    cldc = q.L[el].ldc;
+    cep = q.L[el].ep | EP_BETA0; // (beta 0: the chain launcher's precondition)
+  }
+#define D256_EP(chain_value, value) (CHAIN ? (chain_value) : (value))
   const __amdgpu_buffer_rsrc_t rsrcC = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)(C + (int64_t)(m0 + wm * 128) * p.ldc + n0 + wn * 128), 0, 0x7fffffff, 0x00020000);
-  const unsigned ldcb = (unsigned)((int)p.ldc * 2);
-  if (!(p.ep & EP_BETA0)) { // beta = 1: add C before the single rounding
+      (void *)(D256_EP(cC, C) + (int64_t)(m0 + wm * 128) * D256_EP(cldc, p.ldc) + n0 + wn * 128), 0, 0x7fffffff, 0x00020000);
+  const unsigned ldcb = (unsigned)((int)D256_EP(cldc, p.ldc) * 2);
+  if (!(D256_EP(cep, p.ep) & EP_BETA0)) { // beta = 1: add C before the single rounding
     const int lane1 = fresh_lane(), li = lane1 & 31, lh = lane1 >> 5;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -294,7 +329,7 @@ __device__ __forceinline__ void brgemm_bf16_dma256_body(const GemmArgs &p) {
   __syncthreads(); // every wave is done with the ring (all DMA landed): reuse it as per-wave output tiles
   { // (a scope of its own: these names shadow the K loop's)
   const int lane = fresh_lane(), li = lane & 31, lh = lane >> 5;
-  const bool relu = (p.ep & EP_RELU) != 0;
+  const bool relu = (D256_EP(cep, p.ep) & EP_RELU) != 0;
   constexpr int ES = 272; // bytes per staged row: 128 bf16 + 16 B pad (conflict-free 16-byte accesses)
   unsigned char *ot = smem_x + wave * (64 * ES);
   // EDGE: what this lane stores (d256e_owns). The tile's first d256e_skip rows / columns are a neighbour's: row_lim is the first of the
@@ -314,8 +349,8 @@ __device__ __forceinline__ void brgemm_bf16_dma256_body(const GemmArgs &p) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         u32x2d b2 = {0u, 0u};
-        if (p.ep & EP_BIAS)
-          b2 = *(const u32x2d *)((const unsigned short *)p.D + n0 + wn * 128 + 32 * j + 8 * g + 4 * lh);
+        if (D256_EP(cep, p.ep) & EP_BIAS)
+          b2 = *(const u32x2d *)((const unsigned short *)D256_EP(cD, p.D) + n0 + wn * 128 + 32 * j + 8 * g + 4 * lh);
         bias[g][0] = __uint_as_float(b2[0] << 16);
         bias[g][1] = __uint_as_float(b2[0] & 0xffff0000u);
         bias[g][2] = __uint_as_float(b2[1] << 16);
@@ -364,5 +399,6 @@ __device__ __forceinline__ void brgemm_bf16_dma256_body(const GemmArgs &p) {
 }
 
 #undef TPP_DMA256_ADVANCE
+#undef D256_EP
 
 } // namespace tpp

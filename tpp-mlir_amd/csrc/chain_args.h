@@ -68,6 +68,11 @@ hipError_t launch_bf16_chain_wrounds(int tile, int b_kind, const ChainArgs &a, h
 // workgroups, at most the stream's compute units - the caller's guarantee -, cnt[l][*] reaches epoch * ceil(a.L[l].pad / BN).
 // blw_chain_wragged_launch_ok is what it refuses
 hipError_t launch_bf16_chain_wragged(int tile, int b_kind, const ChainArgs &a, hipStream_t s);
+// a chain on the 256x256 LDS-DMA tile (brgemm_bf16_dma256_chain.hip, xsmm_hip_set_chain_dma256; maps in brgemm_bf16_dma256_chain.h): every layer
+// m x n with 256 dividing both, k(l) in 32-k chunks, beta 0; b_kind 0 VNNI-2 / 2 flat / 4 VNNI-4; a.groups = resident row groups G (0: one
+// round, G = m / 256); the grid is G x n / 256 workgroups, at most the stream's compute units - the caller's guarantee. Refuses with
+// hipErrorInvalidValue, launching nothing, whatever the kernel cannot run
+hipError_t launch_bf16_dma256_chain(int b_kind, const ChainArgs &a, hipStream_t s);
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2; b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);

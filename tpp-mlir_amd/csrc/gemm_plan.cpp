@@ -4,6 +4,8 @@
 #include "brgemm_f32_lw_kedge.h"
 #include "brgemm_bf16_lw_launch.h" // the tile table; brgemm_bf16_lw_kedge.h
 #include "brgemm_bf16_lw_chain_rounds.h"
+#include "brgemm_bf16_dma256_images.h"
+#include "brgemm_bf16_dma256_chain.h"
 #include <string.h>
 
 namespace tpp {
@@ -831,6 +833,59 @@ ChainRoundsPlan plan_chain_rounds(int64_t m, int64_t n, int nlayers, const int64
   if (chain_rounds_rounds((int)tiles_m, groups) > CHAIN_ROUNDS_GATE)
     return ChainRoundsPlan{tile, groups, "gate: more than two rounds measured slower than call by call (profiles/chain_rounds_ab.txt)", true};
   return ChainRoundsPlan{tile, groups, "", false};
+}
+
+int chain_dma256_b_kind(const GemmDesc &d) {
+  if (d.dtype != DT_BF16) return -2;
+  if (d.vnni_c || !d.beta0 || d.generic_forced) return -1;
+  const int kind = bf16_edge_b_kind(d, 3); // (k % 32, the tile's chunk; leading dimensions, strides, lane offsets)
+  return kind >= 0 && d256_b_ldb_ok(kind, d.ldb) ? kind : -1;
+}
+
+bool chain_dma256_on_tile(const GemmDesc &d, int dma256_images) {
+  if (d.dtype != DT_BF16 || d.vnni_c || d.generic_forced) return false;
+  if (d.variant == V_BF16_DMA256) return true;
+  if (dma256_images == 0 || d.variant_forced || d.variant < V_BF16_LWF_32x64 || d.variant > V_BF16_LW4_128x128 || d.m % 256 != 0 || d.n % 256 != 0) return false;
+  const int kind = bf16_lw_b_kind(d);
+  return (kind == 2 || kind == 4) && (dma256_images == 2 || pick_bf16_tile(d) == 2);
+}
+
+// THE GATE of plan_chain_dma256, mode 1 (gemm_plan.h). Measured (profiles/chain_dma256_ab.txt: one box, 256 CUs, three layers, bias + relu, five
+// alternating pairs, us per step, call by call with every chain switch off -> one launch): 1024-wide layers (4 column tiles) at 16384 rows
+// 109.65 -> 108.56 (one round; flat 110.19 -> 109.41, VNNI-4 109.20 -> 108.29) and at 32768 rows 214.65 -> 203.22 (two rounds) gain - every
+// VNNI-2 and VNNI-4 pair faster, four of five flat pairs -; 4096 rows x 4096-wide layers (16 x 16 tiles, 128 chunks per layer) lose in every
+// pair, 334.03 -> 337.64: a consumer there waits for sixteen producers behind layers of 112 us, and the launch it saves is 1 % of a layer.
+// So a chain of MORE THAN EIGHT column tiles stays call by call (sixteen lose, four gain; nothing between was measured). (8192 rows x
+// 1024, 128 tiles, lose 73.02 -> 82.61 under mode 2 - their calls run on the 128x128 tile, which fills the chip; mode 1 never takes them.)
+static bool chain_dma256_gated(int64_t tiles_m, int64_t tiles_n, int groups) {
+  (void)tiles_m, (void)groups;
+  return tiles_n > CHAIN_DMA256_GATE_TILES_N;
+}
+
+ChainDma256Plan plan_chain_dma256(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, bool all_on_tile, int b_kind, int mode, bool strict) {
+  auto no = [](const char *why) { return ChainDma256Plan{false, 0, why, false}; };
+  if (mode != 1 && mode != 2 && !chain_dma256_mode_forced(mode)) return no("chains on the 256x256 tile are off (xsmm_hip_set_chain_dma256)");
+  if (b_kind == -2) return no("a chain on the 256x256 tile is bf16: an f32 call");
+  if (nlayers < 2 || nlayers > 8) return no("fewer than 2 or more than 8 calls");
+  if (!d256_image_ok(b_kind)) return no("the calls of a chain on the 256x256 tile share no B image (VNNI-2 / flat / VNNI-4, beta 0, on the tile's grid)");
+  if (m < D256C_BM || n < D256C_BN || m % D256C_BM != 0 || n % D256C_BN != 0) return no("256 does not divide a chain's m and n");
+  for (int l = 0; l < nlayers; ++l)
+    if (!d256c_k_ok(k[l], br[l])) return no("a layer of a chain on the 256x256 tile has k not in 32-k chunks, or an empty batch");
+  const int64_t tiles_m = m / D256C_BM, tiles_n = n / D256C_BN;
+  if (!d256c_shape_ok(m, n, nlayers, 8, 1)) return no("more tiles than a launch can count");
+  const int gmax = chain_rounds_max_groups((int)tiles_n, cus);
+  if (gmax < 1) return no("a row of tiles is wider than the compute units");
+  if (strict && !all_on_tile) return no("strict mode: one launch only where every call was dispatched on the 256x256 tile");
+  if (chain_dma256_mode_forced(mode)) {
+    const int64_t g = mode - 1000;
+    if (g < 1 || g > tiles_m || g * tiles_n > cus) return no("the forced row groups do not fit: 1 <= G <= tiles_m and G * tiles_n <= compute units");
+    return ChainDma256Plan{true, (int)g, "", false};
+  }
+  if (mode == 1 && !all_on_tile) return no("by rule only where every call runs on the 256x256 tile as a single call");
+  const int groups = tiles_m <= gmax ? (int)tiles_m : chain_rounds_groups((int)tiles_m, gmax);
+  if (mode == 1 && chain_dma256_gated(tiles_m, tiles_n, groups))
+    return ChainDma256Plan{true, groups, "gate: more than eight column tiles measured slower as one launch than call by call (profiles/chain_dma256_ab.txt)", true};
+  return ChainDma256Plan{true, groups, "", false};
 }
 
 static GemmLaunch launch(GemmLauncher l, int tile = 0, const char *text = "", int split = 1, int b_kind = 0, bool even = false) {

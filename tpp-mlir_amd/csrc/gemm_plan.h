@@ -263,6 +263,34 @@ int chain_widths_ragged_b_kind(const GemmDesc &d, int mode, const char **why);
 // why = the gate: the caller does not launch.
 struct ChainWidthsRaggedPlan { int tile; const char *why; bool gated; };
 ChainWidthsRaggedPlan plan_chain_widths_ragged(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, int b_kind, int mode, bool strict);
+// LAYER CHAINS ON THE 256x256 TILE (xsmm_hip_set_chain_dma256; rt_chain.h try_chain_launch, brgemm_bf16_dma256_chain.hip launch_bf16_dma256_chain,
+// maps in brgemm_bf16_dma256_chain.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_dma256.txt is the table of the answers.
+// One call of a chain: the B image (0 VNNI-2, 2 flat, 4 VNNI-4) it would have as a layer of this launch - bf16, beta 0, no VNNI C, not the
+// forced generic kernel, k in 32-k chunks, leading dimensions, strides and lane offsets on the tile's grid - or -1; -2: an f32 call.
+int chain_dma256_b_kind(const GemmDesc &d);
+// Does the call run on the 256x256 tile as a single call TODAY? VNNI-2: it was dispatched on V_BF16_DMA256 (by plan_gemm's rule, or forced).
+// Flat / VNNI-4: xsmm_hip_set_dma256_images (dma256_images, the only other mode this rule reads) is non-zero and plan_gemm_call's block
+// takes the call - planned, not forced, on a loader-wave tile of its image, 256 divides m and n, mode 2 or pick_bf16_tile's rule.
+bool chain_dma256_on_tile(const GemmDesc &d, int dma256_images);
+// The launch: m x n outputs per layer, nlayers layers of k[l] per batch element and br[l] batch elements, cus compute units on the stream,
+// all_on_tile = chain_dma256_on_tile of EVERY call, b_kind = the image every call has by chain_dma256_b_kind (-1: none or not one, -2: an
+// f32 call), mode = the switch's value, strict = xsmm_hip_set_strict. tiles_m = m / 256, tiles_n = n / 256.
+//   mode 1:        only where all_on_tile. Within the compute units: one round, groups = tiles_m. Otherwise Gmax = cus / tiles_n,
+//                  R = ceil(tiles_m / Gmax), G = ceil(tiles_m / R) (chain_rounds_groups).
+//   mode 2:        every eligible chain, groups as mode 1 (tests, measurements).
+//   mode 1000 + G: G row groups, also on a chain that fits: 1 <= G <= tiles_m and G * tiles_n <= cus.
+// take = false, groups = 0 and why = the reason: the switch off, an f32 call, fewer than 2 or more than 8 layers, no shared B image, 256
+// not dividing m or n, a k not in 32-k chunks or an empty batch, a row of tiles wider than the compute units, strict mode unless
+// all_on_tile (the launch then has the separate calls' bits: strict mode takes it), mode 1 without all_on_tile, a forced G that does not fit.
+// THE GATE (mode 1 only; measured, profiles/chain_dma256_ab.txt: three layers on 256 CUs, call by call -> one launch, us per step: 1024-wide
+// layers at 16384 rows 109.65 -> 108.56, at 32768 rows (R = 2) 214.65 -> 203.22, flat 110.19 -> 109.41, VNNI-4 109.20 -> 108.29; but 4096
+// rows x 4096-wide layers, 16 x 16 tiles, 334.03 -> 337.64 in every pair): a chain of MORE THAN EIGHT column tiles (n > 2048) stays call by
+// call. The answer then still names the plan, with gated = true and why = the gate: the caller does not launch. Modes 2 and 1000 + G
+// are never gated.
+struct ChainDma256Plan { bool take; int groups; const char *why; bool gated; };
+constexpr int CHAIN_DMA256_GATE_TILES_N = 8; // most column tiles mode 1 takes
+inline bool chain_dma256_mode_forced(int mode) { return mode > 1000; }
+ChainDma256Plan plan_chain_dma256(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, bool all_on_tile, int b_kind, int mode, bool strict);
 // 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none
 int f32_chain_tile(const GemmDesc &d);
 // tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip; BLW_TILES, brgemm_bf16_lw_launch.h)

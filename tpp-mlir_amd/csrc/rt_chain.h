@@ -181,7 +181,36 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   // whose rows divide m fits the compute units - a bf16 chain may still run as one launch on edge row tiles. `divisible` = the
   // rules as they are with the switch off still hold; edge_kind = the B image of the ragged launch, edge_why = why there is none.
   // With the switch off edge_on is false and every NOCHAIN below is taken exactly as before.
-  const int chain_edge = g_chain_edge.load(std::memory_order_relaxed);
+  // ON THE 256x256 TILE (xsmm_hip_set_chain_dma256, opt-in; gemm_plan.cpp plan_chain_dma256, brgemm_bf16_dma256_chain.hip): asked FIRST, and
+  // only with the switch non-zero. The rule sees the calls' shapes, their shared B image (chain_dma256_b_kind) and whether every call runs
+  // on that tile as a single call (chain_dma256_on_tile; mode 1 reads xsmm_hip_set_dma256_images for it, nothing else reads another mode).
+  // d256 = the launch is that tile's chain kernel on d256_groups row groups: the shape terms of the loader-wave chain below are the
+  // rule's then and no other chain switch is looked at; everything the chain contract asks of the operands is checked as for every
+  // launch, and blocks, targets, probation and the journal are the same. Where the rule refuses or gates, or the mode is 0, d256 is false
+  // and every decision below is exactly what it is without this switch.
+  const int dma256_mode = g_chain_dma256.load(std::memory_order_relaxed);
+  int d256_groups = 0, d256_kind = -1;
+  if (dma256_mode) {
+    const char *w = "the calls differ in m or n, or a batch is empty";
+    const int images = dma256_mode == 1 ? g_dma256_images.load(std::memory_order_relaxed) : 0;
+    bool same = true, on_tile = true;
+    d256_kind = chain_dma256_b_kind(*d[0]);
+    int64_t ks[CH_MAXL], brs[CH_MAXL];
+    for (int i = 0; i < n; ++i) {
+      if (d[i]->m != m || d[i]->n != nn || br[i] < 1) same = false;
+      if (d256_kind != -2 && chain_dma256_b_kind(*d[i]) != d256_kind) d256_kind = chain_dma256_b_kind(*d[i]) == -2 ? -2 : -1;
+      on_tile = on_tile && chain_dma256_on_tile(*d[i], images);
+      ks[i] = d[i]->k, brs[i] = br[i];
+    }
+    if (same) {
+      const ChainDma256Plan dp = plan_chain_dma256(m, nn, n, ks, brs, stream_cus(s), on_tile, d256_kind, dma256_mode, cfg().strict.load(std::memory_order_relaxed));
+      w = dp.why;
+      if (dp.take && !dp.gated) d256_groups = dp.groups; // (gated: the rule's answer is on record in why, nothing is launched)
+    }
+    if (!d256_groups && cfg().trace) fprintf(stderr, "[tpp-xsmm-hip] fused_brgemm_chain: no launch on the 256x256 tile (%s)\n", w);
+  }
+  const bool d256 = d256_groups > 0;
+  const int chain_edge = d256 ? 0 : g_chain_edge.load(std::memory_order_relaxed);
   const bool edge_on = !f32 && chain_edge != 0;
   bool divisible = true;
   const char *edge_why = nullptr;
@@ -190,7 +219,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   // divisible chain but the last one - more tiles than compute units - may run as one launch on G resident row groups. The rule is asked
   // only where the rules below say "more tiles than compute units" - of the tile all calls were planned on, or of every tile -, a
   // forced G (mode 1000 + G) in front of them. With the switch off rounds_mode is 0 and every NOCHAIN below is taken exactly as before.
-  const int rounds_mode = f32 ? 0 : g_chain_rounds.load(std::memory_order_relaxed);
+  const int rounds_mode = f32 || d256 ? 0 : g_chain_rounds.load(std::memory_order_relaxed);
   int groups = 0; // > 0: the multi-round launch on that many row groups
   const char *rounds_why = nullptr;
   // A forced G is asked in front of the one-round rules, so also in front of their m and n terms (bf16_lw_b_kind: 64 rows for VNNI-2):
@@ -206,7 +235,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   // k % 64), plan_chain_edge's refusal (n not in whole column tiles). ragged_w() is the rule's answer, asked at most once: every call
   // passes chain_ragged_b_kind with the same B image and plan_chain_ragged names a tile. ragw = the launch is the ragged-width one. With
   // the switch off ragged_w() is false without a look at the calls and every NOCHAIN below is taken exactly as before.
-  const int chain_ragged = f32 ? 0 : g_chain_ragged.load(std::memory_order_relaxed);
+  const int chain_ragged = f32 || d256 ? 0 : g_chain_ragged.load(std::memory_order_relaxed);
   int ragw_state = chain_ragged ? -1 : 0, ragw_tile = -1, ragw_kind = -1; // -1 not asked yet, 0 no, 1 yes
   bool ragw = false;
   auto ragged_w = [&]() {
@@ -235,12 +264,12 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   // bf16_lw_b_kind - the terms of the divisible chain, which every call must ALSO pass in the loop below (a ragged call ends the launch:
   // `divisible`) -, the same m and a batch, and plan_chain_widths names a tile. widw = the launch is the mixed-width one. With the
   // switch off widths_w() is false without a look at the calls and the NOCHAIN is taken exactly as before.
-  const int chain_widths = f32 ? 0 : g_chain_widths.load(std::memory_order_relaxed);
+  const int chain_widths = f32 || d256 ? 0 : g_chain_widths.load(std::memory_order_relaxed);
   // COLUMN ROUNDS (xsmm_hip_set_chain_width_rounds, opt-in; gemm_plan.cpp plan_chain_width_rounds): the same question about the same calls,
   // answered inside widths_w(): a forced W (1000 + W) in front of plan_chain_widths, the rule (1) where plan_chain_widths refuses or gates
   // or its switch is off. widw_groups > 0 = the launch is the column-round one on that many workgroup columns. With both switches off
   // widths_w() is false without a look at the calls.
-  const int width_rounds = f32 ? 0 : g_chain_width_rounds.load(std::memory_order_relaxed);
+  const int width_rounds = f32 || d256 ? 0 : g_chain_width_rounds.load(std::memory_order_relaxed);
   int widw_state = chain_widths || width_rounds ? -1 : 0, widw_tile = -1, widw_kind = -1, widw_groups = 0; // -1 not asked yet, 0 no, 1 yes
   bool widw = false;
   auto widths_w = [&]() {
@@ -292,7 +321,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   // image, has the same m and a batch, and plan_chain_widths_ragged names a tile without a gate. wragw = the launch is the ragged mixed-width
   // one: the shape terms below are the rule's then, everything else the chain contract asks is checked as for every launch. With the
   // switch off wragged_w() is false without a look at the calls and every NOCHAIN below is taken exactly as before.
-  const int chain_wragged = f32 ? 0 : g_chain_widths_ragged.load(std::memory_order_relaxed);
+  const int chain_wragged = f32 || d256 ? 0 : g_chain_widths_ragged.load(std::memory_order_relaxed);
   int wragw_state = chain_wragged ? -1 : 0, wragw_tile = -1, wragw_kind = -1; // -1 not asked yet, 0 no, 1 yes
   bool wragw = false;
   auto wragged_w = [&]() {
@@ -330,6 +359,8 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
         NOCHAIN("an f32 call is not beta 0 / not planned on the K-split loader-wave tile of the first call");
       if (g.bias && ((uintptr_t)pd[i] & 15)) NOCHAIN("an f32 bias operand is not 16-byte aligned");
       if (g.ldc & 3) NOCHAIN("an f32 output's leading dimension is not a multiple of 4");
+    } else if (d256) {
+      // (the 256x256 tile's chain: bf16, beta 0, one B image, k in 32-k chunks - plan_chain_dma256 has asked)
     } else
     // every layer the same kind of B operand (VNNI-2, flat or VNNI-4: the B image is a template parameter of the launch)
     if (g.dtype != DT_BF16 || g.vnni_c || !g.beta0 || bf16_lw_b_kind(g) < 0 || bf16_lw_b_kind(g) != bf16_lw_b_kind(*d[0])) {
@@ -345,7 +376,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
       if (widw_state == 1) widw = true;
       else wragw = true; // (the mixed-width rules do not take the chain, the ragged mixed-width rule does)
     }
-    if (g.variant == V_GENERIC) { // (a forced generic kernel stays generic; one that is generic only because no tile divides m may run ragged)
+    if (g.variant == V_GENERIC && !d256) { // (a forced generic kernel stays generic; one that is generic only because no tile divides m may run ragged)
       if ((!edge_on || edge_why || g.generic_forced) && !ragw && !wragw) {
         if (!g.generic_forced && ragged_w()) ragw = true;
         else if (!g.generic_forced && wragged_w()) wragw = true;
@@ -402,7 +433,12 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     else NOCHAIN("the calls differ in n and one of them is ragged: different widths combine with no other chain mode");
   }
   if (wragw) widw = ragw = false; // (one launch form: the ragged mixed-width one)
-  if (divisible && !widw && !wragw) {
+  if (d256) { // the 256x256 tile's chain kernel: no loader-wave tile is chosen (bm = bn = 256 below)
+    tile = 3;
+    b_kind = d256_kind;
+    groups = 0;
+  }
+  if (divisible && !widw && !wragw && !d256) {
     // (variants 20 .. 23 VNNI-2, 24 .. 27 flat B, 28 .. 31 VNNI-4: the same four tiles)
     const int planned = blw_variant_tile(d[0]->variant, b_kind);
     bool same = !f32 && planned >= 0 && planned < 4;
@@ -460,6 +496,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   }
   if (f32) (void)f32_chain_tile_dims(tile, &bm, &bn); // bm, bn of the chosen tile
   else blw_tile_dims(tile, &bm, &bn);
+  if (d256) bm = bn = D256C_BM;
   // no operand of the launch may overlap an output (a layer's input rows are read by other workgroups while later layers store)
   Operand A, B, C, D;
   struct Span { const void *p; size_t n; };
@@ -547,6 +584,14 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   c.target = ++blk.epoch * (unsigned)blk.tiles_n;
   if (widw || wragw) c.target = blk.epoch; // (the kernel multiplies by the producing layer's column tiles: chain_widths_target / chain_wragged_target)
   if (f32) HIP_OK(launch_f32_chain(tile, c, s));
+  else if (d256) {
+    c.groups = d256_groups;
+    HIP_OK(launch_bf16_dma256_chain(b_kind, c, s));
+    g_chain_dma256_stats[1].store(d256_groups, std::memory_order_relaxed);
+    g_chain_dma256_stats[2].store(chain_rounds_rounds((int)(m / bm), d256_groups), std::memory_order_relaxed);
+    g_chain_dma256_stats[3].store(b_kind, std::memory_order_relaxed);
+    g_chain_dma256_stats[0].fetch_add(1, std::memory_order_relaxed);
+  }
   else if (wragw) {
     HIP_OK(launch_bf16_chain_wragged(tile, b_kind, c, s));
     g_chain_widths_ragged_stats[1].store((m + bm - 1) / bm, std::memory_order_relaxed);

@@ -13,6 +13,7 @@
 #include "../../include/tpp_xsmm_abi.h"
 #include "xsmm_desc.h"
 #include "chain_args.h"
+#include "brgemm_bf16_dma256_chain.h" // D256C_BM, chain_rounds_rounds (rt_chain.h)
 #include "gemm_plan.h"
 #include "host_cache.h"
 #include "rt_relayout.h" // relayout grids: affine runs of a recorded pack / unpack group (plain C++, outside the unit namespace)
@@ -81,6 +82,13 @@ __attribute__((weak)) int chain_widths_ragged_b_kind(const GemmDesc &, int, cons
 }
 __attribute__((weak)) ChainWidthsRaggedPlan plan_chain_widths_ragged(int64_t, int, const int64_t *, const int64_t *, const int64_t *, int64_t, int, int, int, bool) {
   return ChainWidthsRaggedPlan{-1, "this build has no ragged mixed-width planner", false};
+}
+// (chains on the 256x256 tile, xsmm_hip_set_chain_dma256: the same arrangement - brgemm_bf16_dma256_chain.hip)
+__attribute__((weak)) hipError_t launch_bf16_dma256_chain(int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
+__attribute__((weak)) int chain_dma256_b_kind(const GemmDesc &) { return -1; }
+__attribute__((weak)) bool chain_dma256_on_tile(const GemmDesc &, int) { return false; }
+__attribute__((weak)) ChainDma256Plan plan_chain_dma256(int64_t, int64_t, int, const int64_t *, const int64_t *, int64_t, bool, int, int, bool) {
+  return ChainDma256Plan{false, 0, "this build has no planner of chains on the 256x256 tile", false};
 }
 // (multi-round chains, xsmm_hip_set_chain_rounds: the same arrangement)
 __attribute__((weak)) int chain_rounds_planned_tile(int, const GemmDesc *const *) { return -1; }
@@ -624,6 +632,10 @@ extern "C" void xsmm_hip_chain_width_rounds_stats(int64_t out[4]) {
 extern "C" int xsmm_hip_set_chain_widths_ragged(int mode) { return tpp::chain_widths_ragged_mode_ok(mode) ? tpp::g_chain_widths_ragged.exchange(mode) : -1; }
 extern "C" void xsmm_hip_chain_widths_ragged_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_widths_ragged_stats[i].load(std::memory_order_relaxed);
+}
+extern "C" int xsmm_hip_set_chain_dma256(int mode) { return tpp::chain_dma256_mode_ok(mode) ? tpp::g_chain_dma256.exchange(mode) : -1; }
+extern "C" void xsmm_hip_chain_dma256_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_dma256_stats[i].load(std::memory_order_relaxed);
 }
 extern "C" int xsmm_hip_set_chain_rounds(int mode) { return tpp::chain_rounds_mode_ok(mode) ? tpp::g_chain_rounds.exchange(mode) : -1; }
 extern "C" void xsmm_hip_chain_rounds_stats(int64_t out[4]) {

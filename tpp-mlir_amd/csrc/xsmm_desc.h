@@ -279,6 +279,18 @@ inline std::atomic<int> g_chain_widths_ragged{[] {
   return chain_widths_ragged_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_chain_widths_ragged_stats[4]; // ragged mixed-width launches; row blocks, the widest layer's column tiles (both ceil-divided), GemmVariant of the tile (with its B image) of the latest
+// LAYER CHAINS ON THE 256x256 bf16 TILE (xsmm_hip_set_chain_dma256 / TPP_HIP_CHAIN_DMA256; gemm_plan.cpp plan_chain_dma256, rt_chain.h
+// try_chain_launch, brgemm_bf16_dma256_chain.hip, brgemm_bf16_dma256_chain.h): 0 = off, 1 = a bf16 chain every call of which runs on the 256x256
+// tile as a single call runs as one launch of that tile's chain kernel (the rule and its gate), 2 = every eligible chain (tests,
+// measurements), 1000 + G = every eligible chain on G row groups. A switch of its own: no other switch reads it, and it reads no other
+// mode but xsmm_hip_set_dma256_images' in mode 1 (which calls run on the tile).
+inline bool chain_dma256_mode_ok(int v) { return v == 0 || v == 1 || v == 2 || (v > 1000 && v <= 1000 + 0x10000); }
+inline std::atomic<int> g_chain_dma256{[] {
+  const char *e = getenv("TPP_HIP_CHAIN_DMA256");
+  const int v = e ? atoi(e) : 0;
+  return chain_dma256_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_chain_dma256_stats[4]; // such launches; resident row groups G (tiles_m in one round), rounds R, B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

@@ -125,6 +125,8 @@ _SIGNATURES = {
     "xsmm_hip_dma256_images_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_dma256_edge": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_dma256_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_chain_dma256": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_chain_dma256_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_f32_halves": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_f32_halves_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
@@ -441,6 +443,18 @@ class XsmmRuntime:
         """(edge-tile launches on the 256x256 tile; tile rows, tile columns, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_dma256_edge_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_chain_dma256(self, mode):
+        """bf16 layer chains whose calls run on the 256x256 tile (256 dividing m and n, k % 32 == 0) as one launch of that tile's chain
+        kernel (the same bits): 0 off (default), 1 the rule (every call runs on that tile today; gated as measured), 2 every eligible
+        chain, 1000 + G on G row groups; returns the previous mode, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_chain_dma256(mode)
+
+    def chain_dma256_stats(self):
+        """(chain launches on the 256x256 tile; resident row groups G, rounds, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_chain_dma256_stats(out)
         return tuple(int(v) for v in out)
 
     def set_f32_halves(self, mode):
