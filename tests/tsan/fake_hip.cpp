@@ -3,100 +3,14 @@
 // runtime.cpp (the C-ABI layer: tile queue, multi-producer ring, scheduler thread, host-operand mirroring) is
 // compiled unchanged with g++ -fsanitize=thread and linked against THIS file instead of libamdhip64 and the
 // gfx950 kernels, so that ThreadSanitizer can watch the host-side concurrency on a machine without a GPU:
-//   * the 17 HIP host entry points runtime.cpp uses, over plain host memory ("device" allocations are
-//     malloc'd blocks kept in a table so that hipPointerGetAttributes / hipMemGetAddressRange answer like
-//     the driver); streams are in-order and every operation completes before its call returns;
+//   * the HIP host entry points runtime.cpp uses, over plain host memory: fake_hip_host.h, shared with the host
+//     build of the layer-chain launch decision (tests/chain_dispatch/fake_chain.cpp);
 //   * the 7 launch / plan functions of xsmm_desc.h as scalar f32 loops executed on the launching thread
 //     (so a launch that touches bytes another thread is using IS a data race TSAN reports).
 #include "../../tpp-mlir_amd/csrc/xsmm_desc.h"
 #include "../../tpp-mlir_amd/csrc/chain_args.h"
 #include "../../tpp-mlir_amd/csrc/gemm_plan.h"
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
-
-namespace {
-std::mutex g_mu;
-std::map<uintptr_t, size_t> g_dev; // base -> size of live "device" allocations
-bool find_alloc(const void *p, uintptr_t *base, size_t *size) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  auto it = g_dev.upper_bound((uintptr_t)p);
-  if (it == g_dev.begin()) return false;
-  --it;
-  if ((uintptr_t)p >= it->first + it->second) return false;
-  *base = it->first;
-  *size = it->second;
-  return true;
-}
-} // namespace
-
-extern "C" {
-hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
-hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
-hipError_t hipSetDevice(int) { return hipSuccess; }
-hipError_t hipGetLastError(void) { return hipSuccess; }
-const char *hipGetErrorString(hipError_t) { return "fake hip error"; }
-hipError_t hipMalloc(void **p, size_t bytes) {
-  *p = aligned_alloc(256, (bytes + 255) & ~(size_t)255);
-  if (!*p) return hipErrorOutOfMemory;
-  std::lock_guard<std::mutex> lk(g_mu);
-  g_dev[(uintptr_t)*p] = bytes;
-  return hipSuccess;
-}
-hipError_t hipFree(void *p) {
-  if (!p) return hipSuccess;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    g_dev.erase((uintptr_t)p);
-  }
-  free(p);
-  return hipSuccess;
-}
-hipError_t hipHostMalloc(void **p, size_t bytes, unsigned int) {
-  *p = aligned_alloc(256, (bytes + 255) & ~(size_t)255);
-  return *p ? hipSuccess : hipErrorOutOfMemory;
-}
-hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
-hipError_t hipPointerGetAttributes(hipPointerAttribute_t *attr, const void *p) {
-  uintptr_t base;
-  size_t size;
-  if (!find_alloc(p, &base, &size)) return hipErrorInvalidValue; // plain host memory
-  memset(attr, 0, sizeof(*attr));
-  attr->type = hipMemoryTypeDevice;
-  attr->devicePointer = (void *)p;
-  return hipSuccess;
-}
-hipError_t hipMemGetAddressRange(hipDeviceptr_t *base, size_t *size, hipDeviceptr_t p) {
-  uintptr_t b;
-  size_t s;
-  if (!find_alloc((const void *)p, &b, &s)) return hipErrorInvalidValue;
-  *base = (hipDeviceptr_t)b;
-  *size = s;
-  return hipSuccess;
-}
-hipError_t hipMemcpy(void *dst, const void *src, size_t bytes, hipMemcpyKind) {
-  memcpy(dst, src, bytes);
-  return hipSuccess;
-}
-hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind, hipStream_t) {
-  memcpy(dst, src, bytes);
-  return hipSuccess;
-}
-hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height,
-                            hipMemcpyKind, hipStream_t) {
-  for (size_t r = 0; r < height; ++r) memcpy((char *)dst + r * dpitch, (const char *)src + r * spitch, width);
-  return hipSuccess;
-}
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus *s) { *s = hipStreamCaptureStatusNone; return hipSuccess; }
-hipError_t hipExtStreamGetCUMask(hipStream_t, uint32_t n, uint32_t *m) { for (uint32_t i = 0; i < n; ++i) m[i] = i < 8 ? 0xffffffffu : 0u; return hipSuccess; }
-hipError_t hipMemset(void *p, int v, size_t bytes) { memset(p, v, bytes); return hipSuccess; }
-hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) { *v = 256; return hipSuccess; }
-hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = nullptr; return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
-}
+#include "fake_hip_host.h"
 
 namespace tpp {
 
@@ -126,7 +40,9 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A_, const void *B_, void *
     }
   return hipSuccess;
 }
-// the bf16 chain kernel has no host stand-in: plan_gemm above refuses bf16, so try_chain_launch never gets this far
+// THIS build never reaches a bf16 chain launch: plan_gemm above refuses bf16 and runtime.cpp's weak planner stand-ins refuse every chain,
+// so try_chain_launch ends at its first rule. The host build that runs it to the end - the real gemm_plan.cpp, computing and recording
+// stand-ins of all nine launch forms - is tests/chain_dispatch/fake_chain.cpp (tests/test_chain_dispatch.py).
 int bf16_lw_b_kind(const GemmDesc &) { return -1; }
 void blw_tile_dims(int, int *bm, int *bn) { *bm = *bn = 128; }
 hipError_t launch_bf16_chain(int, int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }

@@ -428,6 +428,18 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (tile >= 0) b_kind = rounds_kind;
     else if (!edge_on || edge_why) NOCHAIN(rounds_why);
   }
+  // the one-round ragged-m rule's answer, asked at most once (only with xsmm_hip_set_chain_edge on and every call passing chain_edge_b_kind)
+  ChainEdgePlan edge_plan{-1, nullptr};
+  bool edge_asked = false;
+  auto ask_edge = [&]() -> const ChainEdgePlan & {
+    if (edge_asked) return edge_plan;
+    edge_asked = true;
+    int64_t ks[CH_MAXL], brs[CH_MAXL];
+    for (int i = 0; i < n; ++i) ks[i] = d[i]->k, brs[i] = br[i];
+    const int et = g_edge_tiles.load(std::memory_order_relaxed);
+    edge_plan = plan_chain_edge(m, nn, n, ks, brs, cus, et >= V_BF16_LW_32x64 && et <= V_BF16_LW_128x128 ? et - V_BF16_LW_32x64 : -1, strict);
+    return edge_plan;
+  };
   if (widw && !wragw && (!divisible || ragw)) {
     if (wragged_w()) wragw = true; // (the rule of the combination, asked instead of the refusal - only with its switch on)
     else NOCHAIN("the calls differ in n and one of them is ragged: different widths combine with no other chain mode");
@@ -448,8 +460,11 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     if (chain_rounds_mode_forced(rounds_mode)) ask_rounds(); // (a forced G that does not fit: everything below as with the switch off)
     if (tile < 0 && same && fits(planned)) tile = planned;
     // the tile all calls were planned on has more tiles than compute units: several rounds on THAT tile - the descriptors' own, G
-    // changes no bit, so strict mode takes it too - in front of one round on another tile, whose bits need not be the calls'
-    if (tile < 0 && rounds_mode == 1 && same) ask_rounds();
+    // changes no bit, so strict mode takes it too - in front of one round on another tile, whose bits need not be the calls'. Not where
+    // the one-round ragged launch applies (xsmm_hip_set_chain_edge on, a tile of other rows fits on its ceil-divided grid): the two
+    // switches never combine, and there the ragged launch wins - 32 * 257 rows x 64 of flat B, planned on 32x64 (257 tiles), run as 129
+    // edge row blocks of 64x64 with both switches on as with xsmm_hip_set_chain_edge alone (tests/test_chain_dispatch.py found the rounds)
+    if (tile < 0 && rounds_mode == 1 && same && !(edge_on && !edge_why && ask_edge().tile >= 0)) ask_rounds();
     if (tile < 0 && strict) NOCHAIN(rounds_why && rounds_mode == 1 ? rounds_why : "strict mode: one launch only on the tile the layers were planned on");
     for (int t = 0; t < 4 && tile < 0; ++t)
       if (fits(t)) tile = t;
@@ -474,10 +489,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   bool ragged = tile < 0; // (only with a switch on: every path to here with both off has a tile)
   if (ragged) {
     // the ragged launch: the tile a forcing edge-tile mode names if it fits, else the smallest that fits - counted on the ceil-divided grid
-    int64_t ks[CH_MAXL], brs[CH_MAXL];
-    for (int i = 0; i < n; ++i) ks[i] = d[i]->k, brs[i] = br[i];
-    const int et = g_edge_tiles.load(std::memory_order_relaxed);
-    const ChainEdgePlan ep = plan_chain_edge(m, nn, n, ks, brs, cus, et >= V_BF16_LW_32x64 && et <= V_BF16_LW_128x128 ? et - V_BF16_LW_32x64 : -1, strict);
+    const ChainEdgePlan &ep = ask_edge();
     if (ep.tile >= 0) {
       tile = ep.tile;
       b_kind = edge_kind;

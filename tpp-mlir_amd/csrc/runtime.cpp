@@ -41,11 +41,15 @@
 
 using namespace tpp;
 
-// Ragged-m chains (rt_chain.h try_chain_launch; xsmm_hip_set_chain_edge): the planner's two functions live in gemm_plan.cpp. The host-only
-// builds of this file (tests/tsan and its kin) do not link it - their kernel stand-ins predate the switch -, so WEAK stand-ins that
-// refuse are defined here: the library's link takes the real definitions, a host-only build these. The chain launcher with its mode
-// (chain_args.h; brgemm_bf16_lw.hip) has ONE such stand-in for the same reason: a host-only build whose own stand-in still has the
-// launcher's earlier signature links, and refuses every bf16 chain.
+// The chain planners (gemm_plan.cpp: chain_*_b_kind, plan_chain_*, chain_rounds_planned_tile, chain_dma256_on_tile) and the chain launchers
+// (chain_args.h; the brgemm_bf16_lw*.hip files, brgemm_bf16_dma256_chain.hip) that rt_chain.h try_chain_launch calls have WEAK stand-ins that
+// refuse here. The library's link takes the real definitions. So does ONE of the two host-only builds of this file:
+//  * tests/tsan/fake_hip.cpp (the sanitizer, host-cache and epilogue-fold drivers) links neither gemm_plan.cpp nor any kernel file - its
+//    kernel stand-ins predate the chain switches and plan every bf16 descriptor away -, takes these stand-ins and refuses every bf16 chain
+//    at the first rule;
+//  * tests/chain_dispatch/fake_chain.cpp (tests/test_chain_dispatch.py) links the real gemm_plan.cpp and defines every launcher itself
+//    (computing through the oracle, recording, with a model of the hand-off counters): there try_chain_launch runs to the end, under
+//    every combination of the switches, on a CPU.
 namespace tpp {
 __attribute__((weak)) hipError_t launch_bf16_chain(int, int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 __attribute__((weak)) int chain_edge_b_kind(const GemmDesc &, int, const char **why) {
