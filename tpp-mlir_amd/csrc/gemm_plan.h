@@ -105,7 +105,10 @@ struct GemmLaunch {
 
 // fills d.variant / d.name / d.generic_forced / d.variant_forced; returns false if no kernel can run the descriptor
 bool plan_gemm(GemmDesc &d, int forced_variant, const GemmPlanEnv &env);
-// one invoke of a planned descriptor with batch count br (launch_gemm)
+// one invoke of a planned descriptor with batch count br (launch_gemm). The refinements in order of precedence, each with the switches it reads
+// besides the descriptor, the call, the CU count and forced_split - pinned under every switch set by tests/test_gemm_call_switches.py: dma256 edge
+// {dma256_edge}, bf16 edge tiles {edge_tiles}, bf16 ragged k {edge_k_bf16, edge_tiles}, half-step ragged k {edge_k8_bf16, edge_tiles}, dma256 images
+// {dma256_images}, f32 edge tiles {edge_tiles}, f32 ragged k {edge_k, edge_tiles}, tail split {tail_split}, halves {halves}; plan_gemm reads none.
 GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br, const GemmAlign &al, const GemmPlanEnv &env);
 // n_items invokes of one descriptor in one launch (launch_gemm_grouped; vec_ok / out_ok / pair_ok / br_hint as there)
 GemmLaunch plan_gemm_group(const GemmDesc &d, int n_items, bool vec_ok, bool out_ok, bool pair_ok, int64_t br_hint, const GemmPlanEnv &env);
