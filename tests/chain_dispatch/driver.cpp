@@ -14,6 +14,7 @@
 //   driver probation <form>   the first launch of a block is starved (e)         - a process of its own: the shared flag is sticky
 //   driver journal            a journaled launch is starved after a verified one (e)
 //   driver sanitize           the 1- / 2- / 8- / 9-call chains and one chain per form, decisions and arithmetic (g: built with sanitizers)
+//   driver cus                how often a chain invoke asks for its stream's compute units: D({}), the seven D({x}) and D(all)   (check h)
 // Exit code 0 and a last line "OK" = every check passed.
 #include "../../include/tpp_xsmm_abi.h"
 #include "../../tpp-mlir_amd/csrc/gemm_plan.h"
@@ -770,6 +771,47 @@ int run_sanitize() {
   }
   return run_arith(false);
 }
+
+// ---- check h: the stream's compute units are asked for at most once per chain invoke ----------------------------------------------
+// (three runtime calls behind every question: hipExtStreamGetCUMask counts them.) Never where the chain contract refuses - the call count,
+// a call that does not read its predecessor's output, a row-striding batch, a misaligned or a host operand: those are checked in front of
+// the decision (two outputs that overlap are found behind it) -, and never where column rounds by rule are asked about calls that differ
+// in n and share no tile they were all dispatched on, with the mixed-width switch off: that answer needs no compute units.
+int run_cus() {
+  fake_chain_set_compute(0);
+  long invokes = 0, asked = 0, contract = 0, gated = 0;
+  for (const Spec &s : lattice())
+    for (int image : IMAGES) {
+      if (s.f32_variant && image != 0) continue;
+      Chain ch = build(s, image, false);
+      const bool by_contract = ch.n < 2 || ch.n > 8 || s.quirk == Q_ROW_STRIDE || s.quirk == Q_NOT_A_CHAIN || s.quirk == Q_MISALIGNED_B ||
+                               s.quirk == Q_MISALIGNED_BIAS || s.quirk == Q_HOST_OPERAND;
+      bool differ_n = false;
+      for (int i = 1; i < ch.n; ++i) differ_n = differ_n || ch.nl[i] != ch.nl[0];
+      for (int i = -1; i <= SW_N; ++i) {
+        apply(CTXS[0], i < 0 ? 0u : i == SW_N ? 127u : 1u << i);
+        char what[200];
+        snprintf(what, sizeof(what), "%s %s set %s", s.name, image_name(ch.image), i < 0 ? "{}" : i == SW_N ? "all" : SW_NAME[i]);
+        const long before = fake_hip_cu_mask_queries();
+        const Decision d = invoke(ch, what);
+        const long q = fake_hip_cu_mask_queries() - before;
+        ++invokes, asked += q;
+        if (q > 1) FAIL("COMPUTE UNITS: %s: asked %ld times in one invoke (%s)", what, q, d.text.c_str());
+        if (by_contract && ++contract && q) FAIL("COMPUTE UNITS: %s: the chain contract refuses the chain, yet the compute units were asked for", what);
+        if (i == SW_WROUNDS && differ_n && d.form < 0 && fake_gemm_launches() == ch.n && ch.n <= 8) {
+          const tpp::GemmDesc *descs[8];
+          for (int l = 0; l < ch.n; ++l) descs[l] = fake_gemm_launch(l)->d;
+          if (tpp::chain_rounds_planned_tile(ch.n, descs) < 0 && ++gated && q)
+            FAIL("COMPUTE UNITS: %s: column rounds by rule without a tile all calls were dispatched on, yet the compute units were asked for", what);
+        }
+      }
+      all_off();
+      destroy(ch);
+    }
+  printf("cus: %ld invokes asked %ld times, %ld invokes refused by the contract and %ld gated column-round invokes asked 0 times\n", invokes, asked, contract, gated);
+  if (!contract || !gated) FAIL("COMPUTE UNITS: no contract-refused or no gated column-round chain in the lattice");
+  return 0;
+}
 } // namespace
 
 int main(int argc, char **argv) {
@@ -787,8 +829,9 @@ int main(int argc, char **argv) {
   else if (!strcmp(mode, "probation")) run_probation(argc > 2 ? atoi(argv[2]) : 0);
   else if (!strcmp(mode, "journal")) run_journal();
   else if (!strcmp(mode, "sanitize")) run_sanitize();
+  else if (!strcmp(mode, "cus")) run_cus();
   else {
-    fprintf(stderr, "usage: driver table|sweep [strict [images]] | arith | sequence | probation <form> | journal | sanitize\n");
+    fprintf(stderr, "usage: driver table|sweep [strict [images]] | arith | sequence | probation <form> | journal | sanitize | cus\n");
     return 2;
   }
   if (fake_chain_counter_mismatches()) FAIL("COUNTER MODEL: %d mismatches", fake_chain_counter_mismatches());

@@ -39,4 +39,5 @@ void fake_chain_set_compute(int on);    // 0: the stand-ins record and count, an
 void fake_chain_starve(int nth, int layer); // the nth chain launch from now (1 = the next) writes 1 + layer into its error word and stores nothing
 int fake_chain_counter_mismatches(void); // seams at which a counter did not hold expected_after - arrivals, or lay outside its block
 int fake_hip_compute_units(void);
+long fake_hip_cu_mask_queries(void);     // calls of hipExtStreamGetCUMask so far (tests/tsan/fake_hip_host.h): how often the stream's compute units were asked for
 }

@@ -152,6 +152,19 @@ def test_a_starved_journaled_launch_and_its_successor_are_rerun_in_order(driver)
 
 
 @pytest.mark.timeout(600)
+def test_a_chain_invoke_asks_for_the_compute_units_at_most_once(driver):
+    """h  the stream's compute units cost three runtime calls per question (hipExtStreamGetCUMask is counted): for every chain of the
+    lattice under D({}), each D({x}) and D(all), at most one question per invoke, none where the chain contract refuses, none where
+    column rounds by rule meet calls that share no tile they were all dispatched on (the mixed-width switch off)."""
+    rc, out, err = run(driver, ["cus"])
+    print(out[-1500:])
+    passed(rc, out, err)
+    line = [l for l in out.splitlines() if l.startswith("cus:")][0].split()
+    invokes, asked, contract, gated = int(line[1]), int(line[4]), int(line[6]), int(line[13])
+    assert 0 < asked <= invokes and contract > 0 and gated > 0, line
+
+
+@pytest.mark.timeout(600)
 def test_driver_under_asan_and_ubsan(tmp_path):
     """the same unchanged sources as a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer, as test_tsan_scheduler.py
     builds its own: the 1- / 2- / 8- / 9-call chains and one computing chain per form. Leak detection off: handles and counter blocks

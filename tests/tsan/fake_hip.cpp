@@ -40,18 +40,14 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A_, const void *B_, void *
     }
   return hipSuccess;
 }
-// THIS build never reaches a bf16 chain launch: plan_gemm above refuses bf16 and runtime.cpp's weak planner stand-ins refuse every chain,
-// so try_chain_launch ends at its first rule. The host build that runs it to the end - the real gemm_plan.cpp, computing and recording
+// THIS build never reaches a chain launch: plan_gemm above refuses bf16 and runtime.cpp's weak stand-in of plan_chain refuses every chain,
+// so try_chain_launch ends behind the chain contract. The host build that runs it to the end - the real gemm_plan.cpp, computing and recording
 // stand-ins of all nine launch forms - is tests/chain_dispatch/fake_chain.cpp (tests/test_chain_dispatch.py).
-int bf16_lw_b_kind(const GemmDesc &) { return -1; }
-void blw_tile_dims(int, int *bm, int *bn) { *bm = *bn = 128; }
 hipError_t launch_bf16_chain(int, int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
-int f32_chain_tile(const GemmDesc &) { return -1; }
 int force_gemm_split(int) { return -1; }
 static bool g_fake_strict = false;
 int set_strict_kernels(int on) { const int prev = g_fake_strict; g_fake_strict = on != 0; return prev; }
 bool strict_kernels() { return g_fake_strict; }
-bool f32_chain_tile_dims(int, int *bm, int *bn) { *bm = *bn = 64; return false; }
 hipError_t launch_f32_chain(int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 const char *last_grouped_kernel() { return "fake_host_gemm"; }
 const char *last_refined_kernel() { return ""; }

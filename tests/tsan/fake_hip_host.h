@@ -5,8 +5,10 @@
 //   * "device" allocations are malloc'd blocks kept in a table so that hipPointerGetAttributes / hipMemGetAddressRange answer like
 //     the driver; streams are in-order and every operation completes before its call returns;
 //   * the device has FAKE_HIP_CUS compute units (default 256): hipDeviceGetAttribute answers it, and the CU mask of every stream
-//     has that many bits.
+//     has that many bits. fake_hip_cu_mask_queries() counts the calls of hipExtStreamGetCUMask (how often a host path asked for a
+//     stream's compute units).
 #pragma once
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -33,6 +35,7 @@ int fake_hip_cus() { // compute units of the fake device
   }();
   return cus;
 }
+std::atomic<long> g_cu_mask_queries{0};
 } // namespace
 
 extern "C" {
@@ -94,7 +97,9 @@ hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t sp
 }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus *s) { *s = hipStreamCaptureStatusNone; return hipSuccess; }
+long fake_hip_cu_mask_queries(void) { return g_cu_mask_queries.load(std::memory_order_relaxed); }
 hipError_t hipExtStreamGetCUMask(hipStream_t, uint32_t n, uint32_t *m) {
+  g_cu_mask_queries.fetch_add(1, std::memory_order_relaxed);
   const uint32_t cus = (uint32_t)fake_hip_cus();
   for (uint32_t i = 0; i < n; ++i) m[i] = cus >= 32 * (i + 1) ? 0xffffffffu : cus > 32 * i ? (1u << (cus - 32 * i)) - 1u : 0u;
   return hipSuccess;

@@ -888,6 +888,242 @@ ChainDma256Plan plan_chain_dma256(int64_t m, int64_t n, int nlayers, const int64
   return ChainDma256Plan{true, groups, "", false};
 }
 
+// ---- plan_chain: the layer-chain launch decision (gemm_plan.h has the order of precedence) ---------------------------------------
+static const ChainLaunchPlan &chain_calls(ChainLaunchPlan &p, const char *why) {
+  p.form = CF_CALLS, p.why = why;
+  return p;
+}
+static void chain_note(ChainLaunchPlan &p, const char *rule, const char *why) {
+  if (p.n_notes < 4) p.notes[p.n_notes++] = ChainLaunchPlan::Note{rule, why};
+}
+// the launch of `form` on `tile`: what try_chain_launch reads besides - the tile's dimensions, the grid and counter-block key (floor- or
+// ceil-divided as the form says), ChainArgs::n. ns[l] = layer l's columns.
+static const ChainLaunchPlan &chain_takes(ChainLaunchPlan &p, ChainForm form, int tile, int b_kind, int groups, int64_t m, int nlayers, const int64_t *ns) {
+  p.form = form, p.tile = tile, p.b_kind = b_kind, p.groups = groups, p.why = "";
+  if (form == CF_DMA256) p.bm = D256C_BM, p.bn = D256C_BN;
+  else if (form == CF_F32) (void)f32_chain_tile_dims(tile, &p.bm, &p.bn);
+  else blw_tile_dims(tile, &p.bm, &p.bn);
+  const int up_m = form == CF_EDGE || form == CF_RAGGED || form == CF_WRAGGED ? p.bm - 1 : 0; // (edge row tiles)
+  const int up_n = form == CF_RAGGED || form == CF_WRAGGED ? p.bn - 1 : 0;                      // (edge column tiles)
+  p.mixed = form == CF_WIDTHS || form == CF_WROUNDS || form == CF_WRAGGED;
+  int64_t widest = ns[0];
+  for (int l = 0; l < nlayers; ++l) {
+    if (ns[l] > widest) widest = ns[l];
+    if (p.mixed) p.tiles_l[l] = (int)((ns[l] + up_n) / p.bn);
+  }
+  p.args_n = (int)widest;
+  p.tiles_m = (int)((m + up_m) / p.bm);
+  p.tiles_n = (int)((widest + up_n) / p.bn);
+  return p;
+}
+
+ChainLaunchPlan plan_chain(int n, const GemmDesc *const *d, const int64_t *br, const ChainPlanEnv &env, ChainCus &cus) {
+  ChainLaunchPlan p{};
+  if (n < 2 || n > CHAIN_PLAN_MAXL) return chain_calls(p, "fewer than 2 or more than 8 calls");
+  // the calls' facts, each gathered once
+  const int64_t m = d[0]->m, nn = d[0]->n;
+  int64_t ks[CHAIN_PLAN_MAXL], ns[CHAIN_PLAN_MAXL];
+  bool differ_m = false, differ_n = false; // (differ_m: or a batch is empty)
+  for (int i = 0; i < n; ++i) {
+    ks[i] = d[i]->k, ns[i] = d[i]->n;
+    differ_m = differ_m || d[i]->m != m || br[i] < 1;
+    differ_n = differ_n || d[i]->n != nn;
+  }
+  const char *const differ_why = "the calls differ in m or n, or a batch is empty";
+
+  // 1. ON THE 256x256 TILE (xsmm_hip_set_chain_dma256, brgemm_bf16_dma256_chain.hip): asked first, and only with the switch non-zero. The rule sees
+  // the calls' shapes, their shared B image and whether every call runs on that tile as a single call (mode 1 reads xsmm_hip_set_dma256_images
+  // for it, nothing else reads another mode). Where it takes the chain no other switch is looked at; where it refuses or gates, everything
+  // below is what it is without this switch.
+  if (env.dma256) {
+    const char *w = differ_why;
+    if (!differ_m && !differ_n) {
+      const int images = env.dma256 == 1 ? env.dma256_images : 0;
+      int kind = chain_dma256_b_kind(*d[0]);
+      bool on_tile = true;
+      for (int i = 0; i < n; ++i) {
+        const int kind_i = chain_dma256_b_kind(*d[i]);
+        if (kind != -2 && kind_i != kind) kind = kind_i == -2 ? -2 : -1;
+        on_tile = on_tile && chain_dma256_on_tile(*d[i], images);
+      }
+      const ChainDma256Plan dp = plan_chain_dma256(m, nn, n, ks, br, cus.get(), on_tile, kind, env.dma256, env.strict);
+      if (dp.take && !dp.gated) return chain_takes(p, CF_DMA256, 3, kind, dp.groups, m, n, ns); // (gated: the rule's answer is on record in why, nothing is launched)
+      w = dp.why;
+    }
+    chain_note(p, "launch on the 256x256 tile", w);
+  }
+
+  // f32 chains: every call planned on the SAME K-split loader-wave tile (the launch is then bit-identical to the calls), all of its
+  // workgroups resident at once. No switch is read.
+  if (d[0]->dtype == DT_F32) {
+    const int tile = f32_chain_tile(*d[0]);
+    for (int i = 0; i < n; ++i) {
+      const GemmDesc &g = *d[i];
+      if (g.dtype != DT_F32 || !g.beta0 || f32_chain_tile(g) < 0 || f32_chain_tile(g) != tile)
+        return chain_calls(p, "an f32 call is not beta 0 / not planned on the K-split loader-wave tile of the first call");
+      if (g.ldc & 3) return chain_calls(p, "an f32 output's leading dimension is not a multiple of 4");
+    }
+    if (differ_m || differ_n) return chain_calls(p, differ_why);
+    int bm = 0, bn = 0;
+    (void)f32_chain_tile_dims(tile, &bm, &bn);
+    if (m % bm != 0 || nn % bn != 0 || (m / bm) * (nn / bn) > cus.get()) return chain_calls(p, "more tiles than compute units");
+    return chain_takes(p, CF_F32, tile, 0, 0, m, n, ns);
+  }
+
+  // bf16. divisible = every call passes the rules of the plain chain: bf16, beta 0, no VNNI C, one B image of the loader-wave tiles
+  // (VNNI-2, flat or VNNI-4: a template parameter of the launch), not on the generic kernel.
+  if (differ_m) return chain_calls(p, differ_why);
+  const int lw_kind = bf16_lw_b_kind(*d[0]);
+  bool divisible = true, some_generic = false;
+  for (int i = 0; i < n; ++i) {
+    const GemmDesc &g = *d[i];
+    if (g.dtype != DT_BF16 || g.vnni_c || !g.beta0 || lw_kind < 0 || bf16_lw_b_kind(g) != lw_kind) divisible = false;
+    if (g.variant == V_GENERIC) {
+      // (a forced generic kernel stays generic; one that is generic only because no tile divides m may run ragged)
+      if (g.generic_forced) return chain_calls(p, "a call was dispatched to the generic kernel");
+      divisible = false, some_generic = true;
+    }
+  }
+  const int et = env.edge_tiles;
+  const int forced_tile = et >= V_BF16_LW_32x64 && et <= V_BF16_LW_128x128 ? et - V_BF16_LW_32x64 : -1; // (what a forcing edge-tile mode names: the ragged rules read it)
+
+  if (differ_n) {
+    // 2. and 4. MIXED WIDTHS (xsmm_hip_set_chain_widths) and COLUMN ROUNDS (xsmm_hip_set_chain_width_rounds): one question about calls the
+    // plain chain's rules pass but for their n - a forced W (1000 + W) in front of plan_chain_widths, column rounds by rule (1) where
+    // plan_chain_widths refuses or gates or its switch is off. Ragged shapes never combine with these two.
+    if (env.widths || env.width_rounds) {
+      const char *w = "a call differs in m, has an empty batch, is not bf16 / beta 0 / on a loader-wave tile, or the calls' B operands differ in kind";
+      if (divisible) {
+        const int planned = chain_rounds_planned_tile(n, d);
+        if (chain_width_rounds_mode_forced(env.width_rounds)) { // (a forced W that does not fit: everything below as with the switch off)
+          const ChainWidthRoundsPlan rp = plan_chain_width_rounds(m, n, ns, ks, br, cus.get(), planned, lw_kind, env.width_rounds, env.strict);
+          if (rp.tile >= 0 && !rp.gated) return chain_takes(p, CF_WROUNDS, rp.tile, lw_kind, rp.groups, m, n, ns);
+          w = rp.why;
+        }
+        if (env.widths) {
+          const ChainWidthsPlan wp = plan_chain_widths(m, n, ns, ks, br, cus.get(), planned, lw_kind, env.widths, env.strict);
+          if (wp.tile >= 0) return chain_takes(p, CF_WIDTHS, wp.tile, lw_kind, 0, m, n, ns);
+          w = wp.why;
+        }
+        // (mode 1 without a tile all calls were dispatched on: plan_chain_width_rounds' gate, or a refusal in front of it - never a launch.
+        // Answered here, without asking for the stream's compute units: on a launch-bound chain the runtime calls behind them
+        // showed - 1024 rows x [1024, 512, 256, 128], gated, call by call with the switch off / on 16.38 / 17.06 us per step in every pair;
+        // with this answer 18.65 / 18.65 in a later session, profiles/chain_width_rounds_ab.txt)
+        if (env.width_rounds == 1 && planned < 0) w = "column rounds by rule only on a tile all calls were dispatched on (plan_chain_width_rounds' gate)";
+        else if (env.width_rounds == 1) {
+          const ChainWidthRoundsPlan rp = plan_chain_width_rounds(m, n, ns, ks, br, cus.get(), planned, lw_kind, env.width_rounds, env.strict);
+          if (rp.tile >= 0 && !rp.gated) return chain_takes(p, CF_WROUNDS, rp.tile, lw_kind, rp.groups, m, n, ns); // (gated: on record in why, nothing is launched)
+          w = rp.why;
+        }
+      }
+      chain_note(p, "mixed-width launch", w);
+    }
+    // 6. RAGGED MIXED WIDTHS (xsmm_hip_set_chain_widths_ragged): where the mixed-width rules do not take the chain - every call passes
+    // chain_widths_ragged_b_kind with the same B image and plan_chain_widths_ragged names a tile without a gate.
+    if (env.widths_ragged) {
+      const char *w = nullptr;
+      int kind = chain_widths_ragged_b_kind(*d[0], env.widths_ragged, &w);
+      for (int i = 1; i < n && kind >= 0; ++i)
+        if (chain_widths_ragged_b_kind(*d[i], env.widths_ragged, &w) != kind) kind = -1;
+      if (kind >= 0) {
+        const ChainWidthsRaggedPlan rp = plan_chain_widths_ragged(m, n, ns, ks, br, cus.get(), forced_tile, kind, env.widths_ragged, env.strict);
+        if (rp.tile >= 0 && !rp.gated) return chain_takes(p, CF_WRAGGED, rp.tile, kind, 0, m, n, ns); // (gated: on record in why, nothing is launched)
+        w = rp.why;
+      }
+      chain_note(p, "ragged mixed-width launch", w ? w : "the calls' B operands differ in kind");
+    }
+    return chain_calls(p, differ_why);
+  }
+
+  // equal widths. RAGGED m (xsmm_hip_set_chain_edge): every call passes chain_edge_b_kind with the same B image; edge_why = why not.
+  const char *edge_why = nullptr;
+  int edge_kind = -1;
+  if (env.edge) {
+    edge_kind = chain_edge_b_kind(*d[0], env.edge, &edge_why);
+    for (int i = 1; i < n && !edge_why; ++i) {
+      const char *w = nullptr;
+      if (chain_edge_b_kind(*d[i], env.edge, &w) != edge_kind) edge_why = w ? w : "the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)";
+    }
+  }
+  const bool edge_on = env.edge && !edge_why;
+  ChainEdgePlan ep{-1, nullptr};
+  ChainRoundsPlan rp{-1, 0, nullptr, false};
+
+  if (divisible) {
+    const int planned = chain_rounds_planned_tile(n, d); // the loader-wave tile ALL calls were planned on
+    auto fits = [&](int t) { // all workgroups must be co-resident (one per CU by LDS): the grid may not exceed the CUs
+      int bm, bn;
+      blw_tile_dims(t, &bm, &bn);
+      return m % bm == 0 && nn % bn == 0 && (m / bm) * (nn / bn) <= cus.get();
+    };
+    // 2. a forced G (1000 + G) in front of the one-round rules (one that does not fit: everything below as with the switch off)
+    if (chain_rounds_mode_forced(env.rounds)) {
+      rp = plan_chain_rounds(m, nn, n, ks, br, cus.get(), planned, env.rounds, env.strict);
+      if (rp.tile >= 0) return chain_takes(p, CF_ROUNDS, rp.tile, lw_kind, rp.groups, m, n, ns);
+    }
+    // 3. the tile every layer was planned on, if it fits: the launch is then bit-identical to the separate launches
+    if (planned >= 0 && fits(planned)) return chain_takes(p, CF_PLAIN, planned, lw_kind, 0, m, n, ns);
+    // 5. the one-round ragged-m launch in front of several rounds: the two switches never combine, and where a tile of other rows fits on
+    // its ceil-divided grid the ragged launch wins - 32 * 257 rows x 64 of flat B, planned on 32x64 (257 tiles), run as 129 edge row
+    // blocks of 64x64 with both switches on as with xsmm_hip_set_chain_edge alone (tests/test_chain_dispatch.py found the rounds)
+    if (edge_on) ep = plan_chain_edge(m, nn, n, ks, br, cus.get(), forced_tile, env.strict);
+    if (env.rounds == 1) rp = plan_chain_rounds(m, nn, n, ks, br, cus.get(), planned, env.rounds, env.strict);
+    const bool rounds = env.rounds == 1 && rp.tile >= 0 && !rp.gated; // (gated: the rule's answer is on record in why, nothing is launched)
+    // the tile all calls were planned on has more tiles than compute units: several rounds on THAT tile - the descriptors' own, G changes
+    // no bit, so strict mode takes it too - in front of one round on another tile, whose bits need not be the calls'
+    if (rounds && planned >= 0 && ep.tile < 0) return chain_takes(p, CF_ROUNDS, rp.tile, lw_kind, rp.groups, m, n, ns);
+    // (the parent's order, kept: strict mode refuses HERE - behind several rounds on the planned tile, in front of the smallest tile that fits)
+    if (env.strict) return chain_calls(p, env.rounds == 1 ? rp.why : "strict mode: one launch only on the tile the layers were planned on");
+    for (int t = 0; t < 4; ++t) // the smallest tile that fits (most CUs busy)
+      if (fits(t)) return chain_takes(p, CF_PLAIN, t, lw_kind, 0, m, n, ns);
+    if (ep.tile >= 0) return chain_takes(p, CF_EDGE, ep.tile, edge_kind, 0, m, n, ns);
+    // only a shape every tile of which divides - one the ragged rule has just refused - may run in several rounds on a tile of the rule's choice
+    if (rounds) return chain_takes(p, CF_ROUNDS, rp.tile, lw_kind, rp.groups, m, n, ns);
+    return chain_calls(p, edge_on ? ep.why : env.rounds == 1 ? rp.why : "more tiles than compute units");
+  }
+
+  // calls the plain chain's rules refuse because of their SHAPE: no loader-wave tile divides one (no B image by bf16_lw_b_kind, planned on
+  // the generic kernel)
+  if (chain_rounds_mode_forced(env.rounds)) {
+    // 2. a forced G is asked in front of the one-round rules, so also in front of their m and n terms (bf16_lw_b_kind: 64 rows for VNNI-2):
+    // every call has one B image by chain_rounds_b_kind
+    int kind = chain_rounds_b_kind(*d[0]);
+    for (int i = 1; i < n; ++i)
+      if (chain_rounds_b_kind(*d[i]) != kind) kind = -1;
+    if (kind >= 0) {
+      rp = plan_chain_rounds(m, nn, n, ks, br, cus.get(), chain_rounds_planned_tile(n, d), env.rounds, env.strict);
+      if (rp.tile >= 0) return chain_takes(p, CF_ROUNDS, rp.tile, kind, rp.groups, m, n, ns);
+      // (the parent's order, kept: a forced G that does not fit ends the decision HERE unless the ragged-m rule may still be asked - the
+      // ragged-width rule below is not asked on its own)
+      if (!edge_on) return chain_calls(p, rp.why);
+    }
+  }
+  // 5. one round on edge row tiles
+  if (edge_on) {
+    ep = plan_chain_edge(m, nn, n, ks, br, cus.get(), forced_tile, env.strict);
+    if (ep.tile >= 0) return chain_takes(p, CF_EDGE, ep.tile, edge_kind, 0, m, n, ns);
+  }
+  // 6. RAGGED WIDTH (xsmm_hip_set_chain_ragged): where the others refuse because of n or k - a k % 64, an n % 64, plan_chain_edge's refusal
+  // (n not in whole column tiles). Every call passes chain_ragged_b_kind with the same B image and plan_chain_ragged names a tile.
+  if (env.ragged) {
+    const char *w = nullptr;
+    int kind = chain_ragged_b_kind(*d[0], env.ragged, &w);
+    for (int i = 1; i < n && kind >= 0; ++i)
+      if (chain_ragged_b_kind(*d[i], env.ragged, &w) != kind) kind = -1;
+    if (kind >= 0) {
+      const ChainRaggedPlan gp = plan_chain_ragged(m, nn, n, ks, br, cus.get(), forced_tile, kind, env.ragged, env.strict);
+      if (gp.tile >= 0) return chain_takes(p, CF_RAGGED, gp.tile, kind, 0, m, n, ns);
+      w = gp.why;
+    }
+    chain_note(p, "ragged-width launch", w ? w : "the calls' B operands differ in kind");
+  }
+  if (env.widths_ragged) chain_note(p, "ragged mixed-width launch", "every call has the same n: the equal-width chain switches decide");
+  if (edge_on) return chain_calls(p, ep.why);
+  if (edge_why) return chain_calls(p, edge_why);
+  return chain_calls(p, some_generic ? "a call was dispatched to the generic kernel"
+                                     : "a call is not bf16 / beta 0 / aligned for the LDS-DMA tiles, or the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)");
+}
+
 static GemmLaunch launch(GemmLauncher l, int tile = 0, const char *text = "", int split = 1, int b_kind = 0, bool even = false) {
   return GemmLaunch{l, tile, split, b_kind, even, false, GG_F32, text};
 }

@@ -1,6 +1,7 @@
 // gemm_plan.h - which GEMM kernel runs a call: the variant a descriptor is planned on at dispatch (plan_gemm), the launch an invoke or a
-// tile-queue group gets (plan_gemm_call, plan_gemm_group), the descriptor facts the chain code asks about. Host-only, every input an
-// argument: the table of choices is checked on a CPU (tests/golden/gemm_plan.txt). brgemm_f32.hip carries a GemmLaunch out.
+// tile-queue group gets (plan_gemm_call, plan_gemm_group), the one launch a layer chain gets (plan_chain: the entry of the chain rules below).
+// Host-only, every input an argument: the table of choices is checked on a CPU (tests/golden/gemm_plan.txt, chain_dispatch.txt).
+// brgemm_f32.hip carries a GemmLaunch out, rt_chain.h try_chain_launch a ChainLaunchPlan.
 #pragma once
 #include "xsmm_desc.h"
 
@@ -123,7 +124,7 @@ inline bool gemm_on_x6(const GemmDesc &d) { return d.variant >= V_F32_X6_64x64 &
 // which B image of the loader-wave bf16 tiles (brgemm_bf16_lw.hip) a descriptor's B operand needs - 0: VNNI-2, 2: flat [k][ldb],
 // 4: VNNI-4 - or -1 if the descriptor cannot run on those tiles (shape / alignment / lane-offset limits of the LDS-DMA panels)
 int bf16_lw_b_kind(const GemmDesc &d);
-// RAGGED-m CHAINS (xsmm_hip_set_chain_edge; rt_chain.h try_chain_launch, brgemm_bf16_lw.hip launch_bf16_chain, BLW_CHAIN_EDGE). Host-only, no HIP calls:
+// RAGGED-m CHAINS (xsmm_hip_set_chain_edge; plan_chain, brgemm_bf16_lw.hip launch_bf16_chain, BLW_CHAIN_EDGE). Host-only, no HIP calls:
 // tests/golden/gemm_plan_chain_edge.txt is the table of both functions' answers.
 // One call of a chain: the B image (0 VNNI-2, 2 flat, 4 VNNI-4) it would run with as a layer of a ragged-m chain - what bf16_lw_b_kind asks of
 // leading dimensions, strides and lane offsets without its m and n terms -, or -1 and *why: the switch is off, an f32 call, a VNNI C,
@@ -138,7 +139,7 @@ int chain_edge_b_kind(const GemmDesc &d, int chain_edge, const char **why);
 // chain's rules decide).
 struct ChainEdgePlan { int tile; const char *why; };
 ChainEdgePlan plan_chain_edge(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, bool strict);
-// RAGGED-WIDTH CHAINS (xsmm_hip_set_chain_ragged; rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_ragged.hip launch_bf16_chain_ragged,
+// RAGGED-WIDTH CHAINS (xsmm_hip_set_chain_ragged; plan_chain, brgemm_bf16_lw_chain_ragged.hip launch_bf16_chain_ragged,
 // BLW_CHAIN_RAGGED, schedule in brgemm_bf16_lw_chain_ragged.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_ragged.txt is the table of
 // both functions' answers.
 // One call of a chain: the B image (0 VNNI-2, 2 flat, 4 VNNI-4) it would run with as a layer of a ragged-width chain - what chain_edge_b_kind
@@ -157,7 +158,7 @@ int chain_ragged_b_kind(const GemmDesc &d, int chain_ragged, const char **why);
 // 1000, 1000] ran 3.5 % slower. Under a forcing edge-tile mode (forced_tile >= 0: tests, measurements) nothing is gated.
 struct ChainRaggedPlan { int tile; const char *why; };
 ChainRaggedPlan plan_chain_ragged(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, int b_kind, int mode, bool strict);
-// MULTI-ROUND CHAINS (xsmm_hip_set_chain_rounds; rt_chain.h try_chain_launch, brgemm_bf16_lw.hip launch_bf16_chain, BLW_CHAIN_ROUNDS, step maps in
+// MULTI-ROUND CHAINS (xsmm_hip_set_chain_rounds; plan_chain, brgemm_bf16_lw.hip launch_bf16_chain, BLW_CHAIN_ROUNDS, step maps in
 // brgemm_bf16_lw_chain_rounds.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_rounds.txt is the table of the function's answers.
 // A bf16 chain that meets every condition of the divisible chain but has MORE output tiles than compute units runs as one launch on
 // G x tiles_n resident workgroups, G row groups walking R = ceil(tiles_m / G) rounds of row blocks. m x n outputs per layer, nlayers layers
@@ -189,7 +190,7 @@ int chain_rounds_planned_tile(int n, const GemmDesc *const *d);
 // beta 1, the generic kernel, k not in 64-k chunks, an operand off the LDS-DMA grid.
 int chain_rounds_b_kind(const GemmDesc &d);
 ChainRoundsPlan plan_chain_rounds(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int mode, bool strict);
-// MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths; rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_widths.hip launch_bf16_chain_widths,
+// MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths; plan_chain, brgemm_bf16_lw_chain_widths.hip launch_bf16_chain_widths,
 // BLW_CHAIN_WIDTHS, schedule in brgemm_bf16_lw_chain_widths.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_widths.txt is the table
 // of the function's answers. A bf16 chain of 2 .. 8 calls with the same m whose n differ runs as one launch on m / BM x max_l(n[l] / BN)
 // workgroups. n[l], k[l], br[l]: layer l's columns, k per batch element and batch count; cus: compute units on the stream; planned_tile
@@ -207,7 +208,7 @@ ChainRoundsPlan plan_chain_rounds(int64_t m, int64_t n, int nlayers, const int64
 // funnel [1024, 512, 256, 128], on the smallest tile, 28 % faster.
 struct ChainWidthsPlan { int tile; const char *why; };
 ChainWidthsPlan plan_chain_widths(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int b_kind, int mode, bool strict);
-// MIXED-WIDTH CHAINS IN COLUMN ROUNDS (xsmm_hip_set_chain_width_rounds; rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_wrounds.hip
+// MIXED-WIDTH CHAINS IN COLUMN ROUNDS (xsmm_hip_set_chain_width_rounds; plan_chain, brgemm_bf16_lw_chain_wrounds.hip
 // launch_bf16_chain_wrounds, BLW_CHAIN_WROUNDS, schedule in brgemm_bf16_lw_chain_wrounds.h). Host-only, no HIP calls:
 // tests/golden/gemm_plan_chain_width_rounds.txt is the table of the function's answers. The mixed-width chain above on m / BM x W resident
 // workgroups, 1 <= W < max_l(n[l] / BN): a workgroup walks several column tiles of a wide layer and one (or none) of a narrow one. The
@@ -240,7 +241,7 @@ ChainWidthsPlan plan_chain_widths(int64_t m, int nlayers, const int64_t *n, cons
 struct ChainWidthRoundsPlan { int tile; int groups; const char *why; bool gated; };
 inline bool chain_width_rounds_mode_forced(int mode) { return mode > 1000; }
 ChainWidthRoundsPlan plan_chain_width_rounds(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int planned_tile, int b_kind, int mode, bool strict);
-// RAGGED MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths_ragged; rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_wragged.hip
+// RAGGED MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths_ragged; plan_chain, brgemm_bf16_lw_chain_wragged.hip
 // launch_bf16_chain_wragged, BLW_CHAIN_WRAGGED, schedule in brgemm_bf16_lw_chain_wragged.h). Host-only, no HIP calls:
 // tests/golden/gemm_plan_chain_widths_ragged.txt is the table of both functions' answers.
 // One call of a chain: chain_ragged_b_kind's question under this switch - the B image (0 VNNI-2, 2 flat, 4 VNNI-4) the call would run with
@@ -266,7 +267,7 @@ int chain_widths_ragged_b_kind(const GemmDesc &d, int mode, const char **why);
 // why = the gate: the caller does not launch.
 struct ChainWidthsRaggedPlan { int tile; const char *why; bool gated; };
 ChainWidthsRaggedPlan plan_chain_widths_ragged(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int forced_tile, int b_kind, int mode, bool strict);
-// LAYER CHAINS ON THE 256x256 TILE (xsmm_hip_set_chain_dma256; rt_chain.h try_chain_launch, brgemm_bf16_dma256_chain.hip launch_bf16_dma256_chain,
+// LAYER CHAINS ON THE 256x256 TILE (xsmm_hip_set_chain_dma256; plan_chain, brgemm_bf16_dma256_chain.hip launch_bf16_dma256_chain,
 // maps in brgemm_bf16_dma256_chain.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_dma256.txt is the table of the answers.
 // One call of a chain: the B image (0 VNNI-2, 2 flat, 4 VNNI-4) it would have as a layer of this launch - bf16, beta 0, no VNNI C, not the
 // forced generic kernel, k in 32-k chunks, leading dimensions, strides and lane offsets on the tile's grid - or -1; -2: an f32 call.
@@ -294,6 +295,52 @@ struct ChainDma256Plan { bool take; int groups; const char *why; bool gated; };
 constexpr int CHAIN_DMA256_GATE_TILES_N = 8; // most column tiles mode 1 takes
 inline bool chain_dma256_mode_forced(int mode) { return mode > 1000; }
 ChainDma256Plan plan_chain_dma256(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, bool all_on_tile, int b_kind, int mode, bool strict);
+// THE LAYER-CHAIN LAUNCH DECISION (rt_chain.h try_chain_launch carries the answer out): which of the nine launch forms runs n calls that
+// the chain contract admits, on which tile, B image and group count - or that they run call by call, and which rule refused. Host-only:
+// no HIP call, no global; the descriptors, the batch counts, the switches and a way to ask for the stream's compute units are arguments.
+// tests/test_chain_dispatch.py pins the answers through the C-ABI under every switch set (tests/golden/chain_dispatch.txt).
+// plan_chain composes the rules above. Each is asked at most once, in ONE order of precedence; behind each rule, the modes it reads:
+//   1. the 256x256 tile       plan_chain_dma256        {dma256; dma256_images in mode 1}   asked first; where it takes the chain nothing else is read
+//      (an f32 chain - every call on the K-split loader-wave tile of the first, within the compute units - reads no switch)
+//   2. a forced G / a forced W  plan_chain_rounds {rounds = 1000 + G}, plan_chain_width_rounds {width_rounds = 1000 + W}: in front of the one-round rules
+//   3. the plain chain on the loader-wave tile all calls were planned on, if it fits the compute units
+//   4. mixed widths            plan_chain_widths        {widths}, then column rounds by rule plan_chain_width_rounds {width_rounds = 1}
+//   5. one round on edge rows  plan_chain_edge          {edge; edge_tiles 20 .. 23} in front of several rounds plan_chain_rounds {rounds = 1};
+//      several rounds on the PLANNED tile in front of the plain chain on another tile (the smallest that fits), on another tile behind both
+//   6. ragged width            plan_chain_ragged        {ragged; edge_tiles}, then ragged mixed widths plan_chain_widths_ragged {widths_ragged; edge_tiles},
+//      where the others refuse
+// Calls that differ in n are rules 4 and 6's (ragged mixed widths) alone, equal widths everyone else's; strict is read by every rule.
+constexpr int CHAIN_PLAN_MAXL = 8; // (= CH_MAXL, chain_args.h)
+enum ChainForm : int { CF_CALLS, CF_F32, CF_PLAIN, CF_EDGE, CF_ROUNDS, CF_RAGGED, CF_WIDTHS, CF_WROUNDS, CF_WRAGGED, CF_DMA256, CF_FORMS };
+// xsmm_hip_set_strict, the seven chain switches (xsmm_hip_set_chain_*), xsmm_hip_set_edge_tiles and xsmm_hip_set_dma256_images; rt_core.h
+// chain_plan_env fills it per invoke
+struct ChainPlanEnv { bool strict; int edge, rounds, ragged, widths, width_rounds, widths_ragged, dma256; int edge_tiles, dma256_images; };
+// The compute units a launch on the invoke's stream can use - the one input that costs runtime calls (rt_chain.h stream_cus: three). Asked
+// lazily and at most once per invoke: a decision that ends in front of every rule that reads them never pays for them.
+struct ChainCus {
+  int64_t (*ask)(void *);
+  void *arg;
+  int64_t known = -1;
+  int64_t get() { return known >= 0 ? known : (known = ask(arg)); }
+};
+struct ChainLaunchPlan {
+  ChainForm form;     // CF_CALLS: call by call, `why` names a rule that refused
+  int tile;           // the launcher's tile: loader-wave tile 0 .. 3, f32 chain tile 1 / 2, 3 for CF_DMA256 (whose launcher takes none)
+  int b_kind;         // the B image of the launch: 0 VNNI-2, 2 flat, 4 VNNI-4 (0 for CF_F32)
+  int groups;         // ChainArgs::groups: row groups G (CF_ROUNDS, CF_DMA256), workgroup columns W (CF_WROUNDS), 0 otherwise
+  int bm, bn;         // the tile's rows and columns (256 x 256 for CF_DMA256)
+  int tiles_m, tiles_n; // the counter-block key and the grid: ceil-divided where the form has edge tiles (m: CF_EDGE, CF_RAGGED, CF_WRAGGED; n: the
+                      // latter two), the widest layer's column tiles in the width forms
+  int tiles_l[CHAIN_PLAN_MAXL]; // the width forms: column tiles per layer, part of the key (what a launch adds to layer l's counters); zero otherwise
+  int args_n;         // ChainArgs::n: the widest layer's n
+  bool mixed;         // a width form (CF_WIDTHS, CF_WROUNDS, CF_WRAGGED): ChainLayer::pad carries each layer's n, and the hand-off target is the
+                      // block's epoch - the kernel multiplies by the producing layer's column tiles; otherwise epoch x tiles_n
+  const char *why;    // CF_CALLS: the refusal, a static string ("" for a launch)
+  // rules that were asked in front of the answer and refused: "no <rule> (<why>)" under TPP_HIP_TRACE
+  struct Note { const char *rule, *why; } notes[4];
+  int n_notes;
+};
+ChainLaunchPlan plan_chain(int n, const GemmDesc *const *d, const int64_t *br, const ChainPlanEnv &env, ChainCus &cus);
 // 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none
 int f32_chain_tile(const GemmDesc &d);
 // tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128 (brgemm_bf16_lw.hip; BLW_TILES, brgemm_bf16_lw_launch.h)

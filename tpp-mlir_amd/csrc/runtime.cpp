@@ -41,65 +41,27 @@
 
 using namespace tpp;
 
-// The chain planners (gemm_plan.cpp: chain_*_b_kind, plan_chain_*, chain_rounds_planned_tile, chain_dma256_on_tile) and the chain launchers
-// (chain_args.h; the brgemm_bf16_lw*.hip files, brgemm_bf16_dma256_chain.hip) that rt_chain.h try_chain_launch calls have WEAK stand-ins that
-// refuse here. The library's link takes the real definitions. So does ONE of the two host-only builds of this file:
+// The layer-chain launch decision (gemm_plan.cpp plan_chain) and the chain launchers (chain_args.h; the brgemm_bf16_lw*.hip files,
+// brgemm_bf16_dma256_chain.hip) that rt_chain.h try_chain_launch calls have WEAK stand-ins that refuse here. The library's link takes the
+// real definitions. So does ONE of the two host-only builds of this file:
 //  * tests/tsan/fake_hip.cpp (the sanitizer, host-cache and epilogue-fold drivers) links neither gemm_plan.cpp nor any kernel file - its
-//    kernel stand-ins predate the chain switches and plan every bf16 descriptor away -, takes these stand-ins and refuses every bf16 chain
-//    at the first rule;
+//    kernel stand-ins predate the chain switches and plan every bf16 descriptor away -, takes these stand-ins and runs every chain call
+//    by call;
 //  * tests/chain_dispatch/fake_chain.cpp (tests/test_chain_dispatch.py) links the real gemm_plan.cpp and defines every launcher itself
 //    (computing through the oracle, recording, with a model of the hand-off counters): there try_chain_launch runs to the end, under
 //    every combination of the switches, on a CPU.
 namespace tpp {
+__attribute__((weak)) ChainLaunchPlan plan_chain(int, const GemmDesc *const *, const int64_t *, const ChainPlanEnv &, ChainCus &) {
+  ChainLaunchPlan p{};
+  p.why = "this build has no chain planner";
+  return p; // (CF_CALLS)
+}
 __attribute__((weak)) hipError_t launch_bf16_chain(int, int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
-__attribute__((weak)) int chain_edge_b_kind(const GemmDesc &, int, const char **why) {
-  if (why) *why = "this build has no ragged-chain planner";
-  return -1;
-}
-__attribute__((weak)) ChainEdgePlan plan_chain_edge(int64_t, int64_t, int, const int64_t *, const int64_t *, int64_t, int, bool) {
-  return ChainEdgePlan{-1, "this build has no ragged-chain planner"};
-}
-// (ragged-width chains, xsmm_hip_set_chain_ragged: the same arrangement, with a launcher of their own - brgemm_bf16_lw_chain_ragged.hip)
 __attribute__((weak)) hipError_t launch_bf16_chain_ragged(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
-__attribute__((weak)) int chain_ragged_b_kind(const GemmDesc &, int, const char **why) {
-  if (why) *why = "this build has no ragged-width-chain planner";
-  return -1;
-}
-__attribute__((weak)) ChainRaggedPlan plan_chain_ragged(int64_t, int64_t, int, const int64_t *, const int64_t *, int64_t, int, int, int, bool) {
-  return ChainRaggedPlan{-1, "this build has no ragged-width-chain planner"};
-}
-// (mixed-width chains, xsmm_hip_set_chain_widths: the same arrangement, with a launcher of their own - brgemm_bf16_lw_chain_widths.hip)
 __attribute__((weak)) hipError_t launch_bf16_chain_widths(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
-__attribute__((weak)) ChainWidthsPlan plan_chain_widths(int64_t, int, const int64_t *, const int64_t *, const int64_t *, int64_t, int, int, int, bool) {
-  return ChainWidthsPlan{-1, "this build has no mixed-width-chain planner"};
-}
-// (column rounds of mixed-width chains, xsmm_hip_set_chain_width_rounds: the same arrangement - brgemm_bf16_lw_chain_wrounds.hip)
 __attribute__((weak)) hipError_t launch_bf16_chain_wrounds(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
-__attribute__((weak)) ChainWidthRoundsPlan plan_chain_width_rounds(int64_t, int, const int64_t *, const int64_t *, const int64_t *, int64_t, int, int, int, bool) {
-  return ChainWidthRoundsPlan{-1, 0, "this build has no column-round planner", false};
-}
-// (ragged mixed-width chains, xsmm_hip_set_chain_widths_ragged: the same arrangement - brgemm_bf16_lw_chain_wragged.hip)
 __attribute__((weak)) hipError_t launch_bf16_chain_wragged(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
-__attribute__((weak)) int chain_widths_ragged_b_kind(const GemmDesc &, int, const char **why) {
-  if (why) *why = "this build has no ragged mixed-width planner";
-  return -1;
-}
-__attribute__((weak)) ChainWidthsRaggedPlan plan_chain_widths_ragged(int64_t, int, const int64_t *, const int64_t *, const int64_t *, int64_t, int, int, int, bool) {
-  return ChainWidthsRaggedPlan{-1, "this build has no ragged mixed-width planner", false};
-}
-// (chains on the 256x256 tile, xsmm_hip_set_chain_dma256: the same arrangement - brgemm_bf16_dma256_chain.hip)
 __attribute__((weak)) hipError_t launch_bf16_dma256_chain(int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
-__attribute__((weak)) int chain_dma256_b_kind(const GemmDesc &) { return -1; }
-__attribute__((weak)) bool chain_dma256_on_tile(const GemmDesc &, int) { return false; }
-__attribute__((weak)) ChainDma256Plan plan_chain_dma256(int64_t, int64_t, int, const int64_t *, const int64_t *, int64_t, bool, int, int, bool) {
-  return ChainDma256Plan{false, 0, "this build has no planner of chains on the 256x256 tile", false};
-}
-// (multi-round chains, xsmm_hip_set_chain_rounds: the same arrangement)
-__attribute__((weak)) int chain_rounds_planned_tile(int, const GemmDesc *const *) { return -1; }
-__attribute__((weak)) int chain_rounds_b_kind(const GemmDesc &) { return -1; }
-__attribute__((weak)) ChainRoundsPlan plan_chain_rounds(int64_t, int64_t, int, const int64_t *, const int64_t *, int64_t, int, int, bool) {
-  return ChainRoundsPlan{-1, 0, "this build has no multi-round-chain planner", false};
-}
 } // namespace tpp
 
 namespace {
