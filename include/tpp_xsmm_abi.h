@@ -502,6 +502,46 @@ TPP_XSMM_EXPORT void xsmm_hip_dma256_images_stats(int64_t out[4]);
  * image (0 VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_dma256_edge(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_dma256_edge_stats(int64_t out[4]);
+/* Skinny-batch bf16 layers (opt-in; also TPP_HIP_SKINNY_BF16, read as a number). A bf16 call with fewer than 32 rows - batch 1, 4, 8 or 16
+ * of online inference - runs on the generic kernel: one workgroup per 32x32 output tile (n / 32 workgroups), a 32-row MFMA of which m rows
+ * are used, B read in 64-byte row pieces and staged through LDS. Such a layer is a weight stream: its time is the bytes of B. With this
+ * switch on, the call runs on ceil(n / BN) workgroups of brgemm_bf16_skinny<IMG, BN, MB> (brgemm_bf16_skinny.hip; maps in
+ * brgemm_bf16_skinny.h), BN = 16, 32 or 64: one workgroup computes ALL m rows of one block of BN columns on v_mfma_f32_16x16x32_bf16 - one
+ * accumulator set for m <= 16 (MB = 16), two that share every B fragment for m = 17 .. 31 (MB = 32). B goes from global memory straight
+ * into the MFMA operand registers, without LDS: per 32-k step a lane loads its 8 k values of BN / 16 consecutive columns - 4 pair-rows of a
+ * VNNI-2 B, 2 k-group rows of a VNNI-4 B, 8 k-rows of a flat B, 4 .. 16 bytes each - and the operand of MFMA j is a selection of their
+ * halves; a lane ends up with BN / 16 consecutive columns of four rows and stores them as one piece per row. A flat B has no BN = 16
+ * instance (it would need 2-byte loads): eight B instances x two MB. The stream of 32-k steps over (batch element, k) is dealt over
+ * W = min(8, br * ceil(k / 32)) waves of the workgroup in contiguous runs, four steps of loads in flight per wave; the partial accumulators
+ * are added through LDS in wave order, then beta 1's C, the bias, relu and ONE rounding to bf16. W depends on br and k alone, so an
+ * element's chain of additions depends neither on m, nor on n, nor on where its column block sits, and the bits are the same on every run.
+ * A row at or beyond m is read from row m - 1 and never stored; for k % 32 != 0 the lane groups of a batch element's last step whose k
+ * values do not exist issue no load and feed zeros on both sides; the last column block is shifted back to end at n and stores only the
+ * columns no other block owns. No load leaves rows [0, m) x [0, k) of A, [0, k) x [0, n) of a B element or the bias row, nothing outside
+ * the m x n window of C is written. No cross-workgroup synchronisation, no scratch block, no counters: legal on a captured stream.
+ * A call is taken, at invoke time, when all of this holds: bf16, B VNNI-2, flat or VNNI-4, no VNNI C, no transposed operand, neither a
+ * kernel variant nor the generic kernel forced, the descriptor's kernel is the generic one, 1 <= m <= 31, n >= BN, n % 8 == 0, k >= 8,
+ * k % 8 == 0 per batch element, batch count >= 1, lda >= k, ldb >= n, ldc >= n, lda, ldb, ldc, stride_a and stride_b multiples of 8
+ * elements, A, B and C 16-byte and the bias row 8-byte aligned. The launcher checks the same again; a call it refuses runs the launch of
+ * mode 0. Everything else runs exactly as with the switch off - f32 calls, m >= 32, every tile-queue group, quad, chain launch and folded
+ * call. No other switch takes a bf16 call with m < 32, and this one reads no other mode: there is no precedence question.
+ * mode 0 = off (default); 1 = the rule, measured (profiles/skinny_bf16_ab.txt: one MI355X, 256 CUs, beta 0 + bias + relu, five alternating
+ * rounds, us per call, generic kernel -> skinny; a BN is taken only where it was faster in every round). THE GATE: a call with m >= 17
+ * that the generic kernel runs on its 16-byte path (a VNNI B, k % 32 == 0) stays there - it lost on every BN in every round (1024 x 1024
+ * (n x K) 5.00 -> 5.72 on BN 16, 4096 x 4096 12.41 -> 14.31, 4096 x 1024 5.07 -> 5.96, 1024 x 4096 10.78 -> 11.36). Every other eligible call is
+ * taken: where B (2 br k n bytes) has at least 16 MiB on the BN whose row piece is one 128-byte line - 32 for VNNI-2, 16 for VNNI-4, 64 for
+ * flat (4096 x 4096, m 1 / 8 / 16: 11.34 / 12.02 / 12.15 -> 9.19 / 10.55 / 10.88; VNNI-4 m 8 11.78 -> 8.35; flat m 8 136.39 -> 14.87) -, a
+ * smaller B on the smallest BN with an instance, 16 or flat 32 (1024 x 1024 m 8 5.02 -> 4.49, 4096 x 1024 4.97 -> 4.31, 1024 x 4096 10.67 ->
+ * 6.75; k = 1000, the generic kernel's element path, 1000 x 1000 m 1 / 8 / 16 / 31: 34.82 / 35.04 / 37.31 / 41.49 -> 4.63 / 4.17 / 4.20 / 5.05),
+ * halved while n < BN. The rule reads no CU count: other counts, several ranks, beta 1 and a B between 8 and 32 MiB were not measured.
+ * 16, 32, 64 = every eligible call on that BN (test / measurement switches; a flat B under 16 and n < BN stay where they are).
+ * Read per invoke; returns the previous mode, -1 (and changes nothing) for any other value. The choice depends on the descriptor, the
+ * batch count, the pointers' alignment and the CU count only: made in strict mode too. xsmm_hip_last_refined_kernel reads
+ * "brgemm_bf16_skinny<MBxBN>", "brgemm_bf16_skinny_flatb<MBxBN>" or "brgemm_bf16_skinny_vnni4<MBxBN>" (MB 16 / 32, BN 16 / 32 / 64).
+ * _stats: out[0] such launches since process start; of the most recent one: [1] workgroups, [2] waves per workgroup, [3] BN, [4] the B
+ * image (0 VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_skinny_bf16(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_skinny_bf16_stats(int64_t out[5]);
 /* Layer chains on the 256x256 bf16 tile (opt-in; also TPP_HIP_CHAIN_DMA256, read as a number). Every chain form above is a form of the
  * loader-wave tiles (32x64 .. 128x128); a chain whose calls run on the 256x256 LDS-DMA tile - 16384 rows x 1024 columns are exactly 256
  * such tiles - ran call by call. With this switch on, xsmm_hip_fused_brgemm_chain_invoke runs such a chain as ONE launch of that tile's

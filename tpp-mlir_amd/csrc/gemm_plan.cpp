@@ -6,6 +6,7 @@
 #include "brgemm_bf16_lw_chain_rounds.h"
 #include "brgemm_bf16_dma256_images.h"
 #include "brgemm_bf16_dma256_chain.h"
+#include "brgemm_bf16_skinny.h"
 #include <string.h>
 
 namespace tpp {
@@ -359,6 +360,38 @@ static bool dma256_edge_rule(const GemmDesc &d) {
   const int64_t t256 = cdiv(d.m, 256) * cdiv(d.n, 256), t128 = cdiv(d.m, 128) * cdiv(d.n, 128);
   auto fill = [](int64_t t) { return (double)t / (double)(((t + 255) / 256) * 256); }; // CU occupancy over the rounds
   return t256 >= 240 && 1.4 * fill(t256) >= fill(t128);
+}
+
+// SKINNY-BATCH bf16 LAYERS (xsmm_hip_set_skinny_bf16, opt-in; brgemm_bf16_skinny.hip, brgemm_bf16_skinny.h): the column-block width BN of a
+// bf16 call with 1 <= m <= 31 and B image `kind` (0 VNNI-2, 2 flat, 4 VNNI-4), or 0: the call stays on the generic kernel. Modes 16 / 32 / 64
+// (tests, measurements): that width if its instance exists (not flat with 16: passed over) and n >= BN.
+// Mode 1, THE RULE, from profiles/skinny_bf16_ab.txt (one box, 256 CUs, beta 0 + bias + relu, five alternating rounds, us per call, generic
+// kernel -> BN 16 / 32 / 64; a BN is taken only where it was faster in EVERY round):
+//   The generic kernel has two paths. On its 16-byte path (a VNNI B, k % 32 == 0) it is nearer the stream's bound than expected: 4096 x
+//   4096 (B 32 MiB) runs at 2.8 TB/s against 6.29 TB/s for a copy. On its element path (every flat B; k % 32 != 0) it is 8 to 9 times slower.
+//   m <= 16, 16-byte path: VNNI-2 4096x4096 m 1 / 8 / 16: 11.34 / 12.02 / 12.15 -> BN 32 9.19 / 10.55 / 10.88 (BN 16 slower in every round:
+//     64-byte row pieces split every 128-byte line of B between two workgroups; BN 64 ahead by 1 .. 11 %); VNNI-4 m 8: 11.78 -> BN 16 8.35
+//     (BN 32 10.03). 1024x1024 (n x K; B 2 MiB) 4.75 / 5.02 / 5.13 -> BN 16 4.51 / 4.49 / 4.80, 4096x1024 (8 MiB) 4.60 / 4.97 / 4.98 -> 3.92 /
+//     4.31 / 4.59, 1024x4096 (8 MiB) 10.33 / 10.67 / 10.72 -> 5.71 / 6.75 / 7.72; BN 32 and 64 lose or win less on all three.
+//     So: a B of at least 16 MiB runs on the BN whose row piece is one 128-byte line (VNNI-2 32, VNNI-4 16, flat 64), a smaller one on the
+//     smallest BN with an instance (16; flat 32) - more workgroups pulling bytes. (Between 8 and 32 MiB nothing was measured.)
+//   m >= 17 (two accumulator sets), 16-byte path: slower on EVERY BN in every round - 1024x1024 5.00 -> 5.72 / 7.01 / 8.38, 4096x4096 12.41
+//     -> 14.31 / 15.10 / 16.65, 4096x1024 5.07 -> 5.96, 1024x4096 10.78 -> 11.36: every workgroup re-reads its 32 rows of A, as many bytes
+//     as its B block on BN 32. THE GATE: such a call stays on the generic kernel.
+//   The element path, every m: 1000x1000 (k = 1000) m 1 / 8 / 16 / 31: 34.82 / 35.04 / 37.31 / 41.49 -> BN 16 4.63 / 4.17 / 4.20 / 5.05; flat
+//     4096x4096 m 8: 136.39 -> BN 64 14.87 (BN 32 15.28). Taken, on the BN of the size rule above.
+// Not measured: other CU counts (the rule does not read them), several ranks, beta 1, a flat or VNNI-4 B off the rows named here.
+// BN depends on n, k, br and the mode; the waves of a workgroup on br and k alone (skn_waves).
+constexpr int64_t SKINNY_LINE_BYTES = 16 << 20; // a B of at least this many bytes: the BN of one 128-byte line per row piece
+static int skinny_bf16_bn(const GemmDesc &d, int kind, int mode, int64_t br, bool ab16) {
+  if (mode == 16 || mode == 32 || mode == 64) return skn_instance_exists(kind, mode) && d.n >= mode ? mode : 0;
+  if (mode != 1) return 0;
+  const GenericOk g = generic_ok(d, ab16);
+  if ((g.vec16 || g.vec16_4) && d.m > 16) return 0; // the gate
+  const int smallest = kind == 2 ? 32 : 16, line = 64 / skn_vfac(kind);
+  int bn = 2 * br * d.k * d.n >= SKINNY_LINE_BYTES ? line : smallest;
+  while (bn > smallest && d.n < bn) bn /= 2;
+  return d.n >= bn ? bn : 0;
 }
 
 // RAGGED k, bf16 (xsmm_hip_set_edge_k_bf16, opt-in; brgemm_bf16_lw_kedge.h): a whole-layer bf16 call whose k is a multiple of 16 but not of
@@ -1159,6 +1192,26 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
   const bool bias_ok8 = !d.bias || al.d8;
   if (v >= V_BF16_FAST && v != V_BF16_SMALL32 && !(al.c16 && bias_ok8)) v = V_GENERIC;
   if (v == V_BF16_SMALL32 && !(al.c8 && bias_ok8)) v = V_GENERIC;
+  // Skinny-batch bf16 layers, if asked for (xsmm_hip_set_skinny_bf16, a switch of its own; brgemm_bf16_skinny.hip, brgemm_bf16_skinny.h): a
+  // bf16 call with 1 <= m <= 31 that is planned - not forced - on the generic kernel, whichever of the three B images it has, on ceil(n / BN)
+  // workgroups that stream B straight into MFMA operand registers. No other refinement takes a call with m < 32, so its place in this
+  // function is free; it reads no other mode. Decided here only - what is queued, grouped, chained or folded never sees it -, from the
+  // descriptor, the batch count, the pointers' alignment and the CU count: allowed in strict mode. The alignment rules are the launcher's
+  // (launch_bf16_skinny: A, B, C 16-byte and the bias row 8-byte aligned, every leading dimension and stride a multiple of 8 elements);
+  // refused there, the call runs the launch it has with the mode off (launch_gemm).
+  if (env.skinny_bf16 != 0 && d.dtype == DT_BF16 && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.variant == V_GENERIC &&
+      skn_shape_ok(d.m, d.n, d.k, br, 16) && d.lda >= d.k && d.ldb >= d.n && d.ldc >= d.n && !((d.lda | d.ldb | d.ldc | d.stride_a | d.stride_b) & 7) &&
+      d.stride_a >= 0 && d.stride_b >= 0 && d.n < (1 << 30) && d.k < (1 << 30) && al.ab16 && al.c16 && bias_ok8) {
+    const int kind = !d.vnni_b ? 2 : d.vnni_factor == 4 ? 4 : 0;
+    const int bn = skinny_bf16_bn(d, kind, env.skinny_bf16, br, al.ab16);
+    if (bn > 0) {
+#define SK_NAMES(F) {{"brgemm_bf16_skinny" F "<16x16>", "brgemm_bf16_skinny" F "<16x32>", "brgemm_bf16_skinny" F "<16x64>"}, \
+                     {"brgemm_bf16_skinny" F "<32x16>", "brgemm_bf16_skinny" F "<32x32>", "brgemm_bf16_skinny" F "<32x64>"}}
+      static const char *const skinny_names[3][2][3] = {SK_NAMES(""), SK_NAMES("_flatb"), SK_NAMES("_vnni4")};
+#undef SK_NAMES
+      return launch(GL_BF16_SKINNY, bn, skinny_names[kind / 2][skn_mb((int)d.m) == 32][bn == 16 ? 0 : bn == 32 ? 1 : 2], 1, kind);
+    }
+  }
   // Edge tiles on the 256x256 tile, if asked for (xsmm_hip_set_dma256_edge, a switch of its own; brgemm_bf16_dma256_edge.hip,
   // brgemm_bf16_dma256_edge.h): a large call - m, n >= 256 - whose m or n the 256x256 tile does not divide, whatever kernel it is planned -
   // not forced - on and whichever of the three B images it has, on the ceil-divided grid of that tile. Mode 1: dma256_edge_rule; mode 2

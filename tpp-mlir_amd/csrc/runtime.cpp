@@ -579,6 +579,10 @@ extern "C" int xsmm_hip_set_dma256_edge(int mode) { return tpp::dma256_edge_mode
 extern "C" void xsmm_hip_dma256_edge_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_dma256_edge_stats[i].load(std::memory_order_relaxed);
 }
+extern "C" int xsmm_hip_set_skinny_bf16(int mode) { return tpp::skinny_bf16_mode_ok(mode) ? tpp::g_skinny_bf16.exchange(mode) : -1; }
+extern "C" void xsmm_hip_skinny_bf16_stats(int64_t out[5]) {
+  for (int i = 0; i < 5; ++i) out[i] = tpp::g_skinny_bf16_stats[i].load(std::memory_order_relaxed);
+}
 extern "C" int xsmm_hip_set_edge_k8_bf16(int mode) { return tpp::edge_k_bf16_mode_ok(mode) ? tpp::g_edge_k8_bf16.exchange(mode) : -1; }
 extern "C" void xsmm_hip_edge_k8_bf16_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k8_bf16_stats[i].load(std::memory_order_relaxed);

@@ -205,6 +205,17 @@ inline std::atomic<int> g_dma256_edge{[] {
   return dma256_edge_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_dma256_edge_stats[4]; // such launches; tile rows, tile columns (ceil-divided), B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
+// SKINNY-BATCH bf16 LAYERS (xsmm_hip_set_skinny_bf16 / TPP_HIP_SKINNY_BF16; gemm_plan.cpp plan_gemm_call, brgemm_bf16_skinny.hip
+// launch_bf16_skinny, brgemm_bf16_skinny.h): 0 = off, 1 = the rule (gemm_plan.cpp skinny_bf16_bn), 16 / 32 / 64 = every eligible whole-layer
+// call (bf16, 1 <= m <= 31, planned on the generic kernel) on column blocks of that width (tests, measurements). A switch of its own: it
+// reads no other mode and no other switch reads it.
+inline bool skinny_bf16_mode_ok(int v) { return v == 0 || v == 1 || v == 16 || v == 32 || v == 64; }
+inline std::atomic<int> g_skinny_bf16{[] {
+  const char *e = getenv("TPP_HIP_SKINNY_BF16");
+  const int v = e ? atoi(e) : 0;
+  return skinny_bf16_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_skinny_bf16_stats[5]; // such launches; workgroups, waves per workgroup, BN, B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
 // HALVES (xsmm_hip_set_f32_halves / TPP_HIP_F32_HALVES; gemm_plan.cpp choose_f32_halves, brgemm_f32_lw.hip launch_f32_lw_halves): 0 = off, 1 =
 // the rule (default: at least one 64x64 tile per CU), 2 = every eligible whole-layer call on the 64x64 + K2 f32 tile runs as two 64x32 + K2
 // workgroups per tile (the same bits).

@@ -125,6 +125,8 @@ _SIGNATURES = {
     "xsmm_hip_dma256_images_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_dma256_edge": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_dma256_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_skinny_bf16": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_skinny_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_dma256": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_dma256_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_f32_halves": (ctypes.c_int, [ctypes.c_int]),
@@ -443,6 +445,18 @@ class XsmmRuntime:
         """(edge-tile launches on the 256x256 tile; tile rows, tile columns, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_dma256_edge_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_skinny_bf16(self, mode):
+        """bf16 whole-layer calls with fewer than 32 rows (1 <= m <= 31, n >= BN, n % 8 == 0, k % 8 == 0) on the skinny-batch kernel, one
+        workgroup per block of BN columns: 0 off (default), 1 the rule, 16 / 32 / 64 that BN wherever eligible; returns the previous mode,
+        -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_skinny_bf16(mode)
+
+    def skinny_bf16_stats(self):
+        """(skinny-batch launches; workgroups, waves per workgroup, BN, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 5)()
+        self.lib.xsmm_hip_skinny_bf16_stats(out)
         return tuple(int(v) for v in out)
 
     def set_chain_dma256(self, mode):
