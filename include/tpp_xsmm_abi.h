@@ -542,6 +542,29 @@ TPP_XSMM_EXPORT void xsmm_hip_dma256_edge_stats(int64_t out[4]);
  * image (0 VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_skinny_bf16(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_skinny_bf16_stats(int64_t out[5]);
+/* A K split across workgroups for the skinny-batch kernel (opt-in; also TPP_HIP_SKINNY_SPLIT, read as a number). The skinny launch above
+ * has ceil(n / BN) workgroups - 64 for a 1024-wide layer on BN 16 -, too few to keep enough bytes of B in flight: it is bound by bytes in
+ * flight, not by HBM. With this switch on, a call that xsmm_hip_set_skinny_bf16 has put on the skinny kernel runs on
+ * brgemm_bf16_skinny_split<IMG, BN, MB> (brgemm_bf16_skinny_split.hip; maps in brgemm_bf16_skinny_split.h): the S = br * ceil(k / 32)
+ * steps of the call go to P_eff = min(P, S) parts in contiguous runs, ceil(n / BN) * P_eff workgroups in all, part-major. A part runs its
+ * steps as the unsplit kernel does, parks its f32 partial accumulators with write-through stores in the stream's scratch block and adds
+ * one to the column block's arrival counter; the LAST workgroup to arrive, whichever it is, resets the counter, sums ALL partials in part
+ * order and runs the unsplit epilogue (beta 1's C, bias, relu, one rounding). No workgroup waits for another and none need be resident
+ * together; a result's bits depend on br, k and P_eff alone, not on m, n, the block or the arrival order. They are NOT the bits of the
+ * unsplit kernel (another order of f32 additions); on exact inputs both are the oracle's.
+ * It refines the skinny launch and nothing else: with xsmm_hip_set_skinny_bf16 at 0 it changes nothing, BN and the m >= 17 gate stay that
+ * switch's, no other switch reads it and no other counter moves. P_eff < 2 is the plain skinny launch. The launcher refuses a launch
+ * with more than 4096 column blocks, more than 16 parts, more than 32 MiB of partials, or without a scratch block (no memory, a 17th
+ * stream, a stream being captured into a graph): the call then runs the UNSPLIT skinny launch of the same BN.
+ * mode 0 = off (default); 1 = the rule (gemm_plan.cpp skinny_split_parts, fitted to profiles/skinny_split_ab.txt); 2 .. 16 = that many
+ * parts P wherever eligible (test / measurement switches). Read per invoke; returns the previous mode, -1 (and changes nothing) for any
+ * other value. The choice depends on the descriptor, the batch count and the CU count only: made in strict mode too.
+ * xsmm_hip_last_refined_kernel reads "brgemm_bf16_skinny_split<MBxBN>", "..._split_flatb<MBxBN>" or "..._split_vnni4<MBxBN>".
+ * _stats: out[0] skinny launches that ran split since process start; of the most recent one: [1] P_eff, [2] workgroups (column blocks *
+ * P_eff). A split launch is still a skinny launch: xsmm_hip_skinny_bf16_stats counts it, with [1] = column blocks * P_eff and [2] = the
+ * waves of part 0. */
+TPP_XSMM_EXPORT int xsmm_hip_set_skinny_split(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_skinny_split_stats(int64_t out[3]);
 /* Layer chains on the 256x256 bf16 tile (opt-in; also TPP_HIP_CHAIN_DMA256, read as a number). Every chain form above is a form of the
  * loader-wave tiles (32x64 .. 128x128); a chain whose calls run on the 256x256 LDS-DMA tile - 16384 rows x 1024 columns are exactly 256
  * such tiles - ran call by call. With this switch on, xsmm_hip_fused_brgemm_chain_invoke runs such a chain as ONE launch of that tile's

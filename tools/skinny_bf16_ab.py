@@ -11,7 +11,14 @@ delivers 8.6 TB/s; B of every row but the largest fits the Infinity Cache, and b
 --controls: calls the switch must not touch, switch off / mode 1: the 4096-row three-layer 1024-wide chain as ONE step of ShardedMlp, and a
 1024 x 1024 x 1024 bf16 call. With --root <a checkout of another commit, built> the same rows run on that library (sides it has no setter
 for are left out): run the two alternately for a parent / tree comparison.
-    python tools/skinny_bf16_ab.py --out profiles/skinny_bf16_ab.txt"""
+--split: the K split across workgroups (xsmm_hip_set_skinny_split) instead. The sides of a row are, per BN that has an
+instance of the row's B image, the skinny kernel unsplit (`16`) and with P = 2, 4, 8, 16 parts forced (`16/2` ..), and `rule`: mode 1 of
+both switches. A gain is measured against the UNSPLIT skinny side of the same BN in the same round, not against the generic kernel: mode
+1 of the split switch may take a row on a P only where that P was faster in EVERY round. Per row the best side is named beside the 6.29
+TB/s of a copy. With --controls: the chain and the 1024^3 call, switches off / mode 1 of both, and the switch-off side of every row (on a
+library without the setters the same, for a parent / tree comparison).
+    python tools/skinny_bf16_ab.py --out profiles/skinny_bf16_ab.txt
+    python tools/skinny_bf16_ab.py --split --out profiles/skinny_split_ab.txt"""
 import argparse
 import importlib
 import os
@@ -36,6 +43,7 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--controls", action="store_true")
+    ap.add_argument("--split", action="store_true")
     ap.add_argument("--root", default=HERE)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -44,6 +52,9 @@ def main():
     pkg = importlib.import_module("tpp-mlir_amd")
     rt = pkg.get_runtime()
     has_switch = hasattr(rt, "set_skinny_bf16")
+    has_split = hasattr(rt, "set_skinny_split")
+    if args.split and not args.controls and not has_split:
+        sys.exit("--split: this library has no xsmm_hip_set_skinny_split")
     torch.cuda.set_device(0)
     rt.set_async(True)
     lines = []
@@ -52,9 +63,11 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    def mode(v):
+    def mode(v, parts=0):
         if has_switch:
             rt.set_skinny_bf16(v)
+        if has_split:
+            rt.set_skinny_split(parts)
 
     def timed(run):
         run()
@@ -83,9 +96,13 @@ def main():
         commit = subprocess.run(["git", "-C", root, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or "unknown"
     except OSError:
         commit = "unknown"
-    say("# skinny-batch bf16 layers (xsmm_hip_set_skinny_bf16): %s, one process, one GPU" % ("controls" if args.controls else "off / 16 / 32 / 64"))
+    if args.split:
+        say("# K split across workgroups of the skinny-batch bf16 kernel (xsmm_hip_set_skinny_split): %s, one process, one GPU" % (
+            "controls" if args.controls else "BN unsplit / BN with P = 2, 4, 8, 16 / mode 1 of both switches"))
+    else:
+        say("# skinny-batch bf16 layers (xsmm_hip_set_skinny_bf16): %s, one process, one GPU" % ("controls" if args.controls else "off / 16 / 32 / 64"))
     say("# box: %s, %d CUs; commit of the library's tree: %s, %s the switch; command: %s" % (
-        props.name, props.multi_processor_count, commit, "with" if has_switch else "WITHOUT", " ".join(sys.argv)))
+        props.name, props.multi_processor_count, commit, ("with" if has_split else "WITHOUT") if args.split else ("with" if has_switch else "WITHOUT"), " ".join(sys.argv)))
     say("# per side: %d invokes between two events, %d alternating rounds; us per invoke: median [min .. max]; B bytes / median" % (args.iters, args.pairs))
     say("# context: a device copy 6.29 TB/s, the Infinity Cache 8.6 TB/s (MI355X_MICROARCH)")
 
@@ -100,7 +117,7 @@ def main():
         mlp = pkg.ShardedMlp(spec, rt=rt)
 
         def chain(s):
-            mode(1 if s == "on" else 0)
+            mode(1 if s == "on" else 0, 1 if s == "on" and args.split else 0)
             us = timed(lambda: mlp.forward(x, ws, bs, acts))
             mode(0)
             return us
@@ -113,7 +130,7 @@ def main():
         h = rt.fused_brgemm_dispatch(BF16, m, n, 64, K, n, n, 64, 64 * n, 4 | VB, 0, 5, 4, 1)
 
         def call(s):
-            mode(1 if s == "on" else 0)
+            mode(1 if s == "on" else 0, 1 if s == "on" and args.split else 0)
             us = timed(lambda: rt.fused_brgemm(BF16, h, A, 0, B, 0, C, 0, D, 0, K // 64))
             mode(0)
             return us
@@ -123,7 +140,7 @@ def main():
             say(name % (mlp.last_step_fused if one is chain else ""))
             for s in sides:
                 say("    %-3s %8.2f [%8.2f .. %8.2f]" % (s, statistics.median(t[s]), min(t[s]), max(t[s])))
-    else:
+    if not args.controls or args.split:
         for image, m, n, K in ROWS:
             k, br = (64, K // 64) if K % 64 == 0 else (K, 1)
             A = (torch.rand(m, K, device="cuda") * 2 - 1).to(torch.bfloat16)
@@ -137,29 +154,45 @@ def main():
             names = {}
 
             def one(s):
-                mode(0 if s == "off" else int(s))
+                if s == "rule":
+                    mode(1, 1)
+                else:
+                    bn, _, parts = s.partition("/")
+                    mode(0 if bn == "off" else int(bn), int(parts or 0))
                 us = timed(lambda: rt.fused_brgemm(BF16, h, A, 0, B, 0, C, 0, D, 0, br))
                 names[s] = rt.last_refined_kernel() or rt.kernel_name(h)
                 mode(0)
                 return us
 
-            sides = ["off"] + ([str(bn) for bn in (16, 32, 64) if not (image == 0 and bn == 16)] if has_switch else [])
+            bns = [str(bn) for bn in (16, 32, 64) if not (image == 0 and bn == 16)]
+            if args.controls:
+                sides = ["off"]
+            elif args.split:
+                sides = [b + p for b in bns for p in ("", "/2", "/4", "/8", "/16")] + ["rule"]
+            else:
+                sides = ["off"] + (bns if has_switch else [])
             rule = "-"
             if has_switch:
-                rt.set_skinny_bf16(1)
-                before = rt.skinny_bf16_stats()[0]
+                mode(1, 1 if args.split else 0)
+                before, sbefore = rt.skinny_bf16_stats()[0], rt.skinny_split_stats()[0] if has_split else 0
                 rt.fused_brgemm(BF16, h, A, 0, B, 0, C, 0, D, 0, br)
                 torch.cuda.synchronize()
                 after = rt.skinny_bf16_stats()
                 rule = "BN %d" % after[3] if after[0] > before else "refuses"
-                rt.set_skinny_bf16(0)
+                if has_split and args.split and after[0] > before:
+                    rule += ", P %d" % rt.skinny_split_stats()[1] if rt.skinny_split_stats()[0] > sbefore else ", unsplit"
+                mode(0)
             t = rounds(sides, one)
             med = {s: statistics.median(t[s]) for s in sides}
             say("%-6s m %2d  n %4d  K %4d (br %2d x k %4d)  B %5.2f MiB  mode 1: %s" % (INAME[image], m, n, K, br, k, 2.0 * K * n / 2 ** 20, rule))
             for s in sides:
-                wins = "" if s == "off" else "  %+6.1f %%, faster than off in %d of %d rounds" % (
-                    100.0 * (med[s] - med["off"]) / med["off"], sum(b < a for a, b in zip(t["off"], t[s])), args.pairs)
-                say("    %-3s %8.2f [%8.2f .. %8.2f]  %5.2f TB/s  %s%s" % (s, med[s], min(t[s]), max(t[s]), 2.0 * K * n / med[s] * 1e-6, names[s], wins))
+                base = s.partition("/")[0] if args.split else "off"  # --split: the unsplit skinny side of the same BN
+                wins = "" if s == base or base not in t else "  %+6.1f %%, faster than %s in %d of %d rounds" % (
+                    100.0 * (med[s] - med[base]) / med[base], base, sum(b < a for a, b in zip(t[base], t[s])), args.pairs)
+                say("    %-5s %8.2f [%8.2f .. %8.2f]  %5.2f TB/s  %s%s" % (s, med[s], min(t[s]), max(t[s]), 2.0 * K * n / med[s] * 1e-6, names[s], wins))
+            if args.split and not args.controls:
+                best = min(sides, key=lambda s_: med[s_])
+                say("    best: %s %.2f us, %.2f TB/s (a device copy: 6.29 TB/s)" % (best, med[best], 2.0 * K * n / med[best] * 1e-6))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

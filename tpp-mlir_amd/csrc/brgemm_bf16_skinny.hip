@@ -215,11 +215,14 @@ template <int IMG, int BN> static hipError_t launch_bf16_skinny_t(const GemmArgs
 //   lda >= k, ldb >= n, ldc >= n; lda, ldb, ldc, stride_a and stride_b multiples of 8 elements; A, B and C 16-byte aligned - every load of A
 //   (16 bytes), of a row piece of B (4 .. 16 bytes) and every piece of C (2 .. 8 bytes) is then naturally aligned -; the bias row 8-byte
 //   aligned (pieces of 2 .. 8 bytes at multiples of 8 columns); no VNNI C.
+// (bf16_skinny_args_ok: the same answer for the split launcher, brgemm_bf16_skinny_split.hip)
+bool bf16_skinny_args_ok(int b_kind, int bn, const GemmArgs &a) {
+  if (!skn_instance_exists(b_kind, bn) || !skn_shape_ok(a.m, a.n, a.k, a.br, bn)) return false;
+  if (a.lda < a.k || a.ldb < a.n || a.ldc < a.n || ((a.lda | a.ldb | a.ldc | a.stride_a | a.stride_b) & 7) || a.stride_a < 0 || a.stride_b < 0) return false;
+  return !((((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.C) & 15) || ((a.ep & EP_BIAS) && (!a.D || ((uintptr_t)a.D & 7))) || (a.ep & EP_VNNI_C));
+}
 hipError_t launch_bf16_skinny(int b_kind, int bn, const GemmArgs &a, hipStream_t s) {
-  if (!skn_instance_exists(b_kind, bn) || !skn_shape_ok(a.m, a.n, a.k, a.br, bn)) return hipErrorInvalidValue;
-  if (a.lda < a.k || a.ldb < a.n || a.ldc < a.n || ((a.lda | a.ldb | a.ldc | a.stride_a | a.stride_b) & 7) || a.stride_a < 0 || a.stride_b < 0)
-    return hipErrorInvalidValue;
-  if ((((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.C) & 15) || ((a.ep & EP_BIAS) && (!a.D || ((uintptr_t)a.D & 7))) || (a.ep & EP_VNNI_C)) return hipErrorInvalidValue;
+  if (!bf16_skinny_args_ok(b_kind, bn, a)) return hipErrorInvalidValue;
   switch (b_kind * 100 + bn) {
   case 16: return launch_bf16_skinny_t<0, 16>(a, s);
   case 32: return launch_bf16_skinny_t<0, 32>(a, s);

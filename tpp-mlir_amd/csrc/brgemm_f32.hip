@@ -29,7 +29,7 @@
 #include "brgemm_f32_lw_kedge.h"
 #include "brgemm_bf16_lw_kedge.h"
 #include "brgemm_bf16_dma256_edge.h"
-#include "brgemm_bf16_skinny.h"
+#include "brgemm_bf16_skinny_split.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -695,6 +695,7 @@ hipError_t launch_gemm_bf16_fast(int tile, const GemmArgs &a, hipStream_t s); //
 hipError_t launch_bf16_dma256_image(int b_kind, const GemmArgs &a, hipStream_t s); // brgemm_bf16_dma256.hip
 hipError_t launch_bf16_dma256_edge(int b_kind, const GemmArgs &a, hipStream_t s); // brgemm_bf16_dma256_edge.hip: m or n not a multiple of 256; hipErrorInvalidValue: not launched
 hipError_t launch_bf16_skinny(int b_kind, int bn, const GemmArgs &a, hipStream_t s); // brgemm_bf16_skinny.hip: 1 <= m <= 31 on column blocks of bn; hipErrorInvalidValue: not launched
+hipError_t launch_bf16_skinny_split(int b_kind, int bn, int parts, const GemmArgs &a, hipStream_t s); // brgemm_bf16_skinny_split.hip: the same over parts workgroups per column block; hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         // brgemm_f32_lw.hip (tile 4: 128x64, forced variant 10 only - it measures within 2 % of brgemm_f32_fast<128x64>)
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
@@ -737,7 +738,8 @@ static GemmPlanEnv gemm_plan_env() {
                      g_edge_tiles.load(std::memory_order_relaxed), g_edge_k.load(std::memory_order_relaxed),
                      g_edge_k_bf16.load(std::memory_order_relaxed), g_f32_halves.load(std::memory_order_relaxed),
                      g_edge_k8_bf16.load(std::memory_order_relaxed), g_dma256_images.load(std::memory_order_relaxed),
-                     g_dma256_edge.load(std::memory_order_relaxed), g_skinny_bf16.load(std::memory_order_relaxed)};
+                     g_dma256_edge.load(std::memory_order_relaxed), g_skinny_bf16.load(std::memory_order_relaxed),
+                     g_skinny_split.load(std::memory_order_relaxed)};
 }
 bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, gemm_plan_env()); }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, gemm_plan_env()); }
@@ -802,7 +804,7 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
   case GL_BF16_FAST:
     if (p.edge) return p.tile == 2 ? launch_bf16_dma256_edge(p.b_kind, a, s) : hipErrorInvalidValue;
     return p.b_kind != 0 ? (p.tile == 2 ? launch_bf16_dma256_image(p.b_kind, a, s) : hipErrorInvalidValue) : launch_gemm_bf16_fast(p.tile, a, s);
-  case GL_BF16_SKINNY: return launch_bf16_skinny(p.b_kind, p.tile, a, s);
+  case GL_BF16_SKINNY: return p.split > 1 ? launch_bf16_skinny_split(p.b_kind, p.tile, p.split, a, s) : launch_bf16_skinny(p.b_kind, p.tile, a, s);
   case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split);
   case GL_BF16_GROUPED64: return launch_bf16_grouped64(a, wi, n_items, s);
   case GL_BF16_LW:
@@ -834,11 +836,23 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   if (p.launcher == GL_NONE) return hipSuccess;
   const GemmArgs a = gemm_args(d, A, B, C, D, (int)(br < 0 ? 0 : br));
   if (p.launcher == GL_BF16_SKINNY) { // a skinny-batch bf16 layer (xsmm_desc.h g_skinny_bf16; brgemm_bf16_skinny.h)
-    const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    if (e == hipErrorInvalidValue && p.split > 1) { // the split refused by its launcher (xsmm_desc.h g_skinny_split): the unsplit skinny launch of the same BN
+      (void)hipGetLastError();
+      env.skinny_split = 0;
+      p = plan_gemm_call(d, br, al, env);
+      e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    }
     if (e != hipErrorInvalidValue) {
       if (e == hipSuccess) {
-        g_skinny_bf16_stats[1].store(skn_blocks(a.n, p.tile), std::memory_order_relaxed);
-        g_skinny_bf16_stats[2].store(skn_waves((long long)a.br * skn_steps(a.k)), std::memory_order_relaxed);
+        const long long s_all = (long long)a.br * skn_steps(a.k);
+        if (p.split > 1) {
+          g_skinny_split_stats[1].store(p.split, std::memory_order_relaxed);
+          g_skinny_split_stats[2].store(sks_grid(skn_blocks(a.n, p.tile), p.split), std::memory_order_relaxed);
+          g_skinny_split_stats[0].fetch_add(1, std::memory_order_relaxed);
+        }
+        g_skinny_bf16_stats[1].store(sks_grid(skn_blocks(a.n, p.tile), p.split), std::memory_order_relaxed);
+        g_skinny_bf16_stats[2].store(p.split > 1 ? sks_block_waves(p.split, (int)s_all) : skn_waves(s_all), std::memory_order_relaxed);
         g_skinny_bf16_stats[3].store(p.tile, std::memory_order_relaxed);
         g_skinny_bf16_stats[4].store(p.b_kind, std::memory_order_relaxed);
         g_skinny_bf16_stats[0].fetch_add(1, std::memory_order_relaxed);

@@ -7,6 +7,7 @@
 #include "brgemm_bf16_dma256_images.h"
 #include "brgemm_bf16_dma256_chain.h"
 #include "brgemm_bf16_skinny.h"
+#include "brgemm_bf16_skinny_split.h"
 #include <string.h>
 
 namespace tpp {
@@ -392,6 +393,43 @@ static int skinny_bf16_bn(const GemmDesc &d, int kind, int mode, int64_t br, boo
   int bn = 2 * br * d.k * d.n >= SKINNY_LINE_BYTES ? line : smallest;
   while (bn > smallest && d.n < bn) bn /= 2;
   return d.n >= bn ? bn : 0;
+}
+
+// K SPLIT ACROSS WORKGROUPS OF A SKINNY-BATCH LAUNCH (xsmm_hip_set_skinny_split, opt-in; brgemm_bf16_skinny_split.hip,
+// brgemm_bf16_skinny_split.h): the parts P_eff of a call already on the skinny kernel with column blocks of bn, or 1: the plain skinny
+// launch. Modes 2 .. 16 (tests, measurements): P = the mode. Reads the descriptor, the batch count and the CU count only.
+// Mode 1, THE RULE, from profiles/skinny_split_ab.txt (one box, 256 CUs, beta 0 + bias + relu, five alternating rounds, us per call, the
+// UNSPLIT skinny launch of the same BN -> P = 2 / 4 / 8 / 16; a P is taken only where it was faster in EVERY round). This replaces the
+// provisional rule min(SPLIT_MAX, cus / blocks, S_all / 8), which took P 4 on 1024 x 1024 (n x K), 1000 x 1000 and 1024 x 4096 and lost there.
+//   The hand-off costs about 1 us at P 2 and 2 us at P 4 on a call of 4 us, and grows with P: 1024 x 1024 m 1 on BN 16 3.91 -> 4.91 / 5.92 /
+//   7.78 / 11.95. It pays only where a workgroup of the unsplit launch streams long enough to hide it. What decides is the bytes of B per
+//   workgroup, 2 BN br k:
+//   256 KiB and more, EVERY row, image and m (1, 8, 16, 31) gains in every round: 4096 x 4096 VNNI-2 BN 32 (128 blocks) m 1 / 8 / 16 / 31 9.07 /
+//     10.53 / 10.90 / 15.09 -> P 2 8.17 / 9.22 / 9.33 / 12.29 (P 4 8.47 / 9.61 / 10.05 / 13.28); BN 64 (64 blocks, 512 KiB) 10.00 / 11.70 / 11.94 /
+//     16.54 -> P 4 8.30 / 9.70 / 9.72 / 12.64 (P 2 less, P 8 level or slower); flat m 8 BN 64 14.77 -> P 4 10.40 (P 2 11.80), BN 32 15.23 -> P 2
+//     14.62; VNNI-4 m 8 BN 32 10.00 -> P 2 9.06, BN 64 11.64 -> P 4 9.74; 1024 x 4096 BN 32 (32 blocks) m 1 / 8 / 16 / 31 7.46 / 9.20 / 10.33 / 14.69 ->
+//     P 2 6.81 / 7.99 / 8.48 / 11.40, BN 64 (16 blocks) 8.16 / 9.98 / 11.01 / 15.99 -> P 4 6.99 / 8.33 / 8.44 / 11.22.
+//   128 KiB: mixed - 1024 x 4096 BN 16 (64 blocks) m 1 / 8 / 16 5.74 / 6.65 / 7.68 -> P 2 6.02 / 6.61 / 7.02, P 4 6.52 / 7.01 / 7.17 (m 1 loses in
+//     every round); 4096 x 4096 BN 16 (256 blocks) and VNNI-4 BN 16 8.32 -> 9.44 lose; every BN 64 row of K = 1024 loses. Not taken.
+//   Less (1024 x 1024, 4096 x 1024, 1000 x 1000 on every BN): every P loses in every round, by 5 .. 50 % at P 2. Not taken.
+//   P 8 gains less than P 4 wherever both gain, P 16 loses on every row but 1024 x 4096 m 31.
+// So: P = 4, else 2, where the parts fit the compute units in one round (blocks * P <= cus) and a part keeps at least 128 KiB of B
+// (2 BN br k >= P * 128 KiB); else the plain launch. On every measured (row, BN) this takes, that P was faster in every round, and it takes
+// nothing else. With mode 1 of the skinny switch (which picks BN) it splits 4096 x 4096: VNNI-2 BN 32 P 2, flat BN 64 P 4; VNNI-4 stays on BN 16
+// unsplit (8.32, the fastest side of its row). Not measured: other CU counts (the rule reads them only through blocks * P <= cus), several
+// ranks, beta 1, other grid orders, K beyond 4096.
+constexpr int64_t SKINNY_PART_BYTES = 128 << 10; // a part streams at least this many bytes of B
+static int skinny_split_parts(const GemmDesc &d, int bn, int mode, int64_t br, int64_t cus) {
+  const int64_t s_all = br * skn_steps((int)d.k), blocks = skn_blocks((int)d.n, bn);
+  int P = mode;
+  if (mode == 1) {
+    P = 1;
+    for (int c : {4, 2})
+      if (P == 1 && blocks * c <= cus && 2 * bn * br * d.k >= c * SKINNY_PART_BYTES) P = c;
+  }
+  if (P < 2 || P > SKS_PMAX) return 1;
+  const int p_eff = sks_parts(P, s_all);
+  return p_eff >= 2 ? p_eff : 1;
 }
 
 // RAGGED k, bf16 (xsmm_hip_set_edge_k_bf16, opt-in; brgemm_bf16_lw_kedge.h): a whole-layer bf16 call whose k is a multiple of 16 but not of
@@ -1198,7 +1236,9 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
   // function is free; it reads no other mode. Decided here only - what is queued, grouped, chained or folded never sees it -, from the
   // descriptor, the batch count, the pointers' alignment and the CU count: allowed in strict mode. The alignment rules are the launcher's
   // (launch_bf16_skinny: A, B, C 16-byte and the bias row 8-byte aligned, every leading dimension and stride a multiple of 8 elements);
-  // refused there, the call runs the launch it has with the mode off (launch_gemm).
+  // refused there, the call runs the launch it has with the mode off (launch_gemm). The one switch read inside this block is
+  // xsmm_hip_set_skinny_split: the K range of the launch over several workgroups per column block (split, text); a split refused by ITS
+  // launcher runs the unsplit launch of the same BN.
   if (env.skinny_bf16 != 0 && d.dtype == DT_BF16 && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.variant == V_GENERIC &&
       skn_shape_ok(d.m, d.n, d.k, br, 16) && d.lda >= d.k && d.ldb >= d.n && d.ldc >= d.n && !((d.lda | d.ldb | d.ldc | d.stride_a | d.stride_b) & 7) &&
       d.stride_a >= 0 && d.stride_b >= 0 && d.n < (1 << 30) && d.k < (1 << 30) && al.ab16 && al.c16 && bias_ok8) {
@@ -1207,9 +1247,12 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
     if (bn > 0) {
 #define SK_NAMES(F) {{"brgemm_bf16_skinny" F "<16x16>", "brgemm_bf16_skinny" F "<16x32>", "brgemm_bf16_skinny" F "<16x64>"}, \
                      {"brgemm_bf16_skinny" F "<32x16>", "brgemm_bf16_skinny" F "<32x32>", "brgemm_bf16_skinny" F "<32x64>"}}
-      static const char *const skinny_names[3][2][3] = {SK_NAMES(""), SK_NAMES("_flatb"), SK_NAMES("_vnni4")};
+      static const char *const skinny_names[2][3][2][3] = {{SK_NAMES(""), SK_NAMES("_flatb"), SK_NAMES("_vnni4")},
+                                                           {SK_NAMES("_split"), SK_NAMES("_split_flatb"), SK_NAMES("_split_vnni4")}};
 #undef SK_NAMES
-      return launch(GL_BF16_SKINNY, bn, skinny_names[kind / 2][skn_mb((int)d.m) == 32][bn == 16 ? 0 : bn == 32 ? 1 : 2], 1, kind);
+      // the K range of the launch over several workgroups per column block, if asked for (xsmm_hip_set_skinny_split): read here only
+      const int parts = env.skinny_split != 0 ? skinny_split_parts(d, bn, env.skinny_split, br, cus) : 1;
+      return launch(GL_BF16_SKINNY, bn, skinny_names[parts > 1][kind / 2][skn_mb((int)d.m) == 32][bn == 16 ? 0 : bn == 32 ? 1 : 2], parts, kind);
     }
   }
   // Edge tiles on the 256x256 tile, if asked for (xsmm_hip_set_dma256_edge, a switch of its own; brgemm_bf16_dma256_edge.hip,

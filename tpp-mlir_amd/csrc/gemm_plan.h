@@ -49,8 +49,9 @@ enum GemmVariant : int {
 // xsmm_hip_set_edge_k_bf16 (0 = off, 1 = the bf16 tile rule, 20 .. 23 = that bf16 GemmVariant's tile) and xsmm_hip_set_f32_halves (0 = off, 1 =
 // the rule, 2 = wherever eligible) and xsmm_hip_set_edge_k8_bf16 (the values of edge_k_bf16, for k % 16 == 8) and xsmm_hip_set_dma256_images
 // (0 = off, 1 = the rule, 2 = wherever eligible) and xsmm_hip_set_dma256_edge (the same values) and xsmm_hip_set_skinny_bf16 (0 = off, 1 = the
-// rule, 16 / 32 / 64 = that column-block width wherever eligible); brgemm_f32.hip gemm_plan_env fills it per call
-struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; int dma256_edge = 0; int skinny_bf16 = 0; };
+// rule, 16 / 32 / 64 = that column-block width wherever eligible) and xsmm_hip_set_skinny_split (0 = off, 1 = the rule, 2 .. 16 = that many parts
+// wherever eligible); brgemm_f32.hip gemm_plan_env fills it per call
+struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; int dma256_edge = 0; int skinny_bf16 = 0; int skinny_split = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
 struct GemmAlign { bool ab16, c16, c8, d8, d16; };
@@ -71,7 +72,7 @@ enum GemmLauncher : int {
   GL_BF16_LW_GROUPED, // launch_bf16_lw_grouped(tile, b_kind, even)
   GL_BF16_LW_QUADS,   // launch_bf16_lw_quads(b_kind)
   GL_GENERIC,         // brgemm_grouped<T, VNNI, VEC, VF, FORM>: generic
-  GL_BF16_SKINNY,     // launch_bf16_skinny(b_kind, tile): tile = the column-block width BN 16 / 32 / 64 (xsmm_hip_set_skinny_bf16; brgemm_bf16_skinny.hip)
+  GL_BF16_SKINNY,     // launch_bf16_skinny(b_kind, tile): tile = the column-block width BN 16 / 32 / 64 (xsmm_hip_set_skinny_bf16; brgemm_bf16_skinny.hip); split > 1 (xsmm_hip_set_skinny_split): launch_bf16_skinny_split(b_kind, tile, split) first
 };
 // the instances of the generic kernel brgemm_grouped<T, VNNI, VEC, VF>: <float, false, false / true>, <unsigned short, true, false / true>,
 // <unsigned short, true, true, 4>, <unsigned short, false, false>; and the f32 instances whose FORM argument says that an operand is
@@ -80,7 +81,7 @@ enum GemmGeneric : int { GG_F32, GG_F32_VEC, GG_BF16_VNNI2, GG_BF16_VNNI2_VEC, G
 struct GemmLaunch {
   GemmLauncher launcher;
   int tile;        // the launcher's tile index (GL_BF16_SKINNY: the column-block width BN)
-  int split;       // workgroups per output tile (1 = none)
+  int split;       // workgroups per output tile (1 = none; GL_BF16_SKINNY: the parts P_eff of a column block)
   int b_kind;      // B image of the bf16 loader-wave tiles and of the 256x256 tile: 0 VNNI-2, 2 flat, 4 VNNI-4
   bool even;       // GL_BF16_LW_GROUPED: every item has an even chunk count
   bool vec;        // GL_F32_X6: A and B 16-byte aligned
@@ -114,6 +115,9 @@ bool plan_gemm(GemmDesc &d, int forced_variant, const GemmPlanEnv &env);
 // {dma256_images}, f32 edge tiles {edge_tiles}, f32 ragged k {edge_k, edge_tiles}, tail split {tail_split}, halves {halves}; plan_gemm reads none.
 // Skinny-batch bf16 layers {skinny_bf16} stand outside that list: they take bf16 calls with m < 32 planned on the generic kernel, which
 // no other refinement takes (each asks for m >= 32), so the partition depends on the descriptor alone (tests/test_gemm_plan_skinny.py).
+// The K split across workgroups of such a launch, xsmm_hip_set_skinny_split {skinny_split, skinny_bf16}, is read INSIDE that block only - for
+// a call already put on GL_BF16_SKINNY - and sets split and text, nothing else: with skinny_bf16 at 0 it is never read, BN and the m >= 17
+// gate do not read it, and no other refinement does (tests/test_gemm_plan_skinny_split.py).
 GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br, const GemmAlign &al, const GemmPlanEnv &env);
 // n_items invokes of one descriptor in one launch (launch_gemm_grouped; vec_ok / out_ok / pair_ok / br_hint as there)
 GemmLaunch plan_gemm_group(const GemmDesc &d, int n_items, bool vec_ok, bool out_ok, bool pair_ok, int64_t br_hint, const GemmPlanEnv &env);

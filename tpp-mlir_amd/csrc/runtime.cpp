@@ -580,6 +580,10 @@ extern "C" void xsmm_hip_dma256_edge_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_dma256_edge_stats[i].load(std::memory_order_relaxed);
 }
 extern "C" int xsmm_hip_set_skinny_bf16(int mode) { return tpp::skinny_bf16_mode_ok(mode) ? tpp::g_skinny_bf16.exchange(mode) : -1; }
+extern "C" int xsmm_hip_set_skinny_split(int mode) { return tpp::skinny_split_mode_ok(mode) ? tpp::g_skinny_split.exchange(mode) : -1; }
+extern "C" void xsmm_hip_skinny_split_stats(int64_t out[3]) {
+  for (int i = 0; i < 3; ++i) out[i] = tpp::g_skinny_split_stats[i].load(std::memory_order_relaxed);
+}
 extern "C" void xsmm_hip_skinny_bf16_stats(int64_t out[5]) {
   for (int i = 0; i < 5; ++i) out[i] = tpp::g_skinny_bf16_stats[i].load(std::memory_order_relaxed);
 }

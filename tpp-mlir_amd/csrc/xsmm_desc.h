@@ -216,6 +216,17 @@ inline std::atomic<int> g_skinny_bf16{[] {
   return skinny_bf16_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_skinny_bf16_stats[5]; // such launches; workgroups, waves per workgroup, BN, B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
+// K SPLIT ACROSS WORKGROUPS OF THE SKINNY-BATCH KERNEL (xsmm_hip_set_skinny_split / TPP_HIP_SKINNY_SPLIT; gemm_plan.cpp plan_gemm_call,
+// brgemm_bf16_skinny_split.hip launch_bf16_skinny_split, brgemm_bf16_skinny_split.h): 0 = off, 1 = the rule (gemm_plan.cpp skinny_split_parts),
+// 2 .. 16 = that many parts wherever eligible (tests, measurements). A refinement of the skinny launch and nothing else: read only for a
+// call the planner has already put on the skinny kernel; with xsmm_hip_set_skinny_bf16 off it changes nothing. No other switch reads it.
+inline bool skinny_split_mode_ok(int v) { return v >= 0 && v <= 16; }
+inline std::atomic<int> g_skinny_split{[] {
+  const char *e = getenv("TPP_HIP_SKINNY_SPLIT");
+  const int v = e ? atoi(e) : 0;
+  return skinny_split_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_skinny_split_stats[3]; // skinny launches that ran split; parts P_eff, workgroups (column blocks * P_eff) of the latest
 // HALVES (xsmm_hip_set_f32_halves / TPP_HIP_F32_HALVES; gemm_plan.cpp choose_f32_halves, brgemm_f32_lw.hip launch_f32_lw_halves): 0 = off, 1 =
 // the rule (default: at least one 64x64 tile per CU), 2 = every eligible whole-layer call on the 64x64 + K2 f32 tile runs as two 64x32 + K2
 // workgroups per tile (the same bits).

@@ -127,6 +127,8 @@ _SIGNATURES = {
     "xsmm_hip_dma256_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_skinny_bf16": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_skinny_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_skinny_split": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_skinny_split_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_dma256": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_dma256_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_f32_halves": (ctypes.c_int, [ctypes.c_int]),
@@ -457,6 +459,18 @@ class XsmmRuntime:
         """(skinny-batch launches; workgroups, waves per workgroup, BN, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 5)()
         self.lib.xsmm_hip_skinny_bf16_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_skinny_split(self, mode):
+        """the K range of a skinny-batch launch (set_skinny_bf16) over several workgroups per column block: 0 off (default), 1 the rule,
+        2 .. 16 that many parts wherever eligible; changes nothing while set_skinny_bf16 is 0; returns the previous mode, -1 for a value
+        it refuses"""
+        return self.lib.xsmm_hip_set_skinny_split(mode)
+
+    def skinny_split_stats(self):
+        """(skinny-batch launches that ran split; parts, workgroups - column blocks * parts - of the most recent one)"""
+        out = (ctypes.c_int64 * 3)()
+        self.lib.xsmm_hip_skinny_split_stats(out)
         return tuple(int(v) for v in out)
 
     def set_chain_dma256(self, mode):
