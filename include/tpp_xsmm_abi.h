@@ -590,6 +590,32 @@ TPP_XSMM_EXPORT void xsmm_hip_skinny_split_stats(int64_t out[3]);
  * rounds ceil(m / 256 / G), [3] the B image (0 VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_chain_dma256(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_chain_dma256_stats(int64_t out[4]);
+/* Skinny-batch layer chains (opt-in; also TPP_HIP_CHAIN_SKINNY, read as a number; a refused value leaves 0). Every chain form above asks for
+ * m >= 32, so a chain with 1 .. 31 rows - decode, small-batch inference - ran call by call. With this switch on,
+ * xsmm_hip_fused_brgemm_chain_invoke runs such a chain as ONE launch of the skinny-batch kernel's chain form (brgemm_bf16_skinny_chain): G
+ * resident workgroups, workgroup w computing the column blocks w, w + G, .. of BN columns of every layer, layer by layer, each block as
+ * the single skinny call computes it. The hand-off between layers is the chain's: write-through stores, ONE counter per seam that only
+ * grows (a launch adds G), a bounded wait that ends in the error word, never in a hang; the next layer's weights are requested ahead of
+ * the wait. Probation, the journal and the re-run of a starved launch are the ones described at xsmm_hip_fused_brgemm_chain_invoke.
+ * Every output is bit for bit the same calls made one by one under xsmm_hip_set_skinny_bf16(BN) with xsmm_hip_set_skinny_split(0).
+ * A chain is eligible when all of this holds: 2 .. 8 calls, all bf16 and beta 0 with the same m in 1 .. 31, no VNNI C, no forced kernel,
+ * one B image (VNNI-2, flat or VNNI-4), per call n >= BN, n % 8 == 0, k >= 8, k % 8 == 0, a batch count >= 1, leading dimensions that
+ * cover their operands and, like the strides, are multiples of 8 elements, lda and ldc below 2^24 - the widths may differ from call to
+ * call - and what every chain launch asks: asynchronous mode, no stream capture, A, B, C 16-byte and bias rows 8-byte aligned, each
+ * call reading its predecessor's output, batch elements inside their rows, device operands, no overlaps. Strict mode
+ * (xsmm_hip_set_strict) stays call by call: the launch has the bits of the skinny kernel, not of the calls as dispatched. Everything
+ * else - every chain with m >= 32, and every chain with the mode 0 - is decided exactly as without this switch. It reads neither
+ * xsmm_hip_set_skinny_bf16 nor xsmm_hip_set_skinny_split, which decide single calls only, and neither reads it.
+ * mode 0 = off (default); 1 = the rule: the smallest BN with an instance, G = min(column blocks of the widest layer, compute units),
+ * subject to the measured gate of gemm_plan.cpp plan_chain_skinny (profiles/chain_skinny_ab.txt): a chain with a layer of more than 2 MiB
+ * of B, and a chain with a flat or a VNNI-4 B, stays call by call - 1024-wide VNNI-2 MLPs gain 22 .. 31 % at m <= 16, 4096-wide ones lose
+ * 14 % and more to the split single calls; 16 / 32 / 64 = that BN wherever eligible, never gated; 1000 * G + BN,
+ * 1 <= G <= 512 = that BN on G resident workgroups, refused where G exceeds the compute units (tests, measurements). Read per invoke;
+ * returns the previous mode, -1 (and changes nothing) for any other value.
+ * _stats: out[0] such launches since process start; of the most recent one: [1] resident workgroups G, [2] BN, [3] the B image (0
+ * VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches, xsmm_hip_skinny_bf16_stats among them, do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_skinny(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_skinny_stats(int64_t out[4]);
 /* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
  * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
  * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two

@@ -30,7 +30,7 @@ struct ChainArgs {
   int nlayers;
   int tiles_m, tiles_n; // filled by the launcher
   int xm;               // filled by the launcher: XCD grid xm x (8 / xm) over the tile grid, 0 = linear tile order
-  int groups;           // a multi-round chain (launch_bf16_chain, BLW_CHAIN_ROUNDS): resident row groups G, the grid is G x tiles_n; column rounds (launch_bf16_chain_wrounds): resident workgroup columns W; 0 in every other launch
+  int groups;           // a multi-round chain (launch_bf16_chain, BLW_CHAIN_ROUNDS): resident row groups G, the grid is G x tiles_n; column rounds (launch_bf16_chain_wrounds): resident workgroup columns W; a skinny-batch chain (launch_bf16_skinny_chain): the resident workgroups G; 0 in every other launch
   // Unused. Keeps L at byte 72 of the argument block: without these bytes every L[] load moves and the compiler assigns
   // registers differently in the f32 chain kernels' K loop, a code change that would have to be measured on its own.
   char reserved[8];
@@ -73,6 +73,12 @@ hipError_t launch_bf16_chain_wragged(int tile, int b_kind, const ChainArgs &a, h
 // round, G = m / 256); the grid is G x n / 256 workgroups, at most the stream's compute units - the caller's guarantee. Refuses with
 // hipErrorInvalidValue, launching nothing, whatever the kernel cannot run
 hipError_t launch_bf16_dma256_chain(int b_kind, const ChainArgs &a, hipStream_t s);
+// a chain of SKINNY-BATCH layers (brgemm_bf16_skinny_chain.hip, xsmm_hip_set_chain_skinny; schedule in brgemm_bf16_skinny_chain.h): 1 <= m <= 31
+// rows, layer l of a.L[l].pad columns (n >= bn, n % 8 == 0) and k(l) >= 8 in multiples of 8, beta 0, on column blocks of bn = 16 / 32 / 64;
+// b_kind 0 VNNI-2 / 2 flat / 4 VNNI-4; a.groups = G resident workgroups, the grid, at most the stream's compute units - the caller's
+// guarantee; ONE counter per seam, cnt[l] reaches a.target = epoch * G. Refuses with hipErrorInvalidValue, launching nothing, whatever
+// the kernel does not assume (the list stands at the launcher)
+hipError_t launch_bf16_skinny_chain(int b_kind, int bn, const ChainArgs &a, hipStream_t s);
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2; b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);

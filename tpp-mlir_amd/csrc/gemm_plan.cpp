@@ -8,6 +8,7 @@
 #include "brgemm_bf16_dma256_chain.h"
 #include "brgemm_bf16_skinny.h"
 #include "brgemm_bf16_skinny_split.h"
+#include "brgemm_bf16_skinny_chain.h"
 #include <string.h>
 
 namespace tpp {
@@ -959,6 +960,75 @@ ChainDma256Plan plan_chain_dma256(int64_t m, int64_t n, int nlayers, const int64
   return ChainDma256Plan{true, groups, "", false};
 }
 
+// SKINNY-BATCH LAYER CHAINS (xsmm_hip_set_chain_skinny, opt-in; brgemm_bf16_skinny_chain.hip, brgemm_bf16_skinny_chain.h; gemm_plan.h has the contract).
+int chain_skinny_b_kind(const GemmDesc &d, const char **why) {
+  auto no = [&](const char *w) {
+    if (why) *why = w;
+    return -1;
+  };
+  if (d.dtype != DT_BF16) return no("a call is not bf16");
+  if (!d.beta0 || d.vnni_c) return no("a call is not beta 0, or stores a VNNI C");
+  if (d.generic_forced || d.variant_forced) return no("a call was dispatched with a forced kernel");
+  if (!skc_ld_ok(d.lda, d.ldb, d.ldc, d.stride_a, d.stride_b, d.n, d.k))
+    return no("a leading dimension does not cover its operand, or a leading dimension or stride is no multiple of 8 elements");
+  return !d.vnni_b ? 2 : d.vnni_factor == 4 ? 4 : 0;
+}
+// Mode 1, BN and THE GATE, from profiles/chain_skinny_ab.txt (one box, 256 CUs, three layers, bias + relu, five alternating rounds, us per step;
+// the baseline (a) = the same calls one by one under xsmm_hip_set_skinny_bf16(1) + xsmm_hip_set_skinny_split(1), the best existing form ->
+// one launch on BN 16 / 32 / 64; a (row, BN) is taken only where it was faster than (a) in EVERY round). This replaces the provisional rule
+// (the single call's BN for the layer with the most bytes of B, and the single call's m >= 17 gate):
+//   Small layers, VNNI-2 - the launch's fixed parts and the stream's restarts are what a step costs: 1024 -> [1024] * 3 (B 2 MiB a layer) m 1 /
+//     8 / 16 / 31: 16.92 / 17.38 / 17.50 / 18.24 -> BN 16 11.77 / 12.92 / 13.62 / 17.71 (BN 32 12.53 / 14.38 / 15.02 / 18.85: wins but for m 31;
+//     BN 64 14.00 / 16.52 / 17.18 / 23.52); 1000 -> [1000] * 3: 17.11 / 17.24 / 17.07 / 17.43 -> BN 16 11.92 / 12.88 / 13.17 / 16.08; the funnel
+//     784 -> 512 -> 256 -> 128: 15.41 / 15.18 / 15.13 / 15.37 -> BN 16 10.58 / 10.66 / 10.62 / 13.37 (BN 32 10.62 / 11.38 / 11.65 / 14.26). BN 16 wins
+//     every round of every such row, m = 31 included (by 3 .. 13 %; 22 .. 31 % at m <= 16), and is the fastest side but for a tie at m 1 of
+//     the funnel. So: BN = the smallest with an instance, and NO m >= 17 gate - what gates the single call there is the re-read of A per
+//     workgroup, which the chain pays too but more than earns back at the seams.
+//   Large layers - the chain has ceil(n / BN) workgroups per layer where the split single call has that times P pulling bytes: 4096 -> [4096]
+//     * 3 (B 32 MiB a layer) m 1 / 8 / 16 / 31: 27.83 / 29.92 / 30.04 / 37.60 -> BN 32 31.87 / 34.12 / 36.03 / 45.12, BN 16 42.06 .. 47.16, BN 64
+//     34.58 .. 51.58; flat 32.22 / 36.10 / 35.99 / 42.71 -> BN 64 37.93 / 42.52 / 45.17 / 56.66; VNNI-4 24.50 / 26.60 / 27.90 / 36.46 -> BN 16 26.18 /
+//     28.12 / 31.57 / 42.50; 4096 -> 4096 -> 11008 -> 4096: 42.94 / 47.85 / 49.82 / 62.17 -> BN 64 58.77 / 62.05 / 63.41 / 75.99: every BN loses
+//     every round (one round of VNNI-4 m 1 apart). THE GATE: a chain with a layer whose B exceeds 2 MiB - the largest that gained; between
+//     2 and 32 MiB nothing was measured - stays call by call.
+//   A flat or a VNNI-4 B was measured on 4096 -> [4096] * 3 alone, where it lost: no row of theirs gained, so mode 1 takes VNNI-2 chains
+//     only. THE GATE names this too. The forced modes take every image.
+// Not measured: other CU counts (the rule reads them through G alone), several ranks, beta 1 (not a chain), layers between 2 and 32 MiB,
+// small flat and VNNI-4 chains, the launch without the weights ahead of the wait (not built).
+constexpr int64_t SKINNY_CHAIN_GATE_BYTES = 2 << 20; // mode 1: the most bytes of B a layer of a taken chain has
+ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int b_kind, int mode, bool strict) {
+  auto no = [](const char *why) { return ChainSkinnyPlan{0, 0, why, false}; };
+  const int forced_bn = mode >= 1000 ? mode % 1000 : mode == 1 ? 0 : mode, forced_g = chain_skinny_mode_forced_g(mode) ? mode / 1000 : 0;
+  if (mode != 1 && !(skn_bn_ok(forced_bn) && (!chain_skinny_mode_forced_g(mode) || (forced_g >= 1 && forced_g <= SKC_GMAX))))
+    return no("skinny-batch chains are off (xsmm_hip_set_chain_skinny)");
+  if (nlayers < 2 || nlayers > SKC_MAXL) return no("fewer than 2 or more than 8 calls");
+  if (m < 1 || m > SKN_M_MAX) return no("m is not 1 .. 31: the tiles' chain forms decide");
+  if (!skn_image_ok(b_kind)) return no("the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)");
+  if (strict) return no("strict mode: the launch has the bits of the calls under xsmm_hip_set_skinny_bf16, not of the calls as dispatched");
+  int64_t narrowest = n[0], most_bytes = 0;
+  for (int l = 0; l < nlayers; ++l) {
+    if (br[l] < 1) return no("a batch is empty");
+    if (!skn_shape_ok(m, n[l], k[l], br[l], 16)) return no("a layer has n < 16, n % 8 != 0, k < 8 or k % 8 != 0");
+    if (n[l] >= (1 << 24) || k[l] >= (1 << 24)) return no("a layer is wider or deeper than 2^24");
+    if (n[l] < narrowest) narrowest = n[l];
+    if (2 * br[l] * k[l] * n[l] > most_bytes) most_bytes = 2 * br[l] * k[l] * n[l];
+  }
+  int bn = forced_bn;
+  if (mode == 1) bn = b_kind == 2 ? 32 : 16; // the smallest with an instance
+  if (!skn_instance_exists(b_kind, bn)) return no("no instance of this B image on this column-block width (flat B on 16)");
+  if (narrowest < bn) return no("a layer is narrower than the column block");
+  int max_blocks = 0;
+  for (int l = 0; l < nlayers; ++l)
+    if (skn_blocks((int)n[l], bn) > max_blocks) max_blocks = skn_blocks((int)n[l], bn);
+  if (cus < 1) return no("the stream's compute units are unknown");
+  if (forced_g > cus) return no("more resident workgroups forced than compute units");
+  const int groups = forced_g ? forced_g : skc_groups(max_blocks, cus);
+  if (mode == 1 && b_kind != 0)
+    return ChainSkinnyPlan{bn, groups, "gate: no measured chain with a flat or a VNNI-4 B gained as one launch (profiles/chain_skinny_ab.txt)", true};
+  if (mode == 1 && most_bytes > SKINNY_CHAIN_GATE_BYTES)
+    return ChainSkinnyPlan{bn, groups, "gate: a layer with more than 2 MiB of B measured slower as one launch than call by call on the split skinny kernel (profiles/chain_skinny_ab.txt)", true};
+  return ChainSkinnyPlan{bn, groups, "", false};
+}
+
 // ---- plan_chain: the layer-chain launch decision (gemm_plan.h has the order of precedence) ---------------------------------------
 static const ChainLaunchPlan &chain_calls(ChainLaunchPlan &p, const char *why) {
   p.form = CF_CALLS, p.why = why;
@@ -1001,6 +1071,35 @@ ChainLaunchPlan plan_chain(int n, const GemmDesc *const *d, const int64_t *br, c
     differ_n = differ_n || d[i]->n != nn;
   }
   const char *const differ_why = "the calls differ in m or n, or a batch is empty";
+
+  // 0. SKINNY BATCHES (xsmm_hip_set_chain_skinny, brgemm_bf16_skinny_chain.hip): asked in front of everything, and only with the switch non-zero, a
+  // bf16 first call and m <= 31 - chains no other form takes (each asks for m >= 32). Widths may differ. Where the rule refuses or gates,
+  // everything below is what it is without this switch.
+  if (env.skinny != 0 && d[0]->dtype == DT_BF16 && m <= SKN_M_MAX) {
+    const char *w = "the calls differ in m, or a batch is empty";
+    if (!differ_m) {
+      w = nullptr;
+      int kind = chain_skinny_b_kind(*d[0], &w);
+      for (int i = 1; i < n && kind >= 0; ++i) {
+        const int kind_i = chain_skinny_b_kind(*d[i], &w);
+        if (kind_i < 0) kind = -1;
+        else if (kind_i != kind) kind = -1, w = "the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)";
+      }
+      if (kind >= 0) {
+        const ChainSkinnyPlan sp = plan_chain_skinny(m, n, ns, ks, br, cus.get(), kind, env.skinny, env.strict);
+        if (sp.bn > 0 && !sp.gated) { // (gated: the rule's answer is on record in why, nothing is launched)
+          p.form = CF_SKINNY, p.tile = sp.bn, p.b_kind = kind, p.groups = sp.groups, p.why = "";
+          p.bm = (int)m, p.bn = sp.bn, p.tiles_m = skc_key_tiles_m(), p.tiles_n = skc_key_tiles_n(sp.groups), p.mixed = false;
+          p.args_n = (int)ns[0];
+          for (int l = 1; l < n; ++l)
+            if (ns[l] > p.args_n) p.args_n = (int)ns[l];
+          return p;
+        }
+        w = sp.why;
+      }
+    }
+    chain_note(p, "skinny-batch launch", w);
+  }
 
   // 1. ON THE 256x256 TILE (xsmm_hip_set_chain_dma256, brgemm_bf16_dma256_chain.hip): asked first, and only with the switch non-zero. The rule sees
   // the calls' shapes, their shared B image and whether every call runs on that tile as a single call (mode 1 reads xsmm_hip_set_dma256_images

@@ -303,12 +303,40 @@ struct ChainDma256Plan { bool take; int groups; const char *why; bool gated; };
 constexpr int CHAIN_DMA256_GATE_TILES_N = 8; // most column tiles mode 1 takes
 inline bool chain_dma256_mode_forced(int mode) { return mode > 1000; }
 ChainDma256Plan plan_chain_dma256(int64_t m, int64_t n, int nlayers, const int64_t *k, const int64_t *br, int64_t cus, bool all_on_tile, int b_kind, int mode, bool strict);
-// THE LAYER-CHAIN LAUNCH DECISION (rt_chain.h try_chain_launch carries the answer out): which of the nine launch forms runs n calls that
+// SKINNY-BATCH LAYER CHAINS (xsmm_hip_set_chain_skinny; plan_chain, brgemm_bf16_skinny_chain.hip launch_bf16_skinny_chain, schedule in
+// brgemm_bf16_skinny_chain.h). Host-only, no HIP calls: tests/golden/gemm_plan_chain_skinny.txt is the table of both functions' answers.
+// One call of a chain: the B image (0 VNNI-2, 2 flat, 4 VNNI-4) it would have as a layer of this launch - bf16, beta 0, no VNNI C, no forced
+// generic kernel and no forced variant, lda / ldb / ldc / stride_a / stride_b multiples of 8 elements and not negative, lda >= k, ldb >= n,
+// ldc >= n, lda and ldc below 2^24 (the leading-dimension and stride part of bf16_skinny_args_ok, and the launch's buffer offsets) - or
+// -1 with *why set.
+int chain_skinny_b_kind(const GemmDesc &d, const char **why);
+// The ONE launch: m = the rows every call has, n / k / br per layer, cus = the stream's compute units, b_kind = the image every call has by
+// chain_skinny_b_kind, mode = the switch's value, strict = xsmm_hip_set_strict. THE PARTITION: m <= 31 is this rule's alone - every other
+// chain form asks for m >= 32 - and it takes nothing else. Takes 2 .. 8 layers with 1 <= m <= 31, every batch >= 1, per layer
+// skn_shape_ok(m, n_l, k_l, br_l, BN) - n_l >= BN, n_l % 8 == 0, k_l >= 8, k_l % 8 == 0 - and an instance of (image, BN); widths may differ.
+//   BN:  modes 16 / 32 / 64 and 1000 * G + BN: that BN. Mode 1: the smallest BN with an instance (16; flat 32) - measured the fastest on
+//        every row that gained. No instance (flat with 16) or a layer narrower than BN: a refusal.
+//   G:   min(max_l skn_blocks(n_l, BN), cus); a forced G as given if G <= cus, else a refusal.
+// Strict mode refuses: the launch has the bits of the calls under xsmm_hip_set_skinny_bf16(BN), not of the calls as the descriptors were planned.
+// THE GATE (mode 1 only; measured, profiles/chain_skinny_ab.txt: three layers on 256 CUs against the calls one by one under xsmm_hip_set_skinny_bf16(1)
+// + xsmm_hip_set_skinny_split(1), us per step: 1024 -> [1024] * 3 at m 1 / 8 / 16 / 31 16.92 / 17.38 / 17.50 / 18.24 -> 11.77 / 12.92 / 13.62 / 17.71 on BN
+// 16, the funnel 784 -> 512 -> 256 -> 128 15.41 .. 15.37 -> 10.58 .. 13.37 in every round; 4096 -> [4096] * 3 27.83 / 29.92 / 30.04 / 37.60 -> 31.87 / 34.12 /
+// 36.03 / 45.12 on its best BN, flat and VNNI-4 likewise slower in every round): a chain with a layer of more than 2 MiB of B, and a chain
+// with a flat or a VNNI-4 B - none of whose measured rows gained -, stays call by call; the rows and what was not measured stand at the
+// rule in gemm_plan.cpp. The answer then names the plan with gated = true and why = the gate, and the caller does not launch. Forced
+// modes are never gated. There is no m >= 17 gate: m = 31 gained in every round wherever m <= 16 did.
+struct ChainSkinnyPlan { int bn; int groups; const char *why; bool gated; };
+inline bool chain_skinny_mode_forced_g(int mode) { return mode >= 1000; }
+ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int b_kind, int mode, bool strict);
+// THE LAYER-CHAIN LAUNCH DECISION (rt_chain.h try_chain_launch carries the answer out): which of the ten launch forms runs n calls that
 // the chain contract admits, on which tile, B image and group count - or that they run call by call, and which rule refused. Host-only:
 // no HIP call, no global; the descriptors, the batch counts, the switches and a way to ask for the stream's compute units are arguments.
 // tests/test_chain_dispatch.py pins the answers through the C-ABI under every switch set (tests/golden/chain_dispatch.txt).
 // plan_chain composes the rules above. Each is asked at most once, in ONE order of precedence; behind each rule, the modes it reads:
-//   1. the 256x256 tile       plan_chain_dma256        {dma256; dma256_images in mode 1}   asked first; where it takes the chain nothing else is read
+//   0. skinny batches         plan_chain_skinny        {skinny}   asked in front of everything, and only with the switch non-zero, a bf16 first call
+//      and m <= 31: no other form takes such a chain, and this rule takes no other. Where it refuses or gates, everything below is what it is
+//      without this switch (call by call today).
+//   1. the 256x256 tile      plan_chain_dma256        {dma256; dma256_images in mode 1}   asked first; where it takes the chain nothing else is read
 //      (an f32 chain - every call on the K-split loader-wave tile of the first, within the compute units - reads no switch)
 //   2. a forced G / a forced W  plan_chain_rounds {rounds = 1000 + G}, plan_chain_width_rounds {width_rounds = 1000 + W}: in front of the one-round rules
 //   3. the plain chain on the loader-wave tile all calls were planned on, if it fits the compute units
@@ -319,10 +347,10 @@ ChainDma256Plan plan_chain_dma256(int64_t m, int64_t n, int nlayers, const int64
 //      where the others refuse
 // Calls that differ in n are rules 4 and 6's (ragged mixed widths) alone, equal widths everyone else's; strict is read by every rule.
 constexpr int CHAIN_PLAN_MAXL = 8; // (= CH_MAXL, chain_args.h)
-enum ChainForm : int { CF_CALLS, CF_F32, CF_PLAIN, CF_EDGE, CF_ROUNDS, CF_RAGGED, CF_WIDTHS, CF_WROUNDS, CF_WRAGGED, CF_DMA256, CF_FORMS };
-// xsmm_hip_set_strict, the seven chain switches (xsmm_hip_set_chain_*), xsmm_hip_set_edge_tiles and xsmm_hip_set_dma256_images; rt_core.h
-// chain_plan_env fills it per invoke
-struct ChainPlanEnv { bool strict; int edge, rounds, ragged, widths, width_rounds, widths_ragged, dma256; int edge_tiles, dma256_images; };
+enum ChainForm : int { CF_CALLS, CF_F32, CF_PLAIN, CF_EDGE, CF_ROUNDS, CF_RAGGED, CF_WIDTHS, CF_WROUNDS, CF_WRAGGED, CF_DMA256, CF_SKINNY, CF_FORMS };
+// xsmm_hip_set_strict, the seven chain switches of the tiles (xsmm_hip_set_chain_*), xsmm_hip_set_edge_tiles and xsmm_hip_set_dma256_images, and
+// xsmm_hip_set_chain_skinny; rt_core.h chain_plan_env fills it per invoke
+struct ChainPlanEnv { bool strict; int edge, rounds, ragged, widths, width_rounds, widths_ragged, dma256; int edge_tiles, dma256_images; int skinny = 0; };
 // The compute units a launch on the invoke's stream can use - the one input that costs runtime calls (rt_chain.h stream_cus: three). Asked
 // lazily and at most once per invoke: a decision that ends in front of every rule that reads them never pays for them.
 struct ChainCus {
@@ -333,10 +361,12 @@ struct ChainCus {
 };
 struct ChainLaunchPlan {
   ChainForm form;     // CF_CALLS: call by call, `why` names a rule that refused
-  int tile;           // the launcher's tile: loader-wave tile 0 .. 3, f32 chain tile 1 / 2, 3 for CF_DMA256 (whose launcher takes none)
+  int tile;           // the launcher's tile: loader-wave tile 0 .. 3, f32 chain tile 1 / 2, 3 for CF_DMA256 (whose launcher takes none), the column-block width BN for CF_SKINNY
   int b_kind;         // the B image of the launch: 0 VNNI-2, 2 flat, 4 VNNI-4 (0 for CF_F32)
-  int groups;         // ChainArgs::groups: row groups G (CF_ROUNDS, CF_DMA256), workgroup columns W (CF_WROUNDS), 0 otherwise
-  int bm, bn;         // the tile's rows and columns (256 x 256 for CF_DMA256)
+  int groups;         // ChainArgs::groups: row groups G (CF_ROUNDS, CF_DMA256), workgroup columns W (CF_WROUNDS), resident workgroups G (CF_SKINNY), 0 otherwise
+  int bm, bn;         // the tile's rows and columns (256 x 256 for CF_DMA256; CF_SKINNY: all m rows x BN)
+                      // CF_SKINNY: tiles_m = 1 and tiles_n = G - the counter-block key and the arrivals per counter (brgemm_bf16_skinny_chain.h) -,
+                      // mixed = false (the target is epoch x G) although ChainLayer::pad carries each layer's n
   int tiles_m, tiles_n; // the counter-block key and the grid: ceil-divided where the form has edge tiles (m: CF_EDGE, CF_RAGGED, CF_WRAGGED; n: the
                       // latter two), the widest layer's column tiles in the width forms
   int tiles_l[CHAIN_PLAN_MAXL]; // the width forms: column tiles per layer, part of the key (what a launch adds to layer l's counters); zero otherwise

@@ -230,7 +230,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   c.groups = plan.groups;
   for (int i = 0; i < n; ++i)
     c.L[i] = ChainLayer{pb[i], pd[i], pc[i], d[i]->ldb, d[i]->ldc, d[i]->stride_a, d[i]->stride_b, (int)d[i]->k, (int)br[i],
-                        EP_BETA0 | (d[i]->bias ? EP_BIAS : 0) | (d[i]->relu ? EP_RELU : 0), plan.mixed ? (int)d[i]->n : 0};
+                        EP_BETA0 | (d[i]->bias ? EP_BIAS : 0) | (d[i]->relu ? EP_RELU : 0), plan.mixed || plan.form == CF_SKINNY ? (int)d[i]->n : 0};
   // the pool of error words is about to run dry (hundreds of launches without a synchronisation): synchronise and check here
   // instead of ever dropping a journal entry
   if (g_chain_journaled.load(std::memory_order_relaxed) >= CHAIN_ERR_POOL - 8) {
@@ -291,6 +291,10 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   case CF_DMA256: // row groups G, rounds R, the B image
     HIP_OK(launch_bf16_dma256_chain(b_kind, c, s)); stats = g_chain_dma256_stats;
     word[0] = plan.groups, word[1] = chain_rounds_rounds(plan.tiles_m, plan.groups), word[2] = b_kind;
+    break;
+  case CF_SKINNY: // resident workgroups G, the column-block width BN (the plan's tile), the B image; the block's key is (1, G): target = epoch * G
+    HIP_OK(launch_bf16_skinny_chain(b_kind, tile, c, s)); stats = g_chain_skinny_stats;
+    word[0] = plan.groups, word[1] = tile, word[2] = b_kind;
     break;
   default: return false; // (CF_CALLS has returned above)
   }

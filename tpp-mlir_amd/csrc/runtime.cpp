@@ -62,6 +62,7 @@ __attribute__((weak)) hipError_t launch_bf16_chain_widths(int, int, const ChainA
 __attribute__((weak)) hipError_t launch_bf16_chain_wrounds(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 __attribute__((weak)) hipError_t launch_bf16_chain_wragged(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 __attribute__((weak)) hipError_t launch_bf16_dma256_chain(int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
+__attribute__((weak)) hipError_t launch_bf16_skinny_chain(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 } // namespace tpp
 
 namespace {
@@ -610,6 +611,10 @@ extern "C" void xsmm_hip_chain_widths_ragged_stats(int64_t out[4]) {
 extern "C" int xsmm_hip_set_chain_dma256(int mode) { return tpp::chain_dma256_mode_ok(mode) ? tpp::g_chain_dma256.exchange(mode) : -1; }
 extern "C" void xsmm_hip_chain_dma256_stats(int64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_dma256_stats[i].load(std::memory_order_relaxed);
+}
+extern "C" int xsmm_hip_set_chain_skinny(int mode) { return tpp::chain_skinny_mode_ok(mode) ? tpp::g_chain_skinny.exchange(mode) : -1; }
+extern "C" void xsmm_hip_chain_skinny_stats(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_skinny_stats[i].load(std::memory_order_relaxed);
 }
 extern "C" int xsmm_hip_set_chain_rounds(int mode) { return tpp::chain_rounds_mode_ok(mode) ? tpp::g_chain_rounds.exchange(mode) : -1; }
 extern "C" void xsmm_hip_chain_rounds_stats(int64_t out[4]) {

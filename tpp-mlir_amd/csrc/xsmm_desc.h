@@ -313,6 +313,21 @@ inline std::atomic<int> g_chain_dma256{[] {
   return chain_dma256_mode_ok(v) ? v : 0;
 }()};
 inline std::atomic<int64_t> g_chain_dma256_stats[4]; // such launches; resident row groups G (tiles_m in one round), rounds R, B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
+// SKINNY-BATCH LAYER CHAINS (xsmm_hip_set_chain_skinny / TPP_HIP_CHAIN_SKINNY; gemm_plan.cpp plan_chain_skinny, rt_chain.h try_chain_launch,
+// brgemm_bf16_skinny_chain.hip, brgemm_bf16_skinny_chain.h): 0 = off, 1 = a bf16 chain with 1 .. 31 rows runs as one launch of the skinny kernel's
+// chain form on the column-block width BN of the rule (and its gate), 16 / 32 / 64 = that BN wherever eligible, 1000 * G + BN (1 <= G <= 512) =
+// that BN on G resident workgroups (tests, measurements). A switch of its own: it reads neither xsmm_hip_set_skinny_bf16 nor
+// xsmm_hip_set_skinny_split - those decide single calls only - and neither reads it.
+inline bool chain_skinny_mode_ok(int v) {
+  const int bn = v >= 1000 ? v % 1000 : v, g = v >= 1000 ? v / 1000 : 1;
+  return v == 0 || v == 1 || ((bn == 16 || bn == 32 || bn == 64) && g >= 1 && g <= 512);
+}
+inline std::atomic<int> g_chain_skinny{[] {
+  const char *e = getenv("TPP_HIP_CHAIN_SKINNY");
+  const int v = e ? atoi(e) : 0;
+  return chain_skinny_mode_ok(v) ? v : 0;
+}()};
+inline std::atomic<int64_t> g_chain_skinny_stats[4]; // such launches; resident workgroups G, column-block width BN, B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)

@@ -131,6 +131,8 @@ _SIGNATURES = {
     "xsmm_hip_skinny_split_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_dma256": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_chain_dma256_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "xsmm_hip_set_chain_skinny": (ctypes.c_int, [ctypes.c_int]),
+    "xsmm_hip_chain_skinny_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_f32_halves": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_f32_halves_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
@@ -483,6 +485,18 @@ class XsmmRuntime:
         """(chain launches on the 256x256 tile; resident row groups G, rounds, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
         out = (ctypes.c_int64 * 4)()
         self.lib.xsmm_hip_chain_dma256_stats(out)
+        return tuple(int(v) for v in out)
+
+    def set_chain_skinny(self, mode):
+        """bf16 layer chains with 1 .. 31 rows as one launch of the skinny-batch kernel's chain form (the bits of the calls under
+        set_skinny_bf16(BN)): 0 off (default), 1 the rule (VNNI-2 chains whose layers have at most 2 MiB of B, on BN 16: as measured), 16 / 32 / 64 that column-block width
+        wherever eligible, 1000 * G + BN that width on G resident workgroups; returns the previous mode, -1 for a value it refuses"""
+        return self.lib.xsmm_hip_set_chain_skinny(mode)
+
+    def chain_skinny_stats(self):
+        """(skinny-batch chain launches; resident workgroups G, BN, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
+        out = (ctypes.c_int64 * 4)()
+        self.lib.xsmm_hip_chain_skinny_stats(out)
         return tuple(int(v) for v in out)
 
     def set_f32_halves(self, mode):
