@@ -27,13 +27,14 @@ def partial_lds_bytes(bn, mb):
     return (WMAX - 1) * (mb // 16) * (bn // 16) * 4 * 64 * 4
 
 
-def resource_usage():
-    """{kernel name: {vgprs, agprs, scratch, sgpr_spill, vgpr_spill, static_lds}} of every kernel in the code object"""
+def resource_usage(src=SRC):
+    """{kernel name: {vgprs, agprs, scratch, sgpr_spill, vgpr_spill, static_lds}} of every kernel in the code object of `src` (this file's
+    kernel, or the split's or the chain's: the same instance table, LDS formula and limits hold for all three)"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         raise RuntimeError("hipcc not found")
     with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c", SRC, "-o", os.path.join(tmp, "k.o"),
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c", src, "-o", os.path.join(tmp, "k.o"),
                             "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = {}

@@ -5,8 +5,11 @@
 // layer's steps over W_l = skn_waves(br_l * skn_steps(k_l)) waves, LDS combine into wave 0 in wave order, bias, relu and ONE rounding - bit
 // for bit the call under xsmm_hip_set_skinny_bf16(BN). The launch has the waves of its deepest layer; a wave at or beyond W_l takes no step
 // in layer l but meets every barrier.
-// The K loop and the epilogue are the unsplit kernel's text, kept here as a copy (as brgemm_bf16_skinny_split.hip keeps one): moved into a
-// shared header they compiled the unsplit kernels to other instructions, and those stay the measured ones.
+// The K loop, the combine and the epilogue below are this file's own text of what brgemm_bf16_skinny_tile.h holds for the unsplit and the
+// split kernel. Built from that tile (sc1 loads of A and the seam wait as a hook in its K loop, sc1 stores in its epilogue) every result
+// bit was the same, but a forced BN 64 launch measured 2 .. 4 % slower than this text (profiles/skinny_tile_refactor_ab.txt, part 4), and
+// the cause was not found. Until it is, a change to the tile's K loop, combine or epilogue has to be made here too: the GPU tests compare
+// the chain with the calls bit for bit (tests/test_chain_skinny_gpu.py).
 //
 // THE SEAM between layer l and l + 1 is the project's chain protocol (brgemm_bf16_lw.hip's header; guide: Guideline 16, recipe R1) on ONE
 // counter per seam, cnt[l]. No memset, no reset: counters only grow, a launch adds exactly G to each, the host passes target = epoch * G.
