@@ -157,7 +157,13 @@ TPP_XSMM_EXPORT int xsmm_hip_set_async(int enable);
  * REPLAYED when its invokes come again - each caller marks its own invokes in the recorded group without taking a lock, and
  * the complete group launches from a work list that already sits in device memory. Programs that do not repeat themselves
  * are handed to a scheduler thread after a few thousand locked arrivals; enable = 2 (TPP_HIP_TILE_QUEUE=2) does that as soon
- * as a second thread shows up (the round-2 behaviour, kept for comparison runs). */
+ * as a second thread shows up (the round-2 behaviour, kept for comparison runs).
+ * On a stream that is being captured into a graph a group is legal: it always gathers its members into a pinned work list of its
+ * own, which the runtime never writes or frees again - every replay of the graph reads it - (160 KiB per captured flush, for the
+ * life of the process), records no event, and a group planned on a split kernel runs and reports the unsplit one. The capture
+ * must be in RELAXED mode (hipStreamCaptureModeRelaxed; torch: capture_error_mode="relaxed"): the ring allocates the pinned buffer
+ * of a slot inside the capture - at a slot's first use, and after every captured flush - and under the global or thread-local
+ * mode that allocation is an error, which ends the process like every other HIP error. */
 TPP_XSMM_EXPORT int xsmm_hip_set_tile_queue(int enable);
 TPP_XSMM_EXPORT void xsmm_hip_flush(void);
 /* n fused_brgemm invokes in ONE call (arrays of length n, one entry per call): exactly the effect of

@@ -6,7 +6,9 @@
 //     the driver; streams are in-order and every operation completes before its call returns;
 //   * the device has FAKE_HIP_CUS compute units (default 256): hipDeviceGetAttribute answers it, and the CU mask of every stream
 //     has that many bits. fake_hip_cu_mask_queries() counts the calls of hipExtStreamGetCUMask (how often a host path asked for a
-//     stream's compute units).
+//     stream's compute units);
+//   * no stream is being captured unless fake_hip_set_capturing(1) says so: hipStreamIsCapturing then answers "active" for every
+//     stream until fake_hip_set_capturing(0) (tests/split_scratch/driver.cpp).
 #pragma once
 #include <atomic>
 #include <cstdlib>
@@ -36,6 +38,7 @@ int fake_hip_cus() { // compute units of the fake device
   return cus;
 }
 std::atomic<long> g_cu_mask_queries{0};
+std::atomic<bool> g_capturing{false}; // what hipStreamIsCapturing answers for every stream (fake_hip_set_capturing): "none" unless a test says so
 } // namespace
 
 extern "C" {
@@ -96,7 +99,11 @@ hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t sp
   return hipSuccess;
 }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus *s) { *s = hipStreamCaptureStatusNone; return hipSuccess; }
+hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus *s) {
+  *s = g_capturing.load(std::memory_order_relaxed) ? hipStreamCaptureStatusActive : hipStreamCaptureStatusNone;
+  return hipSuccess;
+}
+int fake_hip_set_capturing(int on) { return g_capturing.exchange(on != 0, std::memory_order_relaxed); } // returns the answer before
 long fake_hip_cu_mask_queries(void) { return g_cu_mask_queries.load(std::memory_order_relaxed); }
 hipError_t hipExtStreamGetCUMask(hipStream_t, uint32_t n, uint32_t *m) {
   g_cu_mask_queries.fetch_add(1, std::memory_order_relaxed);
@@ -105,6 +112,7 @@ hipError_t hipExtStreamGetCUMask(hipStream_t, uint32_t n, uint32_t *m) {
   return hipSuccess;
 }
 hipError_t hipMemset(void *p, int v, size_t bytes) { memset(p, v, bytes); return hipSuccess; }
+hipError_t hipMemsetAsync(void *p, int v, size_t bytes, hipStream_t) { memset(p, v, bytes); return hipSuccess; }
 hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) { *v = fake_hip_cus(); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = nullptr; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }

@@ -199,8 +199,10 @@ __global__ __launch_bounds__(256) void brgemm_bf16_small32(GemmArgs p, const Wor
 
 // preconditions (checked by the callers): bf16, VNNI-2 B (a.vf == 4: VNNI-4 B), m % 32 == 0, n % 32 == 0, k % 16 == 0, lda % 8 == 0,
 // stride_a % 8 == 0, stride_b % 2 == 0 (VNNI-4: % 4), ldc % 4 == 0; A 16-byte, B 4-byte (VNNI-4: 8-byte), C / D 8-byte aligned
-// split > 1: that many workgroups per output tile (grouped launches and single invokes in the grouped grid form)
-hipError_t launch_bf16_small32(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s, int split) {
+// split > 1: that many workgroups per output tile (grouped launches and single invokes in the grouped grid form); *split_ran: whether
+// the launch made was the split one (the stream may have no scratch block: a 17th stream, a stream being captured into a graph)
+hipError_t launch_bf16_small32(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s, int split, bool *split_ran) {
+  if (split_ran) *split_ran = false;
   GemmArgs args = a;
   const int tiles_m = a.m / 32, tiles_n = (a.n + 31) / 32; // (a ragged last column tile: grouped launches only, n % 4 == 0)
   if (split > 1 && tiles_n <= 65535 && tiles_m <= 65535) {
@@ -212,6 +214,7 @@ hipError_t launch_bf16_small32(const GemmArgs &a, const WorkItem *items, int n_i
       args.split_cnt = sc->cnt;
       if (a.vf == 4) hipLaunchKernelGGL((brgemm_bf16_small32<true, 4>), dim3((unsigned)(n_items * split), tiles_n, tiles_m), dim3(256), 0, s, args, items);
       else hipLaunchKernelGGL((brgemm_bf16_small32<true>), dim3((unsigned)(n_items * split), tiles_n, tiles_m), dim3(256), 0, s, args, items);
+      if (split_ran) *split_ran = true;
       return hipGetLastError();
     } // (no scratch block: the unsplit launch)
   }

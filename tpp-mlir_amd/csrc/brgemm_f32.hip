@@ -706,7 +706,7 @@ hipError_t launch_f32_lw_kedge(int tile, const GemmArgs &a, hipStream_t s); // k
 hipError_t launch_f32_lw16(int tile, const GemmArgs &a, const WorkItem *items, int n_items, bool grouped, hipStream_t s); // brgemm_f32_lw16.hip: tile 0 = 32x16
 hipError_t launch_f32_x6(int tile, const GemmArgs &a, bool vec, hipStream_t s); // brgemm_f32_x6.hip: tile = variant - V_F32_X6_64x64
 hipError_t launch_bf16_grouped64(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s); // brgemm_bf16.hip
-hipError_t launch_bf16_small32(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s, int split = 1); // brgemm_bf16_small.hip
+hipError_t launch_bf16_small32(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s, int split = 1, bool *split_ran = nullptr); // brgemm_bf16_small.hip
 
 template <typename T, bool VNNI, bool VEC, int VF = 2, int FORM = FORM_NONE>
 static hipError_t launch_grouped_t(const GemmArgs &a, const WorkItem *items, int n_items, hipStream_t s) {
@@ -778,7 +778,8 @@ static ChainArgs one_layer(const GemmArgs &a, int br, int m, int n) {
 
 // carries out a plan of gemm_plan.cpp. items / n_items: the work list (WorkItem, QuadItem for quads; nullptr and 1 for a single
 // invoke); br: the batch count of the loader-wave bf16 launches (a group's: the first item's)
-static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br, const void *items, int n_items, bool grouped, hipStream_t s) {
+static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br, const void *items, int n_items, bool grouped, hipStream_t s,
+                                  bool *small_split_ran = nullptr) {
   const WorkItem *wi = (const WorkItem *)items;
   switch (p.launcher) {
   case GL_NONE: return hipSuccess;
@@ -805,7 +806,7 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
     if (p.edge) return p.tile == 2 ? launch_bf16_dma256_edge(p.b_kind, a, s) : hipErrorInvalidValue;
     return p.b_kind != 0 ? (p.tile == 2 ? launch_bf16_dma256_image(p.b_kind, a, s) : hipErrorInvalidValue) : launch_gemm_bf16_fast(p.tile, a, s);
   case GL_BF16_SKINNY: return p.split > 1 ? launch_bf16_skinny_split(p.b_kind, p.tile, p.split, a, s) : launch_bf16_skinny(p.b_kind, p.tile, a, s);
-  case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split);
+  case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split, small_split_ran);
   case GL_BF16_GROUPED64: return launch_bf16_grouped64(a, wi, n_items, s);
   case GL_BF16_LW:
     return launch_bf16_lw(p.edge_k8 ? BLW_KEDGE8 : p.edge_k ? BLW_KEDGE : p.edge ? BLW_EDGE : BLW_LAYER, p.tile, p.b_kind, one_layer(a, br, a.m, a.n), s);
@@ -1001,8 +1002,11 @@ hipError_t launch_gemm_grouped(const GemmDesc &d, const WorkItem *items, int n_i
                                int64_t br_hint, hipStream_t stream) {
   const GemmLaunch p = plan_gemm_group(d, n_items, vec_ok, out_ok, pair_ok, br_hint, gemm_plan_env());
   if (p.launcher == GL_NONE || p.launcher == GL_INVALID) return p.launcher == GL_NONE ? hipSuccess : hipErrorInvalidValue;
-  g_last_grouped.store(p.text, std::memory_order_relaxed);
-  return run_gemm_launch(p, gemm_args(d, nullptr, nullptr, nullptr, nullptr, 0), (int)br_hint, items, n_items, true, stream);
+  bool split_ran = false;
+  const hipError_t e = run_gemm_launch(p, gemm_args(d, nullptr, nullptr, nullptr, nullptr, 0), (int)br_hint, items, n_items, true, stream, &split_ran);
+  // (a group planned on the split of brgemm_bf16_small.hip whose stream has no scratch block ran unsplit: the report says what ran)
+  g_last_grouped.store(p.launcher == GL_BF16_SMALL32 && p.split > 1 && !split_ran ? p.text_unsplit : p.text, std::memory_order_relaxed);
+  return e;
 }
 
 // QUADS (round 6; xsmm_desc.h QuadItem, brgemm_bf16_lw.hip GRP = 2): a group of 64x64 bf16 tile invokes that forms a grid of item rows and

@@ -1696,9 +1696,10 @@ GemmLaunch plan_gemm_group(const GemmDesc &d, int n_items, bool vec_ok, bool out
   if (vec_ok && out_ok && ((d.variant != V_GENERIC && bf16_small_eligible(d)) || small_ragged || small4)) {
     // skinny groups with a long reduction: the K steps of a tile over several workgroups (choose_bf16_small_split)
     const int S = choose_bf16_small_split((long long)n_dec * (d.m / 32) * ((d.n + 31) / 32), (long long)br_hint * (d.k / 16), env);
-    const char *name = S > 1 ? (small4 ? "brgemm_bf16_small32_vnni4 grouped, split" : "brgemm_bf16_small32 grouped, split")
-                             : (small4 ? "brgemm_bf16_small32_vnni4 grouped" : "brgemm_bf16_small32 grouped");
-    return launch(GL_BF16_SMALL32, 0, name, S);
+    const char *unsplit = small4 ? "brgemm_bf16_small32_vnni4 grouped" : "brgemm_bf16_small32 grouped";
+    GemmLaunch l = launch(GL_BF16_SMALL32, 0, S > 1 ? (small4 ? "brgemm_bf16_small32_vnni4 grouped, split" : "brgemm_bf16_small32 grouped, split") : unsplit, S);
+    l.text_unsplit = unsplit;
+    return l;
   }
   static const char *const names[] = {"brgemm_grouped<f32>", "brgemm_grouped<f32>", "brgemm_grouped<bf16,vnni2>", "brgemm_grouped<bf16,vnni2>",
                                       "brgemm_grouped<bf16,vnni4>", "brgemm_grouped<bf16,flat>"};

@@ -105,6 +105,9 @@ struct GemmLaunch {
   // GL_F32_LW, tile 1, halves (xsmm_hip_set_f32_halves): every 64x64 + K2 tile as two 64x32 + K2 workgroups - launch_f32_lw_halves, the
   // same bits; refused by the launcher: launch_f32_lw(1). Variant, kernel name and text are those of the launch with the mode off.
   bool halves = false;
+  // GL_BF16_SMALL32 with split > 1: what a group reports when its stream has no scratch block (a 17th stream, a stream being captured
+  // into a graph) and launch_bf16_small32 ran the unsplit launch instead
+  const char *text_unsplit = nullptr;
 };
 
 // fills d.variant / d.name / d.generic_forced / d.variant_forced; returns false if no kernel can run the descriptor

@@ -731,6 +731,24 @@ struct TileQueue {
     }
     slot = (slot + 1) % SLOTS;
   }
+  // A grouped launch CAPTURED into a graph reads its work list at every replay of the graph, for as long as the graph lives - not
+  // once, behind the capture. So a captured launch never reads memory the queue writes again: it always gathers its members into
+  // pinned[slot] (flush: never the segment's device list, which the next recording of the segment rewrites), and that slot's buffers
+  // then LEAVE the ring for good - they are the graph's from here on and live as long as the process, like the descriptors; the ring
+  // gets new ones at the slot's next use (ensure_slot). No completion event is recorded for them: nothing waits for a launch that
+  // has not run, and an event recorded inside a capture is not one the runtime may wait on. The ring position stays where it is.
+  static bool capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    return cs != hipStreamCaptureStatusNone;
+  }
+  void retire_slot() { // a grouped launch on a capturing `stream` has been issued from pinned[slot] (and post_pinned[slot])
+    pinned[slot] = nullptr;
+    post_pinned[slot] = nullptr;
+  }
   void store_recording(const TraceItem *next) {
     if (learn >= 0 && next && rec_open && rec.items.size() == learn_n) {
       // the group is exactly what was replayed from segs[learn] and `next` conflicts with it: one more way that group ends
@@ -783,8 +801,10 @@ struct TileQueue {
     issue_pending();
     close_window();
     const int rp = replay;
-    // the recorded group, complete, and its device-resident list exists (not while capturing): launch from its own list
-    const bool whole = rp >= 0 && n > 0 && (size_t)n == segs[rp].items.size() && segs[rp].list_valid;
+    const bool captured = n > 0 && capturing(stream); // (one status query per grouped launch; see retire_slot)
+    // the recorded group, complete, and its device-resident list exists: launch from its own list - never a launch that is being
+    // captured, whose list must stay as it is for every replay of the graph: that one gathers its members like an incomplete group
+    const bool whole = !captured && rp >= 0 && n > 0 && (size_t)n == segs[rp].items.size() && segs[rp].list_valid;
     if (rp >= 0 && n > 0 && !whole && segs[rp].post_n) { // a folded group in part: its GEMM items and the stages of their chains that arrived
       const Segment &S = segs[rp];
       std::vector<PostItem> pp;
@@ -812,7 +832,8 @@ struct TileQueue {
       launcher_drain();
       g_last_merged.store(nullptr, std::memory_order_relaxed);
       launch_folded(pp, lv, stages, pd, pos);
-      launched();
+      if (captured) retire_slot();
+      else launched();
       reset_group();
       return;
     }
@@ -833,7 +854,8 @@ struct TileQueue {
       else if (kind == KIND_GEMM) HIP_OK(launch_gemm_grouped(*(const GemmDesc *)desc, pinned[slot], n, vec_ok, out_ok, pair_ok, pinned[slot][0].br, stream));
       else if (kind == KIND_UNARY) HIP_OK(launch_unary_grouped(*(const UnaryDesc *)desc, pinned[slot], n, stream));
       else HIP_OK(launch_binary_grouped(*(const BinaryDesc *)desc, pinned[slot], n, stream));
-      launched();
+      if (captured) retire_slot();
+      else launched();
     }
     reset_group();
   }
