@@ -5,7 +5,7 @@
 // (The other host build, tests/tsan/fake_hip.cpp, plans every bf16 descriptor away and links runtime.cpp's weak refusing stand-ins:
 // there a chain never gets past the first rule.)
 //   * the HIP host entry points: tests/tsan/fake_hip_host.h, FAKE_HIP_CUS compute units;
-//   * plan_gemm / gemm_quads_pay through the real planner, with a GemmPlanEnv filled as brgemm_f32.hip gemm_plan_env fills it;
+//   * plan_gemm / gemm_quads_pay through the real planner, with a GemmPlanEnv filled by the fill brgemm_f32.hip uses (mode_switches.h gemm_plan_env_of);
 //   * launch_gemm and the nine chain launchers COMPUTE through oracle/xsmm_oracle.c (oracle_fused_brgemm): a single call from its
 //     GemmDesc, a chain layer by layer from the ChainArgs ALONE - what the kernels see. Each launcher first asks the refusal function
 //     of its launch mode (brgemm_bf16_lw_launch.h, brgemm_bf16_dma256_chain.h) and answers hipErrorInvalidValue as the real one does;
@@ -16,6 +16,7 @@
 //   * fake_chain_starve: a launch that writes its error word and stores nothing (host memory here: nothing is provoked anywhere).
 #include "fake_chain.h"
 #include "../../tpp-mlir_amd/csrc/gemm_plan.h"
+#include "../../tpp-mlir_amd/csrc/mode_switches.h"
 #include "../../tpp-mlir_amd/csrc/brgemm_bf16_lw_chain_edge.h"
 #include "../../tpp-mlir_amd/csrc/brgemm_bf16_lw_chain_rounds.h"
 #include "../../tpp-mlir_amd/csrc/brgemm_bf16_lw_chain_ragged.h"
@@ -161,10 +162,7 @@ int fake_hip_compute_units(void) { return fake_hip_cus(); }
 namespace tpp {
 
 static GemmPlanEnv fake_plan_env() { // (brgemm_f32.hip gemm_plan_env, with the fake device's compute units)
-  return GemmPlanEnv{fake_hip_cus(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed), g_tail_split.load(std::memory_order_relaxed),
-                     g_edge_tiles.load(std::memory_order_relaxed), g_edge_k.load(std::memory_order_relaxed), g_edge_k_bf16.load(std::memory_order_relaxed),
-                     g_f32_halves.load(std::memory_order_relaxed), g_edge_k8_bf16.load(std::memory_order_relaxed), g_dma256_images.load(std::memory_order_relaxed),
-                     g_dma256_edge.load(std::memory_order_relaxed)};
+  return gemm_plan_env_of(fake_hip_cus(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed));
 }
 bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, fake_plan_env()); }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, fake_plan_env()); }

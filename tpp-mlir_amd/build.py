@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 SO_NAME = "libtpp_xsmm_runner_utils.so"
 SO_PATH = os.path.join(HERE, SO_NAME)
 SOURCES = ["runtime.cpp", "host_cache.cpp", "gemm_plan.cpp", "brgemm_f32.hip", "brgemm_f32_lw.hip", "brgemm_f32_lw16.hip", "brgemm_f32_x6.hip", "brgemm_bf16.hip", "brgemm_bf16_dma256.hip", "brgemm_bf16_dma256_edge.hip", "brgemm_bf16_skinny.hip", "brgemm_bf16_skinny_split.hip", "brgemm_bf16_skinny_chain.hip", "brgemm_bf16_dma256_chain.hip", "brgemm_bf16_small.hip", "brgemm_bf16_lw.hip", "brgemm_bf16_lw_chain_ragged.hip", "brgemm_bf16_lw_chain_widths.hip", "brgemm_bf16_lw_chain_wrounds.hip", "brgemm_bf16_lw_chain_wragged.hip", "eltwise.hip", "relayout.hip", "peer_gather.hip"]
-HEADERS = ["xsmm_desc.h", "gemm_plan.h", "eltwise_ops.h", "host_cache.h", "rt_core.h", "rt_mirror.h", "rt_registry.h", "rt_operands.h", "rt_tile_queue.h", "rt_scheduler.h", "rt_enqueue.h", "rt_rewrites.h", "rt_relayout.h", "rt_invoke.h", "rt_chain.h", "gemm_common.h", "brgemm_f32_lw_tile.h", "brgemm_f32_lw_kedge.h", "brgemm_bf16_lw_kedge.h", "brgemm_bf16_dma256_images.h", "brgemm_bf16_dma256_tile.h", "brgemm_bf16_dma256_edge.h", "brgemm_bf16_skinny.h", "brgemm_bf16_skinny_tile.h", "brgemm_bf16_skinny_split.h", "brgemm_bf16_skinny_chain.h", "brgemm_bf16_dma256_chain.h", "brgemm_bf16_lw_launch.h", "brgemm_bf16_lw_chain_edge.h", "brgemm_bf16_lw_chain_rounds.h", "brgemm_bf16_lw_chain_ragged.h", "brgemm_bf16_lw_chain_widths.h", "brgemm_bf16_lw_chain_wrounds.h", "brgemm_bf16_lw_chain_wragged.h", "chain_args.h", "split_scratch.h", os.path.join("..", "..", "include", "tpp_xsmm_abi.h")]
+HEADERS = ["xsmm_desc.h", "gemm_plan.h", "mode_switches.h", "eltwise_ops.h", "host_cache.h", "rt_core.h", "rt_mirror.h", "rt_registry.h", "rt_operands.h", "rt_tile_queue.h", "rt_scheduler.h", "rt_enqueue.h", "rt_rewrites.h", "rt_relayout.h", "rt_invoke.h", "rt_chain.h", "gemm_common.h", "brgemm_f32_lw_tile.h", "brgemm_f32_lw_kedge.h", "brgemm_bf16_lw_kedge.h", "brgemm_bf16_dma256_images.h", "brgemm_bf16_dma256_tile.h", "brgemm_bf16_dma256_edge.h", "brgemm_bf16_skinny.h", "brgemm_bf16_skinny_tile.h", "brgemm_bf16_skinny_split.h", "brgemm_bf16_skinny_chain.h", "brgemm_bf16_dma256_chain.h", "brgemm_bf16_lw_launch.h", "brgemm_bf16_lw_chain_edge.h", "brgemm_bf16_lw_chain_rounds.h", "brgemm_bf16_lw_chain_ragged.h", "brgemm_bf16_lw_chain_widths.h", "brgemm_bf16_lw_chain_wrounds.h", "brgemm_bf16_lw_chain_wragged.h", "chain_args.h", "split_scratch.h", os.path.join("..", "..", "include", "tpp_xsmm_abi.h")]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -26,6 +26,7 @@
 #include "xsmm_desc.h"
 #include "chain_args.h"
 #include "gemm_plan.h"
+#include "mode_switches.h"
 #include "brgemm_f32_lw_kedge.h"
 #include "brgemm_bf16_lw_kedge.h"
 #include "brgemm_bf16_dma256_edge.h"
@@ -734,12 +735,7 @@ static std::atomic<int> g_strict_kernels{0};
 int set_strict_kernels(int on) { return g_strict_kernels.exchange(on != 0); }
 bool strict_kernels() { return g_strict_kernels.load(std::memory_order_relaxed) != 0; }
 static GemmPlanEnv gemm_plan_env() {
-  return GemmPlanEnv{device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed), g_tail_split.load(std::memory_order_relaxed),
-                     g_edge_tiles.load(std::memory_order_relaxed), g_edge_k.load(std::memory_order_relaxed),
-                     g_edge_k_bf16.load(std::memory_order_relaxed), g_f32_halves.load(std::memory_order_relaxed),
-                     g_edge_k8_bf16.load(std::memory_order_relaxed), g_dma256_images.load(std::memory_order_relaxed),
-                     g_dma256_edge.load(std::memory_order_relaxed), g_skinny_bf16.load(std::memory_order_relaxed),
-                     g_skinny_split.load(std::memory_order_relaxed)};
+  return gemm_plan_env_of(device_cu_count(), strict_kernels(), g_forced_split.load(std::memory_order_relaxed)); // (the switches: mode_switches.h)
 }
 bool plan_gemm(GemmDesc &d, int forced_variant) { return plan_gemm(d, forced_variant, gemm_plan_env()); }
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br) { return gemm_quads_pay(d, n_items, br, gemm_plan_env()); }
@@ -836,9 +832,9 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
   GemmLaunch p = plan_gemm_call(d, br, al, env);
   if (p.launcher == GL_NONE) return hipSuccess;
   const GemmArgs a = gemm_args(d, A, B, C, D, (int)(br < 0 ? 0 : br));
-  if (p.launcher == GL_BF16_SKINNY) { // a skinny-batch bf16 layer (xsmm_desc.h g_skinny_bf16; brgemm_bf16_skinny.h)
+  if (p.launcher == GL_BF16_SKINNY) { // a skinny-batch bf16 layer (mode_switches.h MS_SKINNY_BF16; brgemm_bf16_skinny.h)
     hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
-    if (e == hipErrorInvalidValue && p.split > 1) { // the split refused by its launcher (xsmm_desc.h g_skinny_split): the unsplit skinny launch of the same BN
+    if (e == hipErrorInvalidValue && p.split > 1) { // the split refused by its launcher (mode_switches.h MS_SKINNY_SPLIT): the unsplit skinny launch of the same BN
       (void)hipGetLastError();
       env.skinny_split = 0;
       p = plan_gemm_call(d, br, al, env);
@@ -847,16 +843,8 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     if (e != hipErrorInvalidValue) {
       if (e == hipSuccess) {
         const long long s_all = (long long)a.br * skn_steps(a.k);
-        if (p.split > 1) {
-          g_skinny_split_stats[1].store(p.split, std::memory_order_relaxed);
-          g_skinny_split_stats[2].store(sks_grid(skn_blocks(a.n, p.tile), p.split), std::memory_order_relaxed);
-          g_skinny_split_stats[0].fetch_add(1, std::memory_order_relaxed);
-        }
-        g_skinny_bf16_stats[1].store(sks_grid(skn_blocks(a.n, p.tile), p.split), std::memory_order_relaxed);
-        g_skinny_bf16_stats[2].store(p.split > 1 ? sks_block_waves(p.split, (int)s_all) : skn_waves(s_all), std::memory_order_relaxed);
-        g_skinny_bf16_stats[3].store(p.tile, std::memory_order_relaxed);
-        g_skinny_bf16_stats[4].store(p.b_kind, std::memory_order_relaxed);
-        g_skinny_bf16_stats[0].fetch_add(1, std::memory_order_relaxed);
+        if (p.split > 1) count_mode_launch(MS_SKINNY_SPLIT, {p.split, sks_grid(skn_blocks(a.n, p.tile), p.split)});
+        count_mode_launch(MS_SKINNY_BF16, {sks_grid(skn_blocks(a.n, p.tile), p.split), p.split > 1 ? sks_block_waves(p.split, (int)s_all) : skn_waves(s_all), p.tile, p.b_kind});
       }
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
     }
@@ -864,75 +852,54 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     env.skinny_bf16 = 0;
     p = plan_gemm_call(d, br, al, env);
   }
-  if (p.launcher == GL_BF16_FAST && p.edge) { // edge tiles on the 256x256 tile (xsmm_desc.h g_dma256_edge; brgemm_bf16_dma256_edge.h)
+  if (p.launcher == GL_BF16_FAST && p.edge) { // edge tiles on the 256x256 tile (mode_switches.h MS_DMA256_EDGE; brgemm_bf16_dma256_edge.h)
     const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
     if (e != hipErrorInvalidValue) {
-      if (e == hipSuccess) {
-        g_dma256_edge_stats[1].store(d256e_tiles((int)d.m), std::memory_order_relaxed);
-        g_dma256_edge_stats[2].store(d256e_tiles((int)d.n), std::memory_order_relaxed);
-        g_dma256_edge_stats[3].store(p.b_kind, std::memory_order_relaxed);
-        g_dma256_edge_stats[0].fetch_add(1, std::memory_order_relaxed);
-      }
+      if (e == hipSuccess) count_mode_launch(MS_DMA256_EDGE, {d256e_tiles((int)d.m), d256e_tiles((int)d.n), p.b_kind});
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
     }
     (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
     env.dma256_edge = 0;
     p = plan_gemm_call(d, br, al, env);
   }
-  if (p.launcher == GL_BF16_FAST && p.b_kind != 0) { // a flat or VNNI-4 B on the 256x256 tile (xsmm_desc.h g_dma256_images; brgemm_bf16_dma256_images.h)
+  if (p.launcher == GL_BF16_FAST && p.b_kind != 0) { // a flat or VNNI-4 B on the 256x256 tile (mode_switches.h MS_DMA256_IMAGES; brgemm_bf16_dma256_images.h)
     const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
     if (e != hipErrorInvalidValue) {
-      if (e == hipSuccess) {
-        g_dma256_images_stats[1].store(d.m / 256, std::memory_order_relaxed);
-        g_dma256_images_stats[2].store(d.n / 256, std::memory_order_relaxed);
-        g_dma256_images_stats[3].store(p.b_kind, std::memory_order_relaxed);
-        g_dma256_images_stats[0].fetch_add(1, std::memory_order_relaxed);
-      }
+      if (e == hipSuccess) count_mode_launch(MS_DMA256_IMAGES, {d.m / 256, d.n / 256, p.b_kind});
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
     }
     (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
     env.dma256_images = 0;
     p = plan_gemm_call(d, br, al, env);
   }
-  if (p.edge_k8 && p.launcher == GL_BF16_LW) { // a bf16 half-step ragged-k launch (xsmm_desc.h g_edge_k8_bf16; brgemm_bf16_lw_kedge.h bkedge8_*)
+  if (p.edge_k8 && p.launcher == GL_BF16_LW) { // a bf16 half-step ragged-k launch (mode_switches.h MS_EDGE_K8_BF16; brgemm_bf16_lw_kedge.h bkedge8_*)
     const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
     if (e != hipErrorInvalidValue) {
-      if (e == hipSuccess) { // the tile with its B image: 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4
-        g_edge_k8_bf16_stats[1].store(bkedge_chunks(a.k), std::memory_order_relaxed);
-        g_edge_k8_bf16_stats[2].store(bkedge_overlap(a.k), std::memory_order_relaxed);
-        g_edge_k8_bf16_stats[3].store(blw_variant(p.tile, p.b_kind), std::memory_order_relaxed);
-        g_edge_k8_bf16_stats[0].fetch_add(1, std::memory_order_relaxed);
-      }
+      if (e == hipSuccess) // the tile with its B image: 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4
+        count_mode_launch(MS_EDGE_K8_BF16, {bkedge_chunks(a.k), bkedge_overlap(a.k), blw_variant(p.tile, p.b_kind)});
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
     }
     (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
     env.edge_k8_bf16 = 0;
     p = plan_gemm_call(d, br, al, env);
   }
-  if (p.edge_k && p.launcher == GL_BF16_LW) { // a bf16 ragged-k launch (xsmm_desc.h g_edge_k_bf16; brgemm_bf16_lw_kedge.h)
+  if (p.edge_k && p.launcher == GL_BF16_LW) { // a bf16 ragged-k launch (mode_switches.h MS_EDGE_K_BF16; brgemm_bf16_lw_kedge.h)
     const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
     if (e != hipErrorInvalidValue) {
-      if (e == hipSuccess) { // the tile with its B image: 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4
-        g_edge_k_bf16_stats[1].store(bkedge_chunks(a.k), std::memory_order_relaxed);
-        g_edge_k_bf16_stats[2].store(bkedge_overlap(a.k), std::memory_order_relaxed);
-        g_edge_k_bf16_stats[3].store(blw_variant(p.tile, p.b_kind), std::memory_order_relaxed);
-        g_edge_k_bf16_stats[0].fetch_add(1, std::memory_order_relaxed);
-      }
+      if (e == hipSuccess) // the tile with its B image: 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4
+        count_mode_launch(MS_EDGE_K_BF16, {bkedge_chunks(a.k), bkedge_overlap(a.k), blw_variant(p.tile, p.b_kind)});
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
     }
     (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
     env.edge_k_bf16 = 0;
     p = plan_gemm_call(d, br, al, env);
   }
-  if (p.edge_k) { // a ragged-k launch (xsmm_desc.h g_edge_k; brgemm_f32_lw_kedge.h)
+  if (p.edge_k) { // a ragged-k launch (mode_switches.h MS_EDGE_K; brgemm_f32_lw_kedge.h)
     const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
     if (e != hipErrorInvalidValue) {
       if (e == hipSuccess) {
         static const int variant[5] = {0, V_F32_LW_64x64K2, V_F32_LW_64x32K2, V_F32_LW_32x32K4, V_F32_LW_128x64};
-        g_edge_k_stats[1].store(kedge_chunks(a.k), std::memory_order_relaxed);
-        g_edge_k_stats[2].store(kedge_overlap(a.k), std::memory_order_relaxed);
-        g_edge_k_stats[3].store(variant[p.tile >= 0 && p.tile < 5 ? p.tile : 0], std::memory_order_relaxed);
-        g_edge_k_stats[0].fetch_add(1, std::memory_order_relaxed);
+        count_mode_launch(MS_EDGE_K, {kedge_chunks(a.k), kedge_overlap(a.k), variant[p.tile >= 0 && p.tile < 5 ? p.tile : 0]});
       }
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
     }
@@ -940,7 +907,7 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     env.edge_k = 0;
     p = plan_gemm_call(d, br, al, env);
   }
-  if (p.edge) { // a launch on edge tiles (xsmm_desc.h g_edge_tiles)
+  if (p.edge) { // a launch on edge tiles (mode_switches.h MS_EDGE_TILES)
     const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
     if (e != hipErrorInvalidValue) {
       if (e == hipSuccess) {
@@ -949,10 +916,7 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
         int tbm = bm[ft], tbn = bn[ft], tv = variant[ft];
         if (p.launcher == GL_BF16_LW) // the tile with its B image: 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4
           blw_tile_dims(p.tile, &tbm, &tbn), tv = blw_variant(p.tile, p.b_kind);
-        g_edge_tiles_stats[1].store((d.m + tbm - 1) / tbm, std::memory_order_relaxed);
-        g_edge_tiles_stats[2].store((d.n + tbn - 1) / tbn, std::memory_order_relaxed);
-        g_edge_tiles_stats[3].store(tv, std::memory_order_relaxed);
-        g_edge_tiles_stats[0].fetch_add(1, std::memory_order_relaxed);
+        count_mode_launch(MS_EDGE_TILES, {(d.m + tbm - 1) / tbm, (d.n + tbn - 1) / tbn, tv});
       }
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
     }
@@ -967,15 +931,12 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     (void)hipGetLastError(); // no scratch block: the unsplit launch
     text = "";
   }
-  if (p.tail_tiles > 0 && p.launcher == GL_F32_LW) { // a launch with a split tail (xsmm_desc.h g_tail_split; its scratch block may be missing)
+  if (p.tail_tiles > 0 && p.launcher == GL_F32_LW) { // a launch with a split tail (mode_switches.h MS_TAIL_SPLIT; its scratch block may be missing)
     const hipError_t e = launch_f32_lw_tail(p.tile, a, p.tail_tiles, p.tail_split, stream);
     if (e != hipErrorOutOfMemory && e != hipErrorInvalidValue) {
       if (e == hipSuccess) {
         const int64_t tiles = (d.m / (p.tile == 3 ? 32 : 64)) * (d.n / (p.tile == 1 ? 64 : 32));
-        g_tail_split_stats[1].store(p.tail_tiles, std::memory_order_relaxed);
-        g_tail_split_stats[2].store(p.tail_split, std::memory_order_relaxed);
-        g_tail_split_stats[3].store(tiles - p.tail_tiles, std::memory_order_relaxed);
-        g_tail_split_stats[0].fetch_add(1, std::memory_order_relaxed);
+        count_mode_launch(MS_TAIL_SPLIT, {p.tail_tiles, p.tail_split, tiles - p.tail_tiles});
       }
       return g_last_refined.store(text, std::memory_order_relaxed), e;
     }
@@ -983,14 +944,10 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     text = "";
   }
   g_last_refined.store(text, std::memory_order_relaxed);
-  if (p.halves && p.launcher == GL_F32_LW && p.tile == 1) { // the tiles as two halves each (xsmm_desc.h g_f32_halves): the same kernel name and text
+  if (p.halves && p.launcher == GL_F32_LW && p.tile == 1) { // the tiles as two halves each (mode_switches.h MS_F32_HALVES): the same kernel name and text
     const hipError_t e = launch_f32_lw_halves(a, stream);
     if (e != hipErrorInvalidValue) {
-      if (e == hipSuccess) {
-        g_f32_halves_stats[1].store(d.m / 64, std::memory_order_relaxed);
-        g_f32_halves_stats[2].store(d.n / 64, std::memory_order_relaxed);
-        g_f32_halves_stats[0].fetch_add(1, std::memory_order_relaxed);
-      }
+      if (e == hipSuccess) count_mode_launch(MS_F32_HALVES, {d.m / 64, d.n / 64}); // (word 3 stays 0)
       return e;
     }
     (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off

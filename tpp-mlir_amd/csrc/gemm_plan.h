@@ -50,7 +50,7 @@ enum GemmVariant : int {
 // the rule, 2 = wherever eligible) and xsmm_hip_set_edge_k8_bf16 (the values of edge_k_bf16, for k % 16 == 8) and xsmm_hip_set_dma256_images
 // (0 = off, 1 = the rule, 2 = wherever eligible) and xsmm_hip_set_dma256_edge (the same values) and xsmm_hip_set_skinny_bf16 (0 = off, 1 = the
 // rule, 16 / 32 / 64 = that column-block width wherever eligible) and xsmm_hip_set_skinny_split (0 = off, 1 = the rule, 2 .. 16 = that many parts
-// wherever eligible); brgemm_f32.hip gemm_plan_env fills it per call
+// wherever eligible); mode_switches.h gemm_plan_env_of fills it per call, and the accepted values of each switch stand in its table
 struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; int dma256_edge = 0; int skinny_bf16 = 0; int skinny_split = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
@@ -352,7 +352,7 @@ ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, cons
 constexpr int CHAIN_PLAN_MAXL = 8; // (= CH_MAXL, chain_args.h)
 enum ChainForm : int { CF_CALLS, CF_F32, CF_PLAIN, CF_EDGE, CF_ROUNDS, CF_RAGGED, CF_WIDTHS, CF_WROUNDS, CF_WRAGGED, CF_DMA256, CF_SKINNY, CF_FORMS };
 // xsmm_hip_set_strict, the seven chain switches of the tiles (xsmm_hip_set_chain_*), xsmm_hip_set_edge_tiles and xsmm_hip_set_dma256_images, and
-// xsmm_hip_set_chain_skinny; rt_core.h chain_plan_env fills it per invoke
+// xsmm_hip_set_chain_skinny; mode_switches.h chain_plan_env_of fills it per invoke (rt_core.h chain_plan_env)
 struct ChainPlanEnv { bool strict; int edge, rounds, ragged, widths, width_rounds, widths_ragged, dma256; int edge_tiles, dma256_images; int skinny = 0; };
 // The compute units a launch on the invoke's stream can use - the one input that costs runtime calls (rt_chain.h stream_cus: three). Asked
 // lazily and at most once per invoke: a decision that ends in front of every rule that reads them never pays for them.

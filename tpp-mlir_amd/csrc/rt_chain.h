@@ -271,37 +271,34 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   // the launch and the form's *_stats words (xsmm_hip_chain_*_stats): launches; then row blocks, column tiles and the GemmVariant of the tile
   // with its B image, unless the case says otherwise
   const int tile = plan.tile, b_kind = plan.b_kind;
-  std::atomic<int64_t> *stats = nullptr;
+  tpp::ModeSwitch counted = tpp::MS_COUNT; // the switch whose counters the launch moves (mode_switches.h); MS_COUNT: none
   int64_t word[3] = {plan.tiles_m, plan.tiles_n, blw_variant(tile, b_kind)};
   switch (plan.form) {
   case CF_F32: HIP_OK(launch_f32_chain(tile, c, s)); break;
   case CF_PLAIN: HIP_OK(launch_bf16_chain(BLW_LAYER, tile, b_kind, c, s)); break;
-  case CF_EDGE: HIP_OK(launch_bf16_chain(BLW_CHAIN_EDGE, tile, b_kind, c, s)); stats = g_chain_edge_stats; break;
+  case CF_EDGE: HIP_OK(launch_bf16_chain(BLW_CHAIN_EDGE, tile, b_kind, c, s)); counted = tpp::MS_CHAIN_EDGE; break;
   case CF_ROUNDS: // row groups G, rounds R
-    HIP_OK(launch_bf16_chain(BLW_CHAIN_ROUNDS, tile, b_kind, c, s)); stats = g_chain_rounds_stats;
+    HIP_OK(launch_bf16_chain(BLW_CHAIN_ROUNDS, tile, b_kind, c, s)); counted = tpp::MS_CHAIN_ROUNDS;
     word[0] = plan.groups, word[1] = (plan.tiles_m + plan.groups - 1) / plan.groups;
     break;
-  case CF_RAGGED: HIP_OK(launch_bf16_chain_ragged(tile, b_kind, c, s)); stats = g_chain_ragged_stats; break;
-  case CF_WIDTHS: HIP_OK(launch_bf16_chain_widths(tile, b_kind, c, s)); stats = g_chain_widths_stats; break;
+  case CF_RAGGED: HIP_OK(launch_bf16_chain_ragged(tile, b_kind, c, s)); counted = tpp::MS_CHAIN_RAGGED; break;
+  case CF_WIDTHS: HIP_OK(launch_bf16_chain_widths(tile, b_kind, c, s)); counted = tpp::MS_CHAIN_WIDTHS; break;
   case CF_WROUNDS: // row blocks, resident workgroup columns W
-    HIP_OK(launch_bf16_chain_wrounds(tile, b_kind, c, s)); stats = g_chain_width_rounds_stats;
+    HIP_OK(launch_bf16_chain_wrounds(tile, b_kind, c, s)); counted = tpp::MS_CHAIN_WIDTH_ROUNDS;
     word[1] = plan.groups;
     break;
-  case CF_WRAGGED: HIP_OK(launch_bf16_chain_wragged(tile, b_kind, c, s)); stats = g_chain_widths_ragged_stats; break;
+  case CF_WRAGGED: HIP_OK(launch_bf16_chain_wragged(tile, b_kind, c, s)); counted = tpp::MS_CHAIN_WIDTHS_RAGGED; break;
   case CF_DMA256: // row groups G, rounds R, the B image
-    HIP_OK(launch_bf16_dma256_chain(b_kind, c, s)); stats = g_chain_dma256_stats;
+    HIP_OK(launch_bf16_dma256_chain(b_kind, c, s)); counted = tpp::MS_CHAIN_DMA256;
     word[0] = plan.groups, word[1] = chain_rounds_rounds(plan.tiles_m, plan.groups), word[2] = b_kind;
     break;
   case CF_SKINNY: // resident workgroups G, the column-block width BN (the plan's tile), the B image; the block's key is (1, G): target = epoch * G
-    HIP_OK(launch_bf16_skinny_chain(b_kind, tile, c, s)); stats = g_chain_skinny_stats;
+    HIP_OK(launch_bf16_skinny_chain(b_kind, tile, c, s)); counted = tpp::MS_CHAIN_SKINNY;
     word[0] = plan.groups, word[1] = tile, word[2] = b_kind;
     break;
   default: return false; // (CF_CALLS has returned above)
   }
-  if (stats) {
-    for (int i = 0; i < 3; ++i) stats[1 + i].store(word[i], std::memory_order_relaxed);
-    stats[0].fetch_add(1, std::memory_order_relaxed);
-  }
+  if (counted != tpp::MS_COUNT) tpp::count_mode_launch(counted, {word[0], word[1], word[2]});
   if (blk.verified < 1) {
     // probation (comment at ChainBlock): wait for this launch and look at its error word before anyone can consume its outputs
     HIP_OK(hipStreamSynchronize(s));

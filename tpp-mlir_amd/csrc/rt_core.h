@@ -80,11 +80,7 @@ Config &cfg() {
   return c;
 }
 // what the layer-chain launch decision reads besides the calls and the stream's compute units (gemm_plan.h plan_chain): filled per invoke
-inline tpp::ChainPlanEnv chain_plan_env() {
-  const auto rd = [](const std::atomic<int> &v) { return v.load(std::memory_order_relaxed); };
-  return tpp::ChainPlanEnv{rd(cfg().strict) != 0, rd(tpp::g_chain_edge), rd(tpp::g_chain_rounds), rd(tpp::g_chain_ragged), rd(tpp::g_chain_widths),
-                           rd(tpp::g_chain_width_rounds), rd(tpp::g_chain_widths_ragged), rd(tpp::g_chain_dma256), rd(tpp::g_edge_tiles), rd(tpp::g_dma256_images), rd(tpp::g_chain_skinny)};
-}
+inline tpp::ChainPlanEnv chain_plan_env() { return tpp::chain_plan_env_of(cfg().strict.load(std::memory_order_relaxed) != 0); }
 // the stream an invoke of THIS thread launches on: the process-wide setting, unless the thread is re-running a journaled chain
 // launch on that launch's stream (check_chain_errors; ADVICE r5: the re-run must not change the setting other threads read)
 // (in the static TLS block - initial-exec: a %fs-relative load; the general-dynamic model of a shared library calls __tls_get_addr per

@@ -15,6 +15,7 @@
 #include "chain_args.h"
 #include "brgemm_bf16_dma256_chain.h" // D256C_BM, chain_rounds_rounds (rt_chain.h)
 #include "gemm_plan.h"
+#include "mode_switches.h"
 #include "host_cache.h"
 #include "rt_relayout.h" // relayout grids: affine runs of a recorded pack / unpack group (plain C++, outside the unit namespace)
 
@@ -551,78 +552,30 @@ extern "C" void xsmm_hip_fold_epilogue_stats(int64_t out[3]) {
   out[2] = g_fe_declined.load(std::memory_order_relaxed); // element-wise invokes on a GEMM group that flushed it instead (ineligible)
 }
 extern "C" int xsmm_hip_force_split(int v) { return tpp::force_gemm_split(v); }
-extern "C" int xsmm_hip_set_tail_split(int mode) { return mode < 0 || mode > 16 ? -1 : tpp::g_tail_split.exchange(mode); }
-extern "C" int xsmm_hip_set_edge_tiles(int mode) { return tpp::edge_tiles_mode_ok(mode) ? tpp::g_edge_tiles.exchange(mode) : -1; }
-extern "C" void xsmm_hip_edge_tiles_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_tiles_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_edge_k(int mode) { return tpp::edge_k_mode_ok(mode) ? tpp::g_edge_k.exchange(mode) : -1; }
-extern "C" void xsmm_hip_edge_k_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_f32_halves(int mode) { return tpp::f32_halves_mode_ok(mode) ? tpp::g_f32_halves.exchange(mode) : -1; }
-extern "C" void xsmm_hip_f32_halves_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_f32_halves_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_edge_k_bf16(int mode) { return tpp::edge_k_bf16_mode_ok(mode) ? tpp::g_edge_k_bf16.exchange(mode) : -1; }
-extern "C" void xsmm_hip_edge_k_bf16_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k_bf16_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_chain_edge(int mode) { return tpp::chain_edge_mode_ok(mode) ? tpp::g_chain_edge.exchange(mode) : -1; }
-extern "C" void xsmm_hip_chain_edge_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_edge_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_dma256_images(int mode) { return tpp::dma256_images_mode_ok(mode) ? tpp::g_dma256_images.exchange(mode) : -1; }
-extern "C" void xsmm_hip_dma256_images_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_dma256_images_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_dma256_edge(int mode) { return tpp::dma256_edge_mode_ok(mode) ? tpp::g_dma256_edge.exchange(mode) : -1; }
-extern "C" void xsmm_hip_dma256_edge_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_dma256_edge_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_skinny_bf16(int mode) { return tpp::skinny_bf16_mode_ok(mode) ? tpp::g_skinny_bf16.exchange(mode) : -1; }
-extern "C" int xsmm_hip_set_skinny_split(int mode) { return tpp::skinny_split_mode_ok(mode) ? tpp::g_skinny_split.exchange(mode) : -1; }
-extern "C" void xsmm_hip_skinny_split_stats(int64_t out[3]) {
-  for (int i = 0; i < 3; ++i) out[i] = tpp::g_skinny_split_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" void xsmm_hip_skinny_bf16_stats(int64_t out[5]) {
-  for (int i = 0; i < 5; ++i) out[i] = tpp::g_skinny_bf16_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_edge_k8_bf16(int mode) { return tpp::edge_k_bf16_mode_ok(mode) ? tpp::g_edge_k8_bf16.exchange(mode) : -1; }
-extern "C" void xsmm_hip_edge_k8_bf16_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_edge_k8_bf16_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_chain_ragged(int mode) { return tpp::chain_ragged_mode_ok(mode) ? tpp::g_chain_ragged.exchange(mode) : -1; }
-extern "C" void xsmm_hip_chain_ragged_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_ragged_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_chain_widths(int mode) { return tpp::chain_widths_mode_ok(mode) ? tpp::g_chain_widths.exchange(mode) : -1; }
-extern "C" void xsmm_hip_chain_widths_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_widths_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_chain_width_rounds(int mode) { return tpp::chain_width_rounds_mode_ok(mode) ? tpp::g_chain_width_rounds.exchange(mode) : -1; }
-extern "C" void xsmm_hip_chain_width_rounds_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_width_rounds_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_chain_widths_ragged(int mode) { return tpp::chain_widths_ragged_mode_ok(mode) ? tpp::g_chain_widths_ragged.exchange(mode) : -1; }
-extern "C" void xsmm_hip_chain_widths_ragged_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_widths_ragged_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_chain_dma256(int mode) { return tpp::chain_dma256_mode_ok(mode) ? tpp::g_chain_dma256.exchange(mode) : -1; }
-extern "C" void xsmm_hip_chain_dma256_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_dma256_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_chain_skinny(int mode) { return tpp::chain_skinny_mode_ok(mode) ? tpp::g_chain_skinny.exchange(mode) : -1; }
-extern "C" void xsmm_hip_chain_skinny_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_skinny_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" int xsmm_hip_set_chain_rounds(int mode) { return tpp::chain_rounds_mode_ok(mode) ? tpp::g_chain_rounds.exchange(mode) : -1; }
-extern "C" void xsmm_hip_chain_rounds_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_chain_rounds_stats[i].load(std::memory_order_relaxed);
-}
-extern "C" void xsmm_hip_tail_split_stats(int64_t out[4]) {
-  for (int i = 0; i < 4; ++i) out[i] = tpp::g_tail_split_stats[i].load(std::memory_order_relaxed);
-}
+// the opt-in mode switches: a setter and a counter reader each, over the one table of mode_switches.h (which holds the accepted
+// values, the default, the environment variable and how many words the reader writes)
+#define MODE_SWITCH_ABI(name, ms)                                                        \
+  extern "C" int xsmm_hip_set_##name(int mode) { return tpp::set_mode(tpp::ms, mode); } \
+  extern "C" void xsmm_hip_##name##_stats(int64_t *out) { tpp::mode_stats(tpp::ms, out); }
+MODE_SWITCH_ABI(tail_split, MS_TAIL_SPLIT)
+MODE_SWITCH_ABI(edge_tiles, MS_EDGE_TILES)
+MODE_SWITCH_ABI(edge_k, MS_EDGE_K)
+MODE_SWITCH_ABI(edge_k_bf16, MS_EDGE_K_BF16)
+MODE_SWITCH_ABI(edge_k8_bf16, MS_EDGE_K8_BF16)
+MODE_SWITCH_ABI(dma256_images, MS_DMA256_IMAGES)
+MODE_SWITCH_ABI(dma256_edge, MS_DMA256_EDGE)
+MODE_SWITCH_ABI(skinny_bf16, MS_SKINNY_BF16)
+MODE_SWITCH_ABI(skinny_split, MS_SKINNY_SPLIT)
+MODE_SWITCH_ABI(f32_halves, MS_F32_HALVES)
+MODE_SWITCH_ABI(chain_edge, MS_CHAIN_EDGE)
+MODE_SWITCH_ABI(chain_rounds, MS_CHAIN_ROUNDS)
+MODE_SWITCH_ABI(chain_ragged, MS_CHAIN_RAGGED)
+MODE_SWITCH_ABI(chain_widths, MS_CHAIN_WIDTHS)
+MODE_SWITCH_ABI(chain_width_rounds, MS_CHAIN_WIDTH_ROUNDS)
+MODE_SWITCH_ABI(chain_widths_ragged, MS_CHAIN_WIDTHS_RAGGED)
+MODE_SWITCH_ABI(chain_dma256, MS_CHAIN_DMA256)
+MODE_SWITCH_ABI(chain_skinny, MS_CHAIN_SKINNY)
+#undef MODE_SWITCH_ABI
 // the VNNI blocking factor of bf16 B operands dispatched from now on (2 or 4); returns the previous one, -1 for an invalid factor
 extern "C" int xsmm_hip_set_vnni_factor(int v) {
   if (v != 2 && v != 4) return -1;

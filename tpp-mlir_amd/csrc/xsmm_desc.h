@@ -139,195 +139,6 @@ int force_gemm_split(int workgroups_per_tile); // xsmm_hip_force_split (brgemm_f
 // bf16 VNNI-2 / VNNI-4, m = n = 64, k a multiple of 64; never in strict mode; gemm_plan.h)
 bool gemm_quads_pay(const GemmDesc &d, int n_items, int64_t br);
 hipError_t launch_gemm_quads(const GemmDesc &d, const QuadItem *quads, int n_quads, int64_t br, hipStream_t stream);
-// TAIL SPLIT (xsmm_hip_set_tail_split / TPP_HIP_TAIL_SPLIT; gemm_plan.cpp choose_f32_tail_split): 0 = off, 1 = the model, 2 .. 16 = that
-// many workgroups per tail tile. The setting and the counters of xsmm_hip_tail_split_stats live HERE, as inline variables: the ABI
-// layer (runtime.cpp) sets and reads them, the launch code (brgemm_f32.hip gemm_plan_env, launch_gemm) reads the setting per invoke
-// and counts - and the host-only builds of runtime.cpp (tests/tsan) link without any kernel file.
-inline std::atomic<int> g_tail_split{[] {
-  const char *e = getenv("TPP_HIP_TAIL_SPLIT");
-  const int v = e ? atoi(e) : 0;
-  return v >= 0 && v <= 16 ? v : 0;
-}()};
-inline std::atomic<int64_t> g_tail_split_stats[4]; // launches with a split tail; tail tiles, workgroups per tail tile, body tiles of the latest
-// EDGE TILES (xsmm_hip_set_edge_tiles / TPP_HIP_EDGE_TILES; gemm_plan.cpp choose_f32_edge_variant, choose_bf16_edge_tile): 0 = off, 1 = the
-// f32 tile rule, 6 / 7 / 9 / 10 = that f32 GemmVariant's tile; 2 = the tile rule for f32 (mode 1's) and for bf16, 20 .. 23 = that bf16
-// GemmVariant's tile (f32 as with the mode off). Setting and counters (xsmm_hip_edge_tiles_stats) as inline variables, like the tail split's above.
-inline bool edge_tiles_mode_ok(int v) { return v == 0 || v == 1 || v == 2 || v == 6 || v == 7 || v == 9 || v == 10 || (v >= 20 && v <= 23); }
-inline std::atomic<int> g_edge_tiles{[] {
-  const char *e = getenv("TPP_HIP_EDGE_TILES");
-  const int v = e ? atoi(e) : 0;
-  return edge_tiles_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_edge_tiles_stats[4]; // edge launches; tile rows, tile columns, GemmVariant of the tile of the latest
-// RAGGED k (xsmm_hip_set_edge_k / TPP_HIP_EDGE_K; gemm_plan.cpp plan_gemm_call, brgemm_f32_lw_kedge.h): 0 = off, 1 = the tile rule, 6 / 7 /
-// 9 / 10 = that GemmVariant's tile. A switch of its own: the edge-tile modes leave a k that is not a multiple of 64 where it is.
-inline bool edge_k_mode_ok(int v) { return v == 0 || v == 1 || v == 6 || v == 7 || v == 9 || v == 10; }
-inline std::atomic<int> g_edge_k{[] {
-  const char *e = getenv("TPP_HIP_EDGE_K");
-  const int v = e ? atoi(e) : 0;
-  return edge_k_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_edge_k_stats[4]; // ragged-k launches; chunks per batch element, overlap o, GemmVariant of the tile of the latest
-// RAGGED k, bf16 (xsmm_hip_set_edge_k_bf16 / TPP_HIP_EDGE_K_BF16; gemm_plan.cpp plan_gemm_call, brgemm_bf16_lw_kedge.h): 0 = off, 1 = the
-// tile rule, 20 .. 23 = that bf16 GemmVariant's tile. A switch of its own: xsmm_hip_set_edge_k leaves every bf16 call where it is.
-inline bool edge_k_bf16_mode_ok(int v) { return v == 0 || v == 1 || (v >= 20 && v <= 23); }
-inline std::atomic<int> g_edge_k_bf16{[] {
-  const char *e = getenv("TPP_HIP_EDGE_K_BF16");
-  const int v = e ? atoi(e) : 0;
-  return edge_k_bf16_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_edge_k_bf16_stats[4]; // bf16 ragged-k launches; chunks per batch element, overlap o, GemmVariant of the tile (with its B image) of the latest
-// RAGGED k in HALF steps, bf16 (xsmm_hip_set_edge_k8_bf16 / TPP_HIP_EDGE_K8_BF16; brgemm_bf16_lw_kedge.h bkedge8_*): k % 16 == 8 (1000, 200,
-// 72). The values of g_edge_k_bf16, a switch of its own: the two partition the lengths and neither looks at the other's mode.
-inline std::atomic<int> g_edge_k8_bf16{[] {
-  const char *e = getenv("TPP_HIP_EDGE_K8_BF16");
-  const int v = e ? atoi(e) : 0;
-  return edge_k_bf16_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_edge_k8_bf16_stats[4]; // half-step launches; chunks per batch element, overlap o, GemmVariant of the tile (with its B image) of the latest
-// FLAT and VNNI-4 B on the 256x256 bf16 tile (xsmm_hip_set_dma256_images / TPP_HIP_DMA256_IMAGES; gemm_plan.cpp plan_gemm_call,
-// brgemm_bf16_dma256.hip launch_bf16_dma256_image, brgemm_bf16_dma256_images.h): 0 = off, 1 = the rule (where a VNNI-2 descriptor goes to that tile: at
-// least 240 tiles and the fill term), 2 = every eligible whole-layer call (tests, measurements).
-inline bool dma256_images_mode_ok(int v) { return v >= 0 && v <= 2; }
-inline std::atomic<int> g_dma256_images{[] {
-  const char *e = getenv("TPP_HIP_DMA256_IMAGES");
-  const int v = e ? atoi(e) : 0;
-  return dma256_images_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_dma256_images_stats[4]; // such launches; tile rows, tile columns (256x256 tiles), B image (2 flat, 4 VNNI-4) of the latest
-// EDGE TILES on the 256x256 bf16 tile (xsmm_hip_set_dma256_edge / TPP_HIP_DMA256_EDGE; gemm_plan.cpp plan_gemm_call, brgemm_bf16_dma256_edge.hip
-// launch_bf16_dma256_edge, brgemm_bf16_dma256_edge.h): 0 = off, 1 = the rule (gemm_plan.cpp dma256_edge_rule), 2 = every eligible whole-layer call
-// (m, n >= 256, m or n not a multiple of 256; tests, measurements).
-inline bool dma256_edge_mode_ok(int v) { return v >= 0 && v <= 2; }
-inline std::atomic<int> g_dma256_edge{[] {
-  const char *e = getenv("TPP_HIP_DMA256_EDGE");
-  const int v = e ? atoi(e) : 0;
-  return dma256_edge_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_dma256_edge_stats[4]; // such launches; tile rows, tile columns (ceil-divided), B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
-// SKINNY-BATCH bf16 LAYERS (xsmm_hip_set_skinny_bf16 / TPP_HIP_SKINNY_BF16; gemm_plan.cpp plan_gemm_call, brgemm_bf16_skinny.hip
-// launch_bf16_skinny, brgemm_bf16_skinny.h): 0 = off, 1 = the rule (gemm_plan.cpp skinny_bf16_bn), 16 / 32 / 64 = every eligible whole-layer
-// call (bf16, 1 <= m <= 31, planned on the generic kernel) on column blocks of that width (tests, measurements). A switch of its own: it
-// reads no other mode and no other switch reads it.
-inline bool skinny_bf16_mode_ok(int v) { return v == 0 || v == 1 || v == 16 || v == 32 || v == 64; }
-inline std::atomic<int> g_skinny_bf16{[] {
-  const char *e = getenv("TPP_HIP_SKINNY_BF16");
-  const int v = e ? atoi(e) : 0;
-  return skinny_bf16_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_skinny_bf16_stats[5]; // such launches; workgroups, waves per workgroup, BN, B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
-// K SPLIT ACROSS WORKGROUPS OF THE SKINNY-BATCH KERNEL (xsmm_hip_set_skinny_split / TPP_HIP_SKINNY_SPLIT; gemm_plan.cpp plan_gemm_call,
-// brgemm_bf16_skinny_split.hip launch_bf16_skinny_split, brgemm_bf16_skinny_split.h): 0 = off, 1 = the rule (gemm_plan.cpp skinny_split_parts),
-// 2 .. 16 = that many parts wherever eligible (tests, measurements). A refinement of the skinny launch and nothing else: read only for a
-// call the planner has already put on the skinny kernel; with xsmm_hip_set_skinny_bf16 off it changes nothing. No other switch reads it.
-inline bool skinny_split_mode_ok(int v) { return v >= 0 && v <= 16; }
-inline std::atomic<int> g_skinny_split{[] {
-  const char *e = getenv("TPP_HIP_SKINNY_SPLIT");
-  const int v = e ? atoi(e) : 0;
-  return skinny_split_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_skinny_split_stats[3]; // skinny launches that ran split; parts P_eff, workgroups (column blocks * P_eff) of the latest
-// HALVES (xsmm_hip_set_f32_halves / TPP_HIP_F32_HALVES; gemm_plan.cpp choose_f32_halves, brgemm_f32_lw.hip launch_f32_lw_halves): 0 = off, 1 =
-// the rule (default: at least one 64x64 tile per CU), 2 = every eligible whole-layer call on the 64x64 + K2 f32 tile runs as two 64x32 + K2
-// workgroups per tile (the same bits).
-inline bool f32_halves_mode_ok(int v) { return v >= 0 && v <= 2; }
-inline std::atomic<int> g_f32_halves{[] {
-  const char *e = getenv("TPP_HIP_F32_HALVES");
-  const int v = e ? atoi(e) : 1;
-  return f32_halves_mode_ok(v) ? v : 1;
-}()};
-inline std::atomic<int64_t> g_f32_halves_stats[4]; // launches carried out as halves; tile rows, tile columns (64x64 tiles) of the latest, 0
-// RAGGED-m CHAINS (xsmm_hip_set_chain_edge / TPP_HIP_CHAIN_EDGE; gemm_plan.cpp plan_chain_edge, rt_chain.h try_chain_launch,
-// brgemm_bf16_lw_chain_edge.h): 0 = off, 1 = a bf16 chain whose m the tile's rows do not divide runs as one launch on edge row tiles. A
-// switch of its own: the four ragged-layer switches above decide single calls only and leave every chain decision where it is.
-inline bool chain_edge_mode_ok(int v) { return v == 0 || v == 1; }
-inline std::atomic<int> g_chain_edge{[] {
-  const char *e = getenv("TPP_HIP_CHAIN_EDGE");
-  const int v = e ? atoi(e) : 0;
-  return chain_edge_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_chain_edge_stats[4]; // ragged chain launches; tile rows, tile columns, GemmVariant of the tile (with its B image) of the latest
-// MULTI-ROUND CHAINS (xsmm_hip_set_chain_rounds / TPP_HIP_CHAIN_ROUNDS; gemm_plan.cpp plan_chain_rounds, rt_chain.h try_chain_launch,
-// brgemm_bf16_lw_chain_rounds.h): 0 = off, 1 = a bf16 chain with more output tiles than compute units runs as one launch on G resident row
-// groups, G by rule; 1000 + G = force G row groups (tests and measurements; also for a chain that would fit in one round). A switch of its own.
-inline bool chain_rounds_mode_ok(int v) { return v == 0 || v == 1 || (v > 1000 && v <= 1000 + 0x10000); }
-inline std::atomic<int> g_chain_rounds{[] {
-  const char *e = getenv("TPP_HIP_CHAIN_ROUNDS");
-  const int v = e ? atoi(e) : 0;
-  return chain_rounds_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_chain_rounds_stats[4]; // multi-round chain launches; row groups G, rounds R, GemmVariant of the tile (with its B image) of the latest
-// RAGGED-WIDTH CHAINS (xsmm_hip_set_chain_ragged / TPP_HIP_CHAIN_RAGGED; gemm_plan.cpp plan_chain_ragged, rt_chain.h try_chain_launch,
-// brgemm_bf16_lw_chain_ragged.h): 0 = off, 1 = a bf16 chain with a ragged n and / or a layer whose k is a multiple of 8 but not of 64 runs as
-// one launch on edge tiles with every layer's last chunk shifted back. A switch of its own: xsmm_hip_set_chain_edge keeps ragged-m-only
-// chains, the multi-round switch never combines with this one, the single-call ragged switches decide single calls only.
-inline bool chain_ragged_mode_ok(int v) { return v == 0 || v == 1; }
-inline std::atomic<int> g_chain_ragged{[] {
-  const char *e = getenv("TPP_HIP_CHAIN_RAGGED");
-  const int v = e ? atoi(e) : 0;
-  return chain_ragged_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_chain_ragged_stats[4]; // ragged-width chain launches; tile rows, tile columns (both ceil-divided), GemmVariant of the tile (with its B image) of the latest
-// MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths / TPP_HIP_CHAIN_WIDTHS; gemm_plan.cpp plan_chain_widths, rt_chain.h try_chain_launch,
-// brgemm_bf16_lw_chain_widths.h): 0 = off, 1 = a divisible bf16 chain whose layers differ in n (1024-4096-1024) runs as one launch on
-// m / BM x max_l(n_l / BN) workgroups, each sitting out the layers that have no column tile for it. A switch of its own: equal widths stay
-// the plain chain's, and a ragged m, n or k or several rounds never combine with different widths.
-inline bool chain_widths_mode_ok(int v) { return v == 0 || v == 1; }
-inline std::atomic<int> g_chain_widths{[] {
-  const char *e = getenv("TPP_HIP_CHAIN_WIDTHS");
-  const int v = e ? atoi(e) : 0;
-  return chain_widths_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_chain_widths_stats[4]; // mixed-width chain launches; row blocks, the widest layer's column tiles, GemmVariant of the tile (with its B image) of the latest
-// COLUMN ROUNDS OF MIXED-WIDTH CHAINS (xsmm_hip_set_chain_width_rounds / TPP_HIP_CHAIN_WIDTH_ROUNDS; gemm_plan.cpp plan_chain_width_rounds,
-// rt_chain.h try_chain_launch, brgemm_bf16_lw_chain_wrounds.h): 0 = off, 1 = a divisible bf16 chain whose layers differ in n runs as one launch
-// on m / BM x W resident workgroups, W by rule below the widest layer's column tiles - a workgroup walks several column tiles of a wide
-// layer -, 1000 + W = that W (a test / measurement switch). A switch of its own: xsmm_hip_set_chain_widths keeps its meaning.
-inline bool chain_width_rounds_mode_ok(int v) { return v == 0 || v == 1 || (v > 1000 && v <= 1000 + 0x10000); }
-inline std::atomic<int> g_chain_width_rounds{[] {
-  const char *e = getenv("TPP_HIP_CHAIN_WIDTH_ROUNDS");
-  const int v = e ? atoi(e) : 0;
-  return chain_width_rounds_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_chain_width_rounds_stats[4]; // column-round launches; row blocks, resident workgroup columns W, GemmVariant of the tile (with its B image) of the latest
-// RAGGED MIXED-WIDTH CHAINS (xsmm_hip_set_chain_widths_ragged / TPP_HIP_CHAIN_WIDTHS_RAGGED; gemm_plan.cpp plan_chain_widths_ragged, rt_chain.h
-// try_chain_launch, brgemm_bf16_lw_chain_wragged.h): 0 = off, 1 = a bf16 chain whose layers differ in n AND that no tile divides entirely - a
-// ragged m, some ragged n(l), some k(l) % 64 != 0: 784-512-256-128 - runs as one launch on ceil(m / BM) x max_l ceil(n_l / BN) workgroups. A
-// switch of its own: a chain some tile divides entirely stays xsmm_hip_set_chain_widths', equal widths the other chain switches'.
-inline bool chain_widths_ragged_mode_ok(int v) { return v == 0 || v == 1; }
-inline std::atomic<int> g_chain_widths_ragged{[] {
-  const char *e = getenv("TPP_HIP_CHAIN_WIDTHS_RAGGED");
-  const int v = e ? atoi(e) : 0;
-  return chain_widths_ragged_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_chain_widths_ragged_stats[4]; // ragged mixed-width launches; row blocks, the widest layer's column tiles (both ceil-divided), GemmVariant of the tile (with its B image) of the latest
-// LAYER CHAINS ON THE 256x256 bf16 TILE (xsmm_hip_set_chain_dma256 / TPP_HIP_CHAIN_DMA256; gemm_plan.cpp plan_chain_dma256, rt_chain.h
-// try_chain_launch, brgemm_bf16_dma256_chain.hip, brgemm_bf16_dma256_chain.h): 0 = off, 1 = a bf16 chain every call of which runs on the 256x256
-// tile as a single call runs as one launch of that tile's chain kernel (the rule and its gate), 2 = every eligible chain (tests,
-// measurements), 1000 + G = every eligible chain on G row groups. A switch of its own: no other switch reads it, and it reads no other
-// mode but xsmm_hip_set_dma256_images' in mode 1 (which calls run on the tile).
-inline bool chain_dma256_mode_ok(int v) { return v == 0 || v == 1 || v == 2 || (v > 1000 && v <= 1000 + 0x10000); }
-inline std::atomic<int> g_chain_dma256{[] {
-  const char *e = getenv("TPP_HIP_CHAIN_DMA256");
-  const int v = e ? atoi(e) : 0;
-  return chain_dma256_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_chain_dma256_stats[4]; // such launches; resident row groups G (tiles_m in one round), rounds R, B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
-// SKINNY-BATCH LAYER CHAINS (xsmm_hip_set_chain_skinny / TPP_HIP_CHAIN_SKINNY; gemm_plan.cpp plan_chain_skinny, rt_chain.h try_chain_launch,
-// brgemm_bf16_skinny_chain.hip, brgemm_bf16_skinny_chain.h): 0 = off, 1 = a bf16 chain with 1 .. 31 rows runs as one launch of the skinny kernel's
-// chain form on the column-block width BN of the rule (and its gate), 16 / 32 / 64 = that BN wherever eligible, 1000 * G + BN (1 <= G <= 512) =
-// that BN on G resident workgroups (tests, measurements). A switch of its own: it reads neither xsmm_hip_set_skinny_bf16 nor
-// xsmm_hip_set_skinny_split - those decide single calls only - and neither reads it.
-inline bool chain_skinny_mode_ok(int v) {
-  const int bn = v >= 1000 ? v % 1000 : v, g = v >= 1000 ? v / 1000 : 1;
-  return v == 0 || v == 1 || ((bn == 16 || bn == 32 || bn == 64) && g >= 1 && g <= 512);
-}
-inline std::atomic<int> g_chain_skinny{[] {
-  const char *e = getenv("TPP_HIP_CHAIN_SKINNY");
-  const int v = e ? atoi(e) : 0;
-  return chain_skinny_mode_ok(v) ? v : 0;
-}()};
-inline std::atomic<int64_t> g_chain_skinny_stats[4]; // such launches; resident workgroups G, column-block width BN, B image (0 VNNI-2, 2 flat, 4 VNNI-4) of the latest
 int set_strict_kernels(int on); // returns the previous setting
 bool strict_kernels();
 const char *last_grouped_kernel(); // kernel family of the most recent launch_gemm_grouped ("" before the first)
@@ -341,7 +152,7 @@ hipError_t launch_binary(const BinaryDesc &d, const void *lhs, const void *rhs, 
 // most recent launch_unary / launch_binary: the kernel instance it ran (a static string such as "unary_kernel<f32,v4>, flat",
 // "transpose_vec<bf16,128x128>", "vnni2_rows4<wt>"; "" before the first) and the launch's total block count
 // (xsmm_hip_last_eltwise_kernel / _grid: tests assert which path a shape reached and derive every block's span from the grid; the
-// grouped kernels of the tile queue do not report). Inline variables like g_tail_split above: eltwise.hip stores, runtime.cpp reads,
+// grouped kernels of the tile queue do not report). Inline variables like the mode switches' (mode_switches.h): eltwise.hip stores, runtime.cpp reads,
 // and the host-only builds of runtime.cpp (tests/tsan) link without any kernel file. Relaxed accesses, as last_refined_kernel.
 inline std::atomic<const char *> g_last_eltwise{""};
 inline std::atomic<int64_t> g_last_eltwise_grid{0};

@@ -111,42 +111,6 @@ _SIGNATURES = {
     "xsmm_hip_last_eltwise_grid": (I64, []),
     "xsmm_hip_force_variant": (None, [ctypes.c_int]),
     "xsmm_hip_force_split": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_set_tail_split": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_tail_split_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_edge_tiles": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_edge_tiles_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_edge_k": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_edge_k_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_edge_k_bf16": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_edge_k_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_edge_k8_bf16": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_edge_k8_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_dma256_images": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_dma256_images_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_dma256_edge": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_dma256_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_skinny_bf16": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_skinny_bf16_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_skinny_split": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_skinny_split_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_chain_dma256": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_chain_dma256_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_chain_skinny": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_chain_skinny_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_f32_halves": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_f32_halves_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_chain_edge": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_chain_edge_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_chain_ragged": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_chain_ragged_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_chain_widths": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_chain_widths_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_chain_width_rounds": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_chain_width_rounds_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_chain_widths_ragged": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_chain_widths_ragged_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
-    "xsmm_hip_set_chain_rounds": (ctypes.c_int, [ctypes.c_int]),
-    "xsmm_hip_chain_rounds_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_transpose": (ctypes.c_int, [ctypes.c_int]),
     "xsmm_hip_fold_transpose_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
     "xsmm_hip_set_fold_epilogue": (ctypes.c_int, [ctypes.c_int]),
@@ -159,6 +123,109 @@ _SIGNATURES = {
     "xsmm_hip_get_f32_precision": (ctypes.c_int, []),
     "xsmm_hip_version": (ctypes.c_char_p, []),
 }
+
+# The opt-in mode switches (csrc/mode_switches.h holds the library's table, one row each): name -> (words of the counter block, docstring of
+# XsmmRuntime.set_<name>, docstring of XsmmRuntime.<name>_stats). The signatures of xsmm_hip_set_<name> / xsmm_hip_<name>_stats and both methods
+# are made from it below; what a mode means stands in include/tpp_xsmm_abi.h.
+_MODE_SWITCHES = {
+    "tail_split": (4,
+        """f32 whole-layer calls with a partial last round of workgroups: 0 off (default), 1 the model, 2 .. 16 that many workgroups per
+        tail tile; returns the previous setting, -1 for a value it refuses""",
+        """(launches with a split tail; tail tiles, workgroups per tail tile, body tiles of the most recent one)"""),
+    "edge_tiles": (4,
+        """whole-layer calls whose m or n no tile divides, on the loader-wave tiles: 0 off (default); f32: 1 the tile rule, 6 / 7 / 9 / 10
+        the tile of that kernel variant; 2 the tile rule for f32 (mode 1's) and for bf16; 20 / 21 / 22 / 23 the bf16 tile 32x64 + K2 /
+        64x64 / 64x128 / 128x128 whatever the B image (f32 as with the mode off); returns the previous mode, -1 for a value it refuses""",
+        """(edge launches; tile rows, tile columns, variant number of the tile of the most recent one - bf16: with its B image, 20 + t
+        VNNI-2, 24 + t flat, 28 + t VNNI-4)"""),
+    "edge_k": (4,
+        """f32 whole-layer calls whose k is a multiple of 8 but not of 64 (k >= 64), on the loader-wave tiles: 0 off (default), 1 the tile
+        rule, 6 / 7 / 9 / 10 the tile of that kernel variant; returns the previous mode, -1 for a value it refuses""",
+        """(ragged-k launches; chunks per batch element, re-read k-values of the last chunk, variant number of the tile of the most recent one)"""),
+    "edge_k_bf16": (4,
+        """bf16 whole-layer calls whose k is a multiple of 16 but not of 64 (k >= 64), on the bf16 loader-wave tiles: 0 off (default), 1 the
+        tile rule, 20 .. 23 the tile 32x64 + K2 / 64x64 / 64x128 / 128x128; returns the previous mode, -1 for a value it refuses""",
+        """(bf16 ragged-k launches; chunks per batch element, re-read k-values of the last chunk, variant number of the tile with its B
+        image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""),
+    "edge_k8_bf16": (4,
+        """bf16 whole-layer calls whose k is a multiple of 8 but not of 16 (k >= 64: 1000, 200, 72), on the bf16 loader-wave tiles in half
+        steps: 0 off (default), 1 the tile rule, 20 .. 23 the tile 32x64 + K2 / 64x64 / 64x128 / 128x128; returns the previous mode, -1 for
+        a value it refuses""",
+        """(half-step ragged-k launches; chunks per batch element, re-read k-values of the last chunk, variant number of the tile with
+        its B image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""),
+    "dma256_images": (4,
+        """large bf16 whole-layer calls with a flat or VNNI-4 B on the 256x256 tile (the same bits): 0 off (default), 1 the rule that sends
+        a VNNI-2 call there (at least 240 tiles of 256x256), 2 wherever eligible; returns the previous mode, -1 for a value it refuses""",
+        """(launches of a flat or VNNI-4 B on the 256x256 tile; tile rows, tile columns, B image - 2 flat, 4 VNNI-4 - of the most recent one)"""),
+    "dma256_edge": (4,
+        """large bf16 whole-layer calls whose m or n is not a multiple of 256 (m, n >= 256, n % 8 == 0, k % 32 == 0) on edge tiles of the
+        256x256 tile (the same bits): 0 off (default), 1 the rule, 2 wherever eligible; returns the previous mode, -1 for a value it refuses""",
+        """(edge-tile launches on the 256x256 tile; tile rows, tile columns, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""),
+    "skinny_bf16": (5,
+        """bf16 whole-layer calls with fewer than 32 rows (1 <= m <= 31, n >= BN, n % 8 == 0, k % 8 == 0) on the skinny-batch kernel, one
+        workgroup per block of BN columns: 0 off (default), 1 the rule, 16 / 32 / 64 that BN wherever eligible; returns the previous mode,
+        -1 for a value it refuses""",
+        """(skinny-batch launches; workgroups, waves per workgroup, BN, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""),
+    "skinny_split": (3,
+        """the K range of a skinny-batch launch (set_skinny_bf16) over several workgroups per column block: 0 off (default), 1 the rule,
+        2 .. 16 that many parts wherever eligible; changes nothing while set_skinny_bf16 is 0; returns the previous mode, -1 for a value
+        it refuses""",
+        """(skinny-batch launches that ran split; parts, workgroups - column blocks * parts - of the most recent one)"""),
+    "chain_dma256": (4,
+        """bf16 layer chains whose calls run on the 256x256 tile (256 dividing m and n, k % 32 == 0) as one launch of that tile's chain
+        kernel (the same bits): 0 off (default), 1 the rule (every call runs on that tile today; gated as measured), 2 every eligible
+        chain, 1000 + G on G row groups; returns the previous mode, -1 for a value it refuses""",
+        """(chain launches on the 256x256 tile; resident row groups G, rounds, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""),
+    "chain_skinny": (4,
+        """bf16 layer chains with 1 .. 31 rows as one launch of the skinny-batch kernel's chain form (the bits of the calls under
+        set_skinny_bf16(BN)): 0 off (default), 1 the rule (VNNI-2 chains whose layers have at most 2 MiB of B, on BN 16: as measured), 16 / 32 / 64 that column-block width
+        wherever eligible, 1000 * G + BN that width on G resident workgroups; returns the previous mode, -1 for a value it refuses""",
+        """(skinny-batch chain launches; resident workgroups G, BN, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""),
+    "f32_halves": (4,
+        """f32 whole-layer calls on the 64x64 + K2 tile as two 64x32 + K2 workgroups per tile (the same bits): 0 off, 1 the rule
+        (default: at least one tile per compute unit), 2 wherever eligible; returns the previous mode, -1 for a value it refuses""",
+        """(launches carried out as halves; rows, columns of 64x64 tiles of the most recent one; 0)"""),
+    "chain_edge": (4,
+        """bf16 layer chains whose m the tile's rows do not divide, as one launch on edge row tiles: 0 off (default), 1 on - the tile
+        set_edge_tiles(20 .. 23) names if it fits, else the smallest that fits; returns the previous value, -1 for a value it refuses""",
+        """(ragged chain launches; tile rows, tile columns, variant number of the tile with its B image - 20 + t VNNI-2, 24 + t flat,
+        28 + t VNNI-4 - of the most recent one)"""),
+    "chain_ragged": (4,
+        """bf16 layer chains with a ragged n and / or a layer whose k is a multiple of 8 but not of 64 (1000-wide MLPs), as one launch on
+        edge tiles with every layer's last chunk shifted back: 0 off (default), 1 on - the tile set_edge_tiles(20 .. 23) names if it
+        fits, else the smallest that fits; returns the previous value, -1 for a value it refuses""",
+        """(ragged-width chain launches; tile rows ceil(m / BM), tile columns ceil(n / BN), variant number of the tile with its B image -
+        20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""),
+    "chain_widths": (4,
+        """bf16 layer chains whose layers differ in n (1024-4096-1024, funnels), as one launch on m / BM x max_l(n_l / BN) workgroups, each
+        sitting out the layers that have no column tile for it: 0 off (default), 1 on - the tile all calls were dispatched on if it
+        fits, else (not in strict mode) the smallest that fits; returns the previous value, -1 for a value it refuses""",
+        """(mixed-width chain launches; row blocks m / BM, column tiles of the widest layer, variant number of the tile with its B image -
+        20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""),
+    "chain_width_rounds": (4,
+        """bf16 layer chains whose layers differ in n on m / BM x W resident workgroups, W below the widest layer's column tiles: a
+        workgroup walks several column tiles of a wide layer and one (or none) of a narrow one. 0 off (default), 1 on - tile and W by
+        rule, what measured slower gated back to call by call -, 1000 + W force W workgroup columns (never gated); returns the previous
+        value, -1 for a value it refuses""",
+        """(column-round launches; row blocks m / BM, workgroup columns W, variant number of the tile with its B image - 20 + t VNNI-2,
+        24 + t flat, 28 + t VNNI-4 - of the most recent one)"""),
+    "chain_widths_ragged": (4,
+        """bf16 layer chains whose layers differ in n and that no tile divides entirely - a ragged m, a ragged n in some layer, a k that
+        is a multiple of 8 but not of 64 (784-512-256-128) - as one launch on ceil(m / BM) x max_l ceil(n_l / BN) workgroups: 0 off
+        (default), 1 on - the tile set_edge_tiles(20 .. 23) names if it fits, else the smallest that fits; a chain some tile divides
+        entirely stays set_chain_widths'; returns the previous value, -1 for a value it refuses""",
+        """(ragged mixed-width chain launches; row blocks ceil(m / BM), column tiles of the widest layer max_l ceil(n_l / BN), variant
+        number of the tile with its B image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""),
+    "chain_rounds": (4,
+        """bf16 layer chains with more output tiles than compute units, as one launch on G resident row groups that walk R rounds of
+        row blocks: 0 off (default), 1 on - G by rule -, 1000 + G force G row groups (also for a chain that fits in one round); returns
+        the previous value, -1 for a value it refuses""",
+        """(multi-round chain launches; row groups G, rounds R = ceil(tiles_m / G), variant number of the tile with its B image - 20 + t
+        VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""),
+}
+for _name in _MODE_SWITCHES:
+    _SIGNATURES["xsmm_hip_set_" + _name] = (ctypes.c_int, [ctypes.c_int])
+    _SIGNATURES["xsmm_hip_" + _name + "_stats"] = (None, [ctypes.POINTER(ctypes.c_int64)])
 
 REFERENCE_SYMBOLS = [n for n in _SIGNATURES if not n.startswith("xsmm_hip_")]
 
@@ -369,225 +436,7 @@ class XsmmRuntime:
         """-1 the model, 0 / 1 never, n > 1: n workgroups share the batch-reduce range of one f32 output tile; returns the previous setting"""
         return self.lib.xsmm_hip_force_split(workgroups_per_tile)
 
-    def set_tail_split(self, mode):
-        """f32 whole-layer calls with a partial last round of workgroups: 0 off (default), 1 the model, 2 .. 16 that many workgroups per
-        tail tile; returns the previous setting, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_tail_split(mode)
-
-    def tail_split_stats(self):
-        """(launches with a split tail; tail tiles, workgroups per tail tile, body tiles of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_tail_split_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_edge_tiles(self, mode):
-        """whole-layer calls whose m or n no tile divides, on the loader-wave tiles: 0 off (default); f32: 1 the tile rule, 6 / 7 / 9 / 10
-        the tile of that kernel variant; 2 the tile rule for f32 (mode 1's) and for bf16; 20 / 21 / 22 / 23 the bf16 tile 32x64 + K2 /
-        64x64 / 64x128 / 128x128 whatever the B image (f32 as with the mode off); returns the previous mode, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_edge_tiles(mode)
-
-    def edge_tiles_stats(self):
-        """(edge launches; tile rows, tile columns, variant number of the tile of the most recent one - bf16: with its B image, 20 + t
-        VNNI-2, 24 + t flat, 28 + t VNNI-4)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_edge_tiles_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_edge_k(self, mode):
-        """f32 whole-layer calls whose k is a multiple of 8 but not of 64 (k >= 64), on the loader-wave tiles: 0 off (default), 1 the tile
-        rule, 6 / 7 / 9 / 10 the tile of that kernel variant; returns the previous mode, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_edge_k(mode)
-
-    def edge_k_stats(self):
-        """(ragged-k launches; chunks per batch element, re-read k-values of the last chunk, variant number of the tile of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_edge_k_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_edge_k_bf16(self, mode):
-        """bf16 whole-layer calls whose k is a multiple of 16 but not of 64 (k >= 64), on the bf16 loader-wave tiles: 0 off (default), 1 the
-        tile rule, 20 .. 23 the tile 32x64 + K2 / 64x64 / 64x128 / 128x128; returns the previous mode, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_edge_k_bf16(mode)
-
-    def edge_k_bf16_stats(self):
-        """(bf16 ragged-k launches; chunks per batch element, re-read k-values of the last chunk, variant number of the tile with its B
-        image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_edge_k_bf16_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_edge_k8_bf16(self, mode):
-        """bf16 whole-layer calls whose k is a multiple of 8 but not of 16 (k >= 64: 1000, 200, 72), on the bf16 loader-wave tiles in half
-        steps: 0 off (default), 1 the tile rule, 20 .. 23 the tile 32x64 + K2 / 64x64 / 64x128 / 128x128; returns the previous mode, -1 for
-        a value it refuses"""
-        return self.lib.xsmm_hip_set_edge_k8_bf16(mode)
-
-    def edge_k8_bf16_stats(self):
-        """(half-step ragged-k launches; chunks per batch element, re-read k-values of the last chunk, variant number of the tile with
-        its B image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_edge_k8_bf16_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_dma256_images(self, mode):
-        """large bf16 whole-layer calls with a flat or VNNI-4 B on the 256x256 tile (the same bits): 0 off (default), 1 the rule that sends
-        a VNNI-2 call there (at least 240 tiles of 256x256), 2 wherever eligible; returns the previous mode, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_dma256_images(mode)
-
-    def dma256_images_stats(self):
-        """(launches of a flat or VNNI-4 B on the 256x256 tile; tile rows, tile columns, B image - 2 flat, 4 VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_dma256_images_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_dma256_edge(self, mode):
-        """large bf16 whole-layer calls whose m or n is not a multiple of 256 (m, n >= 256, n % 8 == 0, k % 32 == 0) on edge tiles of the
-        256x256 tile (the same bits): 0 off (default), 1 the rule, 2 wherever eligible; returns the previous mode, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_dma256_edge(mode)
-
-    def dma256_edge_stats(self):
-        """(edge-tile launches on the 256x256 tile; tile rows, tile columns, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_dma256_edge_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_skinny_bf16(self, mode):
-        """bf16 whole-layer calls with fewer than 32 rows (1 <= m <= 31, n >= BN, n % 8 == 0, k % 8 == 0) on the skinny-batch kernel, one
-        workgroup per block of BN columns: 0 off (default), 1 the rule, 16 / 32 / 64 that BN wherever eligible; returns the previous mode,
-        -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_skinny_bf16(mode)
-
-    def skinny_bf16_stats(self):
-        """(skinny-batch launches; workgroups, waves per workgroup, BN, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 5)()
-        self.lib.xsmm_hip_skinny_bf16_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_skinny_split(self, mode):
-        """the K range of a skinny-batch launch (set_skinny_bf16) over several workgroups per column block: 0 off (default), 1 the rule,
-        2 .. 16 that many parts wherever eligible; changes nothing while set_skinny_bf16 is 0; returns the previous mode, -1 for a value
-        it refuses"""
-        return self.lib.xsmm_hip_set_skinny_split(mode)
-
-    def skinny_split_stats(self):
-        """(skinny-batch launches that ran split; parts, workgroups - column blocks * parts - of the most recent one)"""
-        out = (ctypes.c_int64 * 3)()
-        self.lib.xsmm_hip_skinny_split_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_chain_dma256(self, mode):
-        """bf16 layer chains whose calls run on the 256x256 tile (256 dividing m and n, k % 32 == 0) as one launch of that tile's chain
-        kernel (the same bits): 0 off (default), 1 the rule (every call runs on that tile today; gated as measured), 2 every eligible
-        chain, 1000 + G on G row groups; returns the previous mode, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_chain_dma256(mode)
-
-    def chain_dma256_stats(self):
-        """(chain launches on the 256x256 tile; resident row groups G, rounds, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_chain_dma256_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_chain_skinny(self, mode):
-        """bf16 layer chains with 1 .. 31 rows as one launch of the skinny-batch kernel's chain form (the bits of the calls under
-        set_skinny_bf16(BN)): 0 off (default), 1 the rule (VNNI-2 chains whose layers have at most 2 MiB of B, on BN 16: as measured), 16 / 32 / 64 that column-block width
-        wherever eligible, 1000 * G + BN that width on G resident workgroups; returns the previous mode, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_chain_skinny(mode)
-
-    def chain_skinny_stats(self):
-        """(skinny-batch chain launches; resident workgroups G, BN, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_chain_skinny_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_f32_halves(self, mode):
-        """f32 whole-layer calls on the 64x64 + K2 tile as two 64x32 + K2 workgroups per tile (the same bits): 0 off, 1 the rule
-        (default: at least one tile per compute unit), 2 wherever eligible; returns the previous mode, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_f32_halves(mode)
-
-    def f32_halves_stats(self):
-        """(launches carried out as halves; rows, columns of 64x64 tiles of the most recent one; 0)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_f32_halves_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_chain_edge(self, mode):
-        """bf16 layer chains whose m the tile's rows do not divide, as one launch on edge row tiles: 0 off (default), 1 on - the tile
-        set_edge_tiles(20 .. 23) names if it fits, else the smallest that fits; returns the previous value, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_chain_edge(mode)
-
-    def chain_edge_stats(self):
-        """(ragged chain launches; tile rows, tile columns, variant number of the tile with its B image - 20 + t VNNI-2, 24 + t flat,
-        28 + t VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_chain_edge_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_chain_ragged(self, mode):
-        """bf16 layer chains with a ragged n and / or a layer whose k is a multiple of 8 but not of 64 (1000-wide MLPs), as one launch on
-        edge tiles with every layer's last chunk shifted back: 0 off (default), 1 on - the tile set_edge_tiles(20 .. 23) names if it
-        fits, else the smallest that fits; returns the previous value, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_chain_ragged(mode)
-
-    def chain_ragged_stats(self):
-        """(ragged-width chain launches; tile rows ceil(m / BM), tile columns ceil(n / BN), variant number of the tile with its B image -
-        20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_chain_ragged_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_chain_widths(self, mode):
-        """bf16 layer chains whose layers differ in n (1024-4096-1024, funnels), as one launch on m / BM x max_l(n_l / BN) workgroups, each
-        sitting out the layers that have no column tile for it: 0 off (default), 1 on - the tile all calls were dispatched on if it
-        fits, else (not in strict mode) the smallest that fits; returns the previous value, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_chain_widths(mode)
-
-    def chain_widths_stats(self):
-        """(mixed-width chain launches; row blocks m / BM, column tiles of the widest layer, variant number of the tile with its B image -
-        20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_chain_widths_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_chain_width_rounds(self, mode):
-        """bf16 layer chains whose layers differ in n on m / BM x W resident workgroups, W below the widest layer's column tiles: a
-        workgroup walks several column tiles of a wide layer and one (or none) of a narrow one. 0 off (default), 1 on - tile and W by
-        rule, what measured slower gated back to call by call -, 1000 + W force W workgroup columns (never gated); returns the previous
-        value, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_chain_width_rounds(mode)
-
-    def chain_width_rounds_stats(self):
-        """(column-round launches; row blocks m / BM, workgroup columns W, variant number of the tile with its B image - 20 + t VNNI-2,
-        24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_chain_width_rounds_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_chain_widths_ragged(self, mode):
-        """bf16 layer chains whose layers differ in n and that no tile divides entirely - a ragged m, a ragged n in some layer, a k that
-        is a multiple of 8 but not of 64 (784-512-256-128) - as one launch on ceil(m / BM) x max_l ceil(n_l / BN) workgroups: 0 off
-        (default), 1 on - the tile set_edge_tiles(20 .. 23) names if it fits, else the smallest that fits; a chain some tile divides
-        entirely stays set_chain_widths'; returns the previous value, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_chain_widths_ragged(mode)
-
-    def chain_widths_ragged_stats(self):
-        """(ragged mixed-width chain launches; row blocks ceil(m / BM), column tiles of the widest layer max_l ceil(n_l / BN), variant
-        number of the tile with its B image - 20 + t VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_chain_widths_ragged_stats(out)
-        return tuple(int(v) for v in out)
-
-    def set_chain_rounds(self, mode):
-        """bf16 layer chains with more output tiles than compute units, as one launch on G resident row groups that walk R rounds of
-        row blocks: 0 off (default), 1 on - G by rule -, 1000 + G force G row groups (also for a chain that fits in one round); returns
-        the previous value, -1 for a value it refuses"""
-        return self.lib.xsmm_hip_set_chain_rounds(mode)
-
-    def chain_rounds_stats(self):
-        """(multi-round chain launches; row groups G, rounds R = ceil(tiles_m / G), variant number of the tile with its B image - 20 + t
-        VNNI-2, 24 + t flat, 28 + t VNNI-4 - of the most recent one)"""
-        out = (ctypes.c_int64 * 4)()
-        self.lib.xsmm_hip_chain_rounds_stats(out)
-        return tuple(int(v) for v in out)
+    # set_<name>(mode) -> int and <name>_stats() -> tuple of int of the eighteen mode switches: made from _MODE_SWITCHES below the class
 
     def set_fold_transpose(self, enable):
         """transposes that feed a gemm's B operand folded into the gemm (default on); the integer 2 (opt-in): also those that feed its
@@ -640,6 +489,26 @@ class XsmmRuntime:
 
     def version(self):
         return self.lib.xsmm_hip_version().decode()
+
+
+def _mode_switch_methods(name, words, set_doc, stats_doc):
+    def setter(self, mode):
+        return getattr(self.lib, "xsmm_hip_set_" + name)(mode)
+
+    def stats(self):
+        out = (ctypes.c_int64 * words)()
+        getattr(self.lib, "xsmm_hip_" + name + "_stats")(out)
+        return tuple(int(v) for v in out)
+
+    setter.__name__, setter.__qualname__, setter.__doc__ = "set_" + name, "XsmmRuntime.set_" + name, set_doc
+    stats.__name__, stats.__qualname__, stats.__doc__ = name + "_stats", "XsmmRuntime." + name + "_stats", stats_doc
+    return setter, stats
+
+
+for _name, _row in _MODE_SWITCHES.items():
+    _setter, _stats = _mode_switch_methods(_name, *_row)
+    setattr(XsmmRuntime, "set_" + _name, _setter)
+    setattr(XsmmRuntime, _name + "_stats", _stats)
 
 
 _RT = None
