@@ -622,6 +622,35 @@ TPP_XSMM_EXPORT void xsmm_hip_chain_dma256_stats(int64_t out[4]);
  * VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches, xsmm_hip_skinny_bf16_stats among them, do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_chain_skinny(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_chain_skinny_stats(int64_t out[4]);
+/* Skinny-batch f32 layers (opt-in; also TPP_HIP_SKINNY_F32, read as a number; a refused value leaves 0). An f32 call with fewer than 32
+ * rows runs on the generic kernel: one workgroup of four waves per 32x32 output tile, both operands staged through LDS, 32 - m of the
+ * tile's rows idle. With this switch on, the call runs on ceil(n / BN) workgroups of brgemm_f32_skinny<BN, MB> (brgemm_f32_skinny.hip;
+ * maps in brgemm_f32_skinny.h), BN = 16, 32 or 64: one workgroup computes ALL m rows of one block of BN columns on v_mfma_f32_16x16x4_f32
+ * - one accumulator set for m <= 16 (MB = 16), two that share every B register for m = 17 .. 31 (MB = 32). B goes from global memory
+ * straight into the MFMA operand registers, without LDS: per 16-k step lane (g, c) loads rows 4 g .. 4 g + 3 of the step, BN / 16
+ * consecutive floats each (4 .. 16 bytes), and one 16-byte piece of its row of A; every byte of B is loaded by one lane, once. The stream
+ * of 16-k steps over (batch element, k) is dealt over W = min(8, br * ceil(k / 16)) waves of the workgroup in contiguous runs, four steps of
+ * loads in flight per wave; the partial accumulators are added through static LDS in wave order, then beta 1's C, the bias, relu. W
+ * depends on br and k alone, so an element's chain of additions depends neither on m, nor on n, nor on where its column block sits, and
+ * the bits are the same on every run. They are NOT the generic kernel's bits (another order of f32 additions). A row at or beyond m is
+ * read from row m - 1 and never stored; for k % 16 != 0 the lane groups of a batch element's last step whose k values do not exist issue
+ * no load and feed +0.0 on both sides; the last column block is shifted back to end at n and stores only the columns no other block owns.
+ * No cross-workgroup synchronisation, no scratch block, no counters: legal on a captured stream.
+ * A call is taken, at invoke time, when all of this holds: f32, a flat B, no VNNI C, no transposed operand, neither a kernel variant nor
+ * the generic kernel forced, the descriptor's kernel is the generic one, 1 <= m <= 31, n >= BN, n % 4 == 0, k >= 4, k % 4 == 0 per batch
+ * element, batch count >= 1, lda >= k, ldb >= n, ldc >= n, lda, ldb, ldc, stride_a and stride_b multiples of 4 elements and not negative,
+ * A, B, C and the bias row 16-byte aligned; beta 0 or 1, with or without bias and relu. The launcher checks the same again; a call it
+ * refuses runs the launch of mode 0. Everything else runs exactly as with the switch off - bf16 calls, m >= 32, every tile-queue group
+ * (a strict-mode call with m, n <= 64 among them), quad, chain launch and folded call. No other switch takes an f32 call with m < 32, and
+ * this one reads no other mode: there is no precedence question.
+ * mode 0 = off (default); 1 = the rule (gemm_plan.cpp skinny_f32_bn; profiles/skinny_f32_ab.txt); 16, 32, 64 = every eligible call on
+ * that BN (test / measurement switches; n < BN stays where it is). Read per invoke; returns the previous mode, -1 (and changes nothing)
+ * for any other value. The choice depends on the descriptor, the batch count, the pointers' alignment and the CU count only: made in
+ * strict mode too. xsmm_hip_last_refined_kernel reads "brgemm_f32_skinny<MBxBN>" (MB 16 / 32, BN 16 / 32 / 64).
+ * _stats: out[0] such launches since process start; of the most recent one: [1] workgroups, [2] waves per workgroup, [3] BN. The
+ * counters of the other switches do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_skinny_f32(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_skinny_f32_stats(int64_t out[4]);
 /* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
  * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
  * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two

@@ -8,6 +8,7 @@
 #include "brgemm_bf16_dma256_chain.h"
 #include "brgemm_bf16_skinny.h"
 #include "brgemm_bf16_skinny_split.h"
+#include "brgemm_f32_skinny.h"
 #include "brgemm_bf16_skinny_chain.h"
 #include <string.h>
 
@@ -394,6 +395,31 @@ static int skinny_bf16_bn(const GemmDesc &d, int kind, int mode, int64_t br, boo
   int bn = 2 * br * d.k * d.n >= SKINNY_LINE_BYTES ? line : smallest;
   while (bn > smallest && d.n < bn) bn /= 2;
   return d.n >= bn ? bn : 0;
+}
+
+// SKINNY-BATCH f32 LAYERS (xsmm_hip_set_skinny_f32, opt-in; brgemm_f32_skinny.hip, brgemm_f32_skinny.h): the column-block width BN of an
+// f32 call with 1 <= m <= 31, or 0: the call stays on the generic kernel. Modes 16 / 32 / 64 (tests, measurements): that width if n >= BN.
+// Mode 1, THE RULE, from profiles/skinny_f32_ab.txt (one box, 256 CUs, beta 0 + bias + relu, five rounds against the PARENT commit's library in
+// child processes, us per call, the parent's generic kernel -> BN 16 / 32 / 64; a (row class, BN) is taken only where it beat both parent runs
+// of EVERY round). n x K, m 1 / 8 / 16 / 17 / 31:
+//   1024 x 1024 (B 4 MiB)   7.72 / 8.09 / 8.11 / 8.14 / 8.14      -> BN 16 4.82 / 5.33 / 5.62 / 6.89 / 8.03: every m. BN 32 wins less (m <= 16) or loses.
+//   1000 x 1000 (k = 1000)  7.70 / 8.14 / 8.13 / 8.16 / 8.17      -> BN 16 4.88 / 5.48 / 5.44 / 6.84 / 7.54: every m.
+//   4096 x 1024 (16 MiB)    7.93 / 8.28 / 8.24 / 8.17 / 8.17      -> BN 16 5.48 / 6.12 / 6.55 / 7.67 / 9.28: m <= 17; m = 31 lost every round.
+//   1024 x 4096 (16 MiB)    22.14 / 22.70 / 22.70 / 22.72 / 22.73 -> BN 16 12.12 / 13.50 / 16.29 / 18.33 / 22.51: every m (m = 31 by 1.0 %).
+//   4096 x 4096 (64 MiB)    23.46 / 23.38 / 23.49 / 23.53 / 23.59 -> BN 32 17.18 / 17.98 / 19.04 at m <= 16 (a 128-byte line of B per row piece, 3.91 ..
+//                           3.53 TB/s); BN 16 wins less (m 1) or not in every round; m = 17, 31 lost on every BN. BN 64 lost on every row.
+// So: a B (4 br k n bytes) of at least 64 MiB on BN 32 for m <= 16, gated for m >= 17; a B of at most 16 MiB on BN 16, for m >= 18 only with at
+// most 64 column blocks (n <= 1024: the two rows where m = 31 won; at 256 blocks it lost); m = 18 .. 30 were not measured and follow m = 31.
+// GATED because not measured: a B below 4 * 1000 * 1000 bytes, a B between 16 and 64 MiB. Not measured either: other CU counts (the rule
+// does not read them), several ranks, beta 1. BN depends on m, n, k and br; the waves of a workgroup on br and k alone (skf_waves).
+constexpr int64_t SKF_SMALL_BYTES = 4 * 1000 * 1000, SKF_MID_BYTES = 16 << 20, SKF_LINE_BYTES = 64 << 20;
+static int skinny_f32_bn(const GemmDesc &d, int mode, int64_t br) {
+  if (mode == 16 || mode == 32 || mode == 64) return d.n >= mode ? mode : 0;
+  if (mode != 1) return 0;
+  const int64_t bytes = 4 * br * d.k * d.n;
+  if (bytes >= SKF_LINE_BYTES) return d.m <= 16 && d.n >= 32 ? 32 : 0;
+  if (bytes < SKF_SMALL_BYTES || bytes > SKF_MID_BYTES) return 0;
+  return d.n >= 16 && (d.m <= 17 || skf_blocks((int)d.n, 16) <= 64) ? 16 : 0;
 }
 
 // K SPLIT ACROSS WORKGROUPS OF A SKINNY-BATCH LAUNCH (xsmm_hip_set_skinny_split, opt-in; brgemm_bf16_skinny_split.hip,
@@ -1352,6 +1378,23 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
       // the K range of the launch over several workgroups per column block, if asked for (xsmm_hip_set_skinny_split): read here only
       const int parts = env.skinny_split != 0 ? skinny_split_parts(d, bn, env.skinny_split, br, cus) : 1;
       return launch(GL_BF16_SKINNY, bn, skinny_names[parts > 1][kind / 2][skn_mb((int)d.m) == 32][bn == 16 ? 0 : bn == 32 ? 1 : 2], parts, kind);
+    }
+  }
+  // Skinny-batch f32 layers, if asked for (xsmm_hip_set_skinny_f32, a switch of its own; brgemm_f32_skinny.hip, brgemm_f32_skinny.h): an f32
+  // call with 1 <= m <= 31 and a flat B that is planned - not forced - on the generic kernel, on ceil(n / BN) workgroups that stream B
+  // straight into the operand registers of v_mfma_f32_16x16x4_f32. No other refinement takes a call with m < 32, so its place in this
+  // function is free; it reads no other mode and no other mode reads it. Decided here only - what is queued, grouped, chained or folded
+  // never sees it -, from the descriptor, the batch count, the pointers' alignment and the CU count: allowed in strict mode. The alignment
+  // rules are the launcher's (launch_f32_skinny: A, B, C and the bias row 16-byte aligned, every leading dimension and stride a multiple of 4
+  // elements); refused there, the call runs the launch it has with the mode off (launch_gemm).
+  if (env.skinny_f32 != 0 && d.dtype == DT_F32 && !d.vnni_b && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.variant == V_GENERIC &&
+      skf_shape_ok(d.m, d.n, d.k, br, 16) && d.lda >= d.k && d.ldb >= d.n && d.ldc >= d.n && !((d.lda | d.ldb | d.ldc | d.stride_a | d.stride_b) & 3) &&
+      d.stride_a >= 0 && d.stride_b >= 0 && al.ab16 && al.c16 && (!d.bias || al.d16)) {
+    const int bn = skinny_f32_bn(d, env.skinny_f32, br);
+    if (bn > 0) {
+      static const char *const names[2][3] = {{"brgemm_f32_skinny<16x16>", "brgemm_f32_skinny<16x32>", "brgemm_f32_skinny<16x64>"},
+                                              {"brgemm_f32_skinny<32x16>", "brgemm_f32_skinny<32x32>", "brgemm_f32_skinny<32x64>"}};
+      return launch(GL_F32_SKINNY, bn, names[skf_mb((int)d.m) == 32][bn == 16 ? 0 : bn == 32 ? 1 : 2]);
     }
   }
   // Edge tiles on the 256x256 tile, if asked for (xsmm_hip_set_dma256_edge, a switch of its own; brgemm_bf16_dma256_edge.hip,
