@@ -651,6 +651,24 @@ TPP_XSMM_EXPORT void xsmm_hip_chain_skinny_stats(int64_t out[4]);
  * counters of the other switches do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_skinny_f32(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_skinny_f32_stats(int64_t out[4]);
+/* K split across workgroups of a skinny-batch f32 launch (opt-in; also TPP_HIP_SKINNY_F32_SPLIT, read as a number). A refinement of
+ * xsmm_hip_set_skinny_f32 with a switch of its own (xsmm_hip_set_skinny_split is the bf16 kernel's and reads bf16 bytes): a call that
+ * switch puts on column blocks of BN runs as brgemm_f32_skinny_split<BN, MB> (brgemm_f32_skinny_split.hip; maps in
+ * brgemm_f32_skinny_split.h): the S = br * ceil(k / 16) steps of the call go to P_eff = min(P, S) workgroups per column block in
+ * contiguous runs, each workgroup runs the unsplit kernel's K loop and LDS combine on its run, parks its partial accumulators in the
+ * stream's scratch block and arrives at the block's counter; the last arriver adds all P_eff partials in part order and runs the unsplit
+ * epilogue. No workgroup waits for another. The bits depend on br, k and P_eff alone - not on m, n, the block's position, the arrival
+ * order or the run; they are the unsplit kernel's wherever every partial sum is exact.
+ * mode 0 = off (default); 1 = the rule (gemm_plan.cpp skinny_f32_split_parts, fitted to profiles/skinny_f32_split_ab.txt); 2 .. 16 = that
+ * many parts wherever eligible (test / measurement switches). Read per invoke, and only for a call already on the skinny f32 kernel: with
+ * xsmm_hip_set_skinny_f32 at 0 it changes nothing. Returns the previous mode, -1 (and changes nothing) for any other value.
+ * xsmm_hip_last_refined_kernel reads "brgemm_f32_skinny_split<MBxBN>". A split its launcher refuses - fewer than two steps, more than
+ * 4096 column blocks, more partial floats than the scratch block holds, no scratch block (a 17th stream, a stream being captured) - runs
+ * the unsplit skinny launch of the same BN.
+ * _stats: out[0] split launches since process start; of the most recent one: [1] parts P_eff, [2] workgroups (column blocks * P_eff).
+ * Such a launch also counts in xsmm_hip_skinny_f32_stats, with [1] = column blocks * P_eff and [2] = the waves of a workgroup. */
+TPP_XSMM_EXPORT int xsmm_hip_set_skinny_f32_split(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_skinny_f32_split_stats(int64_t out[3]);
 /* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
  * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
  * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two

@@ -32,6 +32,7 @@
 #include "brgemm_bf16_dma256_edge.h"
 #include "brgemm_bf16_skinny_split.h"
 #include "brgemm_f32_skinny.h"
+#include "brgemm_f32_skinny_split.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -699,6 +700,7 @@ hipError_t launch_bf16_dma256_edge(int b_kind, const GemmArgs &a, hipStream_t s)
 hipError_t launch_bf16_skinny(int b_kind, int bn, const GemmArgs &a, hipStream_t s); // brgemm_bf16_skinny.hip: 1 <= m <= 31 on column blocks of bn; hipErrorInvalidValue: not launched
 hipError_t launch_bf16_skinny_split(int b_kind, int bn, int parts, const GemmArgs &a, hipStream_t s); // brgemm_bf16_skinny_split.hip: the same over parts workgroups per column block; hipErrorInvalidValue: not launched
 hipError_t launch_f32_skinny(int bn, const GemmArgs &a, hipStream_t s); // brgemm_f32_skinny.hip: 1 <= m <= 31 of a flat f32 B on column blocks of bn; hipErrorInvalidValue: not launched
+hipError_t launch_f32_skinny_split(int bn, int parts, const GemmArgs &a, hipStream_t s); // brgemm_f32_skinny_split.hip: the same over parts workgroups per column block; hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         // brgemm_f32_lw.hip (tile 4: 128x64, forced variant 10 only - it measures within 2 % of brgemm_f32_fast<128x64>)
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
@@ -804,7 +806,7 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
     if (p.edge) return p.tile == 2 ? launch_bf16_dma256_edge(p.b_kind, a, s) : hipErrorInvalidValue;
     return p.b_kind != 0 ? (p.tile == 2 ? launch_bf16_dma256_image(p.b_kind, a, s) : hipErrorInvalidValue) : launch_gemm_bf16_fast(p.tile, a, s);
   case GL_BF16_SKINNY: return p.split > 1 ? launch_bf16_skinny_split(p.b_kind, p.tile, p.split, a, s) : launch_bf16_skinny(p.b_kind, p.tile, a, s);
-  case GL_F32_SKINNY: return launch_f32_skinny(p.tile, a, s);
+  case GL_F32_SKINNY: return p.split > 1 ? launch_f32_skinny_split(p.tile, p.split, a, s) : launch_f32_skinny(p.tile, a, s);
   case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split, small_split_ran);
   case GL_BF16_GROUPED64: return launch_bf16_grouped64(a, wi, n_items, s);
   case GL_BF16_LW:
@@ -856,9 +858,19 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     p = plan_gemm_call(d, br, al, env);
   }
   if (p.launcher == GL_F32_SKINNY) { // a skinny-batch f32 layer (mode_switches.h MS_SKINNY_F32; brgemm_f32_skinny.h)
-    const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    if (e == hipErrorInvalidValue && p.split > 1) { // the split refused by its launcher (mode_switches.h MS_SKINNY_F32_SPLIT): the unsplit skinny launch of the same BN
+      (void)hipGetLastError();
+      env.skinny_f32_split = 0;
+      p = plan_gemm_call(d, br, al, env);
+      e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    }
     if (e != hipErrorInvalidValue) {
-      if (e == hipSuccess) count_mode_launch(MS_SKINNY_F32, {skf_blocks(a.n, p.tile), skf_waves((long long)a.br * skf_steps(a.k)), p.tile});
+      if (e == hipSuccess) {
+        const long long s_all = (long long)a.br * skf_steps(a.k);
+        if (p.split > 1) count_mode_launch(MS_SKINNY_F32_SPLIT, {p.split, skfs_grid(skf_blocks(a.n, p.tile), p.split)});
+        count_mode_launch(MS_SKINNY_F32, {skfs_grid(skf_blocks(a.n, p.tile), p.split), p.split > 1 ? skfs_block_waves(p.split, (int)s_all) : skf_waves(s_all), p.tile});
+      }
       return g_last_refined.store(p.text, std::memory_order_relaxed), e;
     }
     (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off

@@ -9,6 +9,7 @@
 #include "brgemm_bf16_skinny.h"
 #include "brgemm_bf16_skinny_split.h"
 #include "brgemm_f32_skinny.h"
+#include "brgemm_f32_skinny_split.h"
 #include "brgemm_bf16_skinny_chain.h"
 #include <string.h>
 
@@ -420,6 +421,42 @@ static int skinny_f32_bn(const GemmDesc &d, int mode, int64_t br) {
   if (bytes >= SKF_LINE_BYTES) return d.m <= 16 && d.n >= 32 ? 32 : 0;
   if (bytes < SKF_SMALL_BYTES || bytes > SKF_MID_BYTES) return 0;
   return d.n >= 16 && (d.m <= 17 || skf_blocks((int)d.n, 16) <= 64) ? 16 : 0;
+}
+
+// K SPLIT ACROSS WORKGROUPS OF A SKINNY-BATCH f32 LAUNCH (xsmm_hip_set_skinny_f32_split, opt-in; brgemm_f32_skinny_split.hip,
+// brgemm_f32_skinny_split.h): the parts P_eff of a call already on the skinny f32 kernel with column blocks of bn, or 1: the plain skinny
+// launch. Modes 2 .. 16 (tests, measurements): P = the mode. Reads the descriptor, the batch count and the CU count only.
+// Mode 1, THE RULE, from profiles/skinny_f32_split_ab.txt (one box, 256 CUs, beta 0 + bias + relu, five alternating rounds of child processes,
+// us per call, the UNSPLIT skinny launch of the same BN in the same process -> P = 2 / 4 / 8 / 16; a P is taken only where it was faster in
+// EVERY round). What decides is the bytes of B per workgroup of the unsplit launch, 4 BN br k, as in the bf16 rule above:
+//   256 KiB and more, EVERY m (1, 8, 16, 17, 31) gains in every round where the parts fit the compute units in one round: 1024 x 4096 (n x K)
+//     BN 16 (64 blocks) 11.92 / 13.51 / 16.36 / 18.52 / 22.71 -> P 4 8.31 / 8.93 / 9.23 / 10.71 / 12.17 (P 2 9.31 .. 15.24, P 8 - two rounds of
+//     workgroups - 9.85 .. 13.19); BN 32 (32 blocks, 512 KiB) 15.75 .. 26.24 -> P 4 8.90 / 9.58 / 9.87 / 12.59 / 13.42 (P 8 level); BN 64 (16
+//     blocks, 1 MiB) 24.12 .. 43.72 -> P 4 11.21 .. 18.58 (P 8 10.18 .. 15.52). 4096 x 4096 BN 32 (128 blocks, 512 KiB) 17.13 / 17.93 / 18.99 /
+//     26.14 / 27.68 -> P 2 14.48 / 15.14 / 15.49 / 18.33 / 19.48 (P 4, two rounds, 15.18 .. 21.57). 4096 x 4096 BN 16 (256 blocks: no P fits)
+//     loses on every P.
+//   128 KiB (BN 32 on K = 1024 and 1000): P 4 gains 2 .. 6 % at m <= 16 and 17 .. 20 % at m >= 17 on 32 blocks, P 2 loses at m = 8; on 128
+//     blocks (4096 x 1024) P 2 gains 5 % at m >= 17 only. Mixed: not taken.
+//   64 KiB (BN 16 on K = 1024 and 1000): every P loses in every round, by 12 .. 38 % at P 2, but 1024 x 1024 m = 31 (P 4 -3.5 %). Not taken.
+//   P 16 loses or gains least on every row.
+// So: where a workgroup of the unsplit launch streams at least 256 KiB of B, P = 4, else 2, if the parts fit the compute units in one round
+// (blocks * P <= cus); else the plain launch. On every measured (row, BN) this takes, that P was faster in every round, and it takes nothing
+// else. With mode 1 of the skinny f32 switch (which picks BN) it splits 1024 x 4096 (BN 16 P 4: -30 .. -46 %) and 4096 x 4096 at m <= 16 (BN
+// 32 P 2: -15 .. -18 %). For whoever reopens the BN rule's gates, under forced modes: 4096 x 4096 m 17 / 31 on BN 32 P 2 18.33 / 19.48 against
+// the generic kernel's 23.45 / 23.54; 4096 x 1024 m 31 on BN 32 P 2 10.17 against 8.16 (still a loss). Not measured: other CU counts (the
+// rule reads them only through blocks * P <= cus), several ranks, beta 1, K beyond 4096, a B between 16 and 64 MiB.
+constexpr int64_t SKF_SPLIT_BYTES = 256 << 10; // a workgroup of the unsplit launch streams at least this many bytes of B
+static int skinny_f32_split_parts(const GemmDesc &d, int bn, int mode, int64_t br, int64_t cus) {
+  const int64_t s_all = br * skf_steps((int)d.k), blocks = skf_blocks((int)d.n, bn);
+  int P = mode;
+  if (mode == 1) {
+    P = 1;
+    for (int c : {4, 2})
+      if (P == 1 && blocks * c <= cus && 4 * bn * br * d.k >= SKF_SPLIT_BYTES) P = c;
+  }
+  if (P < 2 || P > SKFS_PMAX) return 1;
+  const int p_eff = skfs_parts(P, s_all);
+  return p_eff >= 2 ? p_eff : 1;
 }
 
 // K SPLIT ACROSS WORKGROUPS OF A SKINNY-BATCH LAUNCH (xsmm_hip_set_skinny_split, opt-in; brgemm_bf16_skinny_split.hip,
@@ -1394,7 +1431,11 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
     if (bn > 0) {
       static const char *const names[2][3] = {{"brgemm_f32_skinny<16x16>", "brgemm_f32_skinny<16x32>", "brgemm_f32_skinny<16x64>"},
                                               {"brgemm_f32_skinny<32x16>", "brgemm_f32_skinny<32x32>", "brgemm_f32_skinny<32x64>"}};
-      return launch(GL_F32_SKINNY, bn, names[skf_mb((int)d.m) == 32][bn == 16 ? 0 : bn == 32 ? 1 : 2]);
+      static const char *const split_names[2][3] = {{"brgemm_f32_skinny_split<16x16>", "brgemm_f32_skinny_split<16x32>", "brgemm_f32_skinny_split<16x64>"},
+                                                    {"brgemm_f32_skinny_split<32x16>", "brgemm_f32_skinny_split<32x32>", "brgemm_f32_skinny_split<32x64>"}};
+      // the K range of the launch over several workgroups per column block, if asked for (xsmm_hip_set_skinny_f32_split): read here only
+      const int parts = env.skinny_f32_split != 0 ? skinny_f32_split_parts(d, bn, env.skinny_f32_split, br, cus) : 1;
+      return launch(GL_F32_SKINNY, bn, (parts > 1 ? split_names : names)[skf_mb((int)d.m) == 32][bn == 16 ? 0 : bn == 32 ? 1 : 2], parts);
     }
   }
   // Edge tiles on the 256x256 tile, if asked for (xsmm_hip_set_dma256_edge, a switch of its own; brgemm_bf16_dma256_edge.hip,

@@ -50,9 +50,10 @@ enum GemmVariant : int {
 // the rule, 2 = wherever eligible) and xsmm_hip_set_edge_k8_bf16 (the values of edge_k_bf16, for k % 16 == 8) and xsmm_hip_set_dma256_images
 // (0 = off, 1 = the rule, 2 = wherever eligible) and xsmm_hip_set_dma256_edge (the same values) and xsmm_hip_set_skinny_bf16 (0 = off, 1 = the
 // rule, 16 / 32 / 64 = that column-block width wherever eligible) and xsmm_hip_set_skinny_split (0 = off, 1 = the rule, 2 .. 16 = that many parts
-// wherever eligible) and xsmm_hip_set_skinny_f32 (0 = off, 1 = the rule, 16 / 32 / 64 = that column-block width wherever eligible);
+// wherever eligible) and xsmm_hip_set_skinny_f32 (0 = off, 1 = the rule, 16 / 32 / 64 = that column-block width wherever eligible) and
+// xsmm_hip_set_skinny_f32_split (0 = off, 1 = the rule, 2 .. 16 = that many parts wherever eligible);
 // mode_switches.h gemm_plan_env_of fills it per call, and the accepted values of each switch stand in its table
-struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; int dma256_edge = 0; int skinny_bf16 = 0; int skinny_split = 0; int skinny_f32 = 0; };
+struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; int dma256_edge = 0; int skinny_bf16 = 0; int skinny_split = 0; int skinny_f32 = 0; int skinny_f32_split = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
 struct GemmAlign { bool ab16, c16, c8, d8, d16; };
@@ -74,7 +75,7 @@ enum GemmLauncher : int {
   GL_BF16_LW_QUADS,   // launch_bf16_lw_quads(b_kind)
   GL_GENERIC,         // brgemm_grouped<T, VNNI, VEC, VF, FORM>: generic
   GL_BF16_SKINNY,     // launch_bf16_skinny(b_kind, tile): tile = the column-block width BN 16 / 32 / 64 (xsmm_hip_set_skinny_bf16; brgemm_bf16_skinny.hip); split > 1 (xsmm_hip_set_skinny_split): launch_bf16_skinny_split(b_kind, tile, split) first
-  GL_F32_SKINNY,      // launch_f32_skinny(tile): tile = the column-block width BN 16 / 32 / 64 (xsmm_hip_set_skinny_f32; brgemm_f32_skinny.hip)
+  GL_F32_SKINNY,      // launch_f32_skinny(tile): tile = the column-block width BN 16 / 32 / 64 (xsmm_hip_set_skinny_f32; brgemm_f32_skinny.hip); split > 1 (xsmm_hip_set_skinny_f32_split): launch_f32_skinny_split(tile, split) first
 };
 // the instances of the generic kernel brgemm_grouped<T, VNNI, VEC, VF>: <float, false, false / true>, <unsigned short, true, false / true>,
 // <unsigned short, true, true, 4>, <unsigned short, false, false>; and the f32 instances whose FORM argument says that an operand is
@@ -130,6 +131,9 @@ bool plan_gemm(GemmDesc &d, int forced_variant, const GemmPlanEnv &env);
 // width, or mode 1's measured rule. It reads no other switch and no other switch reads it; no other refinement takes m < 32; it decides from
 // the descriptor, the batch count, the alignment and the CU count, so strict mode takes it. With skinny_f32 at 0 the block is never entered.
 // Refused by the launcher, the call runs the launch it has with the mode off (tests/test_skinny_f32_cpu.py).
+// The K split across workgroups of such a launch, xsmm_hip_set_skinny_f32_split {skinny_f32_split, skinny_f32}, is read INSIDE that block
+// only - for a call already put on GL_F32_SKINNY - and sets split and text ("brgemm_f32_skinny_split<MBxBN>"), nothing else: with
+// skinny_f32 at 0 it is never read, skinny_f32_bn does not read it, and no other refinement does (tests/test_skinny_f32_split_cpu.py).
 GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br, const GemmAlign &al, const GemmPlanEnv &env);
 // n_items invokes of one descriptor in one launch (launch_gemm_grouped; vec_ok / out_ok / pair_ok / br_hint as there)
 GemmLaunch plan_gemm_group(const GemmDesc &d, int n_items, bool vec_ok, bool out_ok, bool pair_ok, int64_t br_hint, const GemmPlanEnv &env);

@@ -576,6 +576,7 @@ MODE_SWITCH_ABI(chain_widths_ragged, MS_CHAIN_WIDTHS_RAGGED)
 MODE_SWITCH_ABI(chain_dma256, MS_CHAIN_DMA256)
 MODE_SWITCH_ABI(chain_skinny, MS_CHAIN_SKINNY)
 MODE_SWITCH_ABI(skinny_f32, MS_SKINNY_F32)
+MODE_SWITCH_ABI(skinny_f32_split, MS_SKINNY_F32_SPLIT)
 #undef MODE_SWITCH_ABI
 // the VNNI blocking factor of bf16 B operands dispatched from now on (2 or 4); returns the previous one, -1 for an invalid factor
 extern "C" int xsmm_hip_set_vnni_factor(int v) {

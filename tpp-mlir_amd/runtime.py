@@ -176,6 +176,11 @@ _MODE_SWITCHES = {
         workgroup per block of BN columns: 0 off (default), 1 the rule, 16 / 32 / 64 that BN wherever eligible; returns the previous mode,
         -1 for a value it refuses""",
         """(skinny-batch f32 launches; workgroups, waves per workgroup, BN of the most recent one)"""),
+    "skinny_f32_split": (3,
+        """the K range of a skinny-batch f32 launch (set_skinny_f32) over several workgroups per column block: 0 off (default), 1 the
+        rule, 2 .. 16 that many parts wherever eligible; changes nothing while set_skinny_f32 is 0; returns the previous mode, -1 for a
+        value it refuses""",
+        """(skinny-batch f32 launches that ran split; parts, workgroups - column blocks * parts - of the most recent one)"""),
     "chain_dma256": (4,
         """bf16 layer chains whose calls run on the 256x256 tile (256 dividing m and n, k % 32 == 0) as one launch of that tile's chain
         kernel (the same bits): 0 off (default), 1 the rule (every call runs on that tile today; gated as measured), 2 every eligible
