@@ -669,6 +669,29 @@ TPP_XSMM_EXPORT void xsmm_hip_skinny_f32_stats(int64_t out[4]);
  * Such a launch also counts in xsmm_hip_skinny_f32_stats, with [1] = column blocks * P_eff and [2] = the waves of a workgroup. */
 TPP_XSMM_EXPORT int xsmm_hip_set_skinny_f32_split(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_skinny_f32_split_stats(int64_t out[3]);
+/* Skinny-batch f32 layer chains (opt-in; also TPP_HIP_CHAIN_SKINNY_F32, read as a number; a refused value leaves 0). The f32 chain of the
+ * loader-wave tiles asks for 64 rows, so an f32 chain with 1 <= m <= 31 runs call by call. With this switch on,
+ * xsmm_hip_fused_brgemm_chain_invoke runs such a chain as ONE launch of brgemm_f32_skinny_chain<BN, MB> (brgemm_f32_skinny_chain.hip; schedule
+ * in brgemm_f32_skinny_chain.h): G resident workgroups run every layer, workgroup w taking the column blocks w, w + G, .. of a layer's n_l
+ * columns; a block is the body of the unsplit skinny f32 kernel (xsmm_hip_set_skinny_f32 above) - it is built from the same text -, so every
+ * layer has the bits of the same call under xsmm_hip_set_skinny_f32(BN) with xsmm_hip_set_skinny_f32_split at 0 - NOT the generic kernel's
+ * bits: strict mode (xsmm_hip_set_strict) keeps such a chain call by call. Between two layers stands one counter: a workgroup adds 1
+ * behind the write-through stores of its last block of the layer (at once if it owns none), a consumer waits for epoch * G, bounded by a
+ * timeout that sets the launch's error word (probation, journal and the call-by-call re-run are those of every chain launch); the
+ * handed-off activations are read past the compute unit's L1.
+ * A chain is taken when every call is exact f32 with a flat B, beta 0, no VNNI C, no transposed operand and no forced kernel, all calls
+ * have the same 1 <= m <= 31, 2 .. 8 layers, per layer n >= BN, n % 4 == 0, k >= 4, k % 4 == 0, batch count >= 1, lda >= k, ldb >= n, ldc >= n,
+ * every leading dimension and stride a multiple of 4 elements and not negative, lda and ldc below 2^24, besides the chain contract of
+ * xsmm_hip_fused_brgemm_chain_invoke (16-byte aligned operands and bias, asynchronous mode, no captured stream). Widths may differ.
+ * mode 0 = off (default); 1 = the rule (gemm_plan.cpp plan_chain_skinny_f32, fitted to profiles/chain_skinny_f32_ab.txt: whatever did not
+ * beat the calls under both single-call f32 skinny switches in every round, or was not measured, stays call by call); 16, 32, 64 = every
+ * eligible chain on that BN, G = min(max_l ceil(n_l / BN), compute units); 1000 * G + BN (1 <= G <= 512) = that BN on G resident
+ * workgroups, refused if G exceeds the stream's compute units (test / measurement switches, never gated). Read per invoke; returns the
+ * previous mode, -1 (and changes nothing) for any other value. It reads no other switch and no other switch reads it.
+ * _stats: out[0] such launches since process start; of the most recent one: [1] resident workgroups G, [2] BN, [3] waves per workgroup
+ * (the deepest layer's). The counters of the other switches do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_skinny_f32(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_skinny_f32_stats(int64_t out[4]);
 /* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
  * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
  * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two

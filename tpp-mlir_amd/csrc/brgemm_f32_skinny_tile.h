@@ -1,7 +1,10 @@
 // brgemm_f32_skinny_tile.h - the skinny-batch f32 tile (1 .. 31 rows on a block of BN = 16 / 32 / 64 columns), written ONCE for the two
-// kernels built from it: brgemm_f32_skinny.hip (a call) and brgemm_f32_skinny_split.hip (a call with its K range split across
-// workgroups). The split's contract is "inside a part everything is the unsplit kernel's": it runs this text, not a copy of it. Device
-// code only; the maps it walks are brgemm_f32_skinny.h (host-only, tests/test_skinny_f32_cpu.py).
+// kernels built from it: brgemm_f32_skinny.hip (a call), brgemm_f32_skinny_split.hip (a call with its K range split across workgroups)
+// and brgemm_f32_skinny_chain.hip (a chain of such layers in one launch). The split's and the chain's contract is "inside a part / a block
+// everything is the unsplit kernel's": they run this text, not a copy of it. The chain's needs - handed-off A through sc1 buffer loads, the
+// seam wait between the B and the A loads of the first ring slots, sc1 buffer stores - are DEFAULTED template parameters: with the
+// defaults the text is what it was, and the twelve kernels of the other two files compile to the parent's instructions
+// (profiles/chain_skinny_f32_isa.txt). Device code only; the maps it walks are brgemm_f32_skinny.h (host-only, tests/test_skinny_f32_cpu.py).
 //   skf_k_loop    a wave's run of 16-k steps into its accumulators: B from global memory straight into the MFMA operands
 //   skf_park, skf_gather  the waves' partial accumulators through LDS into wave 0, in wave order
 //   skf_epilogue  ownership skip, beta 1's C, bias, relu, the store
@@ -13,7 +16,13 @@ namespace tpp {
 
 typedef __attribute__((address_space(1))) const char skf_gchar;
 typedef float skf_f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int skf_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int SKF_DEPTH = 4; // steps of loads in flight per wave
+constexpr int SKF_SC1 = 16;  // aux of a raw buffer access: sc1 (write-through store / a load past the CU's L1)
+// what a HANDED K loop calls between the B loads and the A loads of its first ring slots: every wave, once, also one without a step
+struct SkfNoWait {
+  __device__ __forceinline__ void operator()() const {}
+};
 
 // a lane's piece of C floats (4 / 8 / 16 bytes, naturally aligned) of a row of B, of the bias or of C
 template <int C> __device__ __forceinline__ void skf_load_piece(float (&d)[C], skf_gchar *p) {
@@ -45,8 +54,12 @@ template <int BN, int MB> struct SkfAcc {
 
 // Steps t0 .. t0 + cnt - 1 of the stream of 16-k steps (numbered batch element by batch element) of the column block at n0, into acc
 // (zeroed here); cnt may be 0. A ring of SKF_DEPTH steps: B then A of a step, the ragged-k mask tested once per step.
-template <int BN, int MB>
-__device__ __forceinline__ void skf_k_loop(const GemmArgs &p, const int lane, const int n0, const int t0, const int cnt, SkfAcc<BN, MB> &acc) {
+// HANDED (the chain, layers > 0): A is a predecessor's output of this launch - every load of it is an sc1 buffer load (byte offsets below
+// 2^31: skfc_ld_ok) -, and the first ring slots load all their B, call wait() and only then load their A: weights do not depend on
+// activations. The same values reach the same MFMAs in the same order either way.
+template <int BN, int MB, bool HANDED = false, class Wait = SkfNoWait>
+__device__ __forceinline__ void skf_k_loop(const GemmArgs &p, const int lane, const int n0, const int t0, const int cnt, SkfAcc<BN, MB> &acc,
+                                           const Wait wait = Wait{}) {
   constexpr int C = skf_cols(BN), SETS = MB / 16;
   const int spb = skf_steps(p.k);
   const int klast = skf_step_klim(p.k, spb - 1); // k values of the last step of a batch element: 4 .. 16
@@ -60,6 +73,12 @@ __device__ __forceinline__ void skf_k_loop(const GemmArgs &p, const int lane, co
     const int row = skf_a_row(s, lane) < p.m ? skf_a_row(s, lane) : p.m - 1; // a row at or beyond m: read from the last row, never stored
     Al[s] = (skf_gchar *)p.A + 4 * ((int64_t)row * p.lda + skf_a_k(lane, 0));
   }
+  // HANDED: the lane's byte offset into the buffer of A, and the step's (inside the row: below 4 lda)
+  auto a_off = [&] __device__(const int s) {
+    const int row = skf_a_row(s, lane) < p.m ? skf_a_row(s, lane) : p.m - 1;
+    return (unsigned)(4 * (row * (int)p.lda + skf_a_k(lane, 0)));
+  };
+  auto a_step = [&] __device__(const int b, const int ks) { return (unsigned)(4 * (b * (int)p.stride_a + ks * SKF_KSTEP)); };
 
   // the load cursor: batch element, step within it
   int cb = t0 / spb, cks = t0 - cb * spb;
@@ -77,8 +96,14 @@ __device__ __forceinline__ void skf_k_loop(const GemmArgs &p, const int lane, co
 #pragma unroll
       for (int r = 0; r < 4; ++r) skf_load_piece<C>(f.b[r], pb + r * row_pitch);
 #pragma unroll
-      for (int s = 0; s < SETS; ++s)
-        f.a[s] = *(__attribute__((address_space(1))) const f32x4 *)(Al[s] + 4 * ((int64_t)cb * p.stride_a + cks * SKF_KSTEP));
+      for (int s = 0; s < SETS; ++s) {
+        if constexpr (HANDED) {
+          const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void *)p.A, 0, 0x7fffffff, 0x00020000);
+          f.a[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, a_off(s), a_step(cb, cks), SKF_SC1));
+        } else {
+          f.a[s] = *(__attribute__((address_space(1))) const f32x4 *)(Al[s] + 4 * ((int64_t)cb * p.stride_a + cks * SKF_KSTEP));
+        }
+      }
     }
     if (++cks == spb) cks = 0, ++cb;
   };
@@ -100,9 +125,38 @@ __device__ __forceinline__ void skf_k_loop(const GemmArgs &p, const int lane, co
 
   // the first slots filled, a steady state that computes and refills every slot, a drain that refills only while steps are left
   SkfStep<BN, MB> ring[SKF_DEPTH];
+  if constexpr (HANDED) { // the first slots in two halves around the wait: the step's B or zeros, then its A or zeros
+    int ab = cb, aks = cks;
 #pragma unroll
-  for (int d = 0; d < SKF_DEPTH; ++d)
-    if (d < cnt) load(ring[d]);
+    for (int d = 0; d < SKF_DEPTH; ++d)
+      if (d < cnt) {
+        const bool masked = cks == spb - 1 && tail_masked;
+        skf_gchar *pb = Bl + 4 * (int64_t)cb * p.stride_b + (int64_t)cks * step_pitch;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (masked) {
+#pragma unroll
+            for (int j = 0; j < C; ++j) ring[d].b[r][j] = 0.f;
+          } else skf_load_piece<C>(ring[d].b[r], pb + r * row_pitch);
+        }
+        if (++cks == spb) cks = 0, ++cb;
+      }
+    wait();
+    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void *)p.A, 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+    for (int d = 0; d < SKF_DEPTH; ++d)
+      if (d < cnt) {
+        const bool masked = aks == spb - 1 && tail_masked;
+#pragma unroll
+        for (int s = 0; s < SETS; ++s)
+          ring[d].a[s] = masked ? f32x4{0.f, 0.f, 0.f, 0.f} : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, a_off(s), a_step(ab, aks), SKF_SC1));
+        if (++aks == spb) aks = 0, ++ab;
+      }
+  } else {
+#pragma unroll
+    for (int d = 0; d < SKF_DEPTH; ++d)
+      if (d < cnt) load(ring[d]);
+  }
   int i = 0;
   for (; i + 2 * SKF_DEPTH <= cnt; i += SKF_DEPTH) {
 #pragma unroll
@@ -149,8 +203,9 @@ template <int BN, int MB> __device__ __forceinline__ void skf_gather(const float
 }
 
 // Wave 0, with the sum of all steps in acc: a lane holds columns n0 + C l15 .. + C - 1 of rows 16 s + 4 g + r - one piece of 4 C bytes per
-// row. The ownership skip of a shifted last block, beta 1's C, the bias, relu.
-template <int BN, int MB>
+// row. The ownership skip of a shifted last block, beta 1's C, the bias, relu. SC1 (the chain; beta 0 only, its launcher's refusal): every
+// piece leaves through a write-through raw buffer store (byte offsets below 2^31: skfc_ld_ok).
+template <int BN, int MB, bool SC1 = false>
 __device__ __forceinline__ void skf_epilogue(const GemmArgs &p, const int lane, const int blk, const int n0, const SkfAcc<BN, MB> &acc) {
   constexpr int C = skf_cols(BN), SETS = MB / 16;
   const int col = skf_out_col(BN, lane, 0);
@@ -169,16 +224,26 @@ __device__ __forceinline__ void skf_epilogue(const GemmArgs &p, const int lane, 
       if (row >= p.m) continue;
       float *const dst = c0 + (int64_t)row * p.ldc;
       float h[C];
-      if (beta1) skf_load_piece<C>(h, (skf_gchar *)dst);
+      if constexpr (!SC1)
+        if (beta1) skf_load_piece<C>(h, (skf_gchar *)dst);
 #pragma unroll
       for (int j = 0; j < C; ++j) {
         float v = acc.v[s][j][r];
-        if (beta1) v += h[j];
+        if constexpr (!SC1)
+          if (beta1) v += h[j];
         if (p.ep & EP_BIAS) v += bias[j];
         if (relu) v = v > 0.f ? v : 0.f;
         h[j] = v;
       }
-      skf_store_piece<C>(dst, h);
+      if constexpr (SC1) {
+        const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, 0x7fffffff, 0x00020000);
+        const unsigned off = (unsigned)(4 * (row * (int)p.ldc + n0 + col));
+        if constexpr (C == 1) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, h[0]), rsC, off, 0, SKF_SC1);
+        else if constexpr (C == 2) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(skf_u32x2, skf_f32x2{h[0], h[1]}), rsC, off, 0, SKF_SC1);
+        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{h[0], h[1], h[2], h[3]}), rsC, off, 0, SKF_SC1);
+      } else {
+        skf_store_piece<C>(dst, h);
+      }
     }
 }
 

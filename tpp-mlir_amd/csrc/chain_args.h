@@ -79,6 +79,12 @@ hipError_t launch_bf16_dma256_chain(int b_kind, const ChainArgs &a, hipStream_t 
 // guarantee; ONE counter per seam, cnt[l] reaches a.target = epoch * G. Refuses with hipErrorInvalidValue, launching nothing, whatever
 // the kernel does not assume (the list stands at the launcher)
 hipError_t launch_bf16_skinny_chain(int b_kind, int bn, const ChainArgs &a, hipStream_t s);
+// a chain of SKINNY-BATCH f32 layers (brgemm_f32_skinny_chain.hip, xsmm_hip_set_chain_skinny_f32; schedule in brgemm_f32_skinny_chain.h): 1 <= m
+// <= 31 rows, layer l of a.L[l].pad columns (n >= bn, n % 4 == 0) and k(l) >= 4 in multiples of 4, flat B, beta 0, on column blocks of bn =
+// 16 / 32 / 64; a.groups = G resident workgroups, the grid, at most the stream's compute units - the caller's guarantee; ONE counter per
+// seam, cnt[l] reaches a.target = epoch * G. Refuses with hipErrorInvalidValue, launching nothing, whatever the kernel does not assume
+// (the list stands at the launcher)
+hipError_t launch_f32_skinny_chain(int bn, const ChainArgs &a, hipStream_t s);
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2; b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);

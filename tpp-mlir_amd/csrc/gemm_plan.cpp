@@ -11,6 +11,7 @@
 #include "brgemm_f32_skinny.h"
 #include "brgemm_f32_skinny_split.h"
 #include "brgemm_bf16_skinny_chain.h"
+#include "brgemm_f32_skinny_chain.h"
 #include <string.h>
 
 namespace tpp {
@@ -1092,6 +1093,70 @@ ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, cons
   return ChainSkinnyPlan{bn, groups, "", false};
 }
 
+// SKINNY-BATCH f32 LAYER CHAINS (xsmm_hip_set_chain_skinny_f32, opt-in; brgemm_f32_skinny_chain.hip, brgemm_f32_skinny_chain.h; gemm_plan.h has the contract).
+bool chain_skinny_f32_ok(const GemmDesc &d, const char **why) {
+  auto no = [&](const char *w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (d.dtype != DT_F32 || d.f32_prec != 0) return no("a call is not exact f32");
+  if (d.vnni_b || d.b_trans || d.a_trans) return no("a call's B is not flat, or an operand is read transposed");
+  if (!d.beta0 || d.vnni_c) return no("a call is not beta 0, or stores a VNNI C");
+  if (d.generic_forced || d.variant_forced) return no("a call was dispatched with a forced kernel");
+  if (!skfc_ld_ok(d.lda, d.ldb, d.ldc, d.stride_a, d.stride_b, d.n, d.k))
+    return no("a leading dimension does not cover its operand or reaches 2^24, or a leading dimension or stride is no multiple of 4 elements");
+  return true;
+}
+// Mode 1, BN and THE GATE, from profiles/chain_skinny_f32_ab.txt and nothing else (one box, 256 CUs, three layers, bias + relu, five alternating
+// rounds, us per step; the baseline (a) = the same calls one by one under xsmm_hip_set_skinny_f32(1) + xsmm_hip_set_skinny_f32_split(1), the best
+// existing form -> one launch on BN 16 / 32 / 64; a (row class, BN) is taken only where it was faster than (a) in EVERY round):
+//   The funnel 784 -> 512 -> 256 -> 128 (largest layer 1.53 MiB of B) m 1 / 8 / 16 / 31: 16.96 / 18.28 / 18.45 / 18.77 -> BN 16 11.84 / 15.45 / 16.13 /
+//     23.87 (BN 32 13.27 / 17.90 / 18.37 / 28.51, BN 64 17.25 .. 36.83): BN 16 wins every round at m 1, 8 and 16 (30 / 15.5 / 12.6 %) and is the
+//     fastest side there; at m 31 every BN loses every round (the second accumulator set's A re-read per workgroup, paid G times a layer).
+//   1024 -> [1024] * 3 (4 MiB a layer): 16.61 / 16.96 / 17.64 / 25.46 -> BN 16 14.94 / 18.70 / 19.79 / 29.68 (BN 32 18.43 .. 36.39, BN 64 25.66 ..
+//     51.16); 1000 -> [1000] * 3: 17.14 / 18.69 / 20.11 / 27.63 -> BN 16 15.44 / 19.39 / 20.69 / 30.58: BN 16 wins every round at m 1 (10 %) and
+//     loses every round from m 8 on - the split single call has P workgroups per column block pulling B, the chain one.
+//   4096 -> [4096] * 3 (64 MiB a layer): 43.39 / 45.40 / 46.09 / 71.56 -> BN 32 50.68 / 55.17 / 59.76 / 88.01, BN 16 80.35 .. 91.53, BN 64 75.11 ..
+//     136.48: every BN loses every round.
+// So: BN 16, for chains whose largest layer has at most the funnel's 784 x 512 x 4 bytes of B at m <= 16, and for chains whose largest layer
+// has at most 4 MiB at m = 1. Everything else is gated - m 2 .. 7 on 1.53 .. 4 MiB layers, layers between 4 and 64 MiB and m 17 .. 30 among
+// it: not measured. Taken without a measurement of their own: layers smaller than the funnel's (its 512 KiB and 128 KiB layers gained inside
+// it) and chains of 2 or 4 .. 8 layers.
+// Not measured: other CU counts (the rule reads them through G alone), several ranks, layers between the measured sizes.
+constexpr const char *SKINNY_F32_CHAIN_GATE_WHY = "gate: not measured faster as one launch than call by call on the split skinny f32 kernel in every round (profiles/chain_skinny_f32_ab.txt)";
+constexpr int64_t SKINNY_F32_CHAIN_GATE_BYTES = 4 * 784 * 512, SKINNY_F32_CHAIN_GATE_BYTES_M1 = 4 << 20; // mode 1: the most bytes of B a layer of a taken chain has, m <= 16 / m = 1
+// the column-block width mode 1 takes for a chain of m rows whose largest layer has most_bytes of B; 0: gated
+static int skinny_f32_chain_bn(int64_t m, int64_t most_bytes) {
+  return (m <= 16 && most_bytes <= SKINNY_F32_CHAIN_GATE_BYTES) || (m == 1 && most_bytes <= SKINNY_F32_CHAIN_GATE_BYTES_M1) ? 16 : 0;
+}
+ChainSkinnyPlan plan_chain_skinny_f32(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int mode, bool strict) {
+  auto no = [](const char *why) { return ChainSkinnyPlan{0, 0, why, false}; };
+  const int forced_bn = mode >= 1000 ? mode % 1000 : mode == 1 ? 0 : mode, forced_g = chain_skinny_mode_forced_g(mode) ? mode / 1000 : 0;
+  if (mode != 1 && !(skf_bn_ok(forced_bn) && (!chain_skinny_mode_forced_g(mode) || (forced_g >= 1 && forced_g <= SKC_GMAX))))
+    return no("skinny-batch f32 chains are off (xsmm_hip_set_chain_skinny_f32)");
+  if (nlayers < 2 || nlayers > SKC_MAXL) return no("fewer than 2 or more than 8 calls");
+  if (m < 1 || m > SKF_M_MAX) return no("m is not 1 .. 31: the f32 chain of the loader-wave tiles decides");
+  if (strict) return no("strict mode: the launch has the bits of the calls under xsmm_hip_set_skinny_f32, not of the calls as dispatched");
+  int64_t narrowest = n[0], most_bytes = 0;
+  for (int l = 0; l < nlayers; ++l) {
+    if (br[l] < 1) return no("a batch is empty");
+    if (!skf_shape_ok(m, n[l], k[l], br[l], 16)) return no("a layer has n < 16, n % 4 != 0, k < 4 or k % 4 != 0");
+    if (n[l] >= SKFC_LD_MAX || k[l] >= SKFC_LD_MAX) return no("a layer is wider or deeper than 2^24");
+    if (n[l] < narrowest) narrowest = n[l];
+    if (4 * br[l] * k[l] * n[l] > most_bytes) most_bytes = 4 * br[l] * k[l] * n[l];
+  }
+  const int bn = mode == 1 ? skinny_f32_chain_bn(m, most_bytes) : forced_bn;
+  if (narrowest < (bn ? bn : 16)) return no("a layer is narrower than the column block");
+  int max_blocks = 0;
+  for (int l = 0; l < nlayers; ++l)
+    if (skf_blocks((int)n[l], bn ? bn : 16) > max_blocks) max_blocks = skf_blocks((int)n[l], bn ? bn : 16);
+  if (cus < 1) return no("the stream's compute units are unknown");
+  if (forced_g > cus) return no("more resident workgroups forced than compute units");
+  const int groups = forced_g ? forced_g : skc_groups(max_blocks, cus);
+  if (bn == 0) return ChainSkinnyPlan{16, groups, SKINNY_F32_CHAIN_GATE_WHY, true};
+  return ChainSkinnyPlan{bn, groups, "", false};
+}
+
 // ---- plan_chain: the layer-chain launch decision (gemm_plan.h has the order of precedence) ---------------------------------------
 static const ChainLaunchPlan &chain_calls(ChainLaunchPlan &p, const char *why) {
   p.form = CF_CALLS, p.why = why;
@@ -1162,6 +1227,30 @@ ChainLaunchPlan plan_chain(int n, const GemmDesc *const *d, const int64_t *br, c
       }
     }
     chain_note(p, "skinny-batch launch", w);
+  }
+  // SKINNY f32 BATCHES (xsmm_hip_set_chain_skinny_f32, brgemm_f32_skinny_chain.hip): directly behind rule 0 and in front of the f32 branch, and
+  // only with the switch non-zero, an f32 first call and m <= 31 - chains the f32 branch below never takes (its tiles have 64 rows). Widths
+  // may differ. Where the rule refuses or gates, everything below is what it is without this switch.
+  if (env.skinny_f32 != 0 && d[0]->dtype == DT_F32 && m <= SKF_M_MAX) {
+    const char *w = "the calls differ in m, or a batch is empty";
+    if (!differ_m) {
+      w = nullptr;
+      bool ok = true;
+      for (int i = 0; i < n && ok; ++i) ok = chain_skinny_f32_ok(*d[i], &w);
+      if (ok) {
+        const ChainSkinnyPlan sp = plan_chain_skinny_f32(m, n, ns, ks, br, cus.get(), env.skinny_f32, env.strict);
+        if (sp.bn > 0 && !sp.gated) { // (gated: the rule's answer is on record in why, nothing is launched)
+          p.form = CF_SKINNY_F32, p.tile = sp.bn, p.b_kind = 0, p.groups = sp.groups, p.why = "";
+          p.bm = (int)m, p.bn = sp.bn, p.tiles_m = skc_key_tiles_m(), p.tiles_n = skc_key_tiles_n(sp.groups), p.mixed = false;
+          p.args_n = (int)ns[0];
+          for (int l = 1; l < n; ++l)
+            if (ns[l] > p.args_n) p.args_n = (int)ns[l];
+          return p;
+        }
+        w = sp.why;
+      }
+    }
+    chain_note(p, "skinny-batch f32 launch", w);
   }
 
   // 1. ON THE 256x256 TILE (xsmm_hip_set_chain_dma256, brgemm_bf16_dma256_chain.hip): asked first, and only with the switch non-zero. The rule sees

@@ -344,6 +344,23 @@ int chain_skinny_b_kind(const GemmDesc &d, const char **why);
 struct ChainSkinnyPlan { int bn; int groups; const char *why; bool gated; };
 inline bool chain_skinny_mode_forced_g(int mode) { return mode >= 1000; }
 ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int b_kind, int mode, bool strict);
+// SKINNY-BATCH f32 LAYER CHAINS (xsmm_hip_set_chain_skinny_f32; plan_chain, brgemm_f32_skinny_chain.hip launch_f32_skinny_chain, schedule in
+// brgemm_f32_skinny_chain.h). Host-only, no HIP calls.
+// One call of a chain: true if it can be a layer of this launch - f32, a flat B (no VNNI, not transposed), beta 0, no VNNI C, no forced
+// generic kernel and no forced variant, skfc_ld_ok (lda / ldb / ldc / stride_a / stride_b multiples of 4 elements and not negative, lda >=
+// k, ldb >= n, ldc >= n, lda and ldc below 2^24: the launch's buffer offsets) - else false with *why set.
+bool chain_skinny_f32_ok(const GemmDesc &d, const char **why);
+// The ONE launch: the arguments of plan_chain_skinny without the image; mode = xsmm_hip_set_chain_skinny_f32's value. THE PARTITION: an f32 chain
+// with m <= 31 is this rule's alone - the f32 chain of the loader-wave tiles asks for 64 rows - and it takes nothing else. Takes 2 .. 8
+// layers with 1 <= m <= 31, every batch >= 1, per layer skf_shape_ok(m, n_l, k_l, br_l, BN) - n_l >= BN, n_l % 4 == 0, k_l >= 4, k_l % 4 == 0;
+// widths may differ.
+//   BN:  modes 16 / 32 / 64 and 1000 * G + BN: that BN; a layer narrower than BN: a refusal. Mode 1: as measured (below).
+//   G:   min(max_l skf_blocks(n_l, BN), cus); a forced G as given if G <= cus, else a refusal.
+// Strict mode refuses: the launch has the bits of the calls under xsmm_hip_set_skinny_f32(BN), not of the calls as the descriptors were planned.
+// It reads neither xsmm_hip_set_skinny_f32, xsmm_hip_set_skinny_f32_split nor xsmm_hip_set_chain_skinny, and none of them reads it.
+// MODE 1 and THE GATE are fitted to profiles/chain_skinny_f32_ab.txt and to nothing else; the rows stand at the rule in gemm_plan.cpp. A
+// gated answer names the plan with gated = true and why = the gate, and the caller does not launch. Forced modes are never gated.
+ChainSkinnyPlan plan_chain_skinny_f32(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int mode, bool strict);
 // THE LAYER-CHAIN LAUNCH DECISION (rt_chain.h try_chain_launch carries the answer out): which of the ten launch forms runs n calls that
 // the chain contract admits, on which tile, B image and group count - or that they run call by call, and which rule refused. Host-only:
 // no HIP call, no global; the descriptors, the batch counts, the switches and a way to ask for the stream's compute units are arguments.
@@ -352,6 +369,8 @@ ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, cons
 //   0. skinny batches         plan_chain_skinny        {skinny}   asked in front of everything, and only with the switch non-zero, a bf16 first call
 //      and m <= 31: no other form takes such a chain, and this rule takes no other. Where it refuses or gates, everything below is what it is
 //      without this switch (call by call today).
+//      skinny f32 batches     plan_chain_skinny_f32    {skinny_f32}   directly behind rule 0, in front of the f32 branch, and only with the switch
+//      non-zero, an f32 first call and m <= 31: these chains are this rule's alone; refused or gated, the answer is what it is without the switch.
 //   1. the 256x256 tile      plan_chain_dma256        {dma256; dma256_images in mode 1}   asked first; where it takes the chain nothing else is read
 //      (an f32 chain - every call on the K-split loader-wave tile of the first, within the compute units - reads no switch)
 //   2. a forced G / a forced W  plan_chain_rounds {rounds = 1000 + G}, plan_chain_width_rounds {width_rounds = 1000 + W}: in front of the one-round rules
@@ -363,10 +382,10 @@ ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, cons
 //      where the others refuse
 // Calls that differ in n are rules 4 and 6's (ragged mixed widths) alone, equal widths everyone else's; strict is read by every rule.
 constexpr int CHAIN_PLAN_MAXL = 8; // (= CH_MAXL, chain_args.h)
-enum ChainForm : int { CF_CALLS, CF_F32, CF_PLAIN, CF_EDGE, CF_ROUNDS, CF_RAGGED, CF_WIDTHS, CF_WROUNDS, CF_WRAGGED, CF_DMA256, CF_SKINNY, CF_FORMS };
+enum ChainForm : int { CF_CALLS, CF_F32, CF_PLAIN, CF_EDGE, CF_ROUNDS, CF_RAGGED, CF_WIDTHS, CF_WROUNDS, CF_WRAGGED, CF_DMA256, CF_SKINNY, CF_SKINNY_F32, CF_FORMS };
 // xsmm_hip_set_strict, the seven chain switches of the tiles (xsmm_hip_set_chain_*), xsmm_hip_set_edge_tiles and xsmm_hip_set_dma256_images, and
 // xsmm_hip_set_chain_skinny; mode_switches.h chain_plan_env_of fills it per invoke (rt_core.h chain_plan_env)
-struct ChainPlanEnv { bool strict; int edge, rounds, ragged, widths, width_rounds, widths_ragged, dma256; int edge_tiles, dma256_images; int skinny = 0; };
+struct ChainPlanEnv { bool strict; int edge, rounds, ragged, widths, width_rounds, widths_ragged, dma256; int edge_tiles, dma256_images; int skinny = 0; int skinny_f32 = 0; /* xsmm_hip_set_chain_skinny_f32 */ };
 // The compute units a launch on the invoke's stream can use - the one input that costs runtime calls (rt_chain.h stream_cus: three). Asked
 // lazily and at most once per invoke: a decision that ends in front of every rule that reads them never pays for them.
 struct ChainCus {

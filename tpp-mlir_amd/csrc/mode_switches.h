@@ -18,7 +18,7 @@ namespace tpp {
 enum ModeSwitch : int {
   MS_TAIL_SPLIT, MS_EDGE_TILES, MS_EDGE_K, MS_EDGE_K_BF16, MS_EDGE_K8_BF16, MS_DMA256_IMAGES, MS_DMA256_EDGE, MS_SKINNY_BF16, MS_SKINNY_SPLIT,
   MS_F32_HALVES, MS_CHAIN_EDGE, MS_CHAIN_ROUNDS, MS_CHAIN_RAGGED, MS_CHAIN_WIDTHS, MS_CHAIN_WIDTH_ROUNDS, MS_CHAIN_WIDTHS_RAGGED, MS_CHAIN_DMA256,
-  MS_CHAIN_SKINNY, MS_SKINNY_F32, MS_SKINNY_F32_SPLIT, MS_COUNT
+  MS_CHAIN_SKINNY, MS_SKINNY_F32, MS_SKINNY_F32_SPLIT, MS_CHAIN_SKINNY_F32, MS_COUNT
 };
 
 // the values a setter accepts (every other value: -1, nothing changed; in the environment: the default)
@@ -89,6 +89,8 @@ inline constexpr ModeSwitchRow MODE_SWITCHES[MS_COUNT] = {
     {MS_SKINNY_F32, "TPP_HIP_SKINNY_F32", 0, skinny_f32_mode_ok, 4},
     // plan_gemm_call, skinny_f32_split_parts - read only for a call already on the skinny f32 kernel; brgemm_f32_skinny_split.hip: parts P_eff, workgroups
     {MS_SKINNY_F32_SPLIT, "TPP_HIP_SKINNY_F32_SPLIT", 0, skinny_f32_split_mode_ok, 3},
+    // plan_chain asks plan_chain_skinny_f32; rt_chain.h launches brgemm_f32_skinny_chain.hip and counts: resident workgroups G, BN, waves of the launch
+    {MS_CHAIN_SKINNY_F32, "TPP_HIP_CHAIN_SKINNY_F32", 0, chain_skinny_mode_ok, 4},
 };
 constexpr bool mode_switch_table_ok() {
   for (int i = 0; i < MS_COUNT; ++i)
@@ -160,6 +162,7 @@ inline ChainPlanEnv chain_plan_env_of(bool strict) {
   e.edge_tiles = mode_of(MS_EDGE_TILES);
   e.dma256_images = mode_of(MS_DMA256_IMAGES);
   e.skinny = mode_of(MS_CHAIN_SKINNY);
+  e.skinny_f32 = mode_of(MS_CHAIN_SKINNY_F32);
   return e;
 }
 

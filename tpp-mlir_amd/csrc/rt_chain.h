@@ -230,7 +230,7 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   c.groups = plan.groups;
   for (int i = 0; i < n; ++i)
     c.L[i] = ChainLayer{pb[i], pd[i], pc[i], d[i]->ldb, d[i]->ldc, d[i]->stride_a, d[i]->stride_b, (int)d[i]->k, (int)br[i],
-                        EP_BETA0 | (d[i]->bias ? EP_BIAS : 0) | (d[i]->relu ? EP_RELU : 0), plan.mixed || plan.form == CF_SKINNY ? (int)d[i]->n : 0};
+                        EP_BETA0 | (d[i]->bias ? EP_BIAS : 0) | (d[i]->relu ? EP_RELU : 0), plan.mixed || plan.form == CF_SKINNY || plan.form == CF_SKINNY_F32 ? (int)d[i]->n : 0};
   // the pool of error words is about to run dry (hundreds of launches without a synchronisation): synchronise and check here
   // instead of ever dropping a journal entry
   if (g_chain_journaled.load(std::memory_order_relaxed) >= CHAIN_ERR_POOL - 8) {
@@ -295,6 +295,11 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
   case CF_SKINNY: // resident workgroups G, the column-block width BN (the plan's tile), the B image; the block's key is (1, G): target = epoch * G
     HIP_OK(launch_bf16_skinny_chain(b_kind, tile, c, s)); counted = tpp::MS_CHAIN_SKINNY;
     word[0] = plan.groups, word[1] = tile, word[2] = b_kind;
+    break;
+  case CF_SKINNY_F32: // resident workgroups G, BN (the plan's tile), the waves of the launch (its deepest layer's); key (1, G), target = epoch * G
+    HIP_OK(launch_f32_skinny_chain(tile, c, s)); counted = tpp::MS_CHAIN_SKINNY_F32;
+    word[0] = plan.groups, word[1] = tile, word[2] = 1;
+    for (int i = 0; i < n; ++i) word[2] = std::max<int64_t>(word[2], skfc_layer_waves(br[i], (int)d[i]->k));
     break;
   default: return false; // (CF_CALLS has returned above)
   }

@@ -101,7 +101,7 @@ class ShardedMlp:
             cur = acts[l]
         if self.chain and hasattr(self.rt, "fused_brgemm_chain"):
             # ONE call for the rank's whole step: the runtime runs the layer chain as a single persistent launch when it can
-            # (bf16, device buffers, async mode: xsmm_hip_fused_brgemm_chain_invoke), else call by call - same result
+            # (bf16 or f32, device buffers, async mode: xsmm_hip_fused_brgemm_chain_invoke), else call by call - same result
             self.last_step_fused = self.rt.fused_brgemm_chain(self.spec.dtype, calls)
         else:
             self.last_step_fused = False

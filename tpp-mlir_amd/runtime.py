@@ -191,6 +191,12 @@ _MODE_SWITCHES = {
         set_skinny_bf16(BN)): 0 off (default), 1 the rule (VNNI-2 chains whose layers have at most 2 MiB of B, on BN 16: as measured), 16 / 32 / 64 that column-block width
         wherever eligible, 1000 * G + BN that width on G resident workgroups; returns the previous mode, -1 for a value it refuses""",
         """(skinny-batch chain launches; resident workgroups G, BN, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""),
+    "chain_skinny_f32": (4,
+        """f32 layer chains with 1 .. 31 rows (flat B, n >= BN, n % 4 == 0, k % 4 == 0) as one launch of the skinny-batch f32 kernel's chain
+        form (the bits of the calls under set_skinny_f32(BN), split off): 0 off (default), 1 the rule (as measured: it gates what did not
+        gain), 16 / 32 / 64 that column-block width wherever eligible, 1000 * G + BN that width on G resident workgroups; returns the
+        previous mode, -1 for a value it refuses""",
+        """(skinny-batch f32 chain launches; resident workgroups G, BN, waves per workgroup of the most recent one)"""),
     "f32_halves": (4,
         """f32 whole-layer calls on the 64x64 + K2 tile as two 64x32 + K2 workgroups per tile (the same bits): 0 off, 1 the rule
         (default: at least one tile per compute unit), 2 wherever eligible; returns the previous mode, -1 for a value it refuses""",
