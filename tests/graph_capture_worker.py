@@ -11,6 +11,9 @@ them up would change what later tests run on):
                                          scratch block (tpp-mlir_amd/csrc/split_scratch.h)
   graph_capture_worker.py streams        a forced-split skinny call on the default stream and on seventeen more: the 17th (device, stream)
                                          pair gets no block and runs unsplit
+  graph_capture_worker.py growth_f32     growth for the skinny f32 split (brgemm_f32_skinny_split.hip keeps its own list of scratch blocks):
+                                         small, large, small at BN 64, m 17 - 24576, 327680, 24576 partial floats
+  graph_capture_worker.py streams_f32    streams for the skinny f32 split, with both counters' words asserted behind every launch
 Each prints one JSON line and exits 0; "errors" lists what did not hold (the test asserts it is empty).
 
 queue: the captured flush is the eighth of its slot group (seven flushes of smaller groups come first), so TileQueue::launched would record
@@ -510,6 +513,128 @@ def streams_scenario(rt):
     return {"scenario": "streams", "errors": errors, "kernels": kernels, "split_moved": moved, "skinny_moved": unsplit_moved}
 
 
+# ------------------------------------------------------------------------------------------------ the scratch block's edges, f32
+# brgemm_f32_skinny_split.hip includes split_scratch.h on its own: split_scratch_for's list of 16 blocks there is not the bf16 kernel's.
+def f32_text(m, bn, split):
+    return "brgemm_f32_skinny%s<%dx%d>" % ("_split" if split else "", 16 if m <= 16 else 32, bn)
+
+
+def f32_split_words(case, bn, P):
+    """what a taken split launch leaves behind the launch counts of skinny_f32_split_stats and skinny_f32_stats, and what the unsplit launch
+    leaves in skinny_f32_stats (include/tpp_xsmm_abi.h; the formulas tests/test_skinny_f32_split_gpu.py run_split asserts)"""
+    steps, blocks = case.br * -(-case.k // 16), -(-case.n // bn)
+    p_eff = min(P, steps)
+    return (p_eff, blocks * p_eff), (blocks * p_eff, min(8, -(-steps // p_eff)), bn), (blocks, min(8, steps), bn)
+
+
+def split_call_f32(rt, case, bn, P, bufs):
+    """one skinny f32 call under BN `bn` and P parts on the runtime's current stream, no synchronisation; the reported kernel"""
+    rt.set_skinny_f32(bn)
+    rt.set_skinny_f32_split(P)
+    try:
+        return invoke(rt, case, case.dispatch(rt), bufs)
+    finally:
+        rt.set_skinny_f32_split(0)
+        rt.set_skinny_f32(0)
+
+
+def exact_f32(case):
+    ref = case.oracle()
+    return ref, np.array_equal(ed.bits(ref[case.win]), ed.bits(case.fp64())) and case.outside_untouched(ref)
+
+
+def growth_f32_scenario(rt):
+    """small, large, small back to back on one side stream: the large call's partial area outgrows the stream's first 2^18-float block, which
+    is freed and allocated anew (behind a drain of the stream) while the first call may still be in flight; the third call runs in the
+    grown block"""
+    import torch
+    errors = []
+    rt.set_async(True)
+    bn, mb = 64, 32
+    small = F32Case(17, 200, 36, 3, 11, beta0=True, bias=True, relu=True)
+    large = F32Case(17, 9 * 64 + 4, 64, 16, 12, beta0=True, bias=True, relu=True)
+    floats = [-(-c.n // bn) * min(P, c.br * -(-c.k // 16)) * mb * bn for c, P in ((small, 3), (large, 16))]
+    if floats != [24576, 327680] or not floats[0] <= 1 << 18 < floats[1] <= 8 << 20:
+        errors.append("the cases do not straddle the first 2^18-float block: %r partial floats" % (floats,))
+    seq = [(small, 3), (large, 16), (small, 3)]
+    refs = {}
+    for c in (small, large):
+        refs[id(c)], ok = exact_f32(c)
+        if not ok:
+            errors.append("not an exact case")
+    bufs = [c.device() for c, _ in seq]
+    torch.cuda.synchronize()
+    sbefore, ubefore = rt.skinny_f32_split_stats(), rt.skinny_f32_stats()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    kernels = []
+    try:
+        rt.set_stream(s)
+        for (c, P), b in zip(seq, bufs):  # back to back: nothing waits between the launches
+            kernels.append(split_call_f32(rt, c, bn, P, b))
+    finally:
+        rt.set_stream(None)
+    rt.synchronize()
+    s.synchronize()
+    torch.cuda.synchronize()
+    for i, ((c, P), b, kern) in enumerate(zip(seq, bufs, kernels)):
+        if kern != f32_text(c.m, bn, True):
+            errors.append("call %d reported %r" % (i, kern))
+        got, ref = download(b[2], c), refs[id(c)]
+        if not same_bits(got[c.win], ref[c.win]):
+            errors.append("call %d (n = %d, P = %d) does not have the oracle's bits" % (i, c.n, P))
+        if not c.outside_untouched(got):
+            errors.append("call %d wrote outside its window" % i)
+    moved, umoved = rt.skinny_f32_split_stats()[0] - sbefore[0], rt.skinny_f32_stats()[0] - ubefore[0]
+    if moved != 3 or umoved != 3:
+        errors.append("the split counter moved by %d, the skinny f32 counter by %d" % (moved, umoved))
+    return {"scenario": "growth_f32", "errors": errors, "kernels": kernels, "partial_floats": floats, "split_launches": moved}
+
+
+def streams_f32_scenario(rt):
+    """streams_scenario for the f32 split: the default stream is the first (device, stream) pair of brgemm_f32_skinny_split.hip's list, fifteen
+    side streams get a block - each zeroes its counters on its own stream in front of its first launch -, the 17th and 18th pair run unsplit"""
+    import torch
+    errors = []
+    rt.set_async(True)
+    bn, P = 32, 3
+    case = F32Case(17, bn + 4, 36, 3, 21, beta0=True, bias=True, relu=True)
+    ref, ok = exact_f32(case)
+    if not ok:
+        errors.append("not an exact case")
+    split_words, skinny_words, unsplit_words = f32_split_words(case, bn, P)
+    streams = [None] + [torch.cuda.Stream() for _ in range(SPLIT_MAX_BLOCKS + 1)]
+    handles = {0 if s is None else s.cuda_stream for s in streams}
+    if len(handles) != len(streams):
+        errors.append("the streams are not %d different ones: %d" % (len(streams), len(handles)))
+    kernels, moved, unsplit_moved = [], [], []
+    for i, s in enumerate(streams):
+        bufs = case.device()
+        torch.cuda.synchronize()
+        sb, ub = rt.skinny_f32_split_stats(), rt.skinny_f32_stats()
+        try:
+            rt.set_stream(s)
+            kernels.append(split_call_f32(rt, case, bn, P, bufs))
+        finally:
+            rt.set_stream(None)
+        rt.synchronize()
+        torch.cuda.synchronize()
+        sa, ua = rt.skinny_f32_split_stats(), rt.skinny_f32_stats()
+        moved.append(sa[0] - sb[0])
+        unsplit_moved.append(ua[0] - ub[0])
+        took = i < SPLIT_MAX_BLOCKS
+        if kernels[-1] != f32_text(case.m, bn, took):
+            errors.append("pair %d reported %r, not %r" % (i + 1, kernels[-1], f32_text(case.m, bn, took)))
+        if tuple(sa) != ((sb[0] + 1,) + split_words if took else tuple(sb)):
+            errors.append("pair %d: the split counter %r -> %r" % (i + 1, sb, sa))
+        if tuple(ua) != (ub[0] + 1,) + (skinny_words if took else unsplit_words):
+            errors.append("pair %d: the skinny f32 counter %r -> %r" % (i + 1, ub, ua))
+        got = download(bufs[2], case)
+        if not same_bits(got[case.win], ref[case.win]) or not case.outside_untouched(got):
+            errors.append("pair %d: not the oracle's bits, or wrote outside the window" % (i + 1))
+    return {"scenario": "streams_f32", "errors": errors, "kernels": kernels, "split_moved": moved, "skinny_moved": unsplit_moved}
+
+
 if __name__ == "__main__":
     rt = pkg.get_runtime()
     what = sys.argv[1:]
@@ -519,6 +644,10 @@ if __name__ == "__main__":
         out = small_split_scenario(rt)
     elif what == ["growth"]:
         out = growth_scenario(rt)
+    elif what == ["growth_f32"]:
+        out = growth_f32_scenario(rt)
+    elif what == ["streams_f32"]:
+        out = streams_f32_scenario(rt)
     else:
         out = streams_scenario(rt)
     rt.synchronize()

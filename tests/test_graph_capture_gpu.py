@@ -16,20 +16,27 @@ asserted for the call inside the capture as for the call outside it. Every switc
   1 forms that are legal in a capture, one smallest eligible shape per form under its forcing mode (the shapes of the form's own test
     file): f32 edge tile, f32 ragged k, f32 halves, bf16 edge tile, bf16 ragged k, bf16 k8, the 256x256 flat and VNNI-4 images, the
     256x256 edge tiles, the skinny bf16 kernel on every (image, BN) instance at m = 17, n = BN + 8, k = 72 (clamped rows, a shifted block
-    and a ragged tail inside the graph). Inside the capture the call reports the same kernel and moves the same counter as outside it,
-    and no other counter moves - single-call, chain or tile-queue.
+    and a ragged tail inside the graph), the skinny f32 kernel on all six (MB, BN) instances at m = 7 / 17, n = BN + 4, k = 36 (two column
+    blocks with the second shifted back, clamped rows, a masked last 16-k step) and once with nine steps dealt over eight waves. Inside
+    the capture the call reports the same kernel and moves the same counter as outside it, and no other counter moves - single-call
+    (both skinny f32 counters among them), chain or tile-queue.
   2 forms that fall back in a capture. Splits - a forced split count on the f32 loader-wave variants, the tail split at the smallest
-    shape the CU count gives, skinny split P = 3 at k = 72 and P = 16 at (k, br) = (64, 16): inside the capture the reported kernel is the
+    shape the CU count gives, skinny split P = 3 at k = 72 and P = 16 at (k, br) = (64, 16), skinny f32 split P = 3 at (k, br) = (36, 3)
+    (masked steps inside the parts) and P = 16 at (k, br) = (64, 16) - launch_gemm's re-plan with the split zeroed, which counts and
+    reports from the re-planned launch: inside the capture the reported kernel is the
     unsplit one, the split's counter stands still and the unsplit counter moves where there is one; between the replays the same call
     runs un-captured on the same stream and IS the split kernel. (The split of brgemm_bf16_small.hip lives in tile-queue groups: in the
-    worker, with section 3.) Chains - every case of tests/test_chain_switches_gpu.py CASES with all switches on, and a skinny chain
-    (m = 17, [3 BN + 8] * 3, k0 = 72): inside a capture xsmm_hip_fused_brgemm_chain_invoke returns 0 and no chain counter moves; every
+    worker, with section 3.) Chains - every case of tests/test_chain_switches_gpu.py CASES with all switches on, a skinny chain
+    (m = 17, [3 BN + 8] * 3, k0 = 72) and a skinny f32 chain (m = 17, [100] * 3, k0 = 36, BN 32; a test function of its own: f32 buffers,
+    every layer checked against fp64 as tests/test_chain_skinny_f32_gpu.py checks it): inside a capture xsmm_hip_fused_brgemm_chain_invoke returns 0 and no chain counter moves; every
     replay equals the oracle layer by layer and the un-captured chain invoke under the same switches. (On exact inputs every form has
     the oracle's bits, so that comparison holds for every form - also where, on random data, the two tile families differ by an ulp as
     tests/test_chain_gpu.py notes: there the comparison would have to be with the call-by-call run.) The largest case (7680 rows x 2048
     columns) draws one fresh input; its second and third are row permutations of it, checked against the same permutation of its oracle rows.
-  3 the tile queue in a capture, 4 the scratch block's edges: tests/graph_capture_worker.py, a process per scenario (the slot ring, the
-    trace cache and the scratch blocks are per process and never freed; a library that exits is a failed assertion here, not a dead pytest)."""
+  3 the tile queue in a capture, 4 the scratch block's edges - growth under launches in flight and the 17th (device, stream) pair, for the
+    bf16 skinny split and for the f32 skinny split (split_scratch_for keeps one list of blocks per translation unit, so each has its own
+    sixteen): tests/graph_capture_worker.py, a process per scenario (the slot ring, the trace cache and the scratch blocks are per process
+    and never freed; a library that exits is a failed assertion here, not a dead pytest)."""
 import importlib
 import json
 import os
@@ -50,6 +57,8 @@ from skinny_bf16_worker import text as skinny_text
 from skinny_split_worker import expected_skinny_stats, expected_split_stats
 from skinny_split_worker import text as split_text
 from test_tail_split_gpu import shape as tail_shape
+from test_chain_skinny_f32_cpu import chains as f32_chains
+from test_chain_skinny_f32_gpu import check_exact as check_exact_f32
 from test_chain_switches_gpu import CASES as CHAIN_CASES
 from test_chain_switches_gpu import assert_exact, golden_form, layers
 from test_chain_switches_gpu import counters as chain_counters
@@ -62,7 +71,8 @@ F32_NAME = {6: "brgemm_f32_lw<64x64,k2>", 7: "brgemm_f32_lw<64x32,k4>", 9: "brge
 F32_TILE = {6: (64, 64), 7: (64, 32), 9: (32, 32)}
 DMA_KIND = {2: 0, 0: 2, 4: 4}
 EP = dict(beta0=True, bias=True, relu=True)  # beta 0: the output window is NaN before every run
-SINGLE = ("edge_tiles", "edge_k", "edge_k_bf16", "edge_k8_bf16", "dma256_images", "dma256_edge", "skinny_bf16", "skinny_split", "tail_split", "f32_halves")
+SINGLE = ("edge_tiles", "edge_k", "edge_k_bf16", "edge_k8_bf16", "dma256_images", "dma256_edge", "skinny_bf16", "skinny_split", "skinny_f32", "skinny_f32_split",
+          "tail_split", "f32_halves")
 
 
 @pytest.fixture(scope="module")
@@ -78,6 +88,7 @@ def all_off(rt):
             getattr(rt, "set_" + name)(0)
     chain_switches(rt, 0)
     rt.set_chain_skinny(0)
+    rt.set_chain_skinny_f32(0)
     rt.force_split(-1)
     rt.force_variant(-1)
     rt.set_stream(None)
@@ -108,6 +119,7 @@ def counters(rt):
 def all_chain_counters(rt):
     c = chain_counters(rt)
     c["skinny"] = rt.chain_skinny_stats()[0]
+    c["skinny_f32"] = rt.chain_skinny_f32_stats()[0]
     return c
 
 
@@ -173,6 +185,10 @@ def bf16_form(name, image, m, n, k, br, on, text, moved):
     return dict(id=name, make=lambda seed: Case(image, m, n, k, br, seed, exact=True, **EP), on=on, text=text, moved=moved, force=None)
 
 
+def skinny_f32_text(m, bn, split=False):
+    return "brgemm_f32_skinny%s<%dx%d>" % ("_split" if split else "", 16 if m <= 16 else 32, bn)
+
+
 FORMS = [
     # tests/test_edge_tiles_gpu.py shapes(9)[0]: one more row than the 32x32 tile, one more 16-byte piece of columns
     f32_form("f32_edge_tile", 33, 36, 64, 1, [("edge_tiles", 9)], F32_NAME[9] + ", edge tiles", {"edge_tiles": (2, 2, 9)}),
@@ -193,6 +209,14 @@ FORMS = [
     bf16_form("skinny_%d_bn%d" % (image, bn), image, 17, bn + 8, 72, 1, [("skinny_bf16", bn)], skinny_text(image, 17, bn),
               {"skinny_bf16": skinny_stats(0, image, bn + 8, 72, 1, bn)[1:]})
     for image in (2, 0, 4) for bn in (16, 32, 64) if instance_exists(image, bn)
+] + [
+    # tests/test_skinny_f32_gpu.py: two column blocks, the second shifted back; rows clamped to m - 1; k = 36: the third 16-k step keeps one
+    # lane group. The counter: column blocks, waves = min(8, br * ceil(k / 16)), BN
+    f32_form("skinny_f32_m%d_bn%d" % (m, bn), m, bn + 4, 36, 1, [("skinny_f32", bn)], skinny_f32_text(m, bn), {"skinny_f32": (2, 3, bn)})
+    for bn in (16, 32, 64) for m in (7, 17)
+] + [
+    # nine steps dealt over eight waves: wave 0 takes two
+    f32_form("skinny_f32_nine_steps", 17, 16 + 4, 36, 3, [("skinny_f32", 16)], skinny_f32_text(17, 16), {"skinny_f32": (2, 8, 16)}),
 ]
 
 
@@ -264,6 +288,23 @@ def test_the_skinny_split_runs_unsplit_in_a_capture(rt, P, k, br):
     run_split(rt, lambda seed: Case(image, m, n, k, br, seed, exact=True, **EP), 80 + P, None, on,
               split_text(image, m, bn), {"skinny_split": expected_split_stats(0, n, k, br, bn, P)[1:], "skinny_bf16": expected_skinny_stats(0, image, n, k, br, bn, P)[1:]},
               skinny_text(image, m, bn), {"skinny_bf16": skinny_stats(0, image, n, k, br, bn)[1:]}, "skinny split P = %d" % P)
+
+
+@pytest.mark.parametrize("P,k,br", [(3, 36, 3), (16, 64, 16)], ids=["P3_k36_br3", "P16_k64_br16"])
+def test_the_skinny_f32_split_runs_unsplit_in_a_capture(rt, P, k, br):
+    """launch_gemm's GL_F32_SKINNY block: the split launcher refuses (split_scratch_for gives a capturing stream no block), the call is
+    planned again with the split zeroed, runs, and is counted and reported from THAT plan. The counters' words are the formulas
+    tests/test_skinny_f32_split_gpu.py run_split asserts (restated here, not read from the counters)"""
+    bn, m, n = 32, 17, 32 + 4
+    steps, blocks = br * -(-k // 16), -(-n // bn)
+    p_eff = min(P, steps)
+
+    def on(r):
+        r.set_skinny_f32(bn), r.set_skinny_f32_split(P)
+
+    run_split(rt, lambda seed: F32Case(m, n, k, br, seed, **EP), 90 + P, None, on,
+              skinny_f32_text(m, bn, split=True), {"skinny_f32_split": (p_eff, blocks * p_eff), "skinny_f32": (blocks * p_eff, min(8, -(-steps // p_eff)), bn)},
+              skinny_f32_text(m, bn), {"skinny_f32": (blocks, min(8, steps), bn)}, "skinny f32 split P = %d" % P)
 
 
 # ------------------------------------------------------------------------------------------------ 2: falls back in a capture - chains
@@ -345,6 +386,62 @@ def test_a_captured_chain_runs_call_by_call(rt, name, row, m, sizes, k_all, imag
         rt.set_chain_skinny(0)
 
 
+def test_a_captured_skinny_f32_chain_runs_call_by_call(rt):
+    """tests/test_chain_skinny_f32_cpu.py chains(32)[0] at m = 17 under xsmm_hip_set_chain_skinny_f32(32), every other switch 0: three layers of
+    100 columns (four column blocks, the last shifted back), k = 36 / 100 / 100. The expected counter words are those run_taken of
+    tests/test_chain_skinny_f32_gpu.py computes: G = min(widest layer's column blocks, compute units), BN, the deepest layer's waves"""
+    bn, m = 32, 17
+    name, ns, ks, brs = f32_chains(bn)[0]
+    assert (ns, ks) == ([100] * 3, [36, 100, 100])
+    ch = WidthsChain(rt, 0, m, ns, ks, brs, 1700, exact=True, dtype=F32)
+    G = min(max(-(-n // bn) for n in ns), torch.cuda.get_device_properties(0).multi_processor_count)
+    waves = max(min(8, b * -(-k // 16)) for k, b in zip(ks, brs))
+    outs_g, outs_r = ch.outputs(), ch.outputs()
+    rt.set_chain_skinny_f32(bn)
+
+    def state():
+        return all_chain_counters(rt), rt.chain_skinny_f32_stats(), rt.skinny_f32_stats(), rt.skinny_f32_split_stats()
+
+    log = []  # every call: (what the chain invoke returned, the counters before, after)
+
+    def call(outs=outs_g):
+        before = state()
+        log.append((rt.fused_brgemm_chain(F32, ch.calls(outs)), before, state()))
+        return log[-1]
+
+    def assert_one_launch(obs, where):
+        ran, (chains0, stats0, single0, split0), (chains1, stats1, single1, split1) = obs
+        moved = {k: chains1[k] - chains0[k] for k in chains1 if chains1[k] != chains0[k]}
+        assert bool(ran) is True and moved == {"skinny_f32": 1}, (where, ran, moved)
+        assert stats1 == (stats0[0] + 1, G, bn, waves), (where, stats0, stats1)
+        assert (single1, split1) == (single0, split0), (where, "a single-call skinny f32 counter moved", single0, single1, split0, split1)
+
+    graph, (ran, before, after), _ = captured(rt, call)
+    assert ran == 0, "a captured chain call must not use the one-launch kernel (returned %r)" % (ran,)
+    assert after == before, ("a counter moved inside the capture", before, after)
+    assert len(log) == 2
+    assert_one_launch(log[0], "the warm-up in front of the capture")
+    rows, rng = m + GUARD_ROWS, np.random.default_rng(17)
+    for rep in range(3):
+        x = np.full((rows, ch.ld_in[0]), np.nan, np.float32)  # a fresh exact layer-0 input, NaN guard rows and gap columns as WidthsChain lays them
+        x[:m, :ks[0]] = rng.integers(-15, 16, (m, ks[0]))
+        ch.x = x.reshape(-1)
+        ch.dx.copy_(torch.from_numpy(ch.x).cuda())
+        ch.refill(outs_g)
+        ch.refill(outs_r)
+        torch.cuda.synchronize()
+        graph.replay()
+        torch.cuda.synchronize()
+        got = ch.host(outs_g)
+        ch.check_windows(got)
+        check_exact_f32(ch, got)  # every layer the fp64 result cast to f32; asserts its own precondition
+        assert_one_launch(call(outs_r), "un-captured, after replay %d" % rep)
+        rt.synchronize()
+        for l in range(ch.L):
+            assert torch.equal(outs_g[l], outs_r[l]), "replay %d: layer %d differs from the un-captured one-launch run" % (rep, l)
+    rt.set_chain_skinny_f32(0)
+
+
 # ------------------------------------------------------------------------------------------------ 3, 4: in a process of their own
 def worker(*args):
     env = {k: v for k, v in os.environ.items() if not k.startswith("TPP_HIP_")}
@@ -382,4 +479,15 @@ def test_the_scratch_block_grows_under_launches_in_flight():
 
 def test_the_seventeenth_stream_runs_unsplit():
     d = worker("streams")
+    assert d["split_moved"] == [1] * 16 + [0, 0] and d["skinny_moved"] == [1] * 18, d
+
+
+def test_the_f32_scratch_block_grows_under_launches_in_flight():
+    d = worker("growth_f32")
+    assert d["split_launches"] == 3 and d["kernels"] == ["brgemm_f32_skinny_split<32x64>"] * 3, d
+
+
+def test_the_seventeenth_stream_runs_the_f32_call_unsplit():
+    d = worker("streams_f32")
+    assert d["kernels"] == ["brgemm_f32_skinny_split<32x32>"] * 16 + ["brgemm_f32_skinny<32x32>"] * 2, d["kernels"]
     assert d["split_moved"] == [1] * 16 + [0, 0] and d["skinny_moved"] == [1] * 18, d
