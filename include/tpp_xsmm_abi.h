@@ -692,6 +692,25 @@ TPP_XSMM_EXPORT void xsmm_hip_skinny_f32_split_stats(int64_t out[3]);
  * (the deepest layer's). The counters of the other switches do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_chain_skinny_f32(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_chain_skinny_f32_stats(int64_t out[4]);
+/* The K split INSIDE a skinny-batch f32 chain launch (opt-in; also TPP_HIP_CHAIN_SKINNY_F32_SPLIT, read as a number; a refused value leaves 0):
+ * a refinement of xsmm_hip_set_chain_skinny_f32, read only for a chain that switch has taken - with that switch at 0 it changes nothing. The
+ * unsplit chain launch has at most one workgroup per column block of its widest layer, each streaming its whole K range alone. With P
+ * parts the launch is brgemm_f32_skinny_chain_split<BN, MB> (brgemm_f32_skinny_chain_split.hip; schedule in brgemm_f32_skinny_chain_split.h): layer
+ * l with S_l = br_l * ceil(k_l / 16) steps is blocks_l * P_l units of work, P_l = min(P, S_l), dealt over G = min(max_l blocks_l * P_l,
+ * compute units) resident workgroups (a forced G of xsmm_hip_set_chain_skinny_f32 stays as given). A unit is one workgroup of the split single
+ * call (xsmm_hip_set_skinny_f32_split above): it parks its part's sum in the stream's scratch block and arrives at the block's counter; the
+ * last arriver adds all parts in part order and stores - nobody waits for a part. Every layer has the bits of the same call under
+ * xsmm_hip_set_skinny_f32(BN) + xsmm_hip_set_skinny_f32_split(P). The seam between layers stays one counter and one bounded wait per workgroup.
+ * Where the stream has no scratch block (no memory, a 17th stream) or a layer does not fit it (more than 4096 column blocks, more than
+ * 32 MiB of parts), the launch is the unsplit one on the same G workgroups.
+ * mode 0 = off (default); 1 = the rule (gemm_plan.cpp plan_chain_skinny_f32, fitted to profiles/chain_skinny_f32_split_ab.txt: only what beat
+ * the calls under both single-call f32 skinny switches in every round); 2 .. 16 = that many parts on every chain the other switch takes
+ * (test / measurement switches). Read per invoke; returns the previous mode, -1 (and changes nothing) for any other value. Besides
+ * xsmm_hip_set_chain_skinny_f32's rule no switch reads it, and it reads no other switch.
+ * _stats: out[0] such launches since process start; of the most recent one: [1] parts P, [2] resident workgroups G. Such a launch also
+ * counts in xsmm_hip_chain_skinny_f32_stats, as (G, BN, waves per workgroup - its deepest part's). */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_skinny_f32_split(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_skinny_f32_split_stats(int64_t out[3]);
 /* Halves (on by default; also TPP_HIP_F32_HALVES, read as a number). A whole-layer f32 call on the 64x64 + K2 loader-wave tile runs one
  * workgroup of 8 MFMA waves per tile and CU; every SIMD then holds two MFMA waves that meet the same barrier. With this switch on, every 64x64
  * tile of such a call runs as TWO independent workgroups of 4 MFMA waves, one per 32-column half (64x32, the chunk still split over two

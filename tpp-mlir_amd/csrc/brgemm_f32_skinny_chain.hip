@@ -27,52 +27,14 @@
 // most 512 threads with at most 56 KiB of static LDS fits one to a compute unit, so all G workgroups are resident at once. A workgroup
 // waits only for arrivals at the seam of an EARLIER layer, and makes each of its arrivals unconditionally after work that itself waits
 // only for still earlier seams: by induction over the layers no wait is cyclic. Every spin is bounded.
-#include "brgemm_f32_skinny_tile.h"
-#include "chain_args.h"
+#include "brgemm_f32_skinny_seam.h"
 #include "brgemm_f32_skinny_chain.h"
 
 namespace tpp {
 
 static_assert(SKC_MAXL == CH_MAXL, "the schedule's layer count is the launch's");
 
-typedef __attribute__((address_space(1))) unsigned int skfc_gu32;
-// the argument block, read where it lies (kernarg segment): the layer table is indexed at run time
-typedef const __attribute__((address_space(4))) ChainArgs skfc_kernarg_t;
-
-// the consumer's side of the seam, as the tile's K loop calls it between the B and the A loads of its first ring slots: wave 0 polls,
-// everybody meets the barrier (the file's header). wait = false: a later block of the layer - the seam is open already, no barrier
-struct SkfcSeam {
-  const unsigned *cnt;
-  unsigned *err;
-  unsigned target;
-  int layer, wave, lane;
-  bool wait;
-  __device__ __forceinline__ void operator()() const {
-    if (!wait) return;
-    if (wave == 0) {
-      skfc_gu32 *c = (skfc_gu32 *)cnt;
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      for (;;) {
-        const unsigned v = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((int)(v - target) >= 0) break;
-        if (__builtin_amdgcn_s_memrealtime() - t0 > CHAIN_TIMEOUT_TICKS) { // never hang the GPU: flag it and go on
-          if (lane == 0) __hip_atomic_store((skfc_gu32 *)err, 1u + (unsigned)layer, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // (no instruction: the A loads behind it stay behind the poll)
-  }
-};
-
-// the argument block's address, opaque to the compiler from here on: what is read through the result is loaded HERE, not ahead of the K
-// loop in front - the layer's facts would otherwise all stay in scalar registers across it (brgemm_bf16_skinny_chain.hip skc_args_again)
-__device__ __forceinline__ skfc_kernarg_t *skfc_args_again(skfc_kernarg_t *pp) {
-  asm volatile("" : "+s"(pp));
-  return pp;
-}
+// SkfcSeam, the consumer's side of the seam, and skfc_args_again: brgemm_f32_skinny_seam.h (shared with brgemm_f32_skinny_chain_split.hip)
 
 template <int BN, int MB> __global__ __launch_bounds__(64 * SKF_WMAX) void brgemm_f32_skinny_chain(ChainArgs p_by_value) {
   skfc_kernarg_t *const pp = (skfc_kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr(); // = &p_by_value (the only explicit argument)
@@ -141,19 +103,23 @@ template <int BN> static hipError_t launch_f32_skinny_chain_t(const ChainArgs &a
 // (leading dimensions that cover the layer, leading dimensions and strides in multiples of 4 elements and not negative, a leading
 // dimension of A or C of 2^24 elements or more), a beta 1 or a VNNI flag, a later layer whose batch elements leave the rows of its input,
 // fewer than 2 or more than CH_MAXL layers, G < 1, no counters or no error word.
-hipError_t launch_f32_skinny_chain(int bn, const ChainArgs &a, hipStream_t s) {
-  if (!skf_bn_ok(bn) || !skc_launch_shape_ok(a.nlayers, a.groups) || !a.cnt || !a.err || !a.A || ((uintptr_t)a.A & 15)) return hipErrorInvalidValue;
-  int waves = 1;
+// (the list as a function: launch_f32_skinny_chain_split, brgemm_f32_skinny_chain_split.hip, refuses the same)
+bool f32_skinny_chain_args_ok(int bn, const ChainArgs &a) {
+  if (!skf_bn_ok(bn) || !skc_launch_shape_ok(a.nlayers, a.groups) || !a.cnt || !a.err || !a.A || ((uintptr_t)a.A & 15)) return false;
   for (int l = 0; l < a.nlayers; ++l) {
     const ChainLayer &L = a.L[l];
     const int64_t lda = l == 0 ? a.lda : a.L[l - 1].ldc;
-    if (!skf_shape_ok(a.m, L.pad, L.k, L.br, bn) || !skfc_ld_ok(lda, L.ldb, L.ldc, L.stride_a, L.stride_b, L.pad, L.k)) return hipErrorInvalidValue;
-    if (!(L.ep & EP_BETA0) || (L.ep & EP_VNNI_C) || !L.B || !L.C || (((uintptr_t)L.B | (uintptr_t)L.C) & 15)) return hipErrorInvalidValue;
-    if ((L.ep & EP_BIAS) && (!L.D || ((uintptr_t)L.D & 15))) return hipErrorInvalidValue;
-    if (l > 0 && (int64_t)(L.br - 1) * L.stride_a + L.k > lda) return hipErrorInvalidValue;
-    const int W = skfc_layer_waves(L.br, L.k);
-    if (W > waves) waves = W;
+    if (!skf_shape_ok(a.m, L.pad, L.k, L.br, bn) || !skfc_ld_ok(lda, L.ldb, L.ldc, L.stride_a, L.stride_b, L.pad, L.k)) return false;
+    if (!(L.ep & EP_BETA0) || (L.ep & EP_VNNI_C) || !L.B || !L.C || (((uintptr_t)L.B | (uintptr_t)L.C) & 15)) return false;
+    if ((L.ep & EP_BIAS) && (!L.D || ((uintptr_t)L.D & 15))) return false;
+    if (l > 0 && (int64_t)(L.br - 1) * L.stride_a + L.k > lda) return false;
   }
+  return true;
+}
+hipError_t launch_f32_skinny_chain(int bn, const ChainArgs &a, hipStream_t s) {
+  if (!f32_skinny_chain_args_ok(bn, a)) return hipErrorInvalidValue;
+  int waves = 1;
+  for (int l = 0; l < a.nlayers; ++l) waves = std::max(waves, skfc_layer_waves(a.L[l].br, a.L[l].k));
   return bn == 16 ? launch_f32_skinny_chain_t<16>(a, waves, s) : bn == 32 ? launch_f32_skinny_chain_t<32>(a, waves, s) : launch_f32_skinny_chain_t<64>(a, waves, s);
 }
 

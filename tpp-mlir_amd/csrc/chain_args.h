@@ -43,6 +43,16 @@ struct ChainArgs {
   int pad_items;
 };
 static_assert(offsetof(ChainArgs, L) == 72, "the kernels' code depends on where the layer table lies");
+// The argument block of a K-SPLIT skinny-batch f32 chain (brgemm_f32_skinny_chain_split.hip): ChainArgs and, behind pad_items, what
+// launch_f32_skinny_chain_split fills - the stream's scratch block (split_scratch.h: the parts' partial sums and one arrival counter per
+// column block, shared by every layer of the launch) and the parts P asked for (layer l runs on min(P, its steps) of them). A block of its
+// own: ChainArgs keeps its 664 bytes, so no other kernel's hidden arguments move (twelve instances of brgemm_bf16_lw read one at byte 664).
+struct ChainSplitArgs : ChainArgs {
+  float *split_scratch;
+  unsigned *split_cnt;
+  int split;
+};
+static_assert(sizeof(ChainArgs) == 664, "the kernels that take a ChainArgs read their hidden arguments behind it");
 
 // The bf16 loader-wave launchers (brgemm_bf16_lw.hip). mode: a launch mode of brgemm_bf16_lw_launch.h (BLW_*), whose blw_launch_ok says what each
 // refuses - hipErrorInvalidValue, nothing launched. tile: 0 = 32x64 (K split over two wave groups), 1 = 64x64, 2 = 64x128, 3 = 128x128,
@@ -85,6 +95,13 @@ hipError_t launch_bf16_skinny_chain(int b_kind, int bn, const ChainArgs &a, hipS
 // seam, cnt[l] reaches a.target = epoch * G. Refuses with hipErrorInvalidValue, launching nothing, whatever the kernel does not assume
 // (the list stands at the launcher)
 hipError_t launch_f32_skinny_chain(int bn, const ChainArgs &a, hipStream_t s);
+// the same chain with every layer's K range split over workgroups inside the one launch (brgemm_f32_skinny_chain_split.hip,
+// xsmm_hip_set_chain_skinny_f32_split; schedule in brgemm_f32_skinny_chain_split.h): layer l is blocks_l * min(parts, steps_l) units of work, dealt
+// over the G = a.groups resident workgroups; every layer has the bits of the call under xsmm_hip_set_skinny_f32(bn) +
+// xsmm_hip_set_skinny_f32_split(parts). Refuses with hipErrorInvalidValue, launching nothing, what launch_f32_skinny_chain refuses, parts outside
+// 2 .. 16, a chain none of whose layers has two steps, and a launch the stream's scratch block cannot hold or that has no block (no memory,
+// a 17th stream, a stream being captured) - the caller then runs launch_f32_skinny_chain with the same arguments
+hipError_t launch_f32_skinny_chain_split(int bn, int parts, const ChainArgs &a, hipStream_t s);
 // tile invokes of one bf16 descriptor in one launch (tile 0 = 32x64 + K2, 1 = 64x64, 4 = 32x32 + K2; b_kind 0 VNNI-2 / 4 VNNI-4; a.m x a.n = one item's
 // shape, a.L[0] / a.lda its leading dimensions and strides; every item's batch count >= 1; even_chunks: every item has an even chunk count)
 hipError_t launch_bf16_lw_grouped(int tile, int b_kind, const ChainArgs &a, const void *items, int n_items, bool even_chunks, hipStream_t s);

@@ -12,6 +12,7 @@
 #include "brgemm_f32_skinny_split.h"
 #include "brgemm_bf16_skinny_chain.h"
 #include "brgemm_f32_skinny_chain.h"
+#include "brgemm_f32_skinny_chain_split.h"
 #include <string.h>
 
 namespace tpp {
@@ -1129,7 +1130,41 @@ constexpr int64_t SKINNY_F32_CHAIN_GATE_BYTES = 4 * 784 * 512, SKINNY_F32_CHAIN_
 static int skinny_f32_chain_bn(int64_t m, int64_t most_bytes) {
   return (m <= 16 && most_bytes <= SKINNY_F32_CHAIN_GATE_BYTES) || (m == 1 && most_bytes <= SKINNY_F32_CHAIN_GATE_BYTES_M1) ? 16 : 0;
 }
-ChainSkinnyPlan plan_chain_skinny_f32(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int mode, bool strict) {
+// THE K SPLIT INSIDE THE LAUNCH (xsmm_hip_set_chain_skinny_f32_split, opt-in; brgemm_f32_skinny_chain_split.hip, brgemm_f32_skinny_chain_split.h): the parts
+// P of a chain the rule below has taken on column blocks of bn, or 0: the unsplit launch. Modes 2 .. 16 (tests, measurements): P = the mode,
+// if some layer has two steps and every split layer fits the scratch block's limits (what the launcher would refuse is not planned).
+// Mode 1, THE RULE, is fitted to profiles/chain_skinny_f32_split_ab.txt and to nothing else: it takes exactly the (shape class, BN, P) that beat
+// the parent's calls under both single-call switches in every round; the rows stand in SKINNY_F32_CHAIN_SPLIT_RULE below.
+struct SkinnyF32ChainSplitRow { int64_t m_min, m_max, bytes_min, bytes_max; int bn, parts; };
+// (m from .. to, the largest layer's bytes of B from .. to, BN, P). The profile (one box, 256 CUs, three layers, bias + relu, five alternating
+// rounds, us per step; (a) = the calls under both single-call switches at 1 on the PARENT's library; BN 16 / 32 x P 2 / 4):
+//   4096 -> [4096] * 3 at m 31: (a) 70.90 -> BN 32 P 2 67.86, faster in every round (-4.3 %), the unsplit BN 32 launch 89.46; P 4 81.25, BN 16
+//     98.11 / 112.53. At m 1 / 8 / 16 every (BN, P) loses every round: (a) 43.23 / 45.08 / 46.13 -> BN 32 P 2 52.39 / 53.33 / 54.68 (unsplit 51.24 /
+//     54.91 / 58.82): the split catches up with the unsplit launch from m 8 on, not with the calls.
+//   The funnel 784 -> 512 -> 256 -> 128 at m 1: all four beat (a) 17.45 in every round (BN 16 P 2 15.03, BN 32 P 2 15.59, P 4 17.26 / 16.82) but
+//     the UNSPLIT BN 16 launch, which mode 1 of the other switch takes there, runs 11.61: not taken - it would slow that row down. At m 8 /
+//     16 / 31 every (BN, P) loses every round.
+//   1024 and 1000 wide: every (BN, P) loses every round at every m, by 17 .. 50 % (m 1: 16.77 -> 20.57 .. 24.27; the unsplit launch 14.80).
+// So ONE row: m = 31 with a largest layer of 64 MiB, on BN 32 with P 2. Everything else is the unsplit rule's answer. Not measured: m 17 ..
+// 30, layers between 4 and 64 MiB or beyond, P 3 and P > 4, BN 64, other CU counts, several ranks.
+constexpr SkinnyF32ChainSplitRow SKINNY_F32_CHAIN_SPLIT_RULE[] = {{31, 31, 4LL * 4096 * 4096, 4LL * 4096 * 4096, 32, 2}};
+// the row of the rule for a chain of m rows whose largest layer has most_bytes of B (and, bn != 0, on that column block), or nullptr
+static const SkinnyF32ChainSplitRow *skinny_f32_chain_split_row(int64_t m, int64_t most_bytes, int bn) {
+  for (const SkinnyF32ChainSplitRow &r : SKINNY_F32_CHAIN_SPLIT_RULE)
+    if (m >= r.m_min && m <= r.m_max && most_bytes >= r.bytes_min && most_bytes <= r.bytes_max && (bn == 0 || bn == r.bn)) return &r;
+  return nullptr;
+}
+// P if some layer has two steps and every split layer fits the scratch block's limits, else 0
+static int skinny_f32_chain_split_parts(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int bn, int P) {
+  if (!skfcs_parts_ok(P)) return 0;
+  bool any = false;
+  for (int l = 0; l < nlayers; ++l) {
+    if (!skfcs_layer_fits((int)n[l], bn, skf_mb((int)m), P, br[l], (int)k[l], SKFCS_MAX_TILES, SKFS_PMAX, SKFCS_MAX_FLOATS)) return 0;
+    any = any || skfcs_layer_parts(P, br[l], (int)k[l]) >= 2;
+  }
+  return any ? P : 0;
+}
+ChainSkinnyPlan plan_chain_skinny_f32(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int mode, bool strict, int split) {
   auto no = [](const char *why) { return ChainSkinnyPlan{0, 0, why, false}; };
   const int forced_bn = mode >= 1000 ? mode % 1000 : mode == 1 ? 0 : mode, forced_g = chain_skinny_mode_forced_g(mode) ? mode / 1000 : 0;
   if (mode != 1 && !(skf_bn_ok(forced_bn) && (!chain_skinny_mode_forced_g(mode) || (forced_g >= 1 && forced_g <= SKC_GMAX))))
@@ -1145,16 +1180,24 @@ ChainSkinnyPlan plan_chain_skinny_f32(int64_t m, int nlayers, const int64_t *n, 
     if (n[l] < narrowest) narrowest = n[l];
     if (4 * br[l] * k[l] * n[l] > most_bytes) most_bytes = 4 * br[l] * k[l] * n[l];
   }
-  const int bn = mode == 1 ? skinny_f32_chain_bn(m, most_bytes) : forced_bn;
+  // the split's rule (split 1) names BN and P together where mode 1 leaves BN open, P alone under a forced BN; a forced P refines whatever BN
+  // the unsplit rule has (none where it gates)
+  const SkinnyF32ChainSplitRow *const row = split == 1 ? skinny_f32_chain_split_row(m, most_bytes, mode == 1 ? 0 : forced_bn) : nullptr;
+  const int bn = mode != 1 ? forced_bn : row && narrowest >= row->bn ? row->bn : skinny_f32_chain_bn(m, most_bytes);
   if (narrowest < (bn ? bn : 16)) return no("a layer is narrower than the column block");
-  int max_blocks = 0;
-  for (int l = 0; l < nlayers; ++l)
-    if (skf_blocks((int)n[l], bn ? bn : 16) > max_blocks) max_blocks = skf_blocks((int)n[l], bn ? bn : 16);
+  const int parts = bn == 0 || split == 0 ? 0 : skinny_f32_chain_split_parts(m, nlayers, n, k, br, bn, split == 1 ? (row && row->bn == bn ? row->parts : 0) : split);
+  int64_t most_units = 0; // (unsplit: the most column blocks of a layer)
+  for (int l = 0; l < nlayers; ++l) {
+    const int64_t units = parts ? skfcs_units((int)n[l], bn, parts, br[l], (int)k[l]) : skf_blocks((int)n[l], bn ? bn : 16);
+    if (units > most_units) most_units = units;
+  }
   if (cus < 1) return no("the stream's compute units are unknown");
   if (forced_g > cus) return no("more resident workgroups forced than compute units");
-  const int groups = forced_g ? forced_g : skc_groups(max_blocks, cus);
+  const int groups = forced_g ? forced_g : skfcs_groups(most_units, cus);
   if (bn == 0) return ChainSkinnyPlan{16, groups, SKINNY_F32_CHAIN_GATE_WHY, true};
-  return ChainSkinnyPlan{bn, groups, "", false};
+  ChainSkinnyPlan taken{bn, groups, "", false};
+  taken.parts = parts;
+  return taken;
 }
 
 // ---- plan_chain: the layer-chain launch decision (gemm_plan.h has the order of precedence) ---------------------------------------
@@ -1238,9 +1281,9 @@ ChainLaunchPlan plan_chain(int n, const GemmDesc *const *d, const int64_t *br, c
       bool ok = true;
       for (int i = 0; i < n && ok; ++i) ok = chain_skinny_f32_ok(*d[i], &w);
       if (ok) {
-        const ChainSkinnyPlan sp = plan_chain_skinny_f32(m, n, ns, ks, br, cus.get(), env.skinny_f32, env.strict);
+        const ChainSkinnyPlan sp = plan_chain_skinny_f32(m, n, ns, ks, br, cus.get(), env.skinny_f32, env.strict, env.skinny_f32_split);
         if (sp.bn > 0 && !sp.gated) { // (gated: the rule's answer is on record in why, nothing is launched)
-          p.form = CF_SKINNY_F32, p.tile = sp.bn, p.b_kind = 0, p.groups = sp.groups, p.why = "";
+          p.form = CF_SKINNY_F32, p.tile = sp.bn, p.b_kind = 0, p.groups = sp.groups, p.parts = sp.parts, p.why = "";
           p.bm = (int)m, p.bn = sp.bn, p.tiles_m = skc_key_tiles_m(), p.tiles_n = skc_key_tiles_n(sp.groups), p.mixed = false;
           p.args_n = (int)ns[0];
           for (int l = 1; l < n; ++l)

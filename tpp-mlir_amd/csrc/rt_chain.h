@@ -296,11 +296,19 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     HIP_OK(launch_bf16_skinny_chain(b_kind, tile, c, s)); counted = tpp::MS_CHAIN_SKINNY;
     word[0] = plan.groups, word[1] = tile, word[2] = b_kind;
     break;
-  case CF_SKINNY_F32: // resident workgroups G, BN (the plan's tile), the waves of the launch (its deepest layer's); key (1, G), target = epoch * G
-    HIP_OK(launch_f32_skinny_chain(tile, c, s)); counted = tpp::MS_CHAIN_SKINNY_F32;
+  case CF_SKINNY_F32: { // resident workgroups G, BN (the plan's tile), the waves of the launch (its deepest layer's); key (1, G), target = epoch * G
+    // with parts (xsmm_hip_set_chain_skinny_f32_split): the K-split launch first - its own counters then hold (P, G) - and, where its launcher
+    // refuses (no scratch block for this stream, or one too small), the unsplit launch on the same G workgroups
+    const hipError_t e = plan.parts >= 2 ? launch_f32_skinny_chain_split(tile, plan.parts, c, s) : hipErrorInvalidValue;
+    if (e != hipErrorInvalidValue) HIP_OK(e);
+    else HIP_OK(launch_f32_skinny_chain(tile, c, s));
+    counted = tpp::MS_CHAIN_SKINNY_F32;
     word[0] = plan.groups, word[1] = tile, word[2] = 1;
-    for (int i = 0; i < n; ++i) word[2] = std::max<int64_t>(word[2], skfc_layer_waves(br[i], (int)d[i]->k));
+    for (int i = 0; i < n; ++i)
+      word[2] = std::max<int64_t>(word[2], e == hipSuccess ? skfcs_layer_waves(plan.parts, br[i], (int)d[i]->k) : skfc_layer_waves(br[i], (int)d[i]->k));
+    if (e == hipSuccess) tpp::count_mode_launch(tpp::MS_CHAIN_SKINNY_F32_SPLIT, {plan.parts, plan.groups});
     break;
+  }
   default: return false; // (CF_CALLS has returned above)
   }
   if (counted != tpp::MS_COUNT) tpp::count_mode_launch(counted, {word[0], word[1], word[2]});

@@ -15,6 +15,7 @@
 #include "chain_args.h"
 #include "brgemm_bf16_dma256_chain.h" // D256C_BM, chain_rounds_rounds (rt_chain.h)
 #include "brgemm_f32_skinny_chain.h"  // skfc_layer_waves (rt_chain.h: the counter words of a skinny-batch f32 chain launch)
+#include "brgemm_f32_skinny_chain_split.h" // skfcs_layer_waves (the same of its K-split form)
 #include "gemm_plan.h"
 #include "mode_switches.h"
 #include "host_cache.h"
@@ -66,6 +67,7 @@ __attribute__((weak)) hipError_t launch_bf16_chain_wragged(int, int, const Chain
 __attribute__((weak)) hipError_t launch_bf16_dma256_chain(int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 __attribute__((weak)) hipError_t launch_bf16_skinny_chain(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 __attribute__((weak)) hipError_t launch_f32_skinny_chain(int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
+__attribute__((weak)) hipError_t launch_f32_skinny_chain_split(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 } // namespace tpp
 
 namespace {
@@ -580,6 +582,7 @@ MODE_SWITCH_ABI(chain_skinny, MS_CHAIN_SKINNY)
 MODE_SWITCH_ABI(skinny_f32, MS_SKINNY_F32)
 MODE_SWITCH_ABI(skinny_f32_split, MS_SKINNY_F32_SPLIT)
 MODE_SWITCH_ABI(chain_skinny_f32, MS_CHAIN_SKINNY_F32)
+MODE_SWITCH_ABI(chain_skinny_f32_split, MS_CHAIN_SKINNY_F32_SPLIT)
 #undef MODE_SWITCH_ABI
 // the VNNI blocking factor of bf16 B operands dispatched from now on (2 or 4); returns the previous one, -1 for an invalid factor
 extern "C" int xsmm_hip_set_vnni_factor(int v) {

@@ -197,6 +197,12 @@ _MODE_SWITCHES = {
         gain), 16 / 32 / 64 that column-block width wherever eligible, 1000 * G + BN that width on G resident workgroups; returns the
         previous mode, -1 for a value it refuses""",
         """(skinny-batch f32 chain launches; resident workgroups G, BN, waves per workgroup of the most recent one)"""),
+    "chain_skinny_f32_split": (3,
+        """the K range of every layer of a skinny-batch f32 chain launch (set_chain_skinny_f32) over several workgroups per column block,
+        inside the one launch (the bits of the calls under set_skinny_f32(BN) + set_skinny_f32_split(P)): 0 off (default), 1 the rule (as
+        measured), 2 .. 16 that many parts wherever eligible; changes nothing while set_chain_skinny_f32 is 0; returns the previous mode,
+        -1 for a value it refuses""",
+        """(skinny-batch f32 chain launches that ran K-split; parts P, resident workgroups G of the most recent one)"""),
     "f32_halves": (4,
         """f32 whole-layer calls on the 64x64 + K2 tile as two 64x32 + K2 workgroups per tile (the same bits): 0 off, 1 the rule
         (default: at least one tile per compute unit), 2 wherever eligible; returns the previous mode, -1 for a value it refuses""",
