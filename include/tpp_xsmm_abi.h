@@ -622,6 +622,26 @@ TPP_XSMM_EXPORT void xsmm_hip_chain_dma256_stats(int64_t out[4]);
  * VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches, xsmm_hip_skinny_bf16_stats among them, do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_chain_skinny(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_chain_skinny_stats(int64_t out[4]);
+/* The K split INSIDE a skinny-batch bf16 chain launch (opt-in; also TPP_HIP_CHAIN_SKINNY_SPLIT, read as a number; a refused value leaves 0): a
+ * refinement of xsmm_hip_set_chain_skinny, read only for a chain that switch has taken - with that switch at 0 it changes nothing. The unsplit
+ * chain launch has at most one workgroup per column block of its widest layer, each streaming its whole K range alone. With P parts the
+ * launch is brgemm_bf16_skinny_chain_split<IMG, BN, MB> (brgemm_bf16_skinny_chain_split.hip; schedule in brgemm_bf16_skinny_chain_split.h): layer l
+ * with S_l = br_l * ceil(k_l / 32) steps is blocks_l * P_l units of work, P_l = min(P, S_l), dealt over G = min(max_l blocks_l * P_l, compute
+ * units) resident workgroups (a forced G of xsmm_hip_set_chain_skinny stays as given). A unit is one workgroup of the split single call
+ * (xsmm_hip_set_skinny_split): it parks its part's f32 sum in the stream's scratch block and arrives at the block's counter; the last
+ * arriver adds all parts in part order, rounds ONCE to bf16 and stores - nobody waits for a part. Every layer has the bits of the same call
+ * under xsmm_hip_set_skinny_bf16(BN) + xsmm_hip_set_skinny_split(P). The seam between layers stays one counter and one bounded wait per
+ * workgroup. Where the stream has no scratch block (no memory, a 17th stream) or a layer does not fit it (more than 4096 column blocks, more
+ * than 32 MiB of parts), the launch is the unsplit one on the same G workgroups.
+ * mode 0 = off (default); 1 = the rule (gemm_plan.cpp plan_chain_skinny, fitted to profiles/chain_skinny_split_ab.txt: only what beat the calls
+ * under both single-call skinny switches in every round - it may take a chain that the 2 MiB gate of xsmm_hip_set_chain_skinny(1) holds
+ * back); 2 .. 16 = that many parts on every chain the other switch takes (test / measurement switches; they lift no gate). Read per invoke;
+ * returns the previous mode, -1 (and changes nothing) for any other value. Besides xsmm_hip_set_chain_skinny's rule no switch reads it, and
+ * it reads no other switch.
+ * _stats: out[0] such launches since process start; of the most recent one: [1] parts P, [2] resident workgroups G. Such a launch also
+ * counts in xsmm_hip_chain_skinny_stats, as (G, BN, B image). */
+TPP_XSMM_EXPORT int xsmm_hip_set_chain_skinny_split(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_chain_skinny_split_stats(int64_t out[3]);
 /* Skinny-batch f32 layers (opt-in; also TPP_HIP_SKINNY_F32, read as a number; a refused value leaves 0). An f32 call with fewer than 32
  * rows runs on the generic kernel: one workgroup of four waves per 32x32 output tile, both operands staged through LDS, 32 - m of the
  * tile's rows idle. With this switch on, the call runs on ceil(n / BN) workgroups of brgemm_f32_skinny<BN, MB> (brgemm_f32_skinny.hip;

@@ -43,8 +43,8 @@ struct ChainArgs {
   int pad_items;
 };
 static_assert(offsetof(ChainArgs, L) == 72, "the kernels' code depends on where the layer table lies");
-// The argument block of a K-SPLIT skinny-batch f32 chain (brgemm_f32_skinny_chain_split.hip): ChainArgs and, behind pad_items, what
-// launch_f32_skinny_chain_split fills - the stream's scratch block (split_scratch.h: the parts' partial sums and one arrival counter per
+// The argument block of a K-SPLIT skinny-batch chain (brgemm_f32_skinny_chain_split.hip, brgemm_bf16_skinny_chain_split.hip): ChainArgs and,
+// behind pad_items, what launch_f32_skinny_chain_split / launch_bf16_skinny_chain_split fills - the stream's scratch block (split_scratch.h: the parts' partial sums and one arrival counter per
 // column block, shared by every layer of the launch) and the parts P asked for (layer l runs on min(P, its steps) of them). A block of its
 // own: ChainArgs keeps its 664 bytes, so no other kernel's hidden arguments move (twelve instances of brgemm_bf16_lw read one at byte 664).
 struct ChainSplitArgs : ChainArgs {
@@ -89,6 +89,13 @@ hipError_t launch_bf16_dma256_chain(int b_kind, const ChainArgs &a, hipStream_t 
 // guarantee; ONE counter per seam, cnt[l] reaches a.target = epoch * G. Refuses with hipErrorInvalidValue, launching nothing, whatever
 // the kernel does not assume (the list stands at the launcher)
 hipError_t launch_bf16_skinny_chain(int b_kind, int bn, const ChainArgs &a, hipStream_t s);
+// the same chain with every layer's K range split over workgroups inside the one launch (brgemm_bf16_skinny_chain_split.hip,
+// xsmm_hip_set_chain_skinny_split; schedule in brgemm_bf16_skinny_chain_split.h): layer l is blocks_l * min(parts, steps_l) units of work, dealt
+// over the G = a.groups resident workgroups; every layer has the bits of the call under xsmm_hip_set_skinny_bf16(bn) +
+// xsmm_hip_set_skinny_split(parts). Refuses with hipErrorInvalidValue, launching nothing, what launch_bf16_skinny_chain refuses, parts outside
+// 2 .. 16, a chain none of whose layers has two steps, and a launch the stream's scratch block cannot hold or that has no block (no memory,
+// a 17th stream, a stream being captured) - the caller then runs launch_bf16_skinny_chain with the same arguments
+hipError_t launch_bf16_skinny_chain_split(int b_kind, int bn, int parts, const ChainArgs &a, hipStream_t s);
 // a chain of SKINNY-BATCH f32 layers (brgemm_f32_skinny_chain.hip, xsmm_hip_set_chain_skinny_f32; schedule in brgemm_f32_skinny_chain.h): 1 <= m
 // <= 31 rows, layer l of a.L[l].pad columns (n >= bn, n % 4 == 0) and k(l) >= 4 in multiples of 4, flat B, beta 0, on column blocks of bn =
 // 16 / 32 / 64; a.groups = G resident workgroups, the grid, at most the stream's compute units - the caller's guarantee; ONE counter per

@@ -13,6 +13,7 @@
 #include "brgemm_bf16_skinny_chain.h"
 #include "brgemm_f32_skinny_chain.h"
 #include "brgemm_f32_skinny_chain_split.h"
+#include "brgemm_bf16_skinny_chain_split.h"
 #include <string.h>
 
 namespace tpp {
@@ -1060,7 +1061,42 @@ int chain_skinny_b_kind(const GemmDesc &d, const char **why) {
 // Not measured: other CU counts (the rule reads them through G alone), several ranks, beta 1 (not a chain), layers between 2 and 32 MiB,
 // small flat and VNNI-4 chains, the launch without the weights ahead of the wait (not built).
 constexpr int64_t SKINNY_CHAIN_GATE_BYTES = 2 << 20; // mode 1: the most bytes of B a layer of a taken chain has
-ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int b_kind, int mode, bool strict) {
+// THE K SPLIT INSIDE THE LAUNCH (xsmm_hip_set_chain_skinny_split, opt-in; brgemm_bf16_skinny_chain_split.hip, brgemm_bf16_skinny_chain_split.h): the parts P
+// of a chain the rule below has taken on column blocks of bn, or 0: the unsplit launch. Modes 2 .. 16 (tests, measurements): P = the mode, if
+// some layer has two steps and every split layer fits the scratch block's limits (what the launcher would refuse is not planned).
+// Mode 1, THE RULE, is fitted to profiles/chain_skinny_split_ab.txt and to nothing else: it takes exactly the (shape class, image, BN, P) that
+// beat the parent's calls under both single-call switches in every round; the rows stand in SKINNY_CHAIN_SPLIT_RULE below.
+struct SkinnyChainSplitRow { int64_t m_min, m_max, bytes_min, bytes_max; int b_kind, bn, parts; };
+// (m from .. to, the largest layer's bytes of B from .. to, the B image, BN, P). The profile (one box, 256 CUs, three layers, bias + relu, five
+// alternating rounds, us per step; (a) = the calls under both single-call switches at 1 on the PARENT's library; every BN with an instance x
+// P 2 / 4 / 8, m 1 / 8 / 16 / 31):
+//   4096 -> [4096] * 3, VNNI-2, m 1 / 31: (a) 27.26 / 37.48 -> the best split, BN 32 P 2, 30.21 / 43.48 (+10.8 / +16.0 %); the unsplit BN 32
+//     launch 31.96 / 45.09. Flat, VNNI-4 and 4096 -> 4096 -> 11008 -> 4096 (m 31: 61.93 -> BN 64 P 4 66.81, unsplit 76.66) the same:
+//     the split closes a third to two thirds of the unsplit launch's gap and wins NO round of any large row.
+//   1024- and 1000-wide: no (BN, P) wins every round; the unsplit BN 16 launch, which mode 1 of the other switch takes, gains 22 .. 33 %.
+//   The funnel 784 -> 512 -> 256 -> 128: BN 16 / 32 / 64 with P 2 / 4 beat (a) in every round (m 1: 16.74 -> BN 16 P 2 13.11) but lose to the
+//     UNSPLIT BN 16 launch (10.68) that mode 1 of the other switch takes there: taking them would slow those rows down.
+// So THE TABLE IS EMPTY: no measured row is faster split than what the switches give without it. Mode 1 takes nothing (parts 0), and every
+// answer under it is the unsplit rule's; the forced modes stay. Not measured: P 3 and beyond 8, layers between 2 and 32 MiB, small flat
+// and VNNI-4 chains, other CU counts, several ranks. (One never-matching row: C++ has no array of zero elements.)
+constexpr SkinnyChainSplitRow SKINNY_CHAIN_SPLIT_RULE[] = {{1, 0, 0, 0, 0, 0, 0}};
+// the row of the rule for a chain of m rows and image b_kind whose largest layer has most_bytes of B (and, bn != 0, on that column block), or nullptr
+static const SkinnyChainSplitRow *skinny_chain_split_row(int64_t m, int64_t most_bytes, int b_kind, int bn) {
+  for (const SkinnyChainSplitRow &r : SKINNY_CHAIN_SPLIT_RULE)
+    if (m >= r.m_min && m <= r.m_max && most_bytes >= r.bytes_min && most_bytes <= r.bytes_max && b_kind == r.b_kind && (bn == 0 || bn == r.bn)) return &r;
+  return nullptr;
+}
+// P if some layer has two steps and every split layer fits the scratch block's limits, else 0
+static int skinny_chain_split_parts(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int bn, int P) {
+  if (!skcs_parts_ok(P)) return 0;
+  bool any = false;
+  for (int l = 0; l < nlayers; ++l) {
+    if (!skcs_layer_fits((int)n[l], bn, skn_mb((int)m), P, br[l], (int)k[l], SKCS_MAX_TILES, SKS_PMAX, SKCS_MAX_FLOATS)) return 0;
+    any = any || skcs_layer_parts(P, br[l], (int)k[l]) >= 2;
+  }
+  return any ? P : 0;
+}
+ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int b_kind, int mode, bool strict, int split) {
   auto no = [](const char *why) { return ChainSkinnyPlan{0, 0, why, false}; };
   const int forced_bn = mode >= 1000 ? mode % 1000 : mode == 1 ? 0 : mode, forced_g = chain_skinny_mode_forced_g(mode) ? mode / 1000 : 0;
   if (mode != 1 && !(skn_bn_ok(forced_bn) && (!chain_skinny_mode_forced_g(mode) || (forced_g >= 1 && forced_g <= SKC_GMAX))))
@@ -1077,21 +1113,30 @@ ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, cons
     if (n[l] < narrowest) narrowest = n[l];
     if (2 * br[l] * k[l] * n[l] > most_bytes) most_bytes = 2 * br[l] * k[l] * n[l];
   }
+  // the split's rule (split 1) names BN and P together where mode 1 leaves BN open, P alone under a forced BN; a forced P refines whatever BN
+  // the unsplit rule has and lifts none of its gates
+  const SkinnyChainSplitRow *const row = split == 1 ? skinny_chain_split_row(m, most_bytes, b_kind, mode == 1 ? 0 : forced_bn) : nullptr;
   int bn = forced_bn;
-  if (mode == 1) bn = b_kind == 2 ? 32 : 16; // the smallest with an instance
+  if (mode == 1) bn = row && narrowest >= row->bn ? row->bn : b_kind == 2 ? 32 : 16; // (the unsplit rule: the smallest with an instance)
   if (!skn_instance_exists(b_kind, bn)) return no("no instance of this B image on this column-block width (flat B on 16)");
   if (narrowest < bn) return no("a layer is narrower than the column block");
-  int max_blocks = 0;
-  for (int l = 0; l < nlayers; ++l)
-    if (skn_blocks((int)n[l], bn) > max_blocks) max_blocks = skn_blocks((int)n[l], bn);
+  const int parts = split == 0 ? 0 : skinny_chain_split_parts(m, nlayers, n, k, br, bn, split == 1 ? (row && row->bn == bn ? row->parts : 0) : split);
+  int64_t most_units = 0; // (unsplit: the most column blocks of a layer)
+  for (int l = 0; l < nlayers; ++l) {
+    const int64_t units = parts ? skcs_units((int)n[l], bn, parts, br[l], (int)k[l]) : skn_blocks((int)n[l], bn);
+    if (units > most_units) most_units = units;
+  }
   if (cus < 1) return no("the stream's compute units are unknown");
   if (forced_g > cus) return no("more resident workgroups forced than compute units");
-  const int groups = forced_g ? forced_g : skc_groups(max_blocks, cus);
-  if (mode == 1 && b_kind != 0)
+  const int groups = forced_g ? forced_g : skcs_groups(most_units, cus);
+  const bool by_row = split == 1 && parts != 0; // a measured row of the split's rule: the two gates below held back what it measured faster
+  if (mode == 1 && b_kind != 0 && !by_row)
     return ChainSkinnyPlan{bn, groups, "gate: no measured chain with a flat or a VNNI-4 B gained as one launch (profiles/chain_skinny_ab.txt)", true};
-  if (mode == 1 && most_bytes > SKINNY_CHAIN_GATE_BYTES)
+  if (mode == 1 && most_bytes > SKINNY_CHAIN_GATE_BYTES && !by_row)
     return ChainSkinnyPlan{bn, groups, "gate: a layer with more than 2 MiB of B measured slower as one launch than call by call on the split skinny kernel (profiles/chain_skinny_ab.txt)", true};
-  return ChainSkinnyPlan{bn, groups, "", false};
+  ChainSkinnyPlan taken{bn, groups, "", false};
+  taken.parts = parts;
+  return taken;
 }
 
 // SKINNY-BATCH f32 LAYER CHAINS (xsmm_hip_set_chain_skinny_f32, opt-in; brgemm_f32_skinny_chain.hip, brgemm_f32_skinny_chain.h; gemm_plan.h has the contract).
@@ -1257,9 +1302,9 @@ ChainLaunchPlan plan_chain(int n, const GemmDesc *const *d, const int64_t *br, c
         else if (kind_i != kind) kind = -1, w = "the calls' B operands differ in kind (VNNI-2 / flat / VNNI-4)";
       }
       if (kind >= 0) {
-        const ChainSkinnyPlan sp = plan_chain_skinny(m, n, ns, ks, br, cus.get(), kind, env.skinny, env.strict);
+        const ChainSkinnyPlan sp = plan_chain_skinny(m, n, ns, ks, br, cus.get(), kind, env.skinny, env.strict, env.skinny_split);
         if (sp.bn > 0 && !sp.gated) { // (gated: the rule's answer is on record in why, nothing is launched)
-          p.form = CF_SKINNY, p.tile = sp.bn, p.b_kind = kind, p.groups = sp.groups, p.why = "";
+          p.form = CF_SKINNY, p.tile = sp.bn, p.b_kind = kind, p.groups = sp.groups, p.parts = sp.parts, p.why = "";
           p.bm = (int)m, p.bn = sp.bn, p.tiles_m = skc_key_tiles_m(), p.tiles_n = skc_key_tiles_n(sp.groups), p.mixed = false;
           p.args_n = (int)ns[0];
           for (int l = 1; l < n; ++l)

@@ -341,9 +341,15 @@ int chain_skinny_b_kind(const GemmDesc &d, const char **why);
 // with a flat or a VNNI-4 B - none of whose measured rows gained -, stays call by call; the rows and what was not measured stand at the
 // rule in gemm_plan.cpp. The answer then names the plan with gated = true and why = the gate, and the caller does not launch. Forced
 // modes are never gated. There is no m >= 17 gate: m = 31 gained in every round wherever m <= 16 did.
-struct ChainSkinnyPlan { int bn; int groups; const char *why; bool gated; int parts = 0; /* plan_chain_skinny_f32 with a K split: P, 2 .. 16; 0: unsplit */ };
+// THE K SPLIT INSIDE THE LAUNCH, split = xsmm_hip_set_chain_skinny_split's value (brgemm_bf16_skinny_chain_split.hip, schedule in
+// brgemm_bf16_skinny_chain_split.h), is a REFINEMENT read here and nowhere else: only for a chain this rule has in hand, so with mode 0 it
+// changes nothing, and with split 0 every answer is what it was. 2 .. 16: parts = that P wherever a layer has at least two steps (layer l
+// then runs on sks_parts(P, S_l) parts per column block, every layer with the bits of the call under xsmm_hip_set_skinny_bf16(BN) +
+// xsmm_hip_set_skinny_split(P)), and G = min(max_l blocks_l * P_l, cus) - a forced G stays as given. 1: the rule, as measured - see
+// gemm_plan.cpp. Strict mode and every other refusal are the unsplit rule's; a forced P lifts the gate of mode 1 for no chain.
+struct ChainSkinnyPlan { int bn; int groups; const char *why; bool gated; int parts = 0; /* with a K split inside the launch: P, 2 .. 16; 0: unsplit */ };
 inline bool chain_skinny_mode_forced_g(int mode) { return mode >= 1000; }
-ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int b_kind, int mode, bool strict);
+ChainSkinnyPlan plan_chain_skinny(int64_t m, int nlayers, const int64_t *n, const int64_t *k, const int64_t *br, int64_t cus, int b_kind, int mode, bool strict, int split = 0);
 // SKINNY-BATCH f32 LAYER CHAINS (xsmm_hip_set_chain_skinny_f32; plan_chain, brgemm_f32_skinny_chain.hip launch_f32_skinny_chain, schedule in
 // brgemm_f32_skinny_chain.h). Host-only, no HIP calls.
 // One call of a chain: true if it can be a layer of this launch - f32, a flat B (no VNNI, not transposed), beta 0, no VNNI C, no forced
@@ -391,7 +397,7 @@ constexpr int CHAIN_PLAN_MAXL = 8; // (= CH_MAXL, chain_args.h)
 enum ChainForm : int { CF_CALLS, CF_F32, CF_PLAIN, CF_EDGE, CF_ROUNDS, CF_RAGGED, CF_WIDTHS, CF_WROUNDS, CF_WRAGGED, CF_DMA256, CF_SKINNY, CF_SKINNY_F32, CF_FORMS };
 // xsmm_hip_set_strict, the seven chain switches of the tiles (xsmm_hip_set_chain_*), xsmm_hip_set_edge_tiles and xsmm_hip_set_dma256_images, and
 // xsmm_hip_set_chain_skinny; mode_switches.h chain_plan_env_of fills it per invoke (rt_core.h chain_plan_env)
-struct ChainPlanEnv { bool strict; int edge, rounds, ragged, widths, width_rounds, widths_ragged, dma256; int edge_tiles, dma256_images; int skinny = 0; int skinny_f32 = 0; /* xsmm_hip_set_chain_skinny_f32 */ int skinny_f32_split = 0; /* xsmm_hip_set_chain_skinny_f32_split */ };
+struct ChainPlanEnv { bool strict; int edge, rounds, ragged, widths, width_rounds, widths_ragged, dma256; int edge_tiles, dma256_images; int skinny = 0; int skinny_f32 = 0; /* xsmm_hip_set_chain_skinny_f32 */ int skinny_f32_split = 0; /* xsmm_hip_set_chain_skinny_f32_split */ int skinny_split = 0; /* xsmm_hip_set_chain_skinny_split */ };
 // The compute units a launch on the invoke's stream can use - the one input that costs runtime calls (rt_chain.h stream_cus: three). Asked
 // lazily and at most once per invoke: a decision that ends in front of every rule that reads them never pays for them.
 struct ChainCus {
@@ -418,8 +424,9 @@ struct ChainLaunchPlan {
   // rules that were asked in front of the answer and refused: "no <rule> (<why>)" under TPP_HIP_TRACE
   struct Note { const char *rule, *why; } notes[4];
   int n_notes;
-  int parts;          // CF_SKINNY_F32 with a K split inside the launch (xsmm_hip_set_chain_skinny_f32_split): the parts P, 2 .. 16 -
-                      // launch_f32_skinny_chain_split first, on its refusal the unsplit launch; 0: unsplit
+  int parts;          // CF_SKINNY_F32 / CF_SKINNY with a K split inside the launch (xsmm_hip_set_chain_skinny_f32_split /
+                      // xsmm_hip_set_chain_skinny_split): the parts P, 2 .. 16 - the form's split launcher first, on its refusal the
+                      // unsplit launch; 0: unsplit
 };
 ChainLaunchPlan plan_chain(int n, const GemmDesc *const *d, const int64_t *br, const ChainPlanEnv &env, ChainCus &cus);
 // 1 / 2 = the f32 chain tile (brgemm_f32_lw.hip launch_f32_chain) the descriptor was planned on, -1 = none

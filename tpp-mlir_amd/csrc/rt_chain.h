@@ -292,10 +292,18 @@ bool try_chain_launch(int n, const GemmDesc *const *d, void *const *pa, void *co
     HIP_OK(launch_bf16_dma256_chain(b_kind, c, s)); counted = tpp::MS_CHAIN_DMA256;
     word[0] = plan.groups, word[1] = chain_rounds_rounds(plan.tiles_m, plan.groups), word[2] = b_kind;
     break;
-  case CF_SKINNY: // resident workgroups G, the column-block width BN (the plan's tile), the B image; the block's key is (1, G): target = epoch * G
-    HIP_OK(launch_bf16_skinny_chain(b_kind, tile, c, s)); counted = tpp::MS_CHAIN_SKINNY;
+  case CF_SKINNY: { // resident workgroups G, the column-block width BN (the plan's tile), the B image; the block's key is (1, G): target = epoch * G
+    // with parts (xsmm_hip_set_chain_skinny_split): the K-split launch first - its own counters then hold (P, G) - and, where its launcher
+    // refuses (no scratch block for this stream, or one too small), the unsplit launch with the same arguments on the same G workgroups:
+    // those beyond a layer's blocks sit it out, key and target are taken already
+    const hipError_t e = plan.parts >= 2 ? launch_bf16_skinny_chain_split(b_kind, tile, plan.parts, c, s) : hipErrorInvalidValue;
+    if (e != hipErrorInvalidValue) HIP_OK(e);
+    else HIP_OK(launch_bf16_skinny_chain(b_kind, tile, c, s));
+    counted = tpp::MS_CHAIN_SKINNY;
     word[0] = plan.groups, word[1] = tile, word[2] = b_kind;
+    if (e == hipSuccess) tpp::count_mode_launch(tpp::MS_CHAIN_SKINNY_SPLIT, {plan.parts, plan.groups});
     break;
+  }
   case CF_SKINNY_F32: { // resident workgroups G, BN (the plan's tile), the waves of the launch (its deepest layer's); key (1, G), target = epoch * G
     // with parts (xsmm_hip_set_chain_skinny_f32_split): the K-split launch first - its own counters then hold (P, G) - and, where its launcher
     // refuses (no scratch block for this stream, or one too small), the unsplit launch on the same G workgroups

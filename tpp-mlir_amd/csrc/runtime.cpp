@@ -68,6 +68,7 @@ __attribute__((weak)) hipError_t launch_bf16_dma256_chain(int, const ChainArgs &
 __attribute__((weak)) hipError_t launch_bf16_skinny_chain(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 __attribute__((weak)) hipError_t launch_f32_skinny_chain(int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 __attribute__((weak)) hipError_t launch_f32_skinny_chain_split(int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
+__attribute__((weak)) hipError_t launch_bf16_skinny_chain_split(int, int, int, const ChainArgs &, hipStream_t) { return hipErrorNotSupported; }
 } // namespace tpp
 
 namespace {
@@ -583,6 +584,7 @@ MODE_SWITCH_ABI(skinny_f32, MS_SKINNY_F32)
 MODE_SWITCH_ABI(skinny_f32_split, MS_SKINNY_F32_SPLIT)
 MODE_SWITCH_ABI(chain_skinny_f32, MS_CHAIN_SKINNY_F32)
 MODE_SWITCH_ABI(chain_skinny_f32_split, MS_CHAIN_SKINNY_F32_SPLIT)
+MODE_SWITCH_ABI(chain_skinny_split, MS_CHAIN_SKINNY_SPLIT)
 #undef MODE_SWITCH_ABI
 // the VNNI blocking factor of bf16 B operands dispatched from now on (2 or 4); returns the previous one, -1 for an invalid factor
 extern "C" int xsmm_hip_set_vnni_factor(int v) {

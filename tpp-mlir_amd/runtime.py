@@ -191,6 +191,12 @@ _MODE_SWITCHES = {
         set_skinny_bf16(BN)): 0 off (default), 1 the rule (VNNI-2 chains whose layers have at most 2 MiB of B, on BN 16: as measured), 16 / 32 / 64 that column-block width
         wherever eligible, 1000 * G + BN that width on G resident workgroups; returns the previous mode, -1 for a value it refuses""",
         """(skinny-batch chain launches; resident workgroups G, BN, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""),
+    "chain_skinny_split": (3,
+        """the K range of every layer of a skinny-batch bf16 chain launch (set_chain_skinny) over several workgroups per column block,
+        inside the one launch (the bits of the calls under set_skinny_bf16(BN) + set_skinny_split(P)): 0 off (default), 1 the rule (as
+        measured), 2 .. 16 that many parts wherever eligible; changes nothing while set_chain_skinny is 0; returns the previous mode,
+        -1 for a value it refuses""",
+        """(skinny-batch bf16 chain launches that ran K-split; parts P, resident workgroups G of the most recent one)"""),
     "chain_skinny_f32": (4,
         """f32 layer chains with 1 .. 31 rows (flat B, n >= BN, n % 4 == 0, k % 4 == 0) as one launch of the skinny-batch f32 kernel's chain
         form (the bits of the calls under set_skinny_f32(BN), split off): 0 off (default), 1 the rule (as measured: it gates what did not
