@@ -571,6 +571,39 @@ TPP_XSMM_EXPORT void xsmm_hip_skinny_bf16_stats(int64_t out[5]);
  * waves of part 0. */
 TPP_XSMM_EXPORT int xsmm_hip_set_skinny_split(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_skinny_split_stats(int64_t out[3]);
+/* Narrow-output bf16 layers (opt-in; also TPP_HIP_NARROW_BF16, read as a number; a refused value leaves 0). The mirrored side of the
+ * skinny-batch switch: a tall bf16 call with a handful of output columns - a 10-way classifier head, a 1- or 2-way regression head, a
+ * 16-wide bottleneck. Every bf16 fast path is at least 32 columns wide, so such a call runs on the generic kernel, one workgroup per
+ * 32x32 tile of which n columns are used, and on its element path whenever n is not a multiple of 8. With this switch on it runs as
+ * brgemm_bf16_narrow<IMG, BM, NB> (brgemm_bf16_narrow.hip; maps in brgemm_bf16_narrow.h): one workgroup computes all n columns of one block
+ * of BM rows (16, 32 or 64; ceil(m / BM) workgroups), A goes from global memory straight into the A operand of v_mfma_f32_16x16x32_bf16 in
+ * 16-byte pieces that each byte of A is part of once, B - a few KiB - is re-read from L2 as its image stores it, NB = 16 (n <= 16) or 32
+ * (two accumulator sets that share every A piece). The 32-k steps over (batch element, k) are dealt over W = min(8, batch count *
+ * ceil(k / 32)) waves and their partial sums added through LDS in wave order, then beta 1's C, the bias, relu and one rounding to bf16:
+ * run-to-run identical bits that depend on br and k alone - not on m, n or the position of the row block -, and NOT the generic kernel's
+ * bits. No scratch block, no counters, no waiting between workgroups: legal on a captured stream.
+ * A call is taken when all of this holds: bf16 with a VNNI-2, flat or VNNI-4 B, no VNNI C, no transposed operand, no forced variant, the
+ * descriptor's kernel is the generic one, m >= 32, 1 <= n <= 31, k >= 8 and k % 8 == 0, batch count >= 1, lda >= k, ldb >= n, ldc >= n, lda
+ * and stride_a multiples of 8 and A 16-byte aligned, a VNNI-2 B 4-byte aligned with an even stride_b, a VNNI-4 B 8-byte aligned with
+ * stride_b % 4 == 0, beta 0 or 1, with or without bias and relu. C, the bias, ldb, ldc and a flat B need their natural 2-byte alignment
+ * only: n = 10 with ldc = 10 is served. Extents: m below 2^24, k, every leading dimension, both strides (not negative) and batch count *
+ * ceil(k / 32) below 2^30 - the kernel's 64-bit byte offsets then cannot overflow; beyond that the call is refused. A call the launcher
+ * refuses runs the launch of mode 0. Everything else runs exactly as with the switch off - f32 calls, n >= 32, m < 32, every tile-queue
+ * group, quad, chain launch (a chain that ends in a narrow layer keeps running call by call) and folded call. No other switch takes a
+ * bf16 call with n < 32, and this one reads no other mode: there is no precedence question.
+ * mode 0 = off (default); 1 = the rule (gemm_plan.cpp narrow_bf16_bm, fitted to profiles/narrow_bf16_ab.txt): BM 16 - it beat mode 0 in
+ * every pair of every row where the generic kernel runs its element path (a VNNI-2 B with n % 8 != 0, every flat B: 4096 x 10 x 1024
+ * 42.3 -> 4.35 us, 1024 x 10 x 128 8.88 -> 4.08, 65536 x 1 x 1024 183.4 -> 23.7) and, by 11 .. 15 %, where it runs its 16-byte path (a
+ * VNNI-2 B with n % 8 == 0, every VNNI-4 B) with batch count * k >= 1024; THE GATE: a 16-byte-path call below that stays on the generic
+ * kernel (both launches sit at the launch floor there; 4 pairs of 5 at K = 128). BM 32 and 64 are never chosen. Not measured: other CU
+ * counts, several ranks, beta 1, strided operands. 16, 32, 64 = every eligible call on that BM (test / measurement switches). Read per invoke; returns the previous mode, -1 (and changes nothing) for any
+ * other value. The choice depends on the descriptor, the batch count and the pointers' alignment only: made in strict mode too.
+ * xsmm_hip_last_refined_kernel reads "brgemm_bf16_narrow<BMxNB>", "brgemm_bf16_narrow_flatb<BMxNB>" or "brgemm_bf16_narrow_vnni4<BMxNB>"
+ * (BM 16 / 32 / 64, NB 16 / 32).
+ * _stats: out[0] such launches since process start; of the most recent one: [1] workgroups, [2] waves per workgroup, [3] BM, [4] the B
+ * image (0 VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_narrow_bf16(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_narrow_bf16_stats(int64_t out[5]);
 /* Layer chains on the 256x256 bf16 tile (opt-in; also TPP_HIP_CHAIN_DMA256, read as a number). Every chain form above is a form of the
  * loader-wave tiles (32x64 .. 128x128); a chain whose calls run on the 256x256 LDS-DMA tile - 16384 rows x 1024 columns are exactly 256
  * such tiles - ran call by call. With this switch on, xsmm_hip_fused_brgemm_chain_invoke runs such a chain as ONE launch of that tile's

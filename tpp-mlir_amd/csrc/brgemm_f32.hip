@@ -32,6 +32,7 @@
 #include "brgemm_bf16_dma256_edge.h"
 #include "brgemm_bf16_skinny_split.h"
 #include "brgemm_f32_skinny.h"
+#include "brgemm_bf16_narrow.h"
 #include "brgemm_f32_skinny_split.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -701,6 +702,7 @@ hipError_t launch_bf16_skinny(int b_kind, int bn, const GemmArgs &a, hipStream_t
 hipError_t launch_bf16_skinny_split(int b_kind, int bn, int parts, const GemmArgs &a, hipStream_t s); // brgemm_bf16_skinny_split.hip: the same over parts workgroups per column block; hipErrorInvalidValue: not launched
 hipError_t launch_f32_skinny(int bn, const GemmArgs &a, hipStream_t s); // brgemm_f32_skinny.hip: 1 <= m <= 31 of a flat f32 B on column blocks of bn; hipErrorInvalidValue: not launched
 hipError_t launch_f32_skinny_split(int bn, int parts, const GemmArgs &a, hipStream_t s); // brgemm_f32_skinny_split.hip: the same over parts workgroups per column block; hipErrorInvalidValue: not launched
+hipError_t launch_bf16_narrow(int b_kind, int bm, const GemmArgs &a, hipStream_t s); // brgemm_bf16_narrow.hip: m >= 32, 1 <= n <= 31 on row blocks of bm; hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         // brgemm_f32_lw.hip (tile 4: 128x64, forced variant 10 only - it measures within 2 % of brgemm_f32_fast<128x64>)
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
@@ -807,6 +809,7 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
     return p.b_kind != 0 ? (p.tile == 2 ? launch_bf16_dma256_image(p.b_kind, a, s) : hipErrorInvalidValue) : launch_gemm_bf16_fast(p.tile, a, s);
   case GL_BF16_SKINNY: return p.split > 1 ? launch_bf16_skinny_split(p.b_kind, p.tile, p.split, a, s) : launch_bf16_skinny(p.b_kind, p.tile, a, s);
   case GL_F32_SKINNY: return p.split > 1 ? launch_f32_skinny_split(p.tile, p.split, a, s) : launch_f32_skinny(p.tile, a, s);
+  case GL_BF16_NARROW: return launch_bf16_narrow(p.b_kind, p.tile, a, s);
   case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split, small_split_ran);
   case GL_BF16_GROUPED64: return launch_bf16_grouped64(a, wi, n_items, s);
   case GL_BF16_LW:
@@ -855,6 +858,16 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     }
     (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
     env.skinny_bf16 = 0;
+    p = plan_gemm_call(d, br, al, env);
+  }
+  if (p.launcher == GL_BF16_NARROW) { // a narrow-output bf16 layer (mode_switches.h MS_NARROW_BF16; brgemm_bf16_narrow.h)
+    const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    if (e != hipErrorInvalidValue) {
+      if (e == hipSuccess) count_mode_launch(MS_NARROW_BF16, {nrw_blocks(a.m, p.tile), nrw_waves((long long)a.br * nrw_steps(a.k)), p.tile, p.b_kind});
+      return g_last_refined.store(p.text, std::memory_order_relaxed), e;
+    }
+    (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
+    env.narrow_bf16 = 0;
     p = plan_gemm_call(d, br, al, env);
   }
   if (p.launcher == GL_F32_SKINNY) { // a skinny-batch f32 layer (mode_switches.h MS_SKINNY_F32; brgemm_f32_skinny.h)

@@ -9,6 +9,7 @@
 #include "brgemm_bf16_skinny.h"
 #include "brgemm_bf16_skinny_split.h"
 #include "brgemm_f32_skinny.h"
+#include "brgemm_bf16_narrow.h"
 #include "brgemm_f32_skinny_split.h"
 #include "brgemm_bf16_skinny_chain.h"
 #include "brgemm_f32_skinny_chain.h"
@@ -460,6 +461,32 @@ static int skinny_f32_split_parts(const GemmDesc &d, int bn, int mode, int64_t b
   if (P < 2 || P > SKFS_PMAX) return 1;
   const int p_eff = skfs_parts(P, s_all);
   return p_eff >= 2 ? p_eff : 1;
+}
+
+// NARROW-OUTPUT bf16 LAYERS (xsmm_hip_set_narrow_bf16, opt-in; brgemm_bf16_narrow.hip, brgemm_bf16_narrow.h): the row-block height BM of a
+// bf16 call with m >= 32 and 1 <= n <= 31, or 0: the call stays on the generic kernel. Modes 16 / 32 / 64 (tests, measurements): that height.
+// Mode 1, THE RULE, from profiles/narrow_bf16_ab.txt (one box, 256 CUs, beta 0 + bias + relu, one process, five ALTERNATING pairs (mode 0, BM)
+// per row and BM, us per call; a BM is taken only where it beat the mode 0 of its own pair in EVERY pair). m x n x k, mode 0 -> BM 16 / 32 / 64:
+//   the generic kernel on its ELEMENT path (VNNI-2 with n % 8 != 0, every flat B) - BM 16 won every pair of all 19 rows:
+//     1024 x 10 x 128    8.88 -> 4.08 / 3.94 / 4.56          4096 x 10 x 1024   42.3 -> 4.35 / 5.27 / 7.98 (1.93 TB/s of A)
+//     65536 x 1 x 1024   183.4 -> 23.7 / 28.8 / 30.9 (5.66 TB/s)   65536 x 10 x 1024  253.0 -> 23.9 / 29.5 / 30.9
+//     4096 x 31 x 4096   171.4 -> 10.1 / 13.9 / 22.5 (3.33 TB/s)   4096 x 10 x 1000   42.1 -> 4.17 / 4.74 / 6.73
+//     4096 x 10 x 64 br 16  42.3 -> 4.39 / 5.28 / 7.98       32 x 10 x 128  8.4 -> 4.42, 64 x 31 x 64  8.2 -> 4.39, 4096 x 17 x 8  6.4 -> 4.60
+//     flat: 4096 x 10 x 1024  35.9 -> 4.79 / 5.46 / 8.18, 4096 x 31 x 4096  160.8 -> 12.6 / 15.8 / 24.5, 256 x 16 x 1024  35.6 -> 4.81
+//   the generic kernel on its 16-BYTE path (VNNI-2 with n % 8 == 0, every VNNI-4 B), which sits near the launch floor (4.6 .. 5.2 us):
+//     K = br k >= 1024: BM 16 won every pair, by 11 .. 15 % - 256 x 16 x 1024  4.93 -> 4.20, 4096 x 16 x 1024  5.04 -> 4.37, 4096 x 8 x 1024
+//     5.08 -> 4.39, 32 x 16 x 4096  10.5 -> 7.25, VNNI-4 4096 x 10 x 1024  5.20 -> 4.51, 256 x 16 x 1024  5.08 -> 4.51 (x 31 x 4096: 185.1 -> 11.1)
+//     K = 128 (VNNI-4, 1024 x 10 and 32 x 10): 4.60 -> 4.51 and 4.83 -> 4.50, 4 pairs of 5 each - LOST, both launches at the floor: GATED, and
+//     with them every 16-byte-path call below K = 1024 (VNNI-2 with n % 8 == 0 was not measured there).
+// BM 32 beat BM 16 on one row only (1024 x 10 x 128 VNNI-2, by 3 % with overlapping spreads) and lost to mode 0 on every 16-byte-path row
+// with K = 1024; BM 64 never beat BM 16: at m = 4096 it leaves three quarters of the CUs idle. So the rule is BM 16 or nothing.
+// Not measured: other CU counts (the rule does not read them), several ranks, beta 1, strided operands, m beyond 65536, K beyond 4096.
+constexpr int64_t NRW_FAST_PATH_K = 1024;
+static int narrow_bf16_bm(const GemmDesc &d, int kind, int mode, int64_t br) {
+  if (mode == 16 || mode == 32 || mode == 64) return mode;
+  if (mode != 1) return 0;
+  const bool generic_16_byte_path = kind == 4 || (kind == 0 && d.n % 8 == 0);
+  return generic_16_byte_path && br * d.k < NRW_FAST_PATH_K ? 0 : 16;
 }
 
 // K SPLIT ACROSS WORKGROUPS OF A SKINNY-BATCH LAUNCH (xsmm_hip_set_skinny_split, opt-in; brgemm_bf16_skinny_split.hip,
@@ -1592,6 +1619,27 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
       // the K range of the launch over several workgroups per column block, if asked for (xsmm_hip_set_skinny_split): read here only
       const int parts = env.skinny_split != 0 ? skinny_split_parts(d, bn, env.skinny_split, br, cus) : 1;
       return launch(GL_BF16_SKINNY, bn, skinny_names[parts > 1][kind / 2][skn_mb((int)d.m) == 32][bn == 16 ? 0 : bn == 32 ? 1 : 2], parts, kind);
+    }
+  }
+  // Narrow-output bf16 layers, if asked for (xsmm_hip_set_narrow_bf16, a switch of its own; brgemm_bf16_narrow.hip, brgemm_bf16_narrow.h): a
+  // bf16 call with m >= 32 and 1 <= n <= 31 that is planned - not forced - on the generic kernel, whichever of the three B images it has, on
+  // ceil(m / BM) workgroups that stream A straight into MFMA operand registers. No other refinement takes a bf16 call with n < 32 (every
+  // loader-wave tile is 64 columns wide, the edge tiles ask for n >= BN, the 32x32 K split for n % 32 == 0), so its place in this function is
+  // free; it reads no other mode and no other mode reads it. Decided here only - what is queued, grouped, chained or folded never sees it -,
+  // from the descriptor and the batch count: allowed in strict mode. The pointers' alignment is the launcher's to check (launch_bf16_narrow:
+  // A 16-byte aligned, a VNNI-2 B 4-byte, a VNNI-4 B 8-byte; C, the bias row and a flat B as 2-byte elements); refused there, the call runs
+  // the launch it has with the mode off (launch_gemm).
+  if (env.narrow_bf16 != 0 && d.dtype == DT_BF16 && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.variant == V_GENERIC &&
+      nrw_shape_ok(d.m, d.n, d.k, br) && nrw_extents_ok(d.lda, d.ldb, d.ldc, d.stride_a, d.stride_b) && d.lda >= d.k && d.ldb >= d.n && d.ldc >= d.n &&
+      !((d.lda | d.stride_a) & 7)) {
+    const int kind = !d.vnni_b ? 2 : d.vnni_factor == 4 ? 4 : 0;
+    const int bm = (d.stride_b & (nrw_vfac(kind) - 1)) ? 0 : narrow_bf16_bm(d, kind, env.narrow_bf16, br);
+    if (bm > 0) {
+#define NRW_NAMES(F) {{"brgemm_bf16_narrow" F "<16x16>", "brgemm_bf16_narrow" F "<16x32>"}, {"brgemm_bf16_narrow" F "<32x16>", "brgemm_bf16_narrow" F "<32x32>"}, \
+                      {"brgemm_bf16_narrow" F "<64x16>", "brgemm_bf16_narrow" F "<64x32>"}}
+      static const char *const narrow_names[3][3][2] = {NRW_NAMES(""), NRW_NAMES("_flatb"), NRW_NAMES("_vnni4")};
+#undef NRW_NAMES
+      return launch(GL_BF16_NARROW, bm, narrow_names[kind / 2][bm == 16 ? 0 : bm == 32 ? 1 : 2][nrw_nb((int)d.n) == 32], 1, kind);
     }
   }
   // Skinny-batch f32 layers, if asked for (xsmm_hip_set_skinny_f32, a switch of its own; brgemm_f32_skinny.hip, brgemm_f32_skinny.h): an f32

@@ -18,7 +18,7 @@ namespace tpp {
 enum ModeSwitch : int {
   MS_TAIL_SPLIT, MS_EDGE_TILES, MS_EDGE_K, MS_EDGE_K_BF16, MS_EDGE_K8_BF16, MS_DMA256_IMAGES, MS_DMA256_EDGE, MS_SKINNY_BF16, MS_SKINNY_SPLIT,
   MS_F32_HALVES, MS_CHAIN_EDGE, MS_CHAIN_ROUNDS, MS_CHAIN_RAGGED, MS_CHAIN_WIDTHS, MS_CHAIN_WIDTH_ROUNDS, MS_CHAIN_WIDTHS_RAGGED, MS_CHAIN_DMA256,
-  MS_CHAIN_SKINNY, MS_SKINNY_F32, MS_SKINNY_F32_SPLIT, MS_CHAIN_SKINNY_F32, MS_CHAIN_SKINNY_F32_SPLIT, MS_CHAIN_SKINNY_SPLIT, MS_COUNT
+  MS_CHAIN_SKINNY, MS_SKINNY_F32, MS_SKINNY_F32_SPLIT, MS_CHAIN_SKINNY_F32, MS_CHAIN_SKINNY_F32_SPLIT, MS_CHAIN_SKINNY_SPLIT, MS_NARROW_BF16, MS_COUNT
 };
 
 // the values a setter accepts (every other value: -1, nothing changed; in the environment: the default)
@@ -30,6 +30,7 @@ constexpr bool dma256_images_mode_ok(int v) { return v >= 0 && v <= 2; }
 constexpr bool dma256_edge_mode_ok(int v) { return v >= 0 && v <= 2; }
 constexpr bool skinny_bf16_mode_ok(int v) { return v == 0 || v == 1 || v == 16 || v == 32 || v == 64; }
 constexpr bool skinny_f32_mode_ok(int v) { return v == 0 || v == 1 || v == 16 || v == 32 || v == 64; }
+constexpr bool narrow_bf16_mode_ok(int v) { return v == 0 || v == 1 || v == 16 || v == 32 || v == 64; }
 constexpr bool skinny_split_mode_ok(int v) { return v >= 0 && v <= 16; }
 constexpr bool skinny_f32_split_mode_ok(int v) { return v >= 0 && v <= 16; }
 constexpr bool chain_skinny_f32_split_mode_ok(int v) { return v >= 0 && v <= 16; }
@@ -97,6 +98,8 @@ inline constexpr ModeSwitchRow MODE_SWITCHES[MS_COUNT] = {
     {MS_CHAIN_SKINNY_F32_SPLIT, "TPP_HIP_CHAIN_SKINNY_F32_SPLIT", 0, chain_skinny_f32_split_mode_ok, 3},
     // plan_chain_skinny - read only for a chain that rule has in hand; rt_chain.h launches brgemm_bf16_skinny_chain_split.hip and counts: parts P, resident workgroups G
     {MS_CHAIN_SKINNY_SPLIT, "TPP_HIP_CHAIN_SKINNY_SPLIT", 0, chain_skinny_split_mode_ok, 3},
+    // plan_gemm_call, narrow_bf16_bm; brgemm_bf16_narrow.hip: workgroups, waves per workgroup, BM, B image
+    {MS_NARROW_BF16, "TPP_HIP_NARROW_BF16", 0, narrow_bf16_mode_ok, 5},
 };
 constexpr bool mode_switch_table_ok() {
   for (int i = 0; i < MS_COUNT; ++i)
@@ -153,6 +156,7 @@ inline GemmPlanEnv gemm_plan_env_of(int cus, bool strict, int forced_split) {
   e.skinny_split = mode_of(MS_SKINNY_SPLIT);
   e.skinny_f32 = mode_of(MS_SKINNY_F32);
   e.skinny_f32_split = mode_of(MS_SKINNY_F32_SPLIT);
+  e.narrow_bf16 = mode_of(MS_NARROW_BF16);
   return e;
 }
 inline ChainPlanEnv chain_plan_env_of(bool strict) {

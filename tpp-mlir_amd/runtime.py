@@ -181,6 +181,11 @@ _MODE_SWITCHES = {
         rule, 2 .. 16 that many parts wherever eligible; changes nothing while set_skinny_f32 is 0; returns the previous mode, -1 for a
         value it refuses""",
         """(skinny-batch f32 launches that ran split; parts, workgroups - column blocks * parts - of the most recent one)"""),
+    "narrow_bf16": (5,
+        """bf16 whole-layer calls with fewer than 32 columns (m >= 32, 1 <= n <= 31, k % 8 == 0: classifier and regression heads) on the
+        narrow-output kernel, one workgroup per block of BM rows: 0 off (default), 1 the rule, 16 / 32 / 64 that BM wherever eligible;
+        returns the previous mode, -1 for a value it refuses""",
+        """(narrow-output launches; workgroups, waves per workgroup, BM, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""),
     "chain_dma256": (4,
         """bf16 layer chains whose calls run on the 256x256 tile (256 dividing m and n, k % 32 == 0) as one launch of that tile's chain
         kernel (the same bits): 0 off (default), 1 the rule (every call runs on that tile today; gated as measured), 2 every eligible
