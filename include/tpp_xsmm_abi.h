@@ -604,6 +604,40 @@ TPP_XSMM_EXPORT void xsmm_hip_skinny_split_stats(int64_t out[3]);
  * image (0 VNNI-2, 2 flat, 4 VNNI-4). The counters of the other switches do not move on these launches. */
 TPP_XSMM_EXPORT int xsmm_hip_set_narrow_bf16(int mode);
 TPP_XSMM_EXPORT void xsmm_hip_narrow_bf16_stats(int64_t out[5]);
+/* Narrow-output f32 layers (opt-in; also TPP_HIP_NARROW_F32, read as a number; a refused value leaves 0). The f32 half of the switch
+ * above: a tall f32 call with a handful of output columns - a 10-way classifier head behind an f32 MLP, a 1- or 2-column regression head,
+ * a 16-wide bottleneck beyond 8192 rows, anything 17 .. 31 wide. Every f32 fast path asks for n >= 32, the 32x16 loader-wave tile for
+ * m % 32 == 0, n % 16 == 0, ldc % 4 == 0 and at most one tile per compute unit, and the skinny-batch kernel stops at m = 31: such a call
+ * runs on the generic kernel, one workgroup per 32x32 tile of which n columns are used. With this switch on it runs as
+ * brgemm_f32_narrow<BM, NB> (brgemm_f32_narrow.hip; maps in brgemm_f32_narrow.h): one workgroup computes all n columns of one block of BM
+ * rows (16, 32 or 64; ceil(m / BM) workgroups), A goes from global memory straight into the A operand of v_mfma_f32_16x16x4_f32 in 16-byte
+ * pieces that each byte of A is part of once, the flat B - a few KiB - is re-read from L2, NB = 16 (n <= 16) or 32 (two accumulator sets
+ * that share every A piece). The 16-k steps over (batch element, k) are dealt over W = min(8, batch count * ceil(k / 16)) waves and their
+ * partial sums added through LDS in wave order, then beta 1's C, the bias and relu: run-to-run identical bits that depend on br and k
+ * alone - not on m, n or the position of the row block -, and NOT the generic kernel's bits. No scratch block, no counters, no waiting
+ * between workgroups: legal on a captured stream.
+ * A call is taken when all of this holds: f32, no VNNI operand, no transposed operand, no forced variant, the descriptor's kernel is the
+ * generic one (a call dispatch put on the 32x16 loader-wave tile stays there), m >= 32, 1 <= n <= 31, k >= 4 and k % 4 == 0, batch count
+ * >= 1, lda >= k, ldb >= n, ldc >= n, lda and stride_a multiples of 4 and A 16-byte aligned, beta 0 or 1, with or without bias and relu.
+ * B, C, the bias, ldb, ldc and stride_b need their natural 4-byte alignment only: n = 10 with ldc = 10 is served. Extents: m below 2^24,
+ * k, every leading dimension, both strides (not negative) and batch count * ceil(k / 16) below 2^30 - the kernel's 64-bit byte offsets
+ * then cannot overflow; beyond that the call is refused. A call the launcher refuses runs the launch of mode 0. Everything else runs
+ * exactly as with the switch off - bf16 calls, n >= 32, m < 32, every tile-queue group, chain launch (a chain that ends in a narrow layer
+ * keeps running call by call) and folded call. This switch reads no other mode and no other rule reads it.
+ * mode 0 = off (default); 1 = the rule (gemm_plan.cpp narrow_f32_bm, fitted to profiles/narrow_f32_ab.txt): BM 32 for
+ * m >= 16384, BM 16 below - each beat mode 0 in every pair of every row of its side where the generic kernel runs its element path (n % 4
+ * != 0: 4096 x 10 x 1024 21.6 -> 6.00 us, 65536 x 10 x 1024 119.4 -> 46.0, 40 x 10 x 36 5.57 -> 4.41) and where it runs its 16-byte path
+ * (n % 4 == 0 with ldb and stride_b multiples of 4) with batch count * k >= 1024, or >= 256 for m >= 16384 (4096 x 8 x 1024 8.47 -> 6.00,
+ * 16384 x 16 x 1024 14.9 -> 14.65); THE GATE: a 16-byte-path call below that stays on the generic kernel (both launches sit at the launch
+ * floor there; 3 and 4 pairs of 5 at K = 128 and 36). BM 64 is never chosen. Not measured: other CU counts, several ranks, beta 1,
+ * strided operands.
+ * 16, 32, 64 = every eligible call on that BM (test / measurement switches). Read per invoke; returns the previous mode, -1 (and changes
+ * nothing) for any other value. The choice depends on the descriptor and the batch count only: made in strict mode too.
+ * xsmm_hip_last_refined_kernel reads "brgemm_f32_narrow<BMxNB>" (BM 16 / 32 / 64, NB 16 / 32).
+ * _stats: out[0] such launches since process start; of the most recent one: [1] workgroups, [2] waves per workgroup, [3] BM. The
+ * counters of the other switches do not move on these launches. */
+TPP_XSMM_EXPORT int xsmm_hip_set_narrow_f32(int mode);
+TPP_XSMM_EXPORT void xsmm_hip_narrow_f32_stats(int64_t out[4]);
 /* Layer chains on the 256x256 bf16 tile (opt-in; also TPP_HIP_CHAIN_DMA256, read as a number). Every chain form above is a form of the
  * loader-wave tiles (32x64 .. 128x128); a chain whose calls run on the 256x256 LDS-DMA tile - 16384 rows x 1024 columns are exactly 256
  * such tiles - ran call by call. With this switch on, xsmm_hip_fused_brgemm_chain_invoke runs such a chain as ONE launch of that tile's

@@ -33,6 +33,7 @@
 #include "brgemm_bf16_skinny_split.h"
 #include "brgemm_f32_skinny.h"
 #include "brgemm_bf16_narrow.h"
+#include "brgemm_f32_narrow.h"
 #include "brgemm_f32_skinny_split.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -703,6 +704,7 @@ hipError_t launch_bf16_skinny_split(int b_kind, int bn, int parts, const GemmArg
 hipError_t launch_f32_skinny(int bn, const GemmArgs &a, hipStream_t s); // brgemm_f32_skinny.hip: 1 <= m <= 31 of a flat f32 B on column blocks of bn; hipErrorInvalidValue: not launched
 hipError_t launch_f32_skinny_split(int bn, int parts, const GemmArgs &a, hipStream_t s); // brgemm_f32_skinny_split.hip: the same over parts workgroups per column block; hipErrorInvalidValue: not launched
 hipError_t launch_bf16_narrow(int b_kind, int bm, const GemmArgs &a, hipStream_t s); // brgemm_bf16_narrow.hip: m >= 32, 1 <= n <= 31 on row blocks of bm; hipErrorInvalidValue: not launched
+hipError_t launch_f32_narrow(int bm, const GemmArgs &a, hipStream_t s); // brgemm_f32_narrow.hip: f32, m >= 32, 1 <= n <= 31 on row blocks of bm; hipErrorInvalidValue: not launched
 hipError_t launch_f32_lw(int tile, const GemmArgs &a, hipStream_t s);         // brgemm_f32_lw.hip (tile 4: 128x64, forced variant 10 only - it measures within 2 % of brgemm_f32_fast<128x64>)
 hipError_t launch_f32_lw_grouped(int tile, const GemmArgs &a, const WorkItem *items, int n_items, int split, hipStream_t s);
 hipError_t launch_f32_lw_split(int tile, const GemmArgs &a, int split, hipStream_t s); // hipErrorOutOfMemory / InvalidValue: not launched
@@ -810,6 +812,7 @@ static hipError_t run_gemm_launch(const GemmLaunch &p, const GemmArgs &a, int br
   case GL_BF16_SKINNY: return p.split > 1 ? launch_bf16_skinny_split(p.b_kind, p.tile, p.split, a, s) : launch_bf16_skinny(p.b_kind, p.tile, a, s);
   case GL_F32_SKINNY: return p.split > 1 ? launch_f32_skinny_split(p.tile, p.split, a, s) : launch_f32_skinny(p.tile, a, s);
   case GL_BF16_NARROW: return launch_bf16_narrow(p.b_kind, p.tile, a, s);
+  case GL_F32_NARROW: return launch_f32_narrow(p.tile, a, s);
   case GL_BF16_SMALL32: return launch_bf16_small32(a, wi, n_items, s, p.split, small_split_ran);
   case GL_BF16_GROUPED64: return launch_bf16_grouped64(a, wi, n_items, s);
   case GL_BF16_LW:
@@ -868,6 +871,16 @@ hipError_t launch_gemm(const GemmDesc &d, const void *A, const void *B, void *C,
     }
     (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
     env.narrow_bf16 = 0;
+    p = plan_gemm_call(d, br, al, env);
+  }
+  if (p.launcher == GL_F32_NARROW) { // a narrow-output f32 layer (mode_switches.h MS_NARROW_F32; brgemm_f32_narrow.h)
+    const hipError_t e = run_gemm_launch(p, a, a.br, nullptr, 1, false, stream);
+    if (e != hipErrorInvalidValue) {
+      if (e == hipSuccess) count_mode_launch(MS_NARROW_F32, {nrf_blocks(a.m, p.tile), nrf_waves((long long)a.br * nrf_steps(a.k)), p.tile});
+      return g_last_refined.store(p.text, std::memory_order_relaxed), e;
+    }
+    (void)hipGetLastError(); // refused by the launcher: the launch the call has with the mode off
+    env.narrow_f32 = 0;
     p = plan_gemm_call(d, br, al, env);
   }
   if (p.launcher == GL_F32_SKINNY) { // a skinny-batch f32 layer (mode_switches.h MS_SKINNY_F32; brgemm_f32_skinny.h)

@@ -10,6 +10,7 @@
 #include "brgemm_bf16_skinny_split.h"
 #include "brgemm_f32_skinny.h"
 #include "brgemm_bf16_narrow.h"
+#include "brgemm_f32_narrow.h"
 #include "brgemm_f32_skinny_split.h"
 #include "brgemm_bf16_skinny_chain.h"
 #include "brgemm_f32_skinny_chain.h"
@@ -487,6 +488,40 @@ static int narrow_bf16_bm(const GemmDesc &d, int kind, int mode, int64_t br) {
   if (mode != 1) return 0;
   const bool generic_16_byte_path = kind == 4 || (kind == 0 && d.n % 8 == 0);
   return generic_16_byte_path && br * d.k < NRW_FAST_PATH_K ? 0 : 16;
+}
+
+// NARROW-OUTPUT f32 LAYERS (xsmm_hip_set_narrow_f32, opt-in; brgemm_f32_narrow.hip, brgemm_f32_narrow.h): the row-block height BM of an f32
+// call with m >= 32 and 1 <= n <= 31, or 0: the call stays on the generic kernel. Modes 16 / 32 / 64 (tests, measurements): that height.
+// Mode 1, THE RULE, from profiles/narrow_f32_ab.txt (one box, 256 CUs, beta 0 + bias + relu, one process, five ALTERNATING pairs (mode 0, BM)
+// per row and BM, us per call; a (shape class, BM) is taken only where it beat the mode 0 of its own pair in EVERY pair). m x n x k,
+// mode 0 -> BM 16 / 32 / 64:
+//   the generic kernel on its ELEMENT path (n % 4 != 0) - 22 rows, m 32 .. 65536, K = br k 16 .. 4096: BM 16 and BM 32 won every pair of all:
+//     4096 x 10 x 1024   21.6 -> 6.00 / 8.16 / 13.7         65536 x 10 x 1024  119.4 -> 48.5 / 46.0 / 53.2 (5.83 TB/s of A on BM 32)
+//     65536 x 1 x 1024   90.2 -> 47.1 / 44.1 / 52.0 (6.09 TB/s)   4096 x 31 x 4096   72.5 -> 20.3 / 30.2 / 53.1
+//     4096 x 10 x 1000   21.1 -> 5.75 / 7.63 / 12.5         4096 x 10 x 64 br 16  21.6 -> 6.02 / 8.16 / 13.8      32 x 31 x 4096  69.1 -> 17.9 / 27.9 / 46.6
+//     1024 x 10 x 128    6.04 -> 4.37 / 4.37 / 5.82         40 x 10 x 36  5.57 -> 4.41, 4096 x 10 x 16  5.45 -> 4.48: the launch floor, still every pair
+//     32768 x 10 x 1024  58.3 -> 26.0 / 25.5 / 28.3         16384 x 31 x 512  18.8 -> 13.4 / 13.1 / 16.2       16384 x 10 x 256  11.2 -> 6.05 / 6.01 / 7.37
+//   the generic kernel on its 16-BYTE path (n % 4 == 0, ldb and stride_b multiples of 4) - 10 rows:
+//     m < 16384, K >= 1024: BM 16 won every pair - 4096 x 8 x 1024  8.47 -> 6.00, 4096 x 12 x 1024  8.54 -> 6.06, 8224 x 16 x 1024  12.7 -> 10.2,
+//       4096 x 28 x 4096  23.2 -> 19.8 (BM 32 LOST there: 29.8)
+//     m >= 16384, K >= 256: BM 32 won every pair - 16384 x 16 x 1024  14.9 -> 14.65 (1.7 %; BM 16 LOST: 1 pair of 5), 16384 x 8 x 1024  14.8 ->
+//       14.55, 65536 x 4 x 1024  53.0 -> 44.5, 65536 x 16 x 256  23.5 -> 16.5
+//     K = 128 and 36 (1024 x 20 x 128  4.59 -> 4.58, 3 pairs of 5; 40 x 12 x 36  4.69 -> 4.57, 4 of 5): LOST, both launches at the floor: GATED,
+//       and with them every 16-byte-path call below the smallest K that won (1024 for m < 16384, 256 from there on).
+// BM 32 beat BM 16 on seven of the nine rows with m >= 16384 (not on 65536 x 16 x 256, by 3 %, and 16384 x 8 x 1024, by 1 %) and is the only
+// BM that won every pair on all nine; below, it was never faster than BM 16 by more than 1 % and up to 56 % slower. BM 64 lost to mode 0 on
+// 10 rows and never beat both others: at m = 4096 it leaves three quarters of the CUs idle. So: BM 32 from m = 16384
+// on - the smallest m at which it was measured, 8224 .. 16383 follow BM 16 unmeasured -, BM 16 below, and the gate above.
+// Not measured: other CU counts (the rule does not read them), several ranks, beta 1, strided operands, unaligned B or C (the generic kernel
+// is then on its element path and the gate only keeps calls that would win), m beyond 65536, K beyond 4096.
+constexpr int64_t NRF_TALL_M = 16384, NRF_FAST_PATH_K = 1024, NRF_FAST_PATH_K_TALL = 256;
+static int narrow_f32_bm(const GemmDesc &d, int mode, int64_t br) {
+  if (mode == 16 || mode == 32 || mode == 64) return mode;
+  if (mode != 1) return 0;
+  const bool tall = d.m >= NRF_TALL_M;
+  const bool generic_16_byte_path = d.n % 4 == 0 && !((d.ldb | d.stride_b) & 3);
+  if (generic_16_byte_path && br * d.k < (tall ? NRF_FAST_PATH_K_TALL : NRF_FAST_PATH_K)) return 0; // the gate
+  return tall ? 32 : 16;
 }
 
 // K SPLIT ACROSS WORKGROUPS OF A SKINNY-BATCH LAUNCH (xsmm_hip_set_skinny_split, opt-in; brgemm_bf16_skinny_split.hip,
@@ -1640,6 +1675,24 @@ GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br_in, const GemmAlign &al,
       static const char *const narrow_names[3][3][2] = {NRW_NAMES(""), NRW_NAMES("_flatb"), NRW_NAMES("_vnni4")};
 #undef NRW_NAMES
       return launch(GL_BF16_NARROW, bm, narrow_names[kind / 2][bm == 16 ? 0 : bm == 32 ? 1 : 2][nrw_nb((int)d.n) == 32], 1, kind);
+    }
+  }
+  // Narrow-output f32 layers, if asked for (xsmm_hip_set_narrow_f32, a switch of its own; brgemm_f32_narrow.hip, brgemm_f32_narrow.h): the
+  // f32 half of the block above - an f32 call with m >= 32 and 1 <= n <= 31 and a flat B that is planned - not forced - on the generic kernel,
+  // on ceil(m / BM) workgroups that stream A straight into the operand registers of v_mfma_f32_16x16x4_f32. Every other f32 refinement asks
+  // for n >= 32 (the loader-wave, edge and ragged-k tiles) or m <= 31 (the skinny kernel), and a call dispatch put on V_F32_LW16_32x16 has
+  // another d.variant and stays there: its place in this function is free; it reads no other mode and no other mode reads it. Decided here
+  // only - what is queued, grouped, chained or folded never sees it -, from the descriptor and the batch count: allowed in strict mode. A's
+  // 16-byte alignment is the launcher's to check (launch_f32_narrow; B, C and the bias row are 4-byte elements); refused there, the call runs
+  // the launch it has with the mode off (launch_gemm).
+  if (env.narrow_f32 != 0 && d.dtype == DT_F32 && !d.vnni_b && !d.vnni_c && !d.generic_forced && !d.variant_forced && d.variant == V_GENERIC &&
+      nrf_shape_ok(d.m, d.n, d.k, br) && nrf_extents_ok(d.lda, d.ldb, d.ldc, d.stride_a, d.stride_b) && d.lda >= d.k && d.ldb >= d.n && d.ldc >= d.n &&
+      !((d.lda | d.stride_a) & 3)) {
+    const int bm = narrow_f32_bm(d, env.narrow_f32, br);
+    if (bm > 0) {
+      static const char *const names[3][2] = {{"brgemm_f32_narrow<16x16>", "brgemm_f32_narrow<16x32>"}, {"brgemm_f32_narrow<32x16>", "brgemm_f32_narrow<32x32>"},
+                                              {"brgemm_f32_narrow<64x16>", "brgemm_f32_narrow<64x32>"}};
+      return launch(GL_F32_NARROW, bm, names[bm == 16 ? 0 : bm == 32 ? 1 : 2][nrf_nb((int)d.n) == 32]);
     }
   }
   // Skinny-batch f32 layers, if asked for (xsmm_hip_set_skinny_f32, a switch of its own; brgemm_f32_skinny.hip, brgemm_f32_skinny.h): an f32

@@ -52,9 +52,9 @@ enum GemmVariant : int {
 // rule, 16 / 32 / 64 = that column-block width wherever eligible) and xsmm_hip_set_skinny_split (0 = off, 1 = the rule, 2 .. 16 = that many parts
 // wherever eligible) and xsmm_hip_set_skinny_f32 (0 = off, 1 = the rule, 16 / 32 / 64 = that column-block width wherever eligible) and
 // xsmm_hip_set_skinny_f32_split (0 = off, 1 = the rule, 2 .. 16 = that many parts wherever eligible) and xsmm_hip_set_narrow_bf16 (0 = off,
-// 1 = the rule, 16 / 32 / 64 = that row-block height wherever eligible);
+// 1 = the rule, 16 / 32 / 64 = that row-block height wherever eligible) and xsmm_hip_set_narrow_f32 (the same values);
 // mode_switches.h gemm_plan_env_of fills it per call, and the accepted values of each switch stand in its table
-struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; int dma256_edge = 0; int skinny_bf16 = 0; int skinny_split = 0; int skinny_f32 = 0; int skinny_f32_split = 0; int narrow_bf16 = 0; };
+struct GemmPlanEnv { int cus; bool strict; int forced_split; int tail_split = 0; int edge_tiles = 0; int edge_k = 0; int edge_k_bf16 = 0; int halves = 0; int edge_k8_bf16 = 0; int dma256_images = 0; int dma256_edge = 0; int skinny_bf16 = 0; int skinny_split = 0; int skinny_f32 = 0; int skinny_f32_split = 0; int narrow_bf16 = 0; int narrow_f32 = 0; };
 
 // pointer facts of one invoke: A and B 16-byte aligned, C 16- / 8-byte aligned, the bias row D 8- / 16-byte aligned
 struct GemmAlign { bool ab16, c16, c8, d8, d16; };
@@ -78,6 +78,7 @@ enum GemmLauncher : int {
   GL_BF16_SKINNY,     // launch_bf16_skinny(b_kind, tile): tile = the column-block width BN 16 / 32 / 64 (xsmm_hip_set_skinny_bf16; brgemm_bf16_skinny.hip); split > 1 (xsmm_hip_set_skinny_split): launch_bf16_skinny_split(b_kind, tile, split) first
   GL_F32_SKINNY,      // launch_f32_skinny(tile): tile = the column-block width BN 16 / 32 / 64 (xsmm_hip_set_skinny_f32; brgemm_f32_skinny.hip); split > 1 (xsmm_hip_set_skinny_f32_split): launch_f32_skinny_split(tile, split) first
   GL_BF16_NARROW,     // launch_bf16_narrow(b_kind, tile): tile = the row-block height BM 16 / 32 / 64 (xsmm_hip_set_narrow_bf16; brgemm_bf16_narrow.hip)
+  GL_F32_NARROW,      // launch_f32_narrow(tile): tile = the row-block height BM 16 / 32 / 64 (xsmm_hip_set_narrow_f32; brgemm_f32_narrow.hip)
 };
 // the instances of the generic kernel brgemm_grouped<T, VNNI, VEC, VF>: <float, false, false / true>, <unsigned short, true, false / true>,
 // <unsigned short, true, true, 4>, <unsigned short, false, false>; and the f32 instances whose FORM argument says that an operand is
@@ -144,6 +145,13 @@ bool plan_gemm(GemmDesc &d, int forced_variant, const GemmPlanEnv &env);
 // launcher's to check: refused there, the call runs the launch it has with the mode off. No other switch takes a bf16 call with n < 32 and
 // this one reads no other mode; it decides from the descriptor and the batch count, so strict mode takes it. With narrow_bf16 at 0 the
 // block is never entered (tests/test_narrow_bf16_cpu.py).
+// Narrow-output f32 layers {narrow_f32}, directly behind, are that block's f32 half: an f32 call with m >= 32 and 1 <= n <= 31 planned -
+// not forced - on the generic kernel (d.variant == V_GENERIC: a call that dispatch put on V_F32_LW16_32x16 stays there), flat B, no VNNI C,
+// no transposed operand, k >= 4, k % 4 == 0, br >= 1, lda >= k, ldb >= n, ldc >= n, lda and stride_a multiples of 4, everything inside the
+// kernel's offset arithmetic (nrf_shape_ok, nrf_extents_ok) -> launch(GL_F32_NARROW, BM, "brgemm_f32_narrow<BMxNB>"), BM by narrow_f32_bm:
+// the forced height, or mode 1's measured rule. A's 16-byte alignment is the launcher's to check: refused there, the call runs the launch
+// it has with the mode off. It reads no other mode and no other rule reads it; it decides from the descriptor and the batch count, so
+// strict mode takes it. With narrow_f32 at 0 the block is never entered.
 GemmLaunch plan_gemm_call(const GemmDesc &d, int64_t br, const GemmAlign &al, const GemmPlanEnv &env);
 // n_items invokes of one descriptor in one launch (launch_gemm_grouped; vec_ok / out_ok / pair_ok / br_hint as there)
 GemmLaunch plan_gemm_group(const GemmDesc &d, int n_items, bool vec_ok, bool out_ok, bool pair_ok, int64_t br_hint, const GemmPlanEnv &env);

@@ -18,7 +18,7 @@ namespace tpp {
 enum ModeSwitch : int {
   MS_TAIL_SPLIT, MS_EDGE_TILES, MS_EDGE_K, MS_EDGE_K_BF16, MS_EDGE_K8_BF16, MS_DMA256_IMAGES, MS_DMA256_EDGE, MS_SKINNY_BF16, MS_SKINNY_SPLIT,
   MS_F32_HALVES, MS_CHAIN_EDGE, MS_CHAIN_ROUNDS, MS_CHAIN_RAGGED, MS_CHAIN_WIDTHS, MS_CHAIN_WIDTH_ROUNDS, MS_CHAIN_WIDTHS_RAGGED, MS_CHAIN_DMA256,
-  MS_CHAIN_SKINNY, MS_SKINNY_F32, MS_SKINNY_F32_SPLIT, MS_CHAIN_SKINNY_F32, MS_CHAIN_SKINNY_F32_SPLIT, MS_CHAIN_SKINNY_SPLIT, MS_NARROW_BF16, MS_COUNT
+  MS_CHAIN_SKINNY, MS_SKINNY_F32, MS_SKINNY_F32_SPLIT, MS_CHAIN_SKINNY_F32, MS_CHAIN_SKINNY_F32_SPLIT, MS_CHAIN_SKINNY_SPLIT, MS_NARROW_BF16, MS_NARROW_F32, MS_COUNT
 };
 
 // the values a setter accepts (every other value: -1, nothing changed; in the environment: the default)
@@ -31,6 +31,7 @@ constexpr bool dma256_edge_mode_ok(int v) { return v >= 0 && v <= 2; }
 constexpr bool skinny_bf16_mode_ok(int v) { return v == 0 || v == 1 || v == 16 || v == 32 || v == 64; }
 constexpr bool skinny_f32_mode_ok(int v) { return v == 0 || v == 1 || v == 16 || v == 32 || v == 64; }
 constexpr bool narrow_bf16_mode_ok(int v) { return v == 0 || v == 1 || v == 16 || v == 32 || v == 64; }
+constexpr bool narrow_f32_mode_ok(int v) { return v == 0 || v == 1 || v == 16 || v == 32 || v == 64; }
 constexpr bool skinny_split_mode_ok(int v) { return v >= 0 && v <= 16; }
 constexpr bool skinny_f32_split_mode_ok(int v) { return v >= 0 && v <= 16; }
 constexpr bool chain_skinny_f32_split_mode_ok(int v) { return v >= 0 && v <= 16; }
@@ -100,6 +101,8 @@ inline constexpr ModeSwitchRow MODE_SWITCHES[MS_COUNT] = {
     {MS_CHAIN_SKINNY_SPLIT, "TPP_HIP_CHAIN_SKINNY_SPLIT", 0, chain_skinny_split_mode_ok, 3},
     // plan_gemm_call, narrow_bf16_bm; brgemm_bf16_narrow.hip: workgroups, waves per workgroup, BM, B image
     {MS_NARROW_BF16, "TPP_HIP_NARROW_BF16", 0, narrow_bf16_mode_ok, 5},
+    // plan_gemm_call, narrow_f32_bm; brgemm_f32_narrow.hip: workgroups, waves per workgroup, BM
+    {MS_NARROW_F32, "TPP_HIP_NARROW_F32", 0, narrow_f32_mode_ok, 4},
 };
 constexpr bool mode_switch_table_ok() {
   for (int i = 0; i < MS_COUNT; ++i)
@@ -157,6 +160,7 @@ inline GemmPlanEnv gemm_plan_env_of(int cus, bool strict, int forced_split) {
   e.skinny_f32 = mode_of(MS_SKINNY_F32);
   e.skinny_f32_split = mode_of(MS_SKINNY_F32_SPLIT);
   e.narrow_bf16 = mode_of(MS_NARROW_BF16);
+  e.narrow_f32 = mode_of(MS_NARROW_F32);
   return e;
 }
 inline ChainPlanEnv chain_plan_env_of(bool strict) {

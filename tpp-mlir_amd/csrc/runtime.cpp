@@ -586,6 +586,7 @@ MODE_SWITCH_ABI(chain_skinny_f32, MS_CHAIN_SKINNY_F32)
 MODE_SWITCH_ABI(chain_skinny_f32_split, MS_CHAIN_SKINNY_F32_SPLIT)
 MODE_SWITCH_ABI(chain_skinny_split, MS_CHAIN_SKINNY_SPLIT)
 MODE_SWITCH_ABI(narrow_bf16, MS_NARROW_BF16)
+MODE_SWITCH_ABI(narrow_f32, MS_NARROW_F32)
 #undef MODE_SWITCH_ABI
 // the VNNI blocking factor of bf16 B operands dispatched from now on (2 or 4); returns the previous one, -1 for an invalid factor
 extern "C" int xsmm_hip_set_vnni_factor(int v) {

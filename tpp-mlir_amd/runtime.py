@@ -186,6 +186,11 @@ _MODE_SWITCHES = {
         narrow-output kernel, one workgroup per block of BM rows: 0 off (default), 1 the rule, 16 / 32 / 64 that BM wherever eligible;
         returns the previous mode, -1 for a value it refuses""",
         """(narrow-output launches; workgroups, waves per workgroup, BM, B image - 0 VNNI-2, 2 flat, 4 VNNI-4 - of the most recent one)"""),
+    "narrow_f32": (4,
+        """f32 whole-layer calls with fewer than 32 columns (m >= 32, 1 <= n <= 31, k % 4 == 0, A 16-byte aligned: classifier and regression
+        heads behind an f32 MLP) on the narrow-output f32 kernel, one workgroup per block of BM rows: 0 off (default), 1 the rule, 16 / 32 /
+        64 that BM wherever eligible; returns the previous mode, -1 for a value it refuses""",
+        """(narrow-output f32 launches; workgroups, waves per workgroup, BM of the most recent one)"""),
     "chain_dma256": (4,
         """bf16 layer chains whose calls run on the 256x256 tile (256 dividing m and n, k % 32 == 0) as one launch of that tile's chain
         kernel (the same bits): 0 off (default), 1 the rule (every call runs on that tile today; gated as measured), 2 every eligible
